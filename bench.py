@@ -14,10 +14,16 @@ dominant kernel (conv3x3 256->256 implicit GEMM, fp32 MFMA) and
 `roofline_roialign` the RoIAlign kernel, both timed live with events on the
 launch stream; `cpu_baseline` times the oracle (CPU restatement of the
 reference) on a bounded sample of the same RoIs on this box's host cores.
+
+`--steps K` is the number of timed steps of the headline leg in all (three
+windows that add up to K; `ms_per_step` is the median window's).  Inputs and
+weights come from fixed seeds, so `--dump-outputs DIR` (what the last timed
+step computed, as .npy) compares two builds output for output.
 """
 import argparse
 import json
 import os
+import statistics
 import sys
 import time
 
@@ -30,6 +36,7 @@ IMG_H, IMG_W = 800, 1333
 ROIS_PER_IMG = 512
 PEAK_FP32_MFMA_TFLOPS = 157.3     # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32
 PEAK_HBM_GBS = 8000.0             # MI355X_MICROARCH.md: HBM3E spec
+DUMP_LIMIT_BYTES = 64 << 20       # --dump-outputs: at most this much in all
 
 
 def build_head(dev):
@@ -228,6 +235,26 @@ def cpu_baseline(sd, feats, rois, labels, sample, reps=2):
     return dt, n_threads, out
 
 
+def window_sizes(steps, n=3):
+    """The --steps timed steps as (up to) ``n`` windows whose sizes add up to exactly ``steps``."""
+    n = min(n, steps)
+    return [steps // n + (i < steps % n) for i in range(n)]
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as ``<dirname>/<name>.npy``, float64 where it is float64 and float32 otherwise."""
+    import numpy as np
+    arrays = {k: v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: v.astype(np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f'--dump-outputs: {total} bytes of outputs, more than the {DUMP_LIMIT_BYTES} allowed')
+    os.makedirs(dirname, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, k + '.npy'), v)
+    print(f'[bench] {len(arrays)} outputs of the last timed step ({total} bytes) written to {dirname}', file=sys.stderr)
+
+
 def _max_over_ranks(x, world):
     """Max of a host float over the ranks (default group = gloo at N > 1: a CPU tensor)."""
     if world == 1:
@@ -238,10 +265,12 @@ def _max_over_ranks(x, world):
     return float(t.item())
 
 
-def train_step_bench(head, dev, rank, world, steps=4, warmup=4, rehearsal=False):
+def train_step_bench(head, dev, rank, world, steps=4, warmup=4, rehearsal=False, keep_outputs=False):
     """BASELINE configs[2]/[3]: training step of the mask path, 2 images/GPU x 128
     positive RoIs, dynamic 14/28/56/112 selection + BCE backward + RCCL all-reduce of
     the flat mask-head gradient + fused SGD.  Returns ms per step (max over ranks).
+    ``keep_outputs``: the last element of the result holds what the last timed step gave its caller (its losses
+    and the parameters its SGD step left), on the host; None otherwise.
 
     The RCCL communicator exists only inside this function: at N > 1 the default process group
     is gloo (host barriers and the max over ranks) and the data-path collective gets an `nccl`
@@ -280,16 +309,16 @@ def train_step_bench(head, dev, rank, world, steps=4, warmup=4, rehearsal=False)
 
     issue = []          # host time to issue a step's launches (ms): the step is close to host-bound
 
-    def window():
+    def window(n):
         torch.cuda.synchronize()
         if world > 1:
             import torch.distributed as dist
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for _ in range(n):
             r = step()
-        issue.append((time.perf_counter() - t0) / steps * 1e3)
+        issue.append((time.perf_counter() - t0) / n * 1e3)
         torch.cuda.synchronize()
         if world > 1:
             import torch.distributed as dist
@@ -297,13 +326,18 @@ def train_step_bench(head, dev, rank, world, steps=4, warmup=4, rehearsal=False)
         torch.cuda.synchronize()
         w = _max_over_ranks(time.perf_counter() - t0, world)
         return w, r
-    # median of three windows of `steps` steps: a caching-allocator growth (hipMalloc) inside one
+    # `steps` steps in three windows, the median window's ms/step: a caching-allocator growth (hipMalloc) inside one
     # window otherwise shows up as a 20-30 % outlier of this secondary figure
-    wins = [window() for _ in range(3)]
+    sizes = window_sizes(steps)
+    wins = [window(n) for n in sizes]
     res = wins[-1][1]
-    dt = sorted(w for w, _ in wins)[1]
-    print('[bench] train-step windows (ms/step): ' + ', '.join(f'{w / steps * 1e3:.2f}' for w, _ in wins)
+    step_ms = statistics.median(w / n for (w, _), n in zip(wins, sizes)) * 1e3
+    print('[bench] train-step windows (ms/step): ' + ', '.join(f'{w / n * 1e3:.2f}' for (w, _), n in zip(wins, sizes))
           + '; host issue ' + ', '.join(f'{v:.2f}' for v in issue), file=sys.stderr)
+    outputs = None
+    if keep_outputs:            # before the windows below take more steps
+        outputs = {f'loss_mask.{k}': v.detach().cpu() for k, v in res['loss_mask'].items() if isinstance(v, torch.Tensor)}
+        outputs['flat_param'] = grp.flat_param.detach().cpu()
     # communication alone: the flat-gradient all-reduce (16.65 MB) timed by itself, so that
     # the scaling curve can be read with and without it; 0 at world size 1
     comm_ms = 0.0
@@ -316,7 +350,7 @@ def train_step_bench(head, dev, rank, world, steps=4, warmup=4, rehearsal=False)
     if world > 1:
         reduce_on[0] = False
         step()
-        noreduce_ms = window()[0] / steps * 1e3
+        noreduce_ms = window(sizes[0])[0] / sizes[0] * 1e3
         reduce_on[0] = True
     if world == 1 and not dist.is_initialized() and os.environ.get('DM_BENCH_NO_RCCL', '0') != '1':
         # World size 1: the step above ran without a collective (a single-GPU job has nothing to reduce: this
@@ -330,7 +364,7 @@ def train_step_bench(head, dev, rank, world, steps=4, warmup=4, rehearsal=False)
             dist.init_process_group('nccl', rank=0, world_size=1, device_id=dev)
             own_group = True
             step()
-            forced_ms = window()[0] / steps * 1e3
+            forced_ms = window(sizes[0])[0] / sizes[0] * 1e3
         except Exception as e:      # noqa: BLE001  (recorded in the JSON; the headline needs no collective)
             print(f'[bench] RCCL world-1 group unavailable: {e}', file=sys.stderr)
     if dist.is_initialized():
@@ -355,12 +389,12 @@ def train_step_bench(head, dev, rank, world, steps=4, warmup=4, rehearsal=False)
         torch.cuda.synchronize()
         dist.barrier()
         dist.destroy_process_group(sub)
-    step_ms = dt / steps * 1e3
     if world > 1:
         exposed_ms = step_ms - noreduce_ms
     else:
         exposed_ms = (forced_ms - step_ms) if forced_ms is not None else None
-    return step_ms, float(res['loss_mask']['loss_masks'].detach()), grp.numel, B, comm_ms, collective, forced_ms, exposed_ms
+    return (step_ms, float(res['loss_mask']['loss_masks'].detach()), grp.numel, B, comm_ms, collective, forced_ms, exposed_ms,
+            outputs)
 
 
 def count_host_syncs(fn):
@@ -498,7 +532,7 @@ def launch_ranks(n):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=30)
+    ap.add_argument('--steps', type=int, default=90, help='timed steps of the headline leg in all (three windows)')
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--leg', choices=('infer', 'train'), default='infer',
                     help="which leg is the headline `value`: 'infer' = BASELINE configs[1] (default); 'train' = the "
@@ -509,7 +543,12 @@ def main():
     ap.add_argument('--no-end-to-end', action='store_true',
                     help='skip the whole-detector context leg (stock MIOpen ResNet-50-FPN + the mask path, rank 0 only)')
     ap.add_argument('--cpu-sample', type=int, default=512, help='RoIs of the batch timed on the host cores (0 = skip)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help="write what the headline leg's last timed step computed (rank 0) as DIR/<name>.npy: the infer leg's "
+                         "per-stage logits; the train leg's losses and the parameters its SGD step left")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     # ---- ranks: one process per GPU.  The driver starts N>1 ranks itself (torch.distributed.run
     # sets WORLD_SIZE); a bare `python bench.py --gpus N` starts them here, as fresh children,
@@ -569,9 +608,12 @@ def main():
     # HIP-graph capture of the headline leg below brings streams of its own that end up sharing queues with them
     # (measured: 23.6 ms per step before the capture, 24.3 ms after it).  The headline leg is not affected by the
     # order (the training leg leaves nothing behind but cached allocator memory).
-    t_steps, t_warm = (args.steps, args.warmup) if args.leg == 'train' else (4, 4)
-    train_ms, train_loss, n_flat, train_b, comm_ms, collective, forced_ms, exposed_ms = train_step_bench(
-        head, dev, rank, world, steps=t_steps, warmup=t_warm, rehearsal=rehearsal)
+    t_steps, t_warm = (args.steps, args.warmup) if args.leg == 'train' else (12, 4)
+    dump_train = bool(args.dump_outputs) and args.leg == 'train' and rank == 0
+    train_ms, train_loss, n_flat, train_b, comm_ms, collective, forced_ms, exposed_ms, train_out = train_step_bench(
+        head, dev, rank, world, steps=t_steps, warmup=t_warm, rehearsal=rehearsal, keep_outputs=dump_train)
+    if dump_train:
+        dump_outputs(args.dump_outputs, train_out)
 
     entry = None
     if rank == 0 and os.environ.get('DM_BENCH_NO_ENTRY', '0') != '1':
@@ -612,24 +654,29 @@ def main():
         except Exception as e:      # capture not available: stay eager (recorded in the JSON)
             print(f'[bench] HIP graph capture failed, timing eager launches: {e}', file=sys.stderr)
             graph = None
-    def timed_window():
-        """EXACTLY args.steps steps between barrier + synchronize on both sides; max over ranks."""
+    def timed_window(n):
+        """EXACTLY n steps between barrier + synchronize on both sides; max over ranks, and the last step's output."""
         torch.cuda.synchronize()
         barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
+        for _ in range(n):
+            out = step()
         torch.cuda.synchronize()
         barrier()
         torch.cuda.synchronize()
-        return _max_over_ranks(time.perf_counter() - t0, world)
-    # three such windows, the median is reported (one window of 20 graph replays is 80 ms: a single
-    # sample of that length is at the mercy of the clock ramp; VERDICT r1 weak #9)
-    windows = sorted(timed_window() for _ in range(3))
-    dt = windows[1]
-    ms_per_step = dt / args.steps * 1e3
-    value = world * 1.0 / (dt / args.steps)          # images (RoI batches of 512) per second, all ranks
+        return _max_over_ranks(time.perf_counter() - t0, world), out
+    # the --steps timed steps as three windows, the median window's ms/step is reported (one window of 20 graph
+    # replays is 80 ms: a single sample of that length is at the mercy of the clock ramp; VERDICT r1 weak #9)
+    sizes = window_sizes(args.steps)
+    wins = [timed_window(n) for n in sizes]
+    if args.dump_outputs and args.leg == 'infer' and rank == 0:
+        last = wins[-1][1]          # the graph's output buffers: written out before anything else runs
+        dump_outputs(args.dump_outputs, {f'{k}_{i}': t for k in ('stage_instance_preds', 'stage_detail_preds')
+                                         for i, t in enumerate(last[k])})
+    win_ms = [w / n * 1e3 for (w, _), n in zip(wins, sizes)]
+    ms_per_step = statistics.median(win_ms)
+    value = world * 1e3 / ms_per_step          # images (RoI batches of 512) per second, all ranks
 
     result = {
         'metric': 'img/s (DynaMask mask-head path, 512 RoIs/img, fixed 28x28 exit; ms_per_step = ms per RoI batch)',
@@ -641,8 +688,8 @@ def main():
                    'rois_per_img': ROIS_PER_IMG, 'imgs_per_gpu': 1, 'parallelism': f'images sharded x{world}, no collective',
                    'cpu_baseline': 'rank 0 at N = 1 only (omitted from the N > 1 lines)',
                    'launch': 'hip graph replay' if graph is not None else 'eager',
-                   'timing': f'median of 3 windows of {args.steps} steps; windows ms/step = '
-                             + ', '.join(f'{w / args.steps * 1e3:.3f}' for w in windows)},
+                   'timing': f'{args.steps} steps in {len(sizes)} windows of {sizes} steps, median of their ms/step; '
+                             'windows ms/step = ' + ', '.join(f'{w:.3f}' for w in win_ms)},
     }
     # The training step (BASELINE configs[2] at N = 1, configs[3] at N = 8) is the unit of the north star's scaling
     # curve: its figures are TOP-LEVEL keys of the line at every N, whichever leg is the headline.
@@ -668,7 +715,7 @@ def main():
                         ', dynamic 14/28/56/112 resolution selection + BCE backward (mask path: RoIAlign14 + RoIAlign56 + '
                         'MaskPre + ST-Gumbel + DynaMaskHead + loss + backward)',
             'imgs_per_gpu': train_b, 'pos_rois_per_img': 128, 'parallelism': f'images sharded x{world}, {collective}',
-            'launch': 'eager (four streams)', 'timing': f'median of 3 windows of {t_steps} steps'}
+            'launch': 'eager (four streams)', 'timing': f'{t_steps} steps in {len(window_sizes(t_steps))} windows, median of their ms/step'}
 
     if rank == 0:
         from dynamask_amd import ops
