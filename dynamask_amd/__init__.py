@@ -13,3 +13,5 @@ There is no CPU or eager-PyTorch fallback: every operator raises if
 libdynamask_hip.so is missing or its input is not on a HIP device.
 """
 __version__ = '0.1.0'
+
+from .precision import conv_precision, get_conv_precision, set_conv_precision  # noqa: E402,F401

@@ -72,16 +72,68 @@ struct ConvArgs {
 // column-gradient GEMMs 1.56 -> 1.20, 0.94 -> 0.78, 0.75 -> 0.67 ms, fusion 130->64 @56^2 0.56 -> 0.45 ms.
 // The kernel body takes its place in the grid as arguments (bx of gx workgroups, split by): conv_igemm_kernel passes
 // blockIdx / gridDim, conv_igemm_group_kernel (several independent convolutions in one launch) a range of its grid.
-template <int KS, int WGM, int WGN, int WM, int WN, int CK, int MAXPOS, int TAIL = 0>
+//
+// PREC (round 7, opt-in: flag bit 4 of dm_conv2d_fwd / dm_conv2d_fwd_ws / dm_conv1x1_group_fwd, inference only): the
+// bf16x3 split on the bf16 matrix cores.  An fp32 value is cut into three bf16 planes with round-to-nearest,
+// x = hi + mid + lo (hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid): 24 significant bits), and a product is
+// the six largest cross terms lo*hi + mid*mid + hi*lo + mid*hi + hi*mid + hi*hi -- six v_mfma_f32_32x32x16_bf16 per 16
+// channels, issued in that fixed order (smallest first), accumulated in fp32: the five correction terms in an accumulator
+// of their own, added to hi*hi's once at the end (their roundings then are ~2^-8 of the main sum's).  The dropped terms are below 2^-24
+// relative: sums differ from the exact kernel's in rounding only.  16 channels x 32 cycles per bf16 MFMA against 2 x 64
+// per v_mfma_f32_32x32x2_f32: 16 x 64 / (6 x 32 x 2) = 2.7 x the fp32 matrix rate.  K is walked in chunks of 16 channels;
+// a "word" (16 bytes) holds 8 consecutive channels of one (cout | pixel) as bf16, and the six words of a chunk are
+// (channels 0-7 | 8-15) x (hi, mid, lo).  Weights are split once, by pack_weight_bf16x3_kernel (sources padded to 16
+// channels); activations when a thread commits its prefetched floats to LDS (once per staged value: split at the read,
+// a 3x3 tile would split each value nine times, once per tap, in the MFMA loop).  When hi is not finite, mid = lo = 0,
+// so an Inf or NaN operand makes the same outputs non-finite as in the exact kernel (the pattern is kept, not the
+// value: Inf times a zero mid or lo plane of the other operand is NaN where the exact kernel has +-Inf).  Only 64-cout x 128-pixel tiles and no TAIL rows are built: a
+// 36-cout launch (the DCN offset convolutions) runs as one 64-cout tile, its tail couts on the bf16 MFMA like the rest;
+// launches the split build does not cover (3x3 maps wider than ~16 pixels) return DM_ERR_UNSUPPORTED, and the host's
+// routing table (ops.BF16X3_ROUTES) keeps the shapes where the split is not faster on the exact kernel.
+typedef __bf16 dm_bf16x8 __attribute__((ext_vector_type(8)));
+
+// x -> (hi, mid, lo), round-to-nearest-even; fp32 subnormal residuals are kept (bf16 has fp32's exponent range, and the
+// build keeps fp32 denormals), a non-finite hi gets mid = lo = 0
+__device__ __forceinline__ void dm_split3(float x, __bf16& h, __bf16& m, __bf16& l) {
+  h = (__bf16)x;
+  const float hf = (float)h;
+  if (__builtin_isfinite(hf)) {
+    const float r1 = x - hf;          // exact: hf is x rounded to 8 significant bits
+    m = (__bf16)r1;
+    l = (__bf16)(r1 - (float)m);      // exact likewise
+  } else {
+    m = (__bf16)0.f;
+    l = (__bf16)0.f;
+  }
+}
+
+// 8 floats -> their hi, mid and lo words (8 bf16 each)
+__device__ __forceinline__ void dm_split8x3(const dm_f32x4& q0, const dm_f32x4& q1, dm_f32x4 (&out)[3]) {
+  dm_bf16x8 w[3];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    __bf16 h, m, l;
+    dm_split3(e < 4 ? q0[e] : q1[e - 4], h, m, l);
+    w[0][e] = h;
+    w[1][e] = m;
+    w[2][e] = l;
+  }
+#pragma unroll
+  for (int p = 0; p < 3; ++p) out[p] = __builtin_bit_cast(dm_f32x4, w[p]);
+}
+
+template <int KS, int WGM, int WGN, int WM, int WN, int CK, int MAXPOS, int TAIL = 0, int PREC = 0>
 __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx, const int gx, const int by) {
   static_assert(TAIL == 0 || (TAIL == 4 && WGM == 1), "tail rows need a single cout tile");
+  static_assert(PREC == 0 || (PREC == 1 && CK == 16 && TAIL == 0 && WM == 1 && WN == 2 && WGM == 2 && WGN == 2),
+                "the bf16x3 build: 64 x 128 tiles, 16-channel chunks, no tail rows");
   constexpr int TM = WGM * WM * 32;
   constexpr int TMA = TM + TAIL;              // rows of the LDS A image
   constexpr int TN = WGN * WN * 32;
   constexpr int NT = WGM * WGN * 64;
   constexpr int TAPS = KS * KS;
   constexpr int NQ = CK / 4;                      // channel quads per chunk (what a thread prefetches of a pixel)
-  constexpr int NWC = NQ;                         // 16-byte words per chunk and (cout | pixel) in LDS and in the packed weights
+  constexpr int NWC = PREC ? 6 : NQ;              // 16-byte words per chunk and (cout | pixel) in LDS and in the packed weights
   constexpr int A_F4 = TAPS * NWC * TMA;          // float4 slots of the A chunk
   constexpr int A_PER_T = (A_F4 + NT - 1) / NT;
   constexpr int B1_PER_T = (NQ * TN + NT - 1) / NT;   // 1x1: float4 slots per thread
@@ -162,9 +214,9 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
       const int x = p - y * W;
       const int seg = n - n0;
       const int r = (seg == 0) ? (y - y00 + 1) : (rows0 + 2) + (seg - 1) * (H + 2) + (y + 1);
-      lane_base[wn] = (r - 1) * Wp + x + hi * plane;
+      lane_base[wn] = (r - 1) * Wp + x + (PREC ? 3 * hi : hi) * plane;      // (PREC: lane half = channels 8 hi .. = words 3 hi ..)
     } else {
-      lane_base[wn] = j + hi * plane;
+      lane_base[wn] = j + (PREC ? 3 * hi : hi) * plane;
     }
   }
 
@@ -214,6 +266,14 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
     for (int j = 0; j < WN; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  constexpr int WMX = PREC ? WM : 1, WNX = PREC ? WN : 1;
+  dm_f32x16 accx[WMX][WNX];   // PREC: the correction terms' accumulators
+#pragma unroll
+  for (int i = 0; i < WMX; ++i)
+#pragma unroll
+    for (int j = 0; j < WNX; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) accx[i][j][r] = 0.f;
   dm_f32x4 acct[WN];      // tail couts TM .. TM+3 of this lane's pixel (lanes >= 32: the other K half)
 #pragma unroll
   for (int j = 0; j < WN; ++j) acct[j] = dm_f32x4{0.f, 0.f, 0.f, 0.f};
@@ -225,7 +285,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
   auto chunk_valid = [&]() { return cs < a.num_srcs && k_left > 0; };
   auto chunk_advance = [&]() {
     const int ckv = min(CK, curC - cc0);
-    ckq += ((ckv + 7) / 8) * 2;
+    ckq += PREC ? NWC : ((ckv + 7) / 8) * 2;      // (PREC: every source is padded to whole 16-channel chunks)
     cc0 += CK;
     if (cc0 >= curC) {
       cs++;
@@ -252,11 +312,11 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
   // issue the global loads of the chunk at (cs, cc0, ckq) into registers
   auto prefetch = [&]() {
     const int ckv = min(CK, curC - cc0);
-    const int nq = ((ckv + 7) / 8) * 2;    // quads of this chunk present in the packed weights
+    const int nq = PREC ? NWC : ((ckv + 7) / 8) * 2;    // quads (words) of this chunk present in the packed weights
     // the chunk's part of an address is uniform (ckq, cc0); the thread's part is fixed for the K loop
     // (per source for B) and kept in a register: no 64-bit multiplies per load next to the MFMAs
     const float* abase = a.wq + (size_t)ckq * a.CoutP * 4;
-    if (KS == 1 && A_F4 % NT == 0 && NQ * TN % NT == 0 && a.off32 && ckv == CK) {
+    if (KS == 1 && (A_F4 % NT == 0 || PREC) && NQ * TN % NT == 0 && a.off32 && ckv == CK) {
       // Full chunk of a 1x1 build: nothing is predicated.  (The general path below guards every dword -- pixel inside the
       // matrix, channel inside the source, quad inside the chunk -- with an exec-mask branch and a 64-bit vector address:
       // ~150 instructions per 16 MFMAs in the 64-cout build, 4.8 VALU + 5.6 SALU per MFMA on the 576 -> 64 GEMM
@@ -264,7 +324,8 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
       // thread was clamped to -- its output column is never stored; rows past CoutP repeat the last row.  Addresses are a
       // uniform row base (SALU) plus the thread's 32-bit pixel offset.
 #pragma unroll
-      for (int i = 0; i < A_PER_T; ++i) ra[i] = *reinterpret_cast<const dm_f32x4*>(abase + a_off[i]);
+      for (int i = 0; i < A_PER_T; ++i)
+        if (A_F4 % NT == 0 || tid + i * NT < A_F4) ra[i] = *reinterpret_cast<const dm_f32x4*>(abase + a_off[i]);   // (PREC: wave-uniform)
       if (b_src != cs) {
         b_off32 = (unsigned)((size_t)max(st_n[0], 0) * (size_t)a.src_bs[cs] + st_pix[0]);
         b_srcp = a.src[cs];
@@ -275,7 +336,8 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
       const int qw = (TN % 64 == 0) ? __builtin_amdgcn_readfirstlane(tid / TN) : tid / TN;      // (uniform per wave from 64 columns on)
 #pragma unroll
       for (int i = 0; i < B1_PER_T; ++i) {
-        const float* rq = rp + (size_t)((qw + i * (NT / TN)) * 4) * HW;
+        // (PREC: a thread stages the two quads of one 8-channel half -- commit splits them into its three words)
+        const float* rq = rp + (size_t)((PREC ? qw * 2 + i : qw + i * (NT / TN)) * 4) * HW;
 #pragma unroll
         for (int e = 0; e < 4; ++e) rb[i][e] = rq[(size_t)e * HW + b_off32];
       }
@@ -335,7 +397,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
       const float* gp = sp + b_off[0];
 #pragma unroll
       for (int i = 0; i < B1_PER_T; ++i) {
-        const int qd = tid / TN + i * (NT / TN);
+        const int qd = PREC ? (tid / TN) * 2 + i : tid / TN + i * (NT / TN);
         dm_f32x4 v = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -353,7 +415,31 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
       const int idx = tid + i * NT;
       if (idx < A_F4) ldsA[idx] = ra[i];
     }
-    if (KS == 3) {
+    if (PREC) {
+      // fp32 -> three bf16 words per 8-channel half: [channels 0-7: hi, mid, lo][channels 8-15: hi, mid, lo]
+      if (KS == 3) {
+#pragma unroll
+        for (int k = 0; k < MAXPOS; ++k) {
+          const int pos = tid + k * NT;
+          if (pos < plane) {
+#pragma unroll
+            for (int h8 = 0; h8 < 2; ++h8) {
+              dm_f32x4 wd[3];
+              dm_split8x3(rb[k * NQ + 2 * h8], rb[k * NQ + 2 * h8 + 1], wd);
+#pragma unroll
+              for (int p_ = 0; p_ < 3; ++p_) ldsB[(3 * h8 + p_) * plane + pos] = wd[p_];
+            }
+          }
+        }
+      } else {
+        static_assert(!PREC || KS == 3 || (B1_PER_T == 2 && NT / TN == 2), "1x1 bf16x3 build: two quads (one half) per thread");
+        const int h8 = tid / TN;
+        dm_f32x4 wd[3];
+        dm_split8x3(rb[0], rb[B1_PER_T > 1 ? 1 : 0], wd);
+#pragma unroll
+        for (int p_ = 0; p_ < 3; ++p_) ldsB[(3 * h8 + p_) * plane + (tid % TN)] = wd[p_];
+      }
+    } else if (KS == 3) {
 #pragma unroll
       for (int k = 0; k < MAXPOS; ++k) {
         const int pos = tid + k * NT;
@@ -386,7 +472,44 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
     // Operand fragments are double-buffered in registers: the ds_reads of step s+1 are
     // issued before the 4 x WM x WN MFMAs of step s, so LDS latency never stalls the
     // matrix pipe (the compiler alone re-uses one register set and issues them late).
-    {
+    if (PREC) {
+      // one step per tap: the chunk's 16 channels are ONE k of v_mfma_f32_32x32x16_bf16 (lane half hi = channels 8 hi ..)
+      auto load_frag = [&](int tap, dm_f32x4 (*av)[3], dm_f32x4 (*bv)[3]) {
+        const int tapoff = (KS == 3) ? ((tap / 3) * Wp + (tap % 3)) : 0;
+#pragma unroll
+        for (int i = 0; i < WM; ++i)
+#pragma unroll
+          for (int p_ = 0; p_ < 3; ++p_) av[i][p_] = ldsA[(tap * NWC + 3 * hi + p_) * TMA + (wave_m * WM + i) * 32 + l31];
+#pragma unroll
+        for (int j = 0; j < WN; ++j)
+#pragma unroll
+          for (int p_ = 0; p_ < 3; ++p_) bv[j][p_] = ldsB[p_ * plane + lane_base[j] + tapoff];
+      };
+      auto mfma = [&](const dm_f32x4& x, const dm_f32x4& y, dm_f32x16& c) {
+        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(dm_bf16x8, x), __builtin_bit_cast(dm_bf16x8, y), c, 0, 0, 0);
+      };
+      dm_f32x4 av[2][WM][3], bv[2][WN][3];
+      load_frag(0, av[0], bv[0]);
+#pragma unroll
+      for (int st = 0; st < TAPS; ++st) {
+        const int cur = st & 1;
+        if (st + 1 < TAPS) load_frag(st + 1, av[cur ^ 1], bv[cur ^ 1]);
+#pragma unroll
+        for (int i = 0; i < WM; ++i)
+#pragma unroll
+          for (int j = 0; j < WN; ++j) {
+            // (A part, B part), smallest terms first: the same order in every launch, hence the same bits every run.  The
+            // five correction terms go to an accumulator of their own (~2^-8 of the main one: its roundings are that much
+            // smaller), added to hi*hi's once, before the epilogue.
+            mfma(av[cur][i][2], bv[cur][j][0], accx[i][j]);
+            mfma(av[cur][i][1], bv[cur][j][1], accx[i][j]);
+            mfma(av[cur][i][0], bv[cur][j][2], accx[i][j]);
+            mfma(av[cur][i][1], bv[cur][j][0], accx[i][j]);
+            mfma(av[cur][i][0], bv[cur][j][1], accx[i][j]);
+            mfma(av[cur][i][0], bv[cur][j][0], acc[i][j]);
+          }
+      }
+    } else {
       constexpr int NG = NQ / 2;
       constexpr int STEPS = TAPS * NG;
       auto load_frag = [&](int st, dm_f32x4* av, dm_f32x4* bv) {
@@ -427,6 +550,15 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
       }
     }
     __syncthreads();
+  }
+
+  if (PREC) {
+#pragma unroll
+    for (int i = 0; i < WMX; ++i)
+#pragma unroll
+      for (int j = 0; j < WNX; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[i][j][r] += accx[i][j][r];
   }
 
   // ---- epilogue: bias + ReLU, 32 consecutive pixels per register ------------
@@ -559,9 +691,10 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
   }
 }
 
-template <int KS, int WGM, int WGN, int WM, int WN, int CK, int MAXPOS, int TAIL = 0>
-__global__ __launch_bounds__(WGM* WGN * 64, (KS == 3 && WGM == 2 && WGN == 2 && WM == 2 && WN == 2 && MAXPOS == 1) || (KS == 1 && CK == 16) ? 3 : 1) void conv_igemm_kernel(ConvArgs a) {
-  conv_igemm_body<KS, WGM, WGN, WM, WN, CK, MAXPOS, TAIL>(a, (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.y);
+// (PREC 3x3: 55 KB of A image + the plane -- two workgroups per CU)
+template <int KS, int WGM, int WGN, int WM, int WN, int CK, int MAXPOS, int TAIL = 0, int PREC = 0>
+__global__ __launch_bounds__(WGM* WGN * 64, PREC ? (KS == 1 ? 3 : 2) : (KS == 3 && WGM == 2 && WGN == 2 && WM == 2 && WN == 2 && MAXPOS == 1) || (KS == 1 && CK == 16) ? 3 : 1) void conv_igemm_kernel(ConvArgs a) {
+  conv_igemm_body<KS, WGM, WGN, WM, WN, CK, MAXPOS, TAIL, PREC>(a, (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.y);
 }
 
 // Up to three INDEPENDENT convolutions in one launch (round 6: the three FPN-wide semantic_transform_in 1x1 convolutions of
@@ -572,12 +705,12 @@ struct ConvGroup {
   ConvArgs a[3];
   int end[3];
 };
-template <int KS, int WGM, int WGN, int WM, int WN, int CK, int MAXPOS>
+template <int KS, int WGM, int WGN, int WM, int WN, int CK, int MAXPOS, int PREC = 0>
 __global__ __launch_bounds__(WGM* WGN * 64, (KS == 1 && CK == 16) ? 3 : 1) void conv_igemm_group_kernel(ConvGroup g) {
   const int b = (int)blockIdx.x;
-  if (b < g.end[0]) conv_igemm_body<KS, WGM, WGN, WM, WN, CK, MAXPOS, 0>(g.a[0], b, g.end[0], 0);
-  else if (b < g.end[1]) conv_igemm_body<KS, WGM, WGN, WM, WN, CK, MAXPOS, 0>(g.a[1], b - g.end[0], g.end[1] - g.end[0], 0);
-  else conv_igemm_body<KS, WGM, WGN, WM, WN, CK, MAXPOS, 0>(g.a[2], b - g.end[1], g.end[2] - g.end[1], 0);
+  if (b < g.end[0]) conv_igemm_body<KS, WGM, WGN, WM, WN, CK, MAXPOS, 0, PREC>(g.a[0], b, g.end[0], 0);
+  else if (b < g.end[1]) conv_igemm_body<KS, WGM, WGN, WM, WN, CK, MAXPOS, 0, PREC>(g.a[1], b - g.end[0], g.end[1] - g.end[0], 0);
+  else conv_igemm_body<KS, WGM, WGN, WM, WN, CK, MAXPOS, 0, PREC>(g.a[2], b - g.end[1], g.end[2] - g.end[1], 0);
 }
 
 // Packed weight layout [tap][KQ][CoutP][4]: KQ quads = sum over sources of
@@ -631,6 +764,52 @@ __device__ __forceinline__ void pack_weight_body(const PackArgs& p, int ld, int 
 
 __global__ void pack_weight_kernel(PackArgs p) { pack_weight_body(p, p.Cin, 0); }
 
+// bf16x3 layout (PREC builds): [tap][KQ][colsP][16 bytes], sources padded to 16 channels, KQ = sum of roundup(Cs, 16) / 16
+// * 6 words; word 6 b + 3 h + part of a source's 16-channel block b holds channels 16 b + 8 h .. + 7 of one produced
+// channel as bf16 (part 0 = hi, 1 = mid, 2 = lo: dm_split3).  One thread per (tap, 8-channel half, col).
+__global__ void pack_weight_bf16x3_kernel(PackArgs p) {
+  const int HB = p.KQ / 3;                      // 8-channel halves
+  const long long total = (long long)p.kk * HB * p.colsP;
+  dm_f32x4* out = reinterpret_cast<dm_f32x4*>(p.wq);
+  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
+       idx += (long long)gridDim.x * blockDim.x) {
+    const int col = (int)(idx % p.colsP);
+    const int hb = (int)(idx / p.colsP % HB);
+    const int tap = (int)(idx / ((long long)p.colsP * HB));
+    float v[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      int pc = hb * 8 + e, row = -1, base = 0;
+      for (int s = 0; s < p.nsrc; ++s) {
+        const int padded = (p.src_c[s] + 15) / 16 * 16;
+        if (pc < padded) {
+          if (pc < p.src_c[s]) row = base + pc;
+          break;
+        }
+        pc -= padded;
+        base += p.src_c[s];
+      }
+      float x = 0.f;
+      if (row >= 0 && col < p.cols) {
+        if (p.deconv) {
+          const int phase = col / p.Cout, co = col - phase * p.Cout;
+          x = p.w[((size_t)row * p.Cout + co) * 4 + phase];
+        } else if (!p.flip) {
+          x = p.w[((size_t)col * p.Cin + row) * p.kk + tap];
+        } else {
+          x = p.w[((size_t)row * p.Cin + col) * p.kk + (p.kk - 1 - tap)];
+        }
+      }
+      v[e] = x;
+    }
+    dm_f32x4 wd[3];
+    dm_split8x3(dm_f32x4{v[0], v[1], v[2], v[3]}, dm_f32x4{v[4], v[5], v[6], v[7]}, wd);
+    const size_t w0 = ((size_t)tap * p.KQ + 3 * hb) * p.colsP + col;
+#pragma unroll
+    for (int p_ = 0; p_ < 3; ++p_) out[w0 + (size_t)p_ * p.colsP] = wd[p_];
+  }
+}
+
 // Every pack of a training step in ONE launch (blockIdx.y = job): ~45 weight tensors change with every optimizer
 // step, and a launch per tensor cost the host 1.3 ms of the 3.7 ms it needs to issue a forward pass.
 __global__ void pack_weight_batch_kernel(const dm_pack_job* __restrict__ jobs) {
@@ -653,6 +832,12 @@ __global__ void pack_weight_batch_kernel(const dm_pack_job* __restrict__ jobs) {
 int packed_quads(int nsrc, const int* src_c) {
   int kq = 0;
   for (int s = 0; s < nsrc; ++s) kq += (src_c[s] + 7) / 8 * 2;
+  return kq;
+}
+
+int packed_words_bf16x3(int nsrc, const int* src_c) {
+  int kq = 0;
+  for (int s = 0; s < nsrc; ++s) kq += (src_c[s] + 15) / 16 * 6;
   return kq;
 }
 
@@ -728,15 +913,22 @@ static int conv_split_choice(int chunks, bool k3, int Smax, long long out_floats
   return S;
 }
 
-template <int KS, int WGM, int WGN, int WM, int WN, int CK, int MAXPOS, int TAIL = 0>
+template <int KS, int WGM, int WGN, int WM, int WN, int CK, int MAXPOS, int TAIL = 0, int PREC = 0>
 int launch_conv_mp(ConvArgs& a, hipStream_t st) {
   constexpr int TM = WGM * WM * 32;
   constexpr int TN = WGN * WN * 32;
   constexpr int NT = WGM * WGN * 64;
   const int NTiles = dm_ceil_div(a.Q - a.q_begin, TN);
-  constexpr int NWC = CK / 4;
+  constexpr int NWC = PREC ? 6 : CK / 4;
   const size_t lds_bytes = 16 * ((size_t)KS * KS * NWC * (TM + TAIL) + (size_t)NWC * a.plane);
-  if (lds_bytes > 64 * 1024) return DM_ERR_UNSUPPORTED;
+  if (lds_bytes > 64 * 1024) {
+    // (the bf16x3 3x3 build: 54 KB of A image + 21 KB of plane at 14 x 14; two workgroups per CU)
+    if (!PREC || lds_bytes > 80 * 1024) return DM_ERR_UNSUPPORTED;
+    static bool raised[DM_MAX_DEVICES] = {false};
+    const int rc = dm_ensure_lds_limit(reinterpret_cast<const void*>(&conv_igemm_kernel<KS, WGM, WGN, WM, WN, CK, MAXPOS, TAIL, PREC>),
+                                       80 * 1024, raised);
+    if (rc != DM_OK) return rc;
+  }
   // ---- split-K for launches that leave most of the chip idle (a caller-provided workspace, one launch per call)
   a.ksplit = 1;
   if (a.ws && a.shuffle == 0 && a.q_begin == 0) {
@@ -764,7 +956,7 @@ int launch_conv_mp(ConvArgs& a, hipStream_t st) {
     const float* mask = a.mask;
     float* out = a.out;
     const int flags = a.relu, oct = a.out_ch_total, oco = a.out_ch_offset;
-    DM_LAUNCH((conv_igemm_kernel<KS, WGM, WGN, WM, WN, CK, MAXPOS, TAIL>), dim3(a.MT * NTiles, a.ksplit), dim3(NT), lds_bytes, st, a);
+    DM_LAUNCH((conv_igemm_kernel<KS, WGM, WGN, WM, WN, CK, MAXPOS, TAIL, PREC>), dim3(a.MT * NTiles, a.ksplit), dim3(NT), lds_bytes, st, a);
     int rc = dm_check_launch();
     if (rc != DM_OK) return rc;
     const long long total = a.ws_stride;
@@ -778,11 +970,11 @@ int launch_conv_mp(ConvArgs& a, hipStream_t st) {
                 a.ksplit, a.ws_stride, a.NB, a.Cout, a.HW, bias, flags, out, oct, oco, mask);
     return dm_check_launch();
   }
-  DM_LAUNCH((conv_igemm_kernel<KS, WGM, WGN, WM, WN, CK, MAXPOS, TAIL>), dim3(a.MT * NTiles), dim3(NT), lds_bytes, st, a);
+  DM_LAUNCH((conv_igemm_kernel<KS, WGM, WGN, WM, WN, CK, MAXPOS, TAIL, PREC>), dim3(a.MT * NTiles), dim3(NT), lds_bytes, st, a);
   return dm_check_launch();
 }
 
-template <int KS, int WGM, int WGN, int WM, int WN, int CK, int TAIL = 0>
+template <int KS, int WGM, int WGN, int WM, int WN, int CK, int TAIL = 0, int PREC = 0>
 int launch_conv(ConvArgs& a, hipStream_t st) {
   constexpr int TM = WGM * WM * 32;
   constexpr int TN = WGN * WN * 32;
@@ -793,14 +985,27 @@ int launch_conv(ConvArgs& a, hipStream_t st) {
     const int nsegmax = dm_ceil_div(TN - 1, a.HW) + 1;
     const int rmax = dm_ceil_div(TN - 1, a.W) + 1 + 2 * nsegmax;
     a.plane = rmax * a.Wp;
-    if (a.plane <= NT) return launch_conv_mp<KS, WGM, WGN, WM, WN, CK, 1, TAIL>(a, st);
-    if (a.plane <= 2 * NT) return launch_conv_mp<KS, WGM, WGN, WM, WN, CK, 2, TAIL>(a, st);
-    if (a.plane <= 4 * NT) return launch_conv_mp<KS, WGM, WGN, WM, WN, CK, 4, TAIL>(a, st);
-    return DM_ERR_UNSUPPORTED;
+    if constexpr (PREC != 0) {
+      // bf16x3: one plane position per thread (maps up to ~16 x 16); wider maps would need more than 80 KB of LDS
+      if (a.plane <= NT) return launch_conv_mp<KS, WGM, WGN, WM, WN, CK, 1, TAIL, PREC>(a, st);
+      return DM_ERR_UNSUPPORTED;
+    } else {
+      if (a.plane <= NT) return launch_conv_mp<KS, WGM, WGN, WM, WN, CK, 1, TAIL>(a, st);
+      if (a.plane <= 2 * NT) return launch_conv_mp<KS, WGM, WGN, WM, WN, CK, 2, TAIL>(a, st);
+      if (a.plane <= 4 * NT) return launch_conv_mp<KS, WGM, WGN, WM, WN, CK, 4, TAIL>(a, st);
+      return DM_ERR_UNSUPPORTED;
+    }
   }
   a.Wp = 0;
   a.plane = TN;
-  return launch_conv_mp<KS, WGM, WGN, WM, WN, CK, 1, TAIL>(a, st);
+  return launch_conv_mp<KS, WGM, WGN, WM, WN, CK, 1, TAIL, PREC>(a, st);
+}
+
+int run_pack_bf16x3(PackArgs& p, hipStream_t st) {
+  const long long total = (long long)p.kk * (p.KQ / 3) * p.colsP;
+  const int blocks = (int)min((long long)dm_ceil_div(total, 256), 4096LL);
+  DM_LAUNCH(pack_weight_bf16x3_kernel, dim3(blocks), dim3(256), 0, st, p);
+  return dm_check_launch();
 }
 
 int run_pack(PackArgs& p, hipStream_t st) {
@@ -839,6 +1044,35 @@ extern "C" int dm_conv_pack_weight(const float* w_oihw, int Cout, int Cin, int k
   p.KQ = packed_quads(num_srcs, src_channels);
   p.deconv = 0;
   return run_pack(p, (hipStream_t)stream);
+}
+
+// (ABI 28) the bf16x3 layout of the same weights (the kernel's header): flag bit 4 of dm_conv2d_fwd / _ws /
+// dm_conv1x1_group_fwd reads it
+extern "C" long long dm_conv_packed_floats_bf16x3(int Cout, int ksize, int num_srcs, const int* src_channels) {
+  if (Cout <= 0 || ksize <= 0 || num_srcs < 1 || num_srcs > DM_MAX_SOURCES || !src_channels) return -1;
+  return (long long)ksize * ksize * packed_words_bf16x3(num_srcs, src_channels) * dm_conv_packed_cout(Cout) * 4;
+}
+
+extern "C" int dm_conv_pack_weight_bf16x3(const float* w_oihw, int Cout, int Cin, int ksize, int transpose_flip,
+                                          int num_srcs, const int* src_channels, float* w_packed, dm_stream_t stream) {
+  if (!w_oihw || !w_packed || Cout <= 0 || Cin <= 0 || (ksize != 1 && ksize != 3)) return DM_ERR_INVALID_ARG;
+  if (num_srcs < 1 || num_srcs > DM_MAX_SOURCES || !src_channels) return DM_ERR_INVALID_ARG;
+  PackArgs p;
+  p.w = w_oihw; p.wq = w_packed; p.Cout = Cout; p.Cin = Cin; p.kk = ksize * ksize; p.flip = transpose_flip ? 1 : 0;
+  p.rows = transpose_flip ? Cout : Cin;
+  p.cols = transpose_flip ? Cin : Cout;
+  p.colsP = dm_conv_packed_cout(p.cols);
+  p.nsrc = num_srcs;
+  int sum = 0;
+  for (int s = 0; s < DM_MAX_SOURCES; ++s) {
+    p.src_c[s] = s < num_srcs ? src_channels[s] : 0;
+    if (s < num_srcs && src_channels[s] <= 0) return DM_ERR_INVALID_ARG;
+    sum += p.src_c[s];
+  }
+  if (sum != p.rows) return DM_ERR_INVALID_ARG;
+  p.KQ = packed_words_bf16x3(num_srcs, src_channels);
+  p.deconv = 0;
+  return run_pack_bf16x3(p, (hipStream_t)stream);
 }
 
 extern "C" int dm_conv_pack_weight_batch(const dm_pack_job* jobs_device, int num_jobs, dm_stream_t stream) {
@@ -896,6 +1130,7 @@ extern "C" int dm_conv2d_fwd_masked(const float* const* srcs, const int* src_cha
                                     const float* w_packed, const float* bias, int Cout, int ksize, int relu, float* out,
                                     int out_ch_total, int out_ch_offset, const float* mask, dm_stream_t stream) {
   if (!mask) return DM_ERR_INVALID_ARG;
+  if (relu & 16) return DM_ERR_UNSUPPORTED;      // (no bf16x3 build of the data-gradient launches)
   return conv2d_launch(srcs, src_channels, src_batch_strides, num_srcs, NB, H, W, w_packed, bias, Cout, ksize, relu, out,
                        out_ch_total, out_ch_offset, mask, stream);
 }
@@ -922,8 +1157,9 @@ static int conv2d_launch(const float* const* srcs, const int* src_channels, cons
     }
   }
   a.num_srcs = num_srcs;
-  if (relu & ~15) return DM_ERR_INVALID_ARG;      // (bits 4, 5 selected the bf16-split layouts of ABI 18-21: removed)
-  a.KQ = packed_quads(num_srcs, src_channels);
+  if (relu & ~31) return DM_ERR_INVALID_ARG;      // (bit 5 selected a bf16-split layout of ABI 18-21: removed)
+  const bool bf16x3 = (relu & 16) != 0;          // (ABI 28) w_packed is the bf16x3 layout (dm_conv_pack_weight_bf16x3)
+  a.KQ = bf16x3 ? packed_words_bf16x3(num_srcs, src_channels) : packed_quads(num_srcs, src_channels);
   a.NB = NB; a.H = H; a.W = W; a.HW = H * W; a.Q = NB * H * W;
   a.wq = w_packed; a.bias = bias; a.Cout = Cout; a.CoutP = dm_conv_packed_cout(Cout);
   a.relu = relu & 3; a.out = out; a.out_ch_total = out_ch_total; a.out_ch_offset = out_ch_offset;
@@ -940,6 +1176,12 @@ static int conv2d_launch(const float* const* srcs, const int* src_channels, cons
   // below); accumulating launches read the destination and keep the default policy
   if (!(relu & 2) && (long long)NB * Cout * H * W * 4 > (192LL << 20)) a.relu |= 4;
   hipStream_t st = (hipStream_t)stream;
+  if (bf16x3) {
+    // one build per kernel size: 64 couts x 128 pixels, four waves of 32 x 64 (see the kernel's header); a workspace
+    // lets it split K as the exact launches do (launch_conv_mp's cost model, 16-channel chunks)
+    if (ksize == 3) return launch_conv<3, 2, 2, 1, 2, 16, 0, 1>(a, st);
+    return launch_conv<1, 2, 2, 1, 2, 16, 0, 1>(a, st);
+  }
   if (ksize == 3) {
     if (Cout > 64) {
       // 128 x 128 tiles run two or three to a CU: a launch is a sequence of rounds of 512 / 768 workgroups,
@@ -1039,18 +1281,35 @@ extern "C" int dm_deconv_pack_weight(const float* w_iohw, int Cin, int Cout, flo
   return run_pack(p, (hipStream_t)stream);
 }
 
+// (ABI 28) the bf16x3 layout of the deconv weights (flag bit 4 of dm_deconv2x2_fwd): dm_conv_pack_weight_bf16x3's layout of
+// the 4 * Cout packed columns, dm_conv_packed_floats_bf16x3(4 * Cout, 1, 1, &Cin) floats
+extern "C" int dm_deconv_pack_weight_bf16x3(const float* w_iohw, int Cin, int Cout, float* w_packed, dm_stream_t stream) {
+  if (!w_iohw || !w_packed || Cin <= 0 || Cout <= 0) return DM_ERR_INVALID_ARG;
+  PackArgs p;
+  p.w = w_iohw; p.wq = w_packed; p.Cout = Cout; p.Cin = Cin; p.kk = 1; p.flip = 0;
+  p.rows = Cin; p.cols = 4 * Cout; p.colsP = dm_conv_packed_cout(4 * Cout);
+  p.nsrc = 1;
+  for (int s = 0; s < DM_MAX_SOURCES; ++s) p.src_c[s] = 0;
+  p.src_c[0] = Cin;
+  p.KQ = packed_words_bf16x3(1, p.src_c);
+  p.deconv = 1;
+  return run_pack_bf16x3(p, (hipStream_t)stream);
+}
+
 extern "C" int dm_deconv2x2_fwd(const float* x, int NB, int C, int H, int W, const float* w_packed, const float* bias,
                                 int Cout, int relu, float* out, dm_stream_t stream) {
   if (!x || !w_packed || !out || NB < 0 || C <= 0 || H <= 0 || W <= 0 || Cout <= 0) return DM_ERR_INVALID_ARG;
   if ((long long)NB * H * W > 0x7fffffffLL) return DM_ERR_INVALID_ARG;
   if (NB == 0) return DM_OK;
+  const bool bf16x3 = (relu & 16) != 0;          // (ABI 28) w_packed is dm_deconv_pack_weight_bf16x3's layout
   ConvArgs a;
   for (int s = 0; s < DM_MAX_SOURCES; ++s) { a.src[s] = nullptr; a.src_c[s] = 0; a.src_bs[s] = 0; }
   a.src[0] = x; a.src_c[0] = C; a.src_bs[0] = (long long)C * H * W; a.num_srcs = 1;
-  a.KQ = packed_quads(1, a.src_c);
+  a.KQ = bf16x3 ? packed_words_bf16x3(1, a.src_c) : packed_quads(1, a.src_c);
   a.NB = NB; a.H = H; a.W = W; a.HW = H * W; a.Q = NB * H * W;
   a.wq = w_packed; a.bias = bias; a.Cout = 4 * Cout; a.CoutP = dm_conv_packed_cout(4 * Cout);
-  a.relu = relu; a.out = out; a.out_ch_total = 0; a.out_ch_offset = 0; a.shuffle = Cout; a.q_begin = 0;
+  a.relu = relu & ~16; a.out = out; a.out_ch_total = 0; a.out_ch_offset = 0; a.shuffle = Cout; a.q_begin = 0;
+  if (bf16x3) return launch_conv<1, 2, 2, 1, 2, 16, 0, 1>(a, (hipStream_t)stream);
   return launch_conv<1, 2, 2, 2, 2, 16>(a, (hipStream_t)stream);
 }
 
@@ -1063,7 +1322,8 @@ extern "C" int dm_conv1x1_group_fwd(int count, const float* const* x, const int*
                                     const float* const* w_packed, const float* const* bias, const int* Cout, int relu,
                                     float* const* out, dm_stream_t stream) {
   if (count < 1 || count > 3 || !x || !Cin || !H || !W || !w_packed || !bias || !Cout || !out || NB < 0) return DM_ERR_INVALID_ARG;
-  if (relu & ~1) return DM_ERR_INVALID_ARG;
+  if (relu & ~17) return DM_ERR_INVALID_ARG;
+  const bool bf16x3 = (relu & 16) != 0;          // (ABI 28) every w_packed[i] is the bf16x3 layout
   if (NB == 0) return DM_OK;
   ConvGroup g;
   int total = 0;
@@ -1075,7 +1335,7 @@ extern "C" int dm_conv1x1_group_fwd(int count, const float* const* x, const int*
     ConvArgs& a = g.a[i];
     for (int s = 0; s < DM_MAX_SOURCES; ++s) { a.src[s] = nullptr; a.src_c[s] = 0; a.src_bs[s] = 0; }
     a.src[0] = x[j]; a.src_c[0] = Cin[j]; a.src_bs[0] = (long long)Cin[j] * H[j] * W[j]; a.num_srcs = 1;
-    a.KQ = packed_quads(1, a.src_c);
+    a.KQ = bf16x3 ? packed_words_bf16x3(1, a.src_c) : packed_quads(1, a.src_c);
     a.NB = NB; a.H = H[j]; a.W = W[j]; a.HW = H[j] * W[j]; a.Q = NB * H[j] * W[j];
     a.wq = w_packed[j]; a.bias = bias[j]; a.Cout = Cout[j]; a.CoutP = dm_conv_packed_cout(Cout[j]);
     a.relu = relu & 1; a.out = out[j]; a.out_ch_total = Cout[j]; a.out_ch_offset = 0;
@@ -1086,8 +1346,11 @@ extern "C" int dm_conv1x1_group_fwd(int count, const float* const* x, const int*
     if (i < count) total += a.MT * dm_ceil_div(a.Q, TN);
     g.end[i] = total;
   }
-  constexpr int CK = 16, NWC = CK / 4;
-  const size_t lds_bytes = 16 * ((size_t)NWC * TM + (size_t)NWC * TN);
-  DM_LAUNCH((conv_igemm_group_kernel<1, 2, 2, 1, 2, 16, 1>), dim3((unsigned)total), dim3(256), lds_bytes, (hipStream_t)stream, g);
+  const size_t nwc = bf16x3 ? 6 : 16 / 4;
+  const size_t lds_bytes = 16 * (nwc * TM + nwc * TN);
+  if (bf16x3)
+    DM_LAUNCH((conv_igemm_group_kernel<1, 2, 2, 1, 2, 16, 1, 1>), dim3((unsigned)total), dim3(256), lds_bytes, (hipStream_t)stream, g);
+  else
+    DM_LAUNCH((conv_igemm_group_kernel<1, 2, 2, 1, 2, 16, 1>), dim3((unsigned)total), dim3(256), lds_bytes, (hipStream_t)stream, g);
   return dm_check_launch();
 }

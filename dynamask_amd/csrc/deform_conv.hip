@@ -1095,6 +1095,7 @@ static int deform_conv_fwd_impl(const float* x, const float* offset, int NB, int
                                 const float* w_packed, int Cout, int deform_groups, int relu, float* out, float* ws,
                                 long long ws_floats, dm_stream_t stream, const DcnTout* tout) {
   if (!x || !offset || !w_packed || !out) return DM_ERR_INVALID_ARG;
+  if (relu & 16) return DM_ERR_UNSUPPORTED;      // (flag bit 4, the bf16x3 mode of dm_conv2d_fwd: the DCN stays exact fp32)
   if (NB < 0 || C <= 0 || H <= 0 || W <= 0 || Cout <= 0 || deform_groups <= 0 || C % deform_groups != 0)
     return DM_ERR_INVALID_ARG;
   if ((long long)NB * H * W > 0x7fffffffLL) return DM_ERR_INVALID_ARG;

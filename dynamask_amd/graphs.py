@@ -16,6 +16,7 @@ the same bucket.
 import torch
 
 from . import ops
+from .precision import get_conv_precision
 
 # (round 6: 24 / 48 / 80 added -- a call is padded up to its bucket, and the call time grows almost linearly with the RoI
 # count above 16: 0.61 / 0.79 / 0.90 / 1.21 / 1.39 / 1.93 ms at 16 / 24 / 32 / 48 / 64 / 100 detections, so 33 detections
@@ -68,8 +69,10 @@ class GraphedMaskLogits:
         raise RuntimeError('the mask head changed while its graph key was built')
 
     def _key(self, bucket, x):
+        # (the convolution precision and its routing table: a graph captured in one mode never replays in the other)
         return (bucket, tuple(int(t.data_ptr()) for t in x), tuple(tuple(t.shape) for t in x), ops.WEIGHT_EPOCH[0],
-                self._weights_key(), torch.cuda.current_device())
+                self._weights_key(), torch.cuda.current_device(), get_conv_precision(), ops.BF16X3_ROUTES,
+                ops.BF16X3_SEMANTIC_GROUP[0])
 
     def _capture(self, key, bucket, x):
         dev = x[0].device

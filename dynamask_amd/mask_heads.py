@@ -28,10 +28,14 @@ class _Packed:
     def __init__(self):
         self._c = {}
 
-    def get(self, key, param, fn, job=None):
+    def get(self, key, param, fn, job=None, precision='fp32'):
         """``job`` = (transpose_flip, src_channels | None, lo | None, hi | None): the pack is dm_conv_pack_weight of
         the parameter itself (or of its input-channel window lo:hi); such packs of contiguous device parameters are
-        registered with ops.PACK_PLAN and refreshed together in one launch.  Anything else goes through ``fn``."""
+        registered with ops.PACK_PLAN and refreshed together in one launch.  Anything else goes through ``fn``.
+        ``precision='bf16x3'``: ``fn`` makes the bf16x3 layout (inference only: never a PACK_PLAN job), cached under a key
+        of its own, so that both layouts of a weight coexist."""
+        if precision != 'fp32':
+            key, job = (precision, key), None
         if job is not None and param.is_cuda and param.dim() == 4 and param.is_contiguous():
             e = self._c.get(key)
             if e is None or e[0] != 'plan' or e[1]['param']() is not param:
@@ -59,16 +63,22 @@ class _Conv(nn.Module):
         nn.init.kaiming_normal_(self.weight, mode='fan_out', nonlinearity='relu')
         self._pk = _Packed()
 
-    def packed(self, src_channels=None):
+    exact = False         # True: always the exact fp32 kernel, whatever the precision mode (MaskPre, the selector)
+
+    def packed(self, src_channels=None, precision='fp32'):
         key = tuple(src_channels) if src_channels is not None else (self.in_channels,)
-        return self._pk.get(key, self.weight, lambda w: ops.pack_conv_weight(w, src_channels=list(key)),
-                            job=(False, list(key), None, None))
+        return self._pk.get(key, self.weight, lambda w: ops.pack_conv_weight(w, src_channels=list(key), precision=precision),
+                            job=(False, list(key), None, None), precision=precision)
+
+    def precision_for(self, H, W):
+        """The kernel this layer's convolution of an H x W map runs now (ops.conv_precision_for)."""
+        return 'fp32' if self.exact else ops.conv_precision_for(self.out_channels, self.kernel_size, H, W)
 
     def run(self, srcs, relu=False, out=None, out_ch_offset=0):
         b = self.bias.detach() if self.bias is not None else None
         if isinstance(srcs, torch.Tensor):
             srcs = [srcs]
-        wq = self.packed([s.shape[1] for s in srcs])
+        wq = self.packed([s.shape[1] for s in srcs], self.precision_for(srcs[0].shape[2], srcs[0].shape[3]))
         return ops.conv2d(srcs, wq, b, self.out_channels, self.kernel_size, relu=relu, out=out,
                           out_ch_offset=out_ch_offset)
 
@@ -301,7 +311,9 @@ class DynaMaskHead(nn.Module):
         convs = [self.stages[i].semantic_transform_in for i in range(n)]
         if (GROUPED_SEMANTIC_MAPS[0] and 2 <= n <= 3 and not torch.is_grad_enabled() and all(f.is_contiguous() for f in feats)
                 and all(c.bias is not None for c in convs)):
-            return ops.conv1x1_group(feats, [c.packed([c.in_channels]) for c in convs], [c.bias.detach() for c in convs],
+            # (bf16x3 mode: the whole group or none of it, ops.BF16X3_SEMANTIC_GROUP)
+            prec = 'bf16x3' if ops.inference_precision() == 'bf16x3' and ops.BF16X3_SEMANTIC_GROUP[0] else 'fp32'
+            return ops.conv1x1_group(feats, [c.packed([c.in_channels], prec) for c in convs], [c.bias.detach() for c in convs],
                                      [c.out_channels for c in convs], relu=True)
         return [self.stages[i].semantic_map(feats[i]) for i in range(n)]
 
@@ -310,9 +322,12 @@ class DynaMaskHead(nn.Module):
         ``semantic_maps`` owns) on the CURRENT stream.  The caches are filled by whoever asks first; a caller that is
         about to fork RoI chunks onto several streams calls this first, so that no stream reads a pack another
         stream is still writing.  ``fused_dcn``: per stage, whether the fused DCN kernel's layout is the one needed
-        (default: all)."""
+        (default: all).  In the bf16x3 mode (ops.inference_precision) the bf16x3 layout of every convolution is made too:
+        which of the two a chain asks for depends on the map size (ops.BF16X3_ROUTES), and both exist before the fork."""
         for conv in self.instance_convs:
             conv.conv.packed([conv.conv.in_channels])
+            if ops.inference_precision() == 'bf16x3':
+                conv.conv.packed([conv.conv.in_channels], 'bf16x3')
         for i, stage in enumerate(self.stages):
             c, dcn = stage.instance_in_channel, stage.fuse_conv[1]
             stage.fuse_conv[0].packed([c, stage.semantic_transform_in.out_channels, 2])
@@ -320,6 +335,10 @@ class DynaMaskHead(nn.Module):
             if fused_dcn is None or fused_dcn[i]:
                 dcn._pk.get('w', dcn.weight, ops.pack_conv_weight, job=(False, None, None, None))
             stage.fuse_transform_out.packed([dcn.out_channels])
+            if ops.inference_precision() == 'bf16x3':
+                for conv, srcs in ((stage.fuse_conv[0], [c, stage.semantic_transform_in.out_channels, 2]),
+                                   (dcn.conv_offset, [c]), (stage.fuse_transform_out, [dcn.out_channels])):
+                    conv.packed(srcs, 'bf16x3')
             if FUSED_DCN_TOUT[0] and not torch.is_grad_enabled() and stage.fuse_transform_out.weight.is_cuda:
                 stage.fuse_transform_out._pk.get('tout', stage.fuse_transform_out.weight, ops.pack_tout_weight)
 
@@ -553,7 +572,8 @@ class _Deconv(nn.Module):
         self._pk = _Packed()
 
     def forward(self, x, relu=False):
-        wp = self._pk.get('w', self.weight, ops.pack_deconv_weight)
+        p = ops.deconv_precision_for(x.shape[2], x.shape[3])
+        wp = self._pk.get('w', self.weight, lambda w: ops.pack_deconv_weight(w, precision=p), precision=p)
         return ops.deconv2x2(x, wp, self.bias.detach(), self.out_channels, relu=relu)
 
 

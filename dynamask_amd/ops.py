@@ -9,6 +9,7 @@ import ctypes
 import torch
 
 from . import hazard
+from . import precision as _precision
 from ._lib import check, lib
 
 
@@ -292,17 +293,21 @@ def packed_cout(cout):
     return lib().dm_conv_packed_cout(int(cout))
 
 
-def packed_floats(cout, ksize, src_channels):
-    n = lib().dm_conv_packed_floats(int(cout), int(ksize), len(src_channels), _int_array(src_channels))
+def packed_floats(cout, ksize, src_channels, precision='fp32'):
+    fn = lib().dm_conv_packed_floats_bf16x3 if precision == 'bf16x3' else lib().dm_conv_packed_floats
+    n = fn(int(cout), int(ksize), len(src_channels), _int_array(src_channels))
     if n < 0:
         raise ValueError('bad conv packing request')
     return int(n)
 
 
-def pack_conv_weight(w, transpose_flip=False, src_channels=None):
+def pack_conv_weight(w, transpose_flip=False, src_channels=None, precision='fp32'):
     """OIHW -> [k*k][KQ][CoutP][4] (see include/dynamask_hip.h).  ``src_channels``:
-    how the input channels split over the concat sources (default: one source)."""
+    how the input channels split over the concat sources (default: one source).
+    ``precision='bf16x3'``: the split layout of dm_conv_pack_weight_bf16x3, marked as such (``conv_layout``); conv2d
+    and conv1x1_group then run the bf16x3 kernel on it."""
     _chk(w, 'weight')
+    precision = _precision.checked(precision)
     cout, cin, kh, kw = w.shape
     assert kh == kw and kh in (1, 3)
     rows = cout if transpose_flip else cin
@@ -310,10 +315,95 @@ def pack_conv_weight(w, transpose_flip=False, src_channels=None):
     if src_channels is None:
         src_channels = [rows]
     assert sum(src_channels) == rows
-    wp = torch.empty((packed_floats(cols, kh, src_channels),), device=w.device, dtype=torch.float32)
-    check(lib().dm_conv_pack_weight(_p(w), cout, cin, kh, 1 if transpose_flip else 0, len(src_channels),
-                                    _int_array(src_channels), _p(wp), _stream()), 'dm_conv_pack_weight')
+    wp = torch.empty((packed_floats(cols, kh, src_channels, precision),), device=w.device, dtype=torch.float32)
+    fn, name = ((lib().dm_conv_pack_weight_bf16x3, 'dm_conv_pack_weight_bf16x3') if precision == 'bf16x3'
+                else (lib().dm_conv_pack_weight, 'dm_conv_pack_weight'))
+    check(fn(_p(w), cout, cin, kh, 1 if transpose_flip else 0, len(src_channels), _int_array(src_channels), _p(wp),
+             _stream()), name)
+    if precision == 'bf16x3':
+        wp._dm_bf16x3 = True
     return wp
+
+
+def conv_layout(w_packed):
+    """'bf16x3' for a weight packed by ``pack_conv_weight(precision='bf16x3')``, else 'fp32'."""
+    return 'bf16x3' if getattr(w_packed, '_dm_bf16x3', False) else 'fp32'
+
+
+# Per-shape routing of the bf16x3 mode (dynamask_amd/precision.py): the shapes whose bf16x3 launch measured faster than
+# the exact one (profiles/r07_precision.txt, tools/precision_probe.py; DESIGN.md "Opt-in bf16x3 convolutions").  A rule
+# is (ksize, min cout, max cout, max H * W); a shape that no rule covers runs the exact kernel in either mode.
+#   3x3 on 14 x 14 maps: 256 couts 0.64-0.69 of the exact time at 16 / 100 / 512 RoIs, the 36-cout DCN offset
+#     convolution 0.88 (its tail couts run in the 64-cout tile).  Maps of 28 x 28 and wider have no bf16x3 build (LDS).
+#   1x1 on 14 x 14 maps with >= 96 couts: 0.83-0.92; FCNMaskHead's 80-cout conv_logits at 28 x 28: 0.96.  On
+#     28 x 28 / 56 x 56 maps the other 1x1s are not faster (1.01-1.35: the fuse / transform convolutions of 128 and 64
+#     couts, 64 -> 30; the 64-cout fuse at 56 x 56 measured 0.99-1.04 over three collections, no gain): exact.
+BF16X3_ROUTES = (
+    (3, 36, 1 << 30, 16 * 16),
+    (1, 96, 1 << 30, 16 * 16),
+    (1, 80, 80, 28 * 28),
+)
+# the grouped FPN-wide semantic 1x1 convolutions (conv1x1_group, one launch for all three SFM stages)
+BF16X3_SEMANTIC_GROUP = [True]
+# FCNMaskHead's deconv 2x2/s2 (dm_deconv2x2_fwd) on maps up to this many pixels (0: never).  Measured 256 -> 256 @14 x 512
+# RoIs: 0.68-0.70 ms bf16x3 against 0.65 exact (1.04-1.06: its 4 * 256 packed columns already fill the exact 128 x 128 tile; the
+# bf16x3 build's 64-cout tile needs twice the workgroups): exact.
+BF16X3_DECONV_MAX_HW = [0]
+
+
+def _bf16x3_3x3_built(H, W):
+    """dm_conv2d_fwd's bf16x3 3x3 build stages one plane position per thread: the plane of a 128-pixel tile (launch_conv in
+    csrc/conv_igemm.hip) must hold <= 256 positions.  Maps up to 6 x 6 and wide, flat ones (8 x 32, 1 x W) fail that."""
+    hw = H * W
+    nseg = -(-127 // hw) + 1
+    rmax = -(-127 // W) + 1 + 2 * nseg
+    return rmax * (W + 2) <= 256
+
+
+def bf16x3_routed(cout, ksize, H, W):
+    """Does the routing table send this shape to the bf16x3 kernel (and is there a build for it)?"""
+    if ksize == 3 and not _bf16x3_3x3_built(H, W):
+        return False
+    return any(ksize == k and lo <= cout <= hi and H * W <= hw for k, lo, hi, hw in BF16X3_ROUTES)
+
+
+def deconv_precision_for(H, W):
+    """The kernel FCNMaskHead's deconv of an H x W map runs now (BF16X3_DECONV_MAX_HW)."""
+    return 'bf16x3' if inference_precision() == 'bf16x3' and H * W <= BF16X3_DECONV_MAX_HW[0] else 'fp32'
+
+
+_EXACT_DEPTH = [0]
+
+
+def exact_convs(fn):
+    """Decorator: the convolutions issued inside ``fn`` run exact fp32 whatever the precision mode -- the forward and
+    backward of the training path's autograd Functions, whose bodies run with grad disabled."""
+    import functools
+
+    @functools.wraps(fn)
+    def wrapped(*args, **kw):
+        _EXACT_DEPTH[0] += 1
+        try:
+            return fn(*args, **kw)
+        finally:
+            _EXACT_DEPTH[0] -= 1
+    return wrapped
+
+
+def inference_precision():
+    """The precision an inference convolution runs at now: the mode, or 'fp32' while grad is enabled or inside the
+    training path (``exact_convs``)."""
+    p = _precision.get_conv_precision()
+    if p != 'fp32' and (torch.is_grad_enabled() or _EXACT_DEPTH[0] > 0):
+        return 'fp32'
+    return p
+
+
+def conv_precision_for(cout, ksize, H, W):
+    """'bf16x3' when the mode is on, grad is disabled and the routing table takes this shape; else 'fp32'."""
+    if inference_precision() == 'bf16x3' and bf16x3_routed(cout, ksize, H, W):
+        return 'bf16x3'
+    return 'fp32'
 
 
 class _DevicePlan:
@@ -502,14 +592,15 @@ def conv2d(srcs, w_packed, bias, cout, ksize, relu=False, out=None, out_ch_offse
     for s in srcs:
         assert s.shape[0] == NB and s.shape[2] == H and s.shape[3] == W
     cin = sum(s.shape[1] for s in srcs)
-    assert w_packed.numel() == packed_floats(cout, ksize, [s.shape[1] for s in srcs]), 'weights packed for other sources'
+    layout = conv_layout(w_packed)         # the bf16x3 layout runs the bf16x3 kernel (flag bit 4)
+    assert w_packed.numel() == packed_floats(cout, ksize, [s.shape[1] for s in srcs], layout), 'weights packed for other sources'
     if out is None:
         out = torch.empty((NB, cout, H, W), device=srcs[0].device, dtype=torch.float32)
     else:
         _chk(out, 'out')
         assert out.shape[0] == NB and out.shape[2] == H and out.shape[3] == W
     strides = (ctypes.c_longlong * len(srcs))(*[int(s.stride(0)) for s in srcs])
-    flags = (1 if relu else 0) | (2 if accumulate else 0) | (8 if _overlapped else 0)
+    flags = (1 if relu else 0) | (2 if accumulate else 0) | (8 if _overlapped else 0) | (16 if layout == 'bf16x3' else 0)
     if mask is not None:
         _chk(mask, 'mask')
         assert mask.shape == out.shape
@@ -536,7 +627,8 @@ def conv2d(srcs, w_packed, bias, cout, ksize, relu=False, out=None, out_ch_offse
 
 def conv1x1_group(xs, w_packeds, biases, couts, relu=False, outs=None):
     """Up to three independent single-source 1x1 convolutions (+ bias, + ReLU) as ONE launch (dm_conv1x1_group_fwd): the
-    FPN-wide semantic convolutions of the SFM stages.  Same bits as ``conv2d`` per problem."""
+    FPN-wide semantic convolutions of the SFM stages.  Same bits as ``conv2d`` per problem.  The weights are all of one
+    layout (``conv_layout``): the bf16x3 one runs the bf16x3 kernel."""
     k = len(xs)
     assert 1 <= k <= 3 and len(w_packeds) == k and len(biases) == k and len(couts) == k
     NB = xs[0].shape[0]
@@ -544,8 +636,10 @@ def conv1x1_group(xs, w_packeds, biases, couts, relu=False, outs=None):
         _chk(x, 'x')
         _chk(w, 'w_packed')
         assert x.shape[0] == NB
+    layout = conv_layout(w_packeds[0])
+    assert all(conv_layout(w) == layout for w in w_packeds), 'weights of one group packed in different layouts'
     for x, w, c in zip(xs, w_packeds, couts):
-        assert w.numel() == packed_floats(c, 1, [x.shape[1]]), 'weights packed for other sources'
+        assert w.numel() == packed_floats(c, 1, [x.shape[1]], layout), 'weights packed for other sources'
     if outs is None:
         outs = [torch.empty((NB, c, x.shape[2], x.shape[3]), device=x.device, dtype=torch.float32) for x, c in zip(xs, couts)]
     for o, x, c in zip(outs, xs, couts):
@@ -556,7 +650,8 @@ def conv1x1_group(xs, w_packeds, biases, couts, relu=False, outs=None):
         hazard.note_ptr_array(bias_arr, [b for b in biases if b is not None])
     check(lib().dm_conv1x1_group_fwd(k, _ptr_array(xs), _int_array([x.shape[1] for x in xs]), _int_array([x.shape[2] for x in xs]),
                                      _int_array([x.shape[3] for x in xs]), NB, _ptr_array(w_packeds), bias_arr, _int_array(couts),
-                                     1 if relu else 0, _ptr_array(outs), _stream()), 'dm_conv1x1_group_fwd')
+                                     (1 if relu else 0) | (16 if layout == 'bf16x3' else 0), _ptr_array(outs), _stream()),
+          'dm_conv1x1_group_fwd')
     return outs
 
 
@@ -627,22 +722,31 @@ def deform_conv_tout(x, offset, w_packed, cout, deform_groups, w2t, b2, m2, out2
     return dcn
 
 
-def pack_deconv_weight(w):
+def pack_deconv_weight(w, precision='fp32'):
+    """``precision='bf16x3'``: dm_deconv_pack_weight_bf16x3's layout, marked as such (``conv_layout``)."""
     _chk(w, 'weight')
+    precision = _precision.checked(precision)
     cin, cout, kh, kw = w.shape
     assert kh == 2 and kw == 2
-    wp = torch.empty((packed_floats(4 * cout, 1, [cin]),), device=w.device, dtype=torch.float32)
-    check(lib().dm_deconv_pack_weight(_p(w), cin, cout, _p(wp), _stream()), 'dm_deconv_pack_weight')
+    wp = torch.empty((packed_floats(4 * cout, 1, [cin], precision),), device=w.device, dtype=torch.float32)
+    fn, name = ((lib().dm_deconv_pack_weight_bf16x3, 'dm_deconv_pack_weight_bf16x3') if precision == 'bf16x3'
+                else (lib().dm_deconv_pack_weight, 'dm_deconv_pack_weight'))
+    check(fn(_p(w), cin, cout, _p(wp), _stream()), name)
+    if precision == 'bf16x3':
+        wp._dm_bf16x3 = True
     return wp
 
 
 def deconv2x2(x, w_packed, bias, cout, relu=False):
+    """The bf16x3 layout (``pack_deconv_weight(precision='bf16x3')``) runs the bf16x3 kernel (flag bit 4)."""
     _chk(x, 'x')
     _chk(w_packed, 'w_packed')
     NB, C, H, W = x.shape
+    layout = conv_layout(w_packed)
+    assert w_packed.numel() == packed_floats(4 * cout, 1, [C], layout), 'weights packed for another shape'
     out = torch.empty((NB, cout, 2 * H, 2 * W), device=x.device, dtype=torch.float32)
-    check(lib().dm_deconv2x2_fwd(_p(x), NB, C, H, W, _p(w_packed), _p(bias), cout, 1 if relu else 0, _p(out),
-                                 _stream()), 'dm_deconv2x2_fwd')
+    check(lib().dm_deconv2x2_fwd(_p(x), NB, C, H, W, _p(w_packed), _p(bias), cout,
+                                 (1 if relu else 0) | (16 if layout == 'bf16x3' else 0), _p(out), _stream()), 'dm_deconv2x2_fwd')
     return out
 
 

@@ -78,6 +78,8 @@ class MaskPre(nn.Module):
         self.bn2 = _BN(16)
         self.fc1 = _Linear(3136, 512)
         self.fc2 = _Linear(512, 4)
+        # the selector's input: exact fp32 in every precision mode (dynamask_amd/precision.py), so exits cannot move
+        self.conv1.exact = self.conv2.exact = True
         # torch defaults of the reference (nn.Conv2d): kaiming_uniform(a=sqrt(5))
         for m, ref in ((self.conv1, nn.Conv2d(256, 128, 1)), (self.conv2, nn.Conv2d(128, 16, 3, padding=1))):
             with torch.no_grad():

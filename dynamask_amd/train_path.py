@@ -235,6 +235,7 @@ class MaskHeadFn(torch.autograd.Function):
         return (*ips, *dps)
 
     @staticmethod
+    @ops.exact_convs
     def issue(head, rois, labels, ins_feats, fpn_feats, after_convs=None):
         """The launches of the forward (no autograd state): -> (ips, dps, saved, feats, rois, labels).
         ``after_convs``: called once the instance convolutions of both halves have been issued (the GPU then has
@@ -397,6 +398,7 @@ class MaskHeadFn(torch.autograd.Function):
 
     @staticmethod
     @hazard.backward_node
+    @ops.exact_convs
     def backward(ctx, *grads):
         head, sv, feats, rois, labels = ctx.head, ctx.saved, ctx.feats, ctx.rois, ctx.labels
         hazard.engine_handoff(*grads)
@@ -733,6 +735,7 @@ class FCNMaskHeadFn(torch.autograd.Function):
     upsample (deconv / CARAFE / bilinear / nearest) and the 1x1 logits conv.  Inputs: (head, x, *head.parameters())."""
 
     @staticmethod
+    @ops.exact_convs
     def forward(ctx, head, x, *params):
         acts = [x.detach().contiguous()]
         for conv in head.convs:
@@ -755,6 +758,7 @@ class FCNMaskHeadFn(torch.autograd.Function):
 
     @staticmethod
     @hazard.backward_node
+    @ops.exact_convs
     def backward(ctx, g):
         head, acts, u, aux = ctx.head, ctx.acts, ctx.u, ctx.aux
         hazard.engine_handoff(g)

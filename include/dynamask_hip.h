@@ -55,7 +55,7 @@ extern "C" {
 typedef void* dm_stream_t; /* hipStream_t */
 
 const char* dm_error_string(int code);
-/* ABI version: bumped whenever a signature or the meaning of an argument changes (8: flag bit 3 of dm_conv2d_fwd; 9: RoI assignment / bbox training entry points; 10: dm_detail_target takes the fuse weights from device memory; 11: FCNMaskHead upsample backward; 12: dm_fc_fwd takes a scratch slab, deterministic split-K; 13: dm_deform_coord_grad / dm_deform_col2im, dm_conv2d_fwd_masked, dm_scale, dm_polygon_mask_targets, dm_ignore_columns, dm_upsample2x_bilinear_bwd overwrites; 14: dm_random_sample, dm_bn_relu_maxpool_argmax, the *_fx deterministic accumulators + dm_fx_to_float, dm_mask_loss_fwd_bwd takes a scratch, dm_conv2d_wgrad takes the bias gradient, dm_conv_pack_weight_batch, dm_mask_loss_stage; 15: dm_class_logits_up2x_fwd; 16: dm_conv2d_wgrad_slab / dm_conv2d_wgrad_scratch_floats; 17: dm_class_logits_bwd_slab / dm_class_logits_bwd_scratch_floats; 18: dm_reload_env_knobs, dm_roi_align_fwd_ws / dm_roi_align_workspace_bytes, dm_conv_pack_weight_split / dm_conv_packed_floats_split and flag bits 4, 5 of dm_conv2d_fwd; 19: dm_dcn_bwd_data_fused and its pack; 20: dm_conv2d_fwd_ws / dm_conv2d_splitk_floats; 21: dm_deform_conv_fwd_ws / dm_deform_conv_splitk_floats; 22: the bf16-split layouts (dm_conv_pack_weight_split, dm_conv_packed_floats_split, flag bits 4 / 5 of dm_conv2d_fwd) and the one-kernel DCN data gradient (dm_dcn_bwd_*) REMOVED -- measured, never the parity path, see docs/HISTORY.md; 23: dm_bn_stats takes mean_shift, dm_roi_align_bwd takes the gather form for 16 < P <= 64; 24: dm_build_info; 25: dm_boundary_merge_chain, dm_stage_head_fwd; 26: dm_conv1x1_group_fwd; 27: dm_deform_conv_tout_fwd / dm_deform_conv_tout_supported). */
+/* ABI version: bumped whenever a signature or the meaning of an argument changes (8: flag bit 3 of dm_conv2d_fwd; 9: RoI assignment / bbox training entry points; 10: dm_detail_target takes the fuse weights from device memory; 11: FCNMaskHead upsample backward; 12: dm_fc_fwd takes a scratch slab, deterministic split-K; 13: dm_deform_coord_grad / dm_deform_col2im, dm_conv2d_fwd_masked, dm_scale, dm_polygon_mask_targets, dm_ignore_columns, dm_upsample2x_bilinear_bwd overwrites; 14: dm_random_sample, dm_bn_relu_maxpool_argmax, the *_fx deterministic accumulators + dm_fx_to_float, dm_mask_loss_fwd_bwd takes a scratch, dm_conv2d_wgrad takes the bias gradient, dm_conv_pack_weight_batch, dm_mask_loss_stage; 15: dm_class_logits_up2x_fwd; 16: dm_conv2d_wgrad_slab / dm_conv2d_wgrad_scratch_floats; 17: dm_class_logits_bwd_slab / dm_class_logits_bwd_scratch_floats; 18: dm_reload_env_knobs, dm_roi_align_fwd_ws / dm_roi_align_workspace_bytes, dm_conv_pack_weight_split / dm_conv_packed_floats_split and flag bits 4, 5 of dm_conv2d_fwd; 19: dm_dcn_bwd_data_fused and its pack; 20: dm_conv2d_fwd_ws / dm_conv2d_splitk_floats; 21: dm_deform_conv_fwd_ws / dm_deform_conv_splitk_floats; 22: the bf16-split layouts (dm_conv_pack_weight_split, dm_conv_packed_floats_split, flag bits 4 / 5 of dm_conv2d_fwd) and the one-kernel DCN data gradient (dm_dcn_bwd_*) REMOVED -- measured, never the parity path, see docs/HISTORY.md; 23: dm_bn_stats takes mean_shift, dm_roi_align_bwd takes the gather form for 16 < P <= 64; 24: dm_build_info; 25: dm_boundary_merge_chain, dm_stage_head_fwd; 26: dm_conv1x1_group_fwd; 27: dm_deform_conv_tout_fwd / dm_deform_conv_tout_supported; 28: the opt-in bf16x3 mode -- dm_conv_pack_weight_bf16x3 / dm_conv_packed_floats_bf16x3 and flag bit 4 of dm_conv2d_fwd, dm_conv2d_fwd_ws and dm_conv1x1_group_fwd; dm_deconv_pack_weight_bf16x3 and flag bit 4 of dm_deconv2x2_fwd). */
 int dm_abi_version(void);
 /* "libdynamask_hip abi=N arch=gfx950 compiler=<clang version> flags=<the product-wide flags of dynamask_amd/build.py>"
  * (static storage).  The library must be compiled WITHOUT packed fp32 instructions (flag "-packed-fp32-ops", see
@@ -134,6 +134,15 @@ typedef struct dm_pack_job {
 } dm_pack_job;
 int dm_conv_pack_weight_batch(const dm_pack_job* jobs_device, int num_jobs, dm_stream_t stream);
 
+/* (ABI 28) The bf16x3 layout of the same weights, for the opt-in split mode of the forward convolutions (flag bit 4 of
+ * dm_conv2d_fwd / dm_conv2d_fwd_ws / dm_conv1x1_group_fwd).  Every weight w is stored as three bf16 numbers rounded to
+ * nearest, hi = bf16(w), mid = bf16(w - hi), lo = bf16(w - hi - mid) (mid = lo = 0 when hi is not finite):
+ * [k*k][KQ][CoutP][16 bytes], each source padded with zero rows to a multiple of 16 channels, KQ = sum(roundup(Cs, 16))
+ * / 16 * 6 words, dm_conv_packed_floats_bf16x3() floats.  Arguments as dm_conv_pack_weight's. */
+long long dm_conv_packed_floats_bf16x3(int Cout, int ksize, int num_srcs, const int* src_channels);
+int dm_conv_pack_weight_bf16x3(const float* w_oihw, int Cout, int Cin, int ksize, int transpose_flip,
+                               int num_srcs, const int* src_channels, float* w_packed, dm_stream_t stream);
+
 /* ---------------------------------------------------------------------------
  * K5/K6  dense convolution forward, stride 1, "same" padding, ksize in {1,3},
  * fp32 in / fp32 accumulate on the MFMA units, fused concat + bias + ReLU.
@@ -151,7 +160,13 @@ int dm_conv_pack_weight_batch(const dm_pack_job* jobs_device, int num_jobs, dm_s
  *            for gradient sums in the backward); bit 3: the caller overlaps this
  *            launch with work on another stream (a scheduling hint: the 3x3
  *            kernel then does not split off its last round of workgroups;
- *            results are the same bits either way); any other bit: DM_ERR_INVALID_ARG
+ *            results are the same bits either way); bit 4 (ABI 28): w_packed is
+ *            the dm_conv_pack_weight_bf16x3 layout and the products run as six
+ *            bf16 MFMA cross products of the split operands, fp32 accumulation
+ *            (error at fp32 level, not the exact fp32 chain; the same bits every
+ *            run); 3x3 launches whose staged plane exceeds 256 positions (maps
+ *            wider than ~16 pixels) return DM_ERR_UNSUPPORTED under it;
+ *            any other bit: DM_ERR_INVALID_ARG
  * out      : written at channels [out_ch_offset, out_ch_offset+Cout) of a
  *            tensor [NB, out_ch_total, H, W]
  * ------------------------------------------------------------------------- */
@@ -175,14 +190,17 @@ int dm_conv2d_fwd_ws(const float* const* srcs, const int* src_channels, const lo
  * semantic_transform_in convolutions of the three SFM stages (mmdet/models/roi_heads/mask_heads/dynamask_head.py:104,
  * relu(conv1x1(P4 / P3 / P2))), which no RoI enters and which otherwise head the inference chain as three launches.
  * x, Cin, H, W, w_packed, bias, Cout, out: HOST arrays of `count` entries (device pointers inside); w_packed[i] as
- * dm_conv_pack_weight(ksize 1, one source) lays it out; bias[i] may be NULL.  Same bits as dm_conv2d_fwd per problem. */
+ * dm_conv_pack_weight(ksize 1, one source) lays it out; bias[i] may be NULL.  Same bits as dm_conv2d_fwd per problem.
+ * relu: bit 0 ReLU; bit 4 (ABI 28): every w_packed[i] is the dm_conv_pack_weight_bf16x3 layout (the bf16x3 mode of
+ * dm_conv2d_fwd, same bits as its launches); any other bit: DM_ERR_INVALID_ARG. */
 int dm_conv1x1_group_fwd(int count, const float* const* x, const int* Cin, const int* H, const int* W, int NB,
                          const float* const* w_packed, const float* const* bias, const int* Cout, int relu, float* const* out,
                          dm_stream_t stream);
 
 /* dm_conv2d_fwd whose epilogue also applies a ReLU adjoint: outputs where `mask` (same layout, channel count and
  * channel offset as `out`) is not > 0 are stored as 0.  Used for data gradients: the mask is the activation the
- * gradient flows into, so the separate mask pass (read gradient + activation, write gradient) disappears. */
+ * gradient flows into, so the separate mask pass (read gradient + activation, write gradient) disappears.  Flag bit 4
+ * (the bf16x3 mode) returns DM_ERR_UNSUPPORTED here, as it does on the DCN entry points: those stay exact fp32. */
 int dm_conv2d_fwd_masked(const float* const* srcs, const int* src_channels, const long long* src_batch_strides,
                          int num_srcs, int NB, int H, int W, const float* w_packed, const float* bias, int Cout,
                          int ksize, int relu, float* out, int out_ch_total, int out_ch_offset, const float* mask,
@@ -296,9 +314,11 @@ int dm_boundary_merge_chain(const float* p_s, const float* p_2s, const float* fi
  * K16  deconv 2x2 stride 2 (+bias, +ReLU): nn.ConvTranspose2d(C, Cout, 2, 2)
  * replaces: FCNMaskHead.upsample 'deconv' (mask_heads/fcn_mask_head.py:77-83,121-124).
  * x [NB, C, H, W]; w_packed = dm_deconv_pack_weight of the [C, Cout, 2, 2] weight;
- * out [NB, Cout, 2H, 2W]
+ * out [NB, Cout, 2H, 2W].  relu: bit 0 ReLU; bit 4 (ABI 28): w_packed is dm_deconv_pack_weight_bf16x3's layout (the
+ * bf16x3 mode of dm_conv2d_fwd; dm_conv_packed_floats_bf16x3(4 * Cout, 1, 1, &Cin) floats).
  * ------------------------------------------------------------------------- */
 int dm_deconv_pack_weight(const float* w_iohw, int Cin, int Cout, float* w_packed, dm_stream_t stream);
+int dm_deconv_pack_weight_bf16x3(const float* w_iohw, int Cin, int Cout, float* w_packed, dm_stream_t stream);
 int dm_deconv2x2_fwd(const float* x, int NB, int C, int H, int W, const float* w_packed, const float* bias,
                      int Cout, int relu, float* out, dm_stream_t stream);
 
