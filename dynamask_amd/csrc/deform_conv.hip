@@ -35,12 +35,12 @@ struct DcnArgs {
   long long ws_stride = 0, ws_floats = 0;
   int ksplit = 1, kchan = 0;
   // the 1x1 convolution behind the DCN, chained in the epilogue of the band kernel (round 6, dm_deform_conv_tout_fwd):
-  // out2[m] = relu(b2[m] + sum_k w2[m][k] * relu(dcn[k])), w2t = [Cout][M2P] (transposed, rows of 32-padded couts);
+  // out2[m] = relu(b2[m] + sum_k w2[m][k] * relu(dcn[k])), w2t = [Cout][w2_ld] (transposed; w2_ld = M2 rounded up to 32);
   // store_out = 0: the DCN output itself is not written
   const float* w2t = nullptr;
   const float* b2 = nullptr;
   float* out2 = nullptr;
-  int M2 = 0, out2_ct = 0, store_out = 1;
+  int M2 = 0, w2_ld = 0, out2_ct = 0, store_out = 1;
 };
 
 // One bilinear sample from its two row pairs.  Spelled as an explicit fma chain so that every kernel
@@ -852,13 +852,16 @@ __global__ __launch_bounds__(256, 2) void deform_conv_band_kernel(DcnArgs a, int
   // (0,4),(1,5),(2,6),(3,7),(8,12),... -- the order the 1x1 kernel of conv_igemm.hip uses (quad pairs of a 16-channel
   // chunk): the result has the bits of the two launches it replaces.  The DCN output is then never written (inference).
   if (WGM == 1 && a.w2t) {
-    constexpr int MT2 = (WM + 1) / 2;          // cout tiles of the 1x1 (host: ceil(M2 / 32) <= MT2)
-    constexpr int M2P = MT2 * 32;
+    // MT2: the cout tiles of the 1x1 this build has room for (host: ceil(M2 / 32) <= MT2).  The rows of w2t are w2_ld =
+    // roundup(M2, 32) floats, fewer than MT2 * 32 when M2 needs fewer tiles (128 channels, M2 <= 32): the staging and the
+    // row stride follow w2_ld, and the tiles past M2 are skipped (a wave-uniform branch).
+    constexpr int MT2 = (WM + 1) / 2;
+    const int ld2 = a.w2_ld;
     __syncthreads();                           // every wave is done with the last chunk's operands in LDS
     {
       const dm_f32x4* src = reinterpret_cast<const dm_f32x4*>(a.w2t);
       dm_f32x4* dst = reinterpret_cast<dm_f32x4*>(lds);
-      for (int idx = tid; idx < a.Cout * (M2P / 4); idx += NT) dst[idx] = src[idx];
+      for (int idx = tid; idx < a.Cout * (ld2 / 4); idx += NT) dst[idx] = src[idx];
     }
     __syncthreads();
     const float* w2t = lds;
@@ -875,7 +878,7 @@ __global__ __launch_bounds__(256, 2) void deform_conv_band_kernel(DcnArgs a, int
         const float b = fmaxf(acc[i][r], 0.f);
 #pragma unroll
         for (int t = 0; t < MT2; ++t)
-          acc2[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(w2t[kb * M2P + t * 32 + l31], b, acc2[t], 0, 0, 0);
+          if (t * 32 < ld2) acc2[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(w2t[kb * ld2 + t * 32 + l31], b, acc2[t], 0, 0, 0);
       }
     const int p = p0 + wave_n * 32 + l31;
     if (p < HW) {
@@ -994,7 +997,8 @@ int launch_dcn_band(DcnArgs& a, hipStream_t st) {
   const size_t lds_bytes = 16 * (size_t)(9 * 2 * WM * WGM * 32) + 4 * (size_t)8 * BR * a.W;
   if (a.w2t) {
     // the chained 1x1: this wave layout only (a wave holds every cout of its pixels), its weights must fit the kernel's LDS
-    if (WGM != 1 || dm_ceil_div(a.M2, 32) > (WM + 1) / 2 || (size_t)a.Cout * ((WM + 1) / 2) * 32 * 4 > lds_bytes || a.Cout != WM * 32)
+    if (WGM != 1 || a.w2_ld != dm_ceil_div(a.M2, 32) * 32 || a.w2_ld > (WM + 1) / 2 * 32 || (size_t)a.Cout * a.w2_ld * 4 > lds_bytes ||
+        a.Cout != WM * 32)
       return DM_ERR_UNSUPPORTED;
     a.ws = nullptr;                            // (no split-K: the second GEMM needs the complete channel sums)
   }
@@ -1109,7 +1113,8 @@ static int deform_conv_fwd_impl(const float* x, const float* offset, int NB, int
   a.ws = (ws && ws_floats > 0) ? ws : nullptr;
   a.ws_floats = a.ws ? ws_floats : 0;
   if (tout) {
-    a.w2t = tout->w2t; a.b2 = tout->b2; a.out2 = tout->out2; a.M2 = tout->M2; a.out2_ct = tout->out2_ct;
+    a.w2t = tout->w2t; a.b2 = tout->b2; a.out2 = tout->out2; a.M2 = tout->M2; a.w2_ld = dm_ceil_div(tout->M2, 32) * 32;
+    a.out2_ct = tout->out2_ct;
     a.store_out = (out != tout->out2) ? 1 : 0;
   }
   hipStream_t st = (hipStream_t)stream;

@@ -391,7 +391,9 @@ def test_dcn_with_chained_1x1_has_the_bits_of_the_two_launches(ops):
     """dm_deform_conv_tout_fwd (round 6): DCN 3x3 + ReLU + fuse_transform_out (1x1 + bias + ReLU) in one launch, the second
     GEMM on the accumulators in registers -- bit for bit the two launches, at the 28 x 28 / 128-channel and 56 x 56 /
     64-channel stage shapes with offsets that leave the LDS band, into a channel slice of a wider tensor, with and
-    without keeping the DCN output; shapes the kernel does not take are refused."""
+    without keeping the DCN output; two shapes the kernel does not take are refused.  The other shapes the support
+    predicate accepts or refuses (M2 of one and of two 32-cout tiles at 64 / 128 channels, ragged maps, the few-RoI
+    threshold): tests/test_fused_shapes_gpu.py."""
     gen = torch.Generator().manual_seed(94)
     for C, S, n in ((128, 28, 40), (64, 56, 12), (64, 56, 9)):
         m2 = C // 2 - 2
