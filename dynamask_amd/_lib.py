@@ -75,10 +75,16 @@ SIGNATURES = {
     'dm_rle_scratch_ints': ([_c_int, _c_int, _c_int], ctypes.c_longlong),
     'dm_rle_encode_canvas': ([_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _c_int, _vp], _c_int),
     'dm_paste_rle': ([_vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int, _vp, _vp, _vp, _vp, _c_int, _vp], _c_int),
+    'dm_rle_multi_scratch_ints': ([_c_int, ctypes.c_longlong], ctypes.c_longlong),
+    'dm_paste_masks_multi': ([_vp, _vp, _c_int, _c_int, _c_int, _vp, _c_int, _vp, ctypes.c_longlong, _c_float, _c_int, _vp, _vp], _c_int),
+    'dm_paste_rle_multi': ([_vp, _vp, _c_int, _c_int, _c_int, _vp, _c_int, _vp, ctypes.c_longlong, _c_float, _c_int, _vp, _vp, _vp,
+                            _vp, _c_int, _vp], _c_int),
     'dm_rle_string': ([_vp, _c_int, ctypes.c_longlong, ctypes.c_char_p, ctypes.c_longlong], ctypes.c_longlong),
     'dm_bbox_decode': ([_vp, _c_int, _c_int, _vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _c_float, _c_float, _c_float, _c_float, _c_float, _vp, _vp, _vp], _c_int),
     'dm_nms_mask': ([_vp, _c_int, _c_float, _c_int, _vp, _vp], _c_int),
     'dm_nms_reduce': ([_vp, _c_int, _vp, _c_int], _c_int),
+    'dm_nms_mask_segmented': ([_vp, _c_int, _vp, _c_int, _c_float, _c_int, _vp, ctypes.c_longlong, _vp], _c_int),
+    'dm_nms_reduce_segmented': ([_vp, _c_int, _vp, _c_int, _c_int, _vp, _vp, _vp], _c_int),
     'dm_fc_scratch_floats': ([_c_int, _c_int, _c_int], ctypes.c_longlong),
     'dm_fc_fwd': ([_vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp], _c_int),
     'dm_sgd_momentum_step': ([_vp, _vp, _vp, ctypes.c_longlong, _c_float, _c_float, _c_float, _c_float, _c_int, _vp], _c_int),

@@ -287,6 +287,65 @@ def multiclass_nms(multi_bboxes, multi_scores, score_thr, nms_cfg, max_num=-1, s
     return dets, ci[keep]
 
 
+def multiclass_nms_batch(multi_bboxes_list, multi_scores_list, score_thr, nms_cfg, max_num=-1):
+    """``multiclass_nms`` of B images at once -> list of B (dets [k, 5], labels [k]), each what ``multiclass_nms`` gives
+    for that image alone, bit for bit.  The score cut runs on all images' rows together; every image is one segment of
+    ``ops.nms_segmented`` (suppression bits only within the image, greedy pass on the device, ``max_num`` per image).
+    ``batched_nms``'s class offsets use each image's OWN largest coordinate, as the per-image call does.  Host waits: the
+    candidate count, the per-image candidate counts and the per-image kept counts -- three, whatever B is."""
+    B = len(multi_scores_list)
+    assert len(multi_bboxes_list) == B
+    if B == 0:
+        return []
+    ref = multi_bboxes_list[0]
+    empty = lambda: (ref.new_zeros((0, 5)), ref.new_zeros((0,), dtype=torch.long))      # noqa: E731
+    rows = [int(s.shape[0]) for s in multi_scores_list]
+    if sum(rows) == 0:
+        return [empty() for _ in range(B)]
+    scores_all = torch.cat([s for s in multi_scores_list if s.shape[0] > 0], 0)
+    ncls = scores_all.shape[1] - 1
+    bboxes_all = torch.cat([b.reshape(b.shape[0], -1) for b in multi_bboxes_list if b.shape[0] > 0], 0)
+    n = scores_all.shape[0]
+    fg = scores_all[:, :ncls]
+    cand = (fg > score_thr).nonzero(as_tuple=False)          # row-major: image after image, the per-image order in each
+    if cand.shape[0] == 0:
+        return [empty() for _ in range(B)]
+    ri, ci = cand[:, 0], cand[:, 1]
+    per_class = bboxes_all.view(n, -1, 4)
+    boxes = per_class[ri, ci] if per_class.shape[1] > 1 else per_class[ri, 0]
+    scores = fg[ri, ci]
+    row_start = ops._upload([sum(rows[:b + 1]) for b in range(B)], torch.int64, ref.device)
+    img = torch.searchsorted(row_start, ri, right=True)       # image of every candidate
+    counts = torch.bincount(img, minlength=B).cpu().tolist()
+    cfg = dict(nms_cfg)
+    cfg.pop('type', 'nms')
+    class_agnostic = cfg.pop('class_agnostic', False)
+    if class_agnostic:
+        boxes_for_nms = boxes
+    else:
+        # batched_nms: boxes.max() of the image's own candidates, the same fp32 operations in the same order
+        seg_max = torch.full((B,), float('-inf'), device=boxes.device, dtype=boxes.dtype)
+        seg_max = seg_max.scatter_reduce(0, img, boxes.amax(1), 'amax')
+        offsets = ci.to(boxes) * (seg_max + 1)[img]
+        boxes_for_nms = boxes + offsets[:, None]
+    # per-image stable descending sort == stable descending sort of all, then a stable sort by image
+    o1 = torch.sort(scores, descending=True, stable=True)[1]
+    order = o1[torch.sort(img[o1], stable=True)[1]]
+    sb = boxes_for_nms[order].contiguous()
+    keep, kept = ops.nms_segmented(sb, counts, cfg.get('iou_threshold', cfg.get('iou_thr', 0.5)), max_num=max_num)
+    kept = kept.cpu().tolist()
+    out, start = [], 0
+    for b in range(B):
+        k = kept[b]
+        if k == 0:
+            out.append(empty())
+        else:
+            g = order[keep[start:start + k].long() + start]
+            out.append((torch.cat([boxes[g], scores[g][:, None]], 1), ci[g]))
+        start += counts[b]
+    return out
+
+
 def bbox2result(bboxes, labels, num_classes):
     """core/bbox/transforms.py:76-96."""
     if bboxes.shape[0] == 0:

@@ -84,12 +84,13 @@ __global__ __launch_bounds__(128) void bbox_decode_kernel(DecodeArgs a) {
 }
 
 // mask[i][w] bit b set <=> box j = 64*w + b (j > i) overlaps box i by more than thr.
-// grid = (col tiles, row tiles) of 64 boxes; only the upper triangle does work.
-__global__ __launch_bounds__(64) void nms_mask_kernel(const float* __restrict__ boxes, int M, float thr, float off,
-                                                      unsigned long long* __restrict__ mask, int words) {
-  __shared__ float cb[64 * 4];
-  const int row0 = blockIdx.y * 64, col0 = blockIdx.x * 64;
-  if (blockIdx.x < blockIdx.y) return;
+// One 64 x 64 tile (row tile ty, column tile tx >= ty) of the M boxes at `boxes`, written into the
+// row-major [M][words] matrix at `mask`; shared by the one-matrix and the segmented launch so that both
+// compute the same IoU bits.
+__device__ __forceinline__ void nms_mask_tile(const float* __restrict__ boxes, int M, float thr, float off,
+                                              unsigned long long* __restrict__ mask, int words, int tx, int ty,
+                                              float* cb) {
+  const int row0 = ty * 64, col0 = tx * 64;
   const int t = threadIdx.x;
   const int ncol = min(64, M - col0);
   if (t < ncol) {
@@ -115,7 +116,80 @@ __global__ __launch_bounds__(64) void nms_mask_kernel(const float* __restrict__ 
     const float iou = inter / (area + barea - inter);
     if (iou > thr) bits |= 1ull << j;
   }
-  mask[(size_t)i * words + blockIdx.x] = bits;
+  mask[(size_t)i * words + tx] = bits;
+}
+
+// grid = (col tiles, row tiles) of 64 boxes; only the upper triangle does work.
+__global__ __launch_bounds__(64) void nms_mask_kernel(const float* __restrict__ boxes, int M, float thr, float off,
+                                                      unsigned long long* __restrict__ mask, int words) {
+  __shared__ float cb[64 * 4];
+  if (blockIdx.x < blockIdx.y) return;
+  nms_mask_tile(boxes, M, thr, off, mask, words, blockIdx.x, blockIdx.y, cb);
+}
+
+// Segmented form: segment b = rows [start, start + M) of `boxes` (score-sorted within the segment) and its own
+// [M][ceil(M / 64)] matrix at mask + mask_off -- the diagonal blocks of a block-diagonal layout, no cross-segment
+// words.  seg_tab[b] = (start, M, mask_off).  grid = (max tiles, max tiles, B); tiles past a segment's own return.
+__global__ __launch_bounds__(64) void nms_mask_segmented_kernel(const float* __restrict__ boxes,
+                                                                const long long* __restrict__ seg_tab, float thr,
+                                                                float off, unsigned long long* __restrict__ mask) {
+  __shared__ float cb[64 * 4];
+  const long long* sg = seg_tab + (size_t)blockIdx.z * 3;
+  const int M = (int)sg[1];
+  const int words = (M + 63) >> 6;
+  if ((int)blockIdx.x >= words || (int)blockIdx.y >= words || blockIdx.x < blockIdx.y) return;
+  nms_mask_tile(boxes + (size_t)sg[0] * 4, M, thr, off, mask + sg[2], words, blockIdx.x, blockIdx.y, cb);
+}
+
+// The greedy pass of dm_nms_reduce on the device, one wave per segment (wave64: the 64 bits of a row word are the
+// 64 lanes' boxes).  The boxes are walked 64 at a time: the diagonal words of the 64 rows are loaded one per lane,
+// the serial keep / suppress decisions of the 64 boxes run on the wave-uniform removed word with one lane shuffle per
+// box, then the kept rows are OR-ed into the removed words of the later columns, one word per lane.  Same decisions
+// as dm_nms_reduce: a box is kept unless an earlier kept box suppresses it, and the walk stops at max_keep kept boxes.
+// keep[start + k] = the k-th kept box (index within the segment's sorted rows), counts[b] = number kept.
+__global__ __launch_bounds__(64) void nms_reduce_segmented_kernel(const unsigned long long* __restrict__ mask,
+                                                                  const long long* __restrict__ seg_tab, int max_keep,
+                                                                  int* __restrict__ keep, int* __restrict__ counts) {
+  extern __shared__ unsigned long long removed[];
+  const long long* sg = seg_tab + (size_t)blockIdx.x * 3;
+  const int M = (int)sg[1];
+  const int words = (M + 63) >> 6;
+  const unsigned long long* m = mask + sg[2];
+  int* kp = keep + sg[0];
+  const int lane = threadIdx.x;
+  for (int w = lane; w < words; w += 64) removed[w] = 0ull;
+  __syncthreads();
+  int n = 0;
+  bool stop = false;
+  for (int c = 0; c < words && !stop; ++c) {
+    const int i0 = c * 64;
+    const int rows = min(64, M - i0);
+    const unsigned long long diag = lane < rows ? m[(size_t)(i0 + lane) * words + c] : 0ull;
+    unsigned long long r = removed[c];
+    unsigned long long kept = 0ull;
+    for (int e = 0; e < rows; ++e) {
+      const unsigned long long de = __shfl(diag, e, 64);
+      if ((r >> e) & 1ull) continue;
+      if (max_keep >= 0 && n >= max_keep) { stop = true; break; }
+      if (lane == 0) kp[n] = i0 + e;
+      ++n;
+      kept |= 1ull << e;
+      r |= de;
+    }
+    if (stop) break;
+    for (int w = c + 1 + lane; w < words; w += 64) {
+      unsigned long long acc = removed[w];
+      unsigned long long k = kept;
+      while (k) {
+        const int e = __ffsll((long long)k) - 1;
+        k &= k - 1;
+        acc |= m[(size_t)(i0 + e) * words + w];
+      }
+      removed[w] = acc;
+    }
+    __syncthreads();
+  }
+  if (lane == 0) counts[blockIdx.x] = n;
 }
 
 }  // namespace
@@ -150,6 +224,36 @@ extern "C" int dm_nms_mask(const float* boxes_sorted, int M, float iou_threshold
   if (e != hipSuccess) return DM_ERR_LAUNCH;
   DM_LAUNCH(nms_mask_kernel, dim3(words, words), dim3(64), 0, (hipStream_t)stream, boxes_sorted, M, iou_threshold,
             offset ? 1.f : 0.f, mask, words);
+  return dm_check_launch();
+}
+
+extern "C" int dm_nms_mask_segmented(const float* boxes_sorted, int B, const long long* seg_tab, int max_words,
+                                     float iou_threshold, int offset, unsigned long long* mask, long long mask_words,
+                                     dm_stream_t stream) {
+  if (B < 0 || max_words < 0 || mask_words < 0 || max_words > 65535) return DM_ERR_INVALID_ARG;
+  if (B == 0 || max_words == 0) return DM_OK;
+  if (!boxes_sorted || !seg_tab || !mask || B > 65535) return DM_ERR_INVALID_ARG;
+  hipError_t e = hipMemsetAsync(mask, 0, (size_t)mask_words * sizeof(unsigned long long), (hipStream_t)stream);
+  if (e != hipSuccess) return DM_ERR_LAUNCH;
+  DM_LAUNCH(nms_mask_segmented_kernel, dim3(max_words, max_words, B), dim3(64), 0, (hipStream_t)stream, boxes_sorted,
+            seg_tab, iou_threshold, offset ? 1.f : 0.f, mask);
+  return dm_check_launch();
+}
+
+extern "C" int dm_nms_reduce_segmented(const unsigned long long* mask, int B, const long long* seg_tab, int max_words,
+                                       int max_keep, int* keep, int* counts, dm_stream_t stream) {
+  static bool lds_raised[DM_MAX_DEVICES] = {false};
+  if (B < 0 || max_words < 0) return DM_ERR_INVALID_ARG;
+  if (B == 0) return DM_OK;
+  if (!seg_tab || !counts || (max_words > 0 && (!mask || !keep))) return DM_ERR_INVALID_ARG;
+  const size_t lds = (size_t)max(max_words, 1) * sizeof(unsigned long long);
+  if (lds > 160 * 1024) return DM_ERR_UNSUPPORTED;
+  if (lds > 64 * 1024) {
+    const int rc = dm_ensure_lds_limit((const void*)nms_reduce_segmented_kernel, 160 * 1024, lds_raised);
+    if (rc != DM_OK) return rc;
+  }
+  DM_LAUNCH(nms_reduce_segmented_kernel, dim3(B), dim3(64), lds, (hipStream_t)stream, mask, seg_tab, max_keep, keep,
+            counts);
   return dm_check_launch();
 }
 

@@ -192,6 +192,82 @@ int rle_launch(const Src& src, int N, int img_h, int img_w, int* seg_scratch, in
   return dm_check_launch();
 }
 
+// ----- several images in one launch (dm_paste_rle_multi / dm_paste_masks_multi) -----
+// Detection n belongs to image det_img[n]; img_tab[b] = (img_h, img_w, first detection, canvas byte offset) of image b.
+// The pixel value is PasteSrc::at, the arithmetic of the one-image kernels; only the canvas size is per detection.
+struct MultiCanvas {
+  const int* det_img;
+  const long long* img_tab;
+  int B;
+  // false for a detection whose image index is out of range (it is then skipped: nothing written, no boundary)
+  __device__ __forceinline__ bool get(int n, int& h, int& w, long long& first, long long& off) const {
+    const int b = det_img[n];
+    if (b < 0 || b >= B) return false;
+    const long long* t = img_tab + (size_t)b * 4;
+    h = (int)t[0]; w = (int)t[1]; first = t[2]; off = t[3];
+    return h > 0 && w > 0 && first <= n;
+  }
+};
+
+template <class Src>
+__global__ __launch_bounds__(256) void rle_count_multi_kernel(Src src, MultiCanvas mc, int segs, int* __restrict__ seg_counts) {
+  __shared__ int red[4];
+  const int n = blockIdx.y, seg = blockIdx.x;
+  int h = 1, w = 0;
+  long long first = 0, off = 0;
+  const long long total = mc.get(n, h, w, first, off) ? (long long)h * w : 0;
+  const long long j0 = (long long)seg * kSeg + threadIdx.x * 16;
+  const unsigned bits = thread_boundaries(src, n, h, total, j0);
+  const int s = block_sum_256(__popc(bits), red);
+  if (threadIdx.x == 0) seg_counts[(size_t)n * segs + seg] = s;
+}
+
+template <class Src>
+__global__ __launch_bounds__(256) void rle_write_multi_kernel(Src src, MultiCanvas mc, int segs,
+                                                              const int* __restrict__ seg_offsets, int capacity,
+                                                              int* __restrict__ positions) {
+  __shared__ int wtot[4];
+  const int n = blockIdx.y, seg = blockIdx.x;
+  int h = 1, w = 0;
+  long long first = 0, off = 0;
+  const long long total = mc.get(n, h, w, first, off) ? (long long)h * w : 0;
+  const long long j0 = (long long)seg * kSeg + threadIdx.x * 16;
+  const unsigned bits = thread_boundaries(src, n, h, total, j0);
+  const int cnt = __popc(bits);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  int inc = cnt;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int t = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += t;
+  }
+  if (lane == 63) wtot[wv] = inc;
+  __syncthreads();
+  int pos = seg_offsets[(size_t)n * segs + seg] + inc - cnt;
+  for (int k = 0; k < wv; ++k) pos += wtot[k];
+  unsigned b = bits;
+  while (b) {
+    const int e = __ffs(b) - 1;
+    b &= b - 1;
+    if (pos < capacity) positions[pos] = (int)(j0 + e);
+    ++pos;
+  }
+}
+
+// row-major canvases packed image after image: detection n's [h, w] bitmap at off + (n - first) * h * w
+__global__ __launch_bounds__(256) void paste_masks_multi_kernel(PasteSrc src, MultiCanvas mc, uint8_t* __restrict__ out) {
+  const int n = blockIdx.y;
+  int h = 0, w = 0;
+  long long first = 0, off = 0;
+  if (!mc.get(n, h, w, first, off)) return;
+  const size_t total = (size_t)h * w;
+  uint8_t* o = out + off + (size_t)(n - first) * total;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int py = (int)(i / w), px = (int)(i - (size_t)py * w);
+    o[i] = (uint8_t)src.at(n, py, px);
+  }
+}
+
 }  // namespace
 
 extern "C" long long dm_rle_scratch_ints(int N, int img_h, int img_w) {
@@ -249,4 +325,47 @@ extern "C" long long dm_rle_string(const int* positions, int runs, long long tot
     prev1 = cnt;
   }
   return len <= cap ? len : -len;
+}
+
+extern "C" long long dm_rle_multi_scratch_ints(int N, long long max_pixels) {
+  if (N < 0 || max_pixels <= 0 || max_pixels > 0x7fffffffLL) return -1;
+  return (long long)N * ((max_pixels + kSeg - 1) / kSeg);
+}
+
+extern "C" int dm_paste_rle_multi(const float* masks, const float* boxes, int N, int mask_h, int mask_w, const int* det_img,
+                                  int B, const long long* img_tab, long long max_pixels, float threshold, int apply_sigmoid,
+                                  int* seg_scratch, int* mask_runs, int* mask_start, int* positions, int capacity,
+                                  dm_stream_t stream) {
+  if (N < 0 || B < 0 || mask_h <= 0 || mask_w <= 0 || capacity < 0) return DM_ERR_INVALID_ARG;
+  if (N == 0) return DM_OK;
+  if (B == 0 || max_pixels <= 0 || max_pixels > 0x7fffffffLL || N > 65535) return DM_ERR_INVALID_ARG;
+  if (!masks || !boxes || !det_img || !img_tab || !seg_scratch || !mask_runs || !mask_start || (!positions && capacity > 0))
+    return DM_ERR_INVALID_ARG;
+  PasteSrc src{masks, boxes, mask_h, mask_w, threshold, apply_sigmoid};
+  MultiCanvas mc{det_img, img_tab, B};
+  const int segs = (int)((max_pixels + kSeg - 1) / kSeg);
+  const hipStream_t st = (hipStream_t)stream;
+  DM_LAUNCH(rle_count_multi_kernel<PasteSrc>, dim3(segs, N), dim3(256), 0, st, src, mc, segs, seg_scratch);
+  int rc = dm_check_launch();
+  if (rc != DM_OK) return rc;
+  DM_LAUNCH(rle_scan_kernel, dim3(1), dim3(1024), 0, st, seg_scratch, N * segs, N, segs, mask_runs, mask_start);
+  rc = dm_check_launch();
+  if (rc != DM_OK) return rc;
+  DM_LAUNCH(rle_write_multi_kernel<PasteSrc>, dim3(segs, N), dim3(256), 0, st, src, mc, segs, seg_scratch, capacity,
+            positions);
+  return dm_check_launch();
+}
+
+extern "C" int dm_paste_masks_multi(const float* masks, const float* boxes, int N, int mask_h, int mask_w, const int* det_img,
+                                    int B, const long long* img_tab, long long max_pixels, float threshold,
+                                    int apply_sigmoid, uint8_t* out, dm_stream_t stream) {
+  if (N < 0 || B < 0 || mask_h <= 0 || mask_w <= 0) return DM_ERR_INVALID_ARG;
+  if (N == 0) return DM_OK;
+  if (B == 0 || max_pixels <= 0 || N > 65535) return DM_ERR_INVALID_ARG;
+  if (!masks || !boxes || !det_img || !img_tab || !out) return DM_ERR_INVALID_ARG;
+  PasteSrc src{masks, boxes, mask_h, mask_w, threshold, apply_sigmoid};
+  MultiCanvas mc{det_img, img_tab, B};
+  const int bx = (int)min((max_pixels + 255) / 256, 1024LL);
+  DM_LAUNCH(paste_masks_multi_kernel, dim3(bx, N), dim3(256), 0, (hipStream_t)stream, src, mc, out);
+  return dm_check_launch();
 }

@@ -22,12 +22,17 @@ from .precision import get_conv_precision
 # count above 16: 0.61 / 0.79 / 0.90 / 1.21 / 1.39 / 1.93 ms at 16 / 24 / 32 / 48 / 64 / 100 detections, so 33 detections
 # in the 48-bucket cost 1.21 ms instead of the 64-bucket's 1.39)
 BUCKETS = (16, 24, 32, 48, 64, 80, 100)
+# buckets of the TOTAL RoI count of a batched call (DynaMaskRoIHead.batch_simple_test_mask_logits, B >= 2 images): the
+# one-image buckets and six above 100 for two to four images of up to 100 detections; larger totals run eagerly.  A
+# batched graph is keyed on B and the FPN map shapes as well, apart from the one-image graphs.
+BATCH_BUCKETS = BUCKETS + (128, 160, 200, 256, 320, 400)
 
 
 class GraphedMaskLogits:
-    def __init__(self, roi_head, buckets=BUCKETS, max_graphs=16):
+    def __init__(self, roi_head, buckets=BUCKETS, max_graphs=16, batch_buckets=BATCH_BUCKETS):
         self.head = roi_head
         self.buckets = tuple(sorted(buckets))
+        self.batch_buckets = tuple(sorted(batch_buckets))
         self.max_graphs = max_graphs
         self._graphs = {}          # key -> (graph, rois_static, labels_static, out_static, [filled rows, column 0 dirty])
         self.captures = 0
@@ -122,6 +127,28 @@ class GraphedMaskLogits:
         if n < filled[0]:
             rois[n:filled[0]].zero_()          # empty boxes: zero rows (rows past `filled` are zero already)
         filled[0], filled[1] = n, boxes is None
+        labels[:n].copy_(det_labels)
+        g.replay()
+        self.replays += 1
+        return out[:n]
+
+    def batched(self, x, mask_rois, det_labels, num_images):
+        """The batched form: ``mask_rois`` [n, 5] of ``num_images`` images (batch column = image index into ``x``),
+        ``det_labels`` [n] -> merged logits [n, 1, 112, 112] replayed from the graph of the smallest batch bucket that
+        holds n (None: n is above the largest).  Keyed on ('batch', num_images) + the one-image key, so a graph is
+        never replayed for another image count, map shape or another bucket list."""
+        n = mask_rois.shape[0]
+        bucket = next((b for b in self.batch_buckets if n <= b), None)
+        if bucket is None or not mask_rois.is_cuda:
+            return None
+        x = list(x)
+        key = ('batch', int(num_images)) + self._key(bucket, x)
+        entry = self._graphs.get(key) or self._capture(key, bucket, x)
+        g, rois, labels, out, filled = entry
+        rois[:n].copy_(mask_rois)
+        if n < filled[0]:
+            rois[n:filled[0]].zero_()          # empty boxes: zero rows
+        filled[0], filled[1] = n, True
         labels[:n].copy_(det_labels)
         g.replay()
         self.replays += 1

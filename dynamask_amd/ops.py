@@ -142,10 +142,11 @@ def roi_align_backward(grad_out, feat_shapes, rois, output_size, spatial_scales,
 
 
 # --------------------------------------------------------------- RLE (after the path, 8f rank 2)
-def _rle_collect(N, img_h, img_w, runs, start, positions, launch, capacity):
-    """Shared tail of the two encoders: read the run totals, re-run once with a larger
+def _rle_collect(N, img_h, img_w, runs, start, positions, launch, capacity, sizes=None):
+    """Shared tail of the encoders: read the run totals, re-run once with a larger
     buffer if the boundaries did not fit, copy exactly the used part of `positions`, build
-    the COCO dicts ({'size': [h, w], 'counts': bytes}, what pycocotools' encode returns)."""
+    the COCO dicts ({'size': [h, w], 'counts': bytes}, what pycocotools' encode returns).
+    ``sizes``: per-mask (h, w) canvases (paste_rle_multi) instead of one img_h x img_w."""
     import ctypes as C
     start_h = start.cpu()                        # synchronises the stream
     total = int(start_h[N])
@@ -168,10 +169,11 @@ def _rle_collect(N, img_h, img_w, runs, start, positions, launch, capacity):
         if need > cap:
             cap = need
             buf = C.create_string_buffer(cap)
-        ln = L.dm_rle_string(C.c_void_p(base + 4 * s0), s1 - s0, img_h * img_w, buf, cap)
+        h, w = (img_h, img_w) if sizes is None else sizes[n]
+        ln = L.dm_rle_string(C.c_void_p(base + 4 * s0), s1 - s0, h * w, buf, cap)
         if ln < 0:
             raise RuntimeError('dm_rle_string: buffer too small')
-        out.append({'size': [int(img_h), int(img_w)], 'counts': buf.raw[:ln]})
+        out.append({'size': [int(h), int(w)], 'counts': buf.raw[:ln]})
     return out
 
 
@@ -220,6 +222,89 @@ def paste_rle(masks, boxes, img_h, img_w, threshold=0.5, apply_sigmoid=False):
     positions = torch.empty((capacity,), device=dev, dtype=torch.int32)
     launch(positions, capacity)
     return _rle_collect(N, img_h, img_w, runs, start, positions, launch, capacity)
+
+
+def _upload(vals, dtype, device):
+    """A small host table -> device without a host wait: pinned staging buffer, copy ordered on the current stream."""
+    return torch.tensor(vals, dtype=dtype).pin_memory().to(device, non_blocking=True)
+
+
+def _multi_canvas_table(det_counts, sizes, device):
+    """Detections of B images, image after image -> (det_img int32 [N], img_tab int64 [B, 4] of (h, w, first detection,
+    byte offset of the first canvas) on the device, total canvas bytes, the largest canvas of an image with detections,
+    per-detection (h, w))."""
+    assert len(det_counts) == len(sizes)
+    rows, det_img, det_sizes = [], [], []
+    first = off = max_pixels = 0
+    for b, (n, (h, w)) in enumerate(zip(det_counts, sizes)):
+        h, w, n = int(h), int(w), int(n)
+        if n > 0 and (h <= 0 or w <= 0):
+            raise ValueError(f'image {b}: canvas {h} x {w} holds no pixel')
+        rows.append([h, w, first, off])
+        det_img += [b] * n
+        det_sizes += [(h, w)] * n
+        first += n
+        off += n * h * w
+        if n > 0:
+            max_pixels = max(max_pixels, h * w)
+    return (_upload(det_img, torch.int32, device), _upload(rows, torch.int64, device), off, max_pixels, det_sizes)
+
+
+def paste_masks_multi(masks, boxes, det_counts, sizes, threshold=0.5, apply_sigmoid=False):
+    """``paste_masks`` for the detections of several images in one launch.  masks [N, 1, h, w] or [N, h, w], boxes
+    [N, 4] in canvas pixels, image after image (``det_counts[b]`` detections of image b, canvas ``sizes[b]`` = (h, w)).
+    Returns (packed uint8 buffer of all bitmaps, per-detection byte offsets, per-detection (h, w)): detection n is
+    ``buf[off[n]:off[n] + h * w].view(h, w)``, the bits ``paste_masks`` gives it on its own image."""
+    _chk(masks, 'masks')
+    _chk(boxes, 'boxes')
+    N = masks.shape[0]
+    assert N == sum(int(n) for n in det_counts) and boxes.shape[0] == N
+    dev = masks.device
+    det_img, tab, total, max_pixels, det_sizes = _multi_canvas_table(det_counts, sizes, dev)
+    out = torch.empty((max(total, 1),), device=dev, dtype=torch.uint8)
+    offs, o = [], 0
+    for h, w in det_sizes:
+        offs.append(o)
+        o += h * w
+    if N > 0:
+        mh, mw = masks.shape[-2:]
+        check(lib().dm_paste_masks_multi(_p(masks), _p(boxes), N, mh, mw, _p(det_img), len(det_counts), _p(tab),
+                                         max_pixels, float(threshold), 1 if apply_sigmoid else 0, _p(out), _stream()),
+              'dm_paste_masks_multi')
+    return out[:total], offs, det_sizes
+
+
+def paste_rle_multi(masks, boxes, det_counts, sizes, threshold=0.5, apply_sigmoid=False, capacity=None):
+    """``paste_rle`` for the detections of several images in one launch (arguments as ``paste_masks_multi``): one
+    list of COCO RLE dicts, detection after detection, each with its own image's size.  One run-boundary buffer for all
+    detections, one device -> host copy; ``capacity`` (boundaries; default 4 (h + w) per detection) is the first
+    buffer's size, re-run once with the exact size if it was short (``_rle_collect``)."""
+    _chk(masks, 'masks')
+    _chk(boxes, 'boxes')
+    N = masks.shape[0]
+    assert N == sum(int(n) for n in det_counts) and boxes.shape[0] == N
+    if N == 0:
+        return []
+    mh, mw = masks.shape[-2:]
+    dev = masks.device
+    det_img, tab, _, max_pixels, det_sizes = _multi_canvas_table(det_counts, sizes, dev)
+    ns = lib().dm_rle_multi_scratch_ints(N, max_pixels)
+    if ns < 0:
+        raise ValueError(f'canvas of {max_pixels} pixels is too large for the RLE encoder')
+    scratch = torch.empty((ns,), device=dev, dtype=torch.int32)
+    runs = torch.empty((N,), device=dev, dtype=torch.int32)
+    start = torch.empty((N + 1,), device=dev, dtype=torch.int32)
+    if capacity is None:
+        capacity = max(4096, sum(4 * (h + w) for h, w in det_sizes))
+    B = len(det_counts)
+
+    def launch(positions, cap):
+        check(lib().dm_paste_rle_multi(_p(masks), _p(boxes), N, mh, mw, _p(det_img), B, _p(tab), max_pixels,
+                                       float(threshold), 1 if apply_sigmoid else 0, _p(scratch), _p(runs), _p(start),
+                                       _p(positions), cap, _stream()), 'dm_paste_rle_multi')
+    positions = torch.empty((max(capacity, 1),), device=dev, dtype=torch.int32)
+    launch(positions, capacity)
+    return _rle_collect(N, 0, 0, runs, start, positions, launch, capacity, sizes=det_sizes)
 
 
 # --------------------------------------------------------------- bbox branch (8f rank 4)
@@ -286,6 +371,43 @@ def nms(boxes, scores, iou_threshold, offset=0, max_num=-1):
     keep = order[keep_sorted]
     dets = torch.cat([boxes[keep], scores[keep][:, None]], 1)
     return dets, keep
+
+
+NMS_REDUCE_MAX_WORDS = 20480      # dm_nms_reduce_segmented keeps a segment's removed bits in LDS (160 KB)
+
+
+def nms_segmented(boxes_sorted, counts, iou_threshold, offset=0, max_num=-1):
+    """``nms`` over B segments at once, without a host wait.  boxes_sorted [sum M_b, 4]: the segments one after the
+    other, each already score-sorted on its own; ``counts`` = host list of M_b.  The suppression bits are computed
+    within a segment only (block-diagonal, one [M_b, ceil(M_b / 64)] matrix each) and the greedy pass runs on the
+    device, one wave per segment, stopping at ``max_num`` kept boxes (> 0) per segment.  Returns (keep int32 [sum M_b]:
+    segment b's kept rows, ascending in its sorted order, at keep[start_b : start_b + kept_b]; kept int32 [B]), both
+    on the device."""
+    _chk(boxes_sorted, 'boxes')
+    counts = [int(m) for m in counts]
+    B = len(counts)
+    dev = boxes_sorted.device
+    assert boxes_sorted.shape == (sum(counts), 4)
+    keep = torch.empty((max(sum(counts), 1),), device=dev, dtype=torch.int32)
+    kept = torch.zeros((B,), device=dev, dtype=torch.int32)
+    if B == 0:
+        return keep[:0], kept
+    rows, start, off = [], 0, 0
+    for m in counts:
+        rows.append([start, m, off])
+        start += m
+        off += m * ((m + 63) // 64)
+    max_words = max((m + 63) // 64 for m in counts)
+    if max_words > NMS_REDUCE_MAX_WORDS:
+        raise ValueError(f'{max(counts)} boxes in one segment: the device NMS pass holds at most '
+                         f'{64 * NMS_REDUCE_MAX_WORDS}')
+    tab = _upload(rows, torch.int64, dev)
+    mask = torch.empty((max(off, 1),), device=dev, dtype=torch.int64)
+    check(lib().dm_nms_mask_segmented(_p(boxes_sorted), B, _p(tab), max_words, float(iou_threshold), int(offset),
+                                      _p(mask), off, _stream()), 'dm_nms_mask_segmented')
+    check(lib().dm_nms_reduce_segmented(_p(mask), B, _p(tab), max_words, int(max_num) if max_num > 0 else -1, _p(keep),
+                                        _p(kept), _stream()), 'dm_nms_reduce_segmented')
+    return keep[:sum(counts)], kept
 
 
 # --------------------------------------------------------------- convolutions

@@ -18,6 +18,14 @@ from .mask_heads import _Conv
 from .registry import HEADS, build_head, build_roi_extractor
 
 
+def _bbox2result_host(bboxes, labels, num_classes):
+    """bbox_heads.bbox2result on host arrays already copied (the batched call copies all images' detections at once)."""
+    import numpy as np
+    if bboxes.shape[0] == 0:
+        return [np.zeros((0, 5), dtype=np.float32) for _ in range(num_classes)]
+    return [bboxes[labels == i, :] for i in range(num_classes)]
+
+
 def bbox2roi(bbox_list):
     """mmdet/core/bbox/transforms.py:54-73."""
     rois_list = []
@@ -506,11 +514,13 @@ class DynaMaskRoIHead(nn.Module):
         return (len(h.stages) == 3 and not h.pre_upsample_last_stage
                 and list(h.stage_sup_size) == [h.stage_sup_size[0] * k for k in (1, 2, 4, 8)])
 
-    def enable_inference_graphs(self, on=True, buckets=None):
+    def enable_inference_graphs(self, on=True, buckets=None, batch_buckets=None):
         """Replay ``simple_test_mask_logits`` as a HIP graph per bucket of detection counts (16 / 24 / 32 / 48 / 64 / 80 / 100 by
-        default; see graphs.py for what a graph is tied to).  Off by default: the eager path is the reference one."""
-        from .graphs import BUCKETS, GraphedMaskLogits
-        self._mask_graphs = GraphedMaskLogits(self, buckets or BUCKETS) if on else None
+        default; see graphs.py for what a graph is tied to).  Off by default: the eager path is the reference one.
+        ``batch_buckets``: the buckets of the total RoI count of ``batch_simple_test_mask_logits`` (graphs.BATCH_BUCKETS)."""
+        from .graphs import BATCH_BUCKETS, BUCKETS, GraphedMaskLogits
+        self._mask_graphs = GraphedMaskLogits(self, buckets or BUCKETS,
+                                              batch_buckets=batch_buckets or BATCH_BUCKETS) if on else None
         return self._mask_graphs
 
     # ------------------------------------------------------------ bbox branch (inference)
@@ -538,6 +548,214 @@ class DynaMaskRoIHead(nn.Module):
             return bbox_results
         segm_results = self.simple_test_mask(x, img_metas, det_bboxes, det_labels, rescale=rescale, encode=encode)
         return bbox_results, segm_results
+
+    # ------------------------------------------------------------ batched inference: B images per call
+    # Each method gives, per image, what its one-image counterpart gives for that image alone; the B images share the
+    # launches: one bbox branch over all proposals, one segmented NMS, one mask chain over all detections, one paste.
+    _META_KEYS = ('img_shape', 'ori_shape', 'scale_factor')
+
+    @classmethod
+    def _check_batch(cls, img_metas, _name='img_metas', **lists):
+        """Argument checks of the batch_* methods (before any GPU work): a non-empty per-image list ``img_metas`` (named
+        ``_name`` in the message) and every other per-image list of the same length B."""
+        if not isinstance(img_metas, (list, tuple)) or len(img_metas) == 0:
+            raise ValueError(f'{_name}: a non-empty list with one entry per image')
+        B = len(img_metas)
+        for name, v in lists.items():
+            if v is not None and len(v) != B:
+                raise ValueError(f'{name}: {len(v)} entries for {B} images')
+        return B
+
+    @classmethod
+    def _check_metas(cls, img_metas, keys):
+        for i, m in enumerate(img_metas):
+            missing = [k for k in keys if k not in m]
+            if missing:
+                raise ValueError(f'img_metas[{i}] lacks {missing}')
+
+    @staticmethod
+    def _batch_scale_factor(scale_factor, device):
+        """simple_test_mask's ``torch.from_numpy(scale_factor).to(device)`` (same dtype, same values) through a pinned
+        buffer: no host wait per image."""
+        if isinstance(scale_factor, float):
+            return scale_factor
+        import numpy as np
+        return torch.from_numpy(np.ascontiguousarray(scale_factor)).pin_memory().to(device, non_blocking=True)
+
+    def _batch_mask_boxes(self, det_bboxes_list, img_metas, rescale):
+        """Per image: (boxes the mask chain reads, scale factor as simple_test_mask derives them)."""
+        boxes, sfs = [], []
+        for det, meta in zip(det_bboxes_list, img_metas):
+            sf = meta['scale_factor']
+            if rescale and det.shape[0] > 0:
+                sf = self._batch_scale_factor(sf, det.device)
+            boxes.append(det[:, :4] * sf if rescale and det.shape[0] > 0 else det)
+            sfs.append(sf)
+        return boxes, sfs
+
+    def batch_simple_test_mask_logits(self, x, det_bboxes_list, det_labels_list, scale_factors=None, rescale=False):
+        """``simple_test_mask_logits`` of B images as ONE mask chain: the [sum N, 5] RoI rows of all images (batch column
+        = image index into the B-image FPN tuple ``x``) -> the merged 112 x 112 logits [sum N, 1, 112, 112] and the row
+        offsets [B + 1] (image b: rows offsets[b]:offsets[b + 1]).  ``rescale``: image b's boxes are multiplied by
+        ``scale_factors[b]`` first.  B = 1 is ``simple_test_mask_logits`` itself.  With ``enable_inference_graphs`` the
+        call replays a graph bucketed on the total RoI count (graphs.BATCH_BUCKETS; larger totals run eagerly)."""
+        B = self._check_batch(det_bboxes_list, 'det_bboxes_list', det_labels_list=det_labels_list, scale_factors=scale_factors)
+        if rescale and scale_factors is None:
+            raise ValueError('rescale=True needs scale_factors')
+        counts = [int(d.shape[0]) for d in det_bboxes_list]
+        offsets = [0]
+        for c in counts:
+            offsets.append(offsets[-1] + c)
+        boxes = []
+        for b, det in enumerate(det_bboxes_list):
+            if rescale and det.shape[0] > 0:
+                det = det[:, :4] * self._batch_scale_factor(scale_factors[b], det.device)
+            boxes.append(det)
+        if offsets[-1] == 0:
+            return det_bboxes_list[0].new_zeros((0, 1, 112, 112)), offsets
+        if B == 1:
+            return self.simple_test_mask_logits(x, boxes[0], det_labels_list[0]), offsets
+        mask_rois = bbox2roi(boxes).contiguous()
+        labels = torch.cat(list(det_labels_list)).contiguous()
+        graphs = getattr(self, '_mask_graphs', None)
+        if graphs is not None and not torch.is_grad_enabled():
+            merged = graphs.batched(x, mask_rois, labels, B)
+            if merged is not None:
+                return merged, offsets
+        return self._merged_logits(x, mask_rois, labels), offsets
+
+    def _batch_mask_preds(self, x, boxes_list, labels_list, labels):
+        """The mask logits of all detections, one row per detection, and whether the paste applies the sigmoid."""
+        merged, _ = self.batch_simple_test_mask_logits(x, boxes_list, labels_list)
+        if merged.shape[1] > 1:
+            merged = merged[range(len(merged)), labels][:, None]
+        return merged.contiguous(), True
+
+    def _segm_num_classes(self):
+        return self.mask_head.stage_num_classes[0]
+
+    @torch.no_grad()
+    def batch_simple_test_mask(self, x, img_metas, det_bboxes_list, det_labels_list, rescale=False, encode=False,
+                               _labels_host=None):
+        """``simple_test_mask`` of B images: per image the per-class lists of (h, w) bool masks (``encode``: COCO RLE
+        dicts) of its detections, on its own canvas (``ori_shape``, ``scale_factor``).  One mask chain, one paste launch
+        (dm_paste_masks_multi / dm_paste_rle_multi) and one device -> host copy for all images."""
+        from .mask_heads import _paste_geometry
+        import numpy as np
+        B = self._check_batch(img_metas, det_bboxes_list=det_bboxes_list, det_labels_list=det_labels_list)
+        self._check_metas(img_metas, ('ori_shape', 'scale_factor'))
+        num_classes = self._segm_num_classes()
+        results = [[[] for _ in range(num_classes)] for _ in range(B)]
+        counts = [int(d.shape[0]) for d in det_bboxes_list]
+        if sum(counts) == 0:
+            return results
+        threshold = self.test_cfg.mask_thr_binary
+        if threshold < 0:
+            raise NotImplementedError('visualisation mode (mask_thr_binary < 0) is not on the path')
+        boxes, sfs = self._batch_mask_boxes(det_bboxes_list, img_metas, rescale)
+        labels = torch.cat(list(det_labels_list))
+        preds, apply_sigmoid = self._batch_mask_preds(x, boxes, det_labels_list, labels)
+        canvas_boxes, sizes = [], []
+        for b in range(B):
+            if counts[b] == 0:
+                sizes.append((1, 1))
+                continue
+            cb, h, w = _paste_geometry(boxes[b], img_metas[b]['ori_shape'], sfs[b], rescale)
+            canvas_boxes.append(cb)
+            sizes.append((h, w))
+        canvas_boxes = torch.cat(canvas_boxes).contiguous()
+        if encode:
+            segs = ops.paste_rle_multi(preds, canvas_boxes, counts, sizes, threshold, apply_sigmoid=apply_sigmoid)
+            labels_h = _labels_host if _labels_host is not None else labels.cpu().tolist()
+        else:
+            buf, offs, det_sizes = ops.paste_masks_multi(preds, canvas_boxes, counts, sizes, threshold,
+                                                         apply_sigmoid=apply_sigmoid)
+            host = torch.empty(buf.shape, dtype=torch.uint8, pin_memory=True)
+            host.copy_(buf, non_blocking=True)
+            lab_h = None
+            if _labels_host is None:
+                lab_h = torch.empty(labels.shape, dtype=labels.dtype, pin_memory=True)
+                lab_h.copy_(labels, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            labels_h = _labels_host if _labels_host is not None else lab_h.tolist()
+            flat = host.numpy().view(np.bool_)
+            segs = [flat[o:o + h * w].reshape(h, w) for o, (h, w) in zip(offs, det_sizes)]
+        start = 0
+        for b in range(B):
+            for j in range(start, start + counts[b]):
+                results[b][labels_h[j]].append(segs[j])
+            start += counts[b]
+        return results
+
+    @torch.no_grad()
+    def batch_simple_test_bboxes(self, x, img_metas, proposals, rcnn_test_cfg, rescale=False):
+        """``simple_test_bboxes`` of B images -> list of B (dets [k, 5], labels [k]): one bbox branch over the
+        proposals of all images, per-image decode (its own ``img_shape`` clip and ``scale_factor``), one segmented NMS
+        (bbox_heads.multiclass_nms_batch)."""
+        from .bbox_heads import multiclass_nms_batch
+        B = self._check_batch(img_metas, proposals=proposals)
+        self._check_metas(img_metas, ('img_shape', 'scale_factor'))
+        rows = [int(p.shape[0]) for p in proposals]
+        rois = bbox2roi(proposals).contiguous()
+        if rois.shape[0] == 0:
+            ref = proposals[0]
+            return [(ref.new_zeros((0, 5)), ref.new_zeros((0,), dtype=torch.long)) for _ in range(B)]
+        res = self._bbox_forward(x, rois)
+        cls_score, bbox_pred = res['cls_score'], res['bbox_pred']
+        bl, sl, r0 = [], [], 0
+        for b in range(B):
+            r1 = r0 + rows[b]
+            if r1 == r0:
+                bl.append(rois.new_zeros((0, 4)))
+                sl.append(rois.new_zeros((0, self.bbox_head.num_classes + 1)))
+            else:
+                bboxes, scores = self.bbox_head.get_bboxes(
+                    rois[r0:r1], None if cls_score is None else cls_score[r0:r1],
+                    None if bbox_pred is None else bbox_pred[r0:r1], img_metas[b]['img_shape'],
+                    img_metas[b]['scale_factor'], rescale=rescale, cfg=None)
+                bl.append(bboxes)
+                sl.append(scores)
+            r0 = r1
+        cfg = rcnn_test_cfg
+        return multiclass_nms_batch(bl, sl, cfg.score_thr, cfg.nms, cfg.max_per_img)
+
+    @torch.no_grad()
+    def batch_simple_test(self, x, proposal_list, img_metas, rescale=False, encode=False):
+        """``simple_test`` of B images in one call (the contract of later mmdet releases): ``x`` the FPN tuple with
+        batch dimension B, ``proposal_list`` / ``img_metas`` one entry per image -> list of B ``(bbox_results,
+        segm_results)``, each what ``simple_test`` returns for that image alone (just ``bbox_results`` without a mask
+        branch).  Host waits do not grow with B: the detections of all images cross to the host in one copy."""
+        B = self._check_batch(img_metas, proposal_list=proposal_list)
+        self._check_metas(img_metas, self._META_KEYS)
+        for i, f in enumerate(x):
+            if f.shape[0] != B:
+                raise ValueError(f'x[{i}] has batch dimension {f.shape[0]} for {B} images')
+        dets = self.batch_simple_test_bboxes(x, img_metas, proposal_list, self.test_cfg, rescale=rescale)
+        counts = [int(d.shape[0]) for d, _ in dets]
+        num_classes = self.bbox_head.num_classes
+        if sum(counts) == 0:
+            import numpy as np
+            bbox_results = [[np.zeros((0, 5), dtype=np.float32) for _ in range(num_classes)] for _ in range(B)]
+            labels_h = []
+        else:
+            d_all = torch.cat([d for d, _ in dets])
+            l_all = torch.cat([l for _, l in dets])
+            d_h = torch.empty(d_all.shape, dtype=d_all.dtype, pin_memory=True)
+            l_h = torch.empty(l_all.shape, dtype=l_all.dtype, pin_memory=True)
+            d_h.copy_(d_all, non_blocking=True)
+            l_h.copy_(l_all, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            d_np, l_np = d_h.numpy(), l_h.numpy()
+            labels_h = l_np.tolist()
+            bbox_results, start = [], 0
+            for c in counts:
+                bbox_results.append(_bbox2result_host(d_np[start:start + c], l_np[start:start + c], num_classes))
+                start += c
+        if not self.with_mask:
+            return bbox_results
+        segm_results = self.batch_simple_test_mask(x, img_metas, [d for d, _ in dets], [l for _, l in dets],
+                                                   rescale=rescale, encode=encode, _labels_host=labels_h)
+        return list(zip(bbox_results, segm_results))
 
     # ------------------------------------------------------------ dynamic inference
     @torch.no_grad()
@@ -711,6 +929,33 @@ class StandardRoIHead(DynaMaskRoIHead):
             if mask_results['loss_mask'] is not None:
                 losses.update(mask_results['loss_mask'])
         return losses
+
+    def batch_simple_test_mask_logits(self, x, det_bboxes_list, det_labels_list, scale_factors=None, rescale=False):
+        """The FCNMaskHead logits [sum N, classes, S, S] of B images' detections from ONE ``_mask_forward``, and the row
+        offsets [B + 1] (``rescale``: boxes times ``scale_factors[b]`` first)."""
+        self._check_batch(det_bboxes_list, 'det_bboxes_list', det_labels_list=det_labels_list, scale_factors=scale_factors)
+        if rescale and scale_factors is None:
+            raise ValueError('rescale=True needs scale_factors')
+        offsets = [0]
+        boxes = []
+        for b, det in enumerate(det_bboxes_list):
+            offsets.append(offsets[-1] + int(det.shape[0]))
+            if rescale and det.shape[0] > 0:
+                det = det[:, :4] * self._batch_scale_factor(scale_factors[b], det.device)
+            boxes.append(det)
+        mask_rois = bbox2roi(boxes).contiguous()
+        if mask_rois.shape[0] == 0:
+            h = self.mask_head
+            return mask_rois.new_zeros((0, h.num_classes, 1, 1)), offsets
+        with torch.no_grad():
+            return self._mask_forward(x, mask_rois)['mask_pred'], offsets
+
+    def _batch_mask_preds(self, x, boxes_list, labels_list, labels):
+        mask_pred, _ = self.batch_simple_test_mask_logits(x, boxes_list, labels_list)
+        return self.mask_head._selected(mask_pred, torch.cat([b[:, :4] for b in boxes_list]), labels)
+
+    def _segm_num_classes(self):
+        return self.mask_head.num_classes
 
     def simple_test_mask(self, x, img_metas, det_bboxes, det_labels, rescale=False, encode=False):
         """test_mixins.py:151-176 -> ``cls_segms`` of ``FCNMaskHead.get_seg_masks`` (``encode``: COCO RLE dicts instead of

@@ -55,7 +55,7 @@ extern "C" {
 typedef void* dm_stream_t; /* hipStream_t */
 
 const char* dm_error_string(int code);
-/* ABI version: bumped whenever a signature or the meaning of an argument changes (8: flag bit 3 of dm_conv2d_fwd; 9: RoI assignment / bbox training entry points; 10: dm_detail_target takes the fuse weights from device memory; 11: FCNMaskHead upsample backward; 12: dm_fc_fwd takes a scratch slab, deterministic split-K; 13: dm_deform_coord_grad / dm_deform_col2im, dm_conv2d_fwd_masked, dm_scale, dm_polygon_mask_targets, dm_ignore_columns, dm_upsample2x_bilinear_bwd overwrites; 14: dm_random_sample, dm_bn_relu_maxpool_argmax, the *_fx deterministic accumulators + dm_fx_to_float, dm_mask_loss_fwd_bwd takes a scratch, dm_conv2d_wgrad takes the bias gradient, dm_conv_pack_weight_batch, dm_mask_loss_stage; 15: dm_class_logits_up2x_fwd; 16: dm_conv2d_wgrad_slab / dm_conv2d_wgrad_scratch_floats; 17: dm_class_logits_bwd_slab / dm_class_logits_bwd_scratch_floats; 18: dm_reload_env_knobs, dm_roi_align_fwd_ws / dm_roi_align_workspace_bytes, dm_conv_pack_weight_split / dm_conv_packed_floats_split and flag bits 4, 5 of dm_conv2d_fwd; 19: dm_dcn_bwd_data_fused and its pack; 20: dm_conv2d_fwd_ws / dm_conv2d_splitk_floats; 21: dm_deform_conv_fwd_ws / dm_deform_conv_splitk_floats; 22: the bf16-split layouts (dm_conv_pack_weight_split, dm_conv_packed_floats_split, flag bits 4 / 5 of dm_conv2d_fwd) and the one-kernel DCN data gradient (dm_dcn_bwd_*) REMOVED -- measured, never the parity path, see docs/HISTORY.md; 23: dm_bn_stats takes mean_shift, dm_roi_align_bwd takes the gather form for 16 < P <= 64; 24: dm_build_info; 25: dm_boundary_merge_chain, dm_stage_head_fwd; 26: dm_conv1x1_group_fwd; 27: dm_deform_conv_tout_fwd / dm_deform_conv_tout_supported; 28: the opt-in bf16x3 mode -- dm_conv_pack_weight_bf16x3 / dm_conv_packed_floats_bf16x3 and flag bit 4 of dm_conv2d_fwd, dm_conv2d_fwd_ws and dm_conv1x1_group_fwd; dm_deconv_pack_weight_bf16x3 and flag bit 4 of dm_deconv2x2_fwd). */
+/* ABI version: bumped whenever a signature or the meaning of an argument changes (8: flag bit 3 of dm_conv2d_fwd; 9: RoI assignment / bbox training entry points; 10: dm_detail_target takes the fuse weights from device memory; 11: FCNMaskHead upsample backward; 12: dm_fc_fwd takes a scratch slab, deterministic split-K; 13: dm_deform_coord_grad / dm_deform_col2im, dm_conv2d_fwd_masked, dm_scale, dm_polygon_mask_targets, dm_ignore_columns, dm_upsample2x_bilinear_bwd overwrites; 14: dm_random_sample, dm_bn_relu_maxpool_argmax, the *_fx deterministic accumulators + dm_fx_to_float, dm_mask_loss_fwd_bwd takes a scratch, dm_conv2d_wgrad takes the bias gradient, dm_conv_pack_weight_batch, dm_mask_loss_stage; 15: dm_class_logits_up2x_fwd; 16: dm_conv2d_wgrad_slab / dm_conv2d_wgrad_scratch_floats; 17: dm_class_logits_bwd_slab / dm_class_logits_bwd_scratch_floats; 18: dm_reload_env_knobs, dm_roi_align_fwd_ws / dm_roi_align_workspace_bytes, dm_conv_pack_weight_split / dm_conv_packed_floats_split and flag bits 4, 5 of dm_conv2d_fwd; 19: dm_dcn_bwd_data_fused and its pack; 20: dm_conv2d_fwd_ws / dm_conv2d_splitk_floats; 21: dm_deform_conv_fwd_ws / dm_deform_conv_splitk_floats; 22: the bf16-split layouts (dm_conv_pack_weight_split, dm_conv_packed_floats_split, flag bits 4 / 5 of dm_conv2d_fwd) and the one-kernel DCN data gradient (dm_dcn_bwd_*) REMOVED -- measured, never the parity path, see docs/HISTORY.md; 23: dm_bn_stats takes mean_shift, dm_roi_align_bwd takes the gather form for 16 < P <= 64; 24: dm_build_info; 25: dm_boundary_merge_chain, dm_stage_head_fwd; 26: dm_conv1x1_group_fwd; 27: dm_deform_conv_tout_fwd / dm_deform_conv_tout_supported; 28: the opt-in bf16x3 mode -- dm_conv_pack_weight_bf16x3 / dm_conv_packed_floats_bf16x3 and flag bit 4 of dm_conv2d_fwd, dm_conv2d_fwd_ws and dm_conv1x1_group_fwd; dm_deconv_pack_weight_bf16x3 and flag bit 4 of dm_deconv2x2_fwd).  Entry points ADDED without a signature or meaning change leave the number as it is (the loader resolves every symbol of _lib.SIGNATURES by name, so an older library fails at load): the multi-image post-processing dm_nms_mask_segmented / dm_nms_reduce_segmented, dm_paste_masks_multi, dm_paste_rle_multi / dm_rle_multi_scratch_ints. */
 int dm_abi_version(void);
 /* "libdynamask_hip abi=N arch=gfx950 compiler=<clang version> flags=<the product-wide flags of dynamask_amd/build.py>"
  * (static storage).  The library must be compiled WITHOUT packed fp32 instructions (flag "-packed-fp32-ops", see
@@ -476,6 +476,24 @@ int dm_paste_rle(const float* masks, const float* boxes, int N, int mask_h, int 
                  int* positions, int capacity, dm_stream_t stream);
 long long dm_rle_string(const int* positions, int runs, long long total_pixels, char* out, long long cap);
 
+/* (added to ABI 28) K18 / K19 for the detections of SEVERAL images in one launch (DynaMaskRoIHead.batch_simple_test_mask).
+ * Detection n [0, N) belongs to image det_img[n] (int32, device) and the detections of one image are consecutive;
+ * img_tab (int64, device) [B][4] = (img_h, img_w, index of the image's first detection, byte offset of its first canvas
+ * in `out`); max_pixels = the largest img_h * img_w of the images that have detections.  A detection's pixels are
+ * exactly what dm_paste_masks / dm_paste_rle give for it on its own image (same arithmetic).
+ * dm_paste_masks_multi: detection n's row-major [img_h, img_w] uint8 bitmap at out + off_b + (n - first_b) * h * w.
+ * dm_paste_rle_multi: as dm_paste_rle, with positions local to each detection's own canvas (j = x * img_h + y); the
+ * boundaries of all detections are packed into one `positions` buffer (mask_start [N + 1]); boundaries past `capacity`
+ * are counted, not stored.  seg_scratch: dm_rle_multi_scratch_ints(N, max_pixels) int32.  A detection whose image index
+ * is outside [0, B) is skipped (no pixels written, no runs). */
+long long dm_rle_multi_scratch_ints(int N, long long max_pixels);
+int dm_paste_masks_multi(const float* masks, const float* boxes, int N, int mask_h, int mask_w, const int* det_img, int B,
+                         const long long* img_tab, long long max_pixels, float threshold, int apply_sigmoid, uint8_t* out,
+                         dm_stream_t stream);
+int dm_paste_rle_multi(const float* masks, const float* boxes, int N, int mask_h, int mask_w, const int* det_img, int B,
+                       const long long* img_tab, long long max_pixels, float threshold, int apply_sigmoid, int* seg_scratch,
+                       int* mask_runs, int* mask_start, int* positions, int capacity, dm_stream_t stream);
+
 /* K22  fully connected layer out[N, M] = x[N, K] . w[M, K]^T + bias (nn.Linear layouts), optional
  * ReLU; fp32 MFMA.  replaces: the nn.Linear stack of Shared2FCBBoxHead
  * (roi_heads/bbox_heads/convfc_bbox_head.py:101-108,143-186) and MaskPre's fc1 / fc2
@@ -505,6 +523,18 @@ int dm_bbox_decode(const float* rois, int roi_stride, int roi_x0, const float* c
 int dm_nms_mask(const float* boxes_sorted, int M, float iou_threshold, int offset, unsigned long long* mask,
                 dm_stream_t stream);
 int dm_nms_reduce(const unsigned long long* mask_host, int M, int* keep, int max_keep);
+/* (added to ABI 28) K21 over B segments (images) at once, greedy pass on the device.  boxes_sorted [sum M_b, 4]: the segments
+ * one after the other, each score-sorted on its own; seg_tab (int64, device) [B][3] = (first row, M_b, offset in
+ * unsigned long longs of the segment's matrix in `mask`).  Segment b's matrix is [M_b][ceil(M_b / 64)] (the rows of
+ * dm_nms_mask for those M_b boxes alone): the block-diagonal layout, mask_words = sum M_b * ceil(M_b / 64) in all.
+ * max_words = the largest ceil(M_b / 64).  No bit compares boxes of two segments.
+ * dm_nms_reduce_segmented: dm_nms_reduce of every segment, one wave per segment: keep[first_b + k] (int32) = the k-th
+ * kept box of segment b (index within the segment's sorted rows), counts[b] (int32) = number kept (<= max_keep when
+ * max_keep >= 0).  max_words <= 20480 (the removed bits live in LDS). */
+int dm_nms_mask_segmented(const float* boxes_sorted, int B, const long long* seg_tab, int max_words, float iou_threshold,
+                          int offset, unsigned long long* mask, long long mask_words, dm_stream_t stream);
+int dm_nms_reduce_segmented(const unsigned long long* mask, int B, const long long* seg_tab, int max_words, int max_keep,
+                            int* keep, int* counts, dm_stream_t stream);
 
 /* ===========================================================================
  * Backward (training step).  Replaces what autograd derives for the reference
