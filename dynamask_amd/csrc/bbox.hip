@@ -192,6 +192,68 @@ __global__ __launch_bounds__(64) void nms_reduce_segmented_kernel(const unsigned
   if (lane == 0) counts[blockIdx.x] = n;
 }
 
+// ----- test-time augmentation (BBoxTestMixin.aug_test_bboxes / MaskTestMixin.aug_test_mask) -----
+// View v's parameters: view_tab[v * DM_AUG_VIEW_FLOATS + k], k = 0..3 the scale factor of x1, y1, x2, y2, 4 img_h,
+// 5 img_w (of the view), 6 the flip code (DM_AUG_FLIP_*).  Same fp32 operations in the reference's order.
+
+// bbox_mapping: [n, 4] boxes (row stride `stride`) -> out [V][n][5] RoI rows (batch column 0): b * sf, then the flip.
+__global__ __launch_bounds__(256) void bbox_mapping_multi_kernel(const float* __restrict__ boxes, int stride, int n, int V,
+                                                                 const float* __restrict__ view_tab,
+                                                                 float* __restrict__ out) {
+#pragma clang fp contract(off)
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (long long)n * V) return;
+  const int v = (int)(t / n), i = (int)(t - (long long)v * n);
+  const float* vt = view_tab + (size_t)v * DM_AUG_VIEW_FLOATS;
+  const float* b = boxes + (size_t)i * stride;
+  float x1 = b[0] * vt[0], y1 = b[1] * vt[1], x2 = b[2] * vt[2], y2 = b[3] * vt[3];
+  const int flip = (int)vt[6];
+  if (flip == DM_AUG_FLIP_HORIZONTAL) {
+    const float a = vt[5] - x2, c = vt[5] - x1;
+    x1 = a; x2 = c;
+  } else if (flip == DM_AUG_FLIP_VERTICAL) {
+    const float a = vt[4] - y2, c = vt[4] - y1;
+    y1 = a; y2 = c;
+  }
+  float* o = out + (size_t)t * 5;
+  o[0] = 0.f; o[1] = x1; o[2] = y1; o[3] = x2; o[4] = y2;
+}
+
+// merge_aug_bboxes: views' [n, C4] boxes (bbox_mapping_back: flip, then / sf) and [n, CS] scores, averaged: the sum in
+// view order (starting from view 0's value), then / V.  ptr_tab[v] = (boxes, scores) of view v.  grid = (column
+// blocks, n); column j < C4 is a box coordinate, C4 + k the score k.
+__global__ __launch_bounds__(256) void merge_aug_bboxes_kernel(const long long* __restrict__ ptr_tab,
+                                                               const float* __restrict__ view_tab, int V, int n, int C4,
+                                                               int CS, float* __restrict__ out_boxes,
+                                                               float* __restrict__ out_scores) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.y;
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= C4 + CS) return;
+  float acc = 0.f;
+  if (j < C4) {
+    const int kk = j & 3, base = j - kk;
+    for (int v = 0; v < V; ++v) {
+      const float* vt = view_tab + (size_t)v * DM_AUG_VIEW_FLOATS;
+      const float* b = reinterpret_cast<const float*>(ptr_tab[2 * v]) + (size_t)i * C4;
+      const int flip = (int)vt[6];
+      float x = b[j];
+      if (flip == DM_AUG_FLIP_HORIZONTAL && (kk & 1) == 0) x = vt[5] - b[base + (kk ^ 2)];
+      else if (flip == DM_AUG_FLIP_VERTICAL && (kk & 1) == 1) x = vt[4] - b[base + (kk ^ 2)];
+      x = x / vt[kk];
+      acc = v == 0 ? x : acc + x;
+    }
+    out_boxes[(size_t)i * C4 + j] = acc / (float)V;
+  } else {
+    const int k = j - C4;
+    for (int v = 0; v < V; ++v) {
+      const float x = reinterpret_cast<const float*>(ptr_tab[2 * v + 1])[(size_t)i * CS + k];
+      acc = v == 0 ? x : acc + x;
+    }
+    out_scores[(size_t)i * CS + k] = acc / (float)V;
+  }
+}
+
 }  // namespace
 
 extern "C" int dm_bbox_decode(const float* rois, int roi_stride, int roi_x0, const float* cls_score,
@@ -281,4 +343,27 @@ extern "C" int dm_nms_reduce(const unsigned long long* mask_host, int M, int* ke
   }
   delete[] heap;
   return n;
+}
+
+extern "C" int dm_bbox_mapping_multi(const float* boxes, int box_stride, int n, int V, const float* view_tab, float* out_rois,
+                                     dm_stream_t stream) {
+  if (n < 0 || V < 0 || box_stride < 4) return DM_ERR_INVALID_ARG;
+  if (n == 0 || V == 0) return DM_OK;
+  if (!boxes || !view_tab || !out_rois) return DM_ERR_INVALID_ARG;
+  const long long total = (long long)n * V;
+  if (total > 0x7fffffffLL) return DM_ERR_INVALID_ARG;
+  DM_LAUNCH(bbox_mapping_multi_kernel, dim3(dm_ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, boxes, box_stride,
+            n, V, view_tab, out_rois);
+  return dm_check_launch();
+}
+
+extern "C" int dm_merge_aug_bboxes(const long long* ptr_tab, const float* view_tab, int V, int n, int box_cols,
+                                   int score_cols, float* out_boxes, float* out_scores, dm_stream_t stream) {
+  if (n < 0 || V < 0 || box_cols < 0 || score_cols < 0 || (box_cols & 3)) return DM_ERR_INVALID_ARG;
+  if (n == 0 || box_cols + score_cols == 0) return DM_OK;
+  if (V == 0 || n > 65535 || !ptr_tab || !view_tab || (box_cols && !out_boxes) || (score_cols && !out_scores))
+    return DM_ERR_INVALID_ARG;
+  DM_LAUNCH(merge_aug_bboxes_kernel, dim3(dm_ceil_div(box_cols + score_cols, 256), n), dim3(256), 0, (hipStream_t)stream,
+            ptr_tab, view_tab, V, n, box_cols, score_cols, out_boxes, out_scores);
+  return dm_check_launch();
 }

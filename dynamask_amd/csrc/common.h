@@ -105,5 +105,9 @@ __device__ __forceinline__ void dm_acc_add(float* base, size_t idx, float v, boo
   else atomicAdd(base + idx, v);
 }
 
+// The logistic function of the paste kernels' apply_sigmoid (paste_masks_kernel, PasteSrc) and of the TTA mask merge
+// (dm_merge_aug_masks): one expression, so that a merged probability is bit for bit what the paste computes from the logit.
+__device__ __forceinline__ float dm_sigmoid(float t) { return 1.f / (1.f + expf(-t)); }
+
 typedef float dm_f32x16 __attribute__((ext_vector_type(16)));
 typedef float dm_f32x4 __attribute__((ext_vector_type(4)));

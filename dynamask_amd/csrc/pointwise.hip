@@ -1157,7 +1157,7 @@ __global__ __launch_bounds__(256) void paste_masks_kernel(const float* __restric
       auto at = [&](int yy, int xx) -> float {
         if (yy < 0 || yy >= mh || xx < 0 || xx >= mw) return 0.f;
         const float t = m[yy * mw + xx];
-        return apply_sigmoid ? 1.f / (1.f + expf(-t)) : t;
+        return apply_sigmoid ? dm_sigmoid(t) : t;
       };
       v = at(iy, ix) * (1.f - lx) * (1.f - ly) + at(iy, ix + 1) * lx * (1.f - ly) + at(iy + 1, ix) * (1.f - lx) * ly +
           at(iy + 1, ix + 1) * lx * ly;

@@ -54,7 +54,7 @@ struct PasteSrc {
       auto tap = [&](int yy, int xx) -> float {
         if (yy < 0 || yy >= mh || xx < 0 || xx >= mw) return 0.f;
         const float t = m[yy * mw + xx];
-        return apply_sigmoid ? 1.f / (1.f + expf(-t)) : t;
+        return apply_sigmoid ? dm_sigmoid(t) : t;
       };
       v = tap(iy, ix) * (1.f - lx) * (1.f - ly) + tap(iy, ix + 1) * lx * (1.f - ly) + tap(iy + 1, ix) * (1.f - lx) * ly +
           tap(iy + 1, ix + 1) * lx * ly;
@@ -268,6 +268,34 @@ __global__ __launch_bounds__(256) void paste_masks_multi_kernel(PasteSrc src, Mu
   }
 }
 
+// ----- test-time augmentation: merge_aug_masks of the views' mask logits (MaskTestMixin.aug_test_mask) -----
+// out[i][0][y][x] = (sum over views v, in order, of dm_sigmoid(L_v[i][c_i][y'][x'])) / V, where c_i = labels[i] (K > 1,
+// clamped into [0, K)) or 0, and (y', x') is (y, x) read back through view v's flip (view_tab[v * DM_AUG_VIEW_FLOATS +
+// 6]).  logit_tab[v] = the address of view v's [n, K, S, S] logits.
+__global__ __launch_bounds__(256) void merge_aug_masks_kernel(const long long* __restrict__ logit_tab,
+                                                              const float* __restrict__ view_tab, int V, int n, int K,
+                                                              int S, const long long* __restrict__ labels,
+                                                              float* __restrict__ out) {
+  const long long total = (long long)n * S * S;
+  for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
+    const int i = (int)(t / ((long long)S * S));
+    const int p = (int)(t - (long long)i * S * S);
+    const int y = p / S, x = p - y * S;
+    int c = 0;
+    if (K > 1) c = (int)min(max(labels[i], 0LL), (long long)(K - 1));
+    float acc = 0.f;
+    for (int v = 0; v < V; ++v) {
+      const int flip = (int)view_tab[(size_t)v * DM_AUG_VIEW_FLOATS + 6];
+      const int yy = flip == DM_AUG_FLIP_VERTICAL ? S - 1 - y : y;
+      const int xx = flip == DM_AUG_FLIP_HORIZONTAL ? S - 1 - x : x;
+      const float* L = reinterpret_cast<const float*>(logit_tab[v]);
+      const float pv = dm_sigmoid(L[(((size_t)i * K + c) * S + yy) * S + xx]);
+      acc = v == 0 ? pv : acc + pv;
+    }
+    out[t] = acc / (float)V;
+  }
+}
+
 }  // namespace
 
 extern "C" long long dm_rle_scratch_ints(int N, int img_h, int img_w) {
@@ -367,5 +395,17 @@ extern "C" int dm_paste_masks_multi(const float* masks, const float* boxes, int 
   MultiCanvas mc{det_img, img_tab, B};
   const int bx = (int)min((max_pixels + 255) / 256, 1024LL);
   DM_LAUNCH(paste_masks_multi_kernel, dim3(bx, N), dim3(256), 0, (hipStream_t)stream, src, mc, out);
+  return dm_check_launch();
+}
+
+extern "C" int dm_merge_aug_masks(const long long* logit_tab, const float* view_tab, int V, int n, int K, int S,
+                                  const long long* labels, float* out, dm_stream_t stream) {
+  if (n < 0 || V < 0 || K <= 0 || S <= 0) return DM_ERR_INVALID_ARG;
+  if (n == 0) return DM_OK;
+  if (V == 0 || !logit_tab || !view_tab || !out || (K > 1 && !labels)) return DM_ERR_INVALID_ARG;
+  const long long total = (long long)n * S * S;
+  const int blocks = (int)min((long long)dm_ceil_div(total, 256), 8192LL);
+  DM_LAUNCH(merge_aug_masks_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, logit_tab, view_tab, V, n, K, S, labels,
+            out);
   return dm_check_launch();
 }

@@ -410,6 +410,116 @@ def nms_segmented(boxes_sorted, counts, iou_threshold, offset=0, max_num=-1):
     return keep[:sum(counts)], kept
 
 
+# --------------------------------------------------------------- test-time augmentation (several views of one image)
+AUG_VIEW_FLOATS = 8                 # dynamask_hip.h DM_AUG_VIEW_FLOATS
+AUG_FLIP_CODES = {'horizontal': 1, 'vertical': 2}
+
+
+def aug_view_rows(img_metas):
+    """The per-view parameters of the TTA kernels from V view metas (dicts with ``img_shape``, ``scale_factor``,
+    ``flip`` and, when flipped, ``flip_direction``) -> host rows [V][AUG_VIEW_FLOATS] (sf x1, y1, x2, y2, img_h, img_w,
+    flip code, 0).  The scale factor is taken as the reference's ``bboxes.new_tensor(scale_factor)`` takes it: fp32, a
+    scalar for all four coordinates or one value each.  Raises ValueError for a flip direction other than 'horizontal' /
+    'vertical' (merge_augs.py merge_aug_masks) -- before anything reaches the device."""
+    import numpy as np
+    rows = []
+    for v, m in enumerate(img_metas):
+        sf = np.asarray(m['scale_factor'], dtype=np.float32).reshape(-1)
+        if sf.size == 1:
+            sf = np.repeat(sf, 4)
+        if sf.size != 4:
+            raise ValueError(f'view {v}: scale_factor has {sf.size} values (one, or [w, h, w, h])')
+        flip = 0
+        if m['flip']:
+            d = m.get('flip_direction', 'horizontal')
+            if d not in AUG_FLIP_CODES:
+                raise ValueError(f"view {v}: invalid flipping direction '{d}'")
+            flip = AUG_FLIP_CODES[d]
+        h, w = m['img_shape'][:2]
+        rows.append([float(x) for x in sf] + [float(h), float(w), float(flip), 0.0])
+    return rows
+
+
+def aug_view_table(img_metas, device):
+    """``aug_view_rows`` uploaded without a host wait: float32 [V, AUG_VIEW_FLOATS] on ``device``."""
+    return _upload(aug_view_rows(img_metas), torch.float32, device)
+
+
+def bbox_mapping_multi(boxes, view_tab):
+    """mmdet ``bbox_mapping`` of boxes [n, >= 4] (original image) into every view of ``view_tab`` in one launch ->
+    RoI rows [V, n, 5] (batch column 0): ``b * sf``, then the view's flip."""
+    _chk(view_tab, 'view_tab')
+    if not isinstance(boxes, torch.Tensor) or boxes.dim() != 2 or boxes.shape[1] < 4:
+        raise ValueError('boxes: [n, >= 4] expected')
+    if boxes.stride(1) != 1 or boxes.stride(0) < 4:
+        boxes = boxes.contiguous()
+    if not boxes.is_cuda or boxes.dtype != torch.float32:
+        _chk(boxes, 'boxes')                    # (raises: no CPU fallback / wrong dtype)
+    V, n = view_tab.shape[0], boxes.shape[0]
+    out = torch.empty((V, n, 5), device=boxes.device, dtype=torch.float32)
+    if n > 0 and V > 0:
+        check(lib().dm_bbox_mapping_multi(_p(boxes), boxes.stride(0), n, V, _p(view_tab), _p(out), _stream()),
+              'dm_bbox_mapping_multi')
+    return out
+
+
+def merge_aug_bboxes(bboxes_list, scores_list, view_tab):
+    """mmdet ``merge_aug_bboxes`` in one launch: V views' boxes [n, 4C] (view coordinates) and scores [n, C + 1] ->
+    (boxes mapped back to the original image and averaged [n, 4C], averaged scores [n, C + 1])."""
+    _chk(view_tab, 'view_tab')
+    V = view_tab.shape[0]
+    if len(bboxes_list) != V or len(scores_list) != V or V == 0:
+        raise ValueError(f'{len(bboxes_list)} box and {len(scores_list)} score tensors for {V} views')
+    n, c4 = bboxes_list[0].shape
+    cs = scores_list[0].shape[1]
+    for b, sc in zip(bboxes_list, scores_list):
+        _chk(b, 'bboxes')
+        _chk(sc, 'scores')
+        if tuple(b.shape) != (n, c4) or tuple(sc.shape) != (n, cs):
+            raise ValueError('every view needs boxes and scores of the same shape')
+    dev = bboxes_list[0].device
+    out_b = torch.empty((n, c4), device=dev, dtype=torch.float32)
+    out_s = torch.empty((n, cs), device=dev, dtype=torch.float32)
+    if n > 0:
+        tab = _upload([[b.data_ptr(), sc.data_ptr()] for b, sc in zip(bboxes_list, scores_list)], torch.int64, dev)
+        if hazard.ENABLED[0]:
+            hazard.touch('dm_merge_aug_bboxes (view tables)', reads=list(bboxes_list) + list(scores_list))
+        check(lib().dm_merge_aug_bboxes(_p(tab), _p(view_tab), V, n, c4, cs, _p(out_b), _p(out_s), _stream()),
+              'dm_merge_aug_bboxes')
+    return out_b, out_s
+
+
+def merge_aug_masks(logits_list, labels, view_tab):
+    """mmdet ``merge_aug_masks`` of V views' mask LOGITS [n, K, S, S] in one launch -> probabilities [n, 1, S, S]: the
+    ``labels`` [n] channel when K > 1 (the channel the paste would select), sigmoid (the paste's own), un-flipped,
+    averaged over the views."""
+    _chk(view_tab, 'view_tab')
+    V = view_tab.shape[0]
+    if len(logits_list) != V or V == 0:
+        raise ValueError(f'{len(logits_list)} logit tensors for {V} views')
+    n, K, S, S2 = logits_list[0].shape
+    if S != S2:
+        raise ValueError('square mask logits expected')
+    for t in logits_list:
+        _chk(t, 'logits')
+        if tuple(t.shape) != (n, K, S, S):
+            raise ValueError('every view needs logits of the same shape')
+    dev = logits_list[0].device
+    out = torch.empty((n, 1, S, S), device=dev, dtype=torch.float32)
+    if n == 0:
+        return out
+    if K > 1:
+        _chk(labels, 'labels', torch.int64)
+        if labels.shape != (n,):
+            raise ValueError(f'labels: [{n}] expected')
+    tab = _upload([t.data_ptr() for t in logits_list], torch.int64, dev)
+    if hazard.ENABLED[0]:
+        hazard.touch('dm_merge_aug_masks (view table)', reads=list(logits_list))
+    check(lib().dm_merge_aug_masks(_p(tab), _p(view_tab), V, n, K, S, _p(labels) if K > 1 else _p(None), _p(out),
+                                   _stream()), 'dm_merge_aug_masks')
+    return out
+
+
 # --------------------------------------------------------------- convolutions
 def packed_cout(cout):
     return lib().dm_conv_packed_cout(int(cout))

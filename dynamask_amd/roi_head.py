@@ -757,6 +757,142 @@ class DynaMaskRoIHead(nn.Module):
                                                    rescale=rescale, encode=encode, _labels_host=labels_h)
         return list(zip(bbox_results, segm_results))
 
+    # ------------------------------------------------------------ test-time augmentation: V views of one image
+    # standard_roi_head.py:264-290 + test_mixins.py:73-107,178-208 (MultiScaleFlipAug): ``x`` holds one FPN tuple per view
+    # (batch size 1 each), ``img_metas`` one single-element list per view.  The views share three launches: the mapping of
+    # the boxes into every view (dm_bbox_mapping_multi), the box / score merge (dm_merge_aug_bboxes) and the mask merge
+    # (dm_merge_aug_masks); the bbox branch and the mask chain run once per view through the one-view path.  No host wait
+    # inside the per-view loops.  DynaMask head (this project's definition, the reference cannot run it): a view's mask
+    # prediction is what ``simple_test_mask_logits`` returns for the mapped boxes.
+    _AUG_META_KEYS = ('img_shape', 'scale_factor', 'flip', 'flip_direction', 'ori_shape')
+
+    @classmethod
+    def _check_aug(cls, x, img_metas):
+        """Argument checks of the aug_test* methods (before any GPU work) -> the V view metas."""
+        if not isinstance(img_metas, (list, tuple)) or len(img_metas) == 0:
+            raise ValueError('img_metas: a non-empty list with one single-element list per view')
+        V = len(img_metas)
+        if len(x) != V:
+            raise ValueError(f'x has {len(x)} views, img_metas {V}')
+        views = []
+        for v, m in enumerate(img_metas):
+            if not isinstance(m, (list, tuple)) or len(m) != 1:
+                raise ValueError(f'img_metas[{v}]: one meta per view (test-time augmentation runs one image)')
+            missing = [k for k in cls._AUG_META_KEYS if k not in m[0]]
+            if missing:
+                raise ValueError(f'img_metas[{v}][0] lacks {missing}')
+            if x[v][0].shape[0] != 1:
+                raise ValueError(f'x[{v}] has batch dimension {x[v][0].shape[0]}: one image per view')
+            views.append(m[0])
+        ops.aug_view_rows(views)                    # flip directions and scale factors
+        return views
+
+    @torch.no_grad()
+    def aug_test_bboxes(self, x, img_metas, proposal_list, rcnn_test_cfg):
+        """test_mixins.py:73-107: the proposals ``proposal_list[0]`` (original image) mapped into every view, the bbox
+        branch and ``get_bboxes(rescale=False)`` per view, the views' boxes mapped back and averaged with their scores
+        (merge_aug_bboxes), then ``multiclass_nms`` -> (dets [k, 5], labels [k]) in original-image coordinates."""
+        from .bbox_heads import multiclass_nms
+        views = self._check_aug(x, img_metas)
+        props = proposal_list[0]
+        if props.shape[0] == 0:
+            return props.new_zeros((0, 5)), props.new_zeros((0,), dtype=torch.long)
+        tab = ops.aug_view_table(views, props.device)
+        rois = ops.bbox_mapping_multi(props, tab)
+        aug_bboxes, aug_scores = [], []
+        for v, meta in enumerate(views):
+            res = self._bbox_forward(x[v], rois[v])
+            bboxes, scores = self.bbox_head.get_bboxes(rois[v], res['cls_score'], res['bbox_pred'], meta['img_shape'],
+                                                       meta['scale_factor'], rescale=False, cfg=None)
+            aug_bboxes.append(bboxes.contiguous())
+            aug_scores.append(scores.contiguous())
+        merged_bboxes, merged_scores = ops.merge_aug_bboxes(aug_bboxes, aug_scores, tab)
+        cfg = rcnn_test_cfg
+        return multiclass_nms(merged_bboxes, merged_scores, cfg.score_thr, cfg.nms, cfg.max_per_img)
+
+    def _aug_view_mask_logits(self, x, rois, det_labels):
+        """One view's mask prediction for its RoI rows: the merged 112 x 112 logits [n, 1, 112, 112] of
+        ``simple_test_mask_logits``, valid until the merge (a graph's static output is copied: the next view's replay
+        would overwrite it)."""
+        merged = self.simple_test_mask_logits(x, rois[:, 1:], det_labels)
+        if getattr(self, '_mask_graphs', None) is not None:
+            merged = merged.clone()
+        return merged.contiguous()
+
+    def _aug_empty_probs(self, ref):
+        return ref.new_zeros((0, 1, 112, 112))
+
+    @torch.no_grad()
+    def aug_test_mask_probs(self, x, img_metas, det_bboxes, det_labels):
+        """The merged mask probabilities of test-time augmentation [n, 1, S, S] on the device: ``det_bboxes`` (original
+        image) mapped into every view, the view's mask prediction, then sigmoid, un-flip and mean over the views
+        (merge_aug_masks) of the detection's class channel."""
+        views = self._check_aug(x, img_metas)
+        if det_bboxes.shape[0] == 0:
+            return self._aug_empty_probs(det_bboxes)
+        tab = ops.aug_view_table(views, det_bboxes.device)
+        rois = ops.bbox_mapping_multi(det_bboxes, tab)
+        labels = det_labels.contiguous()
+        logits = [self._aug_view_mask_logits(x[v], rois[v], labels) for v in range(len(views))]
+        return ops.merge_aug_masks(logits, labels, tab)
+
+    @torch.no_grad()
+    def aug_test_mask(self, x, img_metas, det_bboxes, det_labels, encode=False, _labels_host=None):
+        """test_mixins.py:178-208 -> per-class lists of (h, w) bool masks at ``ori_shape`` of the first view
+        (``encode``: COCO RLE dicts): the merged probabilities (``aug_test_mask_probs``) pasted without a sigmoid,
+        ``scale_factor=1.0, rescale=False``, thresholded at ``mask_thr_binary``."""
+        from .mask_heads import _bitmaps_to_host, _paste_geometry
+        views = self._check_aug(x, img_metas)
+        segm_result = [[] for _ in range(self._segm_num_classes())]
+        if det_bboxes.shape[0] == 0:
+            return segm_result
+        threshold = self.test_cfg.mask_thr_binary
+        if threshold < 0:
+            raise NotImplementedError('visualisation mode (mask_thr_binary < 0) is not on the path')
+        probs = self.aug_test_mask_probs(x, img_metas, det_bboxes, det_labels)
+        boxes, img_h, img_w = _paste_geometry(det_bboxes, views[0]['ori_shape'], 1.0, False)
+        if encode:
+            segs = ops.paste_rle(probs, boxes, img_h, img_w, threshold, apply_sigmoid=False)
+        else:
+            im = _bitmaps_to_host(ops.paste_masks(probs, boxes, img_h, img_w, threshold, apply_sigmoid=False))
+            segs = [im[i] for i in range(len(im))]
+        labels_h = _labels_host if _labels_host is not None else det_labels.tolist()
+        for c, segm in zip(labels_h, segs):
+            segm_result[c].append(segm)
+        return segm_result
+
+    @torch.no_grad()
+    def aug_test(self, x, proposal_list, img_metas, rescale=False, encode=False):
+        """standard_roi_head.py:264-290: boxes merged over the views, then masks merged over the views ->
+        ``(bbox_results, segm_results)`` (just ``bbox_results`` without a mask branch).  ``rescale=False`` scales only
+        the boxes of ``bbox_results`` by the first view's ``scale_factor``, as the reference does; the masks stay at
+        the original image's size either way."""
+        import numpy as np
+        views = self._check_aug(x, img_metas)
+        det_bboxes, det_labels = self.aug_test_bboxes(x, img_metas, proposal_list, self.test_cfg)
+        num_classes = self.bbox_head.num_classes
+        if det_bboxes.shape[0] == 0:
+            bbox_results = [np.zeros((0, 5), dtype=np.float32) for _ in range(num_classes)]
+            labels_h = []
+        else:
+            _det_bboxes = det_bboxes
+            if not rescale:
+                _det_bboxes = det_bboxes.clone()
+                sf = views[0]['scale_factor']
+                _det_bboxes[:, :4] *= sf if isinstance(sf, float) else self._batch_scale_factor(
+                    np.asarray(sf, dtype=np.float32), det_bboxes.device)
+            d_h = torch.empty(_det_bboxes.shape, dtype=_det_bboxes.dtype, pin_memory=True)
+            l_h = torch.empty(det_labels.shape, dtype=det_labels.dtype, pin_memory=True)
+            d_h.copy_(_det_bboxes, non_blocking=True)
+            l_h.copy_(det_labels, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            bbox_results = _bbox2result_host(d_h.numpy(), l_h.numpy(), num_classes)
+            labels_h = l_h.tolist()
+        if not self.with_mask:
+            return bbox_results
+        segm_results = self.aug_test_mask(x, img_metas, det_bboxes, det_labels, encode=encode, _labels_host=labels_h)
+        return bbox_results, segm_results
+
     # ------------------------------------------------------------ dynamic inference
     @torch.no_grad()
     def dynamic_mask_logits(self, x, det_bboxes, det_labels, noise=None, merge=True, exits=None):
@@ -956,6 +1092,14 @@ class StandardRoIHead(DynaMaskRoIHead):
 
     def _segm_num_classes(self):
         return self.mask_head.num_classes
+
+    def _aug_view_mask_logits(self, x, rois, det_labels):
+        """One view's ``mask_pred`` [n, classes, S, S] of ``_mask_forward`` for its RoI rows (test_mixins.py:194-195);
+        the merge selects the detection's class channel."""
+        return self._mask_forward(x, rois)['mask_pred'].contiguous()
+
+    def _aug_empty_probs(self, ref):
+        return ref.new_zeros((0, 1, 1, 1))
 
     def simple_test_mask(self, x, img_metas, det_bboxes, det_labels, rescale=False, encode=False):
         """test_mixins.py:151-176 -> ``cls_segms`` of ``FCNMaskHead.get_seg_masks`` (``encode``: COCO RLE dicts instead of

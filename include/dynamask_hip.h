@@ -55,7 +55,7 @@ extern "C" {
 typedef void* dm_stream_t; /* hipStream_t */
 
 const char* dm_error_string(int code);
-/* ABI version: bumped whenever a signature or the meaning of an argument changes (8: flag bit 3 of dm_conv2d_fwd; 9: RoI assignment / bbox training entry points; 10: dm_detail_target takes the fuse weights from device memory; 11: FCNMaskHead upsample backward; 12: dm_fc_fwd takes a scratch slab, deterministic split-K; 13: dm_deform_coord_grad / dm_deform_col2im, dm_conv2d_fwd_masked, dm_scale, dm_polygon_mask_targets, dm_ignore_columns, dm_upsample2x_bilinear_bwd overwrites; 14: dm_random_sample, dm_bn_relu_maxpool_argmax, the *_fx deterministic accumulators + dm_fx_to_float, dm_mask_loss_fwd_bwd takes a scratch, dm_conv2d_wgrad takes the bias gradient, dm_conv_pack_weight_batch, dm_mask_loss_stage; 15: dm_class_logits_up2x_fwd; 16: dm_conv2d_wgrad_slab / dm_conv2d_wgrad_scratch_floats; 17: dm_class_logits_bwd_slab / dm_class_logits_bwd_scratch_floats; 18: dm_reload_env_knobs, dm_roi_align_fwd_ws / dm_roi_align_workspace_bytes, dm_conv_pack_weight_split / dm_conv_packed_floats_split and flag bits 4, 5 of dm_conv2d_fwd; 19: dm_dcn_bwd_data_fused and its pack; 20: dm_conv2d_fwd_ws / dm_conv2d_splitk_floats; 21: dm_deform_conv_fwd_ws / dm_deform_conv_splitk_floats; 22: the bf16-split layouts (dm_conv_pack_weight_split, dm_conv_packed_floats_split, flag bits 4 / 5 of dm_conv2d_fwd) and the one-kernel DCN data gradient (dm_dcn_bwd_*) REMOVED -- measured, never the parity path, see docs/HISTORY.md; 23: dm_bn_stats takes mean_shift, dm_roi_align_bwd takes the gather form for 16 < P <= 64; 24: dm_build_info; 25: dm_boundary_merge_chain, dm_stage_head_fwd; 26: dm_conv1x1_group_fwd; 27: dm_deform_conv_tout_fwd / dm_deform_conv_tout_supported; 28: the opt-in bf16x3 mode -- dm_conv_pack_weight_bf16x3 / dm_conv_packed_floats_bf16x3 and flag bit 4 of dm_conv2d_fwd, dm_conv2d_fwd_ws and dm_conv1x1_group_fwd; dm_deconv_pack_weight_bf16x3 and flag bit 4 of dm_deconv2x2_fwd).  Entry points ADDED without a signature or meaning change leave the number as it is (the loader resolves every symbol of _lib.SIGNATURES by name, so an older library fails at load): the multi-image post-processing dm_nms_mask_segmented / dm_nms_reduce_segmented, dm_paste_masks_multi, dm_paste_rle_multi / dm_rle_multi_scratch_ints. */
+/* ABI version: bumped whenever a signature or the meaning of an argument changes (8: flag bit 3 of dm_conv2d_fwd; 9: RoI assignment / bbox training entry points; 10: dm_detail_target takes the fuse weights from device memory; 11: FCNMaskHead upsample backward; 12: dm_fc_fwd takes a scratch slab, deterministic split-K; 13: dm_deform_coord_grad / dm_deform_col2im, dm_conv2d_fwd_masked, dm_scale, dm_polygon_mask_targets, dm_ignore_columns, dm_upsample2x_bilinear_bwd overwrites; 14: dm_random_sample, dm_bn_relu_maxpool_argmax, the *_fx deterministic accumulators + dm_fx_to_float, dm_mask_loss_fwd_bwd takes a scratch, dm_conv2d_wgrad takes the bias gradient, dm_conv_pack_weight_batch, dm_mask_loss_stage; 15: dm_class_logits_up2x_fwd; 16: dm_conv2d_wgrad_slab / dm_conv2d_wgrad_scratch_floats; 17: dm_class_logits_bwd_slab / dm_class_logits_bwd_scratch_floats; 18: dm_reload_env_knobs, dm_roi_align_fwd_ws / dm_roi_align_workspace_bytes, dm_conv_pack_weight_split / dm_conv_packed_floats_split and flag bits 4, 5 of dm_conv2d_fwd; 19: dm_dcn_bwd_data_fused and its pack; 20: dm_conv2d_fwd_ws / dm_conv2d_splitk_floats; 21: dm_deform_conv_fwd_ws / dm_deform_conv_splitk_floats; 22: the bf16-split layouts (dm_conv_pack_weight_split, dm_conv_packed_floats_split, flag bits 4 / 5 of dm_conv2d_fwd) and the one-kernel DCN data gradient (dm_dcn_bwd_*) REMOVED -- measured, never the parity path, see docs/HISTORY.md; 23: dm_bn_stats takes mean_shift, dm_roi_align_bwd takes the gather form for 16 < P <= 64; 24: dm_build_info; 25: dm_boundary_merge_chain, dm_stage_head_fwd; 26: dm_conv1x1_group_fwd; 27: dm_deform_conv_tout_fwd / dm_deform_conv_tout_supported; 28: the opt-in bf16x3 mode -- dm_conv_pack_weight_bf16x3 / dm_conv_packed_floats_bf16x3 and flag bit 4 of dm_conv2d_fwd, dm_conv2d_fwd_ws and dm_conv1x1_group_fwd; dm_deconv_pack_weight_bf16x3 and flag bit 4 of dm_deconv2x2_fwd).  Entry points ADDED without a signature or meaning change leave the number as it is (the loader resolves every symbol of _lib.SIGNATURES by name, so an older library fails at load): the multi-image post-processing dm_nms_mask_segmented / dm_nms_reduce_segmented, dm_paste_masks_multi, dm_paste_rle_multi / dm_rle_multi_scratch_ints; the test-time augmentation dm_bbox_mapping_multi, dm_merge_aug_bboxes, dm_merge_aug_masks. */
 int dm_abi_version(void);
 /* "libdynamask_hip abi=N arch=gfx950 compiler=<clang version> flags=<the product-wide flags of dynamask_amd/build.py>"
  * (static storage).  The library must be compiled WITHOUT packed fp32 instructions (flag "-packed-fp32-ops", see
@@ -535,6 +535,33 @@ int dm_nms_mask_segmented(const float* boxes_sorted, int B, const long long* seg
                           int offset, unsigned long long* mask, long long mask_words, dm_stream_t stream);
 int dm_nms_reduce_segmented(const unsigned long long* mask, int B, const long long* seg_tab, int max_words, int max_keep,
                             int* keep, int* counts, dm_stream_t stream);
+
+/* (added to ABI 28) Test-time augmentation over V views of one image (DynaMaskRoIHead.aug_test: bbox_mapping,
+ * merge_aug_bboxes and merge_aug_masks of core/bbox/transforms.py and core/post_processing/merge_augs.py).
+ * view_tab (float, device) [V][DM_AUG_VIEW_FLOATS] = (scale factor of x1, y1, x2, y2; img_h, img_w of the view; flip code
+ * DM_AUG_FLIP_*; unused).  Every element is the reference's fp32 operations in its order.
+ * dm_bbox_mapping_multi: boxes [n, box_stride >= 4] (x1 y1 x2 y2 in the first four columns) -> out_rois [V][n][5], the
+ *   RoI rows of view v (batch column 0, then b * sf, then the flip: x = img_w - x' for 'horizontal', y = img_h - y' for
+ *   'vertical', the two coordinates swapped).
+ * dm_merge_aug_bboxes: ptr_tab (int64, device) [V][2] = addresses of view v's boxes [n, box_cols] (box_cols % 4 == 0,
+ *   box_cols / 4 boxes per row) and scores [n, score_cols] (fp32, row-major).  Each box coordinate is flipped back (same
+ *   formula as the mapping) and divided by the view's scale factor; boxes and scores are then summed over the views in
+ *   order and divided by V: out_boxes [n, box_cols], out_scores [n, score_cols].  n <= 65535.
+ * dm_merge_aug_masks: logit_tab (int64, device) [V] = address of view v's logits [n, K, S, S] (fp32); labels (int64,
+ *   device) [n], read only when K > 1 (clamped into [0, K)).  out [n, 1, S, S] = the mean over the views, in order, of
+ *   dm_sigmoid of the label's channel read at the un-flipped position ('horizontal': column S - 1 - x, 'vertical': row
+ *   S - 1 - y).  The sigmoid is the paste kernels' apply_sigmoid, so one view gives the probabilities dm_paste_masks
+ *   computes from the logits, bit for bit. */
+#define DM_AUG_VIEW_FLOATS 8
+#define DM_AUG_FLIP_NONE 0
+#define DM_AUG_FLIP_HORIZONTAL 1
+#define DM_AUG_FLIP_VERTICAL 2
+int dm_bbox_mapping_multi(const float* boxes, int box_stride, int n, int V, const float* view_tab, float* out_rois,
+                          dm_stream_t stream);
+int dm_merge_aug_bboxes(const long long* ptr_tab, const float* view_tab, int V, int n, int box_cols, int score_cols,
+                        float* out_boxes, float* out_scores, dm_stream_t stream);
+int dm_merge_aug_masks(const long long* logit_tab, const float* view_tab, int V, int n, int K, int S, const long long* labels,
+                       float* out, dm_stream_t stream);
 
 /* ===========================================================================
  * Backward (training step).  Replaces what autograd derives for the reference
