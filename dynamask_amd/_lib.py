@@ -88,6 +88,11 @@ SIGNATURES = {
     'dm_bbox_mapping_multi': ([_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp], _c_int),
     'dm_merge_aug_bboxes': ([_vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp], _c_int),
     'dm_merge_aug_masks': ([_vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp], _c_int),
+    'dm_conv3x3_dil_supported': ([_c_int, _c_int, _c_int, _c_int, _c_int, _c_int], _c_int),
+    'dm_conv3x3_dil_fwd': ([_vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _c_int, _c_int, _vp, _vp], _c_int),
+    'dm_conv3x3_multidil_supported': ([_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp], _c_int),
+    'dm_conv3x3_multidil_fwd': ([_vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _c_int, _vp, _c_int, _vp, _vp], _c_int),
+    'dm_sigmoid_fwd': ([_vp, ctypes.c_longlong, _vp, _vp], _c_int),
     'dm_fc_scratch_floats': ([_c_int, _c_int, _c_int], ctypes.c_longlong),
     'dm_fc_fwd': ([_vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp], _c_int),
     'dm_sgd_momentum_step': ([_vp, _vp, _vp, ctypes.c_longlong, _c_float, _c_float, _c_float, _c_float, _c_int, _vp], _c_int),

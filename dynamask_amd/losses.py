@@ -224,3 +224,33 @@ class L1Loss(nn.Module):
         w = weight if weight is not None else torch.ones_like(pred)
         scale = self._scale(pred.numel(), avg_factor, reduction_override)
         return _L1PosFn.apply(pred.reshape(n, -1), lab, target.reshape(n, -1), w.reshape(n, -1), 1, scale)
+
+
+@LOSSES.register_module()
+class RefineCrossEntropyLoss(nn.Module):
+    """mmdet/models/losses/cross_entropy_loss.py RefineCrossEntropyLoss: constructor only, so that configs/refinemask build
+    (RefineMaskHead owns one).  The loss itself belongs to RefineMask training, the follow-up to its inference."""
+
+    def __init__(self, stage_instance_loss_weight=[1.0, 1.0, 1.0, 1.0], semantic_loss_weight=1.0, boundary_width=2,
+                 start_stage=1):
+        super().__init__()
+        self.stage_instance_loss_weight = stage_instance_loss_weight
+        self.semantic_loss_weight = semantic_loss_weight
+        self.boundary_width = boundary_width
+        self.start_stage = start_stage
+
+    def forward(self, stage_instance_preds, semantic_pred, stage_instance_targets, semantic_target):
+        raise NotImplementedError('RefineCrossEntropyLoss.forward: RefineMask training is the follow-up to its inference')
+
+
+@LOSSES.register_module()
+class SmoothL1Loss(nn.Module):
+    """losses/smooth_l1_loss.py SmoothL1Loss: constructor only, so that configs/refinemask/cityscapes (whose bbox head
+    names it) builds for inference.  Its training is part of the RefineMask training follow-up."""
+
+    def __init__(self, beta=1.0, reduction='mean', loss_weight=1.0):
+        super().__init__()
+        self.beta, self.reduction, self.loss_weight = beta, reduction, loss_weight
+
+    def forward(self, *a, **k):
+        raise NotImplementedError('SmoothL1Loss.forward: bbox training with configs/refinemask is the follow-up to its inference')

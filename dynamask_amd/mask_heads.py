@@ -785,3 +785,212 @@ class FCNMaskHead(nn.Module):
         for lab, r in zip(det_labels.tolist(), rles):
             cls_segms[lab].append(r)
         return cls_segms
+
+
+# ---------------------------------------------------------------- RefineMask head (inference)
+class DilatedConvModule(nn.Module):
+    """mmcv ConvModule(3x3, padding = dilation) without norm: conv(bias) (+ ReLU); keys ``conv.weight/bias``.  Runs on the
+    any-width dilated kernel (ops.conv3x3_dil, exact fp32 in every precision mode): RefineMask's semantic convs on the
+    whole stride-4 FPN map (d = 1) and MultiBranchFusion's branches."""
+
+    def __init__(self, in_channels, out_channels, kernel_size=3, padding=1, dilation=1, conv_cfg=None, norm_cfg=None,
+                 act_cfg=dict(type='ReLU')):
+        super().__init__()
+        if conv_cfg is not None or norm_cfg is not None:
+            raise NotImplementedError('conv_cfg / norm_cfg are None in configs/refinemask')
+        if kernel_size != 3 or padding != dilation or not 1 <= dilation <= 8:
+            raise NotImplementedError('3x3 convolutions with padding = dilation in [1, 8] only')
+        self.conv = _Conv(in_channels, out_channels, 3)
+        self.dilation = dilation
+        self.with_activation = act_cfg is not None
+
+    def packed(self):
+        return self.conv.packed([self.conv.in_channels], 'fp32')
+
+    def forward(self, x):
+        b = self.conv.bias.detach() if self.conv.bias is not None else None
+        return ops.conv3x3_dil(x, self.packed(), b, self.conv.out_channels, self.dilation, relu=self.with_activation)
+
+
+class MultiBranchFusion(nn.Module):
+    """refine_mask_head.py:17-33: merge_conv(sum_b relu(conv_{d_b}(x) + b_b)), merge_conv 1x1 without activation (the
+    caller's loop applies the ReLU: ``forward(x, relu=True)``).  The branch sum is ONE launch (ops.conv3x3_multidil; the
+    unfused sequence with ops.FUSED_MULTIDIL[0] = False, same bits).  Keys dilation_conv_{1,2,3}.conv.*, merge_conv.conv.*."""
+
+    def __init__(self, feat_dim, dilations=[1, 3, 5]):
+        super().__init__()
+        if len(dilations) != 3:
+            raise NotImplementedError('MultiBranchFusion has three branches (refine_mask_head.py:28-31)')
+        self.dilations = list(dilations)
+        for idx, dilation in enumerate(dilations):
+            self.add_module(f'dilation_conv_{idx + 1}', DilatedConvModule(feat_dim, feat_dim, 3, padding=dilation,
+                                                                          dilation=dilation))
+        self.merge_conv = ConvModule(feat_dim, feat_dim, 1, act_cfg=None)
+        self.feat_dim = feat_dim
+
+    def branches(self):
+        return [getattr(self, f'dilation_conv_{i + 1}') for i in range(3)]
+
+    def branch_sum(self, x, fused=None):
+        br = self.branches()
+        return ops.conv3x3_multidil(x, [m.packed() for m in br], [m.conv.bias.detach() for m in br], self.feat_dim,
+                                    self.dilations, relu=True, fused=fused)
+
+    def forward(self, x, relu=False):
+        return self.merge_conv.conv.run(self.branch_sum(x), relu=relu)
+
+
+class RefineSFMStage(nn.Module):
+    """refine_mask_head.py:36-136 (fusion_type 'MultiBranchFusion'), inference.  Same keys as the reference's SFMStage."""
+
+    def __init__(self, semantic_in_channel=256, semantic_out_channel=256, instance_in_channel=256, instance_out_channel=256,
+                 fusion_type='MultiBranchFusion', dilations=[1, 3, 5], out_size=14, num_classes=80, semantic_out_stride=4,
+                 mask_use_sigmoid=False, upsample_cfg=dict(type='bilinear', scale_factor=2)):
+        super().__init__()
+        if fusion_type != 'MultiBranchFusion':
+            raise NotImplementedError('fusion_type is MultiBranchFusion in configs/refinemask')
+        if upsample_cfg.get('type') != 'bilinear' or upsample_cfg.get('scale_factor') != 2:
+            raise NotImplementedError('the SFM stage upsample is bilinear x2 in configs/refinemask')
+        self.semantic_out_stride = semantic_out_stride
+        self.mask_use_sigmoid = mask_use_sigmoid
+        self.num_classes = num_classes
+        self.out_size = out_size
+        self.instance_in_channel = instance_in_channel
+        self.instance_out_channel = instance_out_channel
+        self.semantic_transform_in = _Conv(semantic_in_channel, semantic_out_channel, 1)
+        self.semantic_transform_out = _Conv(semantic_out_channel, semantic_out_channel, 1)
+        self.instance_logits = _Conv(instance_in_channel, num_classes, 1)
+        fuse_in_channel = instance_in_channel + semantic_out_channel + 2
+        self.fuse_conv = nn.ModuleList([_Conv(fuse_in_channel, instance_in_channel, 1),
+                                        MultiBranchFusion(instance_in_channel, dilations=dilations)])
+        self.fuse_transform_out = _Conv(instance_in_channel, instance_out_channel - 2, 1)
+
+    def semantic_map(self, semantic_feat):
+        """relu(semantic_transform_in(semantic_feat)) on the whole map (refine_mask_head.py:103): no RoI enters it."""
+        return self.semantic_transform_in.run(semantic_feat, relu=True)
+
+    def forward(self, instance_feats, semantic_feat, semantic_prob, rois, roi_labels, sem=None):
+        """-> (instance logits [n, 1, S, S], the next stage's features [n, out, 2S, 2S]).  ``semantic_prob``: the
+        (sigmoid of the) semantic logits [B, 1, H, W]; ``sem``: a precomputed ``semantic_map``."""
+        n, c, s = instance_feats.shape[0], self.instance_in_channel, self.out_size
+        if sem is None:
+            sem = self.semantic_map(semantic_feat)
+        scale = 1.0 / self.semantic_out_stride
+        # instance-wise semantic feats: SingleRoIExtractor (RoIAlign aligned, sampling_ratio 0, one level) + relu(1x1)
+        ins_sem = self.semantic_transform_out.run(ops.roi_align([sem], rois, s, [scale], 0), relu=True)
+        # [instance mask | semantic mask]: the two extra channels of the fusion input (the same-size interpolations of
+        # refine_mask_head.py:111,118-119 are identities)
+        masks = torch.empty((n, 2, s, s), device=instance_feats.device, dtype=torch.float32)
+        nc = self.num_classes
+        w, b = self.instance_logits.weight.detach().view(nc, c), self.instance_logits.bias.detach()
+        ip, _ = ops.class_logits(instance_feats, w, b, w, b, roi_labels, sig_out=masks if self.mask_use_sigmoid else None)
+        if not self.mask_use_sigmoid:
+            masks[:, 0:1].copy_(ip)
+        masks[:, 1:2].copy_(ops.roi_align([semantic_prob], rois, s, [scale], 0))
+        fused = self.fuse_conv[0].run([instance_feats, ins_sem, masks], relu=True)
+        fused = self.fuse_conv[1](fused, relu=True)
+        fused = self.fuse_transform_out.run(fused, relu=True)
+        # relu(bilinear x2, align_corners=False) of the features, align_corners=True x2 of the two masks (:124-132)
+        nxt = torch.cat([ops.upsample2x(fused, align_corners=False, relu=True), ops.upsample2x(masks, align_corners=True)], 1)
+        return ip, nxt
+
+
+@HEADS.register_module()
+class RefineMaskHead(nn.Module):
+    """refine_mask_head.py:139-337, inference: same constructor kwargs and ``state_dict`` keys as the reference, so
+    RefineMask checkpoints load.  ``forward`` returns (stage_instance_preds, semantic_pred) as the reference.  Training
+    (``loss``, ``get_targets``) is the follow-up: RefineCrossEntropyLoss.forward raises."""
+
+    def __init__(self, num_convs_instance=2, num_convs_semantic=4, conv_in_channels_instance=256,
+                 conv_in_channels_semantic=256, conv_kernel_size_instance=3, conv_kernel_size_semantic=3,
+                 conv_out_channels_instance=256, conv_out_channels_semantic=256, conv_cfg=None, norm_cfg=None,
+                 fusion_type='MultiBranchFusion', dilations=[1, 3, 5], semantic_out_stride=4, mask_use_sigmoid=False,
+                 stage_num_classes=[80, 80, 80, 80], stage_sup_size=[14, 28, 56, 112],
+                 upsample_cfg=dict(type='bilinear', scale_factor=2),
+                 loss_cfg=dict(type='RefineCrossEntropyLoss', stage_instance_loss_weight=[0.25, 0.5, 0.75, 1.0],
+                               semantic_loss_weight=1.0, boundary_width=2, start_stage=1)):
+        super().__init__()
+        self.num_convs_instance = num_convs_instance
+        self.conv_kernel_size_instance = conv_kernel_size_instance
+        self.conv_in_channels_instance = conv_in_channels_instance
+        self.conv_out_channels_instance = conv_out_channels_instance
+        self.num_convs_semantic = num_convs_semantic
+        self.conv_kernel_size_semantic = conv_kernel_size_semantic
+        self.conv_in_channels_semantic = conv_in_channels_semantic
+        self.conv_out_channels_semantic = conv_out_channels_semantic
+        self.conv_cfg, self.norm_cfg = conv_cfg, norm_cfg
+        self.semantic_out_stride = semantic_out_stride
+        self.stage_sup_size = stage_sup_size
+        self.stage_num_classes = stage_num_classes
+        self.mask_use_sigmoid = mask_use_sigmoid
+        if conv_kernel_size_semantic != 3:
+            raise NotImplementedError('the semantic convs are 3x3 in configs/refinemask')
+
+        convs = []
+        for i in range(num_convs_instance):
+            cin = conv_in_channels_instance if i == 0 else conv_out_channels_instance
+            convs.append(ConvModule(cin, conv_out_channels_instance, conv_kernel_size_instance, dilation=1, padding=1))
+        self.instance_convs = nn.ModuleList(convs)
+        convs = []
+        for i in range(num_convs_semantic):
+            cin = conv_in_channels_semantic if i == 0 else conv_out_channels_semantic
+            convs.append(DilatedConvModule(cin, conv_out_channels_semantic, 3, padding=1, dilation=1))
+        self.semantic_convs = nn.ModuleList(convs)
+        self.loss_func = build_loss(loss_cfg)
+
+        assert len(self.stage_sup_size) > 1
+        self.stages = nn.ModuleList()
+        out_channel = conv_out_channels_instance
+        for idx, out_size in enumerate(self.stage_sup_size[:-1]):
+            in_channel = out_channel
+            out_channel = in_channel // 2
+            self.stages.append(RefineSFMStage(
+                semantic_in_channel=conv_out_channels_semantic, semantic_out_channel=in_channel,
+                instance_in_channel=in_channel, instance_out_channel=out_channel, fusion_type=fusion_type,
+                dilations=dilations, out_size=out_size, num_classes=self.stage_num_classes[idx],
+                semantic_out_stride=semantic_out_stride, mask_use_sigmoid=mask_use_sigmoid, upsample_cfg=upsample_cfg))
+        self.final_instance_logits = _Conv(out_channel, self.stage_num_classes[-1], 1)
+        self.semantic_logits = _Conv(conv_out_channels_semantic, 1, 1)
+
+    def init_weights(self):
+        for m in [self.final_instance_logits, self.semantic_logits]:
+            nn.init.kaiming_normal_(m.weight, mode='fan_out', nonlinearity='relu')
+            nn.init.constant_(m.bias, 0)
+
+    def semantic_forward(self, semantic_feat):
+        """The four 3x3 semantic convs on the whole stride-4 map, then semantic_logits -> (features, semantic_pred)
+        (refine_mask_head.py:235-238): once per call, for all images of the batch."""
+        for conv in self.semantic_convs:
+            semantic_feat = conv(semantic_feat)
+        return semantic_feat, self.semantic_logits.run(semantic_feat)
+
+    def forward(self, instance_feats, semantic_feat, rois, roi_labels):
+        """refine_mask_head.py:231-252 -> (stage_instance_preds [n, 1, S_k, S_k] per stage, semantic_pred [B, 1, H, W])."""
+        for conv in self.instance_convs:
+            instance_feats = conv(instance_feats)
+        semantic_feat, semantic_pred = self.semantic_forward(semantic_feat)
+        semantic_prob = ops.sigmoid(semantic_pred) if self.mask_use_sigmoid else semantic_pred
+        roi_labels = roi_labels.long().contiguous()
+        rois = rois.contiguous()
+        stage_instance_preds = []
+        for stage in self.stages:
+            ip, instance_feats = stage(instance_feats, semantic_feat, semantic_prob, rois, roi_labels)
+            stage_instance_preds.append(ip)
+        # (refine_mask_head.py:247-248 clamps the labels to 0 for the class-agnostic last stage (LVIS): the kernel clamps
+        # every label into [0, num_classes - 1] itself, which for one class is that clamp)
+        nc = self.stage_num_classes[-1]
+        c = self.final_instance_logits.in_channels
+        w, b = self.final_instance_logits.weight.detach().view(nc, c), self.final_instance_logits.bias.detach()
+        ip, _ = ops.class_logits(instance_feats, w, b, w, b, roi_labels)
+        stage_instance_preds.append(ip)
+        return stage_instance_preds, semantic_pred
+
+    # refine_mask_head.py:289-337 = dynamask_head.py:279-342 (sigmoid, paste, threshold)
+    get_seg_masks = DynaMaskHead.get_seg_masks
+    get_seg_rles = DynaMaskHead.get_seg_rles
+
+    def get_targets(self, *a, **k):
+        raise NotImplementedError('RefineMask training (targets, RefineCrossEntropyLoss) is the follow-up to inference')
+
+    def loss(self, *a, **k):
+        raise NotImplementedError('RefineMask training (targets, RefineCrossEntropyLoss) is the follow-up to inference')

@@ -954,6 +954,94 @@ def deform_conv_tout(x, offset, w_packed, cout, deform_groups, w2t, b2, m2, out2
     return dcn
 
 
+# ------------------------------------------------ RefineMask: dilated and any-width 3x3 convolutions (csrc/conv_dilated.hip)
+# Exact fp32 in every precision mode (as the DCN kernels): the bf16x3 mode does not reach these launches.
+def _dil_check(x, w_packed, cout):
+    _chk(x, 'x')
+    _chk(w_packed, 'w_packed')
+    if conv_layout(w_packed) != 'fp32':
+        raise ValueError('the dilated 3x3 kernels read the exact fp32 layout (pack_conv_weight(precision="fp32"))')
+    assert w_packed.numel() == packed_floats(cout, 3, [x.shape[1]]), 'weights packed for another shape'
+
+
+def _dil_out(x, cout, out):
+    NB, _, H, W = x.shape
+    if out is None:
+        return torch.empty((NB, cout, H, W), device=x.device, dtype=torch.float32)
+    _chk(out, 'out')
+    assert tuple(out.shape) == (NB, cout, H, W)
+    return out
+
+
+def conv3x3_dil_supported(x, cout, dilation):
+    """Does ``conv3x3_dil`` take this shape (dm_conv3x3_dil_supported: C % 8 == 0, 1 <= dilation <= 8, any H, W)?"""
+    NB, C, H, W = x.shape
+    return bool(lib().dm_conv3x3_dil_supported(NB, C, H, W, int(cout), int(dilation)))
+
+
+def conv3x3_dil(x, w_packed, bias, cout, dilation, relu=False, add=False, out=None):
+    """conv3x3(x, dilation = padding = ``dilation``) + bias (+ ReLU) -> [NB, cout, H, W] (dm_conv3x3_dil_fwd).  ``add``:
+    ``out`` += that value (after the ReLU).  ``w_packed``: ``pack_conv_weight`` of the [cout, C, 3, 3] weight."""
+    _dil_check(x, w_packed, cout)
+    if bias is not None:
+        _chk(bias, 'bias')
+    if add and out is None:
+        raise ValueError('add=True needs out')
+    out = _dil_out(x, cout, out)
+    NB, C, H, W = x.shape
+    check(lib().dm_conv3x3_dil_fwd(_p(x), NB, C, H, W, _p(w_packed), _p(bias), cout, int(dilation),
+                                   (1 if relu else 0) | (4 if add else 0), _p(out), _stream()), 'dm_conv3x3_dil_fwd')
+    return out
+
+
+def conv3x3_multidil_supported(x, cout, dilations):
+    NB, C, H, W = x.shape
+    return bool(lib().dm_conv3x3_multidil_supported(NB, C, H, W, int(cout), len(dilations), _int_array(dilations)))
+
+
+# MultiBranchFusion: the three branches as ONE launch (dm_conv3x3_multidil_fwd); False: three dm_conv3x3_dil_fwd, the
+# second and third adding into the first's output (the A/B baseline; same bits)
+FUSED_MULTIDIL = [os.environ.get('DM_FUSED_MULTIDIL', '1') != '0']
+
+
+def conv3x3_multidil(x, w_packeds, biases, cout, dilations, relu=True, out=None, fused=None):
+    """sum_b act(conv3x3_{dilations[b]}(x) + biases[b]) -> [NB, cout, H, W], act = ReLU if ``relu``: MultiBranchFusion's
+    branch sum (refine_mask_head.py:28-31).  ``fused`` (default FUSED_MULTIDIL): one launch, else the unfused sequence."""
+    k = len(dilations)
+    assert len(w_packeds) == k and len(biases) == k
+    for w in w_packeds:
+        _dil_check(x, w, cout)
+    for b in biases:
+        if b is not None:
+            _chk(b, 'bias')
+    out = _dil_out(x, cout, out)
+    if fused is None:
+        fused = FUSED_MULTIDIL[0]
+    if fused:
+        NB, C, H, W = x.shape
+        bias_arr = (ctypes.c_void_p * k)(*[0 if b is None else b.data_ptr() for b in biases])
+        if hazard.ENABLED[0]:
+            hazard.note_ptr_array(bias_arr, [b for b in biases if b is not None])
+        check(lib().dm_conv3x3_multidil_fwd(_p(x), NB, C, H, W, _ptr_array(w_packeds), bias_arr, cout, k, _int_array(dilations),
+                                            1 if relu else 0, _p(out), _stream()), 'dm_conv3x3_multidil_fwd')
+        return out
+    for i, (w, b, d) in enumerate(zip(w_packeds, biases, dilations)):
+        conv3x3_dil(x, w, b, cout, d, relu=relu, add=i > 0, out=out)
+    return out
+
+
+def sigmoid(x, out=None):
+    """Elementwise logistic (dm_sigmoid_fwd; the paste kernels' expression)."""
+    _chk(x, 'x')
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _chk(out, 'out')
+        assert out.shape == x.shape
+    check(lib().dm_sigmoid_fwd(_p(x), x.numel(), _p(out), _stream()), 'dm_sigmoid_fwd')
+    return out
+
+
 def pack_deconv_weight(w, precision='fp32'):
     """``precision='bf16x3'``: dm_deconv_pack_weight_bf16x3's layout, marked as such (``conv_layout``)."""
     _chk(w, 'weight')

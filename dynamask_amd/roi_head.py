@@ -1116,3 +1116,57 @@ class StandardRoIHead(DynaMaskRoIHead):
             mask_results = self._mask_forward(x, mask_rois)
         to_segs = self.mask_head.get_seg_rles if encode else self.mask_head.get_seg_masks
         return to_segs(mask_results['mask_pred'], _bboxes, det_labels, self.test_cfg, ori_shape, scale_factor, rescale)
+
+
+@HEADS.register_module()
+class RefineRoIHead(DynaMaskRoIHead):
+    """``RefineRoIHead`` -- mmdet/models/roi_heads/refine_roi_head.py:10-113, inference: the RoI head of
+    configs/refinemask, whose mask head is ``RefineMaskHead``.  Like ``StandardRoIHead`` it keeps the parent's bbox
+    branch, ``simple_test``, ``batch_simple_test`` and ``aug_test``, and overrides the mask hooks: ``_mask_forward``
+    (refine_roi_head.py:75-80) and the merged 112 x 112 logits (``_merged_logits``: the boundary-aware merge from stage 1,
+    :102-113, the same merge as DynaMask's, ops.boundary_merge_).  The four semantic 3x3 convolutions run once per call
+    on the whole stride-4 map of every image of the batch (the reference runs them once per chunk of 100 RoIs).  The
+    fork's ``BaseRoIHead`` builds ``mask_predictor`` / ``semantic_roi_extractor`` for EVERY RoI head (Quirk Q4): the
+    parent's constructor does the same, so the ``state_dict`` keys are the reference's.  Training and HIP-graph
+    capture are the follow-up (NotImplementedError)."""
+
+    def _mask_forward(self, x, rois, roi_labels, **kw):
+        """refine_roi_head.py:75-80 -> dict(stage_instance_preds, semantic_pred)."""
+        ext = self.mask_roi_extractor
+        rois = rois.contiguous()
+        with torch.no_grad():
+            ins_feats = ext(x[:ext.num_inputs], rois)
+            ips, sem_pred = self.mask_head(ins_feats, x[0].contiguous(), rois, roi_labels)
+        return dict(stage_instance_preds=ips, semantic_pred=sem_pred)
+
+    def _merged_logits(self, x, mask_rois, det_labels):
+        """The merged logits of the last stage [n, 1, S, S]: stage k's (k >= 1) merged into stage k + 1's where the
+        coarser one is not on a boundary (refine_roi_head.py:102-113), in place."""
+        res = self._mask_forward(x, mask_rois, det_labels)
+        return self.merge_stage_preds(res['stage_instance_preds'])
+
+    def simple_test_mask_logits(self, x, det_bboxes, det_labels, scale_factor=1.0, rescale=False):
+        if det_bboxes.shape[0] == 0:
+            s = self.mask_head.stage_sup_size[-1]
+            return det_bboxes.new_zeros((0, 1, s, s))
+        _bboxes = det_bboxes[:, :4] * scale_factor if rescale else det_bboxes
+        return self._merged_logits(x, bbox2roi([_bboxes]).contiguous(), det_labels)
+
+    def enable_inference_graphs(self, on=True, buckets=None, batch_buckets=None):
+        if on:
+            raise NotImplementedError('RefineRoIHead: HIP-graph capture of the RefineMask call is a follow-up')
+        self._mask_graphs = None
+        return None
+
+    def forward_train(self, x, img_metas, proposal_list, gt_bboxes, gt_labels, gt_bboxes_ignore=None, gt_masks=None):
+        raise NotImplementedError('RefineRoIHead.forward_train: RefineMask training (targets, RefineCrossEntropyLoss, the '
+                                  'dilated-convolution gradients) is the follow-up to its inference')
+
+    def _mask_forward_train(self, *a, **k):
+        raise NotImplementedError('RefineRoIHead._mask_forward_train: RefineMask training is the follow-up to its inference')
+
+    def dynamic_mask_logits(self, *a, **k):
+        raise NotImplementedError('RefineRoIHead: per-RoI early exit is DynaMask\'s, RefineMask has none')
+
+    def dynamic_test_mask(self, *a, **k):
+        raise NotImplementedError('RefineRoIHead: per-RoI early exit is DynaMask\'s, RefineMask has none')

@@ -55,7 +55,7 @@ extern "C" {
 typedef void* dm_stream_t; /* hipStream_t */
 
 const char* dm_error_string(int code);
-/* ABI version: bumped whenever a signature or the meaning of an argument changes (8: flag bit 3 of dm_conv2d_fwd; 9: RoI assignment / bbox training entry points; 10: dm_detail_target takes the fuse weights from device memory; 11: FCNMaskHead upsample backward; 12: dm_fc_fwd takes a scratch slab, deterministic split-K; 13: dm_deform_coord_grad / dm_deform_col2im, dm_conv2d_fwd_masked, dm_scale, dm_polygon_mask_targets, dm_ignore_columns, dm_upsample2x_bilinear_bwd overwrites; 14: dm_random_sample, dm_bn_relu_maxpool_argmax, the *_fx deterministic accumulators + dm_fx_to_float, dm_mask_loss_fwd_bwd takes a scratch, dm_conv2d_wgrad takes the bias gradient, dm_conv_pack_weight_batch, dm_mask_loss_stage; 15: dm_class_logits_up2x_fwd; 16: dm_conv2d_wgrad_slab / dm_conv2d_wgrad_scratch_floats; 17: dm_class_logits_bwd_slab / dm_class_logits_bwd_scratch_floats; 18: dm_reload_env_knobs, dm_roi_align_fwd_ws / dm_roi_align_workspace_bytes, dm_conv_pack_weight_split / dm_conv_packed_floats_split and flag bits 4, 5 of dm_conv2d_fwd; 19: dm_dcn_bwd_data_fused and its pack; 20: dm_conv2d_fwd_ws / dm_conv2d_splitk_floats; 21: dm_deform_conv_fwd_ws / dm_deform_conv_splitk_floats; 22: the bf16-split layouts (dm_conv_pack_weight_split, dm_conv_packed_floats_split, flag bits 4 / 5 of dm_conv2d_fwd) and the one-kernel DCN data gradient (dm_dcn_bwd_*) REMOVED -- measured, never the parity path, see docs/HISTORY.md; 23: dm_bn_stats takes mean_shift, dm_roi_align_bwd takes the gather form for 16 < P <= 64; 24: dm_build_info; 25: dm_boundary_merge_chain, dm_stage_head_fwd; 26: dm_conv1x1_group_fwd; 27: dm_deform_conv_tout_fwd / dm_deform_conv_tout_supported; 28: the opt-in bf16x3 mode -- dm_conv_pack_weight_bf16x3 / dm_conv_packed_floats_bf16x3 and flag bit 4 of dm_conv2d_fwd, dm_conv2d_fwd_ws and dm_conv1x1_group_fwd; dm_deconv_pack_weight_bf16x3 and flag bit 4 of dm_deconv2x2_fwd).  Entry points ADDED without a signature or meaning change leave the number as it is (the loader resolves every symbol of _lib.SIGNATURES by name, so an older library fails at load): the multi-image post-processing dm_nms_mask_segmented / dm_nms_reduce_segmented, dm_paste_masks_multi, dm_paste_rle_multi / dm_rle_multi_scratch_ints; the test-time augmentation dm_bbox_mapping_multi, dm_merge_aug_bboxes, dm_merge_aug_masks. */
+/* ABI version: bumped whenever a signature or the meaning of an argument changes (8: flag bit 3 of dm_conv2d_fwd; 9: RoI assignment / bbox training entry points; 10: dm_detail_target takes the fuse weights from device memory; 11: FCNMaskHead upsample backward; 12: dm_fc_fwd takes a scratch slab, deterministic split-K; 13: dm_deform_coord_grad / dm_deform_col2im, dm_conv2d_fwd_masked, dm_scale, dm_polygon_mask_targets, dm_ignore_columns, dm_upsample2x_bilinear_bwd overwrites; 14: dm_random_sample, dm_bn_relu_maxpool_argmax, the *_fx deterministic accumulators + dm_fx_to_float, dm_mask_loss_fwd_bwd takes a scratch, dm_conv2d_wgrad takes the bias gradient, dm_conv_pack_weight_batch, dm_mask_loss_stage; 15: dm_class_logits_up2x_fwd; 16: dm_conv2d_wgrad_slab / dm_conv2d_wgrad_scratch_floats; 17: dm_class_logits_bwd_slab / dm_class_logits_bwd_scratch_floats; 18: dm_reload_env_knobs, dm_roi_align_fwd_ws / dm_roi_align_workspace_bytes, dm_conv_pack_weight_split / dm_conv_packed_floats_split and flag bits 4, 5 of dm_conv2d_fwd; 19: dm_dcn_bwd_data_fused and its pack; 20: dm_conv2d_fwd_ws / dm_conv2d_splitk_floats; 21: dm_deform_conv_fwd_ws / dm_deform_conv_splitk_floats; 22: the bf16-split layouts (dm_conv_pack_weight_split, dm_conv_packed_floats_split, flag bits 4 / 5 of dm_conv2d_fwd) and the one-kernel DCN data gradient (dm_dcn_bwd_*) REMOVED -- measured, never the parity path, see docs/HISTORY.md; 23: dm_bn_stats takes mean_shift, dm_roi_align_bwd takes the gather form for 16 < P <= 64; 24: dm_build_info; 25: dm_boundary_merge_chain, dm_stage_head_fwd; 26: dm_conv1x1_group_fwd; 27: dm_deform_conv_tout_fwd / dm_deform_conv_tout_supported; 28: the opt-in bf16x3 mode -- dm_conv_pack_weight_bf16x3 / dm_conv_packed_floats_bf16x3 and flag bit 4 of dm_conv2d_fwd, dm_conv2d_fwd_ws and dm_conv1x1_group_fwd; dm_deconv_pack_weight_bf16x3 and flag bit 4 of dm_deconv2x2_fwd).  Entry points ADDED without a signature or meaning change leave the number as it is (the loader resolves every symbol of _lib.SIGNATURES by name, so an older library fails at load): the multi-image post-processing dm_nms_mask_segmented / dm_nms_reduce_segmented, dm_paste_masks_multi, dm_paste_rle_multi / dm_rle_multi_scratch_ints; the test-time augmentation dm_bbox_mapping_multi, dm_merge_aug_bboxes, dm_merge_aug_masks; RefineMask's dilated / any-width 3x3 convolutions and the sigmoid of its semantic map (section K21). */
 int dm_abi_version(void);
 /* "libdynamask_hip abi=N arch=gfx950 compiler=<clang version> flags=<the product-wide flags of dynamask_amd/build.py>"
  * (static storage).  The library must be compiled WITHOUT packed fp32 instructions (flag "-packed-fp32-ops", see
@@ -778,6 +778,36 @@ int dm_class_logits_bwd_fx(const float* x, int N, int C, int HW, const float* w_
 int dm_point_sample_bwd_fx(const float* grad_out, int B, int C, int H, int W, const float* rois, int N, int S,
                            float spatial_scale, long long* grad_feat_fx, dm_stream_t stream);
 int dm_fx_to_float(long long* fx, long long n, float* out, int accumulate, int clear, dm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * K21  RefineMask: 3x3 convolutions with a dilation, on maps of any width (csrc/conv_dilated.hip), and a sigmoid.
+ * replaces: ConvModule(3x3, padding = dilation = d) of refine_mask_head.py -- the semantic_convs on the whole stride-4
+ *           FPN map (d = 1) and MultiBranchFusion's dilation_conv_{1,2,3} (d = 1, 3, 5; refine_mask_head.py:17-33).
+ * x [NB, C, H, W]; w_packed: dm_conv_pack_weight(ksize = 3, one source) of the [Cout, C, 3, 3] weight (the layout
+ * dm_conv2d_fwd reads); bias [Cout] or NULL; out [NB, Cout, H, W].  Exact fp32 (v_mfma_f32_32x32x2_f32) only.
+ * flags: bit 0 ReLU; bit 2 ADD: out = out + v, where v is the value the call would otherwise store (i.e. after the
+ * ReLU -- NOT dm_conv2d_fwd's bit 1, which adds before the ReLU and is refused here with DM_ERR_INVALID_ARG); bit 3 is
+ * accepted and ignored; bit 4 (the bf16x3 layout) returns DM_ERR_UNSUPPORTED.
+ * dm_conv3x3_dil_supported: 1 exactly when NB >= 1, C >= 8 with C % 8 == 0, H >= 1, W >= 1 (no upper bound on
+ * either: a workgroup stages an 8 x 16 pixel block plus a halo of d), Cout >= 1, 1 <= dilation <= 8, and the grid
+ * (NB * ceil(H / 8) * ceil(W / 16) pixel blocks times ceil(roundup(Cout, 32) / (Cout <= 64 ? 64 : 128)) cout tiles)
+ * has at most 2^31 - 1 workgroups.  dm_conv3x3_dil_fwd returns DM_ERR_UNSUPPORTED for anything else.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int dm_conv3x3_dil_supported(int NB, int C, int H, int W, int Cout, int dilation);
+int dm_conv3x3_dil_fwd(const float* x, int NB, int C, int H, int W, const float* w_packed, const float* bias, int Cout,
+                       int dilation, int flags, float* out, dm_stream_t stream);
+/* MultiBranchFusion's branch sum in ONE launch: out (+)= sum_b act(conv3x3_{dilations[b]}(x, w_packed[b]) + bias[b]),
+ * act = ReLU when flag bit 0 is set.  w_packed / bias / dilations: host arrays of num_branches entries (bias may be NULL,
+ * or hold NULL entries).  The branches are added as ((t_0 + t_1) + t_2): bit for bit what three dm_conv3x3_dil_fwd
+ * calls give, the second and third with bit 2.  Flags as dm_conv3x3_dil_fwd.  dm_conv3x3_multidil_supported: 1 exactly
+ * when num_branches == 3, every dilation is in [1, 8] and dm_conv3x3_dil_supported accepts the shape. */
+int dm_conv3x3_multidil_supported(int NB, int C, int H, int W, int Cout, int num_branches, const int* dilations);
+int dm_conv3x3_multidil_fwd(const float* x, int NB, int C, int H, int W, const float* const* w_packed,
+                            const float* const* bias, int Cout, int num_branches, const int* dilations, int flags,
+                            float* out, dm_stream_t stream);
+/* out[i] = 1 / (1 + exp(-x[i])) for i < n (the paste kernels' logistic, bit for bit): RefineMask's sigmoid(semantic_pred)
+ * (refine_mask_head.py:115-117), n = B * H * W.  out may equal x. */
+int dm_sigmoid_fwd(const float* x, long long n, float* out, dm_stream_t stream);
 
 #ifdef __cplusplus
 }
