@@ -93,6 +93,15 @@ SIGNATURES = {
     'dm_conv3x3_multidil_supported': ([_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp], _c_int),
     'dm_conv3x3_multidil_fwd': ([_vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _c_int, _vp, _c_int, _vp, _vp], _c_int),
     'dm_sigmoid_fwd': ([_vp, ctypes.c_longlong, _vp, _vp], _c_int),
+    'dm_point_select_supported': ([_c_int, _c_int, _c_int], _c_int),
+    'dm_point_select': ([_vp, _c_int, _c_int, _c_int, _vp, _vp], _c_int),
+    'dm_point_gather_supported': ([_c_int] * 11, _c_int),
+    'dm_point_gather_fwd': ([_vp, _c_int, _c_int, _c_int, _c_int, _vp, _c_int, _vp, _c_int, _c_int, _c_int, _vp, _c_int,
+                             _c_int, _c_int, _c_float, _vp, _vp], _c_int),
+    'dm_point_mlp_supported': ([_c_int] * 8, _c_int),
+    'dm_point_mlp_fwd': ([_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _c_int, _vp, _vp, _c_int,
+                          _vp, _c_int, _vp], _c_int),
+    'dm_point_scatter': ([_vp, _vp, _c_int, _c_int, _vp, _c_int, _vp], _c_int),
     'dm_fc_scratch_floats': ([_c_int, _c_int, _c_int], ctypes.c_longlong),
     'dm_fc_fwd': ([_vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp], _c_int),
     'dm_sgd_momentum_step': ([_vp, _vp, _vp, ctypes.c_longlong, _c_float, _c_float, _c_float, _c_float, _c_int, _vp], _c_int),

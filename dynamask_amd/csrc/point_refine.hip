@@ -1,0 +1,413 @@
+// PointRend inference: the subdivision step of PointRendRoIHead._mask_point_forward_test
+// (mmdet/models/roi_heads/point_rend_roi_head.py:96-128) on the label channel of the refined map.
+//
+//   dm_point_select      per RoI, the P cells of smallest |v| of an [n, HW] map (MaskPointHead.get_roi_rel_points_test:
+//                        topk(-|logit[label]|)), indices in ascending order; at the cut the lower flat index wins.
+//                        One 1024-thread workgroup per RoI: a radix select on the 31 magnitude bits (four 8-bit passes
+//                        over the map, histogram in LDS), then one pass in index order that compacts the selection.
+//                        The map (up to 224^2 = 50 176 floats, 196 KiB) does not fit the LDS: every pass reads it from
+//                        the L2 / memory.
+//   dm_point_gather_fwd  per (RoI, selected cell): the cell centre (get_roi_rel_points_test's fp32 chain), the C-channel
+//                        point_sample of the RoI's image of the feature map at rel_roi_point_to_rel_img_point of it, and
+//                        the NC-channel point_sample of the RoI's coarse logits at the RoI-relative point -> one
+//                        [n, C + NC, P] buffer (the point head's input, fine channels first).
+//   dm_point_mlp_fwd     MaskPointHead.forward (mask_point_head.py:85-104) on that buffer: nfc layers
+//                        relu(W [F, C + NC] x [h; coarse] + b) (F == C: each layer's output takes the place of the fine
+//                        channels), then the label row of fc_logits, written straight into the refined map at the
+//                        selected cells (the scatter_ of :121-124).  Exact fp32 MFMA (v_mfma_f32_32x32x2_f32).
+//   dm_point_scatter     map[r, idx[r, p]] = vals[r, p]: the scatter of the unfused sequence.
+//
+// point_sample is mmcv's: grid_sample(bilinear, zeros, align_corners=False) of points * 2 - 1.  The sample below
+// repeats the fp32 operations of PyTorch's CPU grid sampler (unnormalize (g + 1) * size / 2 - 0.5, weights from the
+// floor distances, corners added nw, ne, sw, se), with every product and sum rounded on its own (no contraction).
+#include "common.h"
+
+namespace {
+
+// ------------------------------------------------------------------------------------------------ selection
+constexpr int SEL_NT = 1024;
+constexpr int SEL_NW = SEL_NT / DM_WAVE;      // 16 waves
+constexpr unsigned MAG = 0x7fffffffu;          // |v| as an unsigned key: the bit pattern orders like the magnitude
+constexpr long long SEL_MAX_HW = 1LL << 24;
+
+__global__ __launch_bounds__(SEL_NT) void point_select_kernel(const float* __restrict__ map, int HW, int P,
+                                                              int* __restrict__ idx) {
+  __shared__ unsigned hist[256];
+  __shared__ unsigned s_digit, s_k;
+  __shared__ unsigned wcnt[2][SEL_NW];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const unsigned* keys = reinterpret_cast<const unsigned*>(map) + (size_t)blockIdx.x * HW;
+  int* out = idx + (size_t)blockIdx.x * P;
+
+  // radix select: after the four passes T = prefix is the key of the P-th smallest, k the number of keys == T to take
+  unsigned prefix = 0, mask = 0, k = (unsigned)P;
+#pragma unroll 1
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    if (tid < 256) hist[tid] = 0;
+    __syncthreads();
+    for (int i = tid; i < HW; i += SEL_NT) {
+      const unsigned key = keys[i] & MAG;
+      if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    if (wave == 0) {
+      unsigned h[4], s = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        h[j] = hist[4 * lane + j];
+        s += h[j];
+      }
+      unsigned incl = s;
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const unsigned t = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += t;
+      }
+      const unsigned excl = incl - s;
+      if (excl < k && k <= incl) {        // exactly one lane: the digit holding the k-th key
+        unsigned c = excl;
+        int dsel = 4 * lane + 3;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if (c + h[j] >= k) {
+            dsel = 4 * lane + j;
+            break;
+          }
+          c += h[j];
+        }
+        s_digit = (unsigned)dsel;
+        s_k = k - c;
+      }
+    }
+    __syncthreads();
+    prefix |= s_digit << shift;
+    mask |= 255u << shift;
+    k = s_k;
+    __syncthreads();
+  }
+
+  // compaction in index order: key < T, or key == T among the first k such indices
+  const unsigned T = prefix;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  unsigned base_eq = 0, base_sel = 0;
+#pragma unroll 1
+  for (int t0 = 0; t0 < HW; t0 += SEL_NT) {
+    const int i = t0 + tid;
+    const unsigned key = i < HW ? (keys[i] & MAG) : 0xffffffffu;
+    const bool lt = key < T, eq = key == T;
+    const unsigned long long beq = __ballot(eq);
+    if (lane == 0) wcnt[0][wave] = (unsigned)__popcll(beq);
+    __syncthreads();
+    unsigned eq_rank = base_eq + (unsigned)__popcll(beq & below), tot_eq = 0;
+#pragma unroll
+    for (int w = 0; w < SEL_NW; ++w) {
+      const unsigned c = wcnt[0][w];
+      if (w < wave) eq_rank += c;
+      tot_eq += c;
+    }
+    const bool sel = lt || (eq && eq_rank < k);
+    const unsigned long long bsel = __ballot(sel);
+    if (lane == 0) wcnt[1][wave] = (unsigned)__popcll(bsel);
+    __syncthreads();
+    unsigned pos = base_sel + (unsigned)__popcll(bsel & below), tot_sel = 0;
+#pragma unroll
+    for (int w = 0; w < SEL_NW; ++w) {
+      const unsigned c = wcnt[1][w];
+      if (w < wave) pos += c;
+      tot_sel += c;
+    }
+    if (sel && pos < (unsigned)P) out[pos] = i;
+    base_eq += tot_eq;
+    base_sel += tot_sel;
+    __syncthreads();                      // wcnt is rewritten by the next tile
+    if (base_sel >= (unsigned)P) break;   // (uniform)
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ gather
+constexpr int GAT_NT = 256;
+constexpr int GAT_CG = 8;                     // channels per thread
+
+// mmcv point_sample of one channel plane [H, W] at the normalised point (rx, ry) in [0, 1]^2
+__device__ __forceinline__ float grid_sample_zeros(const float* __restrict__ plane, int H, int W, float rx, float ry) {
+  const float gx = __fsub_rn(__fmul_rn(rx, 2.f), 1.f), gy = __fsub_rn(__fmul_rn(ry, 2.f), 1.f);
+  const float ix = __fsub_rn(__fmul_rn(__fadd_rn(gx, 1.f), 0.5f * (float)W), 0.5f);
+  const float iy = __fsub_rn(__fmul_rn(__fadd_rn(gy, 1.f), 0.5f * (float)H), 0.5f);
+  const float x0 = floorf(ix), y0 = floorf(iy);
+  const float w = __fsub_rn(ix, x0), e = __fsub_rn(1.f, w);
+  const float nn = __fsub_rn(iy, y0), s = __fsub_rn(1.f, nn);
+  const float wnw = __fmul_rn(s, e), wne = __fmul_rn(s, w), wsw = __fmul_rn(nn, e), wse = __fmul_rn(nn, w);
+  // corners inside the plane (a point far outside -- a huge box -- never reaches the int conversion)
+  const bool x0in = x0 >= 0.f && x0 < (float)W, x1in = x0 + 1.f >= 0.f && x0 + 1.f < (float)W;
+  const bool y0in = y0 >= 0.f && y0 < (float)H, y1in = y0 + 1.f >= 0.f && y0 + 1.f < (float)H;
+  const int xi = (x0in || x1in) ? (int)x0 : 0, yi = (y0in || y1in) ? (int)y0 : 0;
+  const float vnw = (x0in && y0in) ? plane[(long long)yi * W + xi] : 0.f;
+  const float vne = (x1in && y0in) ? plane[(long long)yi * W + xi + 1] : 0.f;
+  const float vsw = (x0in && y1in) ? plane[(long long)(yi + 1) * W + xi] : 0.f;
+  const float vse = (x1in && y1in) ? plane[(long long)(yi + 1) * W + xi + 1] : 0.f;
+  return __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(vnw, wnw), __fmul_rn(vne, wne)), __fmul_rn(vsw, wsw)), __fmul_rn(vse, wse));
+}
+
+struct GatherArgs {
+  const float* feat;
+  int B, C, H, W;
+  const float* rois;
+  int n;
+  const float* coarse;
+  int NC, CH, CW;
+  const int* idx;
+  int P, MH, MW;
+  float spatial_scale;
+  float* out;
+};
+
+__global__ __launch_bounds__(GAT_NT) void point_gather_kernel(GatherArgs a) {
+  const long long gp = (long long)blockIdx.x * GAT_NT + threadIdx.x;
+  if (gp >= (long long)a.n * a.P) return;
+  const int roi = (int)(gp / a.P), p = (int)(gp - (long long)roi * a.P);
+  const int flat = a.idx[gp];
+  const int col = flat % a.MW, row = flat / a.MW;
+  // get_roi_rel_points_test: w_step = 1.0 / W (Python double) meets the fp32 tensor as an fp32 scalar
+  const float w_step = (float)(1.0 / (double)a.MW), h_step = (float)(1.0 / (double)a.MH);
+  const float px = __fadd_rn(0.5f * w_step, __fmul_rn((float)col, w_step));
+  const float py = __fadd_rn(0.5f * h_step, __fmul_rn((float)row, h_step));
+  const int CT = a.C + a.NC;
+  float* o = a.out + (size_t)roi * CT * a.P + p;
+  const int c0 = blockIdx.y * GAT_CG;
+  if (c0 < a.C) {
+    const float* r = a.rois + (size_t)roi * 5;
+    const float bf = r[0];
+    const int b = (int)bf;
+    if (!(bf >= 0.f) || b >= a.B) {       // a RoI of no image of the batch: zeros
+#pragma unroll
+      for (int c = 0; c < GAT_CG; ++c) o[(size_t)(c0 + c) * a.P] = 0.f;
+      return;
+    }
+    // rel_roi_point_to_rel_img_point: abs = rel * (x2 - x1) + x1, then abs / (W, H) of the map * spatial_scale
+    const float ax = __fadd_rn(__fmul_rn(px, __fsub_rn(r[3], r[1])), r[1]);
+    const float ay = __fadd_rn(__fmul_rn(py, __fsub_rn(r[4], r[2])), r[2]);
+    const float rx = __fmul_rn(__fdiv_rn(ax, (float)a.W), a.spatial_scale);
+    const float ry = __fmul_rn(__fdiv_rn(ay, (float)a.H), a.spatial_scale);
+    const size_t HWf = (size_t)a.H * a.W;
+    const float* f = a.feat + ((size_t)b * a.C + c0) * HWf;
+#pragma unroll
+    for (int c = 0; c < GAT_CG; ++c) o[(size_t)(c0 + c) * a.P] = grid_sample_zeros(f + c * HWf, a.H, a.W, rx, ry);
+  } else {
+    const int k0 = c0 - a.C;
+    const size_t HWc = (size_t)a.CH * a.CW;
+    const float* f = a.coarse + ((size_t)roi * a.NC + k0) * HWc;
+#pragma unroll
+    for (int c = 0; c < GAT_CG; ++c) o[(size_t)(c0 + c) * a.P] = grid_sample_zeros(f + c * HWc, a.CH, a.CW, px, py);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ point MLP
+// Workgroup: 64 points of one RoI, 256 threads = 4 waves; wave w computes output channels [64 w, 64 w + 64) of a
+// layer for the 64 points as 2 x 2 tiles of 32 x 32 (v_mfma_f32_32x32x2_f32, the D layout puts the point on the lane).
+// The activations live in the LDS as [KQ][64 points][4 channels] (KQ = (C + NC) / 4 quads, 86 KB at 336 channels):
+// a layer reads all of them, then (after a barrier) writes its F = C outputs over the first C channels; the NC coarse
+// channels stay.  The weights are dm_conv_pack_weight's 1x1 layout [KQ][CoutP][4], read straight from the L2 (1 MB
+// for three layers, shared by every workgroup): one float4 per lane feeds four MFMAs, the next chunk's float4s are in
+// flight while the current chunk's MFMAs run.
+constexpr int MLP_TP = 64;
+constexpr int MLP_NT = 256;
+constexpr int MLP_F = 256;
+constexpr int MLP_MAXFC = 4;
+constexpr int MLP_MAXNC = 96;
+
+struct MlpArgs {
+  const float* x;
+  int n, P, C, NC, KQ, CoutP, nfc, tiles;
+  const float* w[MLP_MAXFC];
+  const float* b[MLP_MAXFC];
+  const float* wl;
+  const float* bl;
+  int NCL;
+  const long long* labels;
+  const int* idx;
+  float* refined;
+  int HW;
+};
+
+__global__ __launch_bounds__(MLP_NT) void point_mlp_kernel(MlpArgs a) {
+  extern __shared__ dm_f32x4 lds[];            // [KQ][64] activations, then red[4][64], then the logits row
+  float* red = reinterpret_cast<float*>(lds + a.KQ * MLP_TP);
+  float* wrow = red + 4 * MLP_TP;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hi = lane >> 5, l31 = lane & 31;
+  const int roi = blockIdx.x / a.tiles, p0 = (blockIdx.x - roi * a.tiles) * MLP_TP;
+  const int np = min(MLP_TP, a.P - p0);
+  const int CT = a.C + a.NC;
+  const float* xr = a.x + (size_t)roi * CT * a.P + p0;
+
+  for (int e = tid; e < a.KQ * MLP_TP; e += MLP_NT) {
+    const int q = e / MLP_TP, p = e - q * MLP_TP;
+    dm_f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (p < np) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = xr[(size_t)(4 * q + j) * a.P + p];
+    }
+    lds[e] = v;
+  }
+  int lab = (int)a.labels[roi];
+  lab = lab < 0 ? 0 : (lab >= a.NCL ? a.NCL - 1 : lab);
+  for (int k = tid; k < CT; k += MLP_NT) wrow[k] = a.wl[(size_t)lab * CT + k];
+  __syncthreads();
+
+  const int co_w = wave * 64;
+#pragma unroll 1
+  for (int L = 0; L < a.nfc; ++L) {
+    dm_f32x16 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    const dm_f32x4* wq = reinterpret_cast<const dm_f32x4*>(a.w[L]) + co_w + l31;
+    dm_f32x4 av[2], an[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) av[i] = wq[(size_t)hi * a.CoutP + i * 32];
+#pragma unroll 1
+    for (int q0 = 0; q0 < a.KQ; q0 += 2) {
+      const int qn = q0 + 2 < a.KQ ? q0 + 2 : q0;
+#pragma unroll
+      for (int i = 0; i < 2; ++i) an[i] = wq[(size_t)(qn + hi) * a.CoutP + i * 32];
+      dm_f32x4 bv[2];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) bv[j] = lds[(q0 + hi) * MLP_TP + j * 32 + l31];
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i][e], bv[j][e], acc[i][j], 0, 0, 0);
+#pragma unroll
+      for (int i = 0; i < 2; ++i) av[i] = an[i];
+    }
+    __syncthreads();                           // every wave has read this layer's input
+    const float* bias = a.b[L];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int co = co_w + i * 32 + 8 * g + 4 * hi;      // rows co .. co + 3 of D, quad co / 4
+        dm_f32x4 bq = {0.f, 0.f, 0.f, 0.f};
+        if (bias) bq = *reinterpret_cast<const dm_f32x4*>(bias + co);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          dm_f32x4 v;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) v[r] = fmaxf(acc[i][j][4 * g + r] + bq[r], 0.f);
+          lds[(co / 4) * MLP_TP + j * 32 + l31] = v;
+        }
+      }
+    __syncthreads();
+  }
+
+  // the label row of fc_logits: four partial sums per point over quarters of the quads, added in order
+  {
+    const int p = tid & (MLP_TP - 1), part = tid >> 6;
+    const int qper = (a.KQ + 3) / 4, qa = part * qper, qb = min(a.KQ, qa + qper);
+    float s = 0.f;
+    for (int q = qa; q < qb; ++q) {
+      const dm_f32x4 v = lds[q * MLP_TP + p];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s = fmaf(wrow[4 * q + j], v[j], s);
+    }
+    red[part * MLP_TP + p] = s;
+  }
+  __syncthreads();
+  if (tid < np) {
+    const float v = ((red[tid] + red[MLP_TP + tid]) + red[2 * MLP_TP + tid]) + red[3 * MLP_TP + tid] + (a.bl ? a.bl[lab] : 0.f);
+    const int cell = a.idx[(size_t)roi * a.P + p0 + tid];
+    if (cell >= 0 && cell < a.HW) a.refined[(size_t)roi * a.HW + cell] = v;
+  }
+}
+
+size_t mlp_lds_bytes(int KQ, int CT) { return (size_t)KQ * MLP_TP * 16 + 4 * MLP_TP * 4 + (size_t)CT * 4; }
+
+// ------------------------------------------------------------------------------------------------ scatter
+__global__ void point_scatter_kernel(const float* __restrict__ vals, const int* __restrict__ idx, long long total, int P,
+                                     float* __restrict__ map, int HW) {
+  const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= total) return;
+  const long long roi = g / P;
+  const int cell = idx[g];
+  if (cell >= 0 && cell < HW) map[roi * HW + cell] = vals[g];
+}
+
+}  // namespace
+
+extern "C" int dm_point_select_supported(int n, int HW, int P) {
+  return (n >= 0 && HW >= 1 && (long long)HW <= SEL_MAX_HW && P >= 1 && P <= HW) ? 1 : 0;
+}
+
+extern "C" int dm_point_select(const float* map, int n, int HW, int P, int* idx, dm_stream_t stream) {
+  if (!dm_point_select_supported(n, HW, P)) return DM_ERR_UNSUPPORTED;
+  if (n == 0) return DM_OK;
+  if (!map || !idx) return DM_ERR_INVALID_ARG;
+  DM_LAUNCH(point_select_kernel, dim3(n), dim3(SEL_NT), 0, (hipStream_t)stream, map, HW, P, idx);
+  return dm_check_launch();
+}
+
+extern "C" int dm_point_gather_supported(int B, int C, int H, int W, int n, int NC, int CH, int CW, int P, int MH, int MW) {
+  if (B < 1 || C < GAT_CG || C % GAT_CG != 0 || H < 1 || W < 1 || n < 0) return 0;
+  if (NC < GAT_CG || NC % GAT_CG != 0 || CH < 1 || CW < 1 || MH < 1 || MW < 1) return 0;
+  if (P < 1 || (long long)P > (long long)MH * MW || (long long)MH * MW > 0x7fffffffLL) return 0;
+  return dm_ceil_div((long long)n * P, GAT_NT) <= 0x7fffffffLL ? 1 : 0;
+}
+
+extern "C" int dm_point_gather_fwd(const float* feat, int B, int C, int H, int W, const float* rois, int n,
+                                   const float* coarse, int NC, int CH, int CW, const int* idx, int P, int MH, int MW,
+                                   float spatial_scale, float* out, dm_stream_t stream) {
+  if (!dm_point_gather_supported(B, C, H, W, n, NC, CH, CW, P, MH, MW)) return DM_ERR_UNSUPPORTED;
+  if (n == 0) return DM_OK;
+  if (!feat || !rois || !coarse || !idx || !out) return DM_ERR_INVALID_ARG;
+  GatherArgs a = {feat, B, C, H, W, rois, n, coarse, NC, CH, CW, idx, P, MH, MW, spatial_scale, out};
+  const dim3 grid((unsigned)dm_ceil_div((long long)n * P, GAT_NT), (unsigned)((C + NC) / GAT_CG));
+  DM_LAUNCH(point_gather_kernel, grid, dim3(GAT_NT), 0, (hipStream_t)stream, a);
+  return dm_check_launch();
+}
+
+extern "C" int dm_point_mlp_supported(int n, int P, int C, int NC, int F, int num_fcs, int NCL, int HW) {
+  if (n < 0 || P < 1 || P > HW || C != MLP_F || F != MLP_F || NC < 8 || NC % 8 != 0 || NC > MLP_MAXNC) return 0;
+  if (num_fcs < 1 || num_fcs > MLP_MAXFC || NCL < 1) return 0;
+  return (long long)n * dm_ceil_div(P, MLP_TP) <= 0x7fffffffLL ? 1 : 0;
+}
+
+extern "C" int dm_point_mlp_fwd(const float* x, int n, int P, int C, int NC, int F, int num_fcs,
+                                const float* const* w_packed, const float* const* bias, const float* w_logits,
+                                const float* b_logits, int NCL, const long long* labels, const int* idx, int flags,
+                                float* refined, int HW, dm_stream_t stream) {
+  if (flags & 16) return DM_ERR_UNSUPPORTED;    // bf16x3: exact fp32 only
+  if (flags & ~8) return DM_ERR_INVALID_ARG;    // (bit 3, the scheduling hint of dm_conv2d_fwd, is accepted and ignored)
+  if (!dm_point_mlp_supported(n, P, C, NC, F, num_fcs, NCL, HW)) return DM_ERR_UNSUPPORTED;
+  if (n == 0) return DM_OK;
+  if (!x || !w_packed || !w_logits || !labels || !idx || !refined) return DM_ERR_INVALID_ARG;
+  MlpArgs a = {};
+  a.x = x; a.n = n; a.P = P; a.C = C; a.NC = NC; a.KQ = (C + NC) / 4; a.CoutP = dm_conv_packed_cout(F);
+  a.nfc = num_fcs; a.tiles = dm_ceil_div(P, MLP_TP);
+  for (int L = 0; L < num_fcs; ++L) {
+    if (!w_packed[L]) return DM_ERR_INVALID_ARG;
+    a.w[L] = w_packed[L];
+    a.b[L] = bias ? bias[L] : nullptr;
+  }
+  a.wl = w_logits; a.bl = b_logits; a.NCL = NCL; a.labels = labels; a.idx = idx; a.refined = refined; a.HW = HW;
+  const int lds = (int)mlp_lds_bytes(a.KQ, C + NC);
+  static bool raised[DM_MAX_DEVICES] = {false};
+  const int rc = dm_ensure_lds_limit((const void*)point_mlp_kernel, lds, raised);
+  if (rc != DM_OK) return rc;
+  DM_LAUNCH(point_mlp_kernel, dim3((unsigned)((long long)n * a.tiles)), dim3(MLP_NT), lds, (hipStream_t)stream, a);
+  return dm_check_launch();
+}
+
+extern "C" int dm_point_scatter(const float* vals, const int* idx, int n, int P, float* map, int HW, dm_stream_t stream) {
+  if (n < 0 || P < 1 || P > HW) return DM_ERR_UNSUPPORTED;
+  if (n == 0) return DM_OK;
+  if (!vals || !idx || !map) return DM_ERR_INVALID_ARG;
+  const long long total = (long long)n * P;
+  DM_LAUNCH(point_scatter_kernel, dim3((unsigned)dm_ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, vals, idx,
+            total, P, map, HW);
+  return dm_check_launch();
+}

@@ -994,3 +994,183 @@ class RefineMaskHead(nn.Module):
 
     def loss(self, *a, **k):
         raise NotImplementedError('RefineMask training (targets, RefineCrossEntropyLoss) is the follow-up to inference')
+
+
+# ---------------------------------------------------------------- PointRend heads (inference)
+class _DownsampleConv(nn.Module):
+    """Parameter holder named like nn.Conv2d (weight [Cout, Cin, 2, 2], bias) of a 2 x 2 stride-2 convolution, run as
+    dm_pixel_unshuffle2x + a 1x1 convolution over the 4 Cin unshuffled channels, whose weight is this one permuted to
+    the unshuffle's channel order (dy * 2 + dx) * Cin + c."""
+
+    def __init__(self, in_channels, out_channels):
+        super().__init__()
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.weight = nn.Parameter(torch.empty(out_channels, in_channels, 2, 2))
+        self.bias = nn.Parameter(torch.zeros(out_channels))
+        nn.init.kaiming_normal_(self.weight, mode='fan_out', nonlinearity='relu')
+        self._pk = _Packed()
+
+    def packed(self):
+        cin4 = 4 * self.in_channels
+        return self._pk.get('unshuffled', self.weight, lambda w: ops.pack_conv_weight(
+            w.permute(0, 2, 3, 1).reshape(self.out_channels, cin4, 1, 1).contiguous()))
+
+    def run(self, x, relu=True):
+        return ops.conv2d([ops.pixel_unshuffle2x(x)], self.packed(), self.bias.detach(), self.out_channels, 1, relu=relu)
+
+
+class _DownsampleConvModule(nn.Module):
+    """ConvModule(k = s = 2, padding 0) without norm: keys ``conv.weight/bias``."""
+
+    def __init__(self, in_channels, out_channels):
+        super().__init__()
+        self.conv = _DownsampleConv(in_channels, out_channels)
+
+    def forward(self, x):
+        return self.conv.run(x, relu=True)
+
+
+@HEADS.register_module()
+class CoarseMaskHead(FCNMaskHead):
+    """``CoarseMaskHead`` -- mmdet/models/roi_heads/mask_heads/coarse_mask_head.py, inference: ``num_convs`` 3x3
+    convolutions, the 2 x 2 stride-2 ``downsample_conv`` (dm_pixel_unshuffle2x + a 1x1 convolution), ``flatten``,
+    ``num_fcs`` fully connected layers with ReLU and ``fc_logits`` on dm_fc_fwd -> [n, classes, S / 2, S / 2].  No
+    ``conv_logits`` (the reference deletes it).  ``get_seg_masks`` / ``get_seg_rles`` are FCNMaskHead's; PointRendRoIHead
+    hands them the refined map of the label channel only ([n, 1, S, S]), which is pasted as it is."""
+
+    def __init__(self, num_convs=0, num_fcs=2, fc_out_channels=1024, downsample_factor=2, *arg, **kwarg):
+        super().__init__(*arg, num_convs=num_convs, upsample_cfg=dict(type=None), **kwarg)
+        if num_fcs <= 0:
+            raise ValueError('CoarseMaskHead needs num_fcs > 0')
+        if downsample_factor not in (1, 2):
+            raise NotImplementedError('CoarseMaskHead: downsample_factor 1 or 2 (configs/point_rend uses 2)')
+        self.num_fcs = num_fcs
+        self.fc_out_channels = fc_out_channels
+        self.downsample_factor = downsample_factor
+        del self.conv_logits
+        roi = kwarg.get('roi_feat_size', 14)
+        self.roi_feat_size = (roi, roi) if isinstance(roi, int) else tuple(roi)
+        if downsample_factor > 1:
+            cin = self.conv_out_channels if self.num_convs > 0 else self.in_channels
+            self.downsample_conv = _DownsampleConvModule(cin, self.conv_out_channels)
+            last = self.conv_out_channels
+        else:
+            self.downsample_conv = None
+            last = self.conv_out_channels if self.num_convs > 0 else self.in_channels
+        self.output_size = (self.roi_feat_size[0] // downsample_factor, self.roi_feat_size[1] // downsample_factor)
+        self.output_area = self.output_size[0] * self.output_size[1]
+        last_layer_dim = last * self.output_area
+        self.fcs = nn.ModuleList()
+        for i in range(num_fcs):
+            self.fcs.append(nn.Linear(last_layer_dim if i == 0 else fc_out_channels, fc_out_channels))
+        out_channels = 1 if self.class_agnostic else self.num_classes
+        self.fc_logits = nn.Linear(fc_out_channels, out_channels * self.output_area)
+
+    def init_weights(self):
+        for m in self.fcs:
+            nn.init.xavier_uniform_(m.weight)
+            nn.init.constant_(m.bias, 0)
+        nn.init.constant_(self.fc_logits.weight, 0.001)
+        nn.init.constant_(self.fc_logits.bias, 0)
+
+    def forward(self, x):
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()) and x.requires_grad:
+            raise NotImplementedError('CoarseMaskHead: training is broken in the reference fork itself (SURVEY App. C Q5)')
+        for conv in self.convs:
+            x = conv(x)
+        if self.downsample_conv is not None:
+            x = self.downsample_conv(x)
+        n = x.shape[0]
+        x = x.reshape(n, -1)
+        for fc in self.fcs:
+            x = ops.fc(x, fc.weight.detach(), fc.bias.detach(), relu=True)
+        x = ops.fc(x, self.fc_logits.weight.detach(), self.fc_logits.bias.detach())
+        return x.view(n, -1, *self.output_size)
+
+    def _selected(self, mask_pred, det_bboxes, det_labels):
+        if isinstance(mask_pred, torch.Tensor) and mask_pred.dim() == 4 and mask_pred.shape[1] == 1:
+            return mask_pred.contiguous(), True     # PointRend's refined map: the label channel already
+        return super()._selected(mask_pred, det_bboxes, det_labels)
+
+
+class _Conv1d(nn.Module):
+    """Parameter holder named like nn.Conv1d(kernel_size=1) (weight [Cout, Cin, 1], bias)."""
+
+    def __init__(self, in_channels, out_channels):
+        super().__init__()
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.weight = nn.Parameter(torch.empty(out_channels, in_channels, 1))
+        self.bias = nn.Parameter(torch.zeros(out_channels))
+        nn.init.kaiming_normal_(self.weight, mode='fan_out', nonlinearity='relu')
+        self._pk = _Packed()
+
+    def packed(self):
+        return self._pk.get('1x1', self.weight, lambda w: ops.pack_conv_weight(w[..., None].contiguous()))
+
+
+class _PointConvModule(nn.Module):
+    """ConvModule(conv_cfg=Conv1d, 1x1, norm None, ReLU): keys ``conv.weight/bias``."""
+
+    def __init__(self, in_channels, out_channels):
+        super().__init__()
+        self.conv = _Conv1d(in_channels, out_channels)
+
+
+@HEADS.register_module()
+class MaskPointHead(nn.Module):
+    """``MaskPointHead`` -- mmdet/models/roi_heads/mask_heads/mask_point_head.py, inference: ``num_fcs`` shared 1x1
+    layers (256 + classes) -> 256 with ReLU, the coarse point logits re-concatenated after each (coarse_pred_each_layer),
+    then ``fc_logits``.  ``refine_`` runs it on the points of ``ops.point_gather`` and stores the LABEL row of the logits
+    into the refined map (ops.point_mlp_scatter): every other class row would be discarded by the paste.  Training
+    (``get_targets``, ``loss``: ``mask_cross_entropy``, broken in the fork, Quirk Q5) raises."""
+
+    def __init__(self, num_classes, num_fcs=3, in_channels=256, fc_channels=256, class_agnostic=False,
+                 coarse_pred_each_layer=True, conv_cfg=dict(type='Conv1d'), norm_cfg=None, act_cfg=dict(type='ReLU'),
+                 loss_point=dict(type='CrossEntropyLoss', use_mask=True, loss_weight=1.0)):
+        super().__init__()
+        if not coarse_pred_each_layer:
+            raise NotImplementedError('MaskPointHead: coarse_pred_each_layer=True only (configs/point_rend)')
+        if conv_cfg is None or dict(conv_cfg).get('type') != 'Conv1d' or norm_cfg is not None:
+            raise NotImplementedError('MaskPointHead: Conv1d layers without norm only (configs/point_rend)')
+        if act_cfg is None or dict(act_cfg).get('type') != 'ReLU':
+            raise NotImplementedError('MaskPointHead: ReLU activations only (configs/point_rend)')
+        if in_channels != fc_channels:
+            raise NotImplementedError('MaskPointHead: in_channels == fc_channels only (configs/point_rend: 256)')
+        self.num_fcs = num_fcs
+        self.in_channels = in_channels
+        self.fc_channles = fc_channels          # (sic: the reference's attribute name)
+        self.num_classes = num_classes
+        self.class_agnostic = class_agnostic
+        self.coarse_pred_each_layer = coarse_pred_each_layer
+        self.conv_cfg, self.norm_cfg = conv_cfg, norm_cfg
+        self.loss_point_cfg = loss_point
+        cin = in_channels + num_classes
+        self.fcs = nn.ModuleList()
+        for _ in range(num_fcs):
+            self.fcs.append(_PointConvModule(cin, fc_channels))
+            cin = fc_channels + num_classes
+        self.fc_logits = _Conv1d(cin, 1 if class_agnostic else num_classes)
+
+    def init_weights(self):
+        nn.init.normal_(self.fc_logits.weight, 0, 0.001)
+        nn.init.constant_(self.fc_logits.bias, 0)
+
+    def supported(self, point_feats, hw):
+        return ops.point_mlp_supported(point_feats, self.num_fcs, self.fc_logits.out_channels, hw)
+
+    def refine_(self, point_feats, labels, point_indices, refined, fused=None):
+        """``refined`` [n, 1, H, W] (the label channel) at ``point_indices`` [n, P] <- the label row of
+        ``forward(point_feats[:, :256], point_feats[:, 256:])``, in place (point_feats: ``ops.point_gather``)."""
+        hw = ops._cells(refined)
+        if not self.supported(point_feats, hw):
+            raise NotImplementedError(f'MaskPointHead: no kernel for point features {tuple(point_feats.shape)}')
+        fl = self.fc_logits
+        return ops.point_mlp_scatter(point_feats, [m.conv.packed() for m in self.fcs], [m.conv.bias.detach() for m in self.fcs],
+                                     fl.weight.detach().view(fl.out_channels, fl.in_channels), fl.bias.detach(),
+                                     labels, point_indices, refined, fused=fused)
+
+    def get_targets(self, *a, **k):
+        raise NotImplementedError('MaskPointHead.get_targets: PointRend training is broken in the reference (Quirk Q5)')
+
+    def loss(self, *a, **k):
+        raise NotImplementedError('MaskPointHead.loss: mask_cross_entropy is broken in the reference fork (Quirk Q5)')

@@ -1042,6 +1042,130 @@ def sigmoid(x, out=None):
     return out
 
 
+# ------------------------------------------------ PointRend: the subdivision step (csrc/point_refine.hip)
+# Exact fp32 in every precision mode: the bf16x3 mode does not reach these launches.
+def _cells(t):
+    """Cells per row of a [n, ...] map (also when n == 0)."""
+    hw = 1
+    for d in t.shape[1:]:
+        hw *= int(d)
+    return hw
+
+
+def point_select_supported(hw, num_points, n=1):
+    return bool(lib().dm_point_select_supported(int(n), int(hw), int(num_points)))
+
+
+def point_select(refined, num_points, out=None):
+    """The ``num_points`` cells of smallest |v| per row of the label-channel map ``refined`` [n, 1, H, W] (or [n, HW]):
+    ``topk(-|v|, num_points)`` of MaskPointHead.get_roi_rel_points_test -> int32 [n, num_points], indices in ascending
+    order; among equal |v| at the cut the lower index is taken (dm_point_select)."""
+    _chk(refined, 'refined')
+    n = refined.shape[0]
+    hw = _cells(refined)
+    P = int(num_points)
+    if out is None:
+        out = torch.empty((n, P), device=refined.device, dtype=torch.int32)
+    _chk(out, 'out', torch.int32)
+    assert tuple(out.shape) == (n, P)
+    check(lib().dm_point_select(_p(refined), n, hw, P, _p(out), _stream()), 'dm_point_select')
+    return out
+
+
+def point_gather(feat, rois, coarse, idx, mh, mw, spatial_scale, out=None):
+    """The point head's input [n, C + NC, P] at the cells ``idx`` [n, P] of an ``mh`` x ``mw`` grid: channels < C the
+    point_sample of ``feat`` [B, C, H, W] (the image of each RoI) at the cell centres mapped into the image
+    (rel_roi_point_to_rel_img_point with ``spatial_scale``), channels >= C the point_sample of the RoI's ``coarse``
+    [n, NC, CH, CW] logits at the RoI-relative centres (dm_point_gather_fwd)."""
+    _chk(feat, 'feat')
+    _chk(rois, 'rois')
+    _chk(coarse, 'coarse')
+    _chk(idx, 'idx', torch.int32)
+    B, C, H, W = feat.shape
+    n, P = idx.shape
+    NC, CH, CW = coarse.shape[1:]
+    assert rois.shape == (n, 5) and coarse.shape[0] == n
+    if out is None:
+        out = torch.empty((n, C + NC, P), device=feat.device, dtype=torch.float32)
+    _chk(out, 'out')
+    assert tuple(out.shape) == (n, C + NC, P)
+    check(lib().dm_point_gather_fwd(_p(feat), B, C, H, W, _p(rois), n, _p(coarse), NC, CH, CW, _p(idx), P, int(mh), int(mw),
+                                    float(spatial_scale), _p(out), _stream()), 'dm_point_gather_fwd')
+    return out
+
+
+def point_scatter(vals, idx, refined):
+    """refined[r].flatten()[idx[r, p]] = vals[r, p] in place (dm_point_scatter)."""
+    _chk(vals, 'vals')
+    _chk(idx, 'idx', torch.int32)
+    _chk(refined, 'refined')
+    n, P = idx.shape
+    assert vals.numel() == n * P and refined.shape[0] == n
+    check(lib().dm_point_scatter(_p(vals), _p(idx), n, P, _p(refined), _cells(refined), _stream()),
+          'dm_point_scatter')
+    return refined
+
+
+# MaskPointHead's MLP + the scatter as ONE launch (dm_point_mlp_fwd); False: the unfused sequence -- each layer a
+# dm_conv2d_fwd 1x1 on the points as a 1 x P image, dm_class_logits_fwd for the label row, dm_point_scatter (the A/B
+# baseline; the same arithmetic in another association)
+FUSED_POINT_MLP = [os.environ.get('DM_FUSED_POINT_MLP', '1') != '0']
+
+
+def point_mlp_supported(x, num_fcs, ncl, hw):
+    n, CT, P = x.shape
+    return bool(lib().dm_point_mlp_supported(n, P, 256, CT - 256, 256, int(num_fcs), int(ncl), int(hw)))
+
+
+def point_mlp_scatter(x, w_packeds, biases, w_logits, b_logits, labels, idx, refined, fused=None):
+    """MaskPointHead.forward (coarse_pred_each_layer) on the point features ``x`` [n, 256 + NC, P] (``point_gather``):
+    relu(W_l [h; coarse] + b_l) per layer, then the ``labels`` row of fc_logits, stored into ``refined`` [n, 1, H, W] at
+    the cells ``idx`` [n, P] (in place).  ``w_packeds``: ``pack_conv_weight`` of each [256, 256 + NC, 1, 1] weight;
+    ``w_logits`` [NCL, 256 + NC], ``b_logits`` [NCL].  ``fused`` (default FUSED_POINT_MLP): one launch, else the
+    unfused sequence."""
+    _chk(x, 'x')
+    _chk(w_logits, 'w_logits')
+    _chk(labels, 'labels', torch.int64)
+    _chk(idx, 'idx', torch.int32)
+    _chk(refined, 'refined')
+    n, CT, P = x.shape
+    k = len(w_packeds)
+    assert len(biases) == k and tuple(idx.shape) == (n, P) and refined.shape[0] == n and labels.shape == (n,)
+    for w in w_packeds:
+        _chk(w, 'w_packed')
+        if conv_layout(w) != 'fp32':
+            raise ValueError('the point MLP reads the exact fp32 layout (pack_conv_weight(precision="fp32"))')
+        assert w.numel() == packed_floats(256, 1, [CT]), 'weights packed for another shape'
+    if b_logits is not None:
+        _chk(b_logits, 'b_logits')
+    hw = _cells(refined)
+    if fused is None:
+        fused = FUSED_POINT_MLP[0]
+    if fused:
+        bias_arr = (ctypes.c_void_p * k)(*[0 if b is None else _chk(b, 'bias').data_ptr() for b in biases])
+        if hazard.ENABLED[0]:
+            hazard.note_ptr_array(bias_arr, [b for b in biases if b is not None])
+        check(lib().dm_point_mlp_fwd(_p(x), n, P, 256, CT - 256, 256, k, _ptr_array(w_packeds), bias_arr, _p(w_logits),
+                                     _p(b_logits), w_logits.shape[0], _p(labels), _p(idx), 0, _p(refined), hw, _stream()),
+              'dm_point_mlp_fwd')
+        return refined
+    if n == 0:
+        return refined
+    # ping-pong between two [n, 256 + NC, 1, P] buffers that both hold the coarse channels
+    bufs = [x.view(n, CT, 1, P), x.clone().view(n, CT, 1, P), None]
+    bufs[2] = bufs[1].clone()
+    cur = bufs[0]
+    for i, (w, b) in enumerate(zip(w_packeds, biases)):
+        dst = bufs[1 + (i % 2)]
+        conv2d([cur], w, b, 256, 1, relu=True, out=dst, out_ch_offset=0)
+        cur = dst
+    nl = w_logits.shape[0]
+    lab = labels.clamp(0, nl - 1).contiguous()
+    bl = b_logits if b_logits is not None else torch.zeros((nl,), device=x.device, dtype=torch.float32)
+    vals, _ = class_logits(cur, w_logits, bl, w_logits, bl, lab)
+    return point_scatter(vals, idx, refined)
+
+
 def pack_deconv_weight(w, precision='fp32'):
     """``precision='bf16x3'``: dm_deconv_pack_weight_bf16x3's layout, marked as such (``conv_layout``)."""
     _chk(w, 'weight')

@@ -92,3 +92,54 @@ class SingleRoIExtractor(BaseRoIExtractor):
             return feats[0].new_zeros((0, self.out_channels, P, P))
         scales = [l.spatial_scale for l in self.roi_layers]
         return ops.roi_align(feats, rois, P, scales, lay.sampling_ratio, float(self.finest_scale))
+
+
+@ROI_LAYERS.register_module()
+class SimpleRoIAlign(nn.Module):
+    """Parameter holder with mmcv.ops.SimpleRoIAlign's constructor signature: ``point_sample`` of the feature map at
+    the ``output_size`` x ``output_size`` RoI-relative cell centres (dm_point_sample_fwd)."""
+
+    def __init__(self, output_size, spatial_scale, aligned=True):
+        super().__init__()
+        if isinstance(output_size, int):
+            output_size = (output_size, output_size)
+        if output_size[0] != output_size[1]:
+            raise ValueError('only square SimpleRoIAlign outputs are supported')
+        if not aligned:
+            raise NotImplementedError('dynamask_amd SimpleRoIAlign implements aligned=True (align_corners=False)')
+        self.output_size = tuple(output_size)
+        self.spatial_scale = float(spatial_scale)
+        self.aligned = aligned
+
+    def forward(self, input, rois):
+        return ops.point_sample(input, rois, self.output_size[0], self.spatial_scale)
+
+
+@ROI_EXTRACTORS.register_module()
+class GenericRoIExtractor(BaseRoIExtractor):
+    """``GenericRoIExtractor`` -- mmdet/models/roi_heads/roi_extractors/generic_roi_extractor.py: the forms
+    configs/point_rend uses, i.e. ONE level (then the extraction is ``roi_layers[0](feats[0], rois)``, :43-46) without
+    pre- / post-processing modules.  Several levels or plugin modules raise NotImplementedError."""
+
+    def __init__(self, aggregation='sum', pre_cfg=None, post_cfg=None, **kwargs):
+        super().__init__(**kwargs)
+        if aggregation not in ('sum', 'concat'):
+            raise ValueError(f'aggregation must be "sum" or "concat", got {aggregation!r}')
+        if len(self.featmap_strides) != 1:
+            raise NotImplementedError('GenericRoIExtractor: one feature level only (configs/point_rend)')
+        if pre_cfg is not None or post_cfg is not None:
+            raise NotImplementedError('GenericRoIExtractor: pre_cfg / post_cfg are None in configs/point_rend')
+        self.aggregation = aggregation
+        self.with_pre = self.with_post = False
+
+    def forward(self, feats, rois, roi_scale_factor=None):
+        if roi_scale_factor is not None:
+            raise NotImplementedError('roi_scale_factor is not used by the PointRend path')
+        feats = list(feats)[:self.num_inputs]
+        if len(feats) != self.num_inputs:
+            raise ValueError(f'expected {self.num_inputs} feature maps, got {len(feats)}')
+        lay = self.roi_layers[0]
+        if rois.shape[0] == 0:
+            P = lay.output_size[0]
+            return feats[0].new_zeros((0, self.out_channels, P, P))
+        return lay(feats[0].contiguous(), rois.contiguous())

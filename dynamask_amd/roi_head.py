@@ -1170,3 +1170,137 @@ class RefineRoIHead(DynaMaskRoIHead):
 
     def dynamic_test_mask(self, *a, **k):
         raise NotImplementedError('RefineRoIHead: per-RoI early exit is DynaMask\'s, RefineMask has none')
+
+
+@HEADS.register_module()
+class PointRendRoIHead(StandardRoIHead):
+    """``PointRendRoIHead`` -- mmdet/models/roi_heads/point_rend_roi_head.py, inference: the RoI head of configs/point_rend.
+    The bbox branch, ``_mask_forward`` (the ``CoarseMaskHead`` logits [n, classes, 7, 7] of the GenericRoIExtractor's
+    14 x 14 features) and the batch / TTA entry points are the parent's; the mask prediction is refined by the
+    subdivision loop of ``_mask_point_forward_test`` (:96-128): ``subdivision_steps`` bilinear x2 upsamples, and at every
+    step that is not skipped the ``subdivision_num_points`` most uncertain cells re-predicted by ``point_head``
+    (ops.point_select -> ops.point_gather -> MaskPointHead.refine_).
+
+    Only the label channel of the refined map is carried: every operation of the loop is per class channel except the
+    point selection, which reads the label channel, and only the label channel is pasted or merged.  The result is that
+    channel of the reference's [n, classes, 224, 224] map (the coarse point features still hold every class: they are
+    inputs of the point MLP).  ``BaseRoIHead`` builds ``mask_predictor`` / ``semantic_roi_extractor`` for every RoI head
+    (Quirk Q4): the ``state_dict`` keys are the reference's.  Training (Quirk Q5) and HIP-graph capture raise."""
+
+    def __init__(self, point_head, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        if not (self.with_bbox and self.with_mask):
+            raise ValueError('PointRendRoIHead needs a bbox and a mask branch (point_rend_roi_head.py:19)')
+        if self.mask_roi_extractor.num_inputs != 1:
+            raise NotImplementedError('PointRendRoIHead: one fine-grained feature level (configs/point_rend: P2)')
+        self.point_head = build_head(point_head)
+
+    def init_weights(self, pretrained=None):
+        super().init_weights(pretrained)
+        self.point_head.init_weights()
+
+    def _refine_size(self):
+        s = self.mask_head.output_size[0]
+        return s * 2 ** self.test_cfg.subdivision_steps
+
+    def _mask_point_forward_test(self, x, rois, label_pred, mask_pred):
+        """point_rend_roi_head.py:96-128 on the label channel -> refined logits [n, 1, S', S']."""
+        cfg = self.test_cfg
+        if cfg.scale_factor != 2:
+            raise NotImplementedError('PointRendRoIHead: subdivision scale_factor 2 only (configs/point_rend)')
+        steps, num_points = int(cfg.subdivision_steps), int(cfg.subdivision_num_points)
+        n = rois.shape[0]
+        rois = rois.contiguous()
+        labels = label_pred.to(torch.int64).contiguous()
+        mask_pred = mask_pred.contiguous()
+        sel = mask_pred if mask_pred.shape[1] == 1 else mask_pred[torch.arange(n, device=rois.device), labels][:, None]
+        refined = sel.contiguous()
+        feat = x[0].contiguous()
+        scale = 1.0 / float(self.mask_roi_extractor.featmap_strides[0])
+        for step in range(steps):
+            refined = ops.upsample2x(refined)
+            H, W = refined.shape[2:]
+            if num_points >= 4 * H * W and step < steps - 1:
+                continue
+            idx = ops.point_select(refined, min(H * W, num_points))
+            pts = ops.point_gather(feat, rois, mask_pred, idx, H, W, scale)
+            self.point_head.refine_(pts, labels, idx, refined)
+        return refined
+
+    def _refined_logits(self, x, mask_rois, det_labels):
+        with torch.no_grad():
+            coarse = self._mask_forward(x, mask_rois)['mask_pred']
+            return self._mask_point_forward_test(x, mask_rois, det_labels, coarse)
+
+    def simple_test_mask_logits(self, x, det_bboxes, det_labels, scale_factor=1.0, rescale=False):
+        """The refined label-channel logits [n, 1, S', S'] of the detections (S' = 224 in configs/point_rend)."""
+        if det_bboxes.shape[0] == 0:
+            s = self._refine_size()
+            return det_bboxes.new_zeros((0, 1, s, s))
+        _bboxes = det_bboxes[:, :4] * scale_factor if rescale else det_bboxes
+        return self._refined_logits(x, bbox2roi([_bboxes]).contiguous(), det_labels)
+
+    def batch_simple_test_mask_logits(self, x, det_bboxes_list, det_labels_list, scale_factors=None, rescale=False):
+        """The refined label-channel logits [sum N, 1, S', S'] of B images' detections from ONE subdivision loop (the
+        RoI batch column routes the fine-grained sampling), and the row offsets [B + 1]."""
+        self._check_batch(det_bboxes_list, 'det_bboxes_list', det_labels_list=det_labels_list, scale_factors=scale_factors)
+        if rescale and scale_factors is None:
+            raise ValueError('rescale=True needs scale_factors')
+        offsets = [0]
+        boxes = []
+        for b, det in enumerate(det_bboxes_list):
+            offsets.append(offsets[-1] + int(det.shape[0]))
+            if rescale and det.shape[0] > 0:
+                det = det[:, :4] * self._batch_scale_factor(scale_factors[b], det.device)
+            boxes.append(det)
+        mask_rois = bbox2roi(boxes).contiguous()
+        if mask_rois.shape[0] == 0:
+            s = self._refine_size()
+            return mask_rois.new_zeros((0, 1, s, s)), offsets
+        labels = torch.cat(list(det_labels_list)).contiguous()
+        return self._refined_logits(x, mask_rois, labels), offsets
+
+    def _batch_mask_preds(self, x, boxes_list, labels_list, labels):
+        refined, _ = self.batch_simple_test_mask_logits(x, boxes_list, labels_list)
+        return refined.contiguous(), True
+
+    def _aug_view_mask_logits(self, x, rois, det_labels):
+        """One view's refined label-channel logits [n, 1, S', S'] (point_rend_roi_head.py:170-178)."""
+        return self._refined_logits(x, rois.contiguous(), det_labels).contiguous()
+
+    def _aug_empty_probs(self, ref):
+        s = self._refine_size()
+        return ref.new_zeros((0, 1, s, s))
+
+    def simple_test_mask(self, x, img_metas, det_bboxes, det_labels, rescale=False, encode=False):
+        """point_rend_roi_head.py:130-155 -> ``cls_segms`` of ``get_seg_masks`` on the refined map (``encode``: COCO RLE
+        dicts, ``get_seg_rles``)."""
+        ori_shape = img_metas[0]['ori_shape']
+        scale_factor = img_metas[0]['scale_factor']
+        if det_bboxes.shape[0] == 0:
+            return [[] for _ in range(self.mask_head.num_classes)]
+        if rescale and not isinstance(scale_factor, float):
+            scale_factor = torch.from_numpy(scale_factor).to(det_bboxes.device)
+        _bboxes = det_bboxes[:, :4] * scale_factor if rescale else det_bboxes
+        refined = self._refined_logits(x, bbox2roi([_bboxes]).contiguous(), det_labels)
+        to_segs = self.mask_head.get_seg_rles if encode else self.mask_head.get_seg_masks
+        return to_segs(refined, _bboxes, det_labels, self.test_cfg, ori_shape, scale_factor, rescale)
+
+    def enable_inference_graphs(self, on=True, buckets=None, batch_buckets=None):
+        if on:
+            raise NotImplementedError('PointRendRoIHead: HIP-graph capture of the PointRend call is not implemented')
+        self._mask_graphs = None
+        return None
+
+    def forward_train(self, x, img_metas, proposal_list, gt_bboxes, gt_labels, gt_bboxes_ignore=None, gt_masks=None):
+        raise NotImplementedError('PointRendRoIHead.forward_train: PointRend training is broken in the reference '
+                                  '(CoarseMaskHead.loss and the point loss use mask_cross_entropy, Quirk Q5)')
+
+    def _mask_forward_train(self, *a, **k):
+        raise NotImplementedError('PointRendRoIHead: PointRend training is broken in the reference (Quirk Q5)')
+
+    def dynamic_mask_logits(self, *a, **k):
+        raise NotImplementedError('PointRendRoIHead: per-RoI early exit is DynaMask\'s, PointRend has none')
+
+    def dynamic_test_mask(self, *a, **k):
+        raise NotImplementedError('PointRendRoIHead: per-RoI early exit is DynaMask\'s, PointRend has none')

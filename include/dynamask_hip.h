@@ -55,7 +55,8 @@ extern "C" {
 typedef void* dm_stream_t; /* hipStream_t */
 
 const char* dm_error_string(int code);
-/* ABI version: bumped whenever a signature or the meaning of an argument changes (8: flag bit 3 of dm_conv2d_fwd; 9: RoI assignment / bbox training entry points; 10: dm_detail_target takes the fuse weights from device memory; 11: FCNMaskHead upsample backward; 12: dm_fc_fwd takes a scratch slab, deterministic split-K; 13: dm_deform_coord_grad / dm_deform_col2im, dm_conv2d_fwd_masked, dm_scale, dm_polygon_mask_targets, dm_ignore_columns, dm_upsample2x_bilinear_bwd overwrites; 14: dm_random_sample, dm_bn_relu_maxpool_argmax, the *_fx deterministic accumulators + dm_fx_to_float, dm_mask_loss_fwd_bwd takes a scratch, dm_conv2d_wgrad takes the bias gradient, dm_conv_pack_weight_batch, dm_mask_loss_stage; 15: dm_class_logits_up2x_fwd; 16: dm_conv2d_wgrad_slab / dm_conv2d_wgrad_scratch_floats; 17: dm_class_logits_bwd_slab / dm_class_logits_bwd_scratch_floats; 18: dm_reload_env_knobs, dm_roi_align_fwd_ws / dm_roi_align_workspace_bytes, dm_conv_pack_weight_split / dm_conv_packed_floats_split and flag bits 4, 5 of dm_conv2d_fwd; 19: dm_dcn_bwd_data_fused and its pack; 20: dm_conv2d_fwd_ws / dm_conv2d_splitk_floats; 21: dm_deform_conv_fwd_ws / dm_deform_conv_splitk_floats; 22: the bf16-split layouts (dm_conv_pack_weight_split, dm_conv_packed_floats_split, flag bits 4 / 5 of dm_conv2d_fwd) and the one-kernel DCN data gradient (dm_dcn_bwd_*) REMOVED -- measured, never the parity path, see docs/HISTORY.md; 23: dm_bn_stats takes mean_shift, dm_roi_align_bwd takes the gather form for 16 < P <= 64; 24: dm_build_info; 25: dm_boundary_merge_chain, dm_stage_head_fwd; 26: dm_conv1x1_group_fwd; 27: dm_deform_conv_tout_fwd / dm_deform_conv_tout_supported; 28: the opt-in bf16x3 mode -- dm_conv_pack_weight_bf16x3 / dm_conv_packed_floats_bf16x3 and flag bit 4 of dm_conv2d_fwd, dm_conv2d_fwd_ws and dm_conv1x1_group_fwd; dm_deconv_pack_weight_bf16x3 and flag bit 4 of dm_deconv2x2_fwd).  Entry points ADDED without a signature or meaning change leave the number as it is (the loader resolves every symbol of _lib.SIGNATURES by name, so an older library fails at load): the multi-image post-processing dm_nms_mask_segmented / dm_nms_reduce_segmented, dm_paste_masks_multi, dm_paste_rle_multi / dm_rle_multi_scratch_ints; the test-time augmentation dm_bbox_mapping_multi, dm_merge_aug_bboxes, dm_merge_aug_masks; RefineMask's dilated / any-width 3x3 convolutions and the sigmoid of its semantic map (section K21). */
+/* ABI version: bumped whenever a signature or the meaning of an argument changes (8: flag bit 3 of dm_conv2d_fwd; 9: RoI assignment / bbox training entry points; 10: dm_detail_target takes the fuse weights from device memory; 11: FCNMaskHead upsample backward; 12: dm_fc_fwd takes a scratch slab, deterministic split-K; 13: dm_deform_coord_grad / dm_deform_col2im, dm_conv2d_fwd_masked, dm_scale, dm_polygon_mask_targets, dm_ignore_columns, dm_upsample2x_bilinear_bwd overwrites; 14: dm_random_sample, dm_bn_relu_maxpool_argmax, the *_fx deterministic accumulators + dm_fx_to_float, dm_mask_loss_fwd_bwd takes a scratch, dm_conv2d_wgrad takes the bias gradient, dm_conv_pack_weight_batch, dm_mask_loss_stage; 15: dm_class_logits_up2x_fwd; 16: dm_conv2d_wgrad_slab / dm_conv2d_wgrad_scratch_floats; 17: dm_class_logits_bwd_slab / dm_class_logits_bwd_scratch_floats; 18: dm_reload_env_knobs, dm_roi_align_fwd_ws / dm_roi_align_workspace_bytes, dm_conv_pack_weight_split / dm_conv_packed_floats_split and flag bits 4, 5 of dm_conv2d_fwd; 19: dm_dcn_bwd_data_fused and its pack; 20: dm_conv2d_fwd_ws / dm_conv2d_splitk_floats; 21: dm_deform_conv_fwd_ws / dm_deform_conv_splitk_floats; 22: the bf16-split layouts (dm_conv_pack_weight_split, dm_conv_packed_floats_split, flag bits 4 / 5 of dm_conv2d_fwd) and the one-kernel DCN data gradient (dm_dcn_bwd_*) REMOVED -- measured, never the parity path, see docs/HISTORY.md; 23: dm_bn_stats takes mean_shift, dm_roi_align_bwd takes the gather form for 16 < P <= 64; 24: dm_build_info; 25: dm_boundary_merge_chain, dm_stage_head_fwd; 26: dm_conv1x1_group_fwd; 27: dm_deform_conv_tout_fwd / dm_deform_conv_tout_supported; 28: the opt-in bf16x3 mode -- dm_conv_pack_weight_bf16x3 / dm_conv_packed_floats_bf16x3 and flag bit 4 of dm_conv2d_fwd, dm_conv2d_fwd_ws and dm_conv1x1_group_fwd; dm_deconv_pack_weight_bf16x3 and flag bit 4 of dm_deconv2x2_fwd).  Entry points ADDED without a signature or meaning change leave the number as it is (the loader resolves every symbol of _lib.SIGNATURES by name, so an older library fails at load): the multi-image post-processing dm_nms_mask_segmented / dm_nms_reduce_segmented, dm_paste_masks_multi, dm_paste_rle_multi / dm_rle_multi_scratch_ints; the test-time augmentation dm_bbox_mapping_multi, dm_merge_aug_bboxes, dm_merge_aug_masks; RefineMask's dilated / any-width 3x3 convolutions and the sigmoid of its semantic map (section K21); PointRend's point
+ * selection, point gather, point MLP and scatter (section K22). */
 int dm_abi_version(void);
 /* "libdynamask_hip abi=N arch=gfx950 compiler=<clang version> flags=<the product-wide flags of dynamask_amd/build.py>"
  * (static storage).  The library must be compiled WITHOUT packed fp32 instructions (flag "-packed-fp32-ops", see
@@ -808,6 +809,51 @@ int dm_conv3x3_multidil_fwd(const float* x, int NB, int C, int H, int W, const f
 /* out[i] = 1 / (1 + exp(-x[i])) for i < n (the paste kernels' logistic, bit for bit): RefineMask's sigmoid(semantic_pred)
  * (refine_mask_head.py:115-117), n = B * H * W.  out may equal x. */
 int dm_sigmoid_fwd(const float* x, long long n, float* out, dm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * K22  PointRend inference: the subdivision step of PointRendRoIHead._mask_point_forward_test
+ * (mmdet/models/roi_heads/point_rend_roi_head.py:96-128) on the label channel of the refined map (csrc/point_refine.hip).
+ *
+ * dm_point_select: map [n, HW] (the label channel of the upsampled map) -> idx [n, P] int32: per row the P cells of
+ * smallest |v| -- topk(-|v|, P) of MaskPointHead.get_roi_rel_points_test -- in ASCENDING index order.  Tie rule: among
+ * cells of equal |v| at the cut, the lower flat index is taken (torch.topk promises no order).  |v| is compared as the
+ * bit pattern of the magnitude (+0 and -0 are equal; a NaN ranks above +inf, i.e. is never preferred).
+ * dm_point_select_supported: 1 exactly when n >= 0, 1 <= HW <= 2^24 and 1 <= P <= HW.  n == 0 enqueues nothing.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int dm_point_select_supported(int n, int HW, int P);
+int dm_point_select(const float* map, int n, int HW, int P, int* idx, dm_stream_t stream);
+/* dm_point_gather_fwd: for every RoI r and selected cell idx[r, p] of an MH x MW grid, the cell centre
+ * (px, py) = (w_step / 2 + col * w_step, h_step / 2 + row * h_step), w_step = (float)(1.0 / MW) (get_roi_rel_points_test's
+ * fp32 chain), and
+ *   out[r, c, p]      = point_sample(feat[rois[r, 0]], rel_roi_point_to_rel_img_point(rois[r], (px, py), (H, W),
+ *                       spatial_scale))[c]    for c < C  (abs = rel * (x2 - x1) + x1, then abs / W * spatial_scale),
+ *   out[r, C + k, p]  = point_sample(coarse[r], (px, py))[k]   for k < NC  (the RoI's CH x CW coarse logits),
+ * point_sample = mmcv's: grid_sample(bilinear, zeros, align_corners=False) at 2 * point - 1, in the fp32 operations of
+ * PyTorch's CPU grid sampler.  feat [B, C, H, W]; rois [n, 5] (batch index, x1, y1, x2, y2; a batch index outside
+ * [0, B) gives zero fine channels); coarse [n, NC, CH, CW]; idx [n, P] in [0, MH * MW); out [n, C + NC, P].
+ * dm_point_gather_supported: 1 exactly when B >= 1, C >= 8 and NC >= 8 are multiples of 8, H, W, CH, CW, MH, MW >= 1,
+ * MH * MW < 2^31, n >= 0, 1 <= P <= MH * MW and ceil(n * P / 256) < 2^31. */
+int dm_point_gather_supported(int B, int C, int H, int W, int n, int NC, int CH, int CW, int P, int MH, int MW);
+int dm_point_gather_fwd(const float* feat, int B, int C, int H, int W, const float* rois, int n, const float* coarse,
+                        int NC, int CH, int CW, const int* idx, int P, int MH, int MW, float spatial_scale, float* out,
+                        dm_stream_t stream);
+/* dm_point_mlp_fwd: MaskPointHead.forward (mask_point_head.py:85-104, coarse_pred_each_layer) on x [n, C + NC, P]
+ * (dm_point_gather_fwd's layout): h_0 = x[:, :C], h_{l+1} = relu(W_l [h_l; x[:, C:]] + b_l) for l < num_fcs, then
+ * v = w_logits[label] . [h; x[:, C:]] + b_logits[label] and refined[r, idx[r, p]] = v (the scatter_ of
+ * point_rend_roi_head.py:121-124, label channel only).  w_packed[l]: dm_conv_pack_weight(ksize 1, Cin = C + NC, one
+ * source) of the [F, C + NC] weight; bias[l] [F] (the host array, or an entry, may be NULL); w_logits [NCL, C + NC],
+ * b_logits [NCL] or NULL; labels [n] int64, clamped to [0, NCL - 1] (NCL = 1: class-agnostic); refined [n, HW].
+ * Exact fp32 (v_mfma_f32_32x32x2_f32 for the layers, fmaf for the logit row).  flags: bit 3 accepted and ignored; bit 4
+ * (the bf16x3 mode) returns DM_ERR_UNSUPPORTED; any other bit DM_ERR_INVALID_ARG.
+ * dm_point_mlp_supported: 1 exactly when n >= 0, 1 <= P <= HW, C == F == 256, 8 <= NC <= 96 with NC % 8 == 0,
+ * 1 <= num_fcs <= 4, NCL >= 1 and n * ceil(P / 64) < 2^31. */
+int dm_point_mlp_supported(int n, int P, int C, int NC, int F, int num_fcs, int NCL, int HW);
+int dm_point_mlp_fwd(const float* x, int n, int P, int C, int NC, int F, int num_fcs, const float* const* w_packed,
+                     const float* const* bias, const float* w_logits, const float* b_logits, int NCL,
+                     const long long* labels, const int* idx, int flags, float* refined, int HW, dm_stream_t stream);
+/* map[r, idx[r, p]] = vals[r, p] for r < n, p < P (the unfused sequence's scatter); vals [n, P], idx [n, P] in [0, HW),
+ * map [n, HW].  DM_ERR_UNSUPPORTED unless n >= 0 and 1 <= P <= HW. */
+int dm_point_scatter(const float* vals, const int* idx, int n, int P, float* map, int HW, dm_stream_t stream);
 
 #ifdef __cplusplus
 }
