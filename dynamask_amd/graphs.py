@@ -86,7 +86,7 @@ class GraphedMaskLogits:
         head = self.head
 
         def run():
-            return head._merged_logits(x, rois, labels)
+            return head._mask_logits(x, rois, labels)
         with torch.no_grad():
             # once eagerly on a side stream: packs the weights and sizes the allocator before the capture
             s = torch.cuda.Stream(device=dev)

@@ -241,13 +241,57 @@ def _paste_geometry(det_bboxes, ori_shape, scale_factor, rescale):
     return (bboxes / scale_factor).contiguous(), int(img_h), int(img_w)
 
 
-def _bitmaps_to_host(im_mask):
-    """device -> host as the reference does (``im_mask[i].cpu().numpy()``), but ONE copy of all masks into a fresh pinned
-    buffer (PCIe rate instead of the pageable-memory rate); returns the [N, h, w] bool array."""
-    host = torch.empty(im_mask.shape, dtype=im_mask.dtype, pin_memory=True)
-    host.copy_(im_mask, non_blocking=True)
+def _to_host(*tensors):
+    """device -> host as the reference does (``t.cpu().numpy()``), but every tensor into a fresh pinned buffer (PCIe rate
+    instead of the pageable-memory rate; the reference copies each mask on its own), all copies non-blocking and ONE
+    synchronisation of the current stream -> the numpy arrays."""
+    hosts = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in tensors]
+    for h, t in zip(hosts, tensors):
+        h.copy_(t, non_blocking=True)
     torch.cuda.current_stream().synchronize()
-    return host.numpy()
+    return [h.numpy() for h in hosts]
+
+
+def _mask_threshold(rcnn_test_cfg):
+    threshold = rcnn_test_cfg.mask_thr_binary
+    if threshold < 0:
+        raise NotImplementedError('visualisation mode (mask_thr_binary < 0) is not on the path')
+    return threshold
+
+
+def select_label_channel(mask_pred, labels):
+    """[n, C, S, S] -> the channel of every detection's label [n, 1, S, S] (fcn_mask_head.py:211-212): one gather when
+    C > 1 (the sigmoid of the paste commutes with it)."""
+    if mask_pred.shape[1] > 1:
+        mask_pred = mask_pred[torch.arange(len(mask_pred), device=mask_pred.device), labels.to(mask_pred.device)][:, None]
+    return mask_pred.contiguous()
+
+
+def paste_segms(mask_pred, det_bboxes, det_labels, rcnn_test_cfg, ori_shape, scale_factor, rescale, encode=False,
+                apply_sigmoid=True, num_classes=None, labels_host=None):
+    """The paste of every ``get_seg_masks`` / ``get_seg_rles`` (dynamask_head.py:279-342, fcn_mask_head.py:151-237) and
+    of the RoI heads' one-image mask tests: ``mask_pred`` [n, 1, S, S] (the label channel; ``apply_sigmoid``: logits)
+    pasted into the image, thresholded, by one kernel for all detections.  Bitmaps: ONE device -> host copy of all masks
+    -> (h, w) bool arrays.  ``encode``: ``get_seg_masks`` followed by ``encode_mask_results`` (core/mask/utils.py:36-63)
+    without the bitmaps -- paste, threshold and run-length encoding on the device, only run boundaries are copied to the
+    host: COCO RLE dicts, what ``mask_util.encode(np.array(m[:, :, None], order='F'))[0]`` yields for the bitmap.
+    Returns one entry per detection, or with ``num_classes`` the per-class lists (``cls_segms``: a class's detections in
+    detection order; ``labels_host``: ``det_labels`` already on the host)."""
+    bboxes, img_h, img_w = _paste_geometry(det_bboxes, ori_shape, scale_factor, rescale)
+    threshold = _mask_threshold(rcnn_test_cfg)
+    if len(mask_pred) == 0:
+        return [] if num_classes is None else [[] for _ in range(num_classes)]
+    if encode:
+        segs = ops.paste_rle(mask_pred, bboxes, img_h, img_w, threshold, apply_sigmoid=apply_sigmoid)
+    else:
+        im, = _to_host(ops.paste_masks(mask_pred, bboxes, img_h, img_w, threshold, apply_sigmoid=apply_sigmoid))
+        segs = list(im)
+    if num_classes is None:
+        return segs
+    cls_segms = [[] for _ in range(num_classes)]
+    for c, segm in zip(det_labels.tolist() if labels_host is None else labels_host, segs):
+        cls_segms[c].append(segm)
+    return cls_segms
 
 
 @HEADS.register_module()
@@ -528,32 +572,16 @@ class DynaMaskHead(nn.Module):
         return [torch.cat(t) for t in per_stage]
 
     def get_seg_masks(self, mask_pred, det_bboxes, det_labels, rcnn_test_cfg, ori_shape, scale_factor, rescale):
-        """dynamask_head.py:279-342: sigmoid -> paste into the image -> threshold ->
-        list of (h, w) bool numpy arrays (one paste kernel for all detections)."""
-        bboxes, img_h, img_w = _paste_geometry(det_bboxes, ori_shape, scale_factor, rescale)
-        threshold = rcnn_test_cfg.mask_thr_binary
-        if threshold < 0:
-            raise NotImplementedError('visualisation mode (mask_thr_binary < 0) is not on the path')
-        if mask_pred.shape[1] > 1:
-            mask_pred = mask_pred[range(len(mask_pred)), det_labels][:, None]
-        im_mask = ops.paste_masks(mask_pred.contiguous(), bboxes, img_h, img_w, threshold, apply_sigmoid=True)
-        im = _bitmaps_to_host(im_mask)
-        return [im[i] for i in range(len(im))]
-
+        """dynamask_head.py:279-342: sigmoid -> paste into the image -> threshold -> list of (h, w) bool numpy arrays,
+        one per detection (one paste kernel for all detections)."""
+        return paste_segms(select_label_channel(mask_pred, det_labels), det_bboxes, det_labels, rcnn_test_cfg, ori_shape,
+                           scale_factor, rescale)
 
     def get_seg_rles(self, mask_pred, det_bboxes, det_labels, rcnn_test_cfg, ori_shape, scale_factor, rescale):
-        """``get_seg_masks`` followed by ``encode_mask_results`` (dynamask_head.py:279-342 +
-        core/mask/utils.py:36-63) without the bitmaps: paste, threshold and run-length
-        encoding run on the device, only run boundaries are copied to the host.  Returns one
-        COCO RLE dict per detection -- what ``mask_util.encode(np.array(m[:, :, None],
-        order='F'))[0]`` yields for the bitmap ``get_seg_masks`` would have returned."""
-        bboxes, img_h, img_w = _paste_geometry(det_bboxes, ori_shape, scale_factor, rescale)
-        threshold = rcnn_test_cfg.mask_thr_binary
-        if threshold < 0:
-            raise NotImplementedError('visualisation mode (mask_thr_binary < 0) is not on the path')
-        if mask_pred.shape[1] > 1:
-            mask_pred = mask_pred[range(len(mask_pred)), det_labels][:, None]
-        return ops.paste_rle(mask_pred.contiguous(), bboxes, img_h, img_w, threshold, apply_sigmoid=True)
+        """``get_seg_masks`` followed by ``encode_mask_results``, on the device (``paste_segms``): one COCO RLE dict per
+        detection."""
+        return paste_segms(select_label_channel(mask_pred, det_labels), det_bboxes, det_labels, rcnn_test_cfg, ori_shape,
+                           scale_factor, rescale, encode=True)
 
 
 # ---------------------------------------------------------------- FCN mask head
@@ -747,44 +775,23 @@ class FCNMaskHead(nn.Module):
             apply_sigmoid = True            # single-scale testing hands over logits (fcn_mask_head.py:168-169)
         else:                               # multi-scale testing: probabilities, already averaged, as an ndarray (:170-171)
             mask_pred, apply_sigmoid = det_bboxes.new_tensor(mask_pred), False
-        if not self.class_agnostic:
-            n = len(mask_pred)
-            mask_pred = mask_pred[torch.arange(n, device=mask_pred.device), det_labels.to(mask_pred.device)][:, None]
-        return mask_pred.contiguous(), apply_sigmoid
+        return select_label_channel(mask_pred, det_labels), apply_sigmoid
 
     def get_seg_masks(self, mask_pred, det_bboxes, det_labels, rcnn_test_cfg, ori_shape, scale_factor, rescale):
         """fcn_mask_head.py:151-237: (sigmoid ->) class select -> paste into the image -> threshold -> ``cls_segms``:
         one list per class holding the (h, w) bool arrays of that class's detections, in detection order.  The
         [n, classes, S, S] logits are gathered first (the sigmoid commutes with the selection), then one paste kernel
         runs for all detections and ONE device -> host copy carries the bitmaps."""
-        bboxes, img_h, img_w = _paste_geometry(det_bboxes, ori_shape, scale_factor, rescale)
-        threshold = rcnn_test_cfg.mask_thr_binary
-        if threshold < 0:
-            raise NotImplementedError('visualisation mode (mask_thr_binary < 0) is not on the path')
-        cls_segms = [[] for _ in range(self.num_classes)]
-        if len(mask_pred) == 0:
-            return cls_segms
         sel, apply_sigmoid = self._selected(mask_pred, det_bboxes, det_labels)
-        im = _bitmaps_to_host(ops.paste_masks(sel, bboxes, img_h, img_w, threshold, apply_sigmoid=apply_sigmoid))
-        for i, lab in enumerate(det_labels.tolist()):
-            cls_segms[lab].append(im[i])
-        return cls_segms
+        return paste_segms(sel, det_bboxes, det_labels, rcnn_test_cfg, ori_shape, scale_factor, rescale,
+                           apply_sigmoid=apply_sigmoid, num_classes=self.num_classes)
 
     def get_seg_rles(self, mask_pred, det_bboxes, det_labels, rcnn_test_cfg, ori_shape, scale_factor, rescale):
         """``get_seg_masks`` followed by ``encode_mask_results`` (core/mask/utils.py:36-63) without the bitmaps: paste,
         threshold and run-length encoding on the device; returns ``cls_segms`` of COCO RLE dicts."""
-        bboxes, img_h, img_w = _paste_geometry(det_bboxes, ori_shape, scale_factor, rescale)
-        threshold = rcnn_test_cfg.mask_thr_binary
-        if threshold < 0:
-            raise NotImplementedError('visualisation mode (mask_thr_binary < 0) is not on the path')
-        cls_segms = [[] for _ in range(self.num_classes)]
-        if len(mask_pred) == 0:
-            return cls_segms
         sel, apply_sigmoid = self._selected(mask_pred, det_bboxes, det_labels)
-        rles = ops.paste_rle(sel, bboxes, img_h, img_w, threshold, apply_sigmoid=apply_sigmoid)
-        for lab, r in zip(det_labels.tolist(), rles):
-            cls_segms[lab].append(r)
-        return cls_segms
+        return paste_segms(sel, det_bboxes, det_labels, rcnn_test_cfg, ori_shape, scale_factor, rescale, encode=True,
+                           apply_sigmoid=apply_sigmoid, num_classes=self.num_classes)
 
 
 # ---------------------------------------------------------------- RefineMask head (inference)

@@ -1,12 +1,11 @@
-"""DynaMaskRoIHead behind the reference's HEADS registry.
+"""The RoI heads behind the reference's HEADS registry, in the reference's class tree: ``StandardRoIHead``
+(standard_roi_head.py + test_mixins.py) is the base of ``DynaMaskRoIHead``, ``RefineRoIHead`` and ``PointRendRoIHead``.
 
-Mirrors ``mmdet/models/roi_heads/dynamask_roi_head.py:10-158`` +
-``base_roi_head.py:10-58`` for the MASK path: ``_mask_forward``,
-``get_mask_label`` (MaskPre + straight-through Gumbel selector),
-``_mask_forward_train`` and ``simple_test_mask``, plus the callers either side of
-it under the reference's signatures: ``forward_train`` (assigner + sampler, bbox
-branch losses, mask targets on the device; dynamask_roi_head.py:21-46) and
-``simple_test``.
+The base holds the constructor (incl. ``base_roi_head.py:10-58``'s MaskPre, Quirk Q4), the assigner / sampler, the bbox
+branch, the one-image / batched / test-time-augmentation entry points and one mask-test template over a head's
+``_mask_logits``.  ``DynaMaskRoIHead`` mirrors ``mmdet/models/roi_heads/dynamask_roi_head.py:10-158`` for the MASK path:
+``_mask_forward``, ``get_mask_label`` (MaskPre + straight-through Gumbel selector), ``_mask_forward_train`` (assigner +
+sampler, bbox branch losses, mask targets on the device; dynamask_roi_head.py:21-46) and the merged logits of the test.
 """
 import torch
 import torch.nn as nn
@@ -129,9 +128,30 @@ class MaskPre(nn.Module):
                                 bn.weight.detach(), bn.bias.detach(), bn.eps)
         return self._tail(x)
 
+def merge_stage_preds(stage_instance_preds):
+    """Boundary-aware coarse-to-fine merge, dynamask_roi_head.py:138-149 = refine_roi_head.py:102-113
+    (in place on the finer logits, as the reference; the 14x14 exit is unused)."""
+    preds = stage_instance_preds[1:]
+    for idx in range(len(preds) - 1):
+        ops.boundary_merge_(preds[idx], preds[idx + 1])
+    return preds[-1]
+
 
 @HEADS.register_module()
-class DynaMaskRoIHead(nn.Module):
+class StandardRoIHead(nn.Module):
+    """``StandardRoIHead`` -- mmdet/models/roi_heads/standard_roi_head.py:10-290 + ``MaskTestMixin`` (test_mixins.py):
+    the RoI head of configs/mask_rcnn and configs/carafe (BASELINE configs[4]), whose mask head is ``FCNMaskHead``, and
+    the base of the other three RoI heads, as in the reference.  It holds what they share: the constructor, the
+    assigner / sampler, the bbox branch, ``simple_test`` / ``batch_simple_test`` / ``aug_test`` and the mask-test
+    template.  A head supplies its mask prediction through ``_mask_logits(x, mask_rois, labels)`` -> [n, C, S, S] and
+    its (C, S) through ``_mask_logits_size``; the template does the rest once for every head: rescale, ``bbox2roi``,
+    the empty case, the label-channel selection, the paste, the device -> host copy and the grouping by class.  Here the
+    mask branch is the stock one: ``_mask_forward(x, rois)`` -> ``{'mask_pred': [N, classes, 28, 28], 'mask_feats'}``.
+    ``BaseRoIHead.__init__`` of the fork builds ``mask_predictor`` / ``semantic_roi_extractor`` for EVERY RoI head (Quirk
+    Q4), so the ``state_dict`` carries the ``mask_predictor.*`` keys here too, as the reference's does.
+    Training: ``forward_train`` follows standard_roi_head.py:70-134; its mask loss ends in ``FCNMaskHead.loss``, which
+    the fork broke (Quirk Q5) -- it raises here as it does there, the bbox losses and the mask targets are computed."""
+
     def __init__(self, bbox_roi_extractor=None, bbox_head=None, mask_roi_extractor=None, mask_head=None,
                  shared_head=None, train_cfg=None, test_cfg=None):
         super().__init__()
@@ -158,15 +178,7 @@ class DynaMaskRoIHead(nn.Module):
             type='SingleRoIExtractor', roi_layer=dict(type='RoIAlign', output_size=56, sampling_ratio=0),
             out_channels=256, featmap_strides=[4, ]))
         self.mask_predictor = MaskPre()
-        # inference: RoI chunks on separate HIP streams (see _mask_forward)
-        self.num_streams = 2
-        # RoI chunks on two streams from this many RoIs on (profiles/r06_infer_notes.txt (12), 1 / 2 / 3 streams).  Replayed
-        # as a HIP graph: 24 detections 0.734 / 0.764 / 0.767, 32: 0.885 / 0.871 / 0.907, 48: 1.175 / 1.157 / 1.140, 64: 1.459 /
-        # 1.365 / 1.411, 80: 1.646 / 1.604 / 1.647, 100: 2.024 / 1.881 / 1.916 ms.  Eager, the host issues the two chains' launches
-        # one after the other and a call cannot take less than that (~1.6-1.7 ms): 1 / 2 streams at 32 detections 0.88 / 1.69,
-        # 48: 1.17 / 1.71, 64: 1.45 / 1.61, 80: 1.63 / 1.61, 100: 2.01 / 1.89 ms.
-        self.stream_split_min = 80           # eager launches
-        self.stream_split_min_graph = 32     # under HIP-graph capture (graphs.py)
+        self._mask_graphs = None        # graphs.GraphedMaskLogits of ``_mask_logits`` (enable_inference_graphs)
 
     def init_assigner_sampler(self):
         """standard_roi_head.py:13-20."""
@@ -189,6 +201,478 @@ class DynaMaskRoIHead(nn.Module):
         if self.with_mask:
             self.mask_head.init_weights()
             self.mask_roi_extractor.init_weights()
+
+    # ------------------------------------------------------------------ training entry points
+    def _assign_and_sample(self, x, img_metas, proposal_list, gt_bboxes, gt_labels, gt_bboxes_ignore=None):
+        """standard_roi_head.py:86-103: assign gts and sample proposals per image.  Assignment and sampling of every
+        image are enqueued first; the host then waits ONCE for all the (positive, negative) counts that size the heads'
+        tensors, not once per image (RandomSampler.sample_deferred)."""
+        num_imgs = len(img_metas)
+        if gt_bboxes_ignore is None:
+            gt_bboxes_ignore = [None for _ in range(num_imgs)]
+        deferred = hasattr(self.bbox_sampler, 'sample_deferred')
+        do_sample = self.bbox_sampler.sample_deferred if deferred else self.bbox_sampler.sample
+        sampling_results = []
+        for i in range(num_imgs):
+            assign_result = self.bbox_assigner.assign(proposal_list[i], gt_bboxes[i], gt_bboxes_ignore[i], gt_labels[i])
+            sampling_results.append(do_sample(assign_result, proposal_list[i], gt_bboxes[i], gt_labels[i],
+                                              feats=[lvl_feat[i][None] for lvl_feat in x]))
+        if deferred:
+            sampling_results = self.bbox_sampler.finish_samples(sampling_results)
+        return sampling_results
+
+    def forward_train(self, x, img_metas, proposal_list, gt_bboxes, gt_labels, gt_bboxes_ignore=None, gt_masks=None):
+        """standard_roi_head.py:70-134."""
+        sampling_results = self._assign_and_sample(x, img_metas, proposal_list, gt_bboxes, gt_labels, gt_bboxes_ignore)
+        losses = dict()
+        bbox_results = None
+        if self.with_bbox:
+            bbox_results = self._bbox_forward_train(x, sampling_results, gt_bboxes, gt_labels, img_metas)
+            losses.update(bbox_results['loss_bbox'])
+        if self.with_mask:
+            mask_results = self._mask_forward_train(x, sampling_results, None if bbox_results is None else bbox_results['bbox_feats'],
+                                                    gt_masks, img_metas)
+            if mask_results['loss_mask'] is not None:
+                losses.update(mask_results['loss_mask'])
+        return losses
+
+    def _bbox_forward_train(self, x, sampling_results, gt_bboxes, gt_labels, img_metas):
+        """standard_roi_head.py:147-160."""
+        rois = bbox2roi([res.bboxes for res in sampling_results]).contiguous()
+        if torch.is_grad_enabled():
+            from . import train_path
+            bbox_feats = train_path.roi_extract_train(self.bbox_roi_extractor, x, rois)
+        else:
+            bbox_feats = self.bbox_roi_extractor(x[:self.bbox_roi_extractor.num_inputs], rois)
+        cls_score, bbox_pred = self.bbox_head(bbox_feats)
+        bbox_results = dict(cls_score=cls_score, bbox_pred=bbox_pred, bbox_feats=bbox_feats)
+        bbox_targets = self.bbox_head.get_targets(sampling_results, gt_bboxes, gt_labels, self.train_cfg)
+        loss_bbox = self.bbox_head.loss(cls_score, bbox_pred, rois, *bbox_targets)
+        bbox_results.update(loss_bbox=loss_bbox)
+        return bbox_results
+
+    def _mask_forward(self, x, rois=None, pos_inds=None, bbox_feats=None, **kw):
+        """standard_roi_head.py:199-215."""
+        assert (rois is not None) ^ (pos_inds is not None and bbox_feats is not None)
+        if rois is not None:
+            ext = self.mask_roi_extractor
+            mask_feats = ext(x[:ext.num_inputs], rois.contiguous())
+        else:
+            mask_feats = bbox_feats[pos_inds].contiguous()
+        return dict(mask_pred=self.mask_head(mask_feats), mask_feats=mask_feats)
+
+    def _mask_forward_train(self, x, sampling_results, bbox_feats, gt_masks, img_metas, **kw):
+        """standard_roi_head.py:162-197 (the mask branch with its own RoI extractor)."""
+        pos_rois = bbox2roi([res.pos_bboxes for res in sampling_results]).contiguous()
+        if pos_rois.shape[0] == 0:
+            return dict(loss_mask=None)
+        mask_results = self._mask_forward(x, pos_rois)
+        mask_targets = self.mask_head.get_targets(sampling_results, gt_masks, self.train_cfg)
+        pos_labels = torch.cat([res.pos_gt_labels for res in sampling_results])
+        loss_mask = self.mask_head.loss(mask_results['mask_pred'], mask_targets, pos_labels)
+        mask_results.update(loss_mask=loss_mask, mask_targets=mask_targets)
+        return mask_results
+
+    # ------------------------------------------------------------ bbox branch (inference)
+    def _bbox_forward(self, x, rois):
+        """standard_roi_head.py:135-146."""
+        bbox_feats = self.bbox_roi_extractor(x[:self.bbox_roi_extractor.num_inputs], rois)
+        cls_score, bbox_pred = self.bbox_head(bbox_feats)
+        return dict(cls_score=cls_score, bbox_pred=bbox_pred, bbox_feats=bbox_feats)
+
+    @torch.no_grad()
+    def simple_test_bboxes(self, x, img_metas, proposals, rcnn_test_cfg, rescale=False):
+        """test_mixins.py:52-71 (BBoxTestMixin.simple_test_bboxes), one image."""
+        rois = bbox2roi(proposals).contiguous()
+        res = self._bbox_forward(x, rois)
+        return self.bbox_head.get_bboxes(rois, res['cls_score'], res['bbox_pred'], img_metas[0]['img_shape'],
+                                         img_metas[0]['scale_factor'], rescale=rescale, cfg=rcnn_test_cfg)
+
+    @torch.no_grad()
+    def simple_test(self, x, proposal_list, img_metas, proposals=None, rescale=False, encode=False):
+        """standard_roi_head.py:217-236: boxes, then masks of the kept detections."""
+        from .bbox_heads import bbox2result
+        det_bboxes, det_labels = self.simple_test_bboxes(x, img_metas, proposal_list, self.test_cfg, rescale=rescale)
+        bbox_results = bbox2result(det_bboxes, det_labels, self.bbox_head.num_classes)
+        if not self.with_mask:
+            return bbox_results
+        segm_results = self.simple_test_mask(x, img_metas, det_bboxes, det_labels, rescale=rescale, encode=encode)
+        return bbox_results, segm_results
+
+    # ------------------------------------------------------------ mask test: the hooks of a head
+    def _mask_logits(self, x, mask_rois, labels):
+        """The mask prediction of the RoIs [n, C, S, S] that is pasted (after the label-channel selection) or merged
+        over the views of test-time augmentation.  Here: ``_mask_forward``'s ``mask_pred`` (test_mixins.py:166-168)."""
+        with torch.no_grad():
+            return self._mask_forward(x, mask_rois)['mask_pred']
+
+    def _mask_logits_size(self):
+        """(C, S) of what ``_mask_logits`` returns (the shape of the empty results): FCNMaskHead's logits of the RoI
+        extractor's features, upsampled by its ``scale_factor``."""
+        h = self.mask_head
+        s = self.mask_roi_extractor.roi_layers[0].output_size[0]
+        return h.conv_logits.out_channels, int(s * (h.scale_factor if h.upsample is not None else 1))
+
+    def _segm_num_classes(self):
+        """The number of per-class lists of ``simple_test_mask``."""
+        return self.mask_head.num_classes
+
+    def _empty_mask_logits(self, ref, channels=None):
+        c, s = self._mask_logits_size()
+        return ref.new_zeros((0, c if channels is None else channels, s, s))
+
+    def enable_inference_graphs(self, on=True, buckets=None, batch_buckets=None):
+        """HIP-graph replay of the mask call: DynaMaskRoIHead's; for the other heads it is a follow-up."""
+        if on:
+            raise NotImplementedError(f'{type(self).__name__}: HIP-graph capture of its mask call is a follow-up')
+        self._mask_graphs = None
+        return None
+
+    # ------------------------------------------------------------ mask test: one image
+    def simple_test_mask_logits(self, x, det_bboxes, det_labels, scale_factor=1.0, rescale=False):
+        """simple_test_mask up to the mask prediction ``_mask_logits`` [n, C, S, S] of the detections (pasting into the
+        image is the step after the path).  With ``enable_inference_graphs`` the call replays a graph bucketed on the
+        detection count (graphs.BUCKETS; larger counts run eagerly)."""
+        if det_bboxes.shape[0] == 0:
+            return self._empty_mask_logits(det_bboxes)
+        _bboxes = det_bboxes[:, :4] * scale_factor if rescale else det_bboxes
+        if self._mask_graphs is not None and not torch.is_grad_enabled():
+            # bucketed HIP-graph replay (graphs.py); None: too many RoIs.  The boxes go straight into the graph's RoI buffer.
+            merged = self._mask_graphs(x, None, det_labels, boxes=_bboxes)
+            if merged is not None:
+                return merged
+        return self._mask_logits(x, bbox2roi([_bboxes]).contiguous(), det_labels)
+
+    def simple_test_mask(self, x, img_metas, det_bboxes, det_labels, rescale=False, encode=False):
+        """test_mixins.py:151-176 (dynamask_roi_head.py:117-158, point_rend_roi_head.py:130-155) -> per-class lists of
+        (h, w) bool masks: the detections' ``simple_test_mask_logits``, their label channel pasted into the image.
+        ``encode=True`` (extension): per-class lists of COCO RLE dicts instead, i.e. the result after the caller's
+        ``encode_mask_results`` (apis/test.py:52-57), produced on the device."""
+        from .mask_heads import paste_segms, select_label_channel
+        num_classes = self._segm_num_classes()
+        if det_bboxes.shape[0] == 0:
+            return [[] for _ in range(num_classes)]
+        _bboxes, scale_factor = self._mask_boxes(det_bboxes, img_metas[0]['scale_factor'], rescale)
+        logits = self.simple_test_mask_logits(x, _bboxes, det_labels)
+        return paste_segms(select_label_channel(logits, det_labels), _bboxes, det_labels, self.test_cfg,
+                           img_metas[0]['ori_shape'], scale_factor, rescale, encode=encode, num_classes=num_classes)
+
+    # ------------------------------------------------------------ batched inference: B images per call
+    # Each method gives, per image, what its one-image counterpart gives for that image alone; the B images share the
+    # launches: one bbox branch over all proposals, one segmented NMS, one mask chain over all detections, one paste.
+    _META_KEYS = ('img_shape', 'ori_shape', 'scale_factor')
+
+    @classmethod
+    def _check_batch(cls, img_metas, _name='img_metas', **lists):
+        """Argument checks of the batch_* methods (before any GPU work): a non-empty per-image list ``img_metas`` (named
+        ``_name`` in the message) and every other per-image list of the same length B."""
+        if not isinstance(img_metas, (list, tuple)) or len(img_metas) == 0:
+            raise ValueError(f'{_name}: a non-empty list with one entry per image')
+        B = len(img_metas)
+        for name, v in lists.items():
+            if v is not None and len(v) != B:
+                raise ValueError(f'{name}: {len(v)} entries for {B} images')
+        return B
+
+    @classmethod
+    def _check_metas(cls, img_metas, keys):
+        for i, m in enumerate(img_metas):
+            missing = [k for k in keys if k not in m]
+            if missing:
+                raise ValueError(f'img_metas[{i}] lacks {missing}')
+
+    @staticmethod
+    def _scale_factor_on(scale_factor, device):
+        """``torch.from_numpy(scale_factor).to(device)`` of the reference's mask tests (same dtype, same values) through
+        a pinned buffer: no host wait per image."""
+        if isinstance(scale_factor, float):
+            return scale_factor
+        import numpy as np
+        return torch.from_numpy(np.ascontiguousarray(scale_factor)).pin_memory().to(device, non_blocking=True)
+
+    def _mask_boxes(self, det_bboxes, scale_factor, rescale):
+        """(The boxes the mask chain reads, the scale factor the paste divides them by) of one image's detections, as
+        the reference's mask tests derive them (``rescale``: the boxes times ``scale_factor``, on the device)."""
+        if not rescale or det_bboxes.shape[0] == 0:
+            return det_bboxes, scale_factor
+        scale_factor = self._scale_factor_on(scale_factor, det_bboxes.device)
+        return det_bboxes[:, :4] * scale_factor, scale_factor
+
+    def batch_simple_test_mask_logits(self, x, det_bboxes_list, det_labels_list, scale_factors=None, rescale=False):
+        """``simple_test_mask_logits`` of B images as ONE mask chain: the [sum N, 5] RoI rows of all images (batch column
+        = image index into the B-image FPN tuple ``x``) -> the logits [sum N, C, S, S] and the row offsets [B + 1]
+        (image b: rows offsets[b]:offsets[b + 1]).  ``rescale``: image b's boxes are multiplied by ``scale_factors[b]``
+        first.  B = 1 is ``simple_test_mask_logits`` itself.  With ``enable_inference_graphs`` the call replays a graph
+        bucketed on the total RoI count (graphs.BATCH_BUCKETS; larger totals run eagerly)."""
+        B = self._check_batch(det_bboxes_list, 'det_bboxes_list', det_labels_list=det_labels_list, scale_factors=scale_factors)
+        if rescale and scale_factors is None:
+            raise ValueError('rescale=True needs scale_factors')
+        offsets = [0]
+        for det in det_bboxes_list:
+            offsets.append(offsets[-1] + int(det.shape[0]))
+        sfs = scale_factors if rescale else [None] * B
+        boxes = [self._mask_boxes(det, sf, rescale)[0] for det, sf in zip(det_bboxes_list, sfs)]
+        if offsets[-1] == 0:
+            return self._empty_mask_logits(det_bboxes_list[0]), offsets
+        if B == 1:
+            return self.simple_test_mask_logits(x, boxes[0], det_labels_list[0]), offsets
+        mask_rois = bbox2roi(boxes).contiguous()
+        labels = torch.cat(list(det_labels_list)).contiguous()
+        if self._mask_graphs is not None and not torch.is_grad_enabled():
+            merged = self._mask_graphs.batched(x, mask_rois, labels, B)
+            if merged is not None:
+                return merged, offsets
+        return self._mask_logits(x, mask_rois, labels), offsets
+
+    @torch.no_grad()
+    def batch_simple_test_mask(self, x, img_metas, det_bboxes_list, det_labels_list, rescale=False, encode=False,
+                               _labels_host=None):
+        """``simple_test_mask`` of B images: per image the per-class lists of (h, w) bool masks (``encode``: COCO RLE
+        dicts) of its detections, on its own canvas (``ori_shape``, ``scale_factor``).  One mask chain, one paste launch
+        (dm_paste_masks_multi / dm_paste_rle_multi) and one device -> host copy for all images."""
+        from .mask_heads import _mask_threshold, _paste_geometry, _to_host, select_label_channel
+        import numpy as np
+        B = self._check_batch(img_metas, det_bboxes_list=det_bboxes_list, det_labels_list=det_labels_list)
+        self._check_metas(img_metas, ('ori_shape', 'scale_factor'))
+        num_classes = self._segm_num_classes()
+        results = [[[] for _ in range(num_classes)] for _ in range(B)]
+        counts = [int(d.shape[0]) for d in det_bboxes_list]
+        if sum(counts) == 0:
+            return results
+        threshold = _mask_threshold(self.test_cfg)
+        boxes, sfs = zip(*[self._mask_boxes(det, meta['scale_factor'], rescale)
+                           for det, meta in zip(det_bboxes_list, img_metas)])
+        labels = torch.cat(list(det_labels_list))
+        preds = select_label_channel(self.batch_simple_test_mask_logits(x, boxes, det_labels_list)[0], labels)
+        canvas_boxes, sizes = [], []
+        for b in range(B):
+            if counts[b] == 0:
+                sizes.append((1, 1))
+                continue
+            cb, h, w = _paste_geometry(boxes[b], img_metas[b]['ori_shape'], sfs[b], rescale)
+            canvas_boxes.append(cb)
+            sizes.append((h, w))
+        canvas_boxes = torch.cat(canvas_boxes).contiguous()
+        if encode:
+            segs = ops.paste_rle_multi(preds, canvas_boxes, counts, sizes, threshold, apply_sigmoid=True)
+            labels_h = _labels_host if _labels_host is not None else labels.cpu().tolist()
+        else:
+            buf, offs, det_sizes = ops.paste_masks_multi(preds, canvas_boxes, counts, sizes, threshold, apply_sigmoid=True)
+            if _labels_host is None:
+                flat, labels_h = _to_host(buf, labels)
+                labels_h = labels_h.tolist()
+            else:
+                (flat,), labels_h = _to_host(buf), _labels_host
+            flat = flat.view(np.bool_)
+            segs = [flat[o:o + h * w].reshape(h, w) for o, (h, w) in zip(offs, det_sizes)]
+        start = 0
+        for b in range(B):
+            for j in range(start, start + counts[b]):
+                results[b][labels_h[j]].append(segs[j])
+            start += counts[b]
+        return results
+
+    @torch.no_grad()
+    def batch_simple_test_bboxes(self, x, img_metas, proposals, rcnn_test_cfg, rescale=False):
+        """``simple_test_bboxes`` of B images -> list of B (dets [k, 5], labels [k]): one bbox branch over the
+        proposals of all images, per-image decode (its own ``img_shape`` clip and ``scale_factor``), one segmented NMS
+        (bbox_heads.multiclass_nms_batch)."""
+        from .bbox_heads import multiclass_nms_batch
+        B = self._check_batch(img_metas, proposals=proposals)
+        self._check_metas(img_metas, ('img_shape', 'scale_factor'))
+        rows = [int(p.shape[0]) for p in proposals]
+        rois = bbox2roi(proposals).contiguous()
+        if rois.shape[0] == 0:
+            ref = proposals[0]
+            return [(ref.new_zeros((0, 5)), ref.new_zeros((0,), dtype=torch.long)) for _ in range(B)]
+        res = self._bbox_forward(x, rois)
+        cls_score, bbox_pred = res['cls_score'], res['bbox_pred']
+        bl, sl, r0 = [], [], 0
+        for b in range(B):
+            r1 = r0 + rows[b]
+            if r1 == r0:
+                bl.append(rois.new_zeros((0, 4)))
+                sl.append(rois.new_zeros((0, self.bbox_head.num_classes + 1)))
+            else:
+                bboxes, scores = self.bbox_head.get_bboxes(
+                    rois[r0:r1], None if cls_score is None else cls_score[r0:r1],
+                    None if bbox_pred is None else bbox_pred[r0:r1], img_metas[b]['img_shape'],
+                    img_metas[b]['scale_factor'], rescale=rescale, cfg=None)
+                bl.append(bboxes)
+                sl.append(scores)
+            r0 = r1
+        cfg = rcnn_test_cfg
+        return multiclass_nms_batch(bl, sl, cfg.score_thr, cfg.nms, cfg.max_per_img)
+
+    @torch.no_grad()
+    def batch_simple_test(self, x, proposal_list, img_metas, rescale=False, encode=False):
+        """``simple_test`` of B images in one call (the contract of later mmdet releases): ``x`` the FPN tuple with
+        batch dimension B, ``proposal_list`` / ``img_metas`` one entry per image -> list of B ``(bbox_results,
+        segm_results)``, each what ``simple_test`` returns for that image alone (just ``bbox_results`` without a mask
+        branch).  Host waits do not grow with B: the detections of all images cross to the host in one copy."""
+        from .mask_heads import _to_host
+        B = self._check_batch(img_metas, proposal_list=proposal_list)
+        self._check_metas(img_metas, self._META_KEYS)
+        for i, f in enumerate(x):
+            if f.shape[0] != B:
+                raise ValueError(f'x[{i}] has batch dimension {f.shape[0]} for {B} images')
+        dets = self.batch_simple_test_bboxes(x, img_metas, proposal_list, self.test_cfg, rescale=rescale)
+        counts = [int(d.shape[0]) for d, _ in dets]
+        num_classes = self.bbox_head.num_classes
+        if sum(counts) == 0:
+            import numpy as np
+            bbox_results = [[np.zeros((0, 5), dtype=np.float32) for _ in range(num_classes)] for _ in range(B)]
+            labels_h = []
+        else:
+            d_np, l_np = _to_host(torch.cat([d for d, _ in dets]), torch.cat([l for _, l in dets]))
+            labels_h = l_np.tolist()
+            bbox_results, start = [], 0
+            for c in counts:
+                bbox_results.append(_bbox2result_host(d_np[start:start + c], l_np[start:start + c], num_classes))
+                start += c
+        if not self.with_mask:
+            return bbox_results
+        segm_results = self.batch_simple_test_mask(x, img_metas, [d for d, _ in dets], [l for _, l in dets],
+                                                   rescale=rescale, encode=encode, _labels_host=labels_h)
+        return list(zip(bbox_results, segm_results))
+
+    # ------------------------------------------------------------ test-time augmentation: V views of one image
+    # standard_roi_head.py:264-290 + test_mixins.py:73-107,178-208 (MultiScaleFlipAug): ``x`` holds one FPN tuple per view
+    # (batch size 1 each), ``img_metas`` one single-element list per view.  The views share three launches: the mapping of
+    # the boxes into every view (dm_bbox_mapping_multi), the box / score merge (dm_merge_aug_bboxes) and the mask merge
+    # (dm_merge_aug_masks); the bbox branch and the mask chain run once per view through the one-view path.  No host wait
+    # inside the per-view loops.  A view's mask prediction is what ``simple_test_mask_logits`` returns for the mapped
+    # boxes (for the DynaMask head this is the project's definition, the reference cannot run it: DESIGN.md section 4.10).
+    _AUG_META_KEYS = ('img_shape', 'scale_factor', 'flip', 'flip_direction', 'ori_shape')
+
+    @classmethod
+    def _check_aug(cls, x, img_metas):
+        """Argument checks of the aug_test* methods (before any GPU work) -> the V view metas."""
+        if not isinstance(img_metas, (list, tuple)) or len(img_metas) == 0:
+            raise ValueError('img_metas: a non-empty list with one single-element list per view')
+        V = len(img_metas)
+        if len(x) != V:
+            raise ValueError(f'x has {len(x)} views, img_metas {V}')
+        views = []
+        for v, m in enumerate(img_metas):
+            if not isinstance(m, (list, tuple)) or len(m) != 1:
+                raise ValueError(f'img_metas[{v}]: one meta per view (test-time augmentation runs one image)')
+            missing = [k for k in cls._AUG_META_KEYS if k not in m[0]]
+            if missing:
+                raise ValueError(f'img_metas[{v}][0] lacks {missing}')
+            if x[v][0].shape[0] != 1:
+                raise ValueError(f'x[{v}] has batch dimension {x[v][0].shape[0]}: one image per view')
+            views.append(m[0])
+        ops.aug_view_rows(views)                    # flip directions and scale factors
+        return views
+
+    @torch.no_grad()
+    def aug_test_bboxes(self, x, img_metas, proposal_list, rcnn_test_cfg):
+        """test_mixins.py:73-107: the proposals ``proposal_list[0]`` (original image) mapped into every view, the bbox
+        branch and ``get_bboxes(rescale=False)`` per view, the views' boxes mapped back and averaged with their scores
+        (merge_aug_bboxes), then ``multiclass_nms`` -> (dets [k, 5], labels [k]) in original-image coordinates."""
+        from .bbox_heads import multiclass_nms
+        views = self._check_aug(x, img_metas)
+        props = proposal_list[0]
+        if props.shape[0] == 0:
+            return props.new_zeros((0, 5)), props.new_zeros((0,), dtype=torch.long)
+        tab = ops.aug_view_table(views, props.device)
+        rois = ops.bbox_mapping_multi(props, tab)
+        aug_bboxes, aug_scores = [], []
+        for v, meta in enumerate(views):
+            res = self._bbox_forward(x[v], rois[v])
+            bboxes, scores = self.bbox_head.get_bboxes(rois[v], res['cls_score'], res['bbox_pred'], meta['img_shape'],
+                                                       meta['scale_factor'], rescale=False, cfg=None)
+            aug_bboxes.append(bboxes.contiguous())
+            aug_scores.append(scores.contiguous())
+        merged_bboxes, merged_scores = ops.merge_aug_bboxes(aug_bboxes, aug_scores, tab)
+        cfg = rcnn_test_cfg
+        return multiclass_nms(merged_bboxes, merged_scores, cfg.score_thr, cfg.nms, cfg.max_per_img)
+
+    @torch.no_grad()
+    def aug_test_mask_probs(self, x, img_metas, det_bboxes, det_labels):
+        """The merged mask probabilities of test-time augmentation [n, 1, S, S] on the device: ``det_bboxes`` (original
+        image) mapped into every view, the view's mask prediction, then sigmoid, un-flip and mean over the views
+        (merge_aug_masks) of the detection's class channel."""
+        views = self._check_aug(x, img_metas)
+        if det_bboxes.shape[0] == 0:
+            return self._empty_mask_logits(det_bboxes, channels=1)
+        tab = ops.aug_view_table(views, det_bboxes.device)
+        rois = ops.bbox_mapping_multi(det_bboxes, tab)
+        labels = det_labels.contiguous()
+        logits = []
+        for v in range(len(views)):
+            view_logits = self.simple_test_mask_logits(x[v], rois[v][:, 1:], labels)
+            if self._mask_graphs is not None:
+                view_logits = view_logits.clone()       # a graph's static output: the next view's replay overwrites it
+            logits.append(view_logits.contiguous())
+        return ops.merge_aug_masks(logits, labels, tab)
+
+    @torch.no_grad()
+    def aug_test_mask(self, x, img_metas, det_bboxes, det_labels, encode=False, _labels_host=None):
+        """test_mixins.py:178-208 -> per-class lists of (h, w) bool masks at ``ori_shape`` of the first view
+        (``encode``: COCO RLE dicts): the merged probabilities (``aug_test_mask_probs``) pasted without a sigmoid,
+        ``scale_factor=1.0, rescale=False``, thresholded at ``mask_thr_binary``."""
+        from .mask_heads import _mask_threshold, paste_segms
+        views = self._check_aug(x, img_metas)
+        num_classes = self._segm_num_classes()
+        if det_bboxes.shape[0] == 0:
+            return [[] for _ in range(num_classes)]
+        _mask_threshold(self.test_cfg)              # (raises before any device work)
+        probs = self.aug_test_mask_probs(x, img_metas, det_bboxes, det_labels)
+        return paste_segms(probs, det_bboxes, det_labels, self.test_cfg, views[0]['ori_shape'], 1.0, False, encode=encode,
+                           apply_sigmoid=False, num_classes=num_classes, labels_host=_labels_host)
+
+    @torch.no_grad()
+    def aug_test(self, x, proposal_list, img_metas, rescale=False, encode=False):
+        """standard_roi_head.py:264-290: boxes merged over the views, then masks merged over the views ->
+        ``(bbox_results, segm_results)`` (just ``bbox_results`` without a mask branch).  ``rescale=False`` scales only
+        the boxes of ``bbox_results`` by the first view's ``scale_factor``, as the reference does; the masks stay at
+        the original image's size either way."""
+        import numpy as np
+        from .mask_heads import _to_host
+        views = self._check_aug(x, img_metas)
+        det_bboxes, det_labels = self.aug_test_bboxes(x, img_metas, proposal_list, self.test_cfg)
+        num_classes = self.bbox_head.num_classes
+        if det_bboxes.shape[0] == 0:
+            bbox_results = [np.zeros((0, 5), dtype=np.float32) for _ in range(num_classes)]
+            labels_h = []
+        else:
+            _det_bboxes = det_bboxes
+            if not rescale:
+                _det_bboxes = det_bboxes.clone()
+                sf = views[0]['scale_factor']
+                _det_bboxes[:, :4] *= sf if isinstance(sf, float) else self._scale_factor_on(
+                    np.asarray(sf, dtype=np.float32), det_bboxes.device)
+            d_np, l_np = _to_host(_det_bboxes, det_labels)
+            bbox_results = _bbox2result_host(d_np, l_np, num_classes)
+            labels_h = l_np.tolist()
+        if not self.with_mask:
+            return bbox_results
+        segm_results = self.aug_test_mask(x, img_metas, det_bboxes, det_labels, encode=encode, _labels_host=labels_h)
+        return bbox_results, segm_results
+
+
+@HEADS.register_module()
+class DynaMaskRoIHead(StandardRoIHead):
+    """dynamask_roi_head.py:10-158: the selector (MaskPre + straight-through Gumbel), its own training step (the bbox
+    branch and the selector on side streams) and, for inference, the merged 112 x 112 logits of the three stages as the
+    head's ``_mask_logits`` -- split over RoI chunks on HIP streams, optionally replayed as HIP graphs -- plus the per-RoI
+    early exit (``dynamic_mask_logits`` / ``dynamic_test_mask``)."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        # inference: RoI chunks on separate HIP streams (see _mask_forward)
+        self.num_streams = 2
+        # RoI chunks on two streams from this many RoIs on (profiles/r06_infer_notes.txt (12), 1 / 2 / 3 streams).  Replayed
+        # as a HIP graph: 24 detections 0.734 / 0.764 / 0.767, 32: 0.885 / 0.871 / 0.907, 48: 1.175 / 1.157 / 1.140, 64: 1.459 /
+        # 1.365 / 1.411, 80: 1.646 / 1.604 / 1.647, 100: 2.024 / 1.881 / 1.916 ms.  Eager, the host issues the two chains' launches
+        # one after the other and a call cannot take less than that (~1.6-1.7 ms): 1 / 2 streams at 32 detections 0.88 / 1.69,
+        # 48: 1.17 / 1.71, 64: 1.45 / 1.61, 80: 1.63 / 1.61, 100: 2.01 / 1.89 ms.
+        self.stream_split_min = 80           # eager launches
+        self.stream_split_min_graph = 32     # under HIP-graph capture (graphs.py)
+
+    merge_stage_preds = staticmethod(merge_stage_preds)
 
     # ------------------------------------------------------------------ forward
     def _mask_forward(self, x, rois, roi_labels, last_stage=None, _between=None):
@@ -338,20 +822,7 @@ class DynaMaskRoIHead(nn.Module):
         sample proposals per image, bbox branch forward + loss, mask branch forward + loss.
         Returns the dict of losses the detector's ``_parse_losses`` sums.  ``noise`` (extension):
         the uniform draw of the Gumbel selector, for reproducible tests."""
-        num_imgs = len(img_metas)
-        if gt_bboxes_ignore is None:
-            gt_bboxes_ignore = [None for _ in range(num_imgs)]
-        sampling_results = []
-        # assignment and sampling of every image are enqueued first; the host then waits ONCE for all the (positive,
-        # negative) counts that size the heads' tensors, not once per image (RandomSampler.sample_deferred)
-        deferred = hasattr(self.bbox_sampler, 'sample_deferred')
-        do_sample = self.bbox_sampler.sample_deferred if deferred else self.bbox_sampler.sample
-        for i in range(num_imgs):
-            assign_result = self.bbox_assigner.assign(proposal_list[i], gt_bboxes[i], gt_bboxes_ignore[i], gt_labels[i])
-            sampling_results.append(do_sample(assign_result, proposal_list[i], gt_bboxes[i], gt_labels[i],
-                                              feats=[lvl_feat[i][None] for lvl_feat in x]))
-        if deferred:
-            sampling_results = self.bbox_sampler.finish_samples(sampling_results)
+        sampling_results = self._assign_and_sample(x, img_metas, proposal_list, gt_bboxes, gt_labels, gt_bboxes_ignore)
         # the bbox branch and the mask branch meet only in the sum of the losses: the bbox branch is issued on its own
         # stream (its backward follows it there) and joined before the losses are handed back
         losses = {}
@@ -385,21 +856,6 @@ class DynaMaskRoIHead(nn.Module):
         if mask_results is not None:
             losses.update(mask_results['loss_mask'])
         return losses
-
-    def _bbox_forward_train(self, x, sampling_results, gt_bboxes, gt_labels, img_metas):
-        """standard_roi_head.py:147-160."""
-        rois = bbox2roi([res.bboxes for res in sampling_results]).contiguous()
-        if torch.is_grad_enabled():
-            from . import train_path
-            bbox_feats = train_path.roi_extract_train(self.bbox_roi_extractor, x, rois)
-        else:
-            bbox_feats = self.bbox_roi_extractor(x[:self.bbox_roi_extractor.num_inputs], rois)
-        cls_score, bbox_pred = self.bbox_head(bbox_feats)
-        bbox_results = dict(cls_score=cls_score, bbox_pred=bbox_pred, bbox_feats=bbox_feats)
-        bbox_targets = self.bbox_head.get_targets(sampling_results, gt_bboxes, gt_labels, self.train_cfg)
-        loss_bbox = self.bbox_head.loss(cls_score, bbox_pred, rois, *bbox_targets)
-        bbox_results.update(loss_bbox=loss_bbox)
-        return bbox_results
 
     def _mask_forward_train(self, x, sampling_results, bbox_feats=None, gt_bboxes=None, gt_masks=None, gt_labels=None,
                             img_metas=None, noise=None):
@@ -477,37 +933,22 @@ class DynaMaskRoIHead(nn.Module):
                 budget / (self.train_cfg.flops[-1] - self.train_cfg.flops[0]), min=0)}
         return mask_results
 
-    def merge_stage_preds(self, stage_instance_preds):
-        """Boundary-aware coarse-to-fine merge, dynamask_roi_head.py:138-149
-        (in place on the finer logits, as the reference; the 14x14 exit is unused)."""
-        preds = stage_instance_preds[1:]
-        for idx in range(len(preds) - 1):
-            ops.boundary_merge_(preds[idx], preds[idx + 1])
-        return preds[-1]
-
-    def simple_test_mask_logits(self, x, det_bboxes, det_labels, scale_factor=1.0, rescale=False):
-        """simple_test_mask up to the merged 112x112 logits (pasting into the
-        image is the step after the path)."""
-        if det_bboxes.shape[0] == 0:
-            return det_bboxes.new_zeros((0, 1, 112, 112))
-        _bboxes = det_bboxes[:, :4] * scale_factor if rescale else det_bboxes
-        graphs = getattr(self, '_mask_graphs', None)
-        if graphs is not None and not torch.is_grad_enabled():
-            # bucketed HIP-graph replay (graphs.py); None: too many RoIs.  The boxes go straight into the graph's RoI buffer.
-            merged = graphs(x, None, det_labels, boxes=_bboxes)
-            if merged is not None:
-                return merged
-        mask_rois = bbox2roi([_bboxes]).contiguous()
-        return self._merged_logits(x, mask_rois, det_labels)
-
-    def _merged_logits(self, x, mask_rois, det_labels):
-        """The launch sequence of ``simple_test_mask_logits`` (what graphs.GraphedMaskLogits captures)."""
+    # ------------------------------------------------------------------ mask test hooks
+    def _mask_logits(self, x, mask_rois, det_labels):
+        """The merged 112 x 112 logits [n, 1, 112, 112] (dynamask_roi_head.py:138-149): the launch sequence of
+        ``simple_test_mask_logits`` (what graphs.GraphedMaskLogits captures)."""
         # the reference chunks by 100 RoIs "to avoid memory overflow" (:132); 288 GB of HBM do not need it
         if FUSED_MERGE_TAIL[0] and not torch.is_grad_enabled() and self._merged_tail_supported():
             with ops.splitk_scope():
                 return self._mask_forward_infer(x, mask_rois, det_labels, merge=True)
         res = self._mask_forward(x, mask_rois, det_labels)
-        return self.merge_stage_preds(res['stage_instance_preds'])
+        return merge_stage_preds(res['stage_instance_preds'])
+
+    def _mask_logits_size(self):
+        return 1, 112
+
+    def _segm_num_classes(self):
+        return self.mask_head.stage_num_classes[0]
 
     def _merged_tail_supported(self):
         h = self.mask_head
@@ -522,376 +963,6 @@ class DynaMaskRoIHead(nn.Module):
         self._mask_graphs = GraphedMaskLogits(self, buckets or BUCKETS,
                                               batch_buckets=batch_buckets or BATCH_BUCKETS) if on else None
         return self._mask_graphs
-
-    # ------------------------------------------------------------ bbox branch (inference)
-    def _bbox_forward(self, x, rois):
-        """standard_roi_head.py:135-146."""
-        bbox_feats = self.bbox_roi_extractor(x[:self.bbox_roi_extractor.num_inputs], rois)
-        cls_score, bbox_pred = self.bbox_head(bbox_feats)
-        return dict(cls_score=cls_score, bbox_pred=bbox_pred, bbox_feats=bbox_feats)
-
-    @torch.no_grad()
-    def simple_test_bboxes(self, x, img_metas, proposals, rcnn_test_cfg, rescale=False):
-        """test_mixins.py:52-71 (BBoxTestMixin.simple_test_bboxes), one image."""
-        rois = bbox2roi(proposals).contiguous()
-        res = self._bbox_forward(x, rois)
-        return self.bbox_head.get_bboxes(rois, res['cls_score'], res['bbox_pred'], img_metas[0]['img_shape'],
-                                         img_metas[0]['scale_factor'], rescale=rescale, cfg=rcnn_test_cfg)
-
-    @torch.no_grad()
-    def simple_test(self, x, proposal_list, img_metas, proposals=None, rescale=False, encode=False):
-        """standard_roi_head.py:217-236: boxes, then masks of the kept detections."""
-        from .bbox_heads import bbox2result
-        det_bboxes, det_labels = self.simple_test_bboxes(x, img_metas, proposal_list, self.test_cfg, rescale=rescale)
-        bbox_results = bbox2result(det_bboxes, det_labels, self.bbox_head.num_classes)
-        if not self.with_mask:
-            return bbox_results
-        segm_results = self.simple_test_mask(x, img_metas, det_bboxes, det_labels, rescale=rescale, encode=encode)
-        return bbox_results, segm_results
-
-    # ------------------------------------------------------------ batched inference: B images per call
-    # Each method gives, per image, what its one-image counterpart gives for that image alone; the B images share the
-    # launches: one bbox branch over all proposals, one segmented NMS, one mask chain over all detections, one paste.
-    _META_KEYS = ('img_shape', 'ori_shape', 'scale_factor')
-
-    @classmethod
-    def _check_batch(cls, img_metas, _name='img_metas', **lists):
-        """Argument checks of the batch_* methods (before any GPU work): a non-empty per-image list ``img_metas`` (named
-        ``_name`` in the message) and every other per-image list of the same length B."""
-        if not isinstance(img_metas, (list, tuple)) or len(img_metas) == 0:
-            raise ValueError(f'{_name}: a non-empty list with one entry per image')
-        B = len(img_metas)
-        for name, v in lists.items():
-            if v is not None and len(v) != B:
-                raise ValueError(f'{name}: {len(v)} entries for {B} images')
-        return B
-
-    @classmethod
-    def _check_metas(cls, img_metas, keys):
-        for i, m in enumerate(img_metas):
-            missing = [k for k in keys if k not in m]
-            if missing:
-                raise ValueError(f'img_metas[{i}] lacks {missing}')
-
-    @staticmethod
-    def _batch_scale_factor(scale_factor, device):
-        """simple_test_mask's ``torch.from_numpy(scale_factor).to(device)`` (same dtype, same values) through a pinned
-        buffer: no host wait per image."""
-        if isinstance(scale_factor, float):
-            return scale_factor
-        import numpy as np
-        return torch.from_numpy(np.ascontiguousarray(scale_factor)).pin_memory().to(device, non_blocking=True)
-
-    def _batch_mask_boxes(self, det_bboxes_list, img_metas, rescale):
-        """Per image: (boxes the mask chain reads, scale factor as simple_test_mask derives them)."""
-        boxes, sfs = [], []
-        for det, meta in zip(det_bboxes_list, img_metas):
-            sf = meta['scale_factor']
-            if rescale and det.shape[0] > 0:
-                sf = self._batch_scale_factor(sf, det.device)
-            boxes.append(det[:, :4] * sf if rescale and det.shape[0] > 0 else det)
-            sfs.append(sf)
-        return boxes, sfs
-
-    def batch_simple_test_mask_logits(self, x, det_bboxes_list, det_labels_list, scale_factors=None, rescale=False):
-        """``simple_test_mask_logits`` of B images as ONE mask chain: the [sum N, 5] RoI rows of all images (batch column
-        = image index into the B-image FPN tuple ``x``) -> the merged 112 x 112 logits [sum N, 1, 112, 112] and the row
-        offsets [B + 1] (image b: rows offsets[b]:offsets[b + 1]).  ``rescale``: image b's boxes are multiplied by
-        ``scale_factors[b]`` first.  B = 1 is ``simple_test_mask_logits`` itself.  With ``enable_inference_graphs`` the
-        call replays a graph bucketed on the total RoI count (graphs.BATCH_BUCKETS; larger totals run eagerly)."""
-        B = self._check_batch(det_bboxes_list, 'det_bboxes_list', det_labels_list=det_labels_list, scale_factors=scale_factors)
-        if rescale and scale_factors is None:
-            raise ValueError('rescale=True needs scale_factors')
-        counts = [int(d.shape[0]) for d in det_bboxes_list]
-        offsets = [0]
-        for c in counts:
-            offsets.append(offsets[-1] + c)
-        boxes = []
-        for b, det in enumerate(det_bboxes_list):
-            if rescale and det.shape[0] > 0:
-                det = det[:, :4] * self._batch_scale_factor(scale_factors[b], det.device)
-            boxes.append(det)
-        if offsets[-1] == 0:
-            return det_bboxes_list[0].new_zeros((0, 1, 112, 112)), offsets
-        if B == 1:
-            return self.simple_test_mask_logits(x, boxes[0], det_labels_list[0]), offsets
-        mask_rois = bbox2roi(boxes).contiguous()
-        labels = torch.cat(list(det_labels_list)).contiguous()
-        graphs = getattr(self, '_mask_graphs', None)
-        if graphs is not None and not torch.is_grad_enabled():
-            merged = graphs.batched(x, mask_rois, labels, B)
-            if merged is not None:
-                return merged, offsets
-        return self._merged_logits(x, mask_rois, labels), offsets
-
-    def _batch_mask_preds(self, x, boxes_list, labels_list, labels):
-        """The mask logits of all detections, one row per detection, and whether the paste applies the sigmoid."""
-        merged, _ = self.batch_simple_test_mask_logits(x, boxes_list, labels_list)
-        if merged.shape[1] > 1:
-            merged = merged[range(len(merged)), labels][:, None]
-        return merged.contiguous(), True
-
-    def _segm_num_classes(self):
-        return self.mask_head.stage_num_classes[0]
-
-    @torch.no_grad()
-    def batch_simple_test_mask(self, x, img_metas, det_bboxes_list, det_labels_list, rescale=False, encode=False,
-                               _labels_host=None):
-        """``simple_test_mask`` of B images: per image the per-class lists of (h, w) bool masks (``encode``: COCO RLE
-        dicts) of its detections, on its own canvas (``ori_shape``, ``scale_factor``).  One mask chain, one paste launch
-        (dm_paste_masks_multi / dm_paste_rle_multi) and one device -> host copy for all images."""
-        from .mask_heads import _paste_geometry
-        import numpy as np
-        B = self._check_batch(img_metas, det_bboxes_list=det_bboxes_list, det_labels_list=det_labels_list)
-        self._check_metas(img_metas, ('ori_shape', 'scale_factor'))
-        num_classes = self._segm_num_classes()
-        results = [[[] for _ in range(num_classes)] for _ in range(B)]
-        counts = [int(d.shape[0]) for d in det_bboxes_list]
-        if sum(counts) == 0:
-            return results
-        threshold = self.test_cfg.mask_thr_binary
-        if threshold < 0:
-            raise NotImplementedError('visualisation mode (mask_thr_binary < 0) is not on the path')
-        boxes, sfs = self._batch_mask_boxes(det_bboxes_list, img_metas, rescale)
-        labels = torch.cat(list(det_labels_list))
-        preds, apply_sigmoid = self._batch_mask_preds(x, boxes, det_labels_list, labels)
-        canvas_boxes, sizes = [], []
-        for b in range(B):
-            if counts[b] == 0:
-                sizes.append((1, 1))
-                continue
-            cb, h, w = _paste_geometry(boxes[b], img_metas[b]['ori_shape'], sfs[b], rescale)
-            canvas_boxes.append(cb)
-            sizes.append((h, w))
-        canvas_boxes = torch.cat(canvas_boxes).contiguous()
-        if encode:
-            segs = ops.paste_rle_multi(preds, canvas_boxes, counts, sizes, threshold, apply_sigmoid=apply_sigmoid)
-            labels_h = _labels_host if _labels_host is not None else labels.cpu().tolist()
-        else:
-            buf, offs, det_sizes = ops.paste_masks_multi(preds, canvas_boxes, counts, sizes, threshold,
-                                                         apply_sigmoid=apply_sigmoid)
-            host = torch.empty(buf.shape, dtype=torch.uint8, pin_memory=True)
-            host.copy_(buf, non_blocking=True)
-            lab_h = None
-            if _labels_host is None:
-                lab_h = torch.empty(labels.shape, dtype=labels.dtype, pin_memory=True)
-                lab_h.copy_(labels, non_blocking=True)
-            torch.cuda.current_stream().synchronize()
-            labels_h = _labels_host if _labels_host is not None else lab_h.tolist()
-            flat = host.numpy().view(np.bool_)
-            segs = [flat[o:o + h * w].reshape(h, w) for o, (h, w) in zip(offs, det_sizes)]
-        start = 0
-        for b in range(B):
-            for j in range(start, start + counts[b]):
-                results[b][labels_h[j]].append(segs[j])
-            start += counts[b]
-        return results
-
-    @torch.no_grad()
-    def batch_simple_test_bboxes(self, x, img_metas, proposals, rcnn_test_cfg, rescale=False):
-        """``simple_test_bboxes`` of B images -> list of B (dets [k, 5], labels [k]): one bbox branch over the
-        proposals of all images, per-image decode (its own ``img_shape`` clip and ``scale_factor``), one segmented NMS
-        (bbox_heads.multiclass_nms_batch)."""
-        from .bbox_heads import multiclass_nms_batch
-        B = self._check_batch(img_metas, proposals=proposals)
-        self._check_metas(img_metas, ('img_shape', 'scale_factor'))
-        rows = [int(p.shape[0]) for p in proposals]
-        rois = bbox2roi(proposals).contiguous()
-        if rois.shape[0] == 0:
-            ref = proposals[0]
-            return [(ref.new_zeros((0, 5)), ref.new_zeros((0,), dtype=torch.long)) for _ in range(B)]
-        res = self._bbox_forward(x, rois)
-        cls_score, bbox_pred = res['cls_score'], res['bbox_pred']
-        bl, sl, r0 = [], [], 0
-        for b in range(B):
-            r1 = r0 + rows[b]
-            if r1 == r0:
-                bl.append(rois.new_zeros((0, 4)))
-                sl.append(rois.new_zeros((0, self.bbox_head.num_classes + 1)))
-            else:
-                bboxes, scores = self.bbox_head.get_bboxes(
-                    rois[r0:r1], None if cls_score is None else cls_score[r0:r1],
-                    None if bbox_pred is None else bbox_pred[r0:r1], img_metas[b]['img_shape'],
-                    img_metas[b]['scale_factor'], rescale=rescale, cfg=None)
-                bl.append(bboxes)
-                sl.append(scores)
-            r0 = r1
-        cfg = rcnn_test_cfg
-        return multiclass_nms_batch(bl, sl, cfg.score_thr, cfg.nms, cfg.max_per_img)
-
-    @torch.no_grad()
-    def batch_simple_test(self, x, proposal_list, img_metas, rescale=False, encode=False):
-        """``simple_test`` of B images in one call (the contract of later mmdet releases): ``x`` the FPN tuple with
-        batch dimension B, ``proposal_list`` / ``img_metas`` one entry per image -> list of B ``(bbox_results,
-        segm_results)``, each what ``simple_test`` returns for that image alone (just ``bbox_results`` without a mask
-        branch).  Host waits do not grow with B: the detections of all images cross to the host in one copy."""
-        B = self._check_batch(img_metas, proposal_list=proposal_list)
-        self._check_metas(img_metas, self._META_KEYS)
-        for i, f in enumerate(x):
-            if f.shape[0] != B:
-                raise ValueError(f'x[{i}] has batch dimension {f.shape[0]} for {B} images')
-        dets = self.batch_simple_test_bboxes(x, img_metas, proposal_list, self.test_cfg, rescale=rescale)
-        counts = [int(d.shape[0]) for d, _ in dets]
-        num_classes = self.bbox_head.num_classes
-        if sum(counts) == 0:
-            import numpy as np
-            bbox_results = [[np.zeros((0, 5), dtype=np.float32) for _ in range(num_classes)] for _ in range(B)]
-            labels_h = []
-        else:
-            d_all = torch.cat([d for d, _ in dets])
-            l_all = torch.cat([l for _, l in dets])
-            d_h = torch.empty(d_all.shape, dtype=d_all.dtype, pin_memory=True)
-            l_h = torch.empty(l_all.shape, dtype=l_all.dtype, pin_memory=True)
-            d_h.copy_(d_all, non_blocking=True)
-            l_h.copy_(l_all, non_blocking=True)
-            torch.cuda.current_stream().synchronize()
-            d_np, l_np = d_h.numpy(), l_h.numpy()
-            labels_h = l_np.tolist()
-            bbox_results, start = [], 0
-            for c in counts:
-                bbox_results.append(_bbox2result_host(d_np[start:start + c], l_np[start:start + c], num_classes))
-                start += c
-        if not self.with_mask:
-            return bbox_results
-        segm_results = self.batch_simple_test_mask(x, img_metas, [d for d, _ in dets], [l for _, l in dets],
-                                                   rescale=rescale, encode=encode, _labels_host=labels_h)
-        return list(zip(bbox_results, segm_results))
-
-    # ------------------------------------------------------------ test-time augmentation: V views of one image
-    # standard_roi_head.py:264-290 + test_mixins.py:73-107,178-208 (MultiScaleFlipAug): ``x`` holds one FPN tuple per view
-    # (batch size 1 each), ``img_metas`` one single-element list per view.  The views share three launches: the mapping of
-    # the boxes into every view (dm_bbox_mapping_multi), the box / score merge (dm_merge_aug_bboxes) and the mask merge
-    # (dm_merge_aug_masks); the bbox branch and the mask chain run once per view through the one-view path.  No host wait
-    # inside the per-view loops.  DynaMask head (this project's definition, the reference cannot run it): a view's mask
-    # prediction is what ``simple_test_mask_logits`` returns for the mapped boxes (DESIGN.md section 4.10).
-    _AUG_META_KEYS = ('img_shape', 'scale_factor', 'flip', 'flip_direction', 'ori_shape')
-
-    @classmethod
-    def _check_aug(cls, x, img_metas):
-        """Argument checks of the aug_test* methods (before any GPU work) -> the V view metas."""
-        if not isinstance(img_metas, (list, tuple)) or len(img_metas) == 0:
-            raise ValueError('img_metas: a non-empty list with one single-element list per view')
-        V = len(img_metas)
-        if len(x) != V:
-            raise ValueError(f'x has {len(x)} views, img_metas {V}')
-        views = []
-        for v, m in enumerate(img_metas):
-            if not isinstance(m, (list, tuple)) or len(m) != 1:
-                raise ValueError(f'img_metas[{v}]: one meta per view (test-time augmentation runs one image)')
-            missing = [k for k in cls._AUG_META_KEYS if k not in m[0]]
-            if missing:
-                raise ValueError(f'img_metas[{v}][0] lacks {missing}')
-            if x[v][0].shape[0] != 1:
-                raise ValueError(f'x[{v}] has batch dimension {x[v][0].shape[0]}: one image per view')
-            views.append(m[0])
-        ops.aug_view_rows(views)                    # flip directions and scale factors
-        return views
-
-    @torch.no_grad()
-    def aug_test_bboxes(self, x, img_metas, proposal_list, rcnn_test_cfg):
-        """test_mixins.py:73-107: the proposals ``proposal_list[0]`` (original image) mapped into every view, the bbox
-        branch and ``get_bboxes(rescale=False)`` per view, the views' boxes mapped back and averaged with their scores
-        (merge_aug_bboxes), then ``multiclass_nms`` -> (dets [k, 5], labels [k]) in original-image coordinates."""
-        from .bbox_heads import multiclass_nms
-        views = self._check_aug(x, img_metas)
-        props = proposal_list[0]
-        if props.shape[0] == 0:
-            return props.new_zeros((0, 5)), props.new_zeros((0,), dtype=torch.long)
-        tab = ops.aug_view_table(views, props.device)
-        rois = ops.bbox_mapping_multi(props, tab)
-        aug_bboxes, aug_scores = [], []
-        for v, meta in enumerate(views):
-            res = self._bbox_forward(x[v], rois[v])
-            bboxes, scores = self.bbox_head.get_bboxes(rois[v], res['cls_score'], res['bbox_pred'], meta['img_shape'],
-                                                       meta['scale_factor'], rescale=False, cfg=None)
-            aug_bboxes.append(bboxes.contiguous())
-            aug_scores.append(scores.contiguous())
-        merged_bboxes, merged_scores = ops.merge_aug_bboxes(aug_bboxes, aug_scores, tab)
-        cfg = rcnn_test_cfg
-        return multiclass_nms(merged_bboxes, merged_scores, cfg.score_thr, cfg.nms, cfg.max_per_img)
-
-    def _aug_view_mask_logits(self, x, rois, det_labels):
-        """One view's mask prediction for its RoI rows: the merged 112 x 112 logits [n, 1, 112, 112] of
-        ``simple_test_mask_logits``, valid until the merge (a graph's static output is copied: the next view's replay
-        would overwrite it)."""
-        merged = self.simple_test_mask_logits(x, rois[:, 1:], det_labels)
-        if getattr(self, '_mask_graphs', None) is not None:
-            merged = merged.clone()
-        return merged.contiguous()
-
-    def _aug_empty_probs(self, ref):
-        return ref.new_zeros((0, 1, 112, 112))
-
-    @torch.no_grad()
-    def aug_test_mask_probs(self, x, img_metas, det_bboxes, det_labels):
-        """The merged mask probabilities of test-time augmentation [n, 1, S, S] on the device: ``det_bboxes`` (original
-        image) mapped into every view, the view's mask prediction, then sigmoid, un-flip and mean over the views
-        (merge_aug_masks) of the detection's class channel."""
-        views = self._check_aug(x, img_metas)
-        if det_bboxes.shape[0] == 0:
-            return self._aug_empty_probs(det_bboxes)
-        tab = ops.aug_view_table(views, det_bboxes.device)
-        rois = ops.bbox_mapping_multi(det_bboxes, tab)
-        labels = det_labels.contiguous()
-        logits = [self._aug_view_mask_logits(x[v], rois[v], labels) for v in range(len(views))]
-        return ops.merge_aug_masks(logits, labels, tab)
-
-    @torch.no_grad()
-    def aug_test_mask(self, x, img_metas, det_bboxes, det_labels, encode=False, _labels_host=None):
-        """test_mixins.py:178-208 -> per-class lists of (h, w) bool masks at ``ori_shape`` of the first view
-        (``encode``: COCO RLE dicts): the merged probabilities (``aug_test_mask_probs``) pasted without a sigmoid,
-        ``scale_factor=1.0, rescale=False``, thresholded at ``mask_thr_binary``."""
-        from .mask_heads import _bitmaps_to_host, _paste_geometry
-        views = self._check_aug(x, img_metas)
-        segm_result = [[] for _ in range(self._segm_num_classes())]
-        if det_bboxes.shape[0] == 0:
-            return segm_result
-        threshold = self.test_cfg.mask_thr_binary
-        if threshold < 0:
-            raise NotImplementedError('visualisation mode (mask_thr_binary < 0) is not on the path')
-        probs = self.aug_test_mask_probs(x, img_metas, det_bboxes, det_labels)
-        boxes, img_h, img_w = _paste_geometry(det_bboxes, views[0]['ori_shape'], 1.0, False)
-        if encode:
-            segs = ops.paste_rle(probs, boxes, img_h, img_w, threshold, apply_sigmoid=False)
-        else:
-            im = _bitmaps_to_host(ops.paste_masks(probs, boxes, img_h, img_w, threshold, apply_sigmoid=False))
-            segs = [im[i] for i in range(len(im))]
-        labels_h = _labels_host if _labels_host is not None else det_labels.tolist()
-        for c, segm in zip(labels_h, segs):
-            segm_result[c].append(segm)
-        return segm_result
-
-    @torch.no_grad()
-    def aug_test(self, x, proposal_list, img_metas, rescale=False, encode=False):
-        """standard_roi_head.py:264-290: boxes merged over the views, then masks merged over the views ->
-        ``(bbox_results, segm_results)`` (just ``bbox_results`` without a mask branch).  ``rescale=False`` scales only
-        the boxes of ``bbox_results`` by the first view's ``scale_factor``, as the reference does; the masks stay at
-        the original image's size either way."""
-        import numpy as np
-        views = self._check_aug(x, img_metas)
-        det_bboxes, det_labels = self.aug_test_bboxes(x, img_metas, proposal_list, self.test_cfg)
-        num_classes = self.bbox_head.num_classes
-        if det_bboxes.shape[0] == 0:
-            bbox_results = [np.zeros((0, 5), dtype=np.float32) for _ in range(num_classes)]
-            labels_h = []
-        else:
-            _det_bboxes = det_bboxes
-            if not rescale:
-                _det_bboxes = det_bboxes.clone()
-                sf = views[0]['scale_factor']
-                _det_bboxes[:, :4] *= sf if isinstance(sf, float) else self._batch_scale_factor(
-                    np.asarray(sf, dtype=np.float32), det_bboxes.device)
-            d_h = torch.empty(_det_bboxes.shape, dtype=_det_bboxes.dtype, pin_memory=True)
-            l_h = torch.empty(det_labels.shape, dtype=det_labels.dtype, pin_memory=True)
-            d_h.copy_(_det_bboxes, non_blocking=True)
-            l_h.copy_(det_labels, non_blocking=True)
-            torch.cuda.current_stream().synchronize()
-            bbox_results = _bbox2result_host(d_h.numpy(), l_h.numpy(), num_classes)
-            labels_h = l_h.tolist()
-        if not self.with_mask:
-            return bbox_results
-        segm_results = self.aug_test_mask(x, img_metas, det_bboxes, det_labels, encode=encode, _labels_host=labels_h)
-        return bbox_results, segm_results
 
     # ------------------------------------------------------------ dynamic inference
     @torch.no_grad()
@@ -943,41 +1014,22 @@ class DynaMaskRoIHead(nn.Module):
     def dynamic_test_mask(self, x, img_metas, det_bboxes, det_labels, rescale=False, noise=None, merge=True, exits=None):
         """``simple_test_mask`` with per-RoI early exit: same inputs, same per-class lists of
         (h, w) bool masks; each detection is pasted from the logits of its own exit."""
-        import numpy as np
-        ori_shape = img_metas[0]['ori_shape']
-        scale_factor = img_metas[0]['scale_factor']
-        num_classes = self.mask_head.stage_num_classes[0]
-        segm_result = [[] for _ in range(num_classes)]
+        from .mask_heads import _paste_geometry, _to_host
+        segm_result = [[] for _ in range(self._segm_num_classes())]
         n = det_bboxes.shape[0]
         if n == 0:
             return segm_result
-        if rescale and not isinstance(scale_factor, float):
-            scale_factor = torch.from_numpy(scale_factor).to(det_bboxes.device)
-        _bboxes = det_bboxes[:, :4] * scale_factor if rescale else det_bboxes[:, :4]
+        _bboxes, scale_factor = self._mask_boxes(det_bboxes[:, :4], img_metas[0]['scale_factor'], rescale)
         res = self.dynamic_mask_logits(x, _bboxes, det_labels, noise=noise, merge=merge, exits=exits)
         order, n_ge, preds = res['order'], res['n_ge'] + [0], res['preds']
-        # paste geometry as get_seg_masks (dynamask_head.py:279-342)
-        if rescale:
-            img_h, img_w = ori_shape[:2]
-            sf = scale_factor
-        else:
-            img_h = int(np.round(ori_shape[0] * scale_factor).astype(np.int32))
-            img_w = int(np.round(ori_shape[1] * scale_factor).astype(np.int32))
-            sf = 1.0
-        if not isinstance(sf, (float, torch.Tensor)):
-            sf = _bboxes.new_tensor(sf)
-        boxes_s = (_bboxes[order] / sf).contiguous()
+        boxes_s, img_h, img_w = _paste_geometry(_bboxes[order], img_metas[0]['ori_shape'], scale_factor, rescale)
         canvas = torch.empty((n, img_h, img_w), device=_bboxes.device, dtype=torch.uint8)
         thr = self.test_cfg.mask_thr_binary
         for e in range(4):
             lo, hi = n_ge[e + 1], n_ge[e]
             if hi > lo:
                 ops.paste_masks(preds[e][lo:hi], boxes_s[lo:hi], img_h, img_w, thr, apply_sigmoid=True, out=canvas[lo:hi])
-        host = torch.empty(canvas.shape, dtype=torch.bool, pin_memory=True)
-        host.copy_(canvas.view(torch.bool), non_blocking=True)
-        order_h = order.cpu()                     # synchronises the stream: host is complete
-        torch.cuda.current_stream().synchronize()
-        im = host.numpy()
+        im, order_h = _to_host(canvas.view(torch.bool), order)
         by_det = [None] * n
         for p, j in enumerate(order_h.tolist()):
             by_det[j] = im[p]
@@ -985,150 +1037,20 @@ class DynaMaskRoIHead(nn.Module):
             segm_result[c].append(segm)
         return segm_result
 
-    def simple_test_mask(self, x, img_metas, det_bboxes, det_labels, rescale=False, encode=False):
-        """dynamask_roi_head.py:117-158 -> per-class lists of (h, w) bool masks.
-        ``encode=True`` (extension): per-class lists of COCO RLE dicts instead, i.e. the result
-        after the caller's ``encode_mask_results`` (apis/test.py:52-57), produced on the device."""
-        ori_shape = img_metas[0]['ori_shape']
-        scale_factor = img_metas[0]['scale_factor']
-        num_classes = self.mask_head.stage_num_classes[0]
-        segm_result = [[] for _ in range(num_classes)]
-        if det_bboxes.shape[0] == 0:
-            return segm_result
-        if rescale and not isinstance(scale_factor, float):
-            scale_factor = torch.from_numpy(scale_factor).to(det_bboxes.device)
-        _bboxes = det_bboxes[:, :4] * scale_factor if rescale else det_bboxes
-        merged = self.simple_test_mask_logits(x, _bboxes, det_labels)
-        to_segs = self.mask_head.get_seg_rles if encode else self.mask_head.get_seg_masks
-        segs = to_segs(merged, _bboxes, det_labels, self.test_cfg, ori_shape, scale_factor, rescale)
-        for c, segm in zip(det_labels.tolist(), segs):
-            segm_result[c].append(segm)
-        return segm_result
-
 
 @HEADS.register_module()
-class StandardRoIHead(DynaMaskRoIHead):
-    """``StandardRoIHead`` -- mmdet/models/roi_heads/standard_roi_head.py:10-236 + ``MaskTestMixin.simple_test_mask``
-    (test_mixins.py:151-176): the RoI head of configs/mask_rcnn and configs/carafe (BASELINE configs[4]), whose mask head
-    is ``FCNMaskHead``.  The bbox branch, the assigner / sampler and ``simple_test`` are the parent's (the reference's
-    ``DynaMaskRoIHead`` is itself a ``StandardRoIHead``); the mask branch is the stock one: ``_mask_forward(x, rois)`` ->
-    ``{'mask_pred': [N, classes, 28, 28], 'mask_feats'}``, ``simple_test_mask`` -> ``FCNMaskHead.get_seg_masks``.
-    ``BaseRoIHead.__init__`` of the fork builds ``mask_predictor`` / ``semantic_roi_extractor`` for EVERY RoI head (Quirk
-    Q4), so the ``state_dict`` carries the ``mask_predictor.*`` keys here too, as the reference's does.
-    Training: ``forward_train`` follows standard_roi_head.py:70-134; its mask loss ends in ``FCNMaskHead.loss``, which
-    the fork broke (Quirk Q5) -- it raises here as it does there, the bbox losses and the mask targets are computed."""
-
-    def _mask_forward(self, x, rois=None, pos_inds=None, bbox_feats=None, **kw):
-        """standard_roi_head.py:199-215."""
-        assert (rois is not None) ^ (pos_inds is not None and bbox_feats is not None)
-        if rois is not None:
-            ext = self.mask_roi_extractor
-            mask_feats = ext(x[:ext.num_inputs], rois.contiguous())
-        else:
-            mask_feats = bbox_feats[pos_inds].contiguous()
-        return dict(mask_pred=self.mask_head(mask_feats), mask_feats=mask_feats)
-
-    def _mask_forward_train(self, x, sampling_results, bbox_feats, gt_masks, img_metas, **kw):
-        """standard_roi_head.py:162-197 (the mask branch with its own RoI extractor)."""
-        pos_rois = bbox2roi([res.pos_bboxes for res in sampling_results]).contiguous()
-        if pos_rois.shape[0] == 0:
-            return dict(loss_mask=None)
-        mask_results = self._mask_forward(x, pos_rois)
-        mask_targets = self.mask_head.get_targets(sampling_results, gt_masks, self.train_cfg)
-        pos_labels = torch.cat([res.pos_gt_labels for res in sampling_results])
-        loss_mask = self.mask_head.loss(mask_results['mask_pred'], mask_targets, pos_labels)
-        mask_results.update(loss_mask=loss_mask, mask_targets=mask_targets)
-        return mask_results
-
-    def forward_train(self, x, img_metas, proposal_list, gt_bboxes, gt_labels, gt_bboxes_ignore=None, gt_masks=None):
-        """standard_roi_head.py:70-134."""
-        num_imgs = len(img_metas)
-        if gt_bboxes_ignore is None:
-            gt_bboxes_ignore = [None for _ in range(num_imgs)]
-        deferred = hasattr(self.bbox_sampler, 'sample_deferred')
-        do_sample = self.bbox_sampler.sample_deferred if deferred else self.bbox_sampler.sample
-        sampling_results = []
-        for i in range(num_imgs):
-            assign_result = self.bbox_assigner.assign(proposal_list[i], gt_bboxes[i], gt_bboxes_ignore[i], gt_labels[i])
-            sampling_results.append(do_sample(assign_result, proposal_list[i], gt_bboxes[i], gt_labels[i],
-                                              feats=[lvl_feat[i][None] for lvl_feat in x]))
-        if deferred:
-            sampling_results = self.bbox_sampler.finish_samples(sampling_results)
-        losses = dict()
-        bbox_results = None
-        if self.with_bbox:
-            bbox_results = self._bbox_forward_train(x, sampling_results, gt_bboxes, gt_labels, img_metas)
-            losses.update(bbox_results['loss_bbox'])
-        if self.with_mask:
-            mask_results = self._mask_forward_train(x, sampling_results, None if bbox_results is None else bbox_results['bbox_feats'],
-                                                    gt_masks, img_metas)
-            if mask_results['loss_mask'] is not None:
-                losses.update(mask_results['loss_mask'])
-        return losses
-
-    def batch_simple_test_mask_logits(self, x, det_bboxes_list, det_labels_list, scale_factors=None, rescale=False):
-        """The FCNMaskHead logits [sum N, classes, S, S] of B images' detections from ONE ``_mask_forward``, and the row
-        offsets [B + 1] (``rescale``: boxes times ``scale_factors[b]`` first)."""
-        self._check_batch(det_bboxes_list, 'det_bboxes_list', det_labels_list=det_labels_list, scale_factors=scale_factors)
-        if rescale and scale_factors is None:
-            raise ValueError('rescale=True needs scale_factors')
-        offsets = [0]
-        boxes = []
-        for b, det in enumerate(det_bboxes_list):
-            offsets.append(offsets[-1] + int(det.shape[0]))
-            if rescale and det.shape[0] > 0:
-                det = det[:, :4] * self._batch_scale_factor(scale_factors[b], det.device)
-            boxes.append(det)
-        mask_rois = bbox2roi(boxes).contiguous()
-        if mask_rois.shape[0] == 0:
-            h = self.mask_head
-            return mask_rois.new_zeros((0, h.num_classes, 1, 1)), offsets
-        with torch.no_grad():
-            return self._mask_forward(x, mask_rois)['mask_pred'], offsets
-
-    def _batch_mask_preds(self, x, boxes_list, labels_list, labels):
-        mask_pred, _ = self.batch_simple_test_mask_logits(x, boxes_list, labels_list)
-        return self.mask_head._selected(mask_pred, torch.cat([b[:, :4] for b in boxes_list]), labels)
-
-    def _segm_num_classes(self):
-        return self.mask_head.num_classes
-
-    def _aug_view_mask_logits(self, x, rois, det_labels):
-        """One view's ``mask_pred`` [n, classes, S, S] of ``_mask_forward`` for its RoI rows (test_mixins.py:194-195);
-        the merge selects the detection's class channel."""
-        return self._mask_forward(x, rois)['mask_pred'].contiguous()
-
-    def _aug_empty_probs(self, ref):
-        return ref.new_zeros((0, 1, 1, 1))
-
-    def simple_test_mask(self, x, img_metas, det_bboxes, det_labels, rescale=False, encode=False):
-        """test_mixins.py:151-176 -> ``cls_segms`` of ``FCNMaskHead.get_seg_masks`` (``encode``: COCO RLE dicts instead of
-        bitmaps, ``get_seg_rles``: the result after the caller's ``encode_mask_results``)."""
-        ori_shape = img_metas[0]['ori_shape']
-        scale_factor = img_metas[0]['scale_factor']
-        if det_bboxes.shape[0] == 0:
-            return [[] for _ in range(self.mask_head.num_classes)]
-        if rescale and not isinstance(scale_factor, float):
-            scale_factor = torch.from_numpy(scale_factor).to(det_bboxes.device)
-        _bboxes = det_bboxes[:, :4] * scale_factor if rescale else det_bboxes
-        mask_rois = bbox2roi([_bboxes]).contiguous()
-        with torch.no_grad():
-            mask_results = self._mask_forward(x, mask_rois)
-        to_segs = self.mask_head.get_seg_rles if encode else self.mask_head.get_seg_masks
-        return to_segs(mask_results['mask_pred'], _bboxes, det_labels, self.test_cfg, ori_shape, scale_factor, rescale)
-
-
-@HEADS.register_module()
-class RefineRoIHead(DynaMaskRoIHead):
+class RefineRoIHead(StandardRoIHead):
     """``RefineRoIHead`` -- mmdet/models/roi_heads/refine_roi_head.py:10-113, inference: the RoI head of
-    configs/refinemask, whose mask head is ``RefineMaskHead``.  Like ``StandardRoIHead`` it keeps the parent's bbox
-    branch, ``simple_test``, ``batch_simple_test`` and ``aug_test``, and overrides the mask hooks: ``_mask_forward``
-    (refine_roi_head.py:75-80) and the merged 112 x 112 logits (``_merged_logits``: the boundary-aware merge from stage 1,
-    :102-113, the same merge as DynaMask's, ops.boundary_merge_).  The four semantic 3x3 convolutions run once per call
-    on the whole stride-4 map of every image of the batch (the reference runs them once per chunk of 100 RoIs).  The
-    fork's ``BaseRoIHead`` builds ``mask_predictor`` / ``semantic_roi_extractor`` for EVERY RoI head (Quirk Q4): the
-    parent's constructor does the same, so the ``state_dict`` keys are the reference's.  Training and HIP-graph
-    capture are the follow-up (NotImplementedError)."""
+    configs/refinemask, whose mask head is ``RefineMaskHead``.  The bbox branch, ``simple_test``, ``batch_simple_test``,
+    ``aug_test`` and the mask-test template are the base's; the head supplies ``_mask_forward`` (refine_roi_head.py:75-80)
+    and, as ``_mask_logits``, the merged logits of the last stage (the boundary-aware merge from stage 1, :102-113, the
+    same merge as DynaMask's: ``merge_stage_preds``).  The four semantic 3x3 convolutions run once per call on the whole
+    stride-4 map of every image of the batch (the reference runs them once per chunk of 100 RoIs).  The fork's
+    ``BaseRoIHead`` builds ``mask_predictor`` / ``semantic_roi_extractor`` for EVERY RoI head (Quirk Q4): the base's
+    constructor does the same, so the ``state_dict`` keys are the reference's.  Training and HIP-graph capture are the
+    follow-up (NotImplementedError)."""
+
+    merge_stage_preds = staticmethod(merge_stage_preds)
 
     def _mask_forward(self, x, rois, roi_labels, **kw):
         """refine_roi_head.py:75-80 -> dict(stage_instance_preds, semantic_pred)."""
@@ -1139,47 +1061,31 @@ class RefineRoIHead(DynaMaskRoIHead):
             ips, sem_pred = self.mask_head(ins_feats, x[0].contiguous(), rois, roi_labels)
         return dict(stage_instance_preds=ips, semantic_pred=sem_pred)
 
-    def _merged_logits(self, x, mask_rois, det_labels):
+    def _mask_logits(self, x, mask_rois, det_labels):
         """The merged logits of the last stage [n, 1, S, S]: stage k's (k >= 1) merged into stage k + 1's where the
         coarser one is not on a boundary (refine_roi_head.py:102-113), in place."""
         res = self._mask_forward(x, mask_rois, det_labels)
-        return self.merge_stage_preds(res['stage_instance_preds'])
+        return merge_stage_preds(res['stage_instance_preds'])
 
-    def simple_test_mask_logits(self, x, det_bboxes, det_labels, scale_factor=1.0, rescale=False):
-        if det_bboxes.shape[0] == 0:
-            s = self.mask_head.stage_sup_size[-1]
-            return det_bboxes.new_zeros((0, 1, s, s))
-        _bboxes = det_bboxes[:, :4] * scale_factor if rescale else det_bboxes
-        return self._merged_logits(x, bbox2roi([_bboxes]).contiguous(), det_labels)
+    def _mask_logits_size(self):
+        return 1, self.mask_head.stage_sup_size[-1]
 
-    def enable_inference_graphs(self, on=True, buckets=None, batch_buckets=None):
-        if on:
-            raise NotImplementedError('RefineRoIHead: HIP-graph capture of the RefineMask call is a follow-up')
-        self._mask_graphs = None
-        return None
+    def _segm_num_classes(self):
+        return self.mask_head.stage_num_classes[0]
 
     def forward_train(self, x, img_metas, proposal_list, gt_bboxes, gt_labels, gt_bboxes_ignore=None, gt_masks=None):
         raise NotImplementedError('RefineRoIHead.forward_train: RefineMask training (targets, RefineCrossEntropyLoss, the '
                                   'dilated-convolution gradients) is the follow-up to its inference')
-
-    def _mask_forward_train(self, *a, **k):
-        raise NotImplementedError('RefineRoIHead._mask_forward_train: RefineMask training is the follow-up to its inference')
-
-    def dynamic_mask_logits(self, *a, **k):
-        raise NotImplementedError('RefineRoIHead: per-RoI early exit is DynaMask\'s, RefineMask has none')
-
-    def dynamic_test_mask(self, *a, **k):
-        raise NotImplementedError('RefineRoIHead: per-RoI early exit is DynaMask\'s, RefineMask has none')
 
 
 @HEADS.register_module()
 class PointRendRoIHead(StandardRoIHead):
     """``PointRendRoIHead`` -- mmdet/models/roi_heads/point_rend_roi_head.py, inference: the RoI head of configs/point_rend.
     The bbox branch, ``_mask_forward`` (the ``CoarseMaskHead`` logits [n, classes, 7, 7] of the GenericRoIExtractor's
-    14 x 14 features) and the batch / TTA entry points are the parent's; the mask prediction is refined by the
-    subdivision loop of ``_mask_point_forward_test`` (:96-128): ``subdivision_steps`` bilinear x2 upsamples, and at every
-    step that is not skipped the ``subdivision_num_points`` most uncertain cells re-predicted by ``point_head``
-    (ops.point_select -> ops.point_gather -> MaskPointHead.refine_).
+    14 x 14 features) and the mask-test template are the base's; the head's ``_mask_logits`` refines the coarse
+    prediction by the subdivision loop of ``_mask_point_forward_test`` (:96-128): ``subdivision_steps`` bilinear x2
+    upsamples, and at every step that is not skipped the ``subdivision_num_points`` most uncertain cells re-predicted by
+    ``point_head`` (ops.point_select -> ops.point_gather -> MaskPointHead.refine_).
 
     Only the label channel of the refined map is carried: every operation of the loop is per class channel except the
     point selection, which reads the label channel, and only the label channel is pasted or merged.  The result is that
@@ -1202,6 +1108,9 @@ class PointRendRoIHead(StandardRoIHead):
     def _refine_size(self):
         s = self.mask_head.output_size[0]
         return s * 2 ** self.test_cfg.subdivision_steps
+
+    def _mask_logits_size(self):
+        return 1, self._refine_size()
 
     def _mask_point_forward_test(self, x, rois, label_pred, mask_pred):
         """point_rend_roi_head.py:96-128 on the label channel -> refined logits [n, 1, S', S']."""
@@ -1227,80 +1136,12 @@ class PointRendRoIHead(StandardRoIHead):
             self.point_head.refine_(pts, labels, idx, refined)
         return refined
 
-    def _refined_logits(self, x, mask_rois, det_labels):
+    def _mask_logits(self, x, mask_rois, det_labels):
+        """The refined label-channel logits [n, 1, S', S'] of the RoIs (S' = 224 in configs/point_rend)."""
         with torch.no_grad():
             coarse = self._mask_forward(x, mask_rois)['mask_pred']
             return self._mask_point_forward_test(x, mask_rois, det_labels, coarse)
 
-    def simple_test_mask_logits(self, x, det_bboxes, det_labels, scale_factor=1.0, rescale=False):
-        """The refined label-channel logits [n, 1, S', S'] of the detections (S' = 224 in configs/point_rend)."""
-        if det_bboxes.shape[0] == 0:
-            s = self._refine_size()
-            return det_bboxes.new_zeros((0, 1, s, s))
-        _bboxes = det_bboxes[:, :4] * scale_factor if rescale else det_bboxes
-        return self._refined_logits(x, bbox2roi([_bboxes]).contiguous(), det_labels)
-
-    def batch_simple_test_mask_logits(self, x, det_bboxes_list, det_labels_list, scale_factors=None, rescale=False):
-        """The refined label-channel logits [sum N, 1, S', S'] of B images' detections from ONE subdivision loop (the
-        RoI batch column routes the fine-grained sampling), and the row offsets [B + 1]."""
-        self._check_batch(det_bboxes_list, 'det_bboxes_list', det_labels_list=det_labels_list, scale_factors=scale_factors)
-        if rescale and scale_factors is None:
-            raise ValueError('rescale=True needs scale_factors')
-        offsets = [0]
-        boxes = []
-        for b, det in enumerate(det_bboxes_list):
-            offsets.append(offsets[-1] + int(det.shape[0]))
-            if rescale and det.shape[0] > 0:
-                det = det[:, :4] * self._batch_scale_factor(scale_factors[b], det.device)
-            boxes.append(det)
-        mask_rois = bbox2roi(boxes).contiguous()
-        if mask_rois.shape[0] == 0:
-            s = self._refine_size()
-            return mask_rois.new_zeros((0, 1, s, s)), offsets
-        labels = torch.cat(list(det_labels_list)).contiguous()
-        return self._refined_logits(x, mask_rois, labels), offsets
-
-    def _batch_mask_preds(self, x, boxes_list, labels_list, labels):
-        refined, _ = self.batch_simple_test_mask_logits(x, boxes_list, labels_list)
-        return refined.contiguous(), True
-
-    def _aug_view_mask_logits(self, x, rois, det_labels):
-        """One view's refined label-channel logits [n, 1, S', S'] (point_rend_roi_head.py:170-178)."""
-        return self._refined_logits(x, rois.contiguous(), det_labels).contiguous()
-
-    def _aug_empty_probs(self, ref):
-        s = self._refine_size()
-        return ref.new_zeros((0, 1, s, s))
-
-    def simple_test_mask(self, x, img_metas, det_bboxes, det_labels, rescale=False, encode=False):
-        """point_rend_roi_head.py:130-155 -> ``cls_segms`` of ``get_seg_masks`` on the refined map (``encode``: COCO RLE
-        dicts, ``get_seg_rles``)."""
-        ori_shape = img_metas[0]['ori_shape']
-        scale_factor = img_metas[0]['scale_factor']
-        if det_bboxes.shape[0] == 0:
-            return [[] for _ in range(self.mask_head.num_classes)]
-        if rescale and not isinstance(scale_factor, float):
-            scale_factor = torch.from_numpy(scale_factor).to(det_bboxes.device)
-        _bboxes = det_bboxes[:, :4] * scale_factor if rescale else det_bboxes
-        refined = self._refined_logits(x, bbox2roi([_bboxes]).contiguous(), det_labels)
-        to_segs = self.mask_head.get_seg_rles if encode else self.mask_head.get_seg_masks
-        return to_segs(refined, _bboxes, det_labels, self.test_cfg, ori_shape, scale_factor, rescale)
-
-    def enable_inference_graphs(self, on=True, buckets=None, batch_buckets=None):
-        if on:
-            raise NotImplementedError('PointRendRoIHead: HIP-graph capture of the PointRend call is not implemented')
-        self._mask_graphs = None
-        return None
-
     def forward_train(self, x, img_metas, proposal_list, gt_bboxes, gt_labels, gt_bboxes_ignore=None, gt_masks=None):
         raise NotImplementedError('PointRendRoIHead.forward_train: PointRend training is broken in the reference '
                                   '(CoarseMaskHead.loss and the point loss use mask_cross_entropy, Quirk Q5)')
-
-    def _mask_forward_train(self, *a, **k):
-        raise NotImplementedError('PointRendRoIHead: PointRend training is broken in the reference (Quirk Q5)')
-
-    def dynamic_mask_logits(self, *a, **k):
-        raise NotImplementedError('PointRendRoIHead: per-RoI early exit is DynaMask\'s, PointRend has none')
-
-    def dynamic_test_mask(self, *a, **k):
-        raise NotImplementedError('PointRendRoIHead: per-RoI early exit is DynaMask\'s, PointRend has none')

@@ -85,13 +85,13 @@ def _band(m, x1, dets, labels, meta, rescale):
     """Per detection: pixels whose per-image probability lies in [THR - BAND, THR + BAND) -- two pastes of the
     per-image logits at the band's edges."""
     from dynamask_amd import ops
-    from dynamask_amd.mask_heads import _paste_geometry
-    from dynamask_amd.roi_head import StandardRoIHead, bbox2roi
+    from dynamask_amd.mask_heads import FCNMaskHead, _paste_geometry
+    from dynamask_amd.roi_head import bbox2roi
     sf = meta['scale_factor']
     if rescale and not isinstance(sf, float):
         sf = torch.from_numpy(sf).to(dets.device)
     bx = dets[:, :4] * sf if rescale else dets
-    if isinstance(m, StandardRoIHead):
+    if isinstance(m.mask_head, FCNMaskHead):          # (every RoI head is a StandardRoIHead)
         pred = m._mask_forward(x1, bbox2roi([bx]).contiguous())['mask_pred']
         pred, _ = m.mask_head._selected(pred, bx, labels)
     else:
@@ -155,7 +155,8 @@ def test_batch_simple_test_equals_per_image_calls(kind, B, rescale):
 def test_batch_mask_logits_close_to_per_image(kind):
     """B = 4: the logits of one mask chain over all images against each image's own chain (1e-4, the gate of the
     per-image path against the oracle in test_path_gpu.py); B = 1 bit-identical."""
-    from dynamask_amd.roi_head import StandardRoIHead, bbox2roi
+    from dynamask_amd.mask_heads import FCNMaskHead
+    from dynamask_amd.roi_head import bbox2roi
     m = _head(kind)
     x, props, metas = _inputs(4)
     with torch.no_grad():
@@ -167,7 +168,7 @@ def test_batch_mask_logits_close_to_per_image(kind):
         for b, (d, l) in enumerate(dl):
             sf = sfs[b] if isinstance(sfs[b], float) else torch.from_numpy(sfs[b]).cuda()
             bx = d[:, :4] * sf
-            if isinstance(m, StandardRoIHead):
+            if isinstance(m.mask_head, FCNMaskHead):
                 ref = m._mask_forward(_one(x, b), bbox2roi([bx]).contiguous())['mask_pred']
             else:
                 ref = m.simple_test_mask_logits(_one(x, b), bx, l)
