@@ -102,6 +102,12 @@ SIGNATURES = {
     'dm_point_mlp_fwd': ([_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _c_int, _vp, _vp, _c_int,
                           _vp, _c_int, _vp], _c_int),
     'dm_point_scatter': ([_vp, _vp, _c_int, _c_int, _vp, _c_int, _vp], _c_int),
+    'dm_conv3x3_s2_supported': ([_c_int, _c_int, _c_int, _c_int, _c_int, _c_int], _c_int),
+    'dm_conv3x3_s2_workspace_floats': ([_c_int, _c_int, _c_int, _c_int, _c_int, _c_int], ctypes.c_longlong),
+    'dm_conv3x3_s2_fwd': ([_vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, ctypes.c_longlong, _vp], _c_int),
+    'dm_mask_iou_input_supported': ([_c_int, _c_int, _c_int, _c_int], _c_int),
+    'dm_mask_iou_input': ([_vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp], _c_int),
+    'dm_mask_iou_scores': ([_vp, _c_int, _c_int, _vp, _vp, _c_int, _vp, _vp], _c_int),
     'dm_fc_scratch_floats': ([_c_int, _c_int, _c_int], ctypes.c_longlong),
     'dm_fc_fwd': ([_vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp], _c_int),
     'dm_sgd_momentum_step': ([_vp, _vp, _vp, ctypes.c_longlong, _c_float, _c_float, _c_float, _c_float, _c_int, _vp], _c_int),

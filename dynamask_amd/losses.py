@@ -254,3 +254,16 @@ class SmoothL1Loss(nn.Module):
 
     def forward(self, *a, **k):
         raise NotImplementedError('SmoothL1Loss.forward: bbox training with configs/refinemask is the follow-up to its inference')
+
+
+@LOSSES.register_module()
+class MSELoss(nn.Module):
+    """losses/mse_loss.py MSELoss: constructor only, so that configs/ms_rcnn (whose MaskIoUHead names it as ``loss_iou``)
+    builds for inference.  The IoU loss is reachable only past the fork's broken mask loss (Quirk Q5)."""
+
+    def __init__(self, reduction='mean', loss_weight=1.0):
+        super().__init__()
+        self.reduction, self.loss_weight = reduction, loss_weight
+
+    def forward(self, *a, **k):
+        raise NotImplementedError('MSELoss.forward: Mask Scoring R-CNN training is unreachable in the reference fork (Quirk Q5)')

@@ -1181,3 +1181,115 @@ class MaskPointHead(nn.Module):
 
     def loss(self, *a, **k):
         raise NotImplementedError('MaskPointHead.loss: mask_cross_entropy is broken in the reference fork (Quirk Q5)')
+
+
+# ---------------------------------------------------------------- Mask Scoring R-CNN: MaskIoUHead (inference)
+def _to_host_pending(*tensors):
+    """Enqueue device -> host copies into fresh pinned buffers WITHOUT a synchronisation: the buffers hold the values once
+    the current stream has been synchronised by the caller's next host wait (the mask paste's copy, or its RLE
+    collection).  -> the pinned host tensors."""
+    hosts = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in tensors]
+    for h, t in zip(hosts, tensors):
+        h.copy_(t, non_blocking=True)
+    return hosts
+
+
+@HEADS.register_module()
+class MaskIoUHead(nn.Module):
+    """``MaskIoUHead`` -- mmdet/models/roi_heads/mask_heads/maskiou_head.py, inference: the IoU of a detection's mask
+    predicted from the RoI features and the mask head's prediction.  ``convs.{i}`` (3x3, stride 2 on the last),
+    ``fcs.{i}`` and ``fc_mask_iou`` carry the reference's ``state_dict`` keys.  The first conv reads two sources,
+    ``[mask_feat, max_pool2x2(sigmoid(mask_pred[label]))]`` (ops.mask_iou_input), with no concatenation; the stride-1
+    convs run on conv_igemm through ``_Conv.run`` (they follow ``set_conv_precision``), the stride-2 conv on
+    ops.conv3x3_s2 (exact fp32 in every mode), the fully connected layers on dm_fc_fwd.  ``get_targets`` / ``loss`` are
+    reachable only past the fork's broken mask loss (Quirk Q5): they raise."""
+
+    def __init__(self, num_convs=4, num_fcs=2, roi_feat_size=14, in_channels=256, conv_out_channels=256,
+                 fc_out_channels=1024, num_classes=80, loss_iou=dict(type='MSELoss', loss_weight=0.5)):
+        super().__init__()
+        if num_convs < 2:
+            raise NotImplementedError('MaskIoUHead: num_convs >= 2 (the stride-2 conv reads one source; configs/ms_rcnn: 4)')
+        if num_fcs < 1:
+            raise NotImplementedError('MaskIoUHead: num_fcs >= 1 (configs/ms_rcnn: 2)')
+        if conv_out_channels % 8 != 0:
+            raise NotImplementedError('MaskIoUHead: conv_out_channels a multiple of 8 (configs/ms_rcnn: 256)')
+        roi = (roi_feat_size, roi_feat_size) if isinstance(roi_feat_size, int) else tuple(roi_feat_size)
+        if roi[0] % 2 or roi[1] % 2:
+            raise NotImplementedError('MaskIoUHead: an even roi_feat_size (the pooled mask and the stride-2 output '
+                                      'must both be roi_feat_size / 2; configs/ms_rcnn: 14)')
+        self.in_channels = in_channels
+        self.conv_out_channels = conv_out_channels
+        self.fc_out_channels = fc_out_channels
+        self.num_classes = num_classes
+        self.roi_feat_size = roi
+        self.convs = nn.ModuleList()
+        for i in range(num_convs):
+            self.convs.append(_Conv(in_channels + 1 if i == 0 else conv_out_channels, conv_out_channels, 3))
+        pooled_area = (roi[0] // 2) * (roi[1] // 2)
+        self.fcs = nn.ModuleList()
+        for i in range(num_fcs):
+            self.fcs.append(nn.Linear(conv_out_channels * pooled_area if i == 0 else fc_out_channels, fc_out_channels))
+        self.fc_mask_iou = nn.Linear(fc_out_channels, num_classes)
+        self.loss_iou = build_loss(loss_iou)
+
+    def init_weights(self):
+        """maskiou_head.py:67-77."""
+        for conv in self.convs:
+            nn.init.kaiming_normal_(conv.weight, mode='fan_out', nonlinearity='relu')
+            nn.init.constant_(conv.bias, 0)
+        for fc in self.fcs:
+            nn.init.kaiming_uniform_(fc.weight, a=1, mode='fan_in', nonlinearity='leaky_relu')
+            nn.init.constant_(fc.bias, 0)
+        nn.init.normal_(self.fc_mask_iou.weight, 0, 0.01)
+        nn.init.constant_(self.fc_mask_iou.bias, 0)
+
+    def forward(self, mask_feat, mask_pred, labels=None):
+        """maskiou_head.py:79-91 -> mask_iou [n, num_classes].  ``mask_pred``: the reference's [n, S, S] (the label
+        channel already selected), or the mask head's [n, C, S, S] logits with ``labels`` [n] (C == 1: class-agnostic),
+        whose label channel ops.mask_iou_input selects in the same launch as the sigmoid and the 2 x 2 max pool."""
+        if torch.is_grad_enabled() and mask_feat.requires_grad:
+            raise NotImplementedError('MaskIoUHead: training is unreachable in the reference fork (Quirk Q5)')
+        with torch.no_grad():
+            return self._forward(mask_feat, mask_pred, labels)
+
+    def _forward(self, mask_feat, mask_pred, labels):
+        if mask_pred.dim() == 3:
+            mask_pred, labels = mask_pred[:, None], None
+        n = mask_feat.shape[0]
+        if n == 0:
+            return mask_feat.new_zeros((0, self.num_classes))
+        labels = None if labels is None else labels.to(torch.int64).contiguous()
+        pooled = ops.mask_iou_input(mask_pred.contiguous(), labels)
+        x = [mask_feat.contiguous(), pooled]
+        with ops.splitk_scope():            # inference on <= 100 RoIs: the 14 x 14 launches may split their K loop
+            for conv in self.convs[:-1]:
+                x = conv.run(x, relu=True)
+            last = self.convs[-1]
+            x = ops.conv3x3_s2(x, last.packed(), last.bias.detach(), last.out_channels, relu=True)
+        x = x.reshape(n, -1)
+        for fc in self.fcs:
+            x = ops.fc(x, fc.weight.detach(), fc.bias.detach(), relu=True)
+        return ops.fc(x, self.fc_mask_iou.weight.detach(), self.fc_mask_iou.bias.detach())
+
+    def get_mask_scores(self, mask_iou_pred, det_bboxes, det_labels):
+        """maskiou_head.py:171-181: mask_score = mask_iou[label] * bbox_score -> per-class lists (numpy float32) in
+        detection order."""
+        labels = det_labels.to(torch.int64).contiguous()
+        scores = ops.mask_iou_scores(mask_iou_pred.contiguous(), labels, det_bboxes.contiguous())
+        scores_h, labels_h = _to_host(scores, labels)
+        return group_mask_scores(scores_h, labels_h, self.num_classes)
+
+    def get_targets(self, *a, **k):
+        raise NotImplementedError('MaskIoUHead.get_targets: Mask Scoring R-CNN training is unreachable in the reference '
+                                  'fork (FCNMaskHead.loss is broken before it, Quirk Q5)')
+
+    def loss(self, *a, **k):
+        raise NotImplementedError('MaskIoUHead.loss: Mask Scoring R-CNN training is unreachable in the reference fork '
+                                  '(FCNMaskHead.loss is broken before it, Quirk Q5)')
+
+
+def group_mask_scores(scores, labels, num_classes):
+    """Host arrays [n] -> ``[scores[labels == i] for i in range(num_classes)]`` (maskiou_head.py:178-181)."""
+    import numpy as np
+    scores, labels = np.asarray(scores), np.asarray(labels)
+    return [scores[labels == i] for i in range(num_classes)]

@@ -1166,6 +1166,61 @@ def point_mlp_scatter(x, w_packeds, biases, w_logits, b_logits, labels, idx, ref
     return point_scatter(vals, idx, refined)
 
 
+# ------------------------------------------------ Mask Scoring R-CNN: the IoU head's launches (csrc/conv_strided.hip)
+# Exact fp32 in every precision mode: the bf16x3 mode does not reach these launches.
+def conv3x3_s2_supported(x, cout, splits=0):
+    """Does ``conv3x3_s2`` take this shape (dm_conv3x3_s2_supported: C % 8 == 0, any H, W; splits 0 or 1/2/4/8 <= C / 8)?"""
+    NB, C, H, W = x.shape
+    return bool(lib().dm_conv3x3_s2_supported(NB, C, H, W, int(cout), int(splits)))
+
+
+def conv3x3_s2(x, w_packed, bias, cout, relu=False, splits=0, out=None):
+    """Conv2d(C, cout, 3, stride=2, padding=1)(x) + bias (+ ReLU) -> [NB, cout, ceil(H / 2), ceil(W / 2)]
+    (dm_conv3x3_s2_fwd).  ``w_packed``: ``pack_conv_weight`` of the [cout, C, 3, 3] weight (the stride-1 layout).
+    ``splits``: workgroups per tile over the K loop (0: the library's choice; 1, 2, 4, 8: forced)."""
+    _dil_check(x, w_packed, cout)
+    if bias is not None:
+        _chk(bias, 'bias')
+    NB, C, H, W = x.shape
+    shape = (NB, int(cout), (H + 1) // 2, (W + 1) // 2)
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=torch.float32)
+    else:
+        _chk(out, 'out')
+        assert tuple(out.shape) == shape
+    nws = int(lib().dm_conv3x3_s2_workspace_floats(NB, C, H, W, int(cout), int(splits)))
+    ws = torch.empty((nws,), device=x.device, dtype=torch.float32) if nws > 0 else None
+    check(lib().dm_conv3x3_s2_fwd(_p(x), NB, C, H, W, _p(w_packed), _p(bias), int(cout), int(splits), 1 if relu else 0,
+                                  _p(out), _p(ws), max(nws, 0), _stream()), 'dm_conv3x3_s2_fwd')
+    return out
+
+
+def mask_iou_input(mask_pred, labels):
+    """max_pool2d(sigmoid(mask_pred[i, labels[i]]), 2, 2) -> [n, 1, S / 2, S / 2] (dm_mask_iou_input): ``mask_pred``
+    [n, C, S, S] logits (C == 1: class-agnostic, ``labels`` may be None), ``labels`` [n] int64."""
+    _chk(mask_pred, 'mask_pred')
+    n, C, H, W = mask_pred.shape
+    if C > 1 or labels is not None:
+        _chk(labels, 'labels', torch.int64)
+        assert labels.shape == (n,)
+    out = torch.empty((n, 1, H // 2, W // 2), device=mask_pred.device, dtype=torch.float32)
+    check(lib().dm_mask_iou_input(_p(mask_pred), n, C, H, W, _p(labels), _p(out), _stream()), 'dm_mask_iou_input')
+    return out
+
+
+def mask_iou_scores(mask_iou_pred, labels, dets):
+    """mask_iou_pred[i, labels[i]] * dets[i, -1] -> [n] (dm_mask_iou_scores; MaskIoUHead.get_mask_scores)."""
+    _chk(mask_iou_pred, 'mask_iou_pred')
+    _chk(labels, 'labels', torch.int64)
+    _chk(dets, 'dets')
+    n, nc = mask_iou_pred.shape
+    assert labels.shape == (n,) and dets.dim() == 2 and dets.shape[0] == n
+    out = torch.empty((n,), device=mask_iou_pred.device, dtype=torch.float32)
+    check(lib().dm_mask_iou_scores(_p(mask_iou_pred), n, nc, _p(labels), _p(dets), dets.shape[1], _p(out), _stream()),
+          'dm_mask_iou_scores')
+    return out
+
+
 def pack_deconv_weight(w, precision='fp32'):
     """``precision='bf16x3'``: dm_deconv_pack_weight_bf16x3's layout, marked as such (``conv_layout``)."""
     _chk(w, 'weight')

@@ -1,5 +1,6 @@
 """The RoI heads behind the reference's HEADS registry, in the reference's class tree: ``StandardRoIHead``
-(standard_roi_head.py + test_mixins.py) is the base of ``DynaMaskRoIHead``, ``RefineRoIHead`` and ``PointRendRoIHead``.
+(standard_roi_head.py + test_mixins.py) is the base of ``DynaMaskRoIHead``, ``RefineRoIHead``, ``PointRendRoIHead`` and
+``MaskScoringRoIHead``.
 
 The base holds the constructor (incl. ``base_roi_head.py:10-58``'s MaskPre, Quirk Q4), the assigner / sampler, the bbox
 branch, the one-image / batched / test-time-augmentation entry points and one mask-test template over a head's
@@ -145,7 +146,9 @@ class StandardRoIHead(nn.Module):
     assigner / sampler, the bbox branch, ``simple_test`` / ``batch_simple_test`` / ``aug_test`` and the mask-test
     template.  A head supplies its mask prediction through ``_mask_logits(x, mask_rois, labels)`` -> [n, C, S, S] and
     its (C, S) through ``_mask_logits_size``; the template does the rest once for every head: rescale, ``bbox2roi``,
-    the empty case, the label-channel selection, the paste, the device -> host copy and the grouping by class.  Here the
+    the empty case, the label-channel selection, the paste, the device -> host copy and the grouping by class.  A head
+    whose mask test returns more than the masks (MaskScoringRoIHead's scores) overrides ``_mask_test_pred`` and
+    ``_mask_test_result``.  Here the
     mask branch is the stock one: ``_mask_forward(x, rois)`` -> ``{'mask_pred': [N, classes, 28, 28], 'mask_feats'}``.
     ``BaseRoIHead.__init__`` of the fork builds ``mask_predictor`` / ``semantic_roi_extractor`` for EVERY RoI head (Quirk
     Q4), so the ``state_dict`` carries the ``mask_predictor.*`` keys here too, as the reference's does.
@@ -317,6 +320,20 @@ class StandardRoIHead(nn.Module):
         """The number of per-class lists of ``simple_test_mask``."""
         return self.mask_head.num_classes
 
+    def _mask_test_pred(self, x, boxes, labels, det_bboxes):
+        """The mask prediction that ``simple_test_mask`` / ``batch_simple_test_mask`` paste, for the detections of the
+        images of a call (per-image lists: the boxes the mask chain reads, the labels, the detections as given) ->
+        (logits [sum n, C, S, S], what ``_mask_test_result`` adds to the masks or None).  Here: the logits of
+        ``simple_test_mask_logits`` (one image) / ``batch_simple_test_mask_logits``, nothing beside them."""
+        if len(boxes) == 1:
+            return self.simple_test_mask_logits(x, boxes[0], labels[0]), None
+        return self.batch_simple_test_mask_logits(x, boxes, labels)[0], None
+
+    def _mask_test_result(self, segms, pending, start, count):
+        """One image's mask-test result from its per-class ``segms`` and the second value of ``_mask_test_pred``
+        (rows start:start + count are the image's; read only after the paste's host wait): here the masks alone."""
+        return segms
+
     def _empty_mask_logits(self, ref, channels=None):
         c, s = self._mask_logits_size()
         return ref.new_zeros((0, c if channels is None else channels, s, s))
@@ -351,11 +368,12 @@ class StandardRoIHead(nn.Module):
         from .mask_heads import paste_segms, select_label_channel
         num_classes = self._segm_num_classes()
         if det_bboxes.shape[0] == 0:
-            return [[] for _ in range(num_classes)]
+            return self._mask_test_result([[] for _ in range(num_classes)], None, 0, 0)
         _bboxes, scale_factor = self._mask_boxes(det_bboxes, img_metas[0]['scale_factor'], rescale)
-        logits = self.simple_test_mask_logits(x, _bboxes, det_labels)
-        return paste_segms(select_label_channel(logits, det_labels), _bboxes, det_labels, self.test_cfg,
-                           img_metas[0]['ori_shape'], scale_factor, rescale, encode=encode, num_classes=num_classes)
+        logits, pending = self._mask_test_pred(x, [_bboxes], [det_labels], [det_bboxes])
+        segms = paste_segms(select_label_channel(logits, det_labels), _bboxes, det_labels, self.test_cfg,
+                            img_metas[0]['ori_shape'], scale_factor, rescale, encode=encode, num_classes=num_classes)
+        return self._mask_test_result(segms, pending, 0, int(det_bboxes.shape[0]))
 
     # ------------------------------------------------------------ batched inference: B images per call
     # Each method gives, per image, what its one-image counterpart gives for that image alone; the B images share the
@@ -438,12 +456,13 @@ class StandardRoIHead(nn.Module):
         results = [[[] for _ in range(num_classes)] for _ in range(B)]
         counts = [int(d.shape[0]) for d in det_bboxes_list]
         if sum(counts) == 0:
-            return results
+            return [self._mask_test_result(r, None, 0, 0) for r in results]
         threshold = _mask_threshold(self.test_cfg)
         boxes, sfs = zip(*[self._mask_boxes(det, meta['scale_factor'], rescale)
                            for det, meta in zip(det_bboxes_list, img_metas)])
         labels = torch.cat(list(det_labels_list))
-        preds = select_label_channel(self.batch_simple_test_mask_logits(x, boxes, det_labels_list)[0], labels)
+        logits, pending = self._mask_test_pred(x, boxes, det_labels_list, det_bboxes_list)
+        preds = select_label_channel(logits, labels)
         canvas_boxes, sizes = [], []
         for b in range(B):
             if counts[b] == 0:
@@ -465,12 +484,13 @@ class StandardRoIHead(nn.Module):
                 (flat,), labels_h = _to_host(buf), _labels_host
             flat = flat.view(np.bool_)
             segs = [flat[o:o + h * w].reshape(h, w) for o, (h, w) in zip(offs, det_sizes)]
-        start = 0
+        start, out = 0, []
         for b in range(B):
             for j in range(start, start + counts[b]):
                 results[b][labels_h[j]].append(segs[j])
+            out.append(self._mask_test_result(results[b], pending, start, counts[b]))
             start += counts[b]
-        return results
+        return out
 
     @torch.no_grad()
     def batch_simple_test_bboxes(self, x, img_metas, proposals, rcnn_test_cfg, rescale=False):
@@ -1145,3 +1165,54 @@ class PointRendRoIHead(StandardRoIHead):
     def forward_train(self, x, img_metas, proposal_list, gt_bboxes, gt_labels, gt_bboxes_ignore=None, gt_masks=None):
         raise NotImplementedError('PointRendRoIHead.forward_train: PointRend training is broken in the reference '
                                   '(CoarseMaskHead.loss and the point loss use mask_cross_entropy, Quirk Q5)')
+
+
+@HEADS.register_module()
+class MaskScoringRoIHead(StandardRoIHead):
+    """``MaskScoringRoIHead`` -- mmdet/models/roi_heads/mask_scoring_roi_head.py, inference: the RoI head of configs/ms_rcnn,
+    a ``StandardRoIHead`` over ``FCNMaskHead`` plus ``mask_iou_head`` (``MaskIoUHead``).  ``simple_test_mask`` returns
+    ``(segm_result, mask_scores)`` (:58-90; ``encode=True``: ``(rles, mask_scores)``, what ``encode_mask_results`` gives
+    for a tuple), ``batch_simple_test_mask`` that pair per image; the empty form is ``([[]] * C, [[]] * C)``.  The mask
+    branch runs once per call: RoIAlign and FCNMaskHead give ``mask_feats`` and ``mask_pred`` once, the IoU head reads
+    both, and the scores (ops.mask_iou_scores) cross to the host behind the same host wait as the masks.  ``aug_test`` is
+    the base's (masks without scores: the reference does not override it).  Training raises (Quirk Q5: the mask loss it
+    would run first is broken in the fork), and so does HIP-graph capture."""
+
+    def __init__(self, mask_iou_head=None, **kwargs):
+        if mask_iou_head is None:
+            raise ValueError('MaskScoringRoIHead needs a mask_iou_head (mask_scoring_roi_head.py:16)')
+        super().__init__(**kwargs)
+        if not self.with_mask:
+            raise ValueError('MaskScoringRoIHead needs a mask branch')
+        if type(self.mask_head).__name__ != 'FCNMaskHead':
+            raise NotImplementedError('MaskScoringRoIHead: an FCNMaskHead mask branch (configs/ms_rcnn)')
+        self.mask_iou_head = build_head(mask_iou_head)
+
+    def init_weights(self, pretrained=None):
+        super().init_weights(pretrained)
+        self.mask_iou_head.init_weights()
+
+    def forward_train(self, x, img_metas, proposal_list, gt_bboxes, gt_labels, gt_bboxes_ignore=None, gt_masks=None):
+        raise NotImplementedError('MaskScoringRoIHead.forward_train: the mask loss it runs before the IoU loss '
+                                  '(FCNMaskHead.loss) is broken in the reference fork (Quirk Q5)')
+
+    def _mask_test_pred(self, x, boxes, labels, det_bboxes):
+        """One mask branch for the detections of all images: ``mask_pred`` to paste, and the mask scores of
+        ``mask_iou_head`` on the same ``mask_feats`` / ``mask_pred``, copied to pinned host memory without a wait."""
+        from .mask_heads import _to_host_pending
+        rois = bbox2roi(list(boxes)).contiguous()
+        labels = torch.cat([lab.to(torch.int64) for lab in labels]).contiguous()
+        dets = torch.cat(list(det_bboxes)).contiguous()
+        with torch.no_grad():
+            res = self._mask_forward(x, rois)
+            mask_iou_pred = self.mask_iou_head(res['mask_feats'], res['mask_pred'], labels)
+            scores = ops.mask_iou_scores(mask_iou_pred, labels, dets)
+        return res['mask_pred'], _to_host_pending(scores, labels)
+
+    def _mask_test_result(self, segms, pending, start, count):
+        from .mask_heads import group_mask_scores
+        num_classes = self.mask_iou_head.num_classes
+        if pending is None or count == 0:
+            return segms, [[] for _ in range(num_classes)]
+        scores, labels = (t.numpy()[start:start + count] for t in pending)
+        return segms, group_mask_scores(scores, labels, num_classes)

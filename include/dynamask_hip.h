@@ -56,7 +56,8 @@ typedef void* dm_stream_t; /* hipStream_t */
 
 const char* dm_error_string(int code);
 /* ABI version: bumped whenever a signature or the meaning of an argument changes (8: flag bit 3 of dm_conv2d_fwd; 9: RoI assignment / bbox training entry points; 10: dm_detail_target takes the fuse weights from device memory; 11: FCNMaskHead upsample backward; 12: dm_fc_fwd takes a scratch slab, deterministic split-K; 13: dm_deform_coord_grad / dm_deform_col2im, dm_conv2d_fwd_masked, dm_scale, dm_polygon_mask_targets, dm_ignore_columns, dm_upsample2x_bilinear_bwd overwrites; 14: dm_random_sample, dm_bn_relu_maxpool_argmax, the *_fx deterministic accumulators + dm_fx_to_float, dm_mask_loss_fwd_bwd takes a scratch, dm_conv2d_wgrad takes the bias gradient, dm_conv_pack_weight_batch, dm_mask_loss_stage; 15: dm_class_logits_up2x_fwd; 16: dm_conv2d_wgrad_slab / dm_conv2d_wgrad_scratch_floats; 17: dm_class_logits_bwd_slab / dm_class_logits_bwd_scratch_floats; 18: dm_reload_env_knobs, dm_roi_align_fwd_ws / dm_roi_align_workspace_bytes, dm_conv_pack_weight_split / dm_conv_packed_floats_split and flag bits 4, 5 of dm_conv2d_fwd; 19: dm_dcn_bwd_data_fused and its pack; 20: dm_conv2d_fwd_ws / dm_conv2d_splitk_floats; 21: dm_deform_conv_fwd_ws / dm_deform_conv_splitk_floats; 22: the bf16-split layouts (dm_conv_pack_weight_split, dm_conv_packed_floats_split, flag bits 4 / 5 of dm_conv2d_fwd) and the one-kernel DCN data gradient (dm_dcn_bwd_*) REMOVED -- measured, never the parity path, see docs/HISTORY.md; 23: dm_bn_stats takes mean_shift, dm_roi_align_bwd takes the gather form for 16 < P <= 64; 24: dm_build_info; 25: dm_boundary_merge_chain, dm_stage_head_fwd; 26: dm_conv1x1_group_fwd; 27: dm_deform_conv_tout_fwd / dm_deform_conv_tout_supported; 28: the opt-in bf16x3 mode -- dm_conv_pack_weight_bf16x3 / dm_conv_packed_floats_bf16x3 and flag bit 4 of dm_conv2d_fwd, dm_conv2d_fwd_ws and dm_conv1x1_group_fwd; dm_deconv_pack_weight_bf16x3 and flag bit 4 of dm_deconv2x2_fwd).  Entry points ADDED without a signature or meaning change leave the number as it is (the loader resolves every symbol of _lib.SIGNATURES by name, so an older library fails at load): the multi-image post-processing dm_nms_mask_segmented / dm_nms_reduce_segmented, dm_paste_masks_multi, dm_paste_rle_multi / dm_rle_multi_scratch_ints; the test-time augmentation dm_bbox_mapping_multi, dm_merge_aug_bboxes, dm_merge_aug_masks; RefineMask's dilated / any-width 3x3 convolutions and the sigmoid of its semantic map (section K21); PointRend's point
- * selection, point gather, point MLP and scatter (section K22). */
+ * selection, point gather, point MLP and scatter (section K22); Mask Scoring R-CNN's stride-2 3x3 convolution, IoU-head
+ * input and mask scores (section K23). */
 int dm_abi_version(void);
 /* "libdynamask_hip abi=N arch=gfx950 compiler=<clang version> flags=<the product-wide flags of dynamask_amd/build.py>"
  * (static storage).  The library must be compiled WITHOUT packed fp32 instructions (flag "-packed-fp32-ops", see
@@ -854,6 +855,42 @@ int dm_point_mlp_fwd(const float* x, int n, int P, int C, int NC, int F, int num
 /* map[r, idx[r, p]] = vals[r, p] for r < n, p < P (the unfused sequence's scatter); vals [n, P], idx [n, P] in [0, HW),
  * map [n, HW].  DM_ERR_UNSUPPORTED unless n >= 0 and 1 <= P <= HW. */
 int dm_point_scatter(const float* vals, const int* idx, int n, int P, float* map, int HW, dm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * K23  Mask Scoring R-CNN inference: MaskIoUHead (mmdet/models/roi_heads/mask_heads/maskiou_head.py) behind the mask
+ * branch of MaskScoringRoIHead.simple_test_mask (mask_scoring_roi_head.py:58-90), csrc/conv_strided.hip.
+ *
+ * dm_conv3x3_s2_fwd: the IoU head's last conv, Conv2d(C, Cout, 3, stride = 2, padding = 1) + bias (+ ReLU).
+ * x [NB, C, H, W]; w_packed: dm_conv_pack_weight(ksize = 3, one source) of the [Cout, C, 3, 3] weight (the layout
+ * dm_conv2d_fwd reads); bias [Cout] or NULL; out [NB, Cout, ceil(H / 2), ceil(W / 2)].  Exact fp32
+ * (v_mfma_f32_32x32x2_f32) only.  splits: how many workgroups share a tile's K loop -- 1, 2, 4 or 8 (at most C / 8), or 0:
+ * the library's choice (the smallest that puts two workgroups on every CU).  With more than one split the partial sums go
+ * to `workspace` (dm_conv3x3_s2_workspace_floats() floats; may be NULL when that is 0) and a second launch adds them in
+ * split order, then the bias: the same bits every run, which differ between split counts in rounding only.
+ * flags: bit 0 ReLU; bit 3 accepted and ignored; bit 4 (the bf16x3 layout) returns DM_ERR_UNSUPPORTED; any other bit
+ * DM_ERR_INVALID_ARG.  A workspace smaller than needed: DM_ERR_INVALID_ARG.
+ * dm_conv3x3_s2_supported: 1 exactly when NB >= 1, C >= 8 with C % 8 == 0, H >= 1, W >= 1, Cout >= 1, splits is 0 or
+ * one of 1, 2, 4, 8 not above C / 8, and the grid (ceil(NB * ceil(H / 2) * ceil(W / 2) / 64) pixel tiles times
+ * ceil(roundup(Cout, 32) / (Cout <= 64 ? 64 : 128)) cout tiles times the resolved split count) has at most 2^31 - 1
+ * workgroups.  dm_conv3x3_s2_fwd returns DM_ERR_UNSUPPORTED for anything else; dm_conv3x3_s2_workspace_floats -1.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int dm_conv3x3_s2_supported(int NB, int C, int H, int W, int Cout, int splits);
+long long dm_conv3x3_s2_workspace_floats(int NB, int C, int H, int W, int Cout, int splits);
+int dm_conv3x3_s2_fwd(const float* x, int NB, int C, int H, int W, const float* w_packed, const float* bias, int Cout,
+                      int splits, int flags, float* out, float* workspace, long long workspace_floats, dm_stream_t stream);
+/* dm_mask_iou_input: max_pool2d(sigmoid(mask_pred[i, c_i]), 2, 2) -> out [n, 1, H / 2, W / 2] (floor), the IoU head's
+ * second input (maskiou_head.py:80-81).  mask_pred [n, C, H, W] logits; c_i = labels[i] (int64) clamped to [0, C - 1],
+ * 0 when C == 1 (labels may then be NULL).  The sigmoid is the paste kernels' expression; the window's maximum follows
+ * max_pool2d (row-major, a later element wins when larger or NaN).  dm_mask_iou_input_supported: 1 exactly when n >= 0,
+ * C >= 1, H >= 2 and W >= 2.  n == 0 enqueues nothing. */
+int dm_mask_iou_input_supported(int n, int C, int H, int W);
+int dm_mask_iou_input(const float* mask_pred, int n, int C, int H, int W, const long long* labels, float* out,
+                      dm_stream_t stream);
+/* dm_mask_iou_scores: out[i] = mask_iou_pred[i, c_i] * dets[i, D - 1] (MaskIoUHead.get_mask_scores, one fp32 product);
+ * mask_iou_pred [n, NC], labels [n] int64 clamped to [0, NC - 1], dets [n, D] (the detections with their score last).
+ * DM_ERR_UNSUPPORTED unless n >= 0, NC >= 1 and D >= 1.  n == 0 enqueues nothing. */
+int dm_mask_iou_scores(const float* mask_iou_pred, int n, int NC, const long long* labels, const float* dets, int D,
+                       float* out, dm_stream_t stream);
 
 #ifdef __cplusplus
 }
