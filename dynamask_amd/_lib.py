@@ -108,6 +108,14 @@ SIGNATURES = {
     'dm_mask_iou_input_supported': ([_c_int, _c_int, _c_int, _c_int], _c_int),
     'dm_mask_iou_input': ([_vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp], _c_int),
     'dm_mask_iou_scores': ([_vp, _c_int, _c_int, _vp, _vp, _c_int, _vp, _vp], _c_int),
+    'dm_point_topk_select_supported': ([_c_int] * 4, _c_int),
+    'dm_point_topk_select': ([_vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp], _c_int),
+    'dm_point_feat_gather_supported': ([_c_int] * 9, _c_int),
+    'dm_point_feat_gather': ([_vp, _c_int, _c_int, _c_int, _c_int, _vp, _c_int, _vp, _c_int, _vp, _c_int, _c_int, _c_float,
+                              _vp, _vp], _c_int),
+    'dm_point_refine_mlp_supported': ([_c_int] * 7, _c_int),
+    'dm_point_refine_mlp': ([_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _c_int, _vp, _c_int, _vp], _c_int),
+    'dm_point_scatter_rows': ([_vp, _vp, _c_int, _c_int, _c_int, _vp, _c_int, _vp], _c_int),
     'dm_fc_scratch_floats': ([_c_int, _c_int, _c_int], ctypes.c_longlong),
     'dm_fc_fwd': ([_vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp], _c_int),
     'dm_sgd_momentum_step': ([_vp, _vp, _vp, ctypes.c_longlong, _c_float, _c_float, _c_float, _c_float, _c_int, _vp], _c_int),

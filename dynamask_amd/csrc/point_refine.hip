@@ -30,13 +30,31 @@ constexpr int SEL_NW = SEL_NT / DM_WAVE;      // 16 waves
 constexpr unsigned MAG = 0x7fffffffu;          // |v| as an unsigned key: the bit pattern orders like the magnitude
 constexpr long long SEL_MAX_HW = 1LL << 24;
 
+// The selection key of a map value: the P SMALLEST keys are taken.  SEL_MAG: |v| (PointRend's least certain cells).
+// SEL_DESC_RAW / SEL_DESC_SIGMOID: v / dm_sigmoid(v) (the library's logistic) in descending order (PointRefine's topk of
+// the detail map): the order-preserving unsigned image of the float, complemented.
+enum { SEL_MAG = 0, SEL_DESC_RAW = 1, SEL_DESC_SIGMOID = 2 };
+
+template <int MODE>
+__device__ __forceinline__ unsigned sel_key(const float* __restrict__ row, int i) {
+  if constexpr (MODE == SEL_MAG) {
+    return reinterpret_cast<const unsigned*>(row)[i] & MAG;
+  } else {
+    const float v = MODE == SEL_DESC_SIGMOID ? dm_sigmoid(row[i]) : row[i];
+    const unsigned b = __float_as_uint(v);
+    const unsigned up = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    return ~up;
+  }
+}
+
+template <int MODE>
 __global__ __launch_bounds__(SEL_NT) void point_select_kernel(const float* __restrict__ map, int HW, int P,
                                                               int* __restrict__ idx) {
   __shared__ unsigned hist[256];
   __shared__ unsigned s_digit, s_k;
   __shared__ unsigned wcnt[2][SEL_NW];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const unsigned* keys = reinterpret_cast<const unsigned*>(map) + (size_t)blockIdx.x * HW;
+  const float* keys = map + (size_t)blockIdx.x * HW;
   int* out = idx + (size_t)blockIdx.x * P;
 
   // radix select: after the four passes T = prefix is the key of the P-th smallest, k the number of keys == T to take
@@ -46,7 +64,7 @@ __global__ __launch_bounds__(SEL_NT) void point_select_kernel(const float* __res
     if (tid < 256) hist[tid] = 0;
     __syncthreads();
     for (int i = tid; i < HW; i += SEL_NT) {
-      const unsigned key = keys[i] & MAG;
+      const unsigned key = sel_key<MODE>(keys, i);
       if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
     }
     __syncthreads();
@@ -93,7 +111,7 @@ __global__ __launch_bounds__(SEL_NT) void point_select_kernel(const float* __res
 #pragma unroll 1
   for (int t0 = 0; t0 < HW; t0 += SEL_NT) {
     const int i = t0 + tid;
-    const unsigned key = i < HW ? (keys[i] & MAG) : 0xffffffffu;
+    const unsigned key = i < HW ? sel_key<MODE>(keys, i) : 0xffffffffu;
     const bool lt = key < T, eq = key == T;
     const unsigned long long beq = __ballot(eq);
     if (lane == 0) wcnt[0][wave] = (unsigned)__popcll(beq);
@@ -347,7 +365,7 @@ extern "C" int dm_point_select(const float* map, int n, int HW, int P, int* idx,
   if (!dm_point_select_supported(n, HW, P)) return DM_ERR_UNSUPPORTED;
   if (n == 0) return DM_OK;
   if (!map || !idx) return DM_ERR_INVALID_ARG;
-  DM_LAUNCH(point_select_kernel, dim3(n), dim3(SEL_NT), 0, (hipStream_t)stream, map, HW, P, idx);
+  DM_LAUNCH(point_select_kernel<SEL_MAG>, dim3(n), dim3(SEL_NT), 0, (hipStream_t)stream, map, HW, P, idx);
   return dm_check_launch();
 }
 
@@ -409,5 +427,299 @@ extern "C" int dm_point_scatter(const float* vals, const int* idx, int n, int P,
   const long long total = (long long)n * P;
   DM_LAUNCH(point_scatter_kernel, dim3((unsigned)dm_ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, vals, idx,
             total, P, map, HW);
+  return dm_check_launch();
+}
+
+// =====================================================================================================================
+// PointRefine inference (header section K24): one SFMStage of mmdet/models/roi_heads/mask_heads/mask_point_refine.py
+// (:95-132) on the stage features f [n, C, S, S]:
+//
+//   dm_point_topk_select   per RoI, the P cells of LARGEST detail value (topk of sigmoid(detail[label]), or of the raw
+//                          logit without mask_use_sigmoid), indices ascending, the lower flat index first among equal
+//                          keys at the cut: point_select_kernel with the descending keys.
+//   dm_point_feat_gather   the MLP input [n, C + NC, P] in one launch: C channels point_sample'd from the RoI's image of
+//                          the stage's semantic map (dm_point_gather_fwd's expressions), NC channels copied
+//                          exactly from the RoI's [NC, S * S] coarse logit map at the selected cell (torch.gather).
+//   dm_point_refine_mlp    num_fcs layers relu(W [C, C + NC] x [h; coarse] + b), then fc_logits [C, C + NC] (no ReLU),
+//                          ALL C rows written into f at the selected cells (the scatter_ of :126-127).  Exact fp32 MFMA.
+//   dm_point_scatter_rows  f[r, c, idx[r, p]] = vals[r, c, p]: the scatter of the unfused sequence.
+// A NULL index array means "every cell in order" (P == S * S: the select is skipped, the MLP is per point).
+
+namespace {
+
+// ------------------------------------------------------------------------------------------------ gather
+struct FeatGatherArgs {
+  const float* feat;
+  int B, C, H, W;
+  const float* rois;
+  int n;
+  const float* coarse;
+  int NC;
+  const int* idx;
+  int P, S;
+  float spatial_scale;
+  float* out;
+};
+
+__global__ __launch_bounds__(GAT_NT) void point_feat_gather_kernel(FeatGatherArgs a) {
+  const long long gp = (long long)blockIdx.x * GAT_NT + threadIdx.x;
+  if (gp >= (long long)a.n * a.P) return;
+  const int roi = (int)(gp / a.P), p = (int)(gp - (long long)roi * a.P);
+  const int HW = a.S * a.S;
+  const int flat = a.idx ? a.idx[gp] : p;
+  const int CT = a.C + a.NC;
+  float* o = a.out + (size_t)roi * CT * a.P + p;
+  const int c0 = blockIdx.y * GAT_CG;
+  if (c0 < a.C) {
+    const int col = flat % a.S, row = flat / a.S;
+    // get_roi_rel_points_train: w_step = 1.0 / S (Python double) meets the fp32 tensor as an fp32 scalar
+    const float step = (float)(1.0 / (double)a.S);
+    const float px = __fadd_rn(0.5f * step, __fmul_rn((float)col, step));
+    const float py = __fadd_rn(0.5f * step, __fmul_rn((float)row, step));
+    const float* r = a.rois + (size_t)roi * 5;
+    const float bf = r[0];
+    const int b = (int)bf;
+    if (!(bf >= 0.f) || b >= a.B) {       // a RoI of no image of the batch: zeros
+#pragma unroll
+      for (int c = 0; c < GAT_CG; ++c) o[(size_t)(c0 + c) * a.P] = 0.f;
+      return;
+    }
+    const float ax = __fadd_rn(__fmul_rn(px, __fsub_rn(r[3], r[1])), r[1]);
+    const float ay = __fadd_rn(__fmul_rn(py, __fsub_rn(r[4], r[2])), r[2]);
+    const float rx = __fmul_rn(__fdiv_rn(ax, (float)a.W), a.spatial_scale);
+    const float ry = __fmul_rn(__fdiv_rn(ay, (float)a.H), a.spatial_scale);
+    const size_t HWf = (size_t)a.H * a.W;
+    const float* f = a.feat + ((size_t)b * a.C + c0) * HWf;
+#pragma unroll
+    for (int c = 0; c < GAT_CG; ++c) o[(size_t)(c0 + c) * a.P] = grid_sample_zeros(f + c * HWf, a.H, a.W, rx, ry);
+  } else {
+    const int k0 = c0 - a.C;
+    const float* f = a.coarse + ((size_t)roi * a.NC + k0) * HW + flat;
+#pragma unroll
+    for (int c = 0; c < GAT_CG; ++c) o[(size_t)(c0 + c) * a.P] = f[(size_t)c * HW];
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ point MLP
+// Workgroup: 64 points of one RoI, 256 threads = 4 waves.  The C output channels x 64 points of a layer are C / 32 x 2
+// tiles of 32 x 32 (v_mfma_f32_32x32x2_f32, the point on the lane of D): C = 256 -- a wave owns two channel tiles x both
+// point tiles (dm_point_mlp_fwd's split); C = 128 -- one channel tile x both point tiles; C = 64 -- one channel tile x one
+// point tile.  The activations live in the LDS as [KQ][64 points][4 channels] (KQ = (C + NC) / 4: 104 KB at C = 256,
+// NC = 160); a hidden layer's outputs replace the first C channels after a barrier, the NC coarse channels stay.
+// fc_logits is one more layer of the same shape whose outputs (+ bias, no ReLU) go to f at the selected cells.
+// The weights are dm_conv_pack_weight's 1x1 layout [KQ][CoutP][4], read straight from the L2.
+constexpr int RMLP_MAXNC = 160;
+constexpr int RMLP_MAXFC = 4;
+
+struct RefineMlpArgs {
+  const float* x;
+  int n, P, NC, KQ, CoutP, nfc, tiles;
+  const float* w[RMLP_MAXFC + 1];              // the hidden layers, then fc_logits
+  const float* b[RMLP_MAXFC + 1];
+  const int* idx;
+  float* feat;
+  int HW;
+};
+
+template <int C>
+__global__ __launch_bounds__(MLP_NT) void point_refine_mlp_kernel(RefineMlpArgs a) {
+  constexpr int NT32 = C / 32 * 2;              // 32 x 32 tiles of a layer
+  constexpr int TW = NT32 / 4;                  // per wave
+  constexpr int NJ = TW >= 2 ? 2 : 1;           // point tiles per wave
+  constexpr int NI = TW / NJ;                   // channel tiles per wave
+  static_assert(NI * NJ * 4 == NT32, "tile split");
+  extern __shared__ dm_f32x4 lds[];             // [KQ][64]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hi = lane >> 5, l31 = lane & 31;
+  const int roi = blockIdx.x / a.tiles, p0 = (blockIdx.x - roi * a.tiles) * MLP_TP;
+  const int np = min(MLP_TP, a.P - p0);
+  const int CT = C + a.NC;
+  const float* xr = a.x + (size_t)roi * CT * a.P + p0;
+
+  for (int e = tid; e < a.KQ * MLP_TP; e += MLP_NT) {
+    const int q = e / MLP_TP, p = e - q * MLP_TP;
+    dm_f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (p < np) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = xr[(size_t)(4 * q + j) * a.P + p];
+    }
+    lds[e] = v;
+  }
+  __syncthreads();
+
+  const int ci0 = NJ == 2 ? wave * NI : (wave >> 1);     // first channel tile of the wave
+  const int pj0 = NJ == 2 ? 0 : (wave & 1);              // first point tile of the wave
+  const int co_w = ci0 * 32;
+#pragma unroll 1
+  for (int L = 0; L <= a.nfc; ++L) {
+    dm_f32x16 acc[NI][NJ];
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    const dm_f32x4* wq = reinterpret_cast<const dm_f32x4*>(a.w[L]) + co_w + l31;
+    dm_f32x4 av[NI], an[NI];
+#pragma unroll
+    for (int i = 0; i < NI; ++i) av[i] = wq[(size_t)hi * a.CoutP + i * 32];
+#pragma unroll 1
+    for (int q0 = 0; q0 < a.KQ; q0 += 2) {
+      const int qn = q0 + 2 < a.KQ ? q0 + 2 : q0;
+#pragma unroll
+      for (int i = 0; i < NI; ++i) an[i] = wq[(size_t)(qn + hi) * a.CoutP + i * 32];
+      dm_f32x4 bv[NJ];
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) bv[j] = lds[(q0 + hi) * MLP_TP + (pj0 + j) * 32 + l31];
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int i = 0; i < NI; ++i)
+#pragma unroll
+          for (int j = 0; j < NJ; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i][e], bv[j][e], acc[i][j], 0, 0, 0);
+#pragma unroll
+      for (int i = 0; i < NI; ++i) av[i] = an[i];
+    }
+    const float* bias = a.b[L];
+    if (L < a.nfc) {
+      __syncthreads();                         // every wave has read this layer's input
+#pragma unroll
+      for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int co = co_w + i * 32 + 8 * g + 4 * hi;    // rows co .. co + 3 of D, quad co / 4
+          dm_f32x4 bq = {0.f, 0.f, 0.f, 0.f};
+          if (bias) bq = *reinterpret_cast<const dm_f32x4*>(bias + co);
+#pragma unroll
+          for (int j = 0; j < NJ; ++j) {
+            dm_f32x4 v;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[r] = fmaxf(acc[i][j][4 * g + r] + bq[r], 0.f);
+            lds[(co / 4) * MLP_TP + (pj0 + j) * 32 + l31] = v;
+          }
+        }
+      __syncthreads();
+    } else {
+      // fc_logits: every output row into the stage features at the point's cell
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const int p = (pj0 + j) * 32 + l31;
+        if (p >= np) continue;
+        const int cell = a.idx ? a.idx[(size_t)roi * a.P + p0 + p] : p0 + p;
+        if (cell < 0 || cell >= a.HW) continue;
+        float* dst = a.feat + (size_t)roi * C * a.HW + cell;
+#pragma unroll
+        for (int i = 0; i < NI; ++i)
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const int co = co_w + i * 32 + 8 * g + 4 * hi;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) dst[(size_t)(co + r) * a.HW] = acc[i][j][4 * g + r] + (bias ? bias[co + r] : 0.f);
+          }
+      }
+    }
+  }
+}
+
+size_t refine_mlp_lds_bytes(int C, int NC) { return (size_t)((C + NC) / 4) * MLP_TP * 16; }
+
+template <int C>
+int launch_refine_mlp(const RefineMlpArgs& a, dm_stream_t stream) {
+  // the LDS limit is raised once per device to what the widest accepted NC needs
+  static bool raised[DM_MAX_DEVICES] = {false};
+  const int rc = dm_ensure_lds_limit((const void*)point_refine_mlp_kernel<C>, (int)refine_mlp_lds_bytes(C, RMLP_MAXNC), raised);
+  if (rc != DM_OK) return rc;
+  DM_LAUNCH(point_refine_mlp_kernel<C>, dim3((unsigned)((long long)a.n * a.tiles)), dim3(MLP_NT),
+            (int)refine_mlp_lds_bytes(C, a.NC), (hipStream_t)stream, a);
+  return dm_check_launch();
+}
+
+// ------------------------------------------------------------------------------------------------ scatter (rows)
+__global__ void point_scatter_rows_kernel(const float* __restrict__ vals, const int* __restrict__ idx, long long total,
+                                          int C, int P, float* __restrict__ map, int HW) {
+  const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;     // over [n, C, P]
+  if (g >= total) return;
+  const long long rc = g / P;
+  const int p = (int)(g - rc * P);
+  const long long roi = rc / C;
+  const int cell = idx[roi * P + p];
+  if (cell >= 0 && cell < HW) map[rc * HW + cell] = vals[g];
+}
+
+}  // namespace
+
+extern "C" int dm_point_topk_select_supported(int n, int HW, int P, int mode) {
+  return (mode == 0 || mode == 1) && dm_point_select_supported(n, HW, P) ? 1 : 0;
+}
+
+extern "C" int dm_point_topk_select(const float* map, int n, int HW, int P, int mode, int* idx, dm_stream_t stream) {
+  if (!dm_point_topk_select_supported(n, HW, P, mode)) return DM_ERR_UNSUPPORTED;
+  if (n == 0) return DM_OK;
+  if (!map || !idx) return DM_ERR_INVALID_ARG;
+  if (mode == 1)
+    DM_LAUNCH(point_select_kernel<SEL_DESC_SIGMOID>, dim3(n), dim3(SEL_NT), 0, (hipStream_t)stream, map, HW, P, idx);
+  else
+    DM_LAUNCH(point_select_kernel<SEL_DESC_RAW>, dim3(n), dim3(SEL_NT), 0, (hipStream_t)stream, map, HW, P, idx);
+  return dm_check_launch();
+}
+
+extern "C" int dm_point_feat_gather_supported(int B, int C, int H, int W, int n, int NC, int P, int S, int has_idx) {
+  if (B < 1 || C < GAT_CG || C % GAT_CG != 0 || H < 1 || W < 1 || n < 0) return 0;
+  if (NC < GAT_CG || NC % GAT_CG != 0 || S < 1 || (long long)S * S > 0x7fffffffLL) return 0;
+  if (P < 1 || (long long)P > (long long)S * S || (!has_idx && (long long)P != (long long)S * S)) return 0;
+  if ((C + NC) / GAT_CG > 65535) return 0;
+  return dm_ceil_div((long long)n * P, GAT_NT) <= 0x7fffffffLL ? 1 : 0;
+}
+
+extern "C" int dm_point_feat_gather(const float* feat, int B, int C, int H, int W, const float* rois, int n,
+                                    const float* coarse, int NC, const int* idx, int P, int S, float spatial_scale,
+                                    float* out, dm_stream_t stream) {
+  if (!dm_point_feat_gather_supported(B, C, H, W, n, NC, P, S, idx ? 1 : 0)) return DM_ERR_UNSUPPORTED;
+  if (n == 0) return DM_OK;
+  if (!feat || !rois || !coarse || !out) return DM_ERR_INVALID_ARG;
+  FeatGatherArgs a = {feat, B, C, H, W, rois, n, coarse, NC, idx, P, S, spatial_scale, out};
+  const dim3 grid((unsigned)dm_ceil_div((long long)n * P, GAT_NT), (unsigned)((C + NC) / GAT_CG));
+  DM_LAUNCH(point_feat_gather_kernel, grid, dim3(GAT_NT), 0, (hipStream_t)stream, a);
+  return dm_check_launch();
+}
+
+extern "C" int dm_point_refine_mlp_supported(int n, int P, int C, int NC, int num_fcs, int HW, int has_idx) {
+  if (n < 0 || P < 1 || P > HW || (!has_idx && P != HW)) return 0;
+  if (C != 64 && C != 128 && C != 256) return 0;
+  if (NC < 8 || NC > RMLP_MAXNC || (C + NC) % 8 != 0 || num_fcs < 1 || num_fcs > RMLP_MAXFC) return 0;
+  return (long long)n * dm_ceil_div(P, MLP_TP) <= 0x7fffffffLL ? 1 : 0;
+}
+
+extern "C" int dm_point_refine_mlp(const float* x, int n, int P, int C, int NC, int num_fcs, const float* const* w_packed,
+                                   const float* const* bias, const int* idx, int flags, float* feat, int HW,
+                                   dm_stream_t stream) {
+  if (flags & 16) return DM_ERR_UNSUPPORTED;    // bf16x3: exact fp32 only
+  if (flags & ~8) return DM_ERR_INVALID_ARG;    // (bit 3, the scheduling hint of dm_conv2d_fwd, is accepted and ignored)
+  if (!dm_point_refine_mlp_supported(n, P, C, NC, num_fcs, HW, idx ? 1 : 0)) return DM_ERR_UNSUPPORTED;
+  if (n == 0) return DM_OK;
+  if (!x || !w_packed || !feat) return DM_ERR_INVALID_ARG;
+  RefineMlpArgs a = {};
+  a.x = x; a.n = n; a.P = P; a.NC = NC; a.KQ = (C + NC) / 4; a.CoutP = dm_conv_packed_cout(C);
+  a.nfc = num_fcs; a.tiles = dm_ceil_div(P, MLP_TP);
+  for (int L = 0; L <= num_fcs; ++L) {
+    if (!w_packed[L]) return DM_ERR_INVALID_ARG;
+    a.w[L] = w_packed[L];
+    a.b[L] = bias ? bias[L] : nullptr;
+  }
+  a.idx = idx; a.feat = feat; a.HW = HW;
+  if (C == 64) return launch_refine_mlp<64>(a, stream);
+  if (C == 128) return launch_refine_mlp<128>(a, stream);
+  return launch_refine_mlp<256>(a, stream);
+}
+
+extern "C" int dm_point_scatter_rows(const float* vals, const int* idx, int n, int C, int P, float* map, int HW,
+                                     dm_stream_t stream) {
+  if (n < 0 || C < 1 || P < 1 || P > HW) return DM_ERR_UNSUPPORTED;
+  if (n == 0) return DM_OK;
+  if (!vals || !idx || !map) return DM_ERR_INVALID_ARG;
+  const long long total = (long long)n * C * P;
+  if ((total + 255) / 256 > 0x7fffffffLL) return DM_ERR_UNSUPPORTED;
+  DM_LAUNCH(point_scatter_rows_kernel, dim3((unsigned)dm_ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, vals,
+            idx, total, C, P, map, HW);
   return dm_check_launch();
 }

@@ -1183,6 +1183,203 @@ class MaskPointHead(nn.Module):
         raise NotImplementedError('MaskPointHead.loss: mask_cross_entropy is broken in the reference fork (Quirk Q5)')
 
 
+# ---------------------------------------------------------------- PointRefine: PointRefineMaskHead (inference)
+class PointRefineSFMStage(nn.Module):
+    """``SFMStage`` of mmdet/models/roi_heads/mask_heads/mask_point_refine.py:20-132, inference: same keys as the reference
+    (``fcs.j.conv`` Conv1d [C, C + 2 * classes, 1], ``fc_logits``, ``semantic_transform_in``, ``instance_logits``,
+    ``detail_logits``, ``fuse_transform_out``).  ``forward`` refines the stage features at the ``num_points`` cells of
+    largest detail value (ops.point_topk_select -> ops.point_feat_gather -> ops.point_refine_mlp, all C rows of
+    fc_logits into the features), then relu(fuse_transform_out) and relu(bilinear x2)."""
+
+    def __init__(self, semantic_in_channel=256, semantic_out_channel=256, fc_in_channels=256, fc_channels=256,
+                 fc_out_channels=256, num_fcs=3, num_classes=80, semantic_out_stride=4, mask_use_sigmoid=False,
+                 class_agnostic=False, coarse_pred_each_layer=True, upsample_cfg=dict(type='bilinear', scale_factor=2)):
+        super().__init__()
+        if class_agnostic:
+            raise NotImplementedError('PointRefineMaskHead: class_agnostic=False only (fc_logits refines every feature '
+                                      'channel; configs/point_refine)')
+        if not coarse_pred_each_layer:
+            raise NotImplementedError('PointRefineMaskHead: coarse_pred_each_layer=True only (configs/point_refine)')
+        if fc_in_channels != fc_channels or semantic_out_channel != fc_channels:
+            raise NotImplementedError('PointRefineMaskHead: the stage width is one C (fc_in = fc = semantic_out channels)')
+        if fc_channels % 2 != 0 or fc_channels < 8:
+            raise NotImplementedError(f'PointRefineMaskHead: stage width {fc_channels}: an even width >= 8 only')
+        if num_fcs < 1:
+            raise NotImplementedError('PointRefineMaskHead: num_fcs >= 1 only')
+        if upsample_cfg.get('type') != 'bilinear' or upsample_cfg.get('scale_factor') != 2:
+            raise NotImplementedError('the SFM stage upsample is bilinear x2 in configs/point_refine')
+        self.num_fcs = num_fcs
+        self.semantic_out_stride = semantic_out_stride
+        self.mask_use_sigmoid = mask_use_sigmoid
+        self.num_classes = num_classes
+        self.coarse_pred_each_layer = coarse_pred_each_layer
+        self.class_agnostic = class_agnostic
+        self.channels = fc_channels
+        cin = fc_in_channels + 2 * num_classes
+        self.fcs = nn.ModuleList()
+        for _ in range(num_fcs):
+            self.fcs.append(_PointConvModule(cin, fc_channels))
+            cin = fc_channels + 2 * num_classes
+        self.fc_logits = _Conv1d(cin, fc_channels)
+        self.semantic_transform_in = _Conv(semantic_in_channel, semantic_out_channel, 1)
+        self.instance_logits = _Conv(fc_channels, num_classes, 1)
+        self.detail_logits = _Conv(fc_channels, num_classes, 1)
+        self.fuse_transform_out = _Conv(fc_channels, fc_out_channels, 1)
+
+    def mlp_params(self):
+        """(packed weights, biases): the hidden layers, then fc_logits (ops.point_refine_mlp's order)."""
+        layers = [m.conv for m in self.fcs] + [self.fc_logits]
+        return [m.packed() for m in layers], [m.bias.detach() for m in layers]
+
+    def forward(self, instance_feats, sem, rois, roi_labels, num_points, form=None):
+        """mask_point_refine.py:95-132 -> (instance_preds, detail_preds [n, 1, S, S], refined features
+        [n, C_out, 2S, 2S]).  ``sem``: relu(semantic_transform_in(semantic_feat)) of the whole map (computed once per call
+        by the head); ``instance_feats`` [n, C, S, S] is refined IN PLACE (the reference refines a copy)."""
+        n, c, S = instance_feats.shape[0], self.channels, instance_feats.shape[2]
+        nc = self.num_classes
+        dev = instance_feats.device
+        # both logit maps, all classes: the point MLP's coarse inputs
+        coarse = torch.empty((n, 2 * nc, S, S), device=dev, dtype=torch.float32)
+        self.instance_logits.run(instance_feats, out=coarse, out_ch_offset=0)
+        self.detail_logits.run(instance_feats, out=coarse, out_ch_offset=nc)
+        # the label rows (the stage predictions and the selection key)
+        wi, bi = self.instance_logits.weight.detach().view(nc, c), self.instance_logits.bias.detach()
+        wd, bd = self.detail_logits.weight.detach().view(nc, c), self.detail_logits.bias.detach()
+        ip, dp = ops.class_logits(instance_feats, wi, bi, wd, bd, roi_labels)
+        hw = S * S
+        P = min(hw, int(num_points))
+        idx = None if P == hw else ops.point_topk_select(dp, P, use_sigmoid=self.mask_use_sigmoid)
+        if form is None and not ops.point_refine_mlp_supported(n, c, 2 * nc, P, self.num_fcs, hw, idx is not None):
+            form = 'unfused'            # (a width the fused kernel does not take: the 1x1 launch sequence)
+        x = ops.point_feat_gather(sem, rois, coarse, idx, 1.0 / float(self.semantic_out_stride))
+        wq, bs = self.mlp_params()
+        ops.point_refine_mlp(x, c, wq, bs, idx, instance_feats, form=form)
+        fused = self.fuse_transform_out.run(instance_feats, relu=True)
+        return ip, dp, ops.upsample2x(fused, align_corners=False, relu=True)
+
+
+@HEADS.register_module()
+class PointRefineMaskHead(nn.Module):
+    """``PointRefineMaskHead`` -- mmdet/models/roi_heads/mask_heads/mask_point_refine.py:174-402, inference: same
+    constructor kwargs and ``state_dict`` keys (in the reference's order) as the reference, so PointRefine checkpoints
+    load.  ``forward`` returns (stage_instance_preds, stage_detail_preds, semantic_pred) as the reference.  The config's
+    loss, ``PointRefineCrossEntropyLoss``, is registered nowhere in the reference (Quirk Q15): ``loss_cfg`` is stored, not
+    built, and training (``get_targets``, ``loss``) raises."""
+
+    def __init__(self, num_convs_instance=2, num_convs_semantic=4, num_fcs=3, conv_in_channels_instance=256,
+                 conv_in_channels_semantic=256, conv_kernel_size_instance=3, conv_kernel_size_semantic=3,
+                 conv_out_channels_instance=256, conv_out_channels_semantic=256, conv_cfg=None, norm_cfg=None,
+                 semantic_out_stride=4, mask_use_sigmoid=False, class_agnostic=False, coarse_pred_each_layer=True,
+                 stage_num_classes=[80, 80, 80, 80], stage_sup_size=[14, 28, 56, 112],
+                 upsample_cfg=dict(type='bilinear', scale_factor=2),
+                 loss_cfg=dict(type='RefineCrossEntropyLoss', stage_instance_loss_weight=[0.25, 0.5, 0.75, 1.0],
+                               semantic_loss_weight=1.0, boundary_width=2, start_stage=1)):
+        super().__init__()
+        self.num_convs_instance = num_convs_instance
+        self.conv_kernel_size_instance = conv_kernel_size_instance
+        self.conv_in_channels_instance = conv_in_channels_instance
+        self.conv_out_channels_instance = conv_out_channels_instance
+        self.num_convs_semantic = num_convs_semantic
+        self.conv_kernel_size_semantic = conv_kernel_size_semantic
+        self.conv_in_channels_semantic = conv_in_channels_semantic
+        self.conv_out_channels_semantic = conv_out_channels_semantic
+        self.conv_cfg, self.norm_cfg = conv_cfg, norm_cfg
+        self.semantic_out_stride = semantic_out_stride
+        self.stage_sup_size = stage_sup_size
+        self.stage_num_classes = stage_num_classes
+        self.mask_use_sigmoid = mask_use_sigmoid
+        self.num_fcs = num_fcs
+        self.loss_cfg = loss_cfg                 # (not built: Quirk Q15)
+        if conv_kernel_size_semantic != 3:
+            raise NotImplementedError('the semantic convs are 3x3 in configs/point_refine')
+        if class_agnostic or any(k == 1 for k in stage_num_classes):
+            raise NotImplementedError('PointRefineMaskHead: class_agnostic=False with per-class logits only '
+                                      '(configs/point_refine)')
+
+        convs = []
+        for i in range(num_convs_instance):
+            cin = conv_in_channels_instance if i == 0 else conv_out_channels_instance
+            convs.append(ConvModule(cin, conv_out_channels_instance, conv_kernel_size_instance, dilation=1, padding=1))
+        self.instance_convs = nn.ModuleList(convs)
+        convs = []
+        for i in range(num_convs_semantic):
+            cin = conv_in_channels_semantic if i == 0 else conv_out_channels_semantic
+            convs.append(DilatedConvModule(cin, conv_out_channels_semantic, 3, padding=1, dilation=1))
+        self.semantic_convs = nn.ModuleList(convs)
+
+        assert len(self.stage_sup_size) > 1
+        self.stages = nn.ModuleList()
+        out_channel = conv_out_channels_instance
+        for idx, out_size in enumerate(self.stage_sup_size[:-1]):
+            in_channel = out_channel
+            out_channel = in_channel // 2
+            if in_channel % 2 != 0:
+                raise NotImplementedError(f'PointRefineMaskHead: stage {idx} width {in_channel} is odd')
+            self.stages.append(PointRefineSFMStage(
+                semantic_in_channel=conv_out_channels_semantic, semantic_out_channel=in_channel, fc_in_channels=in_channel,
+                fc_channels=in_channel, fc_out_channels=out_channel, num_fcs=num_fcs, num_classes=self.stage_num_classes[idx],
+                semantic_out_stride=semantic_out_stride, mask_use_sigmoid=mask_use_sigmoid, class_agnostic=class_agnostic,
+                coarse_pred_each_layer=coarse_pred_each_layer, upsample_cfg=upsample_cfg))
+        if len(self.stages) > 3:
+            raise NotImplementedError('PointRefineMaskHead: at most three SFM stages (one grouped semantic 1x1 launch)')
+        self.final_instance_logits = _Conv(out_channel, self.stage_num_classes[-1], 1)
+        self.final_detail_logits = _Conv(out_channel, self.stage_num_classes[-1], 1)
+        self.semantic_logits = _Conv(conv_out_channels_semantic, 1, 1)
+
+    def init_weights(self):
+        for m in [self.final_instance_logits, self.final_detail_logits, self.semantic_logits]:
+            nn.init.kaiming_normal_(m.weight, mode='fan_out', nonlinearity='relu')
+            nn.init.constant_(m.bias, 0)
+
+    def semantic_forward(self, semantic_feat):
+        """The four 3x3 semantic convs on the whole stride-4 map (once per call, every image of the batch), then the
+        stages' relu(semantic_transform_in) as ONE grouped 1x1 launch -> (semantic features, [sem per stage])."""
+        for conv in self.semantic_convs:
+            semantic_feat = conv(semantic_feat)
+        ts = [st.semantic_transform_in for st in self.stages]
+        prec = ts[0].precision_for(semantic_feat.shape[2], semantic_feat.shape[3])
+        sems = ops.conv1x1_group([semantic_feat] * len(ts), [t.packed([t.in_channels], prec) for t in ts],
+                                 [t.bias.detach() for t in ts], [t.out_channels for t in ts], relu=True)
+        return semantic_feat, sems
+
+    def forward(self, instance_feats, semantic_feat, rois, roi_labels, cfg, semantic_pred=True, form=None):
+        """mask_point_refine.py:288-313 -> (stage_instance_preds, stage_detail_preds [n, 1, S_k, S_k] per stage,
+        semantic_pred [B, 1, H, W] or None when ``semantic_pred`` is False: test time does not read it).
+        ``cfg.num_points``: the points per stage.  ``form``: the point MLP's form (ops.point_refine_mlp)."""
+        for conv in self.instance_convs:
+            instance_feats = conv(instance_feats)
+        semantic_feat, sems = self.semantic_forward(semantic_feat)
+        sem_pred = self.semantic_logits.run(semantic_feat) if semantic_pred else None
+        roi_labels = roi_labels.long().contiguous()
+        rois = rois.contiguous()
+        num_points = int(cfg.num_points)
+        ips, dps = [], []
+        for stage, sem in zip(self.stages, sems):
+            ip, dp, instance_feats = stage(instance_feats, sem, rois, roi_labels, num_points, form=form)
+            ips.append(ip)
+            dps.append(dp)
+        nc = self.stage_num_classes[-1]
+        c = self.final_instance_logits.in_channels
+        fi, fd = self.final_instance_logits, self.final_detail_logits
+        ip, dp = ops.class_logits(instance_feats, fi.weight.detach().view(nc, c), fi.bias.detach(),
+                                  fd.weight.detach().view(nc, c), fd.bias.detach(), roi_labels)
+        ips.append(ip)
+        dps.append(dp)
+        return ips, dps, sem_pred
+
+    # mask_point_refine.py:350-402 = dynamask_head.py:279-342 (sigmoid, paste, threshold)
+    get_seg_masks = DynaMaskHead.get_seg_masks
+    get_seg_rles = DynaMaskHead.get_seg_rles
+
+    def get_targets(self, *a, **k):
+        raise NotImplementedError('PointRefineMaskHead.get_targets: PointRefine training is out of reach -- the config\'s '
+                                  'PointRefineCrossEntropyLoss is registered nowhere in the reference (Quirk Q15)')
+
+    def loss(self, *a, **k):
+        raise NotImplementedError('PointRefineMaskHead.loss: PointRefineCrossEntropyLoss is registered nowhere in the '
+                                  'reference (Quirk Q15)')
+
+
 # ---------------------------------------------------------------- Mask Scoring R-CNN: MaskIoUHead (inference)
 def _to_host_pending(*tensors):
     """Enqueue device -> host copies into fresh pinned buffers WITHOUT a synchronisation: the buffers hold the values once

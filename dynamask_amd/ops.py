@@ -1166,6 +1166,141 @@ def point_mlp_scatter(x, w_packeds, biases, w_logits, b_logits, labels, idx, ref
     return point_scatter(vals, idx, refined)
 
 
+# ------------------------------------------------ PointRefine: one SFM stage's point step (csrc/point_refine.hip, K24)
+# Exact fp32 in every precision mode: the bf16x3 mode does not reach these launches.
+def point_topk_select_supported(hw, num_points, n=1):
+    return bool(lib().dm_point_topk_select_supported(int(n), int(hw), int(num_points), 1))
+
+
+def point_topk_select(detail, num_points, use_sigmoid=True, out=None):
+    """The ``num_points`` cells of LARGEST key per row of the detail map ``detail`` [n, 1, S, S] (or [n, HW]), key
+    ``sigmoid(v)`` (``use_sigmoid``) or ``v``: ``topk`` of SFMStage.get_roi_rel_points_train -> int32 [n, num_points],
+    indices ascending; among equal keys at the cut the lower index is taken (dm_point_topk_select)."""
+    _chk(detail, 'detail')
+    n = detail.shape[0]
+    hw = _cells(detail)
+    P = int(num_points)
+    if out is None:
+        out = torch.empty((n, P), device=detail.device, dtype=torch.int32)
+    _chk(out, 'out', torch.int32)
+    assert tuple(out.shape) == (n, P)
+    check(lib().dm_point_topk_select(_p(detail), n, hw, P, 1 if use_sigmoid else 0, _p(out), _stream()),
+          'dm_point_topk_select')
+    return out
+
+
+def point_feat_gather(feat, rois, coarse, idx, spatial_scale, out=None):
+    """The point MLP's input [n, C + NC, P] of an SFM stage at the cells ``idx`` [n, P] of the S x S grid of ``coarse``
+    [n, NC, S, S] (``idx`` None: every cell, P = S * S): channels < C the point_sample of ``feat`` [B, C, H, W] (the image
+    of each RoI, ``rois[:, 0]``) at the cell centres mapped into the image (rel_roi_point_to_rel_img_point with
+    ``spatial_scale``), channels >= C the exact values of ``coarse`` at the cells (dm_point_feat_gather)."""
+    _chk(feat, 'feat')
+    _chk(rois, 'rois')
+    _chk(coarse, 'coarse')
+    B, C, H, W = feat.shape
+    n, NC, S = coarse.shape[0], coarse.shape[1], coarse.shape[2]
+    assert coarse.shape[3] == S and tuple(rois.shape) == (n, 5)
+    if idx is None:
+        P = S * S
+    else:
+        _chk(idx, 'idx', torch.int32)
+        assert idx.shape[0] == n
+        P = idx.shape[1]
+    if out is None:
+        out = torch.empty((n, C + NC, P), device=feat.device, dtype=torch.float32)
+    _chk(out, 'out')
+    assert tuple(out.shape) == (n, C + NC, P)
+    check(lib().dm_point_feat_gather(_p(feat), B, C, H, W, _p(rois), n, _p(coarse), NC, _p(idx), P, S, float(spatial_scale),
+                                     _p(out), _stream()), 'dm_point_feat_gather')
+    return out
+
+
+def point_scatter_rows(vals, idx, feat):
+    """feat[r, c].flatten()[idx[r, p]] = vals[r, c, p] in place (dm_point_scatter_rows)."""
+    _chk(vals, 'vals')
+    _chk(idx, 'idx', torch.int32)
+    _chk(feat, 'feat')
+    n, P = idx.shape
+    C = feat.shape[1]
+    assert vals.numel() == n * C * P and feat.shape[0] == n
+    check(lib().dm_point_scatter_rows(_p(vals), _p(idx), n, C, P, _p(feat), _cells(feat) // max(C, 1), _stream()),
+          'dm_point_scatter_rows')
+    return feat
+
+
+# The SFM stage's point MLP + scatter: 'fused' -- one launch (dm_point_refine_mlp); 'unfused' -- each layer a
+# dm_conv2d_fwd 1x1 on the points as a 1 x P image, then dm_point_scatter_rows (when every cell is selected the last
+# layer writes the stage features directly: the dense form).  DM_POINT_REFINE_MLP=fused / unfused forces one;
+# default (None): the per-shape choice of point_refine_mlp_form (DESIGN section 4.14).
+POINT_REFINE_MLP = [os.environ.get('DM_POINT_REFINE_MLP') or None]
+
+
+def point_refine_mlp_supported(n, C, NC, P, num_fcs, hw, has_idx=True):
+    return bool(lib().dm_point_refine_mlp_supported(int(n), int(P), int(C), int(NC), int(num_fcs), int(hw),
+                                                    1 if has_idx else 0))
+
+
+def point_refine_mlp_form(n, C, P, hw):
+    """The default form of an SFM stage's point MLP for n RoIs, C channels and P of hw cells."""
+    if POINT_REFINE_MLP[0] in ('fused', 'unfused'):
+        return POINT_REFINE_MLP[0]
+    # measured at 16 / 100 RoIs: at C = 256 (S = 14, every cell) the dense 1x1 sequence wins (0.075 / 0.19 ms against
+    # 0.125 / 0.29 ms fused), at C = 128 / 64 the fused launch does (0.26 / 0.16 ms against 0.28 / 0.18 ms at 100 RoIs).
+    # The choice does not depend on n, so a batch of images computes what each image alone does.
+    return 'unfused' if C >= 256 else 'fused'
+
+
+def point_refine_mlp(x, C, w_packeds, biases, idx, feat, form=None):
+    """SFMStage's point MLP (coarse_pred_each_layer) on the point features ``x`` [n, C + NC, P] (``point_feat_gather``):
+    relu(W_l [h; coarse] + b_l) per hidden layer, then fc_logits (no ReLU), ALL C rows stored into ``feat`` [n, C, S, S]
+    at the cells ``idx`` [n, P] (in place; ``idx`` None: every cell in order).  ``w_packeds`` / ``biases``: the hidden
+    layers then fc_logits, each ``pack_conv_weight`` of a [C, C + NC, 1, 1] weight.  ``form``: 'fused' (one launch),
+    'unfused' (the launch sequence) or None (``point_refine_mlp_form``)."""
+    _chk(x, 'x')
+    _chk(feat, 'feat')
+    n, CT, P = x.shape
+    NC = CT - C
+    k = len(w_packeds) - 1
+    assert k >= 1 and len(biases) == k + 1 and feat.shape[0] == n and feat.shape[1] == C
+    hw = _cells(feat) // C
+    if idx is not None:
+        _chk(idx, 'idx', torch.int32)
+        assert tuple(idx.shape) == (n, P)
+    else:
+        assert P == hw, 'without an index every cell is a point'
+    for w in w_packeds:
+        _chk(w, 'w_packed')
+        if conv_layout(w) != 'fp32':
+            raise ValueError('the point MLP reads the exact fp32 layout (pack_conv_weight(precision="fp32"))')
+        assert w.numel() == packed_floats(C, 1, [CT]), 'weights packed for another shape'
+    if form is None:
+        form = point_refine_mlp_form(n, C, P, hw)
+    if form == 'fused':
+        bias_arr = (ctypes.c_void_p * (k + 1))(*[0 if b is None else _chk(b, 'bias').data_ptr() for b in biases])
+        if hazard.ENABLED[0]:
+            hazard.note_ptr_array(bias_arr, [b for b in biases if b is not None])
+        check(lib().dm_point_refine_mlp(_p(x), n, P, C, NC, k, _ptr_array(w_packeds), bias_arr, _p(idx), 0, _p(feat), hw,
+                                        _stream()), 'dm_point_refine_mlp')
+        return feat
+    if form != 'unfused':
+        raise ValueError(f'point_refine_mlp: form {form!r} (fused / unfused)')
+    if n == 0:
+        return feat
+    # ping-pong between two [n, C + NC, 1, P] buffers that both hold the coarse channels
+    bufs = [x.view(n, CT, 1, P), x.clone().view(n, CT, 1, P), None]
+    bufs[2] = bufs[1].clone() if k > 1 else None
+    cur = bufs[0]
+    for i in range(k):
+        dst = bufs[1 + (i % 2)]
+        conv2d([cur], w_packeds[i], biases[i], C, 1, relu=True, out=dst, out_ch_offset=0)
+        cur = dst
+    if idx is None:                     # dense: the points are the cells in order, fc_logits writes the features
+        conv2d([cur], w_packeds[k], biases[k], C, 1, out=feat.view(n, C, 1, P))
+        return feat
+    vals = conv2d([cur], w_packeds[k], biases[k], C, 1)
+    return point_scatter_rows(vals, idx, feat)
+
+
 # ------------------------------------------------ Mask Scoring R-CNN: the IoU head's launches (csrc/conv_strided.hip)
 # Exact fp32 in every precision mode: the bf16x3 mode does not reach these launches.
 def conv3x3_s2_supported(x, cout, splits=0):

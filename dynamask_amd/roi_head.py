@@ -1168,6 +1168,50 @@ class PointRendRoIHead(StandardRoIHead):
 
 
 @HEADS.register_module()
+class PointRefineRoIHead(StandardRoIHead):
+    """``PointRefineRoIHead`` -- mmdet/models/roi_heads/point_refine_head.py, inference: the RoI head of
+    configs/point_refine, whose mask head is ``PointRefineMaskHead``.  The bbox branch, ``simple_test``,
+    ``batch_simple_test``, ``aug_test`` and the mask-test template are the base's; the head supplies ``_mask_forward``
+    (point_refine_head.py:86-92) and, as ``_mask_logits``, the merged logits of the last stage (the boundary-aware merge
+    from stage 1, :114-127: ``merge_stage_preds``).  The semantic 3x3 convolutions and the stages' semantic 1x1s run once
+    per call on the whole stride-4 map of every image; each RoI's fine point features come from its own image
+    (``rois[:, 0]``), which is the reference's per-image concatenation whenever the RoIs are grouped by image, as
+    ``bbox2roi`` groups them.  ``aug_test`` is the project's definition: the reference's ``aug_test_mask`` calls
+    ``_mask_forward(x, rois)`` without the labels and fails.  ``BaseRoIHead`` builds ``mask_predictor`` /
+    ``semantic_roi_extractor`` for every RoI head (Quirk Q4): the ``state_dict`` keys are the reference's.  Training
+    (the config's loss exists nowhere in the reference, Quirk Q15) and HIP-graph capture raise."""
+
+    merge_stage_preds = staticmethod(merge_stage_preds)
+
+    def _mask_forward(self, x, rois, roi_labels, cfg=None, semantic_pred=True, form=None):
+        """point_refine_head.py:86-92 -> dict(stage_instance_preds, stage_detail_preds, semantic_pred)."""
+        ext = self.mask_roi_extractor
+        rois = rois.contiguous()
+        with torch.no_grad():
+            ins_feats = ext(x[:ext.num_inputs], rois)
+            ips, dps, sem_pred = self.mask_head(ins_feats, x[0].contiguous(), rois, roi_labels,
+                                                self.test_cfg if cfg is None else cfg, semantic_pred=semantic_pred,
+                                                form=form)
+        return dict(stage_instance_preds=ips, stage_detail_preds=dps, semantic_pred=sem_pred)
+
+    def _mask_logits(self, x, mask_rois, det_labels):
+        """The merged logits of the last stage [n, 1, S, S]: stage k's (k >= 1) merged into stage k + 1's where the
+        coarser one is not on a boundary (point_refine_head.py:114-127), in place."""
+        res = self._mask_forward(x, mask_rois, det_labels, semantic_pred=False)
+        return merge_stage_preds(res['stage_instance_preds'])
+
+    def _mask_logits_size(self):
+        return 1, self.mask_head.stage_sup_size[-1]
+
+    def _segm_num_classes(self):
+        return self.mask_head.stage_num_classes[0]
+
+    def forward_train(self, x, img_metas, proposal_list, gt_bboxes, gt_labels, gt_bboxes_ignore=None, gt_masks=None):
+        raise NotImplementedError('PointRefineRoIHead.forward_train: the config\'s PointRefineCrossEntropyLoss is '
+                                  'registered nowhere in the reference, which cannot build or train this head (Quirk Q15)')
+
+
+@HEADS.register_module()
 class MaskScoringRoIHead(StandardRoIHead):
     """``MaskScoringRoIHead`` -- mmdet/models/roi_heads/mask_scoring_roi_head.py, inference: the RoI head of configs/ms_rcnn,
     a ``StandardRoIHead`` over ``FCNMaskHead`` plus ``mask_iou_head`` (``MaskIoUHead``).  ``simple_test_mask`` returns

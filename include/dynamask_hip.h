@@ -57,7 +57,8 @@ typedef void* dm_stream_t; /* hipStream_t */
 const char* dm_error_string(int code);
 /* ABI version: bumped whenever a signature or the meaning of an argument changes (8: flag bit 3 of dm_conv2d_fwd; 9: RoI assignment / bbox training entry points; 10: dm_detail_target takes the fuse weights from device memory; 11: FCNMaskHead upsample backward; 12: dm_fc_fwd takes a scratch slab, deterministic split-K; 13: dm_deform_coord_grad / dm_deform_col2im, dm_conv2d_fwd_masked, dm_scale, dm_polygon_mask_targets, dm_ignore_columns, dm_upsample2x_bilinear_bwd overwrites; 14: dm_random_sample, dm_bn_relu_maxpool_argmax, the *_fx deterministic accumulators + dm_fx_to_float, dm_mask_loss_fwd_bwd takes a scratch, dm_conv2d_wgrad takes the bias gradient, dm_conv_pack_weight_batch, dm_mask_loss_stage; 15: dm_class_logits_up2x_fwd; 16: dm_conv2d_wgrad_slab / dm_conv2d_wgrad_scratch_floats; 17: dm_class_logits_bwd_slab / dm_class_logits_bwd_scratch_floats; 18: dm_reload_env_knobs, dm_roi_align_fwd_ws / dm_roi_align_workspace_bytes, dm_conv_pack_weight_split / dm_conv_packed_floats_split and flag bits 4, 5 of dm_conv2d_fwd; 19: dm_dcn_bwd_data_fused and its pack; 20: dm_conv2d_fwd_ws / dm_conv2d_splitk_floats; 21: dm_deform_conv_fwd_ws / dm_deform_conv_splitk_floats; 22: the bf16-split layouts (dm_conv_pack_weight_split, dm_conv_packed_floats_split, flag bits 4 / 5 of dm_conv2d_fwd) and the one-kernel DCN data gradient (dm_dcn_bwd_*) REMOVED -- measured, never the parity path, see docs/HISTORY.md; 23: dm_bn_stats takes mean_shift, dm_roi_align_bwd takes the gather form for 16 < P <= 64; 24: dm_build_info; 25: dm_boundary_merge_chain, dm_stage_head_fwd; 26: dm_conv1x1_group_fwd; 27: dm_deform_conv_tout_fwd / dm_deform_conv_tout_supported; 28: the opt-in bf16x3 mode -- dm_conv_pack_weight_bf16x3 / dm_conv_packed_floats_bf16x3 and flag bit 4 of dm_conv2d_fwd, dm_conv2d_fwd_ws and dm_conv1x1_group_fwd; dm_deconv_pack_weight_bf16x3 and flag bit 4 of dm_deconv2x2_fwd).  Entry points ADDED without a signature or meaning change leave the number as it is (the loader resolves every symbol of _lib.SIGNATURES by name, so an older library fails at load): the multi-image post-processing dm_nms_mask_segmented / dm_nms_reduce_segmented, dm_paste_masks_multi, dm_paste_rle_multi / dm_rle_multi_scratch_ints; the test-time augmentation dm_bbox_mapping_multi, dm_merge_aug_bboxes, dm_merge_aug_masks; RefineMask's dilated / any-width 3x3 convolutions and the sigmoid of its semantic map (section K21); PointRend's point
  * selection, point gather, point MLP and scatter (section K22); Mask Scoring R-CNN's stride-2 3x3 convolution, IoU-head
- * input and mask scores (section K23). */
+ * input and mask scores (section K23); PointRefine's descending point selection, point-feature gather, point MLP and
+ * multi-row scatter (section K24). */
 int dm_abi_version(void);
 /* "libdynamask_hip abi=N arch=gfx950 compiler=<clang version> flags=<the product-wide flags of dynamask_amd/build.py>"
  * (static storage).  The library must be compiled WITHOUT packed fp32 instructions (flag "-packed-fp32-ops", see
@@ -891,6 +892,44 @@ int dm_mask_iou_input(const float* mask_pred, int n, int C, int H, int W, const 
  * DM_ERR_UNSUPPORTED unless n >= 0, NC >= 1 and D >= 1.  n == 0 enqueues nothing. */
 int dm_mask_iou_scores(const float* mask_iou_pred, int n, int NC, const long long* labels, const float* dets, int D,
                        float* out, dm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * K24  PointRefine inference: one SFMStage of mmdet/models/roi_heads/mask_heads/mask_point_refine.py (:95-132) on the
+ * stage features f [n, C, S, S], csrc/point_refine.hip.  Exact fp32 in every precision mode.  A NULL idx means every
+ * cell in order (P == S * S): the selection is skipped, and the MLP is per point, so the order does not matter.
+ *
+ * dm_point_topk_select: map [n, HW] (the label row of the detail logits) -> idx [n, P] int32: per row the P cells of
+ * LARGEST key (get_roi_rel_points_train's topk), key = 1 / (1 + expf(-v)) (mode 1, mask_use_sigmoid; the paste kernels'
+ * sigmoid, so saturated cells tie at 1.0f) or v (mode 0); indices in ascending order; among cells of equal key at the
+ * cut, the lower flat index is taken.  dm_point_topk_select_supported: 1 exactly when mode is 0 or 1 and
+ * dm_point_select_supported(n, HW, P).  n == 0 enqueues nothing.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int dm_point_topk_select_supported(int n, int HW, int P, int mode);
+int dm_point_topk_select(const float* map, int n, int HW, int P, int mode, int* idx, dm_stream_t stream);
+/* dm_point_feat_gather: the point MLP's input out [n, C + NC, P]: for the cell c = idx[r, p] (c = p when idx is NULL)
+ * of the S x S grid, out[r, ch, p] for ch < C is dm_point_gather_fwd's fine channel (same expressions, equal within
+ * rounding: point_sample of feat[rois[r, 0]]
+ * [B, C, H, W] at rel_roi_point_to_rel_img_point of the cell centre, spatial_scale), and out[r, C + k, p] =
+ * coarse[r, k, c] exactly (torch.gather of the [n, NC, S * S] logit maps).  dm_point_feat_gather_supported: 1 exactly when
+ * B >= 1, C >= 8 and NC >= 8 are multiples of 8, (C + NC) / 8 <= 65535, H, W, S >= 1, S * S < 2^31, n >= 0,
+ * 1 <= P <= S * S (P == S * S without idx) and ceil(n * P / 256) < 2^31. */
+int dm_point_feat_gather_supported(int B, int C, int H, int W, int n, int NC, int P, int S, int has_idx);
+int dm_point_feat_gather(const float* feat, int B, int C, int H, int W, const float* rois, int n, const float* coarse,
+                         int NC, const int* idx, int P, int S, float spatial_scale, float* out, dm_stream_t stream);
+/* dm_point_refine_mlp: SFMStage's point MLP (coarse_pred_each_layer) on x [n, C + NC, P]: h_0 = x[:, :C],
+ * h_{l+1} = relu(W_l [h_l; x[:, C:]] + b_l) for l < num_fcs, then v = W_L [h; x[:, C:]] + b_L (fc_logits, no ReLU) and
+ * feat[r, :, idx[r, p]] = v[:, p] for all C rows.  w_packed[0 .. num_fcs]: dm_conv_pack_weight(ksize 1, Cin = C + NC, one
+ * source) of the [C, C + NC] weights, fc_logits last; bias[0 .. num_fcs] (the host array, or an entry, may be NULL);
+ * feat [n, C, HW].  Exact fp32 (v_mfma_f32_32x32x2_f32).  flags: bit 3 accepted and ignored; bit 4 (the bf16x3 mode)
+ * returns DM_ERR_UNSUPPORTED; any other bit DM_ERR_INVALID_ARG.  dm_point_refine_mlp_supported: 1 exactly when n >= 0,
+ * 1 <= P <= HW (P == HW without idx), C is 64, 128 or 256, 8 <= NC <= 160 with (C + NC) % 8 == 0,
+ * 1 <= num_fcs <= 4 and n * ceil(P / 64) < 2^31. */
+int dm_point_refine_mlp_supported(int n, int P, int C, int NC, int num_fcs, int HW, int has_idx);
+int dm_point_refine_mlp(const float* x, int n, int P, int C, int NC, int num_fcs, const float* const* w_packed,
+                        const float* const* bias, const int* idx, int flags, float* feat, int HW, dm_stream_t stream);
+/* map[r, c, idx[r, p]] = vals[r, c, p] for r < n, c < C, p < P (the unfused sequence's scatter); vals [n, C, P], idx [n, P]
+ * in [0, HW), map [n, C, HW].  DM_ERR_UNSUPPORTED unless n >= 0, C >= 1, 1 <= P <= HW and ceil(n * C * P / 256) < 2^31. */
+int dm_point_scatter_rows(const float* vals, const int* idx, int n, int C, int P, float* map, int HW, dm_stream_t stream);
 
 #ifdef __cplusplus
 }
