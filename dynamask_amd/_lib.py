@@ -116,6 +116,13 @@ SIGNATURES = {
     'dm_point_refine_mlp_supported': ([_c_int] * 7, _c_int),
     'dm_point_refine_mlp': ([_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _c_int, _vp, _c_int, _vp], _c_int),
     'dm_point_scatter_rows': ([_vp, _vp, _c_int, _c_int, _c_int, _vp, _c_int, _vp], _c_int),
+    'dm_conv2d_group_splits': ([_c_int] * 7 + [ctypes.c_longlong], _c_int),
+    'dm_conv2d_group_splitk_floats': ([_c_int] * 7, ctypes.c_longlong),
+    'dm_conv2d_group_fwd': ([_c_int, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _vp, _vp,
+                             ctypes.c_longlong, _vp], _c_int),
+    'dm_deconv2x2_group_fwd': ([_c_int, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _c_int, _vp, _vp], _c_int),
+    'dm_cascade_refine': ([_vp, _vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _c_float, _vp, _c_int, _vp, _c_int, _vp, _vp],
+                          _c_int),
     'dm_fc_scratch_floats': ([_c_int, _c_int, _c_int], ctypes.c_longlong),
     'dm_fc_fwd': ([_vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp], _c_int),
     'dm_sgd_momentum_step': ([_vp, _vp, _vp, ctypes.c_longlong, _c_float, _c_float, _c_float, _c_float, _c_int, _vp], _c_int),

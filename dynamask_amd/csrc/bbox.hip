@@ -25,6 +25,39 @@ struct DecodeArgs {
   float* bboxes;          // [N, 4 * NB]
 };
 
+// delta2bbox of one box (delta_xywh_bbox_coder.py:165-204): the decode of bbox_decode_kernel and cascade_refine_kernel,
+// one device function so that a cascade stage's boxes have the bits of dm_bbox_decode's.  The fused multiply-adds are
+// spelled out and nothing else is contracted: left to the compiler, the pairs it fuses depend on the code around the call
+// (bbox_decode_kernel computes the centre once per row, outside its loop, and fuses pw * dx into the centre; inlined in
+// a kernel without that loop, (rx1 + rx2) * 0.5f was fused instead).  These are the operations bbox_decode_kernel has
+// always compiled to.
+__device__ __forceinline__ void delta2bbox_one(float rx1, float ry1, float rx2, float ry2, const float* __restrict__ d,
+                                               const float (&mean)[4], const float (&std)[4], float max_ratio, float& x1,
+                                               float& y1, float& x2, float& y2) {
+#pragma clang fp contract(off)
+  const float dx = __builtin_fmaf(d[0], std[0], mean[0]);
+  const float dy = __builtin_fmaf(d[1], std[1], mean[1]);
+  float dw = __builtin_fmaf(d[2], std[2], mean[2]);
+  float dh = __builtin_fmaf(d[3], std[3], mean[3]);
+  dw = fminf(fmaxf(dw, -max_ratio), max_ratio);
+  dh = fminf(fmaxf(dh, -max_ratio), max_ratio);
+  const float px = (rx1 + rx2) * 0.5f, py = (ry1 + ry2) * 0.5f;
+  const float pw = rx2 - rx1, ph = ry2 - ry1;
+  const float gw = pw * expf(dw), gh = ph * expf(dh);
+  const float gx = __builtin_fmaf(pw, dx, px), gy = __builtin_fmaf(ph, dy, py);
+  x1 = __builtin_fmaf(-0.5f, gw, gx);
+  y1 = __builtin_fmaf(-0.5f, gh, gy);
+  x2 = __builtin_fmaf(0.5f, gw, gx);
+  y2 = __builtin_fmaf(0.5f, gh, gy);
+}
+
+__device__ __forceinline__ void clip_box(float& x1, float& y1, float& x2, float& y2, float clip_w, float clip_h) {
+  x1 = fminf(fmaxf(x1, 0.f), clip_w);
+  x2 = fminf(fmaxf(x2, 0.f), clip_w);
+  y1 = fminf(fmaxf(y1, 0.f), clip_h);
+  y2 = fminf(fmaxf(y2, 0.f), clip_h);
+}
+
 __global__ __launch_bounds__(128) void bbox_decode_kernel(DecodeArgs a) {
   __shared__ float red[2];
   const int i = blockIdx.x;
@@ -52,29 +85,9 @@ __global__ __launch_bounds__(128) void bbox_decode_kernel(DecodeArgs a) {
   const float rx1 = r[0], ry1 = r[1], rx2 = r[2], ry2 = r[3];
   for (int c = t; c < a.NB; c += 128) {
     float x1 = rx1, y1 = ry1, x2 = rx2, y2 = ry2;
-    if (a.bbox_pred) {
-      const float* d = a.bbox_pred + ((size_t)i * a.NB + c) * 4;
-      const float dx = d[0] * a.std[0] + a.mean[0];
-      const float dy = d[1] * a.std[1] + a.mean[1];
-      float dw = d[2] * a.std[2] + a.mean[2];
-      float dh = d[3] * a.std[3] + a.mean[3];
-      dw = fminf(fmaxf(dw, -a.max_ratio), a.max_ratio);
-      dh = fminf(fmaxf(dh, -a.max_ratio), a.max_ratio);
-      const float px = (rx1 + rx2) * 0.5f, py = (ry1 + ry2) * 0.5f;
-      const float pw = rx2 - rx1, ph = ry2 - ry1;
-      const float gw = pw * expf(dw), gh = ph * expf(dh);
-      const float gx = px + pw * dx, gy = py + ph * dy;
-      x1 = gx - gw * 0.5f;
-      y1 = gy - gh * 0.5f;
-      x2 = gx + gw * 0.5f;
-      y2 = gy + gh * 0.5f;
-    }
-    if (a.clip_w > 0.f) {
-      x1 = fminf(fmaxf(x1, 0.f), a.clip_w);
-      x2 = fminf(fmaxf(x2, 0.f), a.clip_w);
-      y1 = fminf(fmaxf(y1, 0.f), a.clip_h);
-      y2 = fminf(fmaxf(y2, 0.f), a.clip_h);
-    }
+    if (a.bbox_pred)
+      delta2bbox_one(rx1, ry1, rx2, ry2, a.bbox_pred + ((size_t)i * a.NB + c) * 4, a.mean, a.std, a.max_ratio, x1, y1, x2, y2);
+    if (a.clip_w > 0.f) clip_box(x1, y1, x2, y2, a.clip_w, a.clip_h);
     float* o = a.bboxes + ((size_t)i * a.NB + c) * 4;
     o[0] = x1 * a.inv_sx;
     o[1] = y1 * a.inv_sy;
@@ -254,6 +267,68 @@ __global__ __launch_bounds__(256) void merge_aug_bboxes_kernel(const long long* 
   }
 }
 
+// ----- Cascade R-CNN stage step (CascadeRoIHead.simple_test, cascade_roi_head.py:307-315) -----
+// One wave per RoI row i of stage s:
+//   sum[i, :]  = (s == 0 ? 0 : sum[i, :]) + cls[i, :]       (sum(ms_scores): ((0 + s0) + s1) + s2 in fp32)
+//   label      = cls[i, :NC].argmax()                        (the first maximum; NaN counts as the maximum, as torch's)
+//   out[i, :]  = [rois[i, 0], delta2bbox(rois[i, 1:], pred[i, label | 0]) clipped to img_tab[rois[i, 0]]]
+// (regress_by_class, bbox_head.py:306-334).  out == NULL: the score sum only (the last stage).
+struct CascadeArgs {
+  const float* rois;       // [n, 5]
+  const float* cls;        // [n, NC + 1]
+  const float* pred;       // [n, 4] (class agnostic) or [n, 4 * NC]
+  int n, NC, agnostic;
+  float mean[4], std[4];
+  float max_ratio;
+  const float* img_tab;    // [B, 2] (h, w) per image
+  int B;
+  float* sum;              // [n, NC + 1] or null
+  int first;
+  float* out;              // [n, 5] or null
+};
+
+__device__ __forceinline__ bool argmax_better(float v, int i, float bv, int bi) {
+  const bool vn = v != v, bn = bv != bv;
+  if (vn || bn) return vn && (!bn || i < bi);
+  return v > bv || (v == bv && i < bi);
+}
+
+__global__ __launch_bounds__(64) void cascade_refine_kernel(CascadeArgs a) {
+  const int i = blockIdx.x;
+  const int t = threadIdx.x;
+  const float* s = a.cls + (size_t)i * (a.NC + 1);
+  if (a.sum) {
+    float* o = a.sum + (size_t)i * (a.NC + 1);
+    for (int c = t; c <= a.NC; c += 64) o[c] = (a.first ? 0.f : o[c]) + s[c];
+  }
+  if (!a.out) return;
+  float bv = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int c = t; c < a.NC; c += 64) {
+    const float v = s[c];
+    if (argmax_better(v, c, bv, bi)) { bv = v; bi = c; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(bv, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (argmax_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+  }
+  if (t != 0) return;
+  const float* r = a.rois + (size_t)i * 5;
+  const float b = r[0];
+  const float rx1 = r[1], ry1 = r[2], rx2 = r[3], ry2 = r[4];
+  const int label = bi < a.NC ? bi : 0;
+  const float* d = a.pred + (size_t)i * (a.agnostic ? 4 : 4 * a.NC) + (a.agnostic ? 0 : 4 * label);
+  float x1, y1, x2, y2;
+  delta2bbox_one(rx1, ry1, rx2, ry2, d, a.mean, a.std, a.max_ratio, x1, y1, x2, y2);
+  const int img = min(max((int)b, 0), a.B - 1);
+  const float ch = a.img_tab[2 * img], cw = a.img_tab[2 * img + 1];
+  if (cw > 0.f) clip_box(x1, y1, x2, y2, cw, ch);
+  float* o = a.out + (size_t)i * 5;
+  o[0] = b; o[1] = x1; o[2] = y1; o[3] = x2; o[4] = y2;
+}
+
 }  // namespace
 
 extern "C" int dm_bbox_decode(const float* rois, int roi_stride, int roi_x0, const float* cls_score,
@@ -365,5 +440,30 @@ extern "C" int dm_merge_aug_bboxes(const long long* ptr_tab, const float* view_t
     return DM_ERR_INVALID_ARG;
   DM_LAUNCH(merge_aug_bboxes_kernel, dim3(dm_ceil_div(box_cols + score_cols, 256), n), dim3(256), 0, (hipStream_t)stream,
             ptr_tab, view_tab, V, n, box_cols, score_cols, out_boxes, out_scores);
+  return dm_check_launch();
+}
+
+extern "C" int dm_cascade_refine(const float* rois, const float* cls_score, const float* bbox_pred, int n, int num_classes,
+                                 int class_agnostic, const float* means, const float* stds, float wh_ratio_clip,
+                                 const float* img_shapes, int num_images, float* score_sum, int first_stage, float* out_rois,
+                                 dm_stream_t stream) {
+  if (n < 0 || num_classes <= 0) return DM_ERR_INVALID_ARG;
+  if (!score_sum && !out_rois) return DM_ERR_INVALID_ARG;
+  if (out_rois && (!rois || !bbox_pred || !img_shapes || num_images < 1 || !means || !stds || !(wh_ratio_clip > 0.f)))
+    return DM_ERR_INVALID_ARG;
+  if (out_rois && out_rois == rois) return DM_ERR_INVALID_ARG;
+  if (n == 0) return DM_OK;
+  if (!cls_score) return DM_ERR_INVALID_ARG;
+  CascadeArgs a;
+  a.rois = rois; a.cls = cls_score; a.pred = bbox_pred; a.n = n; a.NC = num_classes; a.agnostic = class_agnostic ? 1 : 0;
+  for (int k = 0; k < 4; ++k) {
+    a.mean[k] = means ? means[k] : 0.f;
+    a.std[k] = stds ? stds[k] : 1.f;
+  }
+  a.max_ratio = out_rois ? fabsf(logf(wh_ratio_clip)) : 0.f;
+  a.img_tab = img_shapes; a.B = num_images;
+  a.sum = score_sum; a.first = first_stage ? 1 : 0;
+  a.out = out_rois;
+  DM_LAUNCH(cascade_refine_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, a);
   return dm_check_launch();
 }

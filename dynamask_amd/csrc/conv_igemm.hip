@@ -705,12 +705,15 @@ struct ConvGroup {
   ConvArgs a[3];
   int end[3];
 };
+// (The cascade's stage-grouped 3x3 / 1x1 / deconv launches, dm_conv2d_group_fwd / dm_deconv2x2_group_fwd, run the same
+// kernel: blockIdx.y is the K split of a grouped split-K launch, as in conv_igemm_kernel.)
 template <int KS, int WGM, int WGN, int WM, int WN, int CK, int MAXPOS, int PREC = 0>
-__global__ __launch_bounds__(WGM* WGN * 64, (KS == 1 && CK == 16) ? 3 : 1) void conv_igemm_group_kernel(ConvGroup g) {
-  const int b = (int)blockIdx.x;
-  if (b < g.end[0]) conv_igemm_body<KS, WGM, WGN, WM, WN, CK, MAXPOS, 0, PREC>(g.a[0], b, g.end[0], 0);
-  else if (b < g.end[1]) conv_igemm_body<KS, WGM, WGN, WM, WN, CK, MAXPOS, 0, PREC>(g.a[1], b - g.end[0], g.end[1] - g.end[0], 0);
-  else conv_igemm_body<KS, WGM, WGN, WM, WN, CK, MAXPOS, 0, PREC>(g.a[2], b - g.end[1], g.end[2] - g.end[1], 0);
+// (The 128 x 128 builds are held to two waves per SIMD here: at three they spill, 5 dwords for the 3x3 and 3 for the 1x1.)
+__global__ __launch_bounds__(WGM* WGN * 64, (KS == 1 && CK == 16 && WM == 1) ? 3 : (WGM == 2 && WGN == 2 && WM == 2 && WN == 2) ? 2 : 1) void conv_igemm_group_kernel(ConvGroup g) {
+  const int b = (int)blockIdx.x, by = (int)blockIdx.y;
+  if (b < g.end[0]) conv_igemm_body<KS, WGM, WGN, WM, WN, CK, MAXPOS, 0, PREC>(g.a[0], b, g.end[0], by);
+  else if (b < g.end[1]) conv_igemm_body<KS, WGM, WGN, WM, WN, CK, MAXPOS, 0, PREC>(g.a[1], b - g.end[0], g.end[1] - g.end[0], by);
+  else conv_igemm_body<KS, WGM, WGN, WM, WN, CK, MAXPOS, 0, PREC>(g.a[2], b - g.end[1], g.end[2] - g.end[1], by);
 }
 
 // Packed weight layout [tap][KQ][CoutP][4]: KQ quads = sum over sources of
@@ -846,10 +849,9 @@ int packed_words_bf16x3(int nsrc, const int* src_c) {
 // (round 5: four outputs per thread and 32-bit index arithmetic where HW % 4 == 0 and everything is 16-byte aligned --
 // one thread per output with two 64-bit divisions took 27 us for the 2.5 M outputs of a 50-RoI convolution, 1.5 TB/s.)
 template <bool V4>
-__global__ __launch_bounds__(256) void conv_splitk_reduce_kernel(const float* __restrict__ ws, int splits, long long stride, int NB,
-                                                                int Cout, int HW, const float* __restrict__ bias, int flags,
-                                                                float* __restrict__ out, int out_ch_total, int out_ch_offset,
-                                                                const float* __restrict__ mask) {
+__device__ __forceinline__ void splitk_reduce_body(const float* __restrict__ ws, int splits, long long stride, int NB, int Cout,
+                                                   int HW, const float* __restrict__ bias, int flags, float* __restrict__ out,
+                                                   int out_ch_total, int out_ch_offset, const float* __restrict__ mask) {
   if (V4) {
     // total = NB * Cout * HW < 2^31 (launcher); a quad never straddles a channel plane (HW % 4 == 0)
     const unsigned total4 = (unsigned)(((long long)NB * Cout * HW) >> 2), hw4 = (unsigned)HW >> 2;
@@ -896,6 +898,28 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_kernel(const float* __
     if (mask) v = (mask[o] > 0.f) ? v : 0.f;
     out[o] = v;
   }
+}
+
+template <bool V4>
+__global__ __launch_bounds__(256) void conv_splitk_reduce_kernel(const float* __restrict__ ws, int splits, long long stride, int NB,
+                                                                int Cout, int HW, const float* __restrict__ bias, int flags,
+                                                                float* __restrict__ out, int out_ch_total, int out_ch_offset,
+                                                                const float* __restrict__ mask) {
+  splitk_reduce_body<V4>(ws, splits, stride, NB, Cout, HW, bias, flags, out, out_ch_total, out_ch_offset, mask);
+}
+
+// The reduction of a grouped split-K launch: blockIdx.y = problem, whose splits lie at ws[p] (the same arithmetic as
+// conv_splitk_reduce_kernel; bias and ReLU only, outputs [NB][Cout][HW] of their own).
+struct ReduceGroup {
+  const float* ws[3];
+  const float* bias[3];
+  float* out[3];
+};
+template <bool V4>
+__global__ __launch_bounds__(256) void conv_splitk_reduce_group_kernel(ReduceGroup r, int splits, long long stride, int NB,
+                                                                      int Cout, int HW, int flags) {
+  const int p = (int)blockIdx.y;
+  splitk_reduce_body<V4>(r.ws[p], splits, stride, NB, Cout, HW, r.bias[p], flags, r.out[p], Cout, 0, nullptr);
 }
 
 // How many K splits pay for a launch that leaves most of the chip idle (1: none).  A launch of one round walks its chunks
@@ -999,6 +1023,111 @@ int launch_conv(ConvArgs& a, hipStream_t st) {
   a.Wp = 0;
   a.plane = TN;
   return launch_conv_mp<KS, WGM, WGN, WM, WN, CK, 1, TAIL, PREC>(a, st);
+}
+
+// One grouped launch (dm_conv2d_group_fwd / dm_deconv2x2_group_fwd) of the problems g.a[0 .. count): the per-problem
+// geometry launch_conv / launch_conv_mp derive, each problem in its own range of the grid, and -- S >= 2, shuffle == 0 --
+// the K loop split over S workgroups per tile exactly as launch_conv_mp splits a lone launch (kchunks = ceil(chunks / S)
+// chunks of CK channels each), with problem p's bare sums at ws + p * S * per, reduced by ONE conv_splitk_reduce_group_kernel.
+template <int KS, int WGM, int WGN, int WM, int WN, int CK, int MAXPOS>
+int launch_group_mp(ConvGroup& g, int count, int S, float* ws, hipStream_t st) {
+  constexpr int TN = WGN * WN * 32;
+  constexpr int TM = WGM * WM * 32;
+  const ConvArgs& a0 = g.a[0];
+  const size_t lds_bytes = 16 * ((size_t)KS * KS * (CK / 4) * TM + (size_t)(CK / 4) * a0.plane);
+  if (lds_bytes > 64 * 1024) return DM_ERR_UNSUPPORTED;
+  int chunks = dm_ceil_div(a0.src_c[0], CK);
+  const long long per = (long long)a0.NB * a0.Cout * a0.HW;
+  int total = 0;
+  for (int i = 0; i < 3; ++i) {
+    ConvArgs& a = g.a[i];
+    a.ksplit = 1;
+    if (S >= 2) {
+      a.kchunks = dm_ceil_div(chunks, S);
+      a.ksplit = dm_ceil_div(chunks, a.kchunks);
+      a.ws = ws + (size_t)min(i, count - 1) * S * per;
+      a.ws_stride = per;
+      a.ws_floats = (long long)S * per;
+    }
+    if (i < count) total += a.MT * dm_ceil_div(a.Q, TN);
+    g.end[i] = total;
+  }
+  const int splits = g.a[0].ksplit;
+  DM_LAUNCH((conv_igemm_group_kernel<KS, WGM, WGN, WM, WN, CK, MAXPOS>), dim3((unsigned)total, (unsigned)splits), dim3(WGM * WGN * 64),
+            lds_bytes, st, g);
+  int rc = dm_check_launch();
+  if (rc != DM_OK || splits < 2) return rc;
+  ReduceGroup r;
+  for (int i = 0; i < 3; ++i) {
+    const ConvArgs& a = g.a[min(i, count - 1)];
+    r.ws[i] = a.ws; r.bias[i] = a.bias; r.out[i] = a.out;
+  }
+  bool v4 = (a0.HW & 3) == 0 && (per & 3) == 0 && per < 0x7fffffffLL && (((uintptr_t)ws) & 15) == 0 && (S * per & 3) == 0;
+  for (int i = 0; i < count; ++i) v4 = v4 && (((uintptr_t)g.a[i].out) & 15) == 0;
+  const int flags = a0.relu & 1;
+  if (v4)
+    DM_LAUNCH(conv_splitk_reduce_group_kernel<true>, dim3((unsigned)min((long long)4096, (per / 4 + 255) / 256), (unsigned)count),
+              dim3(256), 0, st, r, splits, per, a0.NB, a0.Cout, a0.HW, flags);
+  else
+    DM_LAUNCH(conv_splitk_reduce_group_kernel<false>, dim3((unsigned)min((long long)4096, (per + 255) / 256), (unsigned)count),
+              dim3(256), 0, st, r, splits, per, a0.NB, a0.Cout, a0.HW, flags);
+  return dm_check_launch();
+}
+
+// launch_conv's plane geometry for every problem, then launch_group_mp with the MAXPOS build the plane needs
+template <int KS, int WGM, int WGN, int WM, int WN, int CK>
+int launch_group(ConvGroup& g, int count, int S, float* ws, hipStream_t st) {
+  constexpr int TM = WGM * WM * 32;
+  constexpr int TN = WGN * WN * 32;
+  constexpr int NT = WGM * WGN * 64;
+  for (int i = 0; i < 3; ++i) {
+    ConvArgs& a = g.a[i];
+    a.MT = dm_ceil_div(a.CoutP, TM);
+    if (KS == 3) {
+      a.Wp = a.W + 2;
+      const int nsegmax = dm_ceil_div(TN - 1, a.HW) + 1;
+      a.plane = (dm_ceil_div(TN - 1, a.W) + 1 + 2 * nsegmax) * a.Wp;
+    } else {
+      a.Wp = 0;
+      a.plane = TN;
+    }
+  }
+  const int plane = g.a[0].plane;
+  if constexpr (KS == 1) {
+    return launch_group_mp<KS, WGM, WGN, WM, WN, CK, 1>(g, count, S, ws, st);
+  } else {
+    if (plane <= NT) return launch_group_mp<KS, WGM, WGN, WM, WN, CK, 1>(g, count, S, ws, st);
+    if (plane <= 2 * NT) return launch_group_mp<KS, WGM, WGN, WM, WN, CK, 2>(g, count, S, ws, st);
+    if (plane <= 4 * NT) return launch_group_mp<KS, WGM, WGN, WM, WN, CK, 4>(g, count, S, ws, st);
+    return DM_ERR_UNSUPPORTED;
+  }
+}
+
+// The K splits of a grouped 3x3 launch (1: none) for a workspace of ws_floats: the decision conv2d_launch / launch_conv_mp
+// make for ONE problem of this shape, taken on the grouped workgroup count -- a grouped launch fills more of the chip and
+// splits less.  The cost model is the lone launch's (per-problem output size), so a lone dm_conv2d_fwd_ws given S
+// problem-sized workspaces picks the same S (its Smax is then S, and S is the first maximum of the model below any larger
+// Smax).  1x1 problems never split here.
+int group_split_choice(int count, int NB, int H, int W, int Cin, int Cout, int ksize, long long ws_floats) {
+  if (ksize != 3 || NB <= 0 || ws_floats <= 0) return 1;
+  const long long per = (long long)NB * Cout * H * W;
+  const long long Q = (long long)NB * H * W;
+  const int chunks = dm_ceil_div(Cin, 8);
+  const int cus = dm_num_cus();
+  long long wgs, slots;
+  if (Cout > 64) {
+    slots = 2LL * cus;        // (the grouped 128 x 128 build runs two workgroups per CU: conv_igemm_group_kernel's bounds)
+    wgs = (long long)count * dm_ceil_div((Cout + 31) / 32 * 32, 128) * dm_ceil_div(Q, 128);
+    if (wgs >= slots) return 1;
+  } else {
+    slots = 3LL * cus;
+    wgs = (long long)count * dm_ceil_div(Q, 128);
+  }
+  long long Smax = min(8LL, slots / max(wgs, 1LL));
+  Smax = min(Smax, ws_floats / ((long long)count * per));
+  Smax = min(Smax, (long long)(chunks / 4));
+  if (Smax < 2) return 1;
+  return conv_split_choice(chunks, true, (int)Smax, per);
 }
 
 int run_pack_bf16x3(PackArgs& p, hipStream_t st) {
@@ -1353,4 +1482,97 @@ extern "C" int dm_conv1x1_group_fwd(int count, const float* const* x, const int*
   else
     DM_LAUNCH((conv_igemm_group_kernel<1, 2, 2, 1, 2, 16, 1>), dim3((unsigned)total), dim3(256), lds_bytes, (hipStream_t)stream, g);
   return dm_check_launch();
+}
+
+// ---------------------------------------------------------------------------
+// (added to ABI 28) Stage-grouped convolutions: the three FCNMaskHeads of Cascade Mask R-CNN read the same RoIs and have
+// the same shapes, so each layer runs all three stages in ONE launch (conv_igemm_group_kernel over the concatenated grids).
+// Tile build: the one dm_conv2d_fwd picks for a lone problem of this shape (3x3, Cout > 64: 128 x 128 tiles when the K loop
+// splits or the grid fills the chip, else 128 x 32 -- decided on the grouped workgroup count; 3x3, Cout <= 64: 64 / 32 x 128;
+// 1x1: 128 / 64 / 32 couts x 128 px).  Every exact build of the kernel walks K in the order (chunk, tap, quad pair) and
+// every 3x3 build takes 8-channel chunks, so a problem's sums are those of dm_conv2d_fwd whatever tile either launch uses;
+// the 1x1 builds take 16- or 32-channel chunks, and a 32-channel chunk walks its quad pairs as two 16-channel chunks do.
+// With a K split, chunk c of a problem goes to split c / kchunks exactly as in a lone split launch of the same split count,
+// and the splits are added in index order by the same reduction arithmetic.  The 36-cout tail build (the DCN offset
+// convolutions: v_mfma_f32_4x4x1 rows) has no grouped form: 32 < Cout <= 36 with ksize 3 is refused.
+static int conv2d_group_setup(int count, const float* const* x, int NB, int H, int W, int Cin, int Cout, int ksize,
+                              const float* const* w_packed, const float* const* bias, int relu, float* const* out, int shuffle,
+                              ConvGroup& g) {
+  if (count < 1 || count > 3 || !x || !w_packed || !out || NB < 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0)
+    return DM_ERR_INVALID_ARG;
+  if ((long long)NB * H * W > 0x7fffffffLL) return DM_ERR_INVALID_ARG;
+  if (relu & ~(1 | 8 | 16)) return DM_ERR_INVALID_ARG;
+  if (relu & 16) return DM_ERR_UNSUPPORTED;        // exact fp32 only: the bf16x3 mode runs the per-stage path
+  for (int i = 0; i < count && NB > 0; ++i)        // (NB == 0: empty tensors may have null addresses; nothing is read)
+    if (!x[i] || !w_packed[i] || !out[i]) return DM_ERR_INVALID_ARG;
+  const int couts = shuffle ? 4 * Cout : Cout;
+  for (int i = 0; i < 3; ++i) {
+    const int j = i < count ? i : count - 1;          // unused slots repeat the last problem (never selected: end[] stops)
+    ConvArgs& a = g.a[i];
+    for (int s = 0; s < DM_MAX_SOURCES; ++s) { a.src[s] = nullptr; a.src_c[s] = 0; a.src_bs[s] = 0; }
+    a.src[0] = x[j]; a.src_c[0] = Cin; a.src_bs[0] = (long long)Cin * H * W; a.num_srcs = 1;
+    a.KQ = packed_quads(1, a.src_c);
+    a.NB = NB; a.H = H; a.W = W; a.HW = H * W; a.Q = NB * H * W;
+    a.wq = w_packed[j]; a.bias = bias ? bias[j] : nullptr; a.Cout = couts; a.CoutP = dm_conv_packed_cout(couts);
+    a.relu = relu & 1;
+    if (!shuffle && (long long)NB * Cout * H * W * 4 > (192LL << 20)) a.relu |= 4;     // (conv2d_launch's store policy)
+    a.out = out[j]; a.out_ch_total = shuffle ? 0 : Cout; a.out_ch_offset = 0;
+    a.shuffle = shuffle; a.q_begin = 0; a.mask = nullptr; a.ws = nullptr; a.ws_floats = 0; a.ws_stride = 0;
+    a.ksplit = 1; a.kchunks = 0; a.want_split = 0;
+    a.off32 = ((long long)NB * a.src_bs[0] * 4 < (1LL << 32)) ? 1 : 0;
+  }
+  return DM_OK;
+}
+
+extern "C" int dm_conv2d_group_splits(int count, int NB, int H, int W, int Cin, int Cout, int ksize, long long workspace_floats) {
+  if (count < 1 || count > 3 || NB < 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (ksize != 1 && ksize != 3)) return -1;
+  return group_split_choice(count, NB, H, W, Cin, Cout, ksize, workspace_floats);
+}
+
+extern "C" long long dm_conv2d_group_splitk_floats(int count, int NB, int H, int W, int Cin, int Cout, int ksize) {
+  if (count < 1 || count > 3 || NB <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || ksize != 3) return 0;
+  const long long per = (long long)NB * Cout * H * W;
+  const int S = group_split_choice(count, NB, H, W, Cin, Cout, ksize, 8LL * count * per);
+  return S >= 2 ? (long long)S * count * per : 0;
+}
+
+extern "C" int dm_conv2d_group_fwd(int count, const float* const* x, int NB, int H, int W, int Cin, int Cout, int ksize,
+                                   const float* const* w_packed, const float* const* bias, int relu, float* const* out,
+                                   float* workspace, long long workspace_floats, dm_stream_t stream) {
+  if (ksize != 1 && ksize != 3) return DM_ERR_INVALID_ARG;
+  ConvGroup g;
+  const int rc = conv2d_group_setup(count, x, NB, H, W, Cin, Cout, ksize, w_packed, bias, relu, out, 0, g);
+  if (rc != DM_OK) return rc;
+  if (ksize == 3 && Cout > 32 && Cout <= 36) return DM_ERR_UNSUPPORTED;
+  if (workspace_floats < 0 || (workspace_floats > 0 && !workspace)) return DM_ERR_INVALID_ARG;
+  if (NB == 0) return DM_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const int S = workspace ? group_split_choice(count, NB, H, W, Cin, Cout, ksize, workspace_floats) : 1;
+  if (ksize == 3) {
+    if (Cout > 64) {
+      const int cus = dm_num_cus();
+      const int wgs = count * dm_ceil_div(g.a[0].CoutP, 128) * dm_ceil_div(g.a[0].Q, 128);
+      if (S < 2 && (wgs * 10 <= cus * 7 || (wgs > cus && wgs * 20 <= cus * 29)))
+        return launch_group<3, 4, 1, 1, 1, 8>(g, count, 1, nullptr, st);
+      return launch_group<3, 2, 2, 2, 2, 8>(g, count, S, workspace, st);
+    }
+    if (Cout > 32) return launch_group<3, 1, 4, 2, 1, 8>(g, count, S, workspace, st);
+    return launch_group<3, 1, 4, 1, 1, 8>(g, count, S, workspace, st);
+  }
+  if (Cout > 64) return launch_group<1, 2, 2, 2, 2, 16>(g, count, 1, nullptr, st);
+  if (Cout > 32) return launch_group<1, 2, 2, 1, 2, 16>(g, count, 1, nullptr, st);
+  return launch_group<1, 1, 4, 1, 1, 32>(g, count, 1, nullptr, st);
+}
+
+// (added to ABI 28) 1 to 3 deconv 2x2/s2 problems of one shape in one launch: dm_deconv2x2_fwd's GEMM (4 * Cout packed
+// columns, 128 x 128 tiles, the pixel-shuffling epilogue) per problem, in its own range of the grid -- the same build on
+// the same operands, so each output has the bits of its own dm_deconv2x2_fwd.
+extern "C" int dm_deconv2x2_group_fwd(int count, const float* const* x, int NB, int C, int H, int W,
+                                      const float* const* w_packed, const float* const* bias, int Cout, int relu,
+                                      float* const* out, dm_stream_t stream) {
+  ConvGroup g;
+  const int rc = conv2d_group_setup(count, x, NB, H, W, C, Cout, 1, w_packed, bias, relu & ~8, out, Cout, g);
+  if (rc != DM_OK) return rc;
+  if (NB == 0) return DM_OK;
+  return launch_group<1, 2, 2, 2, 2, 16>(g, count, 1, nullptr, (hipStream_t)stream);
 }

@@ -2232,3 +2232,125 @@ def pixel_unshuffle2x(x):
     out = torch.empty((NB, 4 * C, OH // 2, OW // 2), device=x.device, dtype=torch.float32)
     check(lib().dm_pixel_unshuffle2x(_p(x), NB, C, OH // 2, OW // 2, _p(out), _stream()), 'dm_pixel_unshuffle2x')
     return out
+
+
+# ------------------------------------------------------------ Cascade Mask R-CNN (section K25 of the header)
+# CascadeRoIHead: the three stages' FCNMaskHeads as one launch per layer (conv2d_group / deconv2x2_group / conv1x1_group);
+# False: the three stage chains one after the other (the A/B baseline; the same bits when the K split is off)
+CASCADE_GROUPED = [os.environ.get('DM_CASCADE_GROUPED', '1') != '0']
+
+
+def conv2d_group_splits(count, NB, H, W, cin, cout, ksize, workspace_floats):
+    """The K-split count ``conv2d_group`` takes with a workspace of ``workspace_floats`` (1: none)."""
+    return int(lib().dm_conv2d_group_splits(int(count), int(NB), int(H), int(W), int(cin), int(cout), int(ksize),
+                                            int(workspace_floats)))
+
+
+def conv2d_group(xs, w_packeds, biases, cout, ksize, relu=False, outs=None, split=None):
+    """1 to 3 independent single-source "same" convolutions of one shape (+ bias, + ReLU) as ONE launch
+    (dm_conv2d_group_fwd); several ``xs`` may be one tensor.  ``split`` (default: CONV_SPLITK): a 3x3 launch of few
+    workgroups may split its K loop, with the split count decided on the grouped launch.  Exact fp32 only: weights
+    packed in the bf16x3 layout raise.  Per problem the bits of ``conv2d`` (no split) or of dm_conv2d_fwd_ws with the
+    same split count (``conv2d_group_splits``)."""
+    k = len(xs)
+    if not 1 <= k <= 3 or len(w_packeds) != k or len(biases) != k:
+        raise ValueError(f'conv2d_group: 1 to 3 problems with a weight and a bias each (got {k}, {len(w_packeds)}, {len(biases)})')
+    if ksize not in (1, 3):
+        raise ValueError(f'conv2d_group: ksize 1 or 3 (got {ksize})')
+    for x in xs:
+        _chk(x, 'x')
+        if x.dim() != 4 or tuple(x.shape) != tuple(xs[0].shape):
+            raise ValueError('conv2d_group: every problem needs an input of the same [NB, Cin, H, W] shape')
+    NB, cin, H, W = xs[0].shape
+    for w in w_packeds:
+        _chk(w, 'w_packed')
+        if conv_layout(w) != 'fp32':
+            raise ValueError('conv2d_group: the grouped launch is exact fp32 (weights packed in the bf16x3 layout)')
+        if w.numel() != packed_floats(cout, ksize, [cin]):
+            raise ValueError('conv2d_group: weights packed for another shape')
+    if outs is None:
+        outs = [torch.empty((NB, cout, H, W), device=xs[0].device, dtype=torch.float32) for _ in range(k)]
+    for o in outs:
+        _chk(o, 'out')
+        assert tuple(o.shape) == (NB, cout, H, W)
+    bias_arr = (ctypes.c_void_p * k)(*[0 if b is None else _chk(b, 'bias').data_ptr() for b in biases])
+    if hazard.ENABLED[0]:
+        hazard.note_ptr_array(bias_arr, [b for b in biases if b is not None])
+    ws, nws = None, 0
+    if (CONV_SPLITK[0] if split is None else split) and NB > 0:
+        nws = int(lib().dm_conv2d_group_splitk_floats(k, NB, H, W, cin, cout, ksize))
+        if nws > 0:
+            ws = torch.empty((nws,), device=xs[0].device, dtype=torch.float32)
+    check(lib().dm_conv2d_group_fwd(k, _ptr_array(xs), NB, H, W, cin, cout, ksize, _ptr_array(w_packeds), bias_arr,
+                                    1 if relu else 0, _ptr_array(outs), _p(ws), nws, _stream()), 'dm_conv2d_group_fwd')
+    return outs
+
+
+def deconv2x2_group(xs, w_packeds, biases, cout, relu=False):
+    """1 to 3 ``deconv2x2`` problems of one shape as ONE launch (dm_deconv2x2_group_fwd): the bits of ``deconv2x2`` each.
+    Exact fp32 only."""
+    k = len(xs)
+    if not 1 <= k <= 3 or len(w_packeds) != k or len(biases) != k:
+        raise ValueError(f'deconv2x2_group: 1 to 3 problems with a weight and a bias each (got {k})')
+    for x in xs:
+        _chk(x, 'x')
+        if x.dim() != 4 or tuple(x.shape) != tuple(xs[0].shape):
+            raise ValueError('deconv2x2_group: every problem needs an input of the same [NB, C, H, W] shape')
+    NB, C, H, W = xs[0].shape
+    for w in w_packeds:
+        _chk(w, 'w_packed')
+        if conv_layout(w) != 'fp32':
+            raise ValueError('deconv2x2_group: the grouped launch is exact fp32 (weights packed in the bf16x3 layout)')
+        if w.numel() != packed_floats(4 * cout, 1, [C]):
+            raise ValueError('deconv2x2_group: weights packed for another shape')
+    outs = [torch.empty((NB, cout, 2 * H, 2 * W), device=xs[0].device, dtype=torch.float32) for _ in range(k)]
+    bias_arr = (ctypes.c_void_p * k)(*[0 if b is None else _chk(b, 'bias').data_ptr() for b in biases])
+    if hazard.ENABLED[0]:
+        hazard.note_ptr_array(bias_arr, [b for b in biases if b is not None])
+    check(lib().dm_deconv2x2_group_fwd(k, _ptr_array(xs), NB, C, H, W, _ptr_array(w_packeds), bias_arr, cout,
+                                       1 if relu else 0, _ptr_array(outs), _stream()), 'dm_deconv2x2_group_fwd')
+    return outs
+
+
+def image_shape_table(img_metas, device):
+    """The per-image clip table of ``cascade_refine``: float32 [B, 2] = (img_shape h, w) of each meta, uploaded without
+    a host wait."""
+    return _upload([[float(m['img_shape'][0]), float(m['img_shape'][1])] for m in img_metas], torch.float32, device)
+
+
+def cascade_refine(rois, cls_score, bbox_pred, num_classes, img_tab, score_sum, first, class_agnostic=True,
+                   means=(0., 0., 0., 0.), stds=(1., 1., 1., 1.), wh_ratio_clip=16 / 1000, regress=True):
+    """One cascade stage boundary in one launch (dm_cascade_refine): ``score_sum`` += ``cls_score`` (``first``: starts
+    from 0, i.e. python's ``sum``), and -- ``regress`` -- the next stage's RoIs [n, 5]: ``regress_by_class`` of ``rois``
+    [n, 5] by the first argmax of ``cls_score[:, :-1]``, decoded with ``means`` / ``stds`` and clipped to
+    ``img_tab[rois[:, 0]]`` (``image_shape_table``).  Returns the new RoIs (None without ``regress``)."""
+    _chk(cls_score, 'cls_score')
+    n = cls_score.shape[0]
+    if cls_score.shape != (n, num_classes + 1):
+        raise ValueError(f'cls_score: [{n}, {num_classes + 1}] expected, got {list(cls_score.shape)}')
+    if score_sum is not None:
+        _chk(score_sum, 'score_sum')
+        if score_sum.shape != cls_score.shape:
+            raise ValueError('score_sum: the shape of cls_score expected')
+    out = None
+    if regress:
+        _chk(rois, 'rois')
+        _chk(bbox_pred, 'bbox_pred')
+        _chk(img_tab, 'img_tab')
+        if rois.shape != (n, 5):
+            raise ValueError(f'rois: [{n}, 5] expected')
+        if bbox_pred.shape != (n, 4 if class_agnostic else 4 * num_classes):
+            raise ValueError(f'bbox_pred: [{n}, {4 if class_agnostic else 4 * num_classes}] expected')
+        if img_tab.dim() != 2 or img_tab.shape[1] != 2 or img_tab.shape[0] < 1:
+            raise ValueError('img_tab: [B, 2] expected')
+        out = torch.empty((n, 5), device=rois.device, dtype=torch.float32)
+    elif score_sum is None:
+        raise ValueError('cascade_refine: nothing to do (no score sum, no regression)')
+    if n == 0:
+        return out
+    check(lib().dm_cascade_refine(_p(rois if regress else None), _p(cls_score), _p(bbox_pred if regress else None), n,
+                                  int(num_classes), 1 if class_agnostic else 0, _float_array(means), _float_array(stds),
+                                  float(wh_ratio_clip), _p(img_tab if regress else None),
+                                  int(img_tab.shape[0]) if regress else 0, _p(score_sum), 1 if first else 0, _p(out),
+                                  _stream()), 'dm_cascade_refine')
+    return out

@@ -1,6 +1,6 @@
 """The RoI heads behind the reference's HEADS registry, in the reference's class tree: ``StandardRoIHead``
-(standard_roi_head.py + test_mixins.py) is the base of ``DynaMaskRoIHead``, ``RefineRoIHead``, ``PointRendRoIHead`` and
-``MaskScoringRoIHead``.
+(standard_roi_head.py + test_mixins.py) is the base of ``DynaMaskRoIHead``, ``RefineRoIHead``, ``PointRendRoIHead``,
+``MaskScoringRoIHead``, ``PointRefineRoIHead`` and ``CascadeRoIHead``.
 
 The base holds the constructor (incl. ``base_roi_head.py:10-58``'s MaskPre, Quirk Q4), the assigner / sampler, the bbox
 branch, the one-image / batched / test-time-augmentation entry points and one mask-test template over a head's
@@ -283,20 +283,30 @@ class StandardRoIHead(nn.Module):
         cls_score, bbox_pred = self.bbox_head(bbox_feats)
         return dict(cls_score=cls_score, bbox_pred=bbox_pred, bbox_feats=bbox_feats)
 
+    def _bbox_num_classes(self):
+        return self.bbox_head.num_classes
+
+    def _bbox_test_preds(self, x, rois, img_metas):
+        """The bbox branch of the test entry points: RoIs [N, 5] (batch column = index into ``img_metas``) -> (the RoIs
+        the predictions refer to, cls_score, bbox_pred, the bbox head that decodes them).  Here one ``_bbox_forward``;
+        CascadeRoIHead runs its stages."""
+        res = self._bbox_forward(x, rois)
+        return rois, res['cls_score'], res['bbox_pred'], self.bbox_head
+
     @torch.no_grad()
     def simple_test_bboxes(self, x, img_metas, proposals, rcnn_test_cfg, rescale=False):
         """test_mixins.py:52-71 (BBoxTestMixin.simple_test_bboxes), one image."""
         rois = bbox2roi(proposals).contiguous()
-        res = self._bbox_forward(x, rois)
-        return self.bbox_head.get_bboxes(rois, res['cls_score'], res['bbox_pred'], img_metas[0]['img_shape'],
-                                         img_metas[0]['scale_factor'], rescale=rescale, cfg=rcnn_test_cfg)
+        rois, cls_score, bbox_pred, head = self._bbox_test_preds(x, rois, img_metas)
+        return head.get_bboxes(rois, cls_score, bbox_pred, img_metas[0]['img_shape'],
+                               img_metas[0]['scale_factor'], rescale=rescale, cfg=rcnn_test_cfg)
 
     @torch.no_grad()
     def simple_test(self, x, proposal_list, img_metas, proposals=None, rescale=False, encode=False):
         """standard_roi_head.py:217-236: boxes, then masks of the kept detections."""
         from .bbox_heads import bbox2result
         det_bboxes, det_labels = self.simple_test_bboxes(x, img_metas, proposal_list, self.test_cfg, rescale=rescale)
-        bbox_results = bbox2result(det_bboxes, det_labels, self.bbox_head.num_classes)
+        bbox_results = bbox2result(det_bboxes, det_labels, self._bbox_num_classes())
         if not self.with_mask:
             return bbox_results
         segm_results = self.simple_test_mask(x, img_metas, det_bboxes, det_labels, rescale=rescale, encode=encode)
@@ -333,6 +343,9 @@ class StandardRoIHead(nn.Module):
         """One image's mask-test result from its per-class ``segms`` and the second value of ``_mask_test_pred``
         (rows start:start + count are the image's; read only after the paste's host wait): here the masks alone."""
         return segms
+
+    # whether ``_mask_test_pred`` gives logits (the paste applies the sigmoid) or probabilities (CascadeRoIHead's merge)
+    _mask_test_sigmoid = True
 
     def _empty_mask_logits(self, ref, channels=None):
         c, s = self._mask_logits_size()
@@ -372,7 +385,8 @@ class StandardRoIHead(nn.Module):
         _bboxes, scale_factor = self._mask_boxes(det_bboxes, img_metas[0]['scale_factor'], rescale)
         logits, pending = self._mask_test_pred(x, [_bboxes], [det_labels], [det_bboxes])
         segms = paste_segms(select_label_channel(logits, det_labels), _bboxes, det_labels, self.test_cfg,
-                            img_metas[0]['ori_shape'], scale_factor, rescale, encode=encode, num_classes=num_classes)
+                            img_metas[0]['ori_shape'], scale_factor, rescale, encode=encode, num_classes=num_classes,
+                            apply_sigmoid=self._mask_test_sigmoid)
         return self._mask_test_result(segms, pending, 0, int(det_bboxes.shape[0]))
 
     # ------------------------------------------------------------ batched inference: B images per call
@@ -473,10 +487,11 @@ class StandardRoIHead(nn.Module):
             sizes.append((h, w))
         canvas_boxes = torch.cat(canvas_boxes).contiguous()
         if encode:
-            segs = ops.paste_rle_multi(preds, canvas_boxes, counts, sizes, threshold, apply_sigmoid=True)
+            segs = ops.paste_rle_multi(preds, canvas_boxes, counts, sizes, threshold, apply_sigmoid=self._mask_test_sigmoid)
             labels_h = _labels_host if _labels_host is not None else labels.cpu().tolist()
         else:
-            buf, offs, det_sizes = ops.paste_masks_multi(preds, canvas_boxes, counts, sizes, threshold, apply_sigmoid=True)
+            buf, offs, det_sizes = ops.paste_masks_multi(preds, canvas_boxes, counts, sizes, threshold,
+                                                         apply_sigmoid=self._mask_test_sigmoid)
             if _labels_host is None:
                 flat, labels_h = _to_host(buf, labels)
                 labels_h = labels_h.tolist()
@@ -505,16 +520,15 @@ class StandardRoIHead(nn.Module):
         if rois.shape[0] == 0:
             ref = proposals[0]
             return [(ref.new_zeros((0, 5)), ref.new_zeros((0,), dtype=torch.long)) for _ in range(B)]
-        res = self._bbox_forward(x, rois)
-        cls_score, bbox_pred = res['cls_score'], res['bbox_pred']
+        rois, cls_score, bbox_pred, head = self._bbox_test_preds(x, rois, img_metas)
         bl, sl, r0 = [], [], 0
         for b in range(B):
             r1 = r0 + rows[b]
             if r1 == r0:
                 bl.append(rois.new_zeros((0, 4)))
-                sl.append(rois.new_zeros((0, self.bbox_head.num_classes + 1)))
+                sl.append(rois.new_zeros((0, head.num_classes + 1)))
             else:
-                bboxes, scores = self.bbox_head.get_bboxes(
+                bboxes, scores = head.get_bboxes(
                     rois[r0:r1], None if cls_score is None else cls_score[r0:r1],
                     None if bbox_pred is None else bbox_pred[r0:r1], img_metas[b]['img_shape'],
                     img_metas[b]['scale_factor'], rescale=rescale, cfg=None)
@@ -538,7 +552,7 @@ class StandardRoIHead(nn.Module):
                 raise ValueError(f'x[{i}] has batch dimension {f.shape[0]} for {B} images')
         dets = self.batch_simple_test_bboxes(x, img_metas, proposal_list, self.test_cfg, rescale=rescale)
         counts = [int(d.shape[0]) for d, _ in dets]
-        num_classes = self.bbox_head.num_classes
+        num_classes = self._bbox_num_classes()
         if sum(counts) == 0:
             import numpy as np
             bbox_results = [[np.zeros((0, 5), dtype=np.float32) for _ in range(num_classes)] for _ in range(B)]
@@ -600,9 +614,9 @@ class StandardRoIHead(nn.Module):
         rois = ops.bbox_mapping_multi(props, tab)
         aug_bboxes, aug_scores = [], []
         for v, meta in enumerate(views):
-            res = self._bbox_forward(x[v], rois[v])
-            bboxes, scores = self.bbox_head.get_bboxes(rois[v], res['cls_score'], res['bbox_pred'], meta['img_shape'],
-                                                       meta['scale_factor'], rescale=False, cfg=None)
+            view_rois, cls_score, bbox_pred, head = self._bbox_test_preds(x[v], rois[v], [meta])
+            bboxes, scores = head.get_bboxes(view_rois, cls_score, bbox_pred, meta['img_shape'],
+                                             meta['scale_factor'], rescale=False, cfg=None)
             aug_bboxes.append(bboxes.contiguous())
             aug_scores.append(scores.contiguous())
         merged_bboxes, merged_scores = ops.merge_aug_bboxes(aug_bboxes, aug_scores, tab)
@@ -653,7 +667,7 @@ class StandardRoIHead(nn.Module):
         from .mask_heads import _to_host
         views = self._check_aug(x, img_metas)
         det_bboxes, det_labels = self.aug_test_bboxes(x, img_metas, proposal_list, self.test_cfg)
-        num_classes = self.bbox_head.num_classes
+        num_classes = self._bbox_num_classes()
         if det_bboxes.shape[0] == 0:
             bbox_results = [np.zeros((0, 5), dtype=np.float32) for _ in range(num_classes)]
             labels_h = []
@@ -1260,3 +1274,256 @@ class MaskScoringRoIHead(StandardRoIHead):
             return segms, [[] for _ in range(num_classes)]
         scores, labels = (t.numpy()[start:start + count] for t in pending)
         return segms, group_mask_scores(scores, labels, num_classes)
+
+
+@HEADS.register_module()
+class CascadeRoIHead(StandardRoIHead):
+    """cascade_roi_head.py:12-448 for inference: ``num_stages`` bbox stages, each re-regressing all RoIs by the class of
+    its own argmax (``regress_by_class``), the classification scores averaged over the stages, and for the kept
+    detections the mask heads of all stages, whose sigmoids are averaged (``merge_aug_masks``).  ``bbox_roi_extractor``,
+    ``bbox_head``, ``mask_roi_extractor`` and ``mask_head`` are ``ModuleList``s built from a dict (the same config for
+    every stage) or a list of ``num_stages`` dicts; the fork's ``mask_predictor.*`` keys are there (Quirk Q4), so the
+    ``state_dict`` is the reference's.
+
+    HIP: one ``dm_cascade_refine`` per stage boundary (argmax, class gather, decode, clip to the RoI's own image, batch
+    column and the score sum in the reference's order), and the mask heads of up to three stages as ONE launch per layer
+    (``ops.conv2d_group`` / ``deconv2x2_group`` / ``conv1x1_group``; ``ops.CASCADE_GROUPED[0] = False`` or
+    DM_CASCADE_GROUPED=0: the stage chains one after the other).  The mask RoIAlign runs once when the stages' mask
+    extractor configs are equal.  The mask prediction handed to the paste is the merged probabilities [n, 1, S, S]
+    (``_mask_test_sigmoid = False``).  A meta with ``flip=True`` un-flips every stage's mask in ``simple_test`` as the
+    reference's ``merge_aug_masks`` call does (Quirk Q16).  Out of scope: training (Quirk Q5), graph capture, the shared
+    mask extractor form (``mask_roi_extractor=None``) and HTC."""
+
+    _mask_test_sigmoid = False
+
+    def __init__(self, num_stages, stage_loss_weights, bbox_roi_extractor=None, bbox_head=None, mask_roi_extractor=None,
+                 mask_head=None, shared_head=None, train_cfg=None, test_cfg=None):
+        if isinstance(num_stages, bool) or not isinstance(num_stages, int) or num_stages < 1:
+            raise ValueError(f'num_stages: a positive int (got {num_stages!r})')
+        if not isinstance(stage_loss_weights, (list, tuple)) or len(stage_loss_weights) != num_stages:
+            raise ValueError(f'stage_loss_weights: one weight per stage ({num_stages})')
+        if bbox_roi_extractor is None or bbox_head is None:
+            raise ValueError('CascadeRoIHead needs bbox_roi_extractor and bbox_head (cascade_roi_head.py:29-30)')
+        if shared_head is not None:
+            raise NotImplementedError('Shared head is not supported in Cascade RCNN anymore')
+        if mask_head is not None and mask_roi_extractor is None:
+            raise NotImplementedError('the shared-extractor form (mask_roi_extractor=None): no cascade mask config uses it')
+        super().__init__(train_cfg=train_cfg, test_cfg=test_cfg)
+        self._merge_metas = None        # the metas of the current mask test (the flip of Quirk Q16)
+        self.num_stages = num_stages
+        self.stage_loss_weights = stage_loss_weights
+        from . import bbox_heads  # noqa: F401  (registers Shared2FCBBoxHead)
+        exts, heads = self._per_stage(bbox_roi_extractor, 'bbox_roi_extractor'), self._per_stage(bbox_head, 'bbox_head')
+        self.bbox_roi_extractor = nn.ModuleList([build_roi_extractor(c) for c in exts])
+        self.bbox_head = nn.ModuleList([build_head(c) for c in heads])
+        if mask_head is not None:
+            mexts = self._per_stage(mask_roi_extractor, 'mask_roi_extractor')
+            self.mask_head = nn.ModuleList([build_head(c) for c in self._per_stage(mask_head, 'mask_head')])
+            self.share_roi_extractor = False
+            self.mask_roi_extractor = nn.ModuleList([build_roi_extractor(c) for c in mexts])
+            # RoIAlign has no parameters: equal configs give equal features, extracted once
+            self._one_mask_extraction = all(dict(c) == dict(mexts[0]) for c in mexts)
+
+    def _per_stage(self, cfg, name):
+        if isinstance(cfg, (list, tuple)):
+            if len(cfg) != self.num_stages:
+                raise ValueError(f'{name}: {len(cfg)} configs for {self.num_stages} stages')
+            return list(cfg)
+        return [cfg for _ in range(self.num_stages)]
+
+    def init_weights(self, pretrained=None):
+        for h in self.bbox_head:
+            h.init_weights()
+        if self.with_mask:
+            for h in self.mask_head:
+                h.init_weights()
+
+    def forward_train(self, x, img_metas, proposal_list, gt_bboxes, gt_labels, gt_bboxes_ignore=None, gt_masks=None):
+        raise NotImplementedError('CascadeRoIHead training: its mask loss ends in FCNMaskHead.loss, which the reference '
+                                  'fork broke (Quirk Q5)')
+
+    def enable_inference_graphs(self, on=True, buckets=None, batch_buckets=None):
+        if on:
+            raise NotImplementedError('CascadeRoIHead: HIP-graph capture of its mask call is a follow-up')
+        self._mask_graphs = None
+        return None
+
+    # ------------------------------------------------------------ bbox stages
+    def _bbox_num_classes(self):
+        return self.bbox_head[-1].num_classes
+
+    def _bbox_forward_stage(self, i, x, rois):
+        """cascade_roi_head.py:126-137 (test form)."""
+        ext = self.bbox_roi_extractor[i]
+        cls_score, bbox_pred = self.bbox_head[i](ext(x[:ext.num_inputs], rois))
+        return cls_score, bbox_pred
+
+    @torch.no_grad()
+    def _bbox_test_preds(self, x, rois, img_metas):
+        """cascade_roi_head.py:304-318: the stages one after the other, each stage's RoIs ``regress_by_class`` of the
+        previous ones clipped to the RoI's own image (``img_metas[rois[:, 0]]['img_shape']``), the scores summed in stage
+        order and divided by ``num_stages`` as the reference's ``sum(ms_scores) / self.num_stages``."""
+        n = rois.shape[0]
+        head = self.bbox_head[-1]
+        if n == 0:
+            nb = 1 if head.reg_class_agnostic else head.num_classes
+            return rois, rois.new_zeros((0, head.num_classes + 1)), rois.new_zeros((0, 4 * nb)), head
+        img_tab = ops.image_shape_table(img_metas, rois.device)
+        score_sum = None
+        for i in range(self.num_stages):
+            cls_score, bbox_pred = self._bbox_forward_stage(i, x, rois)
+            if score_sum is None:
+                score_sum = torch.empty_like(cls_score)
+            h = self.bbox_head[i]
+            last = i == self.num_stages - 1
+            new_rois = ops.cascade_refine(rois, cls_score.contiguous(), bbox_pred.contiguous(), h.num_classes, img_tab,
+                                          score_sum, first=i == 0, class_agnostic=h.reg_class_agnostic,
+                                          means=h.bbox_coder.means, stds=h.bbox_coder.stds, regress=not last)
+            if not last:
+                rois = new_rois
+        return rois, score_sum / self.num_stages, bbox_pred, head
+
+    # ------------------------------------------------------------ mask stages
+    def _mask_logits_size(self):
+        h = self.mask_head[-1]
+        s = self.mask_roi_extractor[-1].roi_layers[0].output_size[0]
+        return h.conv_logits.out_channels, int(s * (h.scale_factor if h.upsample is not None else 1))
+
+    def _segm_num_classes(self):
+        return self.mask_head[-1].num_classes
+
+    def _grouped_ok(self):
+        """The stage-grouped launches take the stock FCNMaskHead (deconv upsample) of equal shapes, exact fp32."""
+        if not ops.CASCADE_GROUPED[0] or ops.inference_precision() != 'fp32':
+            return False
+        h0 = self.mask_head[0]
+        for h in self.mask_head:
+            if type(h).__name__ != 'FCNMaskHead' or h.upsample_method != 'deconv' or h.num_convs != h0.num_convs or \
+                    h.conv_kernel_size not in (1, 3) or h.conv_kernel_size != h0.conv_kernel_size or \
+                    h.in_channels != h0.in_channels or h.conv_out_channels != h0.conv_out_channels or \
+                    h.conv_logits.out_channels != h0.conv_logits.out_channels:
+                return False
+        return True
+
+    def _fcn_group(self, heads, feats):
+        """FCNMaskHead.forward of up to three stages on their features (one tensor per stage, possibly the same one):
+        one launch per layer."""
+        xs = list(feats)
+        h0 = heads[0]
+        for j in range(h0.num_convs):
+            convs = [h.convs[j].conv for h in heads]
+            xs = ops.conv2d_group(xs, [c.packed([xs[0].shape[1]]) for c in convs], [c.bias.detach() for c in convs],
+                                  convs[0].out_channels, h0.conv_kernel_size, relu=True)
+        ups = [h.upsample for h in heads]
+        wps = [u._pk.get('w', u.weight, lambda w: ops.pack_deconv_weight(w, precision='fp32'), precision='fp32') for u in ups]
+        xs = ops.deconv2x2_group(xs, wps, [u.bias.detach() for u in ups], ups[0].out_channels, relu=True)
+        cls = [h.conv_logits for h in heads]
+        return ops.conv1x1_group(xs, [c.packed([xs[0].shape[1]]) for c in cls], [c.bias.detach() for c in cls],
+                                 [c.out_channels for c in cls])
+
+    @torch.no_grad()
+    def _stage_mask_logits(self, x, mask_rois):
+        """Every stage's mask logits [n, C, S, S] of the RoIs (cascade_roi_head.py:340-344 / 430-433)."""
+        feats = []
+        for i in range(self.num_stages):
+            if i > 0 and self._one_mask_extraction:
+                feats.append(feats[0])
+                continue
+            ext = self.mask_roi_extractor[i]
+            feats.append(ext(x[:ext.num_inputs], mask_rois))
+        with ops.splitk_scope():                # inference: the 14 x 14 launches of few workgroups may split their K loop
+            if not self._grouped_ok():
+                return [self.mask_head[i](feats[i]) for i in range(self.num_stages)]
+            out = []
+            for s0 in range(0, self.num_stages, 3):
+                idx = range(s0, min(s0 + 3, self.num_stages))
+                out += self._fcn_group([self.mask_head[i] for i in idx], [feats[i] for i in idx])
+            return out
+
+    @staticmethod
+    def _merge_view(meta):
+        """The view row ``merge_aug_masks`` gives a stage's mask in simple_test: the meta's flip (Quirk Q16)."""
+        flip = bool(meta.get('flip', False))
+        return dict(img_shape=meta.get('img_shape', (1, 1)), scale_factor=1.0, flip=flip,
+                    flip_direction=meta.get('flip_direction', 'horizontal') if flip else None)
+
+    def _mask_test_pred(self, x, boxes, labels, det_bboxes):
+        """The merged probabilities [sum n, 1, S, S]: every stage's logits of the detections, their label channel,
+        sigmoid, un-flipped by the image's meta and averaged over the stages in stage order (dm_merge_aug_masks)."""
+        mask_rois = bbox2roi(list(boxes)).contiguous()
+        labels_all = torch.cat(list(labels)).contiguous()
+        logits = [t.contiguous() for t in self._stage_mask_logits(x, mask_rois)]
+        metas = self._merge_metas or [dict() for _ in boxes]          # (set by the mask-test entry points)
+        views = [self._merge_view(m) for m in metas]
+        codes = [ops.aug_view_rows([v])[0][6] for v in views]
+        if all(c == codes[0] for c in codes):
+            tab = ops.aug_view_table([views[0]] * self.num_stages, mask_rois.device)
+            return ops.merge_aug_masks(logits, labels_all, tab), None
+        out, r0 = [], 0
+        for b, v in enumerate(views):
+            r1 = r0 + int(boxes[b].shape[0])
+            if r1 > r0:
+                tab = ops.aug_view_table([v] * self.num_stages, mask_rois.device)
+                out.append(ops.merge_aug_masks([t[r0:r1].contiguous() for t in logits], labels_all[r0:r1].contiguous(), tab))
+            r0 = r1
+        return torch.cat(out), None
+
+    def simple_test_mask(self, x, img_metas, det_bboxes, det_labels, rescale=False, encode=False):
+        self._merge_metas = img_metas
+        try:
+            return super().simple_test_mask(x, img_metas, det_bboxes, det_labels, rescale=rescale, encode=encode)
+        finally:
+            self._merge_metas = None
+
+    @torch.no_grad()
+    def batch_simple_test_mask(self, x, img_metas, det_bboxes_list, det_labels_list, rescale=False, encode=False,
+                               _labels_host=None):
+        self._merge_metas = img_metas
+        try:
+            return super().batch_simple_test_mask(x, img_metas, det_bboxes_list, det_labels_list, rescale=rescale,
+                                                  encode=encode, _labels_host=_labels_host)
+        finally:
+            self._merge_metas = None
+
+    def simple_test_mask_logits(self, x, det_bboxes, det_labels, scale_factor=1.0, rescale=False):
+        """The detections' merged probabilities [n, 1, S, S] (no flip): what ``simple_test_mask`` pastes."""
+        if det_bboxes.shape[0] == 0:
+            return self._empty_mask_logits(det_bboxes, channels=1)
+        _bboxes = det_bboxes[:, :4] * scale_factor if rescale else det_bboxes
+        self._merge_metas = [dict()]
+        try:
+            return self._mask_test_pred(x, [_bboxes], [det_labels], [det_bboxes])[0]
+        finally:
+            self._merge_metas = None
+
+    @torch.no_grad()
+    def aug_test_mask_probs(self, x, img_metas, det_bboxes, det_labels):
+        """cascade_roi_head.py:424-437: the detections mapped into every view, every stage's mask prediction there, and
+        the V x num_stages sigmoids un-flipped and averaged in (view, stage) order -- one dm_merge_aug_masks call."""
+        views = self._check_aug(x, img_metas)
+        if det_bboxes.shape[0] == 0:
+            return self._empty_mask_logits(det_bboxes, channels=1)
+        tab = ops.aug_view_table(views, det_bboxes.device)
+        rois = ops.bbox_mapping_multi(det_bboxes, tab)
+        labels = det_labels.contiguous()
+        logits, rows = [], []
+        for v, meta in enumerate(views):
+            logits += [t.contiguous() for t in self._stage_mask_logits(x[v], rois[v].contiguous())]
+            rows += [meta] * self.num_stages
+        return ops.merge_aug_masks(logits, labels, ops.aug_view_table(rows, det_bboxes.device))
+
+    @torch.no_grad()
+    def aug_test(self, x, proposal_list, img_metas, rescale=False, encode=False):
+        """cascade_roi_head.py:360-448: the cascade per view, merge_aug_bboxes + NMS, the masks of every view and stage
+        merged.  The reference returns the boxes in original-image coordinates whatever ``rescale`` is."""
+        return super().aug_test(x, proposal_list, img_metas, rescale=True, encode=encode)
+
+
+def _htc_follow_up(name):
+    def __init__(self, *args, **kwargs):
+        raise NotImplementedError(f'{name} (Hybrid Task Cascade) builds on CascadeRoIHead and is the next step, not built yet')
+    return type(name, (nn.Module,), {'__init__': __init__, '__doc__': f'{name}: not built yet (HTC follows CascadeRoIHead).'})
+
+
+for _name in ('HybridTaskCascadeRoIHead', 'HTCMaskHead', 'FusedSemanticHead'):
+    HEADS.register_module(module=_htc_follow_up(_name))

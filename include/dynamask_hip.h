@@ -58,7 +58,8 @@ const char* dm_error_string(int code);
 /* ABI version: bumped whenever a signature or the meaning of an argument changes (8: flag bit 3 of dm_conv2d_fwd; 9: RoI assignment / bbox training entry points; 10: dm_detail_target takes the fuse weights from device memory; 11: FCNMaskHead upsample backward; 12: dm_fc_fwd takes a scratch slab, deterministic split-K; 13: dm_deform_coord_grad / dm_deform_col2im, dm_conv2d_fwd_masked, dm_scale, dm_polygon_mask_targets, dm_ignore_columns, dm_upsample2x_bilinear_bwd overwrites; 14: dm_random_sample, dm_bn_relu_maxpool_argmax, the *_fx deterministic accumulators + dm_fx_to_float, dm_mask_loss_fwd_bwd takes a scratch, dm_conv2d_wgrad takes the bias gradient, dm_conv_pack_weight_batch, dm_mask_loss_stage; 15: dm_class_logits_up2x_fwd; 16: dm_conv2d_wgrad_slab / dm_conv2d_wgrad_scratch_floats; 17: dm_class_logits_bwd_slab / dm_class_logits_bwd_scratch_floats; 18: dm_reload_env_knobs, dm_roi_align_fwd_ws / dm_roi_align_workspace_bytes, dm_conv_pack_weight_split / dm_conv_packed_floats_split and flag bits 4, 5 of dm_conv2d_fwd; 19: dm_dcn_bwd_data_fused and its pack; 20: dm_conv2d_fwd_ws / dm_conv2d_splitk_floats; 21: dm_deform_conv_fwd_ws / dm_deform_conv_splitk_floats; 22: the bf16-split layouts (dm_conv_pack_weight_split, dm_conv_packed_floats_split, flag bits 4 / 5 of dm_conv2d_fwd) and the one-kernel DCN data gradient (dm_dcn_bwd_*) REMOVED -- measured, never the parity path, see docs/HISTORY.md; 23: dm_bn_stats takes mean_shift, dm_roi_align_bwd takes the gather form for 16 < P <= 64; 24: dm_build_info; 25: dm_boundary_merge_chain, dm_stage_head_fwd; 26: dm_conv1x1_group_fwd; 27: dm_deform_conv_tout_fwd / dm_deform_conv_tout_supported; 28: the opt-in bf16x3 mode -- dm_conv_pack_weight_bf16x3 / dm_conv_packed_floats_bf16x3 and flag bit 4 of dm_conv2d_fwd, dm_conv2d_fwd_ws and dm_conv1x1_group_fwd; dm_deconv_pack_weight_bf16x3 and flag bit 4 of dm_deconv2x2_fwd).  Entry points ADDED without a signature or meaning change leave the number as it is (the loader resolves every symbol of _lib.SIGNATURES by name, so an older library fails at load): the multi-image post-processing dm_nms_mask_segmented / dm_nms_reduce_segmented, dm_paste_masks_multi, dm_paste_rle_multi / dm_rle_multi_scratch_ints; the test-time augmentation dm_bbox_mapping_multi, dm_merge_aug_bboxes, dm_merge_aug_masks; RefineMask's dilated / any-width 3x3 convolutions and the sigmoid of its semantic map (section K21); PointRend's point
  * selection, point gather, point MLP and scatter (section K22); Mask Scoring R-CNN's stride-2 3x3 convolution, IoU-head
  * input and mask scores (section K23); PointRefine's descending point selection, point-feature gather, point MLP and
- * multi-row scatter (section K24). */
+ * multi-row scatter (section K24); Cascade Mask R-CNN's stage-grouped convolutions / deconvolutions and stage step
+ * (section K25). */
 int dm_abi_version(void);
 /* "libdynamask_hip abi=N arch=gfx950 compiler=<clang version> flags=<the product-wide flags of dynamask_amd/build.py>"
  * (static storage).  The library must be compiled WITHOUT packed fp32 instructions (flag "-packed-fp32-ops", see
@@ -930,6 +931,43 @@ int dm_point_refine_mlp(const float* x, int n, int P, int C, int NC, int num_fcs
 /* map[r, c, idx[r, p]] = vals[r, c, p] for r < n, c < C, p < P (the unfused sequence's scatter); vals [n, C, P], idx [n, P]
  * in [0, HW), map [n, C, HW].  DM_ERR_UNSUPPORTED unless n >= 0, C >= 1, 1 <= P <= HW and ceil(n * C * P / 256) < 2^31. */
 int dm_point_scatter_rows(const float* vals, const int* idx, int n, int C, int P, float* map, int HW, dm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * K25  Cascade Mask R-CNN inference (mmdet/models/roi_heads/cascade_roi_head.py:294-448).
+ *
+ * dm_conv2d_group_fwd: count (1..3) independent single-source "same" convolutions of ONE shape in ONE launch:
+ * out[i] [NB, Cout, H, W] = act(conv_ksize(x[i] [NB, Cin, H, W], w_packed[i]) + bias[i]), ksize 1 or 3, weights packed by
+ * dm_conv_pack_weight (one source); several x[i] may be the same pointer; bias (the host array, or an entry) may be NULL.
+ * relu: bit 0 ReLU, bit 3 accepted and ignored; bit 4 (the bf16x3 layout) returns DM_ERR_UNSUPPORTED: the grouped launch is
+ * exact fp32 only; any other bit DM_ERR_INVALID_ARG.  ksize 3 with 32 < Cout <= 36 (the tail build) is DM_ERR_UNSUPPORTED.
+ * workspace (optional, workspace_floats of them): a 3x3 launch of few workgroups splits its K loop as dm_conv2d_fwd_ws
+ * does, the split decided on the GROUPED workgroup count; dm_conv2d_group_splits gives the split count S of a call
+ * (1: none).  Contract: out[i] has the bits of dm_conv2d_fwd_ws(x[i], ...) given a workspace of S * NB * Cout * H * W
+ * floats (S = 1: of dm_conv2d_fwd).  dm_conv2d_group_splitk_floats: the workspace that lets the call split as far as it
+ * would (0: it would not).  NB == 0 enqueues nothing.
+ *
+ * dm_deconv2x2_group_fwd: count (1..3) dm_deconv2x2_fwd problems of one shape in one launch (weights of
+ * dm_deconv_pack_weight; relu bit 0 ReLU, bit 4 DM_ERR_UNSUPPORTED); each out[i] has the bits of its dm_deconv2x2_fwd.
+ *
+ * dm_cascade_refine: one cascade stage boundary, one wave per RoI row i < n:
+ *   score_sum[i, :] = (first_stage ? 0 : score_sum[i, :]) + cls_score[i, :]   ([n, NC + 1]; sum(ms_scores) in fp32);
+ *   label = the first maximum of cls_score[i, :NC] (torch argmax: NaN is the maximum);
+ *   out_rois[i] = [rois[i, 0], delta2bbox(rois[i, 1:5], d)] clipped to img_shapes[rois[i, 0]] = (h, w), where d is
+ *   bbox_pred[i, 0:4] (class_agnostic, [n, 4]) or bbox_pred[i, 4 label : 4 label + 4] ([n, 4 NC]): regress_by_class
+ *   with the same decode as dm_bbox_decode (means, stds, wh_ratio_clip).  The image index is clamped to
+ *   [0, num_images - 1].  score_sum NULL: no sum; out_rois NULL: the sum only (the last stage; rois / bbox_pred unread).
+ *   out_rois may not be rois.  n == 0 enqueues nothing.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int dm_conv2d_group_splits(int count, int NB, int H, int W, int Cin, int Cout, int ksize, long long workspace_floats);
+long long dm_conv2d_group_splitk_floats(int count, int NB, int H, int W, int Cin, int Cout, int ksize);
+int dm_conv2d_group_fwd(int count, const float* const* x, int NB, int H, int W, int Cin, int Cout, int ksize,
+                        const float* const* w_packed, const float* const* bias, int relu, float* const* out, float* workspace,
+                        long long workspace_floats, dm_stream_t stream);
+int dm_deconv2x2_group_fwd(int count, const float* const* x, int NB, int C, int H, int W, const float* const* w_packed,
+                           const float* const* bias, int Cout, int relu, float* const* out, dm_stream_t stream);
+int dm_cascade_refine(const float* rois, const float* cls_score, const float* bbox_pred, int n, int num_classes,
+                      int class_agnostic, const float* means, const float* stds, float wh_ratio_clip, const float* img_shapes,
+                      int num_images, float* score_sum, int first_stage, float* out_rois, dm_stream_t stream);
 
 #ifdef __cplusplus
 }
