@@ -123,6 +123,9 @@ SIGNATURES = {
     'dm_deconv2x2_group_fwd': ([_c_int, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _c_int, _vp, _vp], _c_int),
     'dm_cascade_refine': ([_vp, _vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _c_float, _vp, _c_int, _vp, _c_int, _vp, _vp],
                           _c_int),
+    'dm_resize_bilinear_fwd': ([_vp, ctypes.c_longlong, _c_int, _c_int, _c_int, _c_int, _vp, _vp], _c_int),
+    'dm_conv2d_post_add_fwd': ([_vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _c_int, _vp], _c_int),
+    'dm_roi_align_add_fwd': ([_vp, _c_int, _c_int, _c_int, _c_int, _c_float, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp], _c_int),
     'dm_fc_scratch_floats': ([_c_int, _c_int, _c_int], ctypes.c_longlong),
     'dm_fc_fwd': ([_vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp], _c_int),
     'dm_sgd_momentum_step': ([_vp, _vp, _vp, ctypes.c_longlong, _c_float, _c_float, _c_float, _c_float, _c_int, _vp], _c_int),

@@ -57,6 +57,8 @@ struct ConvArgs {
   long long ws_floats = 0, ws_stride = 0;
   int ksplit = 1, kchunks = 0;
   int want_split = 0;        // host side: the launcher's choice of splits for this launch (0: launch_conv_mp decides)
+  // POST builds (dm_conv2d_post_add_fwd): same layout as out, added AFTER the activation; may be out itself
+  const float* addend = nullptr;
 };
 
 // CK input channels per chunk (multiple of 8); MAXPOS = plane positions per thread (3x3)
@@ -122,11 +124,14 @@ __device__ __forceinline__ void dm_split8x3(const dm_f32x4& q0, const dm_f32x4& 
   for (int p = 0; p < 3; ++p) out[p] = __builtin_bit_cast(dm_f32x4, w[p]);
 }
 
-template <int KS, int WGM, int WGN, int WM, int WN, int CK, int MAXPOS, int TAIL = 0, int PREC = 0>
+// POST (K26, dm_conv2d_post_add_fwd): the epilogue stores addend + act(conv + bias) -- the addend joins after the
+// activation, where the accumulate flag adds before it; everything in front of the store is the POST = 0 build's.
+template <int KS, int WGM, int WGN, int WM, int WN, int CK, int MAXPOS, int TAIL = 0, int PREC = 0, int POST = 0>
 __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx, const int gx, const int by) {
   static_assert(TAIL == 0 || (TAIL == 4 && WGM == 1), "tail rows need a single cout tile");
   static_assert(PREC == 0 || (PREC == 1 && CK == 16 && TAIL == 0 && WM == 1 && WN == 2 && WGM == 2 && WGN == 2),
                 "the bf16x3 build: 64 x 128 tiles, 16-channel chunks, no tail rows");
+  static_assert(POST == 0 || (KS == 1 && TAIL == 0 && PREC == 0), "the post-activation addend: exact fp32 1x1 builds");
   constexpr int TM = WGM * WM * 32;
   constexpr int TMA = TM + TAIL;              // rows of the LDS A image
   constexpr int TN = WGN * WN * 32;
@@ -595,6 +600,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
         for (int r = 0; r < 16; ++r) asm volatile("" : "+v"(bias_r[i][r]));
     }
     const ptrdiff_t mask_off = e_mask ? e_mask - e_out : 0;
+    const ptrdiff_t add_off = POST ? a.addend - e_out : 0;
     // full: the workgroup's tile lies inside the output (every cout row and every pixel column exists) -- uniform, and then
     // no store is predicated: the row and column tests cost an exec-mask sequence each, 600 scalar instructions per wave in
     // front of the 64 stores of a K = 64 GEMM (SQ counters: 4.8 SALU per MFMA on 64 -> 576 @56^2)
@@ -616,6 +622,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
                 float v = acc[i][j][r] + b;
                 if (decltype(acc_mode)::value) v += *op;          // accumulate into the destination (gradient sums)
                 if (relu) v = fmaxf(v, 0.f);
+                if (POST) v = op[add_off] + v;                    // (read before this thread's own store: out may be the addend)
                 if (decltype(mask_mode)::value) v = (op[mask_off] > 0.f) ? v : 0.f;   // the producer's ReLU, looking backward
                 if (decltype(nt_mode)::value) __builtin_nontemporal_store(v, op);   // output larger than the Infinity Cache: stream it
                 else *op = v;
@@ -692,9 +699,9 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
 }
 
 // (PREC 3x3: 55 KB of A image + the plane -- two workgroups per CU)
-template <int KS, int WGM, int WGN, int WM, int WN, int CK, int MAXPOS, int TAIL = 0, int PREC = 0>
+template <int KS, int WGM, int WGN, int WM, int WN, int CK, int MAXPOS, int TAIL = 0, int PREC = 0, int POST = 0>
 __global__ __launch_bounds__(WGM* WGN * 64, PREC ? (KS == 1 ? 3 : 2) : (KS == 3 && WGM == 2 && WGN == 2 && WM == 2 && WN == 2 && MAXPOS == 1) || (KS == 1 && CK == 16) ? 3 : 1) void conv_igemm_kernel(ConvArgs a) {
-  conv_igemm_body<KS, WGM, WGN, WM, WN, CK, MAXPOS, TAIL, PREC>(a, (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.y);
+  conv_igemm_body<KS, WGM, WGN, WM, WN, CK, MAXPOS, TAIL, PREC, POST>(a, (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.y);
 }
 
 // Up to three INDEPENDENT convolutions in one launch (round 6: the three FPN-wide semantic_transform_in 1x1 convolutions of
@@ -937,7 +944,7 @@ static int conv_split_choice(int chunks, bool k3, int Smax, long long out_floats
   return S;
 }
 
-template <int KS, int WGM, int WGN, int WM, int WN, int CK, int MAXPOS, int TAIL = 0, int PREC = 0>
+template <int KS, int WGM, int WGN, int WM, int WN, int CK, int MAXPOS, int TAIL = 0, int PREC = 0, int POST = 0>
 int launch_conv_mp(ConvArgs& a, hipStream_t st) {
   constexpr int TM = WGM * WM * 32;
   constexpr int TN = WGN * WN * 32;
@@ -949,13 +956,13 @@ int launch_conv_mp(ConvArgs& a, hipStream_t st) {
     // (the bf16x3 3x3 build: 54 KB of A image + 21 KB of plane at 14 x 14; two workgroups per CU)
     if (!PREC || lds_bytes > 80 * 1024) return DM_ERR_UNSUPPORTED;
     static bool raised[DM_MAX_DEVICES] = {false};
-    const int rc = dm_ensure_lds_limit(reinterpret_cast<const void*>(&conv_igemm_kernel<KS, WGM, WGN, WM, WN, CK, MAXPOS, TAIL, PREC>),
+    const int rc = dm_ensure_lds_limit(reinterpret_cast<const void*>(&conv_igemm_kernel<KS, WGM, WGN, WM, WN, CK, MAXPOS, TAIL, PREC, POST>),
                                        80 * 1024, raised);
     if (rc != DM_OK) return rc;
   }
   // ---- split-K for launches that leave most of the chip idle (a caller-provided workspace, one launch per call)
   a.ksplit = 1;
-  if (a.ws && a.shuffle == 0 && a.q_begin == 0) {
+  if (a.ws && a.shuffle == 0 && a.q_begin == 0 && !POST) {
     constexpr int CKS = CK;
     int chunks = 0;
     for (int s_ = 0; s_ < a.num_srcs; ++s_) chunks += dm_ceil_div(a.src_c[s_], CKS);
@@ -980,7 +987,7 @@ int launch_conv_mp(ConvArgs& a, hipStream_t st) {
     const float* mask = a.mask;
     float* out = a.out;
     const int flags = a.relu, oct = a.out_ch_total, oco = a.out_ch_offset;
-    DM_LAUNCH((conv_igemm_kernel<KS, WGM, WGN, WM, WN, CK, MAXPOS, TAIL, PREC>), dim3(a.MT * NTiles, a.ksplit), dim3(NT), lds_bytes, st, a);
+    DM_LAUNCH((conv_igemm_kernel<KS, WGM, WGN, WM, WN, CK, MAXPOS, TAIL, PREC, POST>), dim3(a.MT * NTiles, a.ksplit), dim3(NT), lds_bytes, st, a);
     int rc = dm_check_launch();
     if (rc != DM_OK) return rc;
     const long long total = a.ws_stride;
@@ -994,11 +1001,11 @@ int launch_conv_mp(ConvArgs& a, hipStream_t st) {
                 a.ksplit, a.ws_stride, a.NB, a.Cout, a.HW, bias, flags, out, oct, oco, mask);
     return dm_check_launch();
   }
-  DM_LAUNCH((conv_igemm_kernel<KS, WGM, WGN, WM, WN, CK, MAXPOS, TAIL, PREC>), dim3(a.MT * NTiles), dim3(NT), lds_bytes, st, a);
+  DM_LAUNCH((conv_igemm_kernel<KS, WGM, WGN, WM, WN, CK, MAXPOS, TAIL, PREC, POST>), dim3(a.MT * NTiles), dim3(NT), lds_bytes, st, a);
   return dm_check_launch();
 }
 
-template <int KS, int WGM, int WGN, int WM, int WN, int CK, int TAIL = 0, int PREC = 0>
+template <int KS, int WGM, int WGN, int WM, int WN, int CK, int TAIL = 0, int PREC = 0, int POST = 0>
 int launch_conv(ConvArgs& a, hipStream_t st) {
   constexpr int TM = WGM * WM * 32;
   constexpr int TN = WGN * WN * 32;
@@ -1022,7 +1029,7 @@ int launch_conv(ConvArgs& a, hipStream_t st) {
   }
   a.Wp = 0;
   a.plane = TN;
-  return launch_conv_mp<KS, WGM, WGN, WM, WN, CK, 1, TAIL, PREC>(a, st);
+  return launch_conv_mp<KS, WGM, WGN, WM, WN, CK, 1, TAIL, PREC, POST>(a, st);
 }
 
 // One grouped launch (dm_conv2d_group_fwd / dm_deconv2x2_group_fwd) of the problems g.a[0 .. count): the per-problem
@@ -1216,7 +1223,7 @@ static int conv2d_launch(const float* const* srcs, const int* src_channels, cons
                          int num_srcs, int NB, int H, int W,
                          const float* w_packed, const float* bias, int Cout, int ksize, int relu, float* out,
                          int out_ch_total, int out_ch_offset, const float* mask, dm_stream_t stream, float* ws = nullptr,
-                         long long ws_floats = 0);
+                         long long ws_floats = 0, const float* addend = nullptr);
 
 extern "C" int dm_conv2d_fwd(const float* const* srcs, const int* src_channels, const long long* src_batch_strides,
                              int num_srcs, int NB, int H, int W,
@@ -1264,11 +1271,22 @@ extern "C" int dm_conv2d_fwd_masked(const float* const* srcs, const int* src_cha
                        out_ch_total, out_ch_offset, mask, stream);
 }
 
+// (K26) out = addend + act(conv1x1(srcs) + bias): dm_conv2d_fwd's launch with the POST epilogue.  addend: the layout of out
+// (channels [out_ch_offset, out_ch_offset + Cout) of [NB, out_ch_total, H, W]); it may be out.
+extern "C" int dm_conv2d_post_add_fwd(const float* const* srcs, const int* src_channels, const long long* src_batch_strides,
+                                      int num_srcs, int NB, int H, int W, const float* w_packed, const float* bias, int Cout,
+                                      int ksize, int relu, const float* addend, float* out, int out_ch_total, int out_ch_offset,
+                                      dm_stream_t stream) {
+  if (!addend) return DM_ERR_INVALID_ARG;
+  return conv2d_launch(srcs, src_channels, src_batch_strides, num_srcs, NB, H, W, w_packed, bias, Cout, ksize, relu, out,
+                       out_ch_total, out_ch_offset, nullptr, stream, nullptr, 0, addend);
+}
+
 static int conv2d_launch(const float* const* srcs, const int* src_channels, const long long* src_batch_strides,
                          int num_srcs, int NB, int H, int W,
                          const float* w_packed, const float* bias, int Cout, int ksize, int relu, float* out,
                          int out_ch_total, int out_ch_offset, const float* mask, dm_stream_t stream, float* ws,
-                         long long ws_floats) {
+                         long long ws_floats, const float* addend) {
   if (!srcs || !src_channels || num_srcs < 1 || num_srcs > DM_MAX_SOURCES || !w_packed || !out) return DM_ERR_INVALID_ARG;
   if (NB < 0 || H <= 0 || W <= 0 || Cout <= 0 || (ksize != 1 && ksize != 3)) return DM_ERR_INVALID_ARG;
   if (out_ch_offset < 0 || out_ch_offset + Cout > out_ch_total) return DM_ERR_INVALID_ARG;
@@ -1305,6 +1323,14 @@ static int conv2d_launch(const float* const* srcs, const int* src_channels, cons
   // below); accumulating launches read the destination and keep the default policy
   if (!(relu & 2) && (long long)NB * Cout * H * W * 4 > (192LL << 20)) a.relu |= 4;
   hipStream_t st = (hipStream_t)stream;
+  if (addend) {
+    // (K26) the POST builds: exact fp32 1x1, flags ReLU only, no split, default store policy
+    if (ksize != 1 || bf16x3) return DM_ERR_UNSUPPORTED;
+    if ((relu & ~1) || mask) return DM_ERR_INVALID_ARG;
+    a.addend = addend;
+    a.relu = relu & 1;
+    a.ws = nullptr;
+  }
   if (bf16x3) {
     // one build per kernel size: 64 couts x 128 pixels, four waves of 32 x 64 (see the kernel's header); a workspace
     // lets it split K as the exact launches do (launch_conv_mp's cost model, 16-channel chunks)
@@ -1381,16 +1407,17 @@ static int conv2d_launch(const float* const* srcs, const int* src_channels, cons
     // for the 64-cout build: inside the noise, not kept.  DM_CONV1_SMALL_WGS: the threshold in tiles (0: off), for A/B runs.
     static const int small_env = getenv("DM_CONV1_SMALL_WGS") ? atoi(getenv("DM_CONV1_SMALL_WGS")) : -1;
     const int small_wgs = small_env >= 0 ? small_env : (5 * dm_num_cus()) / 4;
+    // (the POST builds take the tiles the plain launch of the shape takes: the same products in the same order)
     if (!(relu & 2) && !mask && dm_ceil_div(a.CoutP, 128) * dm_ceil_div(a.Q, 128) <= small_wgs)
-      return launch_conv<1, 4, 1, 1, 1, 32>(a, st);
-    return launch_conv<1, 2, 2, 2, 2, 16>(a, st);
+      return addend ? launch_conv<1, 4, 1, 1, 1, 32, 0, 0, 1>(a, st) : launch_conv<1, 4, 1, 1, 1, 32>(a, st);
+    return addend ? launch_conv<1, 2, 2, 2, 2, 16, 0, 0, 1>(a, st) : launch_conv<1, 2, 2, 2, 2, 16>(a, st);
   }
   if (Cout > 32) {
     // 64 couts x 128 px as 4 waves of 32 x 64: 0.437 -> 0.379 ms on 576 -> 64 @56^2 x 128 RoIs, 0.098 -> 0.089 ms on
     // 64 -> 64 x 256 (the other tilings tried: docs/HISTORY.md, round 3); one k order per output.
-    return launch_conv<1, 2, 2, 1, 2, 16>(a, st);
+    return addend ? launch_conv<1, 2, 2, 1, 2, 16, 0, 0, 1>(a, st) : launch_conv<1, 2, 2, 1, 2, 16>(a, st);
   }
-  return launch_conv<1, 1, 4, 1, 1, 32>(a, st);
+  return addend ? launch_conv<1, 1, 4, 1, 1, 32, 0, 0, 1>(a, st) : launch_conv<1, 1, 4, 1, 1, 32>(a, st);
 }
 
 // ---------------------------------------------------------------------------

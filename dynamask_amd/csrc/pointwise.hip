@@ -377,6 +377,45 @@ __global__ __launch_bounds__(256) void upsample2x_kernel(const float* __restrict
   }
 }
 
+// ------------------------------------------------------------------ K26
+// Bilinear resize to any size, align_corners=True, no antialiasing (F.interpolate(size=..., mode='bilinear',
+// align_corners=True): FusedSemanticHead's resize of P2 / P4..P6 to the fusion level).  The source coordinate is
+// dst * (in - 1) / (out - 1) (0 when out == 1), the rounded product and the fma chain of upsample2x_kernel's
+// align_corners branch -- at exactly x2 the two kernels give the same bits.
+struct ResizeTap {
+  int i0, i1;
+  float l, h;
+};
+__device__ __forceinline__ float dm_resize_ac_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f; }
+__device__ __forceinline__ ResizeTap dm_resize_ac_tap(float scale, int o, int in) {
+  const float s = dm_mul_rn(scale, (float)o);
+  ResizeTap t;
+  t.i0 = min((int)s, in - 1);
+  t.i1 = t.i0 + ((t.i0 < in - 1) ? 1 : 0);
+  t.l = s - (float)t.i0;
+  t.h = 1.f - t.l;
+  return t;
+}
+
+// One thread = one output pixel (consecutive lanes: consecutive pixels of a row, coalesced stores; the taps of a row
+// come from at most two source rows, which the lanes share through the caches).
+__global__ __launch_bounds__(256) void resize_bilinear_ac_kernel(const float* __restrict__ in, long long NC, int H, int W,
+                                                                 int OH, int OW, float* __restrict__ out) {
+  const long long total = NC * OH * OW;
+  const float rh = dm_resize_ac_scale(H, OH), rw = dm_resize_ac_scale(W, OW);
+  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
+       idx += (long long)gridDim.x * blockDim.x) {
+    const int ox = (int)(idx % OW);
+    const long long t = idx / OW;
+    const int oy = (int)(t % OH);
+    const long long nc = t / OH;
+    const ResizeTap ty = dm_resize_ac_tap(rh, oy, H), tx = dm_resize_ac_tap(rw, ox, W);
+    const float* r0 = in + (nc * H + ty.i0) * (long long)W;
+    const float* r1 = in + (nc * H + ty.i1) * (long long)W;
+    out[idx] = dm_up2x_interp(ty.h, ty.l, tx.h, tx.l, r0[tx.i0], r0[tx.i1], r1[tx.i0], r1[tx.i1]);
+  }
+}
+
 // Half-pixel (align_corners=False) x2 fast path, W even: a thread owns two horizontally adjacent
 // input pixels, i.e. a 2 x 4 block of outputs, and reads the 3 x 4 input neighbourhood once
 // (1.5 loads per output instead of 4); two 16-byte stores.  The interpolation weights are the
@@ -949,6 +988,16 @@ extern "C" int dm_upsample2x_bilinear_fwd(const float* in, int NC, int H, int W,
   const int blocks = (int)min((size_t)dm_ceil_div((long long)total, 256), (size_t)32768);
   DM_LAUNCH(upsample2x_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, in, NC, H, W, align_corners,
                      relu, out);
+  return dm_check_launch();
+}
+
+extern "C" int dm_resize_bilinear_fwd(const float* in, long long NC, int H, int W, int OH, int OW, float* out,
+                                      dm_stream_t stream) {
+  if (!in || !out || NC < 0 || H <= 0 || W <= 0 || OH <= 0 || OW <= 0) return DM_ERR_INVALID_ARG;
+  if (NC == 0) return DM_OK;
+  const long long total = NC * OH * OW;
+  const int blocks = (int)min((long long)dm_ceil_div(total, 256), 65536LL);
+  DM_LAUNCH(resize_bilinear_ac_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, in, NC, H, W, OH, OW, out);
   return dm_check_launch();
 }
 

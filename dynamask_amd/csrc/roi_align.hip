@@ -191,7 +191,36 @@ __device__ __forceinline__ void roi_bin_fast(const RoiArgs& a, const float* __re
   }
 }
 
-template <bool BWD>
+// What the forward does with a bin average (K26, dm_roi_align_add_fwd): MODE 0 stores it (RoIAlign); MODE 1 adds it to
+// out[k, c, ph, pw] (out [N, C, P, P] holds the RoI features the map's features join); MODE 2 adds the mean of each 2 x 2
+// block of bins to out[k, c, ph / 2, pw / 2] (out [N, C, P / 2, P / 2]: adaptive_avg_pool2d P -> P / 2 of the bins, then
+// the add).  In MODE 2 thread t holds bin (2 (o / (P / 2)) + (s >> 1), 2 (o % (P / 2)) + (s & 1)), o = t >> 2, s = t & 3:
+// the four bins of a block sit in four neighbouring lanes and are summed as (a + b) + (c + d) by two lane exchanges.
+template <int MODE>
+__device__ __forceinline__ void roi_bin_of_thread(int t, int P, int& ph, int& pw) {
+  if (MODE == 2) {
+    const int o = t >> 2, s = t & 3, P2 = P >> 1;
+    const int oh = o / P2;
+    ph = 2 * oh + (s >> 1);
+    pw = 2 * (o - oh * P2) + (s & 1);
+  } else {
+    ph = t / P;
+    pw = t - ph * P;
+  }
+}
+// a product that stays a product: the add that follows it in MODE 1 / 2 must not be contracted into an fma with it
+// (MODE 0 stores the rounded product, and MODE 1 promises that value plus the feature)
+__device__ __forceinline__ float roi_mul_rn(float x, float y) {
+#pragma clang fp contract(off)
+  return x * y;
+}
+// the 2 x 2 block mean of MODE 2 (every lane of the block returns it)
+__device__ __forceinline__ float roi_block_mean(float v) {
+  const float s = v + __shfl_xor(v, 1, 64);
+  return (s + __shfl_xor(s, 2, 64)) * 0.25f;
+}
+
+template <bool BWD, int MODE = 0>
 __device__ __forceinline__ void roi_bin_generic(const RoiArgs& a, const float* __restrict__ f, float* __restrict__ gf,
                                                 int Hl, int Wl, float sh, float sw, float bh, float bw, int gh, int gw,
                                                 float inv_count, int ph, int pw, int k, int c0, int c1) {
@@ -223,7 +252,16 @@ __device__ __forceinline__ void roi_bin_generic(const RoiArgs& a, const float* _
         }
       }
     }
-    if (!BWD) a.out[oidx] = acc * inv_count;
+    if (!BWD) {
+      if (MODE == 0) a.out[oidx] = acc * inv_count;
+      else if (MODE == 1) a.out[oidx] = a.out[oidx] + roi_mul_rn(acc, inv_count);
+      else {
+        const float m = roi_block_mean(roi_mul_rn(acc, inv_count));
+        const int P2 = P >> 1;
+        float* o = a.out + (((size_t)k * a.C + c) * P2 + (ph >> 1)) * P2 + (pw >> 1);
+        if (((ph | pw) & 1) == 0) *o = *o + m;
+      }
+    }
   }
 }
 
@@ -437,7 +475,7 @@ __device__ __forceinline__ void axis_stencil(float start, float bin, int g, int 
   }
 }
 
-template <int G>
+template <int G, int MODE = 0>
 __device__ __forceinline__ void roi_tile_fwd(const RoiArgs& a, const float* __restrict__ fimg, int Hl, int Wl, float sh,
                                              float sw, float bh, float bw, int gh, int gw, float inv_count, int k,
                                              int c0, int c1, const TileGeom tg, float4* __restrict__ lds) {
@@ -446,8 +484,22 @@ __device__ __forceinline__ void roi_tile_fwd(const RoiArgs& a, const float* __re
   const int tid = threadIdx.x;
   const int P = a.P, PP = P * P;
   const bool active = tid < PP;
-  const int ph = active ? (int)__umulhi((unsigned)tid, 0xFFFFFFFFu / (unsigned)P + 1u) : 0;      // tid / P (P >= 2)
-  const int pw = active ? tid - ph * P : 0;
+  int ph = active ? (int)__umulhi((unsigned)tid, 0xFFFFFFFFu / (unsigned)P + 1u) : 0;      // tid / P (P >= 2)
+  int pw = active ? tid - ph * P : 0;
+  if (MODE == 2 && active) roi_bin_of_thread<2>(tid, P, ph, pw);
+  // MODE 0 / 1: the bin's place in the output plane is tid; MODE 2: the block's place in the pooled plane
+  const int PPo = MODE == 2 ? PP >> 2 : PP;
+  const bool writes = MODE != 2 || (tid & 3) == 0;
+  // one value of a channel plane: store (MODE 0), add (MODE 1), or block mean and add (MODE 2)
+  auto emit = [&](float v, char* plane_ptr) {
+    if (MODE == 0) {
+      __builtin_nontemporal_store(v, reinterpret_cast<float*>(plane_ptr));
+    } else {
+      if (MODE == 2) v = roi_block_mean(v);
+      float* o = reinterpret_cast<float*>(plane_ptr);
+      if (writes) *o = *o + v;
+    }
+  };
   const int plane_px = tg.FH * tg.pitch;              // <= kBufPx (checked by the caller)
   // as many channel quads per batch as the buffer holds: the staging is bound by bytes in
   // flight, so every fetch should fill the 2 x 4 x 16-byte loads each thread can issue
@@ -559,9 +611,9 @@ __device__ __forceinline__ void roi_tile_fwd(const RoiArgs& a, const float* __re
       const int nq = min(NQ, (c1 - cb) >> 2);
       const float4* t = lds + buf * kBufPx;
       // (uniform base + 32-bit lane offset; C % 4 == 0 and CT % 4 == 0: a quad is never cut by c1)
-      char* const ob = reinterpret_cast<char*>(a.out + ((size_t)k * a.C + cb) * PP);
-      const unsigned ot = (unsigned)tid << 2;
-      const size_t PB = (size_t)PP * 4;
+      char* const ob = reinterpret_cast<char*>(a.out + ((size_t)k * a.C + cb) * PPo);
+      const unsigned ot = (unsigned)(MODE == 2 ? tid >> 2 : tid) << 2;
+      const size_t PB = (size_t)PPo * 4;
       if (G == 0) {
         // run-time grid (slivers): samples outermost, groups of 4 channel quads accumulate per sample
         for (int q0 = 0; q0 < nq; q0 += 4) {
@@ -596,10 +648,17 @@ __device__ __forceinline__ void roi_tile_fwd(const RoiArgs& a, const float* __re
             const int q = q0 + u;
             if (q < nq) {
               char* const oq = ob + (size_t)(4 * q) * PB;
-              *reinterpret_cast<float*>(oq + ot) = acc[u].x;
-              *reinterpret_cast<float*>(oq + PB + ot) = acc[u].y;
-              *reinterpret_cast<float*>(oq + 2 * PB + ot) = acc[u].z;
-              *reinterpret_cast<float*>(oq + 3 * PB + ot) = acc[u].w;
+              if (MODE == 0) {
+                *reinterpret_cast<float*>(oq + ot) = acc[u].x;
+                *reinterpret_cast<float*>(oq + PB + ot) = acc[u].y;
+                *reinterpret_cast<float*>(oq + 2 * PB + ot) = acc[u].z;
+                *reinterpret_cast<float*>(oq + 3 * PB + ot) = acc[u].w;
+              } else {
+                emit(acc[u].x, oq + ot);
+                emit(acc[u].y, oq + PB + ot);
+                emit(acc[u].z, oq + 2 * PB + ot);
+                emit(acc[u].w, oq + 3 * PB + ot);
+              }
             }
           }
         }
@@ -633,10 +692,10 @@ __device__ __forceinline__ void roi_tile_fwd(const RoiArgs& a, const float* __re
           // cold and full of another kernel's data -- 86 -> 81 us from cold caches, cache-warm and the headline step unchanged
           // (round 4 had tried them cache-warm only: no difference there).  The same hint on the LOADS costs 30 us: the maps
           // are shared by neighbouring workgroups through the caches.
-          __builtin_nontemporal_store(acc.x, reinterpret_cast<float*>(oq + ot));
-          __builtin_nontemporal_store(acc.y, reinterpret_cast<float*>(oq + PB + ot));
-          __builtin_nontemporal_store(acc.z, reinterpret_cast<float*>(oq + 2 * PB + ot));
-          __builtin_nontemporal_store(acc.w, reinterpret_cast<float*>(oq + 3 * PB + ot));
+          emit(acc.x, oq + ot);
+          emit(acc.y, oq + PB + ot);
+          emit(acc.z, oq + 2 * PB + ot);
+          emit(acc.w, oq + 3 * PB + ot);
         }
       }
     }
@@ -722,7 +781,10 @@ __global__ __launch_bounds__(256) void roi_order_kernel(RoiArgs a, float* __rest
   }
 }
 
-__global__ __launch_bounds__(256, 4) void roi_align_tile_kernel(RoiArgs a) {
+// MODE 0: the RoIAlign; MODE 1 / 2 (K26, dm_roi_align_add_fwd): the same extraction, its bins added into the RoI features
+// or pooled 2 x 2 first (P even, so P * P is a multiple of 4 and the four lanes of a block are live together)
+template <int MODE>
+__global__ __launch_bounds__(256, MODE == 2 ? 2 : 4) void roi_align_tile_kernel(RoiArgs a) {      // (MODE 2: the block mean keeps more live values: no VGPR cap at 128, no scratch)
   extern __shared__ __attribute__((aligned(16))) float4 lds4[];
   const int chunks = (a.C + a.CT - 1) / a.CT;
   int k, chunk;
@@ -764,8 +826,12 @@ __global__ __launch_bounds__(256, 4) void roi_align_tile_kernel(RoiArgs a) {
   const float inv_count = 1.0f / (float)max(gh * gw, 1);
   const float* fimg = flvl + (bad_batch ? 0 : (size_t)b * a.C * Hl * Wl);
   if (gh <= 0 || gw <= 0 || bad_batch) {
-    // empty sampling grid (degenerate RoI) / malformed batch index -> zeros
-    for (int i = threadIdx.x; i < (c1 - c0) * PP; i += blockDim.x) a.out[((size_t)k * a.C + c0) * PP + i] = 0.f;
+    // empty sampling grid (degenerate RoI) / malformed batch index -> zeros (MODE 1 / 2: the zeros are added, -0 -> +0)
+    const int PPo = MODE == 2 ? PP >> 2 : PP;
+    for (int i = threadIdx.x; i < (c1 - c0) * PPo; i += blockDim.x) {
+      float* o = a.out + ((size_t)k * a.C + c0) * PPo + i;
+      *o = MODE == 0 ? 0.f : *o + 0.f;
+    }
     return;
   }
   {
@@ -788,7 +854,7 @@ __global__ __launch_bounds__(256, 4) void roi_align_tile_kernel(RoiArgs a) {
     tg.ymax = min(ylast + 1, Hl - 1);
     tg.xmax = min(xlast + 1, Wl - 1);
     const int px = tg.FH * tg.pitch;
-#define DM_ROI_TILE(GG) roi_tile_fwd<GG>(a, fimg, Hl, Wl, sh, sw, bh, bw, gh, gw, inv_count, k, c0, c1, tg, lds4)
+#define DM_ROI_TILE(GG) roi_tile_fwd<GG, MODE>(a, fimg, Hl, Wl, sh, sw, bh, bw, gh, gw, inv_count, k, c0, c1, tg, lds4)
     // with the FPN level map the footprint stays below ~1700 pixels (a 200 x 4 sliver)
     if (px <= kTileFloats4) {
       if (!merged) DM_ROI_TILE(0);
@@ -801,11 +867,12 @@ __global__ __launch_bounds__(256, 4) void roi_align_tile_kernel(RoiArgs a) {
 #undef DM_ROI_TILE
   }
   for (int pos = threadIdx.x; pos < PP; pos += blockDim.x) {
-    const int ph = pos / P;
-    const int pw = pos - ph * P;
-    roi_bin_generic<false>(a, fimg, nullptr, Hl, Wl, sh, sw, bh, bw, gh, gw, inv_count, ph, pw, k, c0, c1);
+    int ph, pw;
+    roi_bin_of_thread<MODE>(pos, P, ph, pw);
+    roi_bin_generic<false, MODE>(a, fimg, nullptr, Hl, Wl, sh, sw, bh, bw, gh, gw, inv_count, ph, pw, k, c0, c1);
   }
 }
+
 
 // ---------------------------------------------------------------------------
 // Forward kernel for larger output grids (16 < P <= 64: the 56x56 extraction on P2 that
@@ -1400,7 +1467,7 @@ int roi_align_fwd_impl(const float* const* feats, const int* H, const int* W, co
     a.order = 1;
     int chunks = dm_ceil_div(C, a.CT);
     if (chunks % 8 != 0) a.order = 0;
-    DM_LAUNCH(roi_align_tile_kernel, dim3(N * chunks), dim3(256), (kTileFloats4 + 64) * sizeof(float4), (hipStream_t)stream, a);
+    DM_LAUNCH(roi_align_tile_kernel<0>, dim3(N * chunks), dim3(256), (kTileFloats4 + 64) * sizeof(float4), (hipStream_t)stream, a);
     return dm_check_launch();
   }
   if (tile_ok) {
@@ -1412,7 +1479,7 @@ int roi_align_fwd_impl(const float* const* feats, const int* H, const int* W, co
     a.order = 1;
     int chunks = dm_ceil_div(C, a.CT);
     if (chunks % 8 != 0) a.order = 0;
-    DM_LAUNCH(roi_align_tile_kernel, dim3(N * chunks), dim3(256), (kTileFloats4 + 64) * sizeof(float4), (hipStream_t)stream, a);
+    DM_LAUNCH(roi_align_tile_kernel<0>, dim3(N * chunks), dim3(256), (kTileFloats4 + 64) * sizeof(float4), (hipStream_t)stream, a);
     return dm_check_launch();
   }
   bool band_ok = P > 16 && P <= 64 && C % 4 == 0;
@@ -1447,6 +1514,33 @@ extern "C" int dm_roi_align_fwd(const float* const* feats, const int* H, const i
                                 float finest_scale, float* out, int32_t* levels_out, dm_stream_t stream) {
   return roi_align_fwd_impl(feats, H, W, spatial_scales, num_levels, B, C, rois, N, P, sampling_ratio, finest_scale, out,
                             levels_out, nullptr, 0, stream);
+}
+
+// (K26) the RoIAlign of ONE map added into RoI features, no [N, C, P, P] intermediate.  The launch is dm_roi_align_fwd's
+// tile launch (16 channels per workgroup, the XCD-aware order): MODE 1 adds where that launch stores, the same bins.
+extern "C" int dm_roi_align_add_fwd(const float* feat, int B, int C, int H, int W, float spatial_scale, const float* rois,
+                                    int N, int P, int sampling_ratio, int pool, float* out, dm_stream_t stream) {
+  RoiArgs a;
+  if (pool != 1 && pool != 2) return DM_ERR_INVALID_ARG;
+  int rc = fill_args(a, &H, &W, &spatial_scale, 1, B, C, rois, N, P, sampling_ratio, 56.f);
+  if (rc != DM_OK) return rc;
+  if (N == 0) return DM_OK;
+  if (!feat || !out) return DM_ERR_INVALID_ARG;
+  if (P * P > 256 || P < 2 || C % 4 != 0 || (long long)H * W > (1 << 23) || (pool == 2 && (P & 1))) return DM_ERR_UNSUPPORTED;
+  a.feat[0] = feat;
+  a.out = out;
+  // the channels per workgroup of the launch the host binding's RoIAlign of these RoIs takes (32 where it orders them)
+  const RoiKnobs& kn = roi_knobs();
+  a.CT = (kn.sort && P * P >= 128 && N >= kn.sort_min && N <= kOrderMaxRois) ? 32 : 16;
+  a.order = 1;
+  const int chunks = dm_ceil_div(C, a.CT);
+  if (chunks % 8 != 0) a.order = 0;
+  if ((long long)N * chunks > 0x7fffffffLL) return DM_ERR_UNSUPPORTED;
+  if (pool == 1)
+    DM_LAUNCH(roi_align_tile_kernel<1>, dim3(N * chunks), dim3(256), (kTileFloats4 + 64) * sizeof(float4), (hipStream_t)stream, a);
+  else
+    DM_LAUNCH(roi_align_tile_kernel<2>, dim3(N * chunks), dim3(256), (kTileFloats4 + 64) * sizeof(float4), (hipStream_t)stream, a);
+  return dm_check_launch();
 }
 
 extern "C" long long dm_roi_align_workspace_bytes(int N, int P) {

@@ -1490,3 +1490,109 @@ def group_mask_scores(scores, labels, num_classes):
     import numpy as np
     scores, labels = np.asarray(scores), np.asarray(labels)
     return [scores[labels == i] for i in range(num_classes)]
+
+
+@HEADS.register_module()
+class HTCMaskHead(FCNMaskHead):
+    """htc_mask_head.py:8-43: FCNMaskHead whose input may carry the previous cascade stage's features (mask information
+    flow): ``x + relu(conv_res(res_feat))`` in front of the convs, and the features after the convs handed on.  ``conv_res``
+    and the add are ONE launch (ops.conv1x1_post_add: the addend joins after the ReLU; ``x`` is left as it was for the next
+    stage), always the exact fp32 kernel.  Inference only (the fork's ``FCNMaskHead.loss`` is broken: Quirk Q5)."""
+
+    def __init__(self, with_conv_res=True, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.with_conv_res = with_conv_res
+        if self.with_conv_res:
+            self.conv_res = ConvModule(self.conv_out_channels, self.conv_out_channels, 1)
+
+    def res_feat(self, x, res_feat=None):
+        """The features after the convs (htc_mask_head.py:27-33): what the next stage's ``conv_res`` and this stage's
+        upsample read."""
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError('HTCMaskHead is inference only (run under torch.no_grad()): its loss is '
+                                      'FCNMaskHead.loss, which the reference fork broke (Quirk Q5)')
+        if res_feat is not None:
+            assert self.with_conv_res
+            c = self.conv_res.conv
+            x = ops.conv1x1_post_add(res_feat, c.packed([res_feat.shape[1]]), c.bias.detach(), c.out_channels, x, relu=True)
+        for conv in self.convs:
+            x = conv(x)
+        return x
+
+    def logits(self, res_feat):
+        """htc_mask_head.py:36-40."""
+        x = res_feat
+        if self.upsample is not None:
+            x = self.upsample(x, relu=(self.upsample_method == 'deconv'))
+        return self.conv_logits.run(x)
+
+    def forward(self, x, res_feat=None, return_logits=True, return_feat=True):
+        res_feat = self.res_feat(x, res_feat)
+        outs = []
+        if return_logits:
+            outs.append(self.logits(res_feat))
+        if return_feat:
+            outs.append(res_feat)
+        return outs if len(outs) > 1 else outs[0]
+
+
+@HEADS.register_module()
+class FusedSemanticHead(nn.Module):
+    """fused_semantic_head.py:9-107 for inference: every FPN level resized to the fusion level's size
+    (``align_corners=True``), a 1x1 lateral conv + ReLU each, summed -- the fusion level first, then the others in
+    ascending order, each as ``x += relu(conv1x1(resize(feat)))`` --, ``num_convs`` 3x3 convs and the 1x1 embedding.
+    ``forward(feats)`` returns the embedded feature [B, conv_out_channels, H, W] of the B images of ``feats``; the
+    ``num_classes`` segmentation logits (``conv_logits``) are a training output and are not computed, their weights stay
+    in the ``state_dict``.  HIP: ops.resize_bilinear per level, the lateral conv and the add in one launch
+    (ops.conv1x1_post_add, in place into the sum), the 3x3 convs on the any-width kernel (ops.conv3x3_dil, dilation 1: a
+    100 x 168 map is wider than the tiles of ops.conv2d's 3x3 build stage), the embedding through ops.conv2d."""
+
+    def __init__(self, num_ins, fusion_level, num_convs=4, in_channels=256, conv_out_channels=256, num_classes=183,
+                 ignore_label=255, loss_weight=0.2, conv_cfg=None, norm_cfg=None):
+        super().__init__()
+        if not 0 <= fusion_level < num_ins:
+            raise ValueError(f'fusion_level {fusion_level} of {num_ins} inputs')
+        self.num_ins = num_ins
+        self.fusion_level = fusion_level
+        self.num_convs = num_convs
+        self.in_channels = in_channels
+        self.conv_out_channels = conv_out_channels
+        self.num_classes = num_classes
+        self.ignore_label = ignore_label
+        self.loss_weight = loss_weight
+        self.conv_cfg = conv_cfg
+        self.norm_cfg = norm_cfg
+        self.fp16_enabled = False
+        # (ConvModule raises NotImplementedError for a conv_cfg / norm_cfg other than None)
+        self.lateral_convs = nn.ModuleList([ConvModule(in_channels, in_channels, 1, conv_cfg=conv_cfg, norm_cfg=norm_cfg)
+                                            for _ in range(num_ins)])
+        # (the 3x3 convs see the whole stride-8 map: the any-width kernel, as RefineMask's and PointRefine's semantic convs)
+        self.convs = nn.ModuleList([DilatedConvModule(in_channels if i == 0 else conv_out_channels, conv_out_channels, 3,
+                                                      padding=1, dilation=1, conv_cfg=conv_cfg, norm_cfg=norm_cfg)
+                                    for i in range(num_convs)])
+        self.conv_embedding = ConvModule(conv_out_channels, conv_out_channels, 1, conv_cfg=conv_cfg, norm_cfg=norm_cfg)
+        self.conv_logits = _Conv(conv_out_channels, num_classes, 1)
+
+    def init_weights(self):
+        nn.init.kaiming_normal_(self.conv_logits.weight, mode='fan_out', nonlinearity='relu')
+        nn.init.constant_(self.conv_logits.bias, 0)
+
+    @torch.no_grad()
+    def forward(self, feats):
+        feats = list(feats)
+        if len(feats) != self.num_ins:
+            raise ValueError(f'FusedSemanticHead: {self.num_ins} feature maps expected, got {len(feats)}')
+        x = self.lateral_convs[self.fusion_level](feats[self.fusion_level].contiguous())
+        size = tuple(x.shape[-2:])
+        for i, feat in enumerate(feats):
+            if i == self.fusion_level:
+                continue
+            c = self.lateral_convs[i].conv
+            r = ops.resize_bilinear(feat.contiguous(), size)
+            ops.conv1x1_post_add(r, c.packed([r.shape[1]]), c.bias.detach(), c.out_channels, x, relu=True, out=x)
+        for conv in self.convs:
+            x = conv(x)
+        return self.conv_embedding(x)
+
+    def loss(self, mask_pred, labels):
+        raise NotImplementedError('FusedSemanticHead: the semantic segmentation loss is training (HTC is inference only here)')

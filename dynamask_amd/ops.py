@@ -2354,3 +2354,92 @@ def cascade_refine(rois, cls_score, bbox_pred, num_classes, img_tab, score_sum, 
                                   int(img_tab.shape[0]) if regress else 0, _p(score_sum), 1 if first else 0, _p(out),
                                   _stream()), 'dm_cascade_refine')
     return out
+
+
+# ------------------------------------------------------------------ Hybrid Task Cascade (dynamask_hip.h section K26)
+def resize_coords(n_in, n_out):
+    """The taps of ``resize_bilinear`` along one axis, on the host in fp32 as the kernel computes them: (low index,
+    high index, weight of the high tap) per output -- ``F.interpolate(align_corners=True)``'s rule, source coordinate
+    ``dst * (in - 1) / (out - 1)`` and 0 when ``out == 1``."""
+    import numpy as np
+    scale = np.float32(n_in - 1) / np.float32(n_out - 1) if n_out > 1 else np.float32(0)
+    src = (scale * np.arange(n_out, dtype=np.float32)).astype(np.float32)
+    lo = np.minimum(src.astype(np.int64), n_in - 1)
+    hi = np.minimum(lo + 1, n_in - 1)
+    return lo, hi, (src - lo.astype(np.float32)).astype(np.float32)
+
+
+def resize_bilinear(x, size, out=None):
+    """``F.interpolate(x, size=size, mode='bilinear', align_corners=True)`` of [N, C, H, W], up or down."""
+    _chk(x, 'x')
+    N, C, H, W = x.shape
+    OH, OW = int(size[0]), int(size[1])
+    if OH < 1 or OW < 1:
+        raise ValueError(f'resize_bilinear: size {size}')
+    if out is None:
+        out = torch.empty((N, C, OH, OW), device=x.device, dtype=torch.float32)
+    else:
+        _chk(out, 'out')
+        assert tuple(out.shape) == (N, C, OH, OW)
+    check(lib().dm_resize_bilinear_fwd(_p(x), N * C, H, W, OH, OW, _p(out), _stream()), 'dm_resize_bilinear_fwd')
+    return out
+
+
+def conv1x1_post_add(srcs, w_packed, bias, cout, addend, relu=True, out=None):
+    """``out = addend + act(conv1x1(cat(srcs)) + bias)``: the addend joins after the activation (``conv2d``'s
+    ``accumulate`` adds in front of it).  ``out`` defaults to a new tensor; it may be ``addend`` (in place).  Exact fp32
+    whatever the inference precision: the bits of ``conv2d(relu)`` followed by an fp32 add."""
+    if isinstance(srcs, torch.Tensor):
+        srcs = [srcs]
+    srcs = [_chk_src(s) for s in srcs]
+    _chk(w_packed, 'w_packed')
+    _chk(addend, 'addend')
+    if bias is not None:
+        _chk(bias, 'bias')
+    NB, _, H, W = srcs[0].shape
+    for s in srcs:
+        assert s.shape[0] == NB and s.shape[2] == H and s.shape[3] == W
+    if conv_layout(w_packed) != 'fp32':
+        raise ValueError('conv1x1_post_add: exact fp32 only (weights packed for bf16x3)')
+    assert w_packed.numel() == packed_floats(cout, 1, [s.shape[1] for s in srcs]), 'weights packed for other sources'
+    if tuple(addend.shape) != (NB, cout, H, W):
+        raise ValueError(f'addend: {[NB, cout, H, W]} expected, got {list(addend.shape)}')
+    if out is None:
+        out = torch.empty_like(addend)
+    else:
+        _chk(out, 'out')
+        assert out.shape == addend.shape
+    strides = (ctypes.c_longlong * len(srcs))(*[int(s.stride(0)) for s in srcs])
+    check(lib().dm_conv2d_post_add_fwd(_ptr_array(srcs), _int_array([s.shape[1] for s in srcs]), strides, len(srcs), NB, H,
+                                       W, _p(w_packed), _p(bias), cout, 1, 1 if relu else 0, _p(addend), _p(out), cout, 0,
+                                       _stream()), 'dm_conv2d_post_add_fwd')
+    return out
+
+
+def roi_align_pool(size, out_size):
+    """The pooling that joins ``size`` x ``size`` RoIAlign bins to ``out_size`` x ``out_size`` features in
+    ``roi_align_add_``: 1 (identity) or 2 (the exact 2 x 2 mean = ``adaptive_avg_pool2d`` size -> size / 2)."""
+    if size == out_size:
+        return 1
+    if size == 2 * out_size:
+        return 2
+    raise NotImplementedError(f'semantic RoI features of {size} x {size} join RoI features of {out_size} x {out_size} only '
+                              'by the identity or the 2 x 2 mean (adaptive_avg_pool2d with other windows: no kernel)')
+
+
+def roi_align_add_(feats, fmap, rois, size, spatial_scale, sampling_ratio=0):
+    """``feats += pool(RoIAlign_size(fmap, rois))`` in place, one launch: ``fmap`` [B, C, H, W] (one level, no level
+    mapping), ``rois`` [N, 5], ``feats`` [N, C, size, size] (identity) or [N, C, size / 2, size / 2] (2 x 2 mean)."""
+    _chk(feats, 'feats')
+    _chk(fmap, 'fmap')
+    _chk(rois, 'rois')
+    B, C, H, W = fmap.shape
+    N = rois.shape[0]
+    if feats.dim() != 4 or feats.shape[0] != N or feats.shape[1] != C or feats.shape[2] != feats.shape[3]:
+        raise ValueError(f'feats: [{N}, {C}, s, s] expected, got {list(feats.shape)}')
+    pool = roi_align_pool(int(size), int(feats.shape[2]))
+    if N == 0:
+        return feats
+    check(lib().dm_roi_align_add_fwd(_p(fmap), B, C, H, W, float(spatial_scale), _p(rois), N, int(size), int(sampling_ratio),
+                                     pool, _p(feats), _stream()), 'dm_roi_align_add_fwd')
+    return feats

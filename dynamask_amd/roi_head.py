@@ -1291,8 +1291,8 @@ class CascadeRoIHead(StandardRoIHead):
     DM_CASCADE_GROUPED=0: the stage chains one after the other).  The mask RoIAlign runs once when the stages' mask
     extractor configs are equal.  The mask prediction handed to the paste is the merged probabilities [n, 1, S, S]
     (``_mask_test_sigmoid = False``).  A meta with ``flip=True`` un-flips every stage's mask in ``simple_test`` as the
-    reference's ``merge_aug_masks`` call does (Quirk Q16).  Out of scope: training (Quirk Q5), graph capture, the shared
-    mask extractor form (``mask_roi_extractor=None``) and HTC."""
+    reference's ``merge_aug_masks`` call does (Quirk Q16).  Out of scope: training (Quirk Q5), graph capture and the shared
+    mask extractor form (``mask_roi_extractor=None``).  HybridTaskCascadeRoIHead builds on this head."""
 
     _mask_test_sigmoid = False
 
@@ -1519,11 +1519,176 @@ class CascadeRoIHead(StandardRoIHead):
         return super().aug_test(x, proposal_list, img_metas, rescale=True, encode=encode)
 
 
-def _htc_follow_up(name):
-    def __init__(self, *args, **kwargs):
-        raise NotImplementedError(f'{name} (Hybrid Task Cascade) builds on CascadeRoIHead and is the next step, not built yet')
-    return type(name, (nn.Module,), {'__init__': __init__, '__doc__': f'{name}: not built yet (HTC follows CascadeRoIHead).'})
+@HEADS.register_module()
+class HybridTaskCascadeRoIHead(CascadeRoIHead):
+    """htc_roi_head.py:11-560 for inference: CascadeRoIHead with (1) a semantic branch over the whole image
+    (``semantic_head``, a FusedSemanticHead) whose feature map is RoIAligned (``semantic_roi_extractor``) and added to the
+    RoI features of every box stage (pooled to their size) and of the mask branch (``semantic_fusion``), and (2) mask
+    information flow: stage i's mask head reads ``mask_feats + relu(conv_res_i(stage i - 1's features))``.
+
+    The semantic feature is computed once per public call and view and shared by the box stages and the mask branch: a
+    cache that lives for the duration of the outermost public entry point and is keyed on the identity of the view's
+    feature list; a partial entry point called alone computes it itself.  HIP: the fusion is ONE launch per use
+    (ops.roi_align_add_: no [N, 256, 14, 14] intermediate); the mask RoIAlign runs once (``mask_roi_extractor[-1]``); the
+    stages' conv chains run one after the other (the information flow orders them), their deconvs and logits convs as
+    one grouped launch each (ops.CASCADE_GROUPED, exact fp32), the merge is CascadeRoIHead's (Quirk Q16 included).
+    ``simple_test`` / ``aug_test`` never add a ``last_pred`` to the stage logits (only the reference's unused
+    ``_mask_forward_test`` does).  Quirks Q17-Q20 are kept.  Out of scope: training, graph capture."""
+
+    def __init__(self, num_stages, stage_loss_weights, semantic_roi_extractor=None, semantic_head=None,
+                 semantic_fusion=('bbox', 'mask'), interleaved=True, mask_info_flow=True, **kwargs):
+        super().__init__(num_stages, stage_loss_weights, **kwargs)
+        if not (self.with_bbox and self.with_mask):
+            raise ValueError('HybridTaskCascadeRoIHead needs bbox and mask heads (htc_roi_head.py:28)')
+        if not mask_info_flow:
+            raise NotImplementedError('mask_info_flow=False cannot run in the reference: HTCMaskHead.forward returns the list '
+                                      '[mask_pred, res_feat] and htc_roi_head.py:351 calls .sigmoid() on it (Quirk Q20)')
+        for h in self.mask_head:
+            if type(h).__name__ != 'HTCMaskHead':
+                raise NotImplementedError(f'mask information flow needs HTCMaskHead stages (got {type(h).__name__})')
+        if semantic_head is not None:
+            # (overwrites the 56 x 56 stride-4 extractor BaseRoIHead gives every RoI head: Quirk Q4)
+            self.semantic_roi_extractor = build_roi_extractor(semantic_roi_extractor)
+            self.semantic_head = build_head(semantic_head)
+        self.semantic_fusion = semantic_fusion
+        self.interleaved = interleaved
+        self.mask_info_flow = mask_info_flow
+        self._sem_cache = None          # {id(view feature list): (the list, its semantic feature)} inside a public call
+        self._sem_depth = 0
+        self._aug_mask = False          # inside aug_test_mask_probs (Quirk Q17)
+        if self.with_semantic:
+            if len(self.semantic_roi_extractor.roi_layers) != 1:
+                raise NotImplementedError('semantic_roi_extractor: one feature level (the semantic map)')
+            s = self._semantic_size()
+            if 'bbox' in self.semantic_fusion:
+                for e in self.bbox_roi_extractor:
+                    ops.roi_align_pool(s, e.roi_layers[0].output_size[0])           # (raises NotImplementedError)
+            # the mask branch: the identity only -- simple_test adds without pooling (Quirk Q18)
+            if ops.roi_align_pool(s, self.mask_roi_extractor[-1].roi_layers[0].output_size[0]) != 1:
+                raise NotImplementedError(f'semantic RoI features of {s} x {s} join mask RoI features of the same size only')
+
+    @property
+    def with_semantic(self):
+        return getattr(self, 'semantic_head', None) is not None
+
+    def init_weights(self, pretrained=None):
+        super().init_weights(pretrained)
+        if self.with_semantic:
+            self.semantic_head.init_weights()
+
+    def forward_train(self, *args, **kwargs):
+        raise NotImplementedError('HybridTaskCascadeRoIHead training: its mask loss ends in FCNMaskHead.loss, which the '
+                                  'reference fork broke (Quirk Q5); the semantic loss and the interleaved sampling are not built')
+
+    # ------------------------------------------------------------ the semantic feature of a view
+    def _semantic_size(self):
+        return self.semantic_roi_extractor.roi_layers[0].output_size[0]
+
+    def _semantic_feat(self, x):
+        """``semantic_head(x)`` of the view whose feature list is ``x`` (None without a semantic head); inside a public
+        entry point it is computed once per list object."""
+        if not self.with_semantic:
+            return None
+        if self._sem_cache is None:
+            return self.semantic_head(x)
+        e = self._sem_cache.get(id(x))
+        if e is None or e[0] is not x:
+            e = (x, self.semantic_head(x))          # (the list is held: its id cannot be reused while the entry lives)
+            self._sem_cache[id(x)] = e
+        return e[1]
+
+    def _fuse_semantic_(self, feats, x, rois):
+        """``feats += pool(RoIAlign(semantic feature, rois))`` (htc_roi_head.py:170-176 / :339-342), one launch."""
+        lay = self.semantic_roi_extractor.roi_layers[0]
+        return ops.roi_align_add_(feats, self._semantic_feat(x), rois.contiguous(), lay.output_size[0], lay.spatial_scale,
+                                  lay.sampling_ratio)
+
+    # ------------------------------------------------------------ bbox stages
+    def _bbox_forward_stage(self, i, x, rois):
+        """htc_roi_head.py:165-181."""
+        ext = self.bbox_roi_extractor[i]
+        feats = ext(x[:ext.num_inputs], rois)
+        if self.with_semantic and 'bbox' in self.semantic_fusion:
+            self._fuse_semantic_(feats, x, rois)
+        return self.bbox_head[i](feats)
+
+    # ------------------------------------------------------------ mask stages
+    def _grouped_ok(self):
+        """CascadeRoIHead's condition for the HTC stages' deconvs and logits convs (their conv chains never group)."""
+        if not ops.CASCADE_GROUPED[0] or ops.inference_precision() != 'fp32':
+            return False
+        h0 = self.mask_head[0]
+        for h in self.mask_head:
+            if h.upsample_method != 'deconv' or h.conv_out_channels != h0.conv_out_channels or \
+                    h.conv_logits.out_channels != h0.conv_logits.out_channels or h.scale_factor != h0.scale_factor:
+                return False
+        return True
+
+    @torch.no_grad()
+    def _stage_mask_logits(self, x, mask_rois):
+        """htc_roi_head.py:333-351 (simple_test) / :521-543 (aug_test): one RoIAlign, the semantic RoI feature added, the
+        stages' conv chains in sequence with information flow, then every stage's deconv and logits."""
+        ext = self.mask_roi_extractor[-1]
+        mask_feats = ext(x[:ext.num_inputs], mask_rois)
+        if self.with_semantic and (self._aug_mask or 'mask' in self.semantic_fusion):       # (Quirk Q17)
+            self._fuse_semantic_(mask_feats, x, mask_rois)
+        res, last = [], None
+        with ops.splitk_scope():
+            for h in self.mask_head:
+                last = h.res_feat(mask_feats, last)
+                res.append(last)
+        # (outside the split scope: both forms of the tail then give the same bits)
+        if not self._grouped_ok():
+            return [h.logits(r) for h, r in zip(self.mask_head, res)]
+        out = []
+        for s0 in range(0, self.num_stages, 3):
+            heads = [self.mask_head[i] for i in range(s0, min(s0 + 3, self.num_stages))]
+            ups = [h.upsample for h in heads]
+            wps = [u._pk.get('w', u.weight, lambda w: ops.pack_deconv_weight(w, precision='fp32'), precision='fp32') for u in ups]
+            xs = ops.deconv2x2_group(res[s0:s0 + 3], wps, [u.bias.detach() for u in ups], ups[0].out_channels, relu=True)
+            cls = [h.conv_logits for h in heads]
+            out += ops.conv1x1_group(xs, [c.packed([xs[0].shape[1]]) for c in cls], [c.bias.detach() for c in cls],
+                                     [c.out_channels for c in cls])
+        return out
+
+    @torch.no_grad()
+    def aug_test_mask_probs(self, x, img_metas, det_bboxes, det_labels):
+        self._aug_mask = True
+        try:
+            return self._scoped('aug_test_mask_probs', x, img_metas, det_bboxes, det_labels)
+        finally:
+            self._aug_mask = False
+
+    @torch.no_grad()
+    def aug_test_mask(self, x, img_metas, det_bboxes, det_labels, encode=False, _labels_host=None):
+        if det_bboxes.shape[0] == 0:
+            self._check_aug(x, img_metas)
+            return [[] for _ in range(self._segm_num_classes() - 1)]        # htc_roi_head.py:497-500 (Quirk Q19)
+        return self._scoped('aug_test_mask', x, img_metas, det_bboxes, det_labels, encode=encode, _labels_host=_labels_host)
+
+    # ------------------------------------------------------------ the public entry points hold the semantic cache
+    def _scoped(self, name, *args, **kwargs):
+        """CascadeRoIHead's ``name`` with the semantic cache open; the outermost call closes (and empties) it."""
+        if self._sem_depth == 0:
+            self._sem_cache = {}
+        self._sem_depth += 1
+        try:
+            return getattr(super(), name)(*args, **kwargs)
+        finally:
+            self._sem_depth -= 1
+            if self._sem_depth == 0:
+                self._sem_cache = None
 
 
-for _name in ('HybridTaskCascadeRoIHead', 'HTCMaskHead', 'FusedSemanticHead'):
-    HEADS.register_module(module=_htc_follow_up(_name))
+def _scoped_entry(name):
+    def entry(self, *args, **kwargs):
+        return self._scoped(name, *args, **kwargs)
+    entry.__name__ = name
+    entry.__doc__ = getattr(CascadeRoIHead, name).__doc__
+    return entry
+
+
+for _name in ('simple_test', 'batch_simple_test', 'aug_test', 'simple_test_bboxes', 'batch_simple_test_bboxes',
+              'aug_test_bboxes', 'simple_test_mask', 'batch_simple_test_mask', 'simple_test_mask_logits',
+              'batch_simple_test_mask_logits'):
+    setattr(HybridTaskCascadeRoIHead, _name, _scoped_entry(_name))

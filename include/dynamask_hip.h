@@ -59,7 +59,7 @@ const char* dm_error_string(int code);
  * selection, point gather, point MLP and scatter (section K22); Mask Scoring R-CNN's stride-2 3x3 convolution, IoU-head
  * input and mask scores (section K23); PointRefine's descending point selection, point-feature gather, point MLP and
  * multi-row scatter (section K24); Cascade Mask R-CNN's stage-grouped convolutions / deconvolutions and stage step
- * (section K25). */
+ * (section K25); Hybrid Task Cascade's resize, post-activation addend and RoIAlign-add (section K26). */
 int dm_abi_version(void);
 /* "libdynamask_hip abi=N arch=gfx950 compiler=<clang version> flags=<the product-wide flags of dynamask_amd/build.py>"
  * (static storage).  The library must be compiled WITHOUT packed fp32 instructions (flag "-packed-fp32-ops", see
@@ -968,6 +968,43 @@ int dm_deconv2x2_group_fwd(int count, const float* const* x, int NB, int C, int 
 int dm_cascade_refine(const float* rois, const float* cls_score, const float* bbox_pred, int n, int num_classes,
                       int class_agnostic, const float* means, const float* stds, float wh_ratio_clip, const float* img_shapes,
                       int num_images, float* score_sum, int first_stage, float* out_rois, dm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * K26  Hybrid Task Cascade inference (mmdet/models/roi_heads/htc_roi_head.py, mask_heads/fused_semantic_head.py,
+ *      mask_heads/htc_mask_head.py).  All exact fp32, deterministic.
+ *
+ * dm_resize_bilinear_fwd: F.interpolate(size=(OH, OW), mode='bilinear', align_corners=True) of in [NC, H, W] ->
+ * out [NC, OH, OW], up or down, no antialiasing (fused_semantic_head.py:91-92).  Source coordinate of output o along
+ * an axis: o * ((in - 1) / (out - 1)), the factor computed in fp32 and 0 when out == 1; low tap floor(.), high tap low + 1
+ * clamped to in - 1.  At OH = 2 H, OW = 2 W the bits are dm_upsample2x_bilinear_fwd(align_corners = 1)'s.
+ *
+ * dm_conv2d_post_add_fwd: out = addend + act(conv(srcs) + bias) -- the addend joins AFTER the activation (dm_conv2d_fwd's
+ * accumulate flag gives act(out + conv + bias)): FusedSemanticHead's lateral sum x += relu(conv1x1(resized level))
+ * (fused_semantic_head.py:93) and HTCMaskHead's x = mask_feats + relu(conv_res(res_feat)) (htc_mask_head.py:28-30).
+ * Arguments as dm_conv2d_fwd's; addend has out's layout (channels [out_ch_offset, out_ch_offset + Cout) of
+ * [NB, out_ch_total, H, W]) and may be out itself; no source may overlap out.  relu: bit 0 only (any other bit
+ * DM_ERR_INVALID_ARG); ksize 3 and the bf16x3 layout: DM_ERR_UNSUPPORTED.  The launch is dm_conv2d_fwd's launch of the
+ * shape with one more epilogue step: every output has the bits of dm_conv2d_fwd followed by an fp32 add.
+ *
+ * dm_roi_align_add_fwd: RoIAlign (aligned, avg, dm_roi_align_fwd's arithmetic with num_levels == 1: no level mapping) of
+ * ONE map feat [B, C, H, W] at P x P bins per RoI, added into RoI features without the [N, C, P, P] intermediate
+ * (htc_roi_head.py:170-176 for the box branch, :339-342 / :137-141 for the mask branch):
+ *   pool == 1: out [N, C, P, P]         out[n, c, y, x] += bin(n, c, y, x)   -- the bits of the extraction + an fp32 add,
+ *              the extraction being dm_roi_align_fwd_ws with the workspace it asks for where that call orders the RoIs
+ *              (P * P >= 128, DM_ROI_SORT_MIN <= N <= 1024), else dm_roi_align_fwd: the launch takes that call's channels
+ *              per workgroup, because bins of sampling grids above 4 x 4 differ in the last bit between the two;
+ *   pool == 2: out [N, C, P / 2, P / 2]  out[n, c, y, x] += ((b00 + b01) + (b10 + b11)) * 0.25 of the 2 x 2 block of bins
+ *              (adaptive_avg_pool2d P -> P / 2, P even): bin averages first, then the block mean, then the add.
+ * rois [N, 5] as dm_roi_align_fwd's (the batch column picks the image of feat; an index outside [0, B) adds zeros).
+ * P * P <= 256, P >= 2, C % 4 == 0 and H * W <= 2^23, else DM_ERR_UNSUPPORTED; N == 0 enqueues nothing.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int dm_resize_bilinear_fwd(const float* in, long long NC, int H, int W, int OH, int OW, float* out, dm_stream_t stream);
+int dm_conv2d_post_add_fwd(const float* const* srcs, const int* src_channels, const long long* src_batch_strides,
+                           int num_srcs, int NB, int H, int W, const float* w_packed, const float* bias, int Cout,
+                           int ksize, int relu, const float* addend, float* out, int out_ch_total, int out_ch_offset,
+                           dm_stream_t stream);
+int dm_roi_align_add_fwd(const float* feat, int B, int C, int H, int W, float spatial_scale, const float* rois, int N,
+                         int P, int sampling_ratio, int pool, float* out, dm_stream_t stream);
 
 #ifdef __cplusplus
 }
