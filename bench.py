@@ -9,11 +9,18 @@ upsample) -> stage-1 class logits at 28x28.  A "step" is one such RoI batch;
 inputs are resident in HBM before the timed region.
 
 One JSON line on stdout (rank 0).  `value` = images (RoI batches) per second
-over all ranks; `ms_per_step` = ms per RoI batch; `roofline` prices the
-dominant kernel (conv3x3 256->256 implicit GEMM, fp32 MFMA) and
-`roofline_roialign` the RoIAlign kernel, both timed live with events on the
-launch stream; `cpu_baseline` times the oracle (CPU restatement of the
-reference) on a bounded sample of the same RoIs on this box's host cores.
+over all ranks; `ms_per_step` = ms per RoI batch.
+
+A plain run does only what the headline figure needs: set-up, warm-up, the
+timed steps of the headline leg (`--leg`), `--dump-outputs`, the line.
+`--full` adds everything else to the same line: the other leg (the training
+step's figures as top-level keys), the reference's entry points as a whole,
+`roofline` (the dominant kernel: conv3x3 256->256 implicit GEMM, fp32 MFMA),
+`roofline_dcn` and `roofline_roialign` (timed live with events on the launch
+stream), the other exits and inference shapes in `extra`, `cpu_baseline` (the
+oracle, a CPU restatement of the reference, on a bounded sample of the same
+RoIs on the host cores) and the whole-detector context leg.  The headline leg
+is the same code, in the same order, either way.
 
 `--steps K` is the number of timed steps of the headline leg in all (three
 windows that add up to K; `ms_per_step` is the median window's).  Inputs and
@@ -265,12 +272,14 @@ def _max_over_ranks(x, world):
     return float(t.item())
 
 
-def train_step_bench(head, dev, rank, world, steps=4, warmup=4, rehearsal=False, keep_outputs=False):
+def train_step_bench(head, dev, rank, world, steps=4, warmup=4, rehearsal=False, keep_outputs=False, extras=True):
     """BASELINE configs[2]/[3]: training step of the mask path, 2 images/GPU x 128
     positive RoIs, dynamic 14/28/56/112 selection + BCE backward + RCCL all-reduce of
     the flat mask-head gradient + fused SGD.  Returns ms per step (max over ranks).
     ``keep_outputs``: the last element of the result holds what the last timed step gave its caller (its losses
     and the parameters its SGD step left), on the host; None otherwise.
+    ``extras`` (--full): after the timed windows, also the collective by itself and what it costs the step (one more
+    window without it at N > 1, a forced one-rank all-reduce at N = 1); without them those figures are 0.0 / None.
 
     The RCCL communicator exists only inside this function: at N > 1 the default process group
     is gloo (host barriers and the max over ranks) and the data-path collective gets an `nccl`
@@ -347,12 +356,12 @@ def train_step_bench(head, dev, rank, world, steps=4, warmup=4, rehearsal=False,
     # the same steps without the all-reduce (the ranks then drift apart -- timing only, parameters are restored below);
     # exposed = step with - step without.  At world 1 the pair is (forced one-rank all-reduce, plain step), below.
     noreduce_ms = None
-    if world > 1:
+    if extras and world > 1:
         reduce_on[0] = False
         step()
         noreduce_ms = window(sizes[0])[0] / sizes[0] * 1e3
         reduce_on[0] = True
-    if world == 1 and not dist.is_initialized() and os.environ.get('DM_BENCH_NO_RCCL', '0') != '1':
+    if extras and world == 1 and not dist.is_initialized() and os.environ.get('DM_BENCH_NO_RCCL', '0') != '1':
         # World size 1: the step above ran without a collective (a single-GPU job has nothing to reduce: this
         # is the N = 1 point of the scaling curve).  So that the RCCL call, its side stream and the 1/world
         # scaling of the fused SGD step still run on hardware in EVERY round, a one-rank communicator is
@@ -367,7 +376,7 @@ def train_step_bench(head, dev, rank, world, steps=4, warmup=4, rehearsal=False,
             forced_ms = window(sizes[0])[0] / sizes[0] * 1e3
         except Exception as e:      # noqa: BLE001  (recorded in the JSON; the headline needs no collective)
             print(f'[bench] RCCL world-1 group unavailable: {e}', file=sys.stderr)
-    if dist.is_initialized():
+    if extras and dist.is_initialized():
         for _ in range(2):
             grp.all_reduce_async(force=True); grp.wait()
         torch.cuda.synchronize(); dist.barrier(); torch.cuda.synchronize()
@@ -390,7 +399,7 @@ def train_step_bench(head, dev, rank, world, steps=4, warmup=4, rehearsal=False,
         dist.barrier()
         dist.destroy_process_group(sub)
     if world > 1:
-        exposed_ms = step_ms - noreduce_ms
+        exposed_ms = (step_ms - noreduce_ms) if noreduce_ms is not None else None
     else:
         exposed_ms = (forced_ms - step_ms) if forced_ms is not None else None
     return (step_ms, float(res['loss_mask']['loss_masks'].detach()), grp.numel, B, comm_ms, collective, forced_ms, exposed_ms,
@@ -529,6 +538,71 @@ def launch_ranks(n):
     return rc
 
 
+def infer_leg(head, feats, rois, labels, args, rank, world):
+    """The inference leg (BASELINE configs[1]): --warmup eager steps, the step captured as one HIP graph, then the
+    --steps timed steps in three windows; --dump-outputs (infer leg, rank 0) writes what the last of them computed.
+    Returns (median window's ms per step, every window's ms per step, the window sizes, the graph that was timed or
+    None for eager launches, the eager step)."""
+    import torch.distributed as dist
+
+    def step():
+        with torch.no_grad():
+            return head._mask_forward(feats, rois, labels, last_stage=1)
+    eager_step = step
+
+    def barrier():
+        if world > 1:
+            dist.barrier()
+
+    for _ in range(args.warmup):
+        step()
+    torch.cuda.synchronize()
+    # The step is ~25 dependent launches; replay it as one HIP graph (no tracing
+    # compiler involved: the graph holds exactly the C-ABI launches of step()).
+    graph = None
+    if not args.no_graph:
+        try:
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                graph_out = step()
+            g.replay()
+            torch.cuda.synchronize()
+            ref_out = step()
+            if not torch.equal(graph_out['stage_instance_preds'][1], ref_out['stage_instance_preds'][1]):
+                raise RuntimeError('graph replay differs from eager')
+            graph = g
+
+            def step():          # noqa: F811
+                graph.replay()
+                return graph_out
+        except Exception as e:      # capture not available: stay eager (recorded in the JSON)
+            print(f'[bench] HIP graph capture failed, timing eager launches: {e}', file=sys.stderr)
+            graph = None
+
+    def timed_window(n):
+        """EXACTLY n steps between barrier + synchronize on both sides; max over ranks, and the last step's output."""
+        torch.cuda.synchronize()
+        barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            out = step()
+        torch.cuda.synchronize()
+        barrier()
+        torch.cuda.synchronize()
+        return _max_over_ranks(time.perf_counter() - t0, world), out
+    # the --steps timed steps as three windows, the median window's ms/step is reported (one window of 20 graph
+    # replays is 80 ms: a single sample of that length is at the mercy of the clock ramp; VERDICT r1 weak #9)
+    sizes = window_sizes(args.steps)
+    wins = [timed_window(n) for n in sizes]
+    if args.dump_outputs and args.leg == 'infer' and rank == 0:
+        last = wins[-1][1]          # the graph's output buffers: written out before anything else runs
+        dump_outputs(args.dump_outputs, {f'{k}_{i}': t for k in ('stage_instance_preds', 'stage_detail_preds')
+                                         for i, t in enumerate(last[k])})
+    win_ms = [w / n * 1e3 for (w, _), n in zip(wins, sizes)]
+    return statistics.median(win_ms), win_ms, sizes, graph, eager_step
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -536,13 +610,17 @@ def main():
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--leg', choices=('infer', 'train'), default='infer',
                     help="which leg is the headline `value`: 'infer' = BASELINE configs[1] (default); 'train' = the "
-                         "configs[2]/[3] training step, timed over exactly --steps steps (the other leg's figures stay "
-                         "top-level keys of the same line)")
+                         "configs[2]/[3] training step, timed over exactly --steps steps (with --full the other leg's figures "
+                         "stay top-level keys of the same line)")
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beside the headline leg and put it on the same line: the other leg, the '
+                         "reference's entry points, the roofline kernels, other exits and inference shapes, the CPU baseline, "
+                         'the whole-detector context leg (off by default: a plain run times the headline leg alone)')
     ap.add_argument('--no-graph', action='store_true', help='time eager launches instead of a HIP graph replay')
     ap.add_argument('--end-to-end', action='store_true', help='(default since round 4; kept for old command lines)')
     ap.add_argument('--no-end-to-end', action='store_true',
-                    help='skip the whole-detector context leg (stock MIOpen ResNet-50-FPN + the mask path, rank 0 only)')
-    ap.add_argument('--cpu-sample', type=int, default=512, help='RoIs of the batch timed on the host cores (0 = skip)')
+                    help='--full: skip the whole-detector context leg (stock MIOpen ResNet-50-FPN + the mask path, rank 0 only)')
+    ap.add_argument('--cpu-sample', type=int, default=512, help='--full: RoIs of the batch timed on the host cores (0 = skip)')
     ap.add_argument('--dump-outputs', metavar='DIR',
                     help="write what the headline leg's last timed step computed (rank 0) as DIR/<name>.npy: the infer leg's "
                          "per-stage logits; the train leg's losses and the parameters its SGD step left")
@@ -598,107 +676,60 @@ def main():
         # multi-stream launch sequences by ~10 %, measured on full_head_112_ms: 10.0 -> 11.45 ms).
         dist.init_process_group('gloo')
 
-    head, sd = build_head(dev)
-    feats_c, rois_c, labels_c = make_inputs(rank, dev)
-    feats = [f.to(dev) for f in feats_c]
-    rois, labels = rois_c.to(dev), labels_c.to(dev)
+    full = args.full
+    run_train = full or args.leg == 'train'         # a plain run times the headline leg alone
+    run_infer = full or args.leg == 'infer'
 
-    # training step (configs[2]/[3]) on every rank (parameters are restored afterwards); reported in `extra`, not
-    # the headline.  It runs FIRST: its four streams must each sit on a hardware queue of their own, and the
-    # HIP-graph capture of the headline leg below brings streams of its own that end up sharing queues with them
-    # (measured: 23.6 ms per step before the capture, 24.3 ms after it).  The headline leg is not affected by the
-    # order (the training leg leaves nothing behind but cached allocator memory).
-    t_steps, t_warm = (args.steps, args.warmup) if args.leg == 'train' else (12, 4)
-    dump_train = bool(args.dump_outputs) and args.leg == 'train' and rank == 0
-    train_ms, train_loss, n_flat, train_b, comm_ms, collective, forced_ms, exposed_ms, train_out = train_step_bench(
-        head, dev, rank, world, steps=t_steps, warmup=t_warm, rehearsal=rehearsal, keep_outputs=dump_train)
-    if dump_train:
-        dump_outputs(args.dump_outputs, train_out)
+    head, sd = build_head(dev)
+    if run_infer:
+        feats_c, rois_c, labels_c = make_inputs(rank, dev)
+        feats = [f.to(dev) for f in feats_c]
+        rois, labels = rois_c.to(dev), labels_c.to(dev)
+
+    # training step (configs[2]/[3]) on every rank (parameters are restored afterwards): the headline of --leg train,
+    # top-level keys of a --full line otherwise.  It runs FIRST: its four streams must each sit on a hardware queue of
+    # their own, and the HIP-graph capture of the inference leg below brings streams of its own that end up sharing
+    # queues with them (measured: 23.6 ms per step before the capture, 24.3 ms after it).  The inference leg is not
+    # affected by the order (the training leg leaves nothing behind but cached allocator memory).
+    if run_train:
+        t_steps, t_warm = (args.steps, args.warmup) if args.leg == 'train' else (12, 4)
+        dump_train = bool(args.dump_outputs) and args.leg == 'train' and rank == 0
+        train_ms, train_loss, n_flat, train_b, comm_ms, collective, forced_ms, exposed_ms, train_out = train_step_bench(
+            head, dev, rank, world, steps=t_steps, warmup=t_warm, rehearsal=rehearsal, keep_outputs=dump_train, extras=full)
+        if dump_train:
+            dump_outputs(args.dump_outputs, train_out)
 
     entry = None
-    if rank == 0 and os.environ.get('DM_BENCH_NO_ENTRY', '0') != '1':
+    if full and rank == 0 and os.environ.get('DM_BENCH_NO_ENTRY', '0') != '1':
         # the reference's real entry points as a whole (rank 0): before the headline's graph capture, like the training leg
         entry = entry_points_bench(sd, dev)
         torch.cuda.empty_cache()
 
-    def step():
-        with torch.no_grad():
-            return head._mask_forward(feats, rois, labels, last_stage=1)
-    eager_step = step
-
-    def barrier():
-        if world > 1:
-            dist.barrier()
-
-    for _ in range(args.warmup):
-        step()
-    torch.cuda.synchronize()
-    # The step is ~25 dependent launches; replay it as one HIP graph (no tracing
-    # compiler involved: the graph holds exactly the C-ABI launches of step()).
-    graph = None
-    if not args.no_graph:
-        try:
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                graph_out = step()
-            g.replay()
-            torch.cuda.synchronize()
-            ref_out = step()
-            if not torch.equal(graph_out['stage_instance_preds'][1], ref_out['stage_instance_preds'][1]):
-                raise RuntimeError('graph replay differs from eager')
-            graph = g
-
-            def step():          # noqa: F811
-                graph.replay()
-                return graph_out
-        except Exception as e:      # capture not available: stay eager (recorded in the JSON)
-            print(f'[bench] HIP graph capture failed, timing eager launches: {e}', file=sys.stderr)
-            graph = None
-    def timed_window(n):
-        """EXACTLY n steps between barrier + synchronize on both sides; max over ranks, and the last step's output."""
-        torch.cuda.synchronize()
-        barrier()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(n):
-            out = step()
-        torch.cuda.synchronize()
-        barrier()
-        torch.cuda.synchronize()
-        return _max_over_ranks(time.perf_counter() - t0, world), out
-    # the --steps timed steps as three windows, the median window's ms/step is reported (one window of 20 graph
-    # replays is 80 ms: a single sample of that length is at the mercy of the clock ramp; VERDICT r1 weak #9)
-    sizes = window_sizes(args.steps)
-    wins = [timed_window(n) for n in sizes]
-    if args.dump_outputs and args.leg == 'infer' and rank == 0:
-        last = wins[-1][1]          # the graph's output buffers: written out before anything else runs
-        dump_outputs(args.dump_outputs, {f'{k}_{i}': t for k in ('stage_instance_preds', 'stage_detail_preds')
-                                         for i, t in enumerate(last[k])})
-    win_ms = [w / n * 1e3 for (w, _), n in zip(wins, sizes)]
-    ms_per_step = statistics.median(win_ms)
-    value = world * 1e3 / ms_per_step          # images (RoI batches of 512) per second, all ranks
-
-    result = {
-        'metric': 'img/s (DynaMask mask-head path, 512 RoIs/img, fixed 28x28 exit; ms_per_step = ms per RoI batch)',
-        'value': value, 'unit': 'img/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
-        'ms_per_step': ms_per_step, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
-        'dtype': 'f32', 'data': 'synthetic',
-        'config': {'workload': 'BASELINE configs[1]: DynaMask R-50-FPN mask head inference, 1333x800 FPN shapes, '
-                               '512 RoIs/img, fixed 28x28 exit (RoIAlign14 + 2 conv3x3 + SFM stage 0 + stage-1 logits)',
-                   'rois_per_img': ROIS_PER_IMG, 'imgs_per_gpu': 1, 'parallelism': f'images sharded x{world}, no collective',
-                   'cpu_baseline': 'rank 0 at N = 1 only (omitted from the N > 1 lines)',
-                   'launch': 'hip graph replay' if graph is not None else 'eager',
-                   'timing': f'{args.steps} steps in {len(sizes)} windows of {sizes} steps, median of their ms/step; '
-                             'windows ms/step = ' + ', '.join(f'{w:.3f}' for w in win_ms)},
-    }
+    result = {'unit': 'img/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'higher_is_better': True,
+              'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic', 'full': full}
+    if run_infer:
+        ms_per_step, win_ms, sizes, graph, eager_step = infer_leg(head, feats, rois, labels, args, rank, world)
+        value = world * 1e3 / ms_per_step          # images (RoI batches of 512) per second, all ranks
+        result.update({
+            'metric': 'img/s (DynaMask mask-head path, 512 RoIs/img, fixed 28x28 exit; ms_per_step = ms per RoI batch)',
+            'value': value, 'ms_per_step': ms_per_step,
+            'config': {'workload': 'BASELINE configs[1]: DynaMask R-50-FPN mask head inference, 1333x800 FPN shapes, '
+                                   '512 RoIs/img, fixed 28x28 exit (RoIAlign14 + 2 conv3x3 + SFM stage 0 + stage-1 logits)',
+                       'rois_per_img': ROIS_PER_IMG, 'imgs_per_gpu': 1, 'parallelism': f'images sharded x{world}, no collective',
+                       'cpu_baseline': '--full only: rank 0 at N = 1 (omitted from the N > 1 lines)',
+                       'launch': 'hip graph replay' if graph is not None else 'eager',
+                       'timing': f'{args.steps} steps in {len(sizes)} windows of {sizes} steps, median of their ms/step; '
+                                 'windows ms/step = ' + ', '.join(f'{w:.3f}' for w in win_ms)},
+            'infer_ms_per_roi_batch': ms_per_step, 'infer_img_per_s': value,
+        })
     # The training step (BASELINE configs[2] at N = 1, configs[3] at N = 8) is the unit of the north star's scaling
-    # curve: its figures are TOP-LEVEL keys of the line at every N (VERDICT r2 #1), whichever leg is the headline.
-    result.update({
-        'train_ms_per_step': train_ms, 'train_img_per_s': world * train_b / (train_ms * 1e-3),
-        'train_imgs_per_gpu': train_b, 'train_steps_timed': t_steps,
-        'allreduce_alone_ms': comm_ms, 'allreduce_exposed_ms': exposed_ms, 'collective': collective,
-        'infer_ms_per_roi_batch': ms_per_step, 'infer_img_per_s': value,
-    })
+    # curve: its figures are TOP-LEVEL keys of the --full line at every N, whichever leg is the headline.
+    if run_train:
+        result.update({
+            'train_ms_per_step': train_ms, 'train_img_per_s': world * train_b / (train_ms * 1e-3),
+            'train_imgs_per_gpu': train_b, 'train_steps_timed': t_steps,
+            'allreduce_alone_ms': comm_ms, 'allreduce_exposed_ms': exposed_ms, 'collective': collective,
+        })
     if entry is not None:
         for k in ('forward_train_ms', 'get_targets_ms', 'paste_rle_ms'):
             result[k] = entry[k]
@@ -717,7 +748,7 @@ def main():
             'imgs_per_gpu': train_b, 'pos_rois_per_img': 128, 'parallelism': f'images sharded x{world}, {collective}',
             'launch': 'eager (four streams)', 'timing': f'{t_steps} steps in {len(window_sizes(t_steps))} windows, median of their ms/step'}
 
-    if rank == 0:
+    if full and rank == 0:
         from dynamask_amd import ops
         # ---- roofline of the dominant kernel: conv3x3 256->256 on [512,256,14,14] ----
         x = torch.randn(ROIS_PER_IMG, 256, 14, 14, device=dev)
@@ -1024,16 +1055,17 @@ def main():
                         'for 100 detections incl. merge, paste and D2H of the bool masks; RPN / bbox head / NMS not included'}
 
     if rank == 0:
-        extra = result['extra']
-        extra['train_step'] = {'ms_per_step': train_ms, 'img_per_s': world * train_b / (train_ms * 1e-3),
-                               'imgs_per_gpu': train_b, 'pos_rois_per_img': 128, 'loss': train_loss,
-                               'allreduce_floats': n_flat, 'allreduce_alone_ms': comm_ms,
-                               'collective': collective, 'ms_per_step_with_forced_one_rank_allreduce': forced_ms,
-                               'allreduce_exposed_ms': exposed_ms,
-                               'allreduce_exposed_how': 'N > 1: step with the all-reduce - the same window without it; N = 1: step with the '
-                                                        'forced one-rank all-reduce - plain step',
-                               'what': 'fwd + loss + bwd (head, MaskPre, RoIAlign) + RCCL all-reduce of the flat '
-                                       'mask-path gradient + fused SGD; BASELINE configs[2] (N=1) / configs[3] (N=8)'}
+        if full:
+            result['extra']['train_step'] = {
+                'ms_per_step': train_ms, 'img_per_s': world * train_b / (train_ms * 1e-3),
+                'imgs_per_gpu': train_b, 'pos_rois_per_img': 128, 'loss': train_loss,
+                'allreduce_floats': n_flat, 'allreduce_alone_ms': comm_ms,
+                'collective': collective, 'ms_per_step_with_forced_one_rank_allreduce': forced_ms,
+                'allreduce_exposed_ms': exposed_ms,
+                'allreduce_exposed_how': 'N > 1: step with the all-reduce - the same window without it; N = 1: step with the '
+                                         'forced one-rank all-reduce - plain step',
+                'what': 'fwd + loss + bwd (head, MaskPre, RoIAlign) + RCCL all-reduce of the flat '
+                        'mask-path gradient + fused SGD; BASELINE configs[2] (N=1) / configs[3] (N=8)'}
         os.write(json_fd, (json.dumps(result) + '\n').encode())
     if dist.is_initialized():
         dist.barrier()

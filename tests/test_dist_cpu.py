@@ -206,6 +206,19 @@ def test_bench_leg_train_is_an_option_of_the_command_line():
     assert r.returncode == 0 and '--leg' in r.stdout and 'train' in r.stdout
 
 
+def test_bench_full_is_an_option_off_by_default_and_the_profile_script_asks_for_it():
+    """Everything beside the headline leg is behind --full: the option exists and is a flag, and the script whose files
+    hold the figures that moved there (the training step at top level, rooflines, entry points) passes it on every call."""
+    import re
+    r = _run_bench(['--help'], {})
+    assert r.returncode == 0 and re.search(r'\[--full\]', r.stdout)
+    r = _run_bench(['--gpus', '2', '--full'], {'DM_BENCH_LAUNCH_ONLY': '1'})
+    assert r.returncode == 0, r.stderr[-2000:]
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    calls = [l for l in open(os.path.join(root, 'tools', 'collect_profiles.sh')) if re.search(r'python3 bench\.py', l)]
+    assert len(calls) >= 4 and all('bench.py --full' in l for l in calls), calls
+
+
 def test_bench_steps_are_the_timed_steps_and_outputs_dump_as_npy(tmp_path):
     """--steps K times exactly K steps (split into at most three windows); --dump-outputs writes float32 / float64
     .npy files and refuses more than its 64 MB."""

@@ -13,14 +13,14 @@ stats() {  # stats <dir> <dest>: copy the kernel_stats.csv of a rocprofv3 --stat
   cp "$(ls -t $1/*/*kernel_stats.csv | head -1)" "$2"
 }
 # ---- the driver's line, the two-rank launch rehearsal (both ranks on cuda:0, gloo), the training step as the headline
-python3 bench.py > $out/${tag}_bench.json 2> $out/${tag}_bench.stderr
+python3 bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.stderr
 tail -1 $out/${tag}_bench.json | cut -c1-200
-DM_BENCH_REHEARSAL=1 DM_BENCH_NO_ENTRY=1 python3 bench.py --gpus 2 --steps 10 --warmup 2 --cpu-sample 0 --no-end-to-end > $out/${tag}_bench_rehearsal_gpus2.json 2>> $out/${tag}_bench.stderr
-DM_BENCH_NO_ENTRY=1 python3 bench.py --leg train --steps 8 --warmup 4 --cpu-sample 0 --no-end-to-end > $out/${tag}_bench_leg_train.json 2>> $out/${tag}_bench.stderr
+DM_BENCH_REHEARSAL=1 DM_BENCH_NO_ENTRY=1 python3 bench.py --full --gpus 2 --steps 10 --warmup 2 --cpu-sample 0 --no-end-to-end > $out/${tag}_bench_rehearsal_gpus2.json 2>> $out/${tag}_bench.stderr
+DM_BENCH_NO_ENTRY=1 python3 bench.py --full --leg train --steps 8 --warmup 4 --cpu-sample 0 --no-end-to-end > $out/${tag}_bench_leg_train.json 2>> $out/${tag}_bench.stderr
 echo "bench done"
 # ---- per-kernel times: the whole bench command (the file the line's numbers can be checked against), the three roofline
 # kernels alone (bench.py reads its *_rocprof_committed figures from this one), the headline step alone, the training step
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_bench -- python3 bench.py --cpu-sample 0 > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_bench -- python3 bench.py --full --cpu-sample 0 > /dev/null 2>&1
 stats $out/prof_bench $out/${tag}_bench_kernel_stats.csv
 PROBE_ITERS=40 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_roof -- python3 tools/pmc_probe.py > /dev/null 2>&1
 stats $out/prof_roof $out/${tag}_roofline_kernel_stats.csv
