@@ -46,6 +46,8 @@ struct DcnArgs {
 // One bilinear sample from its two row pairs.  Spelled as an explicit fma chain so that every kernel
 // variant rounds the same way (left to the compiler, the two gathers contracted differently and
 // results differed in the last bit depending on which variant a launch size selected).
+typedef float dm_f32x2 __attribute__((ext_vector_type(2)));
+
 __device__ __forceinline__ float dcn_bilinear(float wt0, float wt1, float wb0, float wb1, float ta, float tb, float ba, float bb) {
   return __builtin_fmaf(wb1, bb, __builtin_fmaf(wb0, ba, __builtin_fmaf(wt1, tb, wt0 * ta)));
 }
@@ -606,6 +608,270 @@ __global__ __launch_bounds__(256, 2) void deform_conv_lds_kernel(DcnArgs a) {
 }
 
 // ---------------------------------------------------------------------------
+// The small-map kernel for 256 output channels: a workgroup owns ALL 256 couts of 64 flat pixels, so a sample is gathered
+// once (the 128 x 128 kernel above gathers it twice, once in each of the two cout workgroups of a pixel tile), and the
+// gather is the part of the non-MFMA instruction budget that bounds that kernel (tools/micro/mfma_mix.hip).  Still four
+// waves and two workgroups per CU (the 8-wave 256 x 128 tile of docs/experiments/r05_dcn256.patch ran alone on its CU and
+// lost in the two-stream step).  Wave w owns couts 64 w .. 64 w + 63 over all 64 pixels (2 x 2 blocks of 32 x 32), so a
+// weight fragment is used by exactly one wave: it is not staged through LDS but read from the packed weights (L2 hits:
+// 512 contiguous bytes per half-wave) straight into the registers the MFMAs read, one step ahead, into two register
+// sets that alternate by step.  No A ring, none of its writes.
+// B is the scheme of the kernel above: planes staged per chunk as [image][quad][pixel] float4, double buffered; a
+// two-slot ring of 3-tap steps, one barrier per step.  The 384 quad-items of a step (3 taps x 2 quads x 64 pixels) are
+// dealt over 256 threads as one whole item (tap 3 s + rb, rb = tid >> 7) plus one HALF item of the step's third tap
+// (channels 2 rb, 2 rb + 1 of the quad: 8-byte corner reads, 8-byte write); a thread keeps the parameters of 6 taps.
+// Same products in the same order, same fma chain: the same bits as every other variant.
+__global__ __launch_bounds__(256, 2) void deform_conv_c256_kernel(DcnArgs a) {
+  constexpr int TN = 64, NT = 256;
+  constexpr int BS_F4 = 3 * 2 * TN;               // one B slot: [tap of the step][quad][pixel] float4
+  constexpr int X_PER_T = 4;                      // float4 per thread for 2 images x 8 planes (H*W <= 256)
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  dm_f32x4* ldsB = reinterpret_cast<dm_f32x4*>(lds);                 // [2][BS_F4]
+  dm_f32x4* ldsX = ldsB + 2 * BS_F4;                                 // [2 buffers][2 image slots][2 quads][H*W] float4
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int hi = lane >> 5, l31 = lane & 31;
+  const int q0 = a.q_begin + (int)blockIdx.x * TN;
+  const int HW = a.HW, W = a.W, H = a.H;
+  const int n0 = q0 / HW;                          // first image of the tile; the tile touches n0 and n0 + 1 at most
+  const int xbuf = 2 * 2 * HW;                     // float4 per staging buffer
+
+  // gather role: pixel gj of the tile, channel quad gh of the chunk; rb picks the whole item's tap and the half item's channels
+  const int gj = tid & 63, gh = (tid >> 6) & 1, rb = tid >> 7;
+  int gq = q0 + gj;
+  const bool g_ok = gq < a.Q;
+  gq = min(gq, a.Q - 1);
+  const int gn = gq / HW, gp = gq - gn * HW;
+  const int gy = gp / W, gx = gp - gy * W;
+  const int xbase = ((gn - n0) * 2 + gh) * HW;               // this thread's quad inside a staging buffer
+
+  // [step s][0: tap 3s + rb (whole item), 1: tap 3s + 2 (half item)]
+  int otb[3][2];                                   // top | bottom << 16: offsets inside a plane (< 256)
+  float wt0[3][2], wt1[3][2], wb0[3][2], wb1[3][2];
+  const int cpg = a.C / a.dg;
+  auto load_params = [&](int group) {
+    const float* offp = a.offset + ((size_t)gn * a.dg + group) * 18 * HW + gp;
+#pragma unroll
+    for (int s = 0; s < 3; ++s)
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        otb[s][r] = 0;
+        wt0[s][r] = wt1[s][r] = wb0[s][r] = wb1[s][r] = 0.f;
+        if (g_ok) {
+          const int ki = s, kj = r ? 2 : rb, tap = 3 * s + kj;
+          const float h_im = (float)(gy - 1 + ki) + offp[(size_t)(2 * tap) * HW];
+          const float w_im = (float)(gx - 1 + kj) + offp[(size_t)(2 * tap + 1) * HW];
+          if (h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W) {
+            const int h_low = (int)floorf(h_im), w_low = (int)floorf(w_im);
+            const float lh = h_im - (float)h_low, lw = w_im - (float)w_low;
+            const float hh = 1.f - lh, hw = 1.f - lw;
+            const float wr_t = (h_low >= 0) ? hh : 0.f;
+            const float wr_b = (h_low + 1 <= H - 1) ? lh : 0.f;
+            const int rt = min(max(h_low, 0), H - 1), rbm = min(max(h_low + 1, 0), H - 1);
+            const int cb = min(max(w_low, 0), W - 2);
+            const float wc0 = (cb == w_low ? hw : 0.f) + (cb == w_low + 1 ? lw : 0.f);
+            const float wc1 = (cb + 1 == w_low ? hw : 0.f) + (cb + 1 == w_low + 1 ? lw : 0.f);
+            otb[s][r] = (rt * W + cb) | ((rbm * W + cb) << 16);
+            wt0[s][r] = wr_t * wc0; wt1[s][r] = wr_t * wc1;
+            wb0[s][r] = wr_b * wc0; wb1[s][r] = wr_b * wc1;
+          }
+        }
+      }
+  };
+
+  dm_f32x16 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+  dm_f32x4 rx[X_PER_T];
+  // Global loads go through buffer descriptors: the lane's part of an address is one 32-bit register that never changes,
+  // the chunk / tap part is scalar.  (With flat 64-bit addresses the compiler keeps a register pair per tap and row block
+  // alive through the loop, and the kernel spills.)
+  const __amdgpu_buffer_rsrc_t xsrc = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float*>(a.x) + (size_t)n0 * a.C * HW, 0, min(2, a.NB - n0) * a.C * HW * 4, 0x00020000);
+  const __amdgpu_buffer_rsrc_t wsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.wp), 0, 9 * a.KQ * a.CoutP * 16, 0x00020000);
+  unsigned x_off[X_PER_T];                         // bytes; places as in deform_conv_lds_kernel
+#pragma unroll
+  for (int i = 0; i < X_PER_T; ++i) {
+    const int idx = tid + i * NT;
+    const int img = idx / (2 * HW), r = idx - img * 2 * HW;
+    const int quad = r / HW, px = r - quad * HW;
+    const int ii = (idx < 4 * HW) ? img : 0, qq = (idx < 4 * HW) ? quad : 0, pp = (idx < 4 * HW) ? px : 0;
+    x_off[i] = 4u * (unsigned)(((min(n0 + ii, a.NB - 1) - n0) * a.C + qq * 4) * HW + pp);
+  }
+  // A: lane (l31, hi) holds, per tap, the float4 of channel quad 2 * (chunk) + hi of cout rows 64 w + 32 i + l31
+  // (rows past CoutP: the last row again -- never stored; an unconditional load keeps exec-mask branches out of the loop)
+  unsigned a_off[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) a_off[i] = 16u * (unsigned)(hi * a.CoutP + min(wave * 64 + i * 32 + l31, a.CoutP - 1));   // bytes
+  const int a_quad = a.CoutP * 16, a_tap = a.KQ * a_quad;      // bytes per channel quad / per tap of the packed weights
+  auto load_a1 = [&](dm_f32x4 (&dst)[6], int c0, int g, int u) {   // weights of tap 3g + u, channels c0 .. c0+7
+    const int so = (3 * g + u) * a_tap + (c0 >> 2) * a_quad;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) dst[u * 2 + i] = __builtin_bit_cast(dm_f32x4, __builtin_amdgcn_raw_buffer_load_b128(wsrc, a_off[i], so, 0));
+  };
+  auto load_x = [&](int c0) {                     // lanes = consecutive pixels: coalesced dword loads
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int so = (c0 + e) * HW * 4;
+#pragma unroll
+      for (int i = 0; i < X_PER_T; ++i) rx[i][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xsrc, x_off[i], so, 0));
+    }
+  };
+  auto store_x = [&](int buf) {
+#pragma unroll
+    for (int i = 0; i < X_PER_T; ++i) {
+      const int idx = tid + i * NT;
+      if (idx < 4 * HW) ldsX[buf * xbuf + idx] = rx[i];
+    }
+  };
+  // the whole item of step s: tap 3s + rb, four channels; the half item: tap 3s + 2, channels 2 rb and 2 rb + 1
+  auto whole_read = [&](const dm_f32x4* xq, int s, dm_f32x4& tl, dm_f32x4& tr, dm_f32x4& bl, dm_f32x4& br) {
+    const dm_f32x4* pt = xq + (otb[s][0] & 0xffff);
+    const dm_f32x4* pb = xq + (otb[s][0] >> 16);
+    tl = pt[0]; tr = pt[1]; bl = pb[0]; br = pb[1];
+  };
+  auto whole_write = [&](int slot, int s, const dm_f32x4& tl, const dm_f32x4& tr, const dm_f32x4& bl, const dm_f32x4& br) {
+    dm_f32x4 v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = dcn_bilinear(wt0[s][0], wt1[s][0], wb0[s][0], wb1[s][0], tl[e], tr[e], bl[e], br[e]);
+    ldsB[slot * BS_F4 + (rb * 2 + gh) * TN + gj] = v;
+  };
+  auto half_read = [&](const dm_f32x4* xq, int s, dm_f32x2& tl, dm_f32x2& tr, dm_f32x2& bl, dm_f32x2& br) {
+    const dm_f32x2* pt = reinterpret_cast<const dm_f32x2*>(xq + (otb[s][1] & 0xffff)) + rb;
+    const dm_f32x2* pb = reinterpret_cast<const dm_f32x2*>(xq + (otb[s][1] >> 16)) + rb;
+    tl = pt[0]; tr = pt[2]; bl = pb[0]; br = pb[2];
+  };
+  auto half_write = [&](int slot, int s, const dm_f32x2& tl, const dm_f32x2& tr, const dm_f32x2& bl, const dm_f32x2& br) {
+    dm_f32x2 v;
+#pragma unroll
+    for (int e = 0; e < 2; ++e) v[e] = dcn_bilinear(wt0[s][1], wt1[s][1], wb0[s][1], wb1[s][1], tl[e], tr[e], bl[e], br[e]);
+    reinterpret_cast<dm_f32x2*>(&ldsB[slot * BS_F4 + (2 * 2 + gh) * TN + gj])[rb] = v;
+  };
+  // One step: the MFMAs of 3 taps, A from register set ``cur``, B from ring slot ``slot``.  If ``fill``, step ``sn``'s
+  // items are gathered from staging buffer ``gbuf`` into the other slot (the whole item inside the first tap's MFMA
+  // cluster, the half item inside the second's); if ``pre``, the weights of step (pc0, pg) are loaded into ``nxt``, one
+  // tap's two float4 in front of each cluster.
+  auto step = [&](const dm_f32x4 (&cur)[6], dm_f32x4 (&nxt)[6], int slot, bool fill, int sn, int gbuf, bool pre, int pc0, int pg) {
+    const dm_f32x4* xq = ldsX + gbuf * xbuf + xbase;
+#pragma unroll
+    for (int u = 0; u < 3; ++u) {
+      dm_f32x4 bv[2];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) bv[j] = ldsB[slot * BS_F4 + (u * 2 + hi) * TN + j * 32 + l31];
+      dm_f32x4 tl, tr, bl, br;
+      dm_f32x2 htl, htr, hbl, hbr;
+      if (fill && u == 0) whole_read(xq, sn, tl, tr, bl, br);
+      if (fill && u == 1) half_read(xq, sn, htl, htr, hbl, hbr);
+      if (pre) load_a1(nxt, pc0, pg, u);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int e = 0; e < 2; ++e)
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(cur[u * 2 + i][e], bv[j][e], acc[i][j], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+      if (fill && u == 0) whole_write(slot ^ 1, sn, tl, tr, bl, br);
+      if (fill && u == 1) half_write(slot ^ 1, sn, htl, htr, hbl, hbr);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int e = 2; e < 4; ++e)
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(cur[u * 2 + i][e], bv[j][e], acc[i][j], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  // One chunk of 8 channels.  On entry ``p`` holds (or has in flight) the weights of its step 0 and ring slot ``slot``
+  // its gathered taps 0..2; on exit ``q`` and slot ^ 1 hold those of the next chunk: the caller swaps p and q.
+  int cur_group = 0;
+  auto chunk = [&](dm_f32x4 (&p)[6], dm_f32x4 (&q)[6], int c0, int buf, int slot) {
+    const int cn = c0 + 8;
+    const bool more = cn < a.C;
+    // step 0: MFMAs of taps 0..2; fills taps 3..5
+    if (more) load_x(cn);
+    step(p, q, slot, true, 1, buf, true, c0, 1);
+    __syncthreads();
+    // step 1: MFMAs of taps 3..5; fills taps 6..8; the quads of the next chunk go to the other buffer
+    if (more) store_x(buf ^ 1);
+    step(q, p, slot ^ 1, true, 2, buf, true, c0, 2);
+    __syncthreads();
+    // step 2: MFMAs of taps 6..8; fills taps 0..2 of the next chunk
+    if (more) {
+      const int group = cn / cpg;
+      if (group != cur_group) {
+        cur_group = group;
+        load_params(group);
+      }
+    }
+    step(p, q, slot, more, 0, buf ^ 1, more, cn, 0);
+    __syncthreads();
+  };
+
+  // prologue: planes of chunk 0, weights and gathered pixels of step 0
+  dm_f32x4 a0[6], a1[6];
+  load_params(0);
+  load_x(0);
+#pragma unroll
+  for (int u = 0; u < 3; ++u) load_a1(a0, 0, 0, u);
+  store_x(0);
+  __syncthreads();
+  {
+    const dm_f32x4* xq = ldsX + xbase;
+    dm_f32x4 tl, tr, bl, br;
+    dm_f32x2 htl, htr, hbl, hbr;
+    whole_read(xq, 0, tl, tr, bl, br);
+    half_read(xq, 0, htl, htr, hbl, hbr);
+    whole_write(0, 0, tl, tr, bl, br);
+    half_write(0, 0, htl, htr, hbl, hbr);
+  }
+  __syncthreads();
+  // (a chunk is three steps: the ring slot and the register set of step 0 both alternate from chunk to chunk)
+  for (int c0 = 0; c0 < a.C; c0 += 16) {
+    chunk(a0, a1, c0, 0, 0);
+    if (c0 + 8 < a.C) chunk(a1, a0, c0 + 8, 1, 1);
+  }
+
+  {
+    float* pj[2];
+    bool col_ok[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      int q = q0 + j * 32 + l31;
+      col_ok[j] = q < a.Q;
+      q = min(q, a.Q - 1);
+      const int n = q / HW;
+      pj[j] = a.out + (size_t)n * a.Cout * HW + (q - n * HW);
+    }
+    const int co_lane = wave * 64 + 4 * hi;
+    const size_t off_lane = (size_t)co_lane * HW;
+    const bool relu = a.relu != 0;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int k = i * 32 + (r & 3) + 8 * (r >> 2);
+        if (co_lane + k < a.Cout) {
+          const size_t o = off_lane + (size_t)k * HW;
+#pragma unroll
+          for (int j = 0; j < 2; ++j)
+            if (col_ok[j]) {
+              float v = acc[i][j][r];
+              if (relu) v = fmaxf(v, 0.f);
+              pj[j][o] = v;
+            }
+        }
+      }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Variant for the large maps (28 x 28, 56 x 56): the bilinear gather runs IN the wave that consumes it.
 // What holds the kernel at the top to a third of the MFMA rate at 64 channels is the path of a sample:
 // two 8-byte global loads (texture path, L2 hits), a combine, a 16-byte LDS write, and an LDS read back by
@@ -1024,6 +1290,31 @@ int launch_dcn(DcnArgs& a, hipStream_t st) {
   return dcn_finish_split(a, a.relu, a.out, st);
 }
 
+// deform_conv_c256_kernel: CoutP == 256, 128 <= H*W <= 256, no split-K.  Two workgroups per CU; with ``tail`` the pixels
+// of a nearly empty last round go to a second launch with 64 x 64 tiles (same bits), as for the 128 x 128 kernel.
+int launch_dcn_c256(DcnArgs& a, bool tail, hipStream_t st) {
+  // B ring (2 x 3 taps x 2 quads x 64 float4) + 2 plane buffers of 2 images x 8 channels: 37 KB at 14 x 14, 44 KB at H*W = 256
+  const size_t lds_bytes = 16 * ((size_t)2 * 3 * 2 * 64) + (size_t)4 * 2 * 2 * 8 * a.HW;
+  const int NTiles = dm_ceil_div(a.Q, 64);
+  const int slots = 2 * dm_num_cus();
+  const int full_rounds = NTiles / slots;
+  const int rem = NTiles - full_rounds * slots;
+  a.ksplit = 1;
+  if (tail && full_rounds >= 1 && rem > 0 && rem * 20 <= 3 * slots) {
+    const int n_main = full_rounds * slots;
+    const int Q = a.Q;
+    a.Q = n_main * 64;
+    DM_LAUNCH(deform_conv_c256_kernel, dim3(n_main), dim3(256), lds_bytes, st, a);
+    int rc = dm_check_launch();
+    if (rc != DM_OK) return rc;
+    a.q_begin = a.Q;
+    a.Q = Q;
+    return launch_dcn<2, 2, 1, 1>(a, st);
+  }
+  DM_LAUNCH(deform_conv_c256_kernel, dim3(NTiles), dim3(256), lds_bytes, st, a);
+  return dm_check_launch();
+}
+
 }  // namespace
 
 struct DcnTout {      // the chained 1x1 (nullptr members: plain DCN)
@@ -1118,10 +1409,11 @@ static int deform_conv_fwd_impl(const float* x, const float* offset, int NB, int
     a.store_out = (out != tout->out2) ? 1 : 0;
   }
   hipStream_t st = (hipStream_t)stream;
-  // 8-wave workgroups: 4 threads share a pixel column, so a thread owns <= 3 taps
-  // (a 256-cout tile would gather each sample once but needs > 256 VGPRs: it spills)
-  // 4-wave workgroups of 128 x 64: two of them share a CU (the 8-wave 128 x 128 tile needs
-  // > 128 VGPRs and runs alone: 1.81 ms vs 1.59 ms at 256 channels)
+  // Tiles.  Every variant runs 4-wave workgroups, two per CU (8-wave tiles run alone on their CU and lose: 128 x 128 from
+  // global memory 1.81 vs 1.59 ms at 256 channels, 256 x 128 from LDS -1 % in the two-stream step).  A wave holds 64
+  // accumulator registers, so a workgroup covers 128 couts x 128 pixels, or 128 x 64 where the gather runs from global
+  // memory -- or 256 couts x 64 pixels on the small maps (deform_conv_c256_kernel: every cout of a pixel in one
+  // workgroup, a sample gathered once; the waves own different couts and read their weights straight from L2).
   // Launches that leave most of the chip idle (a handful of RoIs: real inference) are bound by the time
   // of one workgroup; 64 x 64 tiles give four times the workgroups of the 128 x 128 LDS kernel
   // (14 x 14, 8 RoIs: 0.208 -> 0.108 ms, 32 RoIs: 0.213 -> 0.168 ms; from 64 RoIs on the big tiles win).
@@ -1175,6 +1467,12 @@ static int deform_conv_fwd_impl(const float* x, const float* offset, int NB, int
     // not when the caller overlaps launches on a second stream (flag bit 3: measured 259 vs 251 img/s).
     static const int tail_mode = getenv("DM_DCN_TAIL") ? atoi(getenv("DM_DCN_TAIL")) : 1;
     const int slots = 2 * dm_num_cus();
+    if (a.CoutP == 256) {
+      // 256 couts: one workgroup per 64 pixels holds every cout (deform_conv_c256_kernel: each sample gathered once).
+      // Launches that split their K loop (a caller's workspace and less than one round of tiles) stay on the kernel below.
+      dcn_choose_split(a, (long long)a.MT * NTiles, slots, a.ws_floats, true);
+      if (a.ksplit == 1) return launch_dcn_c256(a, tail_mode && !(relu & 8), st);
+    }
     const int full_rounds = (a.MT * NTiles) / slots;
     const int rem = a.MT * NTiles - full_rounds * slots;
     if (tail_mode && !(relu & 8) && full_rounds >= 1 && rem > 0 && rem * 20 <= 3 * slots) {
