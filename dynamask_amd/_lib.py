@@ -126,6 +126,15 @@ SIGNATURES = {
     'dm_resize_bilinear_fwd': ([_vp, ctypes.c_longlong, _c_int, _c_int, _c_int, _c_int, _vp, _vp], _c_int),
     'dm_conv2d_post_add_fwd': ([_vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _c_int, _vp], _c_int),
     'dm_roi_align_add_fwd': ([_vp, _c_int, _c_int, _c_int, _c_int, _c_float, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp], _c_int),
+    'dm_group_norm_supported': ([ctypes.c_longlong, _c_int, _c_int, _c_int, _c_int], _c_int),
+    'dm_group_norm_fwd': ([_vp, ctypes.c_longlong, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_float, _c_int, _vp, _vp], _c_int),
+    'dm_grid_fusion_supported': ([_c_int] * 4, _c_int),
+    'dm_grid_fusion_table_floats': ([_c_int, _c_int], ctypes.c_longlong),
+    'dm_grid_fusion_fwd': ([_vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp], _c_int),
+    'dm_deconv4x4_s2_grouped_supported': ([_c_int] * 5, _c_int),
+    'dm_deconv4x4_s2_grouped_fwd': ([_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp], _c_int),
+    'dm_grid_get_bboxes_supported': ([_c_int] * 4, _c_int),
+    'dm_grid_get_bboxes': ([_vp, _c_int, _c_int, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp, _vp], _c_int),
     'dm_fc_scratch_floats': ([_c_int, _c_int, _c_int], ctypes.c_longlong),
     'dm_fc_fwd': ([_vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp], _c_int),
     'dm_sgd_momentum_step': ([_vp, _vp, _vp, ctypes.c_longlong, _c_float, _c_float, _c_float, _c_float, _c_int, _vp], _c_int),
@@ -199,7 +208,13 @@ def lib():
         import torch  # noqa: F401
         L = ctypes.CDLL(LIB_PATH)
         for name, (argtypes, restype) in SIGNATURES.items():
-            fn = getattr(L, name)       # AttributeError if the symbol is missing
+            try:
+                fn = getattr(L, name)
+            except AttributeError:
+                # (entry points that are only added keep ABI_VERSION: a library from before them has the number right
+                # and lacks the symbol)
+                raise DynaMaskLibraryError(f'libdynamask_hip.so lacks {name}: it is older than this package, '
+                                           'rebuild') from None
             fn.argtypes = argtypes
             fn.restype = restype
         if L.dm_abi_version() != ABI_VERSION:

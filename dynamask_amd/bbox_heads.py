@@ -73,8 +73,11 @@ class Shared2FCBBoxHead(nn.Module):
                  reg_class_agnostic=False, reg_decoded_bbox=False, loss_cls=None, loss_bbox=None,
                  conv_out_channels=256, conv_cfg=None, norm_cfg=None):
         super().__init__()
-        if with_avg_pool or not with_cls or not with_reg or conv_cfg is not None or norm_cfg is not None:
+        if with_avg_pool or not with_cls or conv_cfg is not None or norm_cfg is not None:
             raise NotImplementedError('configs/dynamask use the plain Shared2FCBBoxHead')
+        # with_reg=False (configs/grid_rcnn: the grid head regresses the box): no fc_reg, forward gives (cls_score, None),
+        # get_bboxes returns the clipped RoIs (bbox_head.py:205-212)
+        self.with_reg = with_reg
         self.roi_feat_size = (roi_feat_size, roi_feat_size) if isinstance(roi_feat_size, int) else tuple(roi_feat_size)
         self.roi_feat_area = self.roi_feat_size[0] * self.roi_feat_size[1]
         self.in_channels = in_channels
@@ -93,14 +96,16 @@ class Shared2FCBBoxHead(nn.Module):
         self.shared_fcs = nn.ModuleList([_FC(in_channels * self.roi_feat_area, fc_out_channels),
                                          _FC(fc_out_channels, fc_out_channels)])
         self.fc_cls = _FC(fc_out_channels, num_classes + 1)
-        self.fc_reg = _FC(fc_out_channels, 4 if reg_class_agnostic else 4 * num_classes)
+        if with_reg:
+            self.fc_reg = _FC(fc_out_channels, 4 if reg_class_agnostic else 4 * num_classes)
 
     def init_weights(self):
         """bbox_head.py:62-70 + convfc_bbox_head.py:128-136."""
         nn.init.normal_(self.fc_cls.weight, 0, 0.01)
         nn.init.constant_(self.fc_cls.bias, 0)
-        nn.init.normal_(self.fc_reg.weight, 0, 0.001)
-        nn.init.constant_(self.fc_reg.bias, 0)
+        if self.with_reg:
+            nn.init.normal_(self.fc_reg.weight, 0, 0.001)
+            nn.init.constant_(self.fc_reg.bias, 0)
         for fc in self.shared_fcs:
             nn.init.xavier_uniform_(fc.weight)
             nn.init.constant_(fc.bias, 0)
@@ -108,11 +113,14 @@ class Shared2FCBBoxHead(nn.Module):
     def forward(self, x):
         """convfc_bbox_head.py:138-186 for the Shared2FC configuration."""
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            if not self.with_reg:
+                raise NotImplementedError('Shared2FCBBoxHead(with_reg=False): the training path (BBoxHeadFn) has both '
+                                          'branches; Grid R-CNN is inference only (run under torch.no_grad())')
             return BBoxHeadFn.apply(self, x, *list(self.parameters()))
         x = x.flatten(1)
         for fc in self.shared_fcs:
             x = fc.run(x, relu=True)
-        return self.fc_cls.run(x), self.fc_reg.run(x)
+        return self.fc_cls.run(x), (self.fc_reg.run(x) if self.with_reg else None)
 
     # ------------------------------------------------------------------ training
     def _get_target_single(self, pos_bboxes, neg_bboxes, pos_gt_bboxes, pos_gt_labels, cfg):

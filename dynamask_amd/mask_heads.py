@@ -51,6 +51,16 @@ class _Packed:
             self._c[key] = e
         return e[1]
 
+    def get_multi(self, key, params, fn):
+        """One pack made from several parameters (a table): ``fn()`` runs again when any of them changes."""
+        ver = tuple((p.data_ptr(), p._version) for p in params) + (params[0].device, ops.WEIGHT_EPOCH[0])
+        e = self._c.get(key)
+        if e is None or e[0] != ver:
+            with torch.no_grad():
+                e = (ver, fn())
+            self._c[key] = e
+        return e[1]
+
 
 class _Conv(nn.Module):
     """Parameter holder named like nn.Conv2d (weight [Cout,Cin,k,k], bias)."""
@@ -1596,3 +1606,256 @@ class FusedSemanticHead(nn.Module):
 
     def loss(self, mask_pred, labels):
         raise NotImplementedError('FusedSemanticHead: the semantic segmentation loss is training (HTC is inference only here)')
+
+
+# ---------------------------------------------------------------- Grid R-CNN head (inference)
+def grid_sub_regions(grid_points, whole_map_size):
+    """grid_head.py:189-218 (calc_sub_regions), restated with its ``int(...)`` truncations: per point the
+    (x1, y1, x2, y2) of its half-sized region of the ``whole_map_size`` map."""
+    grid_size = int(math.sqrt(grid_points))
+    half_size = whole_map_size // 4 * 2
+    sub_regions = []
+    for i in range(grid_points):
+        x_idx = i // grid_size
+        y_idx = i % grid_size
+        if x_idx == 0:
+            sub_x1 = 0
+        elif x_idx == grid_size - 1:
+            sub_x1 = half_size
+        else:
+            ratio = x_idx / (grid_size - 1) - 0.25
+            sub_x1 = max(int(ratio * whole_map_size), 0)
+        if y_idx == 0:
+            sub_y1 = 0
+        elif y_idx == grid_size - 1:
+            sub_y1 = half_size
+        else:
+            ratio = y_idx / (grid_size - 1) - 0.25
+            sub_y1 = max(int(ratio * whole_map_size), 0)
+        sub_regions.append((sub_x1, sub_y1, sub_x1 + half_size, sub_y1 + half_size))
+    return sub_regions
+
+
+class _GroupNorm(nn.Module):
+    """Parameter holder named like nn.GroupNorm (weight, bias [C]); the normalisation is ops.group_norm."""
+
+    def __init__(self, num_groups, num_channels, eps=1e-5):
+        super().__init__()
+        if num_channels % num_groups != 0:
+            raise ValueError(f'GroupNorm: {num_channels} channels do not split into {num_groups} groups')
+        self.num_groups, self.num_channels, self.eps = num_groups, num_channels, eps
+        self.weight = nn.Parameter(torch.ones(num_channels))
+        self.bias = nn.Parameter(torch.zeros(num_channels))
+
+    def run_(self, x, relu=False):
+        """In place."""
+        return ops.group_norm(x, self.weight.detach(), self.bias.detach(), self.num_groups, self.eps, relu=relu, out=x)
+
+
+class GNConvModule(nn.Module):
+    """mmcv ConvModule with ``norm_cfg=dict(type='GN', num_groups=G)``: 3x3 conv (bias) -> GroupNorm -> ReLU, keys
+    ``conv.weight / conv.bias / gn.weight / gn.bias``.  Stride 1 runs on ops.conv2d (conv_igemm), stride 2 on
+    ops.conv3x3_s2, both always on the exact fp32 layout with one fixed association of the K sum (no split-K: a RoI's
+    bits do not depend on how many RoIs share the call); the norm and the ReLU are one in-place ops.group_norm.
+    (``ConvModule`` above stays the norm-free class: it refuses ``norm_cfg``.)"""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, conv_cfg=None, norm_cfg=None,
+                 act_cfg=dict(type='ReLU'), bias=True):
+        super().__init__()
+        if conv_cfg is not None:
+            raise NotImplementedError('GNConvModule: conv_cfg is None in configs/grid_rcnn')
+        if not isinstance(norm_cfg, dict) or norm_cfg.get('type') != 'GN' or set(norm_cfg) - {'type', 'num_groups', 'requires_grad'}:
+            raise NotImplementedError('GNConvModule: norm_cfg=dict(type="GN", num_groups=G) only')
+        if kernel_size != 3 or padding != 1 or stride not in (1, 2) or not bias:
+            raise NotImplementedError('GNConvModule: 3x3 convolutions with padding 1, stride 1 or 2 and a bias only')
+        if in_channels % 8 != 0:
+            raise NotImplementedError('GNConvModule: in_channels a multiple of 8 (the 3x3 kernels\' K chunk)')
+        self.stride = stride
+        self.conv = _Conv(in_channels, out_channels, 3)
+        self.conv.exact = True
+        self.gn = _GroupNorm(norm_cfg['num_groups'], out_channels)
+        self.with_activation = act_cfg is not None
+
+    def forward(self, x):
+        conv = self.conv
+        if self.stride == 2:
+            if not ops.conv3x3_s2_supported(x, conv.out_channels, 1):
+                raise NotImplementedError(f'GNConvModule: no stride-2 kernel for {tuple(x.shape)} -> {conv.out_channels}')
+            y = ops.conv3x3_s2(x, conv.packed(), conv.bias.detach(), conv.out_channels, relu=False, splits=1)
+        else:
+            y = ops.conv2d([x], conv.packed(), conv.bias.detach(), conv.out_channels, 3, relu=False)
+        return self.gn.run_(y, relu=self.with_activation)
+
+
+class _GridTransition(nn.Sequential):
+    """One transition of the neighbour fusion, keys ``0.*`` (depthwise 5x5) and ``1.*`` (1x1) as the reference's
+    nn.Sequential(nn.Conv2d(c, c, 5, padding=2, groups=c), nn.Conv2d(c, c, 1)); parameters only -- all transitions of an
+    order run in one ops.grid_fusion launch."""
+
+    def __init__(self, channels):
+        dw, pw = nn.Module(), nn.Module()
+        dw.weight = nn.Parameter(torch.empty(channels, 1, 5, 5))
+        dw.bias = nn.Parameter(torch.zeros(channels))
+        pw.weight = nn.Parameter(torch.empty(channels, channels, 1, 1))
+        pw.bias = nn.Parameter(torch.zeros(channels))
+        nn.init.kaiming_normal_(dw.weight, mode='fan_out', nonlinearity='relu')
+        nn.init.kaiming_normal_(pw.weight, mode='fan_out', nonlinearity='relu')
+        super().__init__(dw, pw)
+
+    def forward(self, x):
+        raise NotImplementedError('a transition does not run alone: GridHead fuses all of an order in one launch')
+
+
+class _GroupedDeconv(nn.Module):
+    """Parameter holder named like nn.ConvTranspose2d(cin, cout, 4, stride=2, padding=1, groups=g): weight
+    [cin, cout / g, 4, 4], bias [cout]; runs on ops.deconv4x4_s2_grouped, which reads torch's layout as it is."""
+
+    def __init__(self, in_channels, out_channels, groups):
+        super().__init__()
+        self.in_channels, self.out_channels, self.groups = in_channels, out_channels, groups
+        self.weight = nn.Parameter(torch.empty(in_channels, out_channels // groups, 4, 4))
+        self.bias = nn.Parameter(torch.zeros(out_channels))
+        nn.init.normal_(self.weight, 0, 0.001)
+
+    def run(self, x):
+        if not ops.deconv4x4_s2_grouped_supported(x, self.out_channels, self.groups):
+            raise NotImplementedError(f'grouped deconv: no kernel for {tuple(x.shape)} -> {self.out_channels} '
+                                      f'in {self.groups} groups')
+        return ops.deconv4x4_s2_grouped(x, self.weight.detach(), self.bias.detach(), self.groups)
+
+
+@HEADS.register_module()
+class GridHead(nn.Module):
+    """``GridHead`` -- mmdet/models/roi_heads/mask_heads/grid_head.py, inference (:13-187, :189-218, :294-359): per RoI
+    the heatmaps of ``grid_points`` grid points, from which ``get_bboxes`` votes the refined box.  The reference's
+    constructor arguments and ``state_dict`` keys: ``convs.{i}.conv / .gn``, ``deconv1``, ``norm1``, ``deconv2``,
+    ``forder_trans.{i}.{j}.{0,1}`` and ``sorder_trans.{i}.{j}.{0,1}`` (j in the reference's neighbour order left, up, down,
+    right).  The launches: conv 0 on ops.conv3x3_s2, convs 1.. on ops.conv2d, GroupNorm + ReLU in place after each, one
+    ops.grid_fusion per fusion order (the 48 transitions of an order in one launch, their weights in one packed table per
+    weight version), ops.deconv4x4_s2_grouped twice, ops.grid_get_bboxes.  Everything is exact fp32 whatever
+    ``set_conv_precision`` says.  What the kernels were not run on is refused here."""
+
+    def __init__(self, grid_points=9, num_convs=8, roi_feat_size=14, in_channels=256, conv_kernel_size=3,
+                 point_feat_channels=64, deconv_kernel_size=4, class_agnostic=False,
+                 loss_grid=dict(type='CrossEntropyLoss', use_sigmoid=True, loss_weight=15), conv_cfg=None,
+                 norm_cfg=dict(type='GN', num_groups=36)):
+        super().__init__()
+        if grid_points < 4:
+            raise ValueError('grid_points >= 4')
+        grid_size = int(math.sqrt(grid_points))
+        if grid_size * grid_size != grid_points:
+            raise ValueError('grid_points must be a square number')
+        if not isinstance(roi_feat_size, int):
+            raise ValueError('Only square RoIs are supporeted in Grid R-CNN')
+        if grid_points != 9:
+            raise NotImplementedError('GridHead: grid_points=9 only (configs/grid_rcnn)')
+        if point_feat_channels != 64:
+            raise NotImplementedError('GridHead: point_feat_channels=64 only (configs/grid_rcnn; the fusion kernel\'s width)')
+        if roi_feat_size != 14:
+            raise NotImplementedError('GridHead: roi_feat_size=14 only (7 x 7 maps inside the head, 28 x 28 heatmaps)')
+        if conv_kernel_size != 3 or deconv_kernel_size != 4:
+            raise NotImplementedError('GridHead: conv_kernel_size=3 and deconv_kernel_size=4 only (configs/grid_rcnn)')
+        if num_convs < 1:
+            raise NotImplementedError('GridHead: num_convs >= 1 (the first convolution is the stride-2 one)')
+        if in_channels % 8 != 0:
+            raise NotImplementedError('GridHead: in_channels a multiple of 8 (configs/grid_rcnn: 256)')
+        if conv_cfg is not None:
+            raise NotImplementedError('GridHead: conv_cfg is None in configs/grid_rcnn')
+        self.grid_points = grid_points
+        self.num_convs = num_convs
+        self.roi_feat_size = roi_feat_size
+        self.in_channels = in_channels
+        self.conv_kernel_size = conv_kernel_size
+        self.point_feat_channels = point_feat_channels
+        self.conv_out_channels = point_feat_channels * grid_points
+        self.class_agnostic = class_agnostic
+        self.conv_cfg = conv_cfg
+        self.norm_cfg = norm_cfg
+        if not isinstance(norm_cfg, dict) or norm_cfg.get('type') != 'GN':
+            raise NotImplementedError('GridHead: norm_cfg=dict(type="GN", num_groups=G) only (configs/grid_rcnn)')
+        if self.conv_out_channels % norm_cfg['num_groups'] != 0:
+            raise ValueError(f'GridHead: {self.conv_out_channels} channels do not split into {norm_cfg["num_groups"]} groups')
+        self.grid_size = grid_size
+        self.whole_map_size = roi_feat_size * 4
+        self.sub_regions = self.calc_sub_regions()
+        self.convs = nn.Sequential(*[
+            GNConvModule(in_channels if i == 0 else self.conv_out_channels, self.conv_out_channels, 3,
+                         stride=2 if i == 0 else 1, padding=1, norm_cfg=norm_cfg) for i in range(num_convs)])
+        self.deconv1 = _GroupedDeconv(self.conv_out_channels, self.conv_out_channels, grid_points)
+        self.norm1 = _GroupNorm(grid_points, self.conv_out_channels)
+        self.deconv2 = _GroupedDeconv(self.conv_out_channels, grid_points, grid_points)
+        self.neighbor_points = ops.grid_neighbors(grid_points)
+        self.num_edges = sum(len(p) for p in self.neighbor_points)
+        self.forder_trans = nn.ModuleList()
+        self.sorder_trans = nn.ModuleList()
+        for neighbors in self.neighbor_points:
+            self.forder_trans.append(nn.ModuleList([_GridTransition(point_feat_channels) for _ in neighbors]))
+            self.sorder_trans.append(nn.ModuleList([_GridTransition(point_feat_channels) for _ in neighbors]))
+        from . import losses  # noqa: F401  (registers CrossEntropyLoss)
+        self.loss_grid = build_loss(loss_grid)
+        self._pk = _Packed()
+
+    def init_weights(self):
+        """grid_head.py:141-149."""
+        for m in self.modules():
+            if isinstance(m, (_Conv, _GridTransition)):
+                for p in ([m.weight] if isinstance(m, _Conv) else [m[0].weight, m[1].weight]):
+                    nn.init.kaiming_normal_(p, mode='fan_out', nonlinearity='relu')
+                for b in ([m.bias] if isinstance(m, _Conv) else [m[0].bias, m[1].bias]):
+                    nn.init.constant_(b, 0)
+        for m in (self.deconv1, self.deconv2):
+            nn.init.normal_(m.weight, 0, 0.001)
+            nn.init.constant_(m.bias, 0)
+        nn.init.constant_(self.deconv2.bias, -math.log(0.99 / 0.01))
+
+    def calc_sub_regions(self):
+        """grid_head.py:189-218."""
+        return grid_sub_regions(self.grid_points, self.whole_map_size)
+
+    def _fusion_table(self, name):
+        """The packed table of one fusion order, rebuilt when any of its parameters changes (``_Packed.get_multi``)."""
+        trans = getattr(self, name)
+
+        def pack():
+            slots = [[(t[0].weight, t[0].bias, t[1].weight, t[1].bias) for t in point] for point in trans]
+            return ops.pack_grid_fusion_table(slots, self.grid_points, self.point_feat_channels)
+        return self._pk.get_multi(name, [p for t in trans for p in t.parameters()], pack)
+
+    def forward(self, x):
+        """grid_head.py:151-187 in eval mode -> ``dict(fused=heatmap [n, P, 28, 28], unfused=the same tensor)``."""
+        if self.training or (torch.is_grad_enabled() and x.requires_grad):
+            raise NotImplementedError('GridHead: training (the unfused branch, get_targets, the loss) is the follow-up to '
+                                      'inference; call it in eval mode under torch.no_grad()')
+        if x.dim() != 4 or x.shape[1] != self.in_channels or x.shape[-1] != self.roi_feat_size or \
+                x.shape[-2] != self.roi_feat_size:
+            raise ValueError(f'GridHead: RoI features [n, {self.in_channels}, {self.roi_feat_size}, {self.roi_feat_size}] '
+                             f'expected, got {list(x.shape)}')
+        half = self.whole_map_size // 4 * 2
+        if x.shape[0] == 0:
+            heat = x.new_zeros((0, self.grid_points, half, half))
+            return dict(fused=heat, unfused=heat)
+        with torch.no_grad():
+            x = self.convs(x.contiguous())
+            if not ops.grid_fusion_supported(x, self.grid_points):
+                raise NotImplementedError(f'GridHead: no fusion kernel for {tuple(x.shape)}')
+            x_fo = ops.grid_fusion(x, x, self._fusion_table('forder_trans'), self.grid_points)
+            x_so = ops.grid_fusion(x, x_fo, self._fusion_table('sorder_trans'), self.grid_points)
+            x2 = self.norm1.run_(self.deconv1.run(x_so), relu=True)
+            heat = self.deconv2.run(x2)
+        return dict(fused=heat, unfused=heat)
+
+    def get_bboxes(self, det_bboxes, grid_pred, img_metas=None):
+        """grid_head.py:294-359 on the device (ops.grid_get_bboxes) -> [n, 5], on ``det_bboxes``' device.  The boxes are
+        not clipped to the image: the reference's ``clamp_`` works on a copy (Quirk Q21), ``img_metas`` is unread."""
+        assert det_bboxes.shape[0] == grid_pred.shape[0]
+        half = self.whole_map_size // 4 * 2
+        assert grid_pred.shape[1] == self.grid_points and grid_pred.shape[2] == grid_pred.shape[3] == half
+        if det_bboxes.shape[0] == 0:
+            return det_bboxes.new_zeros((0, 5))
+        return ops.grid_get_bboxes(grid_pred.contiguous(), det_bboxes.contiguous(), self.sub_regions)
+
+    def get_targets(self, *a, **k):
+        raise NotImplementedError('GridHead.get_targets: Grid R-CNN training is the follow-up to inference')
+
+    def loss(self, *a, **k):
+        raise NotImplementedError('GridHead.loss: Grid R-CNN training is the follow-up to inference')

@@ -2443,3 +2443,145 @@ def roi_align_add_(feats, fmap, rois, size, spatial_scale, sampling_ratio=0):
     check(lib().dm_roi_align_add_fwd(_p(fmap), B, C, H, W, float(spatial_scale), _p(rois), N, int(size), int(sampling_ratio),
                                      pool, _p(feats), _stream()), 'dm_roi_align_add_fwd')
     return feats
+
+
+# ------------------------------------------------ Grid R-CNN: the GridHead launches (csrc/grid_head.hip)
+# Exact fp32 in every precision mode: the bf16x3 mode does not reach these launches.
+def group_norm_supported(x, num_groups):
+    N, C, H, W = x.shape
+    return bool(lib().dm_group_norm_supported(N, C, int(num_groups), H, W))
+
+
+def group_norm(x, weight, bias, num_groups, eps=1e-5, relu=False, out=None):
+    """GroupNorm(num_groups, C, eps)(x) (+ ReLU) of x [N, C, H, W] with per-channel ``weight`` / ``bias`` [C]
+    (dm_group_norm_fwd; biased variance, two-pass statistics).  ``out`` may be ``x`` itself: in place."""
+    _chk(x, 'x')
+    _chk(weight, 'weight')
+    _chk(bias, 'bias')
+    if x.dim() != 4:
+        raise ValueError(f'x: [N, C, H, W] expected, got {list(x.shape)}')
+    N, C, H, W = x.shape
+    assert weight.shape == (C,) and bias.shape == (C,)
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _chk(out, 'out')
+        assert out.shape == x.shape
+    check(lib().dm_group_norm_fwd(_p(x), N, C, int(num_groups), H, W, _p(weight), _p(bias), float(eps), 1 if relu else 0,
+                                  _p(out), _stream()), 'dm_group_norm_fwd')
+    return out
+
+
+def grid_neighbors(grid_points):
+    """grid_head.py:88-102: per point (= column * grid_size + row) its neighbours in the order left, up, down, right."""
+    gs = int(round(grid_points ** 0.5))
+    assert gs * gs == grid_points
+    out = []
+    for i in range(gs):
+        for j in range(gs):
+            nb = []
+            if i > 0:
+                nb.append((i - 1) * gs + j)
+            if j > 0:
+                nb.append(i * gs + j - 1)
+            if j < gs - 1:
+                nb.append(i * gs + j + 1)
+            if i < gs - 1:
+                nb.append((i + 1) * gs + j)
+            out.append(tuple(nb))
+    return out
+
+
+def grid_fusion_supported(x, grid_points):
+    N, C, H, W = x.shape
+    return H == W and C % grid_points == 0 and bool(lib().dm_grid_fusion_supported(N, int(grid_points), C // grid_points, H))
+
+
+def pack_grid_fusion_table(trans, grid_points, channels):
+    """The weight table of one fusion order (dm_grid_fusion_fwd): ``trans[i][j]`` = (dw weight [c, 1, 5, 5], dw bias [c],
+    1x1 weight [c, c, 1, 1], 1x1 bias [c]) of point i's j-th neighbour -> [P][4][25 c + c + c c + c] floats, the 1x1
+    weight transposed to [k][o]; the slots a point has no neighbour for stay zero."""
+    P, c = int(grid_points), int(channels)
+    total = int(lib().dm_grid_fusion_table_floats(P, c))
+    if total < 0:
+        raise NotImplementedError(f'grid fusion: no kernel for {P} points of {c} channels')
+    E = total // (4 * P)
+    dev = trans[0][0][0].device
+    table = torch.zeros((P, 4, E), device=dev, dtype=torch.float32)
+    for i, slots in enumerate(trans):
+        assert len(slots) <= 4
+        for j, (dw_w, dw_b, w1, b1) in enumerate(slots):
+            assert dw_w.shape == (c, 1, 5, 5) and dw_b.shape == (c,) and w1.shape == (c, c, 1, 1) and b1.shape == (c,)
+            table[i, j] = torch.cat([dw_w.detach().reshape(-1), dw_b.detach(), w1.detach().reshape(c, c).t().reshape(-1),
+                                     b1.detach()])
+    return table.reshape(-1)
+
+
+def grid_fusion(x, src, table, grid_points, out=None):
+    """One order of GridHead's neighbour fusion in one launch (dm_grid_fusion_fwd): per point i,
+    ``x_i + sum_j trans_ij(src_{neighbour j of i})`` -> [N, P c, S, S].  ``src`` is ``x`` (first order) or the first
+    order's result (second order); ``out`` may be neither."""
+    _chk(x, 'x')
+    _chk(src, 'src')
+    _chk(table, 'table')
+    N, C, H, W = x.shape
+    P = int(grid_points)
+    assert src.shape == x.shape and H == W and C % P == 0
+    assert table.numel() == int(lib().dm_grid_fusion_table_floats(P, C // P)), 'table packed for another shape'
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _chk(out, 'out')
+        assert out.shape == x.shape
+    check(lib().dm_grid_fusion_fwd(_p(x), _p(src), N, P, C // P, H, _p(table), _p(out), _stream()), 'dm_grid_fusion_fwd')
+    return out
+
+
+def deconv4x4_s2_grouped_supported(x, cout, groups):
+    N, C, H, W = x.shape
+    g = int(groups)
+    return H == W and C % g == 0 and cout % g == 0 and bool(
+        lib().dm_deconv4x4_s2_grouped_supported(N, g, C // g, int(cout) // g, H))
+
+
+def deconv4x4_s2_grouped(x, weight, bias, groups, out=None):
+    """ConvTranspose2d(C, cout, 4, stride=2, padding=1, groups=groups)(x) (dm_deconv4x4_s2_grouped_fwd): ``weight``
+    [C, cout / groups, 4, 4] in torch's layout (no packing), ``bias`` [cout] or None -> [N, cout, 2 S, 2 S]."""
+    _chk(x, 'x')
+    _chk(weight, 'weight')
+    if bias is not None:
+        _chk(bias, 'bias')
+    N, C, H, W = x.shape
+    g = int(groups)
+    assert H == W and C % g == 0 and weight.dim() == 4 and weight.shape[0] == C and tuple(weight.shape[2:]) == (4, 4)
+    co = int(weight.shape[1])
+    assert bias is None or bias.shape == (g * co,)
+    shape = (N, g * co, 2 * H, 2 * W)
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=torch.float32)
+    else:
+        _chk(out, 'out')
+        assert tuple(out.shape) == shape
+    check(lib().dm_deconv4x4_s2_grouped_fwd(_p(x), N, g, C // g, co, H, _p(weight), _p(bias), _p(out), _stream()),
+          'dm_deconv4x4_s2_grouped_fwd')
+    return out
+
+
+def grid_get_bboxes(heat, det_bboxes, sub_regions, out=None, return_cells=False):
+    """GridHead.get_bboxes on the device (dm_grid_get_bboxes): ``heat`` [n, P, HS, HS] logits, ``det_bboxes`` [n, D >= 5]
+    (score last), ``sub_regions`` the P (x1, y1, x2, y2) of calc_sub_regions -> [n, 5], NOT clipped to the image.
+    ``return_cells``: also the cell of each point's maximum within its map, int32 [n, P]."""
+    _chk(heat, 'heat')
+    _chk(det_bboxes, 'det_bboxes')
+    n, P, HS, HS2 = heat.shape
+    assert HS == HS2 and det_bboxes.dim() == 2 and det_bboxes.shape[0] == n and len(sub_regions) == P
+    if out is None:
+        out = torch.empty((n, 5), device=heat.device, dtype=torch.float32)
+    else:
+        _chk(out, 'out')
+        assert tuple(out.shape) == (n, 5)
+    cells = torch.empty((n, P), device=heat.device, dtype=torch.int32) if return_cells else None
+    check(lib().dm_grid_get_bboxes(_p(heat), n, P, HS, _p(det_bboxes), det_bboxes.shape[1],
+                                   _int_array([r[0] for r in sub_regions]), _int_array([r[1] for r in sub_regions]),
+                                   _p(out), _p(cells), _stream()), 'dm_grid_get_bboxes')
+    return (out, cells) if return_cells else out

@@ -1,6 +1,6 @@
 """The RoI heads behind the reference's HEADS registry, in the reference's class tree: ``StandardRoIHead``
 (standard_roi_head.py + test_mixins.py) is the base of ``DynaMaskRoIHead``, ``RefineRoIHead``, ``PointRendRoIHead``,
-``MaskScoringRoIHead``, ``PointRefineRoIHead`` and ``CascadeRoIHead``.
+``MaskScoringRoIHead``, ``PointRefineRoIHead``, ``GridRoIHead`` and ``CascadeRoIHead``.
 
 The base holds the constructor (incl. ``base_roi_head.py:10-58``'s MaskPre, Quirk Q4), the assigner / sampler, the bbox
 branch, the one-image / batched / test-time-augmentation entry points and one mask-test template over a head's
@@ -1274,6 +1274,137 @@ class MaskScoringRoIHead(StandardRoIHead):
             return segms, [[] for _ in range(num_classes)]
         scores, labels = (t.numpy()[start:start + count] for t in pending)
         return segms, group_mask_scores(scores, labels, num_classes)
+
+
+@HEADS.register_module()
+class GridRoIHead(StandardRoIHead):
+    """``GridRoIHead`` -- mmdet/models/roi_heads/grid_roi_head.py, inference (:15-24, :127-164): the RoI head of
+    configs/grid_rcnn, a ``StandardRoIHead`` whose bbox head only classifies (``Shared2FCBBoxHead(with_reg=False)``: the
+    detections are the clipped proposals that survive the NMS) and whose ``grid_head`` (``GridHead``) then moves every kept
+    box to the vote of nine predicted grid points.  ``grid_roi_extractor=None`` shares the bbox extractor.  ``simple_test``
+    is the reference's sequence; ``batch_simple_test`` runs one grid chain for the detections of all images and gives,
+    per image, ``simple_test``'s bits.  A configured ``mask_head`` runs the base class's mask test on the refined boxes.
+    Training, test-time augmentation and HIP-graph capture raise."""
+
+    def __init__(self, grid_roi_extractor=None, grid_head=None, **kwargs):
+        if grid_head is None:
+            raise ValueError('GridRoIHead needs a grid_head (grid_roi_head.py:16)')
+        super().__init__(**kwargs)
+        if not self.with_bbox:
+            raise ValueError('GridRoIHead needs a bbox branch (grid_roi_head.py:134)')
+        if grid_roi_extractor is not None:
+            self.grid_roi_extractor = build_roi_extractor(grid_roi_extractor)
+            self.share_roi_extractor = False
+        else:
+            self.share_roi_extractor = True
+            self.grid_roi_extractor = self.bbox_roi_extractor
+        self.grid_head = build_head(grid_head)
+
+    def init_weights(self, pretrained=None):
+        super().init_weights(pretrained)
+        self.grid_head.init_weights()
+        if not self.share_roi_extractor:
+            self.grid_roi_extractor.init_weights()
+
+    def forward_train(self, x, img_metas, proposal_list, gt_bboxes, gt_labels, gt_bboxes_ignore=None, gt_masks=None):
+        raise NotImplementedError('GridRoIHead.forward_train: Grid R-CNN training (the jittered positives, the grid targets, '
+                                  'the unfused branch and the loss) is the follow-up to inference')
+
+    def aug_test(self, x, proposal_list, img_metas, rescale=False, encode=False):
+        raise NotImplementedError('GridRoIHead.aug_test: the reference has none for Grid R-CNN (grid_roi_head.py inherits '
+                                  'StandardRoIHead.aug_test, which never runs the grid head)')
+
+    def enable_inference_graphs(self, on=True, buckets=None, batch_buckets=None):
+        if on:
+            raise NotImplementedError('GridRoIHead: HIP-graph capture of the grid chain is a follow-up')
+        self._mask_graphs = None
+        return None
+
+    def _grid_refine(self, x, det_bboxes_list):
+        """The grid chain of grid_roi_head.py:139-147 for the detections of the images of a call, as one chain: RoIs from
+        ``det_bboxes[:, :4]`` (batch column = image index), the 14 x 14 RoI features, ``grid_head``, ``get_bboxes`` on the
+        ``fused`` heatmap -> the refined [sum n, 5].  Nothing is launched for zero detections."""
+        dets = torch.cat(list(det_bboxes_list)).contiguous() if len(det_bboxes_list) > 1 else det_bboxes_list[0].contiguous()
+        if dets.shape[0] == 0:
+            return dets.new_zeros((0, 5))
+        with torch.no_grad():
+            grid_rois = bbox2roi([d[:, :4] for d in det_bboxes_list]).contiguous()
+            ext = self.grid_roi_extractor
+            grid_feats = ext(x[:len(ext.featmap_strides)], grid_rois)
+            grid_pred = self.grid_head(grid_feats)
+            return self.grid_head.get_bboxes(dets, grid_pred['fused'])
+
+    def _rescale_(self, det_bboxes, scale_factor):
+        """grid_roi_head.py:148-152."""
+        if det_bboxes.shape[0] == 0:
+            return det_bboxes
+        if not isinstance(scale_factor, (float, torch.Tensor)):
+            import numpy as np
+            scale_factor = self._scale_factor_on(np.asarray(scale_factor, dtype=np.float32), det_bboxes.device)
+        det_bboxes[:, :4] /= scale_factor
+        return det_bboxes
+
+    @torch.no_grad()
+    def simple_test_grid(self, x, proposal_list, img_metas, rescale=False):
+        """``simple_test`` up to the refined detections on the device -> (det_bboxes [n, 5], det_labels [n])."""
+        det_bboxes, det_labels = self.simple_test_bboxes(x, img_metas, proposal_list, self.test_cfg, rescale=False)
+        det_bboxes = self._grid_refine(x, [det_bboxes])
+        if rescale:
+            det_bboxes = self._rescale_(det_bboxes, img_metas[0]['scale_factor'])
+        return det_bboxes, det_labels
+
+    @torch.no_grad()
+    def simple_test(self, x, proposal_list, img_metas, proposals=None, rescale=False, encode=False):
+        """grid_roi_head.py:127-164."""
+        from .bbox_heads import bbox2result
+        det_bboxes, det_labels = self.simple_test_grid(x, proposal_list, img_metas, rescale=rescale)
+        bbox_results = bbox2result(det_bboxes, det_labels, self._bbox_num_classes())
+        if not self.with_mask:
+            return bbox_results
+        segm_results = self.simple_test_mask(x, img_metas, det_bboxes, det_labels, rescale=rescale, encode=encode)
+        return bbox_results, segm_results
+
+    @torch.no_grad()
+    def batch_simple_test_grid(self, x, proposal_list, img_metas, rescale=False):
+        """``simple_test_grid`` of B images -> list of B (det_bboxes, det_labels), each with the bits of the one-image
+        call: one bbox branch, one segmented NMS and ONE grid chain over the detections of all images."""
+        B = self._check_batch(img_metas, proposal_list=proposal_list)
+        self._check_metas(img_metas, self._META_KEYS)
+        for i, f in enumerate(x):
+            if f.shape[0] != B:
+                raise ValueError(f'x[{i}] has batch dimension {f.shape[0]} for {B} images')
+        dets = self.batch_simple_test_bboxes(x, img_metas, proposal_list, self.test_cfg, rescale=False)
+        refined = self._grid_refine(x, [d for d, _ in dets])
+        out, start = [], 0
+        for (d, labels), meta in zip(dets, img_metas):
+            r = refined[start:start + d.shape[0]]
+            start += d.shape[0]
+            if rescale:
+                r = self._rescale_(r.clone(), meta['scale_factor'])
+            out.append((r, labels))
+        return out
+
+    @torch.no_grad()
+    def batch_simple_test(self, x, proposal_list, img_metas, rescale=False, encode=False):
+        from .mask_heads import _to_host
+        dets = self.batch_simple_test_grid(x, proposal_list, img_metas, rescale=rescale)
+        counts = [int(d.shape[0]) for d, _ in dets]
+        num_classes = self._bbox_num_classes()
+        if sum(counts) == 0:
+            bbox_results = [_bbox2result_host(dets[0][0].new_zeros((0, 5)), None, num_classes) for _ in dets]
+            labels_h = []
+        else:
+            d_np, l_np = _to_host(torch.cat([d for d, _ in dets]), torch.cat([l for _, l in dets]))
+            labels_h = l_np.tolist()
+            bbox_results, start = [], 0
+            for c in counts:
+                bbox_results.append(_bbox2result_host(d_np[start:start + c], l_np[start:start + c], num_classes))
+                start += c
+        if not self.with_mask:
+            return bbox_results
+        segm_results = self.batch_simple_test_mask(x, img_metas, [d for d, _ in dets], [l for _, l in dets],
+                                                   rescale=rescale, encode=encode, _labels_host=labels_h)
+        return list(zip(bbox_results, segm_results))
 
 
 @HEADS.register_module()

@@ -59,7 +59,8 @@ const char* dm_error_string(int code);
  * selection, point gather, point MLP and scatter (section K22); Mask Scoring R-CNN's stride-2 3x3 convolution, IoU-head
  * input and mask scores (section K23); PointRefine's descending point selection, point-feature gather, point MLP and
  * multi-row scatter (section K24); Cascade Mask R-CNN's stage-grouped convolutions / deconvolutions and stage step
- * (section K25); Hybrid Task Cascade's resize, post-activation addend and RoIAlign-add (section K26). */
+ * (section K25); Hybrid Task Cascade's resize, post-activation addend and RoIAlign-add (section K26); Grid R-CNN's
+ * GroupNorm, neighbour fusion, grouped 4x4 stride-2 deconvolution and box vote (section K27). */
 int dm_abi_version(void);
 /* "libdynamask_hip abi=N arch=gfx950 compiler=<clang version> flags=<the product-wide flags of dynamask_amd/build.py>"
  * (static storage).  The library must be compiled WITHOUT packed fp32 instructions (flag "-packed-fp32-ops", see
@@ -1005,6 +1006,55 @@ int dm_conv2d_post_add_fwd(const float* const* srcs, const int* src_channels, co
                            dm_stream_t stream);
 int dm_roi_align_add_fwd(const float* feat, int B, int C, int H, int W, float spatial_scale, const float* rois, int N,
                          int P, int sampling_ratio, int pool, float* out, dm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * K27  Grid R-CNN inference: GridHead (mmdet/models/roi_heads/mask_heads/grid_head.py:151-187, :294-359),
+ *      csrc/grid_head.hip.  All exact fp32 in every precision mode, one fixed summation order, no atomics: the same bits
+ *      on every run, and a sample's result does not depend on the other samples of the call.
+ *
+ * dm_group_norm_fwd: y = GroupNorm(G groups, eps, per-channel gamma / beta)(x) (+ ReLU when relu == 1) of x [N, C, H, W];
+ * biased variance; y may be x (in place).  The statistics are two passes over the group on values shifted by its first
+ * element (never E[x^2] - E[x]^2): a constant group gives exactly beta.  dm_group_norm_supported: 1 exactly when N >= 0,
+ * C, G, H, W >= 1, C % G == 0, (C / G) * H * W <= 2^24 and N * G < 2^31.  N == 0 enqueues nothing; relu other than 0 / 1
+ * or eps <= 0: DM_ERR_INVALID_ARG.
+ *
+ * dm_grid_fusion_fwd: one order of the neighbour fusion (grid_head.py:157-170) in one launch.  x, src, out
+ * [N, P * c, S, S] (point i = channels [i c, (i + 1) c)); for every sample and point i
+ *   out_i = x_i + sum_j (W1_ij * dw5x5_ij(src_{nb(i, j)}) + b1_ij),
+ * dw5x5 the depthwise 5 x 5 convolution (padding 2) with its bias, W1 the 1x1 convolution c -> c, nb(i, j) the j-th
+ * neighbour of point i = column * sqrt(P) + row in the reference's order (left, up, down, right: grid_head.py:88-102), the
+ * terms added in that order.  First order: src = x; second order: src = the first order's out.  out may be neither x nor
+ * src.  table: [P][4][E] floats, E = 25 c + c + c c + c, slot (i, j) = [dw weight [c][25]][dw bias [c]][W1 transposed
+ * [k][o]][b1 [c]]; slots past a point's neighbour count are not read.  dm_grid_fusion_table_floats: P * 4 * E (-1 for an
+ * unsupported P, c).  dm_grid_fusion_supported: 1 exactly when N >= 0, P is 4 or 9, c is 8 or 64, S is 3 or 7.
+ *
+ * dm_deconv4x4_s2_grouped_fwd: ConvTranspose2d(G ci, G co, kernel 4, stride 2, padding 1, groups = G) + bias:
+ * x [N, G ci, S, S], w [G ci, co, 4, 4] (torch's layout), bias [G co] or NULL, out [N, G co, 2 S, 2 S].  Four output
+ * phases of 2 x 2 taps each.  dm_deconv4x4_s2_grouped_supported: 1 exactly when N >= 0, G is 4 or 9, ci is 8 or 64,
+ * co is 1, 8 or 64 and S is 1, 3, 7 or 14.
+ *
+ * dm_grid_get_bboxes: GridHead.get_bboxes on the device.  heat [n, P, HS, HS] logits, det [n, D] (x1, y1, x2, y2, ...,
+ * score last), sub_x / sub_y: HOST arrays of P ints (calc_sub_regions' x1, y1 per point), out [n, 5].  Per (sample,
+ * point): the maximum of sigmoid(heat) (the paste kernels' expression) and its FIRST cell among equal sigmoid values --
+ * not the argmax of the logits: saturated cells tie -- then, one fp32 rounding per operation as in the reference:
+ * xs = cell % HS + sub_x, ys = cell / HS + sub_y; abs = (xs + 0.5) / HS * width + (x1 - width / 2) on the box expanded by
+ * half its size each side; each box side = sum(abs * score) / sum(score) over the sqrt(P) points of that side;
+ * out[:, 4] = det[:, D - 1]; cells (int32 [n, P], may be NULL) receives each point's cell.  The box is NOT clipped to the image (the reference clamps a copy).
+ * dm_grid_get_bboxes_supported: 1 exactly when n >= 0, P is 4 or 9, 1 <= HS <= 1024 and D >= 5.  n == 0 enqueues nothing.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int dm_group_norm_supported(long long N, int C, int G, int H, int W);
+int dm_group_norm_fwd(const float* x, long long N, int C, int G, int H, int W, const float* gamma, const float* beta,
+                      float eps, int relu, float* y, dm_stream_t stream);
+int dm_grid_fusion_supported(int N, int P, int c, int S);
+long long dm_grid_fusion_table_floats(int P, int c);
+int dm_grid_fusion_fwd(const float* x, const float* src, int N, int P, int c, int S, const float* table, float* out,
+                       dm_stream_t stream);
+int dm_deconv4x4_s2_grouped_supported(int N, int G, int ci, int co, int S);
+int dm_deconv4x4_s2_grouped_fwd(const float* x, int N, int G, int ci, int co, int S, const float* w, const float* bias,
+                                float* out, dm_stream_t stream);
+int dm_grid_get_bboxes_supported(int n, int P, int HS, int D);
+int dm_grid_get_bboxes(const float* heat, int n, int P, int HS, const float* det, int D, const int* sub_x, const int* sub_y,
+                       float* out, int* cells, dm_stream_t stream);
 
 #ifdef __cplusplus
 }
