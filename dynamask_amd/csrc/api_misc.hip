@@ -11,7 +11,7 @@ extern "C" const char* dm_error_string(int code) {
   }
 }
 
-extern "C" int dm_abi_version(void) { return 28; }
+extern "C" int dm_abi_version(void) { return DM_ABI_VERSION; }
 
 // How this library was compiled: the compiler and the product-wide flag set dynamask_amd/build.py passed (it hands them
 // over as -DDM_BUILD_FLAGS="..."; a recipe that does not say what it used yields "flags=unknown").  The host binding
@@ -21,8 +21,10 @@ extern "C" int dm_abi_version(void) { return 28; }
 #ifndef DM_BUILD_FLAGS
 #define DM_BUILD_FLAGS "unknown"
 #endif
+#define DM_STR_(x) #x
+#define DM_STR(x) DM_STR_(x)
 extern "C" const char* dm_build_info(void) {
-  return "libdynamask_hip abi=28 arch=gfx950 compiler=" __clang_version__ " flags=" DM_BUILD_FLAGS;
+  return "libdynamask_hip abi=" DM_STR(DM_ABI_VERSION) " arch=gfx950 compiler=" __clang_version__ " flags=" DM_BUILD_FLAGS;
 }
 
 // ---------------------------------------------------------------------------

@@ -24,13 +24,12 @@ The core (``Tracker``) is plain Python over integer stream ids and byte ranges: 
 without a GPU; tests/test_hazard_gpu.py runs the training step under it.
 """
 import os
-import re
 import weakref
+
+from . import _abi
 
 ENABLED = [os.environ.get('DM_HAZARD', '0') not in ('', '0')]
 RAISE = [os.environ.get('DM_HAZARD', '0') == '2']
-
-_HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'dynamask_hip.h')
 
 
 class HazardError(RuntimeError):
@@ -38,27 +37,10 @@ class HazardError(RuntimeError):
 
 
 # --------------------------------------------------------------------------- prototypes -> argument roles
-def parse_header(path=_HEADER):
+def parse_header(path=_abi.HEADER):
     """{function: [role, ...]} with role in 'in' (const T*), 'out' (T*), 'in[]' / 'out[]' (host array of device
-    pointers), 'stream', 'scalar'."""
-    src = open(path).read()
-    src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
-    out = {}
-    for name, args in re.findall(r'\b(?:int|long long|const char\*)\s+(dm_\w+)\s*\((.*?)\)\s*;', src, flags=re.S):
-        roles = []
-        for a in [' '.join(x.split()) for x in args.split(',')]:
-            if a in ('void', ''):
-                continue
-            if a.startswith('dm_stream_t'):
-                roles.append('stream')
-            elif '*' not in a:
-                roles.append('scalar')
-            elif a.count('*') == 2:
-                roles.append('in[]' if a.startswith('const') else 'out[]')
-            else:
-                roles.append('in' if a.startswith('const') else 'out')
-        out[name] = roles
-    return out
+    pointers), 'stream', 'scalar': the roles side of the one header parse (_abi.py)."""
+    return {name: [role for _, role in args] for name, (_, args) in _abi.load(path)[0].items()}
 
 
 # --------------------------------------------------------------------------- access patterns

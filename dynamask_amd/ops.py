@@ -8,7 +8,7 @@ import ctypes
 
 import torch
 
-from . import hazard
+from . import _abi, hazard
 from . import precision as _precision
 from ._lib import check, lib
 
@@ -411,7 +411,7 @@ def nms_segmented(boxes_sorted, counts, iou_threshold, offset=0, max_num=-1):
 
 
 # --------------------------------------------------------------- test-time augmentation (several views of one image)
-AUG_VIEW_FLOATS = 8                 # dynamask_hip.h DM_AUG_VIEW_FLOATS
+AUG_VIEW_FLOATS = _abi.load()[1]['DM_AUG_VIEW_FLOATS']           # (prototypes, constants) of dynamask_hip.h
 AUG_FLIP_CODES = {'horizontal': 1, 'vertical': 2}
 
 

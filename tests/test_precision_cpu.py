@@ -61,9 +61,9 @@ def test_symbols_exported_and_abi():
     roles = hazard.parse_header()
     assert roles['dm_conv_pack_weight_bf16x3'][0] == 'in' and roles['dm_conv_pack_weight_bf16x3'][7] == 'out'
     header = open(os.path.join(ROOT, 'include', 'dynamask_hip.h')).read()
-    assert '28: the opt-in bf16x3 mode' in header
+    assert '28: the opt-in bf16x3 mode' in header and '#define DM_ABI_VERSION 28' in header
     src = open(os.path.join(ROOT, 'dynamask_amd', 'csrc', 'api_misc.hip')).read()
-    assert 'dm_abi_version(void) { return 28; }' in src
+    assert 'dm_abi_version(void) { return DM_ABI_VERSION; }' in src
 
 
 def test_mode_applies_only_without_grad_and_outside_the_training_path():
