@@ -364,10 +364,10 @@ int launch_carafe_bwd(const float* x, const float* enc, const float* gout, int N
   constexpr int KK = K * K, R = K / 2;
   const int cpg = C / group, HW = H * W;
   const int CT = (cpg % 32 == 0) ? 32 : (cpg % 16 == 0) ? 16 : 4;      // x tile of CT channels: 41 KB at 32 (18 x 18 padded)
-  if (hipMemsetAsync(gm, 0, (size_t)NB * group * 4 * KK * HW * sizeof(float), st) != hipSuccess) return DM_ERR_LAUNCH;
   const size_t lds_a = (size_t)(CT / 4) * (H + 2 * R) * (W + 2 * R) * sizeof(float4);
   const size_t lds_b = (size_t)4 * KK * HW * sizeof(float) + (size_t)4 * HW * sizeof(float4);
-  if (lds_a > 64 * 1024 || lds_b > 160 * 1024) return DM_ERR_UNSUPPORTED;
+  if (lds_a > 64 * 1024 || lds_b > 160 * 1024) return DM_ERR_UNSUPPORTED;      // (before anything is enqueued: a refusal writes nothing)
+  if (hipMemsetAsync(gm, 0, (size_t)NB * group * 4 * KK * HW * sizeof(float), st) != hipSuccess) return DM_ERR_LAUNCH;
   const dim3 grid((unsigned)(NB * group * (cpg / CT)));
   static bool attr_set[DM_MAX_DEVICES] = {false};
   if (lds_b > 64 * 1024 &&
@@ -435,7 +435,7 @@ extern "C" int dm_carafe_bwd(const float* x, const float* enc, const float* grad
     return DM_ERR_INVALID_ARG;
   if (NB == 0) return DM_OK;
   // the mask head's shape only (14x14 -> 28x28): one image's normalised kernels fit LDS
-  if (scale != 2 || H * W > 256 || (C / group) % 4 != 0 || W % 1 != 0) return DM_ERR_UNSUPPORTED;
+  if (scale != 2 || H * W > 256 || (C / group) % 4 != 0) return DM_ERR_UNSUPPORTED;
   if (up_kernel == 5) return launch_carafe_bwd<5>(x, enc, grad_out, NB, C, H, W, group, grad_x, grad_enc, scratch, (hipStream_t)stream);
   if (up_kernel == 3) return launch_carafe_bwd<3>(x, enc, grad_out, NB, C, H, W, group, grad_x, grad_enc, scratch, (hipStream_t)stream);
   return DM_ERR_UNSUPPORTED;

@@ -1148,7 +1148,7 @@ extern "C" int dm_class_balance_fwd_bwd(const float* mask_labels, int N, int K, 
 
 extern "C" int dm_gumbel_select_bwd(const float* y_soft, const float* grad_y, int N, int K, float temperature,
                                     float* grad_logits, dm_stream_t stream) {
-  if (!y_soft || !grad_y || !grad_logits || N < 0 || K <= 0 || temperature <= 0.f) return DM_ERR_INVALID_ARG;
+  if (!y_soft || !grad_y || !grad_logits || N < 0 || K <= 0 || K > 8 || temperature <= 0.f) return DM_ERR_INVALID_ARG;
   if (N == 0) return DM_OK;
   DM_LAUNCH(gumbel_bwd_kernel, dim3(dm_ceil_div(N, 64)), dim3(64), 0, (hipStream_t)stream, y_soft, grad_y, N, K,
                      temperature, grad_logits);

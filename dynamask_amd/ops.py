@@ -2136,7 +2136,8 @@ def bbox_encode(proposals, gt, means=(0., 0., 0., 0.), stds=(1., 1., 1., 1.)):
 
 
 def softmax_ce(cls_score, labels, weight, scale, need_grad=True):
-    """-> (loss [1] = scale * sum_i w_i CE_i, acc [1] percent, grad [N, C] or None)."""
+    """-> (loss [1] = scale * sum_i w_i CE_i, acc [1] percent, grad [N, C] or None).  The prediction behind ``acc`` is the
+    LOWEST index among a row's maxima: an exact tie at the top counts as correct only for the lowest tied class."""
     _chk(cls_score, 'cls_score')
     _chk(labels, 'labels', torch.int64)
     if weight is not None:

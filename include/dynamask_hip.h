@@ -660,8 +660,10 @@ int dm_sgd_momentum_step(float* params, const float* grads, float* momentum_buf,
 /* Backward of the FCNMaskHead upsample layers (mask_heads/fcn_mask_head.py:84-96; the forward of the
  * deconv / CARAFE / bilinear forms is above).
  * dm_carafe_bwd: gradients of dm_carafe_fwd with respect to x and enc (mmcv carafe backward +
- *   kernel_normalizer backward), for scale 2 and H*W <= 256 (the mask head: 14x14 -> 28x28); other shapes
- *   return DM_ERR_UNSUPPORTED.  scratch: dm_carafe_bwd_scratch_floats() floats.
+ *   kernel_normalizer backward), for scale 2, H*W <= 256 (the mask head: 14x14 -> 28x28), up_kernel 3 or 5,
+ *   (C / group) % 4 == 0 and a padded x tile of CT channels (CT = 32, 16 or 4, the largest that divides C / group)
+ *   within 64 KB of LDS; any H and W under that, odd ones included.  Other shapes return DM_ERR_UNSUPPORTED and
+ *   write nothing.  scratch: dm_carafe_bwd_scratch_floats() floats.
  * dm_upsample2x_nearest_fwd / _bwd: nn.Upsample(scale_factor=2, mode='nearest') and its adjoint.
  * dm_pixel_unshuffle2x: out[n, (dy*2+dx)*C + c, y, x] = in[n, c, 2y+dy, 2x+dx]: with it the backward of the
  *   2x2 stride-2 ConvTranspose2d is dm_conv2d_fwd (data) + dm_conv2d_wgrad (weights) on 1x1 GEMMs. */

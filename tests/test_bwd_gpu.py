@@ -207,20 +207,52 @@ def test_sigmoid_backward(ops):
     _close(out, logit.grad, atol=1e-4, rtol=1e-4)
 
 
-@pytest.mark.parametrize('N,C,S', [(5, 64, 14), (3, 32, 28), (2, 16, 9)])
-def test_deform_conv_backward(ops, N, C, S):
+# (N, C, S, deform_groups); the first three keep their ids from before deform_groups was a parameter; (2, 256, 14) is
+# the training shape
+DCN_BWD_CASES = [(5, 64, 14, 2), (3, 32, 28, 2), (2, 16, 9, 2), (5, 64, 14, 1), (3, 32, 28, 4), (2, 16, 9, 1), (2, 16, 9, 4),
+                 (2, 256, 14, 1), (2, 256, 14, 2), (2, 256, 14, 4)]
+
+
+def _dcn_bwd_inputs(N, C, S, dg):
     x = torch.randn(N, C, S, S, generator=_g(70), requires_grad=True)
     w = (torch.randn(C, C, 3, 3, generator=_g(71)) / (9 * C) ** 0.5).requires_grad_(True)
-    off = (torch.randn(N, 36, S, S, generator=_g(72)) * 1.2)
+    off = (torch.randn(N, 18 * dg, S, S, generator=_g(72)) * 1.2)
     off[0, :, 0, 0] = 30.0
     off = off.requires_grad_(True)
-    y = ref_ops.deform_conv2d(x, off, w, 1, 1, 1, 2)
+    y = ref_ops.deform_conv2d(x, off, w, 1, 1, 1, dg)
     go = torch.randn(y.shape, generator=_g(73))
     y.backward(go)
-    gx, goff, gw = ops.deform_conv_backward(_dev(x), _dev(off), _dev(w), _dev(go), 2)
+    return x, w, off, go
+
+
+@pytest.mark.parametrize('N,C,S,dg', DCN_BWD_CASES,
+                         ids=[f'{n}-{c}-{s}' if dg == 2 and c != 256 else f'{n}-{c}-{s}-dg{dg}' for n, c, s, dg in DCN_BWD_CASES])
+def test_deform_conv_backward(ops, N, C, S, dg):
+    x, w, off, go = _dcn_bwd_inputs(N, C, S, dg)
+    gx, goff, gw = ops.deform_conv_backward(_dev(x), _dev(off), _dev(w), _dev(go), dg)
     _close(gx, x.grad, atol=1e-4, rtol=1e-4)
     _close(goff, off.grad, atol=1e-4, rtol=1e-4)
     _close(gw, w.grad, atol=1e-4, rtol=1e-4)
+
+
+def test_deform_conv_backward_accumulates_into_gw_accum_with_a_kept_col(ops):
+    """``gw_accum=`` and ``col=`` (what the training path passes): nothing is returned for the weight gradient, and the
+    accumulator holds what it held plus the gradient."""
+    N, C, S, dg = 3, 32, 28, 4
+    x, w, off, go = _dcn_bwd_inputs(N, C, S, dg)
+    xd, od, wd, gd = _dev(x), _dev(off), _dev(w), _dev(go)
+    _, _, gw = ops.deform_conv_backward(xd, od, wd, gd, dg)
+    before = torch.randn(C, C, 3, 3, generator=_g(74))
+    acc = _dev(before)
+    col = ops.deform_im2col(xd, od, dg)
+    gx, goff, none = ops.deform_conv_backward(xd, od, wd, gd, dg, gw_accum=acc, col=col)
+    assert none is None
+    _close(gx, x.grad, atol=1e-4, rtol=1e-4)
+    _close(goff, off.grad, atol=1e-4, rtol=1e-4)
+    _close(acc, before + w.grad, atol=1e-4, rtol=1e-4)
+    # ... which is the gradient the call without gw_accum returns, added once (2e-6 of the largest value: this file's bound
+    # for the same sums met in another order)
+    assert float((acc.cpu() - (before + gw.cpu())).abs().max()) <= 2e-6 * max(float(gw.abs().max()), float(before.abs().max()))
 
 
 @pytest.mark.parametrize('N,cins,cout,H,W,ks', [(9, [64], 64, 14, 14, 1), (5, [64, 64, 2], 64, 28, 28, 1), (3, [48], 200, 10, 6, 3),
