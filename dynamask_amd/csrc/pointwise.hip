@@ -1182,6 +1182,8 @@ __global__ __launch_bounds__(256) void threshold_kernel(const float* __restrict_
 // image pixel centres mapped into its box, thresholded.  grid = (row blocks, N).
 // (_do_paste_mask, fcn_mask_head.py:240-308 with skip_empty=False, + the >= thr of
 // get_seg_masks, dynamask_head.py:333-334)
+// A NaN coordinate samples nothing: the value is 0 and the bit is 0 >= thr.  (A zero-width box with a pixel centre
+// exactly on it gives 0 / 0.)
 __global__ __launch_bounds__(256) void paste_masks_kernel(const float* __restrict__ masks, const float* __restrict__ boxes,
                                                           int N, int mh, int mw, int img_h, int img_w, float thr,
                                                           int apply_sigmoid, uint8_t* __restrict__ out) {
@@ -1239,6 +1241,7 @@ extern "C" int dm_threshold_ge(const float* x, long long count, float thr, float
 extern "C" int dm_paste_masks(const float* masks, const float* boxes, int N, int mask_h, int mask_w, int img_h, int img_w,
                               float threshold, int apply_sigmoid, uint8_t* out, dm_stream_t stream) {
   if (N < 0 || mask_h <= 0 || mask_w <= 0 || img_h <= 0 || img_w <= 0) return DM_ERR_INVALID_ARG;
+  if (N > 65535) return DM_ERR_INVALID_ARG;      // the masks are the grid's y dimension
   if (N == 0) return DM_OK;
   if (!masks || !boxes || !out) return DM_ERR_INVALID_ARG;
   const int bx = min(dm_ceil_div((long long)img_h * img_w, 256 * 4), 1024);

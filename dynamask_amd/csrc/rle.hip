@@ -307,6 +307,7 @@ extern "C" long long dm_rle_scratch_ints(int N, int img_h, int img_w) {
 extern "C" int dm_rle_encode_canvas(const uint8_t* canvas, int N, int img_h, int img_w, int* seg_scratch, int* mask_runs,
                                     int* mask_start, int* positions, int capacity, dm_stream_t stream) {
   if (N < 0 || img_h <= 0 || img_w <= 0 || capacity < 0) return DM_ERR_INVALID_ARG;
+  if (N > 65535) return DM_ERR_INVALID_ARG;      // the masks are the grid's y dimension
   if (N == 0) return DM_OK;
   if (!canvas || !seg_scratch || !mask_runs || !mask_start || (!positions && capacity > 0)) return DM_ERR_INVALID_ARG;
   CanvasSrc src{canvas, img_h, img_w};
@@ -317,6 +318,7 @@ extern "C" int dm_paste_rle(const float* masks, const float* boxes, int N, int m
                             float threshold, int apply_sigmoid, int* seg_scratch, int* mask_runs, int* mask_start,
                             int* positions, int capacity, dm_stream_t stream) {
   if (N < 0 || mask_h <= 0 || mask_w <= 0 || img_h <= 0 || img_w <= 0 || capacity < 0) return DM_ERR_INVALID_ARG;
+  if (N > 65535) return DM_ERR_INVALID_ARG;      // the masks are the grid's y dimension
   if (N == 0) return DM_OK;
   if (!masks || !boxes || !seg_scratch || !mask_runs || !mask_start || (!positions && capacity > 0)) return DM_ERR_INVALID_ARG;
   PasteSrc src{masks, boxes, mask_h, mask_w, threshold, apply_sigmoid};

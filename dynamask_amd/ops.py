@@ -142,6 +142,14 @@ def roi_align_backward(grad_out, feat_shapes, rois, output_size, spatial_scales,
 
 
 # --------------------------------------------------------------- RLE (after the path, 8f rank 2)
+MAX_MASKS_PER_LAUNCH = 65535      # dm_paste_masks, dm_rle_encode_canvas, dm_paste_rle: the masks are the grid's y dimension
+
+
+def _chk_mask_count(N, name):
+    if N > MAX_MASKS_PER_LAUNCH:
+        raise ValueError(f'{name}: {N} masks in one call, at most {MAX_MASKS_PER_LAUNCH} (split the batch)')
+
+
 def _rle_collect(N, img_h, img_w, runs, start, positions, launch, capacity, sizes=None):
     """Shared tail of the encoders: read the run totals, re-run once with a larger
     buffer if the boundaries did not fit, copy exactly the used part of `positions`, build
@@ -165,6 +173,8 @@ def _rle_collect(N, img_h, img_w, runs, start, positions, launch, capacity, size
     buf = C.create_string_buffer(cap)
     for n in range(N):
         s0, s1 = int(start_h[n]), int(start_h[n + 1])
+        if not 0 <= s0 <= s1 <= total:           # dm_rle_string would read past the host copy of the boundaries
+            raise RuntimeError(f'RLE encoder: mask {n} has its boundaries at [{s0}, {s1}) of {total} counted in all')
         need = (s1 - s0 + 1) * 7             # <= 7 characters per count (31-bit values)
         if need > cap:
             cap = need
@@ -185,6 +195,7 @@ def rle_encode(canvas):
     N, h, w = canvas.shape
     if N == 0:
         return []
+    _chk_mask_count(N, 'rle_encode')
     dev = canvas.device
     scratch = torch.empty((lib().dm_rle_scratch_ints(N, h, w),), device=dev, dtype=torch.int32)
     runs = torch.empty((N,), device=dev, dtype=torch.int32)
@@ -207,6 +218,7 @@ def paste_rle(masks, boxes, img_h, img_w, threshold=0.5, apply_sigmoid=False):
     N = masks.shape[0]
     if N == 0:
         return []
+    _chk_mask_count(N, 'paste_rle')
     mh, mw = masks.shape[-2:]
     dev = masks.device
     img_h, img_w = int(img_h), int(img_w)
@@ -352,7 +364,8 @@ def bbox_decode(rois, cls_score, bbox_pred, num_classes, means=(0., 0., 0., 0.),
 
 def nms(boxes, scores, iou_threshold, offset=0, max_num=-1):
     """mmcv.ops.nms: (dets [k, 5] in descending score order, keep indices [k] into the input).
-    Suppression matrix on the device, greedy pass on the host."""
+    Suppression matrix on the device, greedy pass on the host.  ``max_num`` <= 0: no limit, as in ``nms_segmented``
+    and ``multiclass_nms``."""
     import ctypes as C
     _chk(boxes, 'boxes')
     _chk(scores, 'scores')
@@ -366,7 +379,8 @@ def nms(boxes, scores, iou_threshold, offset=0, max_num=-1):
     check(lib().dm_nms_mask(_p(sb), M, float(iou_threshold), int(offset), _p(mask), _stream()), 'dm_nms_mask')
     mask_h = mask.cpu()                                   # synchronises
     keep_h = torch.empty((M,), dtype=torch.int32)
-    n = lib().dm_nms_reduce(C.c_void_p(mask_h.data_ptr()), M, C.c_void_p(keep_h.data_ptr()), int(max_num))
+    n = lib().dm_nms_reduce(C.c_void_p(mask_h.data_ptr()), M, C.c_void_p(keep_h.data_ptr()),
+                            int(max_num) if max_num > 0 else -1)
     keep_sorted = keep_h[:n].to(device=boxes.device, dtype=torch.long)
     keep = order[keep_sorted]
     dets = torch.cat([boxes[keep], scores[keep][:, None]], 1)
@@ -2024,10 +2038,13 @@ def threshold_ge(x, thr):
 def paste_masks(masks, boxes, img_h, img_w, threshold=0.5, apply_sigmoid=False, out=None):
     """masks [N, 1, h, w] or [N, h, w], boxes [N, 4] -> bool [N, img_h, img_w].
     ``out``: optional contiguous uint8 [N, img_h, img_w] slab to paste into (a slice of a
-    larger canvas when detections are pasted bucket by bucket)."""
+    larger canvas when detections are pasted bucket by bucket).
+    A NaN coordinate samples nothing: the value is 0 and the bit is ``0 >= threshold``.  (A zero-width box with a pixel
+    centre exactly on it gives 0 / 0.)"""
     _chk(masks, 'masks')
     _chk(boxes, 'boxes')
     N = masks.shape[0]
+    _chk_mask_count(N, 'paste_masks')
     mh, mw = masks.shape[-2:]
     if out is None:
         out = torch.empty((N, img_h, img_w), device=masks.device, dtype=torch.uint8)

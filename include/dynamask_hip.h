@@ -459,7 +459,8 @@ int dm_polygon_mask_targets(const double* verts, const int* poly_start, const in
  * and binarise: out[n, y, x] = (grid_sample(mask_n) >= threshold) as uint8.
  * replaces: _do_paste_mask (mask_heads/fcn_mask_head.py:240-308, skip_empty=False) +
  * the threshold of get_seg_masks (mask_heads/dynamask_head.py:325-339).
- * apply_sigmoid != 0 takes logits (mask_pred.sigmoid() of dynamask_head.py:281). */
+ * apply_sigmoid != 0 takes logits (mask_pred.sigmoid() of dynamask_head.py:281).
+ * N <= 65535 (the masks are the grid's y dimension): more returns DM_ERR_INVALID_ARG before anything is launched. */
 int dm_paste_masks(const float* masks, const float* boxes, int N, int mask_h, int mask_w, int img_h, int img_w,
                    float threshold, int apply_sigmoid, uint8_t* out, dm_stream_t stream);
 
@@ -473,7 +474,9 @@ int dm_paste_masks(const float* masks, const float* boxes, int N, int mask_h, in
  * Boundaries past `capacity` are counted but not stored (caller re-runs with a larger buffer).
  * seg_scratch: dm_rle_scratch_ints(N, img_h, img_w) int32.
  * dm_rle_string (host code, no GPU work): boundaries -> run lengths -> the printable
- * `counts` string of the COCO RLE format; returns its length, or -(needed) if cap is short. */
+ * `counts` string of the COCO RLE format; returns its length, or -(needed) if cap is short.
+ * dm_rle_encode_canvas and dm_paste_rle: N <= 65535 (the masks are the grid's y dimension); more returns
+ * DM_ERR_INVALID_ARG before anything is launched. */
 long long dm_rle_scratch_ints(int N, int img_h, int img_w);
 int dm_rle_encode_canvas(const uint8_t* canvas, int N, int img_h, int img_w, int* seg_scratch, int* mask_runs,
                          int* mask_start, int* positions, int capacity, dm_stream_t stream);
