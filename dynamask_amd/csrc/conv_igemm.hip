@@ -32,6 +32,13 @@
 
 namespace {
 
+// dm_conv2d_plan's recorder (host side): launch_conv_mp writes one record per launch it would make and launches nothing.
+// A record is DM_CONV_PLAN_INTS ints in the order the header documents.
+struct ConvPlan {
+  int count = 0;
+  int rec[DM_CONV_PLAN_MAX_LAUNCHES][DM_CONV_PLAN_INTS];
+};
+
 struct ConvArgs {
   const float* src[DM_MAX_SOURCES];
   int src_c[DM_MAX_SOURCES];
@@ -59,6 +66,7 @@ struct ConvArgs {
   int want_split = 0;        // host side: the launcher's choice of splits for this launch (0: launch_conv_mp decides)
   // POST builds (dm_conv2d_post_add_fwd): same layout as out, added AFTER the activation; may be out itself
   const float* addend = nullptr;
+  ConvPlan* plan = nullptr;  // host side, null in every product call: record the launch instead of making it (dm_conv2d_plan)
 };
 
 // CK input channels per chunk (multiple of 8); MAXPOS = plane positions per thread (3x3)
@@ -953,12 +961,17 @@ int launch_conv_mp(ConvArgs& a, hipStream_t st) {
   constexpr int NWC = PREC ? 6 : CK / 4;
   const size_t lds_bytes = 16 * ((size_t)KS * KS * NWC * (TM + TAIL) + (size_t)NWC * a.plane);
   if (lds_bytes > 64 * 1024) {
-    // (the bf16x3 3x3 build: 54 KB of A image + 21 KB of plane at 14 x 14; two workgroups per CU)
-    if (!PREC || lds_bytes > 80 * 1024) return DM_ERR_UNSUPPORTED;
-    static bool raised[DM_MAX_DEVICES] = {false};
-    const int rc = dm_ensure_lds_limit(reinterpret_cast<const void*>(&conv_igemm_kernel<KS, WGM, WGN, WM, WN, CK, MAXPOS, TAIL, PREC, POST>),
-                                       80 * 1024, raised);
-    if (rc != DM_OK) return rc;
+    // (the bf16x3 3x3 build: 54 KB of A image + 21 KB of plane at 14 x 14; two workgroups per CU.  The exact 128-cout 3x3
+    // builds whose plane holds more than 896 positions -- 36 KB of A image + 32 bytes per position: maps 148 .. 168 wide,
+    // and narrower single-row ones, 1 x 100: 9 rows of 102 -- while the 64- and 32-cout builds stage every plane up to the
+    // 1024-position limit in 64 KB: whether a map can be staged must not depend on Cout)
+    if (lds_bytes > 80 * 1024) return DM_ERR_UNSUPPORTED;
+    if (!a.plan) {
+      static bool raised[DM_MAX_DEVICES] = {false};
+      const int rc = dm_ensure_lds_limit(reinterpret_cast<const void*>(&conv_igemm_kernel<KS, WGM, WGN, WM, WN, CK, MAXPOS, TAIL, PREC, POST>),
+                                         80 * 1024, raised);
+      if (rc != DM_OK) return rc;
+    }
   }
   // ---- split-K for launches that leave most of the chip idle (a caller-provided workspace, one launch per call)
   a.ksplit = 1;
@@ -981,6 +994,15 @@ int launch_conv_mp(ConvArgs& a, hipStream_t st) {
       a.ksplit = dm_ceil_div(chunks, a.kchunks);
       a.ws_stride = per;
     }
+  }
+  if (a.plan) {
+    // (dm_conv2d_plan) what the launches below would be given, and nothing launched
+    if (a.plan->count >= DM_CONV_PLAN_MAX_LAUNCHES) return DM_ERR_INVALID_ARG;
+    const int rec[DM_CONV_PLAN_INTS] = {KS, WGM, WGN, WM, WN, CK, TAIL, PREC, POST, MAXPOS, a.ksplit, a.ksplit > 1 ? a.kchunks : 0,
+                                        a.q_begin, a.Q, a.MT * NTiles, a.ksplit, (a.relu & 4) ? 1 : 0};
+    for (int i = 0; i < DM_CONV_PLAN_INTS; ++i) a.plan->rec[a.plan->count][i] = rec[i];
+    a.plan->count++;
+    return DM_OK;
   }
   if (a.ksplit > 1) {
     const float* bias = a.bias;
@@ -1223,7 +1245,7 @@ static int conv2d_launch(const float* const* srcs, const int* src_channels, cons
                          int num_srcs, int NB, int H, int W,
                          const float* w_packed, const float* bias, int Cout, int ksize, int relu, float* out,
                          int out_ch_total, int out_ch_offset, const float* mask, dm_stream_t stream, float* ws = nullptr,
-                         long long ws_floats = 0, const float* addend = nullptr);
+                         long long ws_floats = 0, const float* addend = nullptr, ConvPlan* plan = nullptr);
 
 extern "C" int dm_conv2d_fwd(const float* const* srcs, const int* src_channels, const long long* src_batch_strides,
                              int num_srcs, int NB, int H, int W,
@@ -1266,7 +1288,6 @@ extern "C" int dm_conv2d_fwd_masked(const float* const* srcs, const int* src_cha
                                     const float* w_packed, const float* bias, int Cout, int ksize, int relu, float* out,
                                     int out_ch_total, int out_ch_offset, const float* mask, dm_stream_t stream) {
   if (!mask) return DM_ERR_INVALID_ARG;
-  if (relu & 16) return DM_ERR_UNSUPPORTED;      // (no bf16x3 build of the data-gradient launches)
   return conv2d_launch(srcs, src_channels, src_batch_strides, num_srcs, NB, H, W, w_packed, bias, Cout, ksize, relu, out,
                        out_ch_total, out_ch_offset, mask, stream);
 }
@@ -1282,17 +1303,39 @@ extern "C" int dm_conv2d_post_add_fwd(const float* const* srcs, const int* src_c
                        out_ch_total, out_ch_offset, nullptr, stream, nullptr, 0, addend);
 }
 
+// (added to ABI 28) What dm_conv2d_fwd / _ws / _masked / dm_conv2d_post_add_fwd would launch for these host arguments: the
+// launcher itself runs with a recorder and launches nothing (no pointer below is read; the header has the record layout).
+extern "C" int dm_conv2d_plan(const int* src_channels, const long long* src_batch_strides, int num_srcs, int NB, int H, int W,
+                              int Cout, int ksize, int relu, int out_ch_total, int out_ch_offset, long long workspace_floats,
+                              int has_mask, int has_addend, int* records, int max_records) {
+  if (!records || max_records < DM_CONV_PLAN_MAX_LAUNCHES || workspace_floats < 0) return DM_ERR_INVALID_ARG;
+  if ((has_mask || has_addend) && workspace_floats > 0) return DM_ERR_INVALID_ARG;      // (no entry point takes both)
+  if (has_mask && has_addend) return DM_ERR_INVALID_ARG;
+  static float dummy[4];
+  const float* srcs[DM_MAX_SOURCES] = {dummy, dummy, dummy, dummy};
+  ConvPlan plan;
+  const int rc = conv2d_launch(srcs, src_channels, src_batch_strides, num_srcs, NB, H, W, dummy, nullptr, Cout, ksize, relu, dummy,
+                               out_ch_total, out_ch_offset, has_mask ? dummy : nullptr, nullptr,
+                               workspace_floats > 0 ? dummy : nullptr, workspace_floats, has_addend ? dummy : nullptr, &plan);
+  if (rc != DM_OK) return rc;
+  for (int l = 0; l < plan.count; ++l)
+    for (int i = 0; i < DM_CONV_PLAN_INTS; ++i) records[l * DM_CONV_PLAN_INTS + i] = plan.rec[l][i];
+  return plan.count;
+}
+
 static int conv2d_launch(const float* const* srcs, const int* src_channels, const long long* src_batch_strides,
                          int num_srcs, int NB, int H, int W,
                          const float* w_packed, const float* bias, int Cout, int ksize, int relu, float* out,
                          int out_ch_total, int out_ch_offset, const float* mask, dm_stream_t stream, float* ws,
-                         long long ws_floats, const float* addend) {
+                         long long ws_floats, const float* addend, ConvPlan* plan) {
+  if (mask && (relu & 16)) return DM_ERR_UNSUPPORTED;      // (no bf16x3 build of the data-gradient launches)
   if (!srcs || !src_channels || num_srcs < 1 || num_srcs > DM_MAX_SOURCES || !w_packed || !out) return DM_ERR_INVALID_ARG;
   if (NB < 0 || H <= 0 || W <= 0 || Cout <= 0 || (ksize != 1 && ksize != 3)) return DM_ERR_INVALID_ARG;
   if (out_ch_offset < 0 || out_ch_offset + Cout > out_ch_total) return DM_ERR_INVALID_ARG;
   if ((long long)NB * H * W > 0x7fffffffLL) return DM_ERR_INVALID_ARG;
   if (NB == 0) return DM_OK;
   ConvArgs a;
+  a.plan = plan;
   for (int s = 0; s < DM_MAX_SOURCES; ++s) {
     a.src[s] = s < num_srcs ? srcs[s] : nullptr;
     a.src_c[s] = s < num_srcs ? src_channels[s] : 0;
@@ -1304,7 +1347,7 @@ static int conv2d_launch(const float* const* srcs, const int* src_channels, cons
     }
   }
   a.num_srcs = num_srcs;
-  if (relu & ~31) return DM_ERR_INVALID_ARG;      // (bit 5 selected a bf16-split layout of ABI 18-21: removed)
+  if (relu & ~(1 | 2 | 8 | 16)) return DM_ERR_INVALID_ARG;      // (bit 2 is the launcher's own store-policy bit; bit 5 selected a bf16-split layout of ABI 18-21: removed)
   const bool bf16x3 = (relu & 16) != 0;          // (ABI 28) w_packed is the bf16x3 layout (dm_conv_pack_weight_bf16x3)
   a.KQ = bf16x3 ? packed_words_bf16x3(num_srcs, src_channels) : packed_quads(num_srcs, src_channels);
   a.NB = NB; a.H = H; a.W = W; a.HW = H * W; a.Q = NB * H * W;
@@ -1355,6 +1398,10 @@ static int conv2d_launch(const float* const* srcs, const int* src_channels, cons
       // of the kernel; 14 x 14 maps), else 2
       const int rmax128 = dm_ceil_div(127, a.W) + 1 + 2 * (dm_ceil_div(127, a.HW) + 1);
       const int slots = (rmax128 * (a.W + 2) <= 256 ? 3 : 2) * dm_num_cus();
+      // A 128-pixel tile whose plane no build can stage (more than 4 x 256 positions: 1 x 1 maps, a tile of 128 images)
+      // while the 32-pixel tile's fits: the whole launch takes the 128 x 32 build, whatever its size -- the answer must
+      // not depend on NB.  (Maps wider than 168 fit neither: launch_conv refuses them.)
+      if (rmax128 * (a.W + 2) > 4 * 256) return launch_conv<3, 4, 1, 1, 1, 8>(a, st);
       const int full_rounds = (MT * NTiles) / slots;
       const int rem = MT * NTiles - full_rounds * slots;
       // Launches that do not fill the chip: up to one 128 x 128 tile per CU costs a lone workgroup's

@@ -871,6 +871,37 @@ def conv2d(srcs, w_packed, bias, cout, ksize, relu=False, out=None, out_ch_offse
     return out
 
 
+CONV_PLAN_FIELDS = ('KS', 'WGM', 'WGN', 'WM', 'WN', 'CK', 'TAIL', 'PREC', 'POST', 'MAXPOS', 'ksplit', 'kchunks', 'q_begin', 'Q',
+                    'grid_x', 'grid_y', 'nontemporal')
+
+
+def conv2d_plan_raw(src_channels, NB, H, W, cout, ksize, flags=0, out_ch_total=None, out_ch_offset=0, workspace_floats=0,
+                    has_mask=False, has_addend=False, src_batch_strides=None):
+    """dm_conv2d_plan: (return code, records).  The code is the number of launches or the (negative) error the call with
+    these arguments would return; ``flags`` are dm_conv2d_fwd's.  Host only: no tensor, no device."""
+    consts = _abi.load()[1]
+    n, cap = consts['DM_CONV_PLAN_INTS'], consts['DM_CONV_PLAN_MAX_LAUNCHES']
+    assert len(CONV_PLAN_FIELDS) == n
+    rec = (ctypes.c_int * (n * cap))(*([-1] * (n * cap)))
+    strides = None if src_batch_strides is None else (ctypes.c_longlong * len(src_batch_strides))(*[int(v) for v in src_batch_strides])
+    rc = lib().dm_conv2d_plan(_int_array(src_channels), strides, len(src_channels), int(NB), int(H), int(W), int(cout), int(ksize),
+                              int(flags), int(cout if out_ch_total is None else out_ch_total), int(out_ch_offset),
+                              int(workspace_floats), 1 if has_mask else 0, 1 if has_addend else 0, rec, cap)
+    return rc, [dict(zip(CONV_PLAN_FIELDS, rec[i * n:(i + 1) * n])) for i in range(max(rc, 0))]
+
+
+def conv2d_plan(src_channels, NB, H, W, cout, ksize, relu=False, accumulate=False, overlapped=False, bf16x3=False, **kw):
+    """The launches ``conv2d`` would make for this shape, as the launcher reports them (include/dynamask_hip.h,
+    dm_conv2d_plan): a list of one or two dicts with the keys CONV_PLAN_FIELDS (two: a 3x3 launch whose underfull last
+    round goes to a second launch).  Raises where the call would fail.  ``workspace_floats`` > 0: the dm_conv2d_fwd_ws
+    call; ``has_mask`` / ``has_addend``: the masked / post-add calls."""
+    flags = (1 if relu else 0) | (2 if accumulate else 0) | (8 if overlapped else 0) | (16 if bf16x3 else 0)
+    rc, recs = conv2d_plan_raw(src_channels, NB, H, W, cout, ksize, flags, **kw)
+    if rc < 0:
+        check(rc, 'dm_conv2d_plan')
+    return recs
+
+
 def conv1x1_group(xs, w_packeds, biases, couts, relu=False, outs=None):
     """Up to three independent single-source 1x1 convolutions (+ bias, + ReLU) as ONE launch (dm_conv1x1_group_fwd): the
     FPN-wide semantic convolutions of the SFM stages.  Same bits as ``conv2d`` per problem.  The weights are all of one

@@ -60,7 +60,8 @@ const char* dm_error_string(int code);
  * input and mask scores (section K23); PointRefine's descending point selection, point-feature gather, point MLP and
  * multi-row scatter (section K24); Cascade Mask R-CNN's stage-grouped convolutions / deconvolutions and stage step
  * (section K25); Hybrid Task Cascade's resize, post-activation addend and RoIAlign-add (section K26); Grid R-CNN's
- * GroupNorm, neighbour fusion, grouped 4x4 stride-2 deconvolution and box vote (section K27). */
+ * GroupNorm, neighbour fusion, grouped 4x4 stride-2 deconvolution and box vote (section K27); the convolution launcher's
+ * own report of its launches, dm_conv2d_plan (section K5/K6). */
 #define DM_ABI_VERSION 28 /* the one definition: dm_abi_version(), dm_build_info() and _lib.ABI_VERSION read it */
 int dm_abi_version(void);
 /* "libdynamask_hip abi=N arch=gfx950 compiler=<clang version> flags=<the product-wide flags of dynamask_amd/build.py>"
@@ -172,7 +173,14 @@ int dm_conv_pack_weight_bf16x3(const float* w_oihw, int Cout, int Cin, int ksize
  *            (error at fp32 level, not the exact fp32 chain; the same bits every
  *            run); 3x3 launches whose staged plane exceeds 256 positions (maps
  *            wider than ~16 pixels) return DM_ERR_UNSUPPORTED under it;
- *            any other bit: DM_ERR_INVALID_ARG
+ *            any other bit (bit 2 included: it is the launcher's own
+ *            store-policy bit, never the caller's): DM_ERR_INVALID_ARG
+ * 3x3 maps : every exact build stages the input plane of a pixel tile in LDS, at
+ *            most 1024 positions: maps wider than 168 pixels return
+ *            DM_ERR_UNSUPPORTED whatever Cout and NB.  A 1 x 1 map overflows the
+ *            plane of the 128-pixel tiles (128 images of 3 x 3 padded positions):
+ *            Cout <= 64 returns DM_ERR_UNSUPPORTED; Cout > 64 runs the 128-cout x
+ *            32-pixel build for every NB (the answer does not depend on NB).
  * out      : written at channels [out_ch_offset, out_ch_offset+Cout) of a
  *            tensor [NB, out_ch_total, H, W]
  * ------------------------------------------------------------------------- */
@@ -191,6 +199,28 @@ int dm_conv2d_fwd_ws(const float* const* srcs, const int* src_channels, const lo
                      int num_srcs, int NB, int H, int W, const float* w_packed, const float* bias, int Cout, int ksize,
                      int relu, float* out, int out_ch_total, int out_ch_offset, float* workspace,
                      long long workspace_floats, dm_stream_t stream);
+
+/* (added to ABI 28) The launches dm_conv2d_fwd / dm_conv2d_fwd_ws / dm_conv2d_fwd_masked / dm_conv2d_post_add_fwd would
+ * make for these HOST arguments, reported by the launcher itself (the same code runs with a recorder instead of launching:
+ * nothing is launched, no device is needed -- without one the compute-unit count is taken as 256).  Arguments as
+ * dm_conv2d_fwd_ws's, without the pointers: workspace_floats = 0 for the entry points without a workspace; has_mask /
+ * has_addend != 0: the _masked / _post_add call (neither takes a workspace: DM_ERR_INVALID_ARG with one).  The
+ * DM_CONV_TAIL / DM_CONV1_SMALL_WGS knobs apply as they do to launches (read once per process).
+ * records: HOST array of max_records (>= DM_CONV_PLAN_MAX_LAUNCHES) x DM_CONV_PLAN_INTS ints.  Returns the number of
+ * launches (0: NB = 0; 1; 2: a 3x3 launch that sends its underfull last round of workgroups to a second launch) or the
+ * error code the call would return, and then writes nothing.  Record l, ints [l * DM_CONV_PLAN_INTS ..):
+ *   0 KS, 1 WGM, 2 WGN, 3 WM, 4 WN, 5 CK, 6 TAIL, 7 PREC, 8 POST: the build (a workgroup is WGM x WGN waves of WM x WN
+ *     32 x 32 blocks: 32 WGM WM couts (+ TAIL) x 32 WGN WN pixels, CK-channel chunks; PREC 1 = bf16x3, POST 1 = addend);
+ *   9 MAXPOS: staged plane positions per thread (3x3; 1 for 1x1);
+ *   10 ksplit, 11 kchunks: K splits (1: none) and chunks per split (0 without a split);
+ *   12 q_begin, 13 Q: the flat pixels [q_begin, Q) of the batch this launch covers;
+ *   14 grid x (cout tiles x pixel tiles), 15 grid y (= ksplit);
+ *   16: 1 when the output is written with nontemporal stores. */
+#define DM_CONV_PLAN_INTS 17
+#define DM_CONV_PLAN_MAX_LAUNCHES 2
+int dm_conv2d_plan(const int* src_channels, const long long* src_batch_strides, int num_srcs, int NB, int H, int W, int Cout,
+                   int ksize, int relu, int out_ch_total, int out_ch_offset, long long workspace_floats, int has_mask,
+                   int has_addend, int* records, int max_records);
 
 /* (ABI 26) Up to three independent single-source 1x1 convolutions (+ bias, + ReLU) as ONE launch -- the FPN-wide
  * semantic_transform_in convolutions of the three SFM stages (mmdet/models/roi_heads/mask_heads/dynamask_head.py:104,
@@ -506,8 +536,9 @@ int dm_paste_rle_multi(const float* masks, const float* boxes, int N, int mask_h
 /* K22  fully connected layer out[N, M] = x[N, K] . w[M, K]^T + bias (nn.Linear layouts), optional
  * ReLU; fp32 MFMA.  replaces: the nn.Linear stack of Shared2FCBBoxHead
  * (roi_heads/bbox_heads/convfc_bbox_head.py:101-108,143-186) and MaskPre's fc1 / fc2
- * (roi_heads/base_roi_head.py:17-18,24-26).  K % 4 == 0.  K is split over workgroups in segments
- * whose length depends on K alone; the partial sums go to `scratch` (dm_fc_scratch_floats() floats; may be NULL when that
+ * (roi_heads/base_roi_head.py:17-18,24-26).  K % 4 == 0 (else DM_ERR_UNSUPPORTED).  K is split over workgroups in segments
+ * whose length depends on K alone (256 elements up to K = 4096, 1024 above; dm_fc_scratch_floats = segments x N x M, 0
+ * for a single segment); the partial sums go to `scratch` (dm_fc_scratch_floats() floats; may be NULL when that
  * is 0) and are added in a fixed order: an output row has the same bits whatever N is, run to run. */
 long long dm_fc_scratch_floats(int N, int K, int M);
 int dm_fc_fwd(const float* x, const float* w, const float* bias, int N, int K, int M, int relu, float* out,
