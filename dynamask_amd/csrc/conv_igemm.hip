@@ -76,7 +76,8 @@ struct ConvArgs {
 // convs of the DCN layers then cost 32 + 4 rows of MFMA work instead of 64.
 // The 3x3 128 x 128 build with one plane position per thread is held to 168 VGPRs (5 dwords of
 // scratch): three workgroups per CU instead of two hide each other's barriers better
-// (14 x 14, 3 full rounds: 0.916 -> 0.876 ms; 752 RoIs: 135 TFLOP/s).  The 1x1 builds with 32-channel
+// (14 x 14, 3 full rounds: 0.916 -> 0.876 ms; 752 RoIs: 135 TFLOP/s; 150 VGPRs and no scratch since its weight fragments
+// come from the packed tensor: conv_direct_a below).  The 1x1 builds with 32-channel
 // chunks spill 35-55 dwords at 168 and lose a third of their rate; with 16-channel chunks (half the
 // prefetch registers) they fit without scratch, and three per CU beats the longer chunk: the DCN
 // column-gradient GEMMs 1.56 -> 1.20, 0.94 -> 0.78, 0.75 -> 0.67 ms, fusion 130->64 @56^2 0.56 -> 0.45 ms.
@@ -132,6 +133,27 @@ __device__ __forceinline__ void dm_split8x3(const dm_f32x4& q0, const dm_f32x4& 
   for (int p = 0; p < 3; ++p) out[p] = __builtin_bit_cast(dm_f32x4, w[p]);
 }
 
+// Builds that read their weight (A) fragments straight from the packed tensor: the exact fp32 128 x 128 builds (four waves
+// of 2 x 2 MFMA blocks, no tail rows) of the 3x3 kernel at every MAXPOS and of the 1x1 kernel with 16-channel chunks, POST
+// twin and grouped launches included.  A wave's fragment of a step is one 16-byte load per lane and 32-row block from
+// [tap][quad][cout][4] -- 512 contiguous bytes per half-wave, L2 hits: every workgroup of a launch walks the same weights --
+// into the registers the MFMAs read, one step ahead.  Such a build has no A image in LDS (ldsB starts at 0) and none of its
+// traffic: per wave and 8-channel chunk of the 3x3 build 9 global loads, 9 ds_write_b128 and 18 ds_read_b128 become 18
+// buffer loads.  A compile-time property of the build: the launchers size the LDS with it, nothing else knows it.
+// DM_CONV_DIRECT_A (bit 0: the 3x3 builds, bit 1: the 1x1 builds) says which of them take the path.  The 1x1 builds are
+// OFF: measured against the LDS image (profiles/conv_direct_weights.txt) the fusion GEMM 514 -> 256 @14 lost 6 % in
+// every pass (0.286 / 0.293 -> 0.303 / 0.310 ms) -- with two steps per chunk, the wait for step 1's fragment is also a wait
+// for the staging loads issued behind it (loads return in order), a chunk earlier than commit() needs them.  The 3x3
+// builds gained in every pass (conv 256 -> 256 @14: 1.041 / 1.056 -> 1.011 / 1.029 ms).  -DDM_CONV_DIRECT_A=n: A/B libraries.
+#ifndef DM_CONV_DIRECT_A
+#define DM_CONV_DIRECT_A 1
+#endif
+template <int KS, int WGM, int WGN, int WM, int WN, int CK, int TAIL, int PREC>
+constexpr bool conv_direct_a() {
+  return PREC == 0 && TAIL == 0 && WGM == 2 && WGN == 2 && WM == 2 && WN == 2 &&
+         ((KS == 3 && CK == 8 && (DM_CONV_DIRECT_A & 1)) || (KS == 1 && CK == 16 && (DM_CONV_DIRECT_A & 2)));
+}
+
 // POST (K26, dm_conv2d_post_add_fwd): the epilogue stores addend + act(conv + bias) -- the addend joins after the
 // activation, where the accumulate flag adds before it; everything in front of the store is the POST = 0 build's.
 template <int KS, int WGM, int WGN, int WM, int WN, int CK, int MAXPOS, int TAIL = 0, int PREC = 0, int POST = 0>
@@ -147,8 +169,10 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
   constexpr int TAPS = KS * KS;
   constexpr int NQ = CK / 4;                      // channel quads per chunk (what a thread prefetches of a pixel)
   constexpr int NWC = PREC ? 6 : NQ;              // 16-byte words per chunk and (cout | pixel) in LDS and in the packed weights
-  constexpr int A_F4 = TAPS * NWC * TMA;          // float4 slots of the A chunk
+  constexpr bool DIRECT = conv_direct_a<KS, WGM, WGN, WM, WN, CK, TAIL, PREC>();      // A fragments from the packed tensor
+  constexpr int A_F4 = DIRECT ? 0 : TAPS * NWC * TMA;      // float4 slots of the A chunk in LDS
   constexpr int A_PER_T = (A_F4 + NT - 1) / NT;
+  constexpr int AREG = A_PER_T ? A_PER_T : 1;
   constexpr int B1_PER_T = (NQ * TN + NT - 1) / NT;   // 1x1: float4 slots per thread
   constexpr int BREG = (KS == 3) ? MAXPOS * NQ : B1_PER_T;
 
@@ -307,9 +331,9 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
     }
   };
 
-  dm_f32x4 ra[A_PER_T];
+  dm_f32x4 ra[AREG];
   dm_f32x4 rb[BREG];
-  unsigned a_off[A_PER_T];          // float offset of A slot i inside a chunk's weights (fixed per thread)
+  unsigned a_off[AREG];          // float offset of A slot i inside a chunk's weights (fixed per thread)
 #pragma unroll
   for (int i = 0; i < A_PER_T; ++i) {
     const int idx = tid + i * NT;
@@ -321,6 +345,25 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
   int b_src = -1;
   unsigned b_off32 = 0;             // 1x1 fast path: the same offset in 32 bits
   const float* b_srcp = nullptr;    // 1x1 fast path: base of the current source
+
+  // DIRECT: the A fragment of step (tap, quad pair g) of the chunk whose first quad is cq -- lanes 0-31 quad 2 g, lanes 32-63
+  // quad 2 g + 1 of cout rows (wave_m WM + i) 32 + l31, the lane layout of the LDS image.  Through a buffer descriptor: the
+  // lane's part of the address is one 32-bit register fixed for the whole K loop (rows past CoutP: the last row again, never
+  // stored), the chunk / tap / quad-pair part is scalar.  (Flat 64-bit addresses keep a register pair per tap alive through
+  // the loop: deform_conv_c256_kernel.)  The descriptor ends with the packed tensor (the launcher keeps it below 2 GB).
+  constexpr int NGD = NQ / 2;                       // quad pairs per chunk = MFMA steps per tap
+  const __amdgpu_buffer_rsrc_t wsrc =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.wq), 0, DIRECT ? TAPS * a.KQ * a.CoutP * 16 : 0, 0x00020000);
+  const int a_quad = a.CoutP * 16, a_tap = a.KQ * a_quad;      // bytes per channel quad / per tap of the packed weights
+  unsigned a_lane[WM];                              // bytes
+#pragma unroll
+  for (int i = 0; i < WM; ++i) a_lane[i] = 16u * (unsigned)(hi * a.CoutP + min(m0 + (wave_m * WM + i) * 32 + l31, a.CoutP - 1));
+  auto load_a = [&](int cq, int st, dm_f32x4* av) {
+    const int tap = st / NGD, g = st - tap * NGD;
+    const int so = tap * a_tap + (cq + 2 * g) * a_quad;
+#pragma unroll
+    for (int i = 0; i < WM; ++i) av[i] = __builtin_bit_cast(dm_f32x4, __builtin_amdgcn_raw_buffer_load_b128(wsrc, a_lane[i], so, 0));
+  };
 
   // issue the global loads of the chunk at (cs, cc0, ckq) into registers
   auto prefetch = [&]() {
@@ -471,14 +514,31 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
   };
 
   for (; k_skip > 0 && cs < a.num_srcs; --k_skip) chunk_advance();      // (split-K: this split's first chunk)
-  if (chunk_valid()) prefetch();
+  // DIRECT: which fragment loads are issued.  A load is issued only for a step whose MFMAs run: a chunk that exists in this
+  // launch's (this split's) K range -- every load of a chunk sits behind the chunk_valid() that admits the chunk -- and in
+  // it a quad pair with live channels, the `live` test of the MFMAs themselves.  A skipped quad pair (a 1x1 chunk of at most
+  // 8 channels: the end of a source) is not in the packed tensor at all -- its address is the next source's first quad pair,
+  // or past the tensor at the last source.  Inside a live quad pair, channels past the source's end (a source of 3 or 12
+  // channels) are the zero rows dm_conv_pack_weight writes up to the next multiple of 8; their B values are staged as zeros.
+  dm_f32x4 avn[DIRECT ? WM : 1];      // DIRECT: step 0's A fragment of the next chunk, loaded under the current chunk's last step
+  if (chunk_valid()) {
+    prefetch();
+    if (DIRECT) load_a(ckq, 0, avn);
+  }
   while (chunk_valid()) {
     const int ckv_cur = min(CK, curC - cc0);
     const int ngroups = (ckv_cur + 7) / 8;   // quad pairs holding live channels
+    const int ckq_cur = ckq;                 // DIRECT: the chunk the MFMAs below multiply (ckq moves on to the next one)
     commit();
     __syncthreads();
     chunk_advance();
     --k_left;
+    dm_f32x4 av[2][WM + (TAIL ? 1 : 0)], bv[2][WN];      // the exact builds' operand fragments
+    if (DIRECT && !PREC) {
+      // step 1's fragment in front of the next chunk's staging loads: loads return in order, and so its wait does not
+      // include theirs (step 0's is in avn)
+      if (TAPS * NGD > 1 && (NGD == 1 || 1 < ngroups)) load_a(ckq_cur, 1, av[1]);
+    }
     if (chunk_valid()) prefetch();
 
     // ---- MFMA over the committed chunk ---------------------------------------
@@ -529,12 +589,12 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
         const int tap = st / NG, g = st - tap * NG;
         const int tapoff = (KS == 3) ? ((tap / 3) * Wp + (tap % 3)) : 0;
 #pragma unroll
-        for (int i = 0; i < WM; ++i) av[i] = ldsA[(tap * NQ + 2 * g + hi) * TMA + (wave_m * WM + i) * 32 + l31];
+        for (int i = 0; i < WM; ++i)
+          if (!DIRECT) av[i] = ldsA[(tap * NQ + 2 * g + hi) * TMA + (wave_m * WM + i) * 32 + l31];
         if (TAIL) av[WM] = ldsA[(tap * NQ + 2 * g + hi) * TMA + TM + (lane & 3)];
 #pragma unroll
         for (int j = 0; j < WN; ++j) bv[j] = ldsB[(2 * g) * plane + lane_base[j] + tapoff];
       };
-      dm_f32x4 av[2][WM + (TAIL ? 1 : 0)], bv[2][WN];
       load_frag(0, av[0], bv[0]);
 #pragma unroll
       for (int st = 0; st < STEPS; ++st) {
@@ -542,6 +602,11 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
         // quad pairs beyond the chunk's live channels hold zeros (1x1, ragged sources): skip them
         const bool live = (NG == 1) || ((st % NG) < ngroups);
         if (st + 1 < STEPS) load_frag(st + 1, av[cur ^ 1], bv[cur ^ 1]);
+        if (DIRECT) {
+          // one step ahead (step 1: above); under the last step, step 0 of the next chunk -- (cs, ckq) are the next chunk's
+          if (st >= 1 && st + 1 < STEPS && (NG == 1 || ((st + 1) % NG) < ngroups)) load_a(ckq_cur, st + 1, av[cur ^ 1]);
+          if (st + 1 == STEPS && chunk_valid()) load_a(ckq, 0, avn);      // (step 0 read avn, not av[0]: STEPS > 1)
+        }
         if (live) {
           // (s_setprio 1 around this cluster: +4 % in tools/micro/mfma_mix.hip, -3.5 % on the headline -- with three workgroups
           // per CU the prioritised waves starve the ones staging the next chunk)
@@ -551,7 +616,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
             for (int i = 0; i < WM; ++i)
 #pragma unroll
               for (int j = 0; j < WN; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[cur][i][e], bv[cur][j][e], acc[i][j], 0, 0, 0);
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32((DIRECT && st == 0 ? avn : av[cur])[i][e], bv[cur][j][e], acc[i][j], 0, 0, 0);
           if (TAIL) {
 #pragma unroll
             for (int e = 0; e < 4; ++e)
@@ -959,7 +1024,10 @@ int launch_conv_mp(ConvArgs& a, hipStream_t st) {
   constexpr int NT = WGM * WGN * 64;
   const int NTiles = dm_ceil_div(a.Q - a.q_begin, TN);
   constexpr int NWC = PREC ? 6 : CK / 4;
-  const size_t lds_bytes = 16 * ((size_t)KS * KS * NWC * (TM + TAIL) + (size_t)NWC * a.plane);
+  constexpr bool DIRECT = conv_direct_a<KS, WGM, WGN, WM, WN, CK, TAIL, PREC>();      // no A image: the B planes only
+  const size_t lds_bytes = 16 * ((DIRECT ? 0 : (size_t)KS * KS * NWC * (TM + TAIL)) + (size_t)NWC * a.plane);
+  // (the fragment loads address the packed weights through a buffer descriptor with 32-bit byte offsets)
+  if (DIRECT && (long long)KS * KS * a.KQ * a.CoutP * 16 > 0x7fffffffLL) return DM_ERR_UNSUPPORTED;
   if (lds_bytes > 64 * 1024) {
     // (the bf16x3 3x3 build: 54 KB of A image + 21 KB of plane at 14 x 14; two workgroups per CU.  The exact 128-cout 3x3
     // builds whose plane holds more than 896 positions -- 36 KB of A image + 32 bytes per position: maps 148 .. 168 wide,
@@ -1063,7 +1131,9 @@ int launch_group_mp(ConvGroup& g, int count, int S, float* ws, hipStream_t st) {
   constexpr int TN = WGN * WN * 32;
   constexpr int TM = WGM * WM * 32;
   const ConvArgs& a0 = g.a[0];
-  const size_t lds_bytes = 16 * ((size_t)KS * KS * (CK / 4) * TM + (size_t)(CK / 4) * a0.plane);
+  constexpr bool DIRECT = conv_direct_a<KS, WGM, WGN, WM, WN, CK, 0, 0>();      // (as in launch_conv_mp)
+  const size_t lds_bytes = 16 * ((DIRECT ? 0 : (size_t)KS * KS * (CK / 4) * TM) + (size_t)(CK / 4) * a0.plane);
+  if (DIRECT && (long long)KS * KS * a0.KQ * a0.CoutP * 16 > 0x7fffffffLL) return DM_ERR_UNSUPPORTED;
   if (lds_bytes > 64 * 1024) return DM_ERR_UNSUPPORTED;
   int chunks = dm_ceil_div(a0.src_c[0], CK);
   const long long per = (long long)a0.NB * a0.Cout * a0.HW;

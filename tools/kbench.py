@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Per-kernel timings at the benchmark shapes (512 RoIs, 1333x800 FPN): one
-process, event-timed, prints a table with achieved TFLOP/s or GB/s."""
+process, event-timed, prints a table with achieved TFLOP/s or GB/s.
+KB_ONLY=a,b: only the convolution / DCN rows whose name contains one of the strings (A/B runs of one kernel)."""
 import os
 import sys
 
@@ -28,8 +29,12 @@ def main():
     N = int(os.environ.get('KB_N', 512))
     dev = torch.device('cuda')
     rows = []
+    only = [s for s in os.environ.get('KB_ONLY', '').split(',') if s]
+    sel = lambda name: not only or any(s in name for s in only)
 
     def conv(name, srcs_c, cout, S, ks, nb=N, hw=None):
+        if not sel(name):
+            return
         H, W = (S, S) if hw is None else hw
         xs = [torch.randn(nb, c, H, W, device=dev) for c in srcs_c]
         cin = sum(srcs_c)
@@ -58,6 +63,8 @@ def main():
     conv('sem1x1 256->64 P2', [256], 64, 0, 1, nb=1, hw=(200, 336))
 
     def dcn(name, C, S):
+        if not sel(name):
+            return
         x = torch.randn(N, C, S, S, device=dev)
         off = torch.randn(N, 36, S, S, device=dev)
         w = torch.randn(C, C, 3, 3, device=dev) / (9 * C) ** 0.5
@@ -69,6 +76,8 @@ def main():
     dcn('dcn 128 @28', 128, 28)
     dcn('dcn 64 @56', 64, 56)
 
+    if only:
+        return show(rows)
     feats = [f.to(dev) for f in synth.make_fpn(1, 800, 1333, 256, seed=0)]
     rois = synth.make_rois(1, N, 800, 1333, seed=1).to(dev)
     ms = t(lambda: ops.roi_align(feats[:4], rois, 14, [1 / 4, 1 / 8, 1 / 16, 1 / 32]))
@@ -115,6 +124,10 @@ def main():
         wgrad('wgrad1x1 128->128 @28', 128, 128, 28, 1)
         wgrad('wgrad1x1 64->64 @56', 64, 64, 56, 1)
         wgrad('wgrad1x1 64->30 @56', 64, 30, 56, 1)
+    show(rows)
+
+
+def show(rows):
     print(f'{"kernel":32s} {"ms":>9s} {"rate":>10s}')
     for name, ms, rate, unit in rows:
         print(f'{name:32s} {ms:9.3f} {rate:10.1f} {unit}')
