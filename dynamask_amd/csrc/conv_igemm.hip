@@ -26,6 +26,9 @@
 // the 128x128 tile): the NEXT chunk's global loads are issued into registers
 // before the MFMAs of the current chunk and written to LDS after them
 // (issue-early / write-late), so L2 latency hides under 144 MFMAs per wave.
+// The builds without an A image (conv_direct_a) have a K loop of their own:
+// a ring of weight-fragment sets that runs on through the chunks, and the next
+// chunk's staging loads dealt over the current chunk's steps, unpredicated.
 #include <type_traits>
 
 #include "common.h"
@@ -136,15 +139,16 @@ __device__ __forceinline__ void dm_split8x3(const dm_f32x4& q0, const dm_f32x4& 
 // Builds that read their weight (A) fragments straight from the packed tensor: the exact fp32 128 x 128 builds (four waves
 // of 2 x 2 MFMA blocks, no tail rows) of the 3x3 kernel at every MAXPOS and of the 1x1 kernel with 16-channel chunks, POST
 // twin and grouped launches included.  A wave's fragment of a step is one 16-byte load per lane and 32-row block from
-// [tap][quad][cout][4] -- 512 contiguous bytes per half-wave, L2 hits: every workgroup of a launch walks the same weights --
-// into the registers the MFMAs read, one step ahead.  Such a build has no A image in LDS (ldsB starts at 0) and none of its
-// traffic: per wave and 8-channel chunk of the 3x3 build 9 global loads, 9 ds_write_b128 and 18 ds_read_b128 become 18
-// buffer loads.  A compile-time property of the build: the launchers size the LDS with it, nothing else knows it.
-// DM_CONV_DIRECT_A (bit 0: the 3x3 builds, bit 1: the 1x1 builds) says which of them take the path.  The 1x1 builds are
-// OFF: measured against the LDS image (profiles/conv_direct_weights.txt) the fusion GEMM 514 -> 256 @14 lost 6 % in
-// every pass (0.286 / 0.293 -> 0.303 / 0.310 ms) -- with two steps per chunk, the wait for step 1's fragment is also a wait
-// for the staging loads issued behind it (loads return in order), a chunk earlier than commit() needs them.  The 3x3
-// builds gained in every pass (conv 256 -> 256 @14: 1.041 / 1.056 -> 1.011 / 1.029 ms).  -DDM_CONV_DIRECT_A=n: A/B libraries.
+// [tap][quad][cout][4] -- 512 contiguous bytes per half-wave, L2 hits: every workgroup of a launch walks the same weights
+// -- into the registers the MFMAs read, two steps ahead (the ring of the K loop below).  Such a build has no A image in LDS
+// (ldsB starts at 0) and none of its traffic: per wave and 8-channel chunk of the 3x3 build 9 global loads, 9 ds_write_b128
+// and 18 ds_read_b128 become 18 buffer loads.  A compile-time property of the build: the launchers size the LDS with it,
+// nothing else knows it. DM_CONV_DIRECT_A (bit 0: the 3x3 builds, bit 1: the 1x1 builds) says which of them take the path.
+// The 1x1 builds are OFF: measured against the LDS image (profiles/conv_direct_weights.txt) the fusion GEMM 514 -> 256 @14
+// lost 6 % in every pass (0.286 / 0.293 -> 0.303 / 0.310 ms), and with the ring loop below it still loses 4 % (0.290 /
+// 0.286 / 0.286 -> 0.301 / 0.295 / 0.298 ms, profiles/conv_fragment_ring.txt): with two steps per chunk the next chunk's
+// staging loads have to land inside the chunk they are issued in, whatever the waits count.  The 3x3 builds gained in every
+// pass (conv 256 -> 256 @14: 1.041 / 1.056 -> 1.011 / 1.029 ms).  -DDM_CONV_DIRECT_A=n: A/B libraries.
 #ifndef DM_CONV_DIRECT_A
 #define DM_CONV_DIRECT_A 1
 #endif
@@ -358,8 +362,10 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
   unsigned a_lane[WM];                              // bytes
 #pragma unroll
   for (int i = 0; i < WM; ++i) a_lane[i] = 16u * (unsigned)(hi * a.CoutP + min(m0 + (wave_m * WM + i) * 32 + l31, a.CoutP - 1));
-  auto load_a = [&](int cq, int st, dm_f32x4* av) {
-    const int tap = st / NGD, g = st - tap * NGD;
+  // ng: the chunk's quad pairs with live channels.  A dead quad pair (a 1x1 chunk of at most 8 channels) is not in the
+  // packed tensor at all: its step loads the chunk's last live pair again, and no MFMA reads it.
+  auto load_a = [&](int cq, int ng, int st, dm_f32x4* av) {
+    const int tap = st / NGD, g = min(st - tap * NGD, ng - 1);
     const int so = tap * a_tap + (cq + 2 * g) * a_quad;
 #pragma unroll
     for (int i = 0; i < WM; ++i) av[i] = __builtin_bit_cast(dm_f32x4, __builtin_amdgcn_raw_buffer_load_b128(wsrc, a_lane[i], so, 0));
@@ -465,7 +471,25 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
     }
   };
 
+  // DIRECT: the chunk whose B values are in flight to rb (the staging cursor): its first channel in its source and its live
+  // channels.  The staging loads of these builds are never predicated: a padding position reads pixel 0 of image 0, a channel
+  // past the source the source's last one, and commit() SELECTS the zero (a select, not a product: the value read may be Inf).
+  const float* st_base = nullptr;
+  int st_ckv = CK;
+  const int st_qw = (KS == 1 && TN % 64 == 0) ? __builtin_amdgcn_readfirstlane(tid / TN) : tid / TN;      // 1x1: the thread's first quad
+  auto st_channel = [&](int i, int e) {      // channel inside the chunk of element e of rb[i]
+    return ((KS == 3 ? i % NQ : st_qw + i * (NT / TN)) * 4 + e);
+  };
+
   auto commit = [&]() {   // registers -> LDS
+    if constexpr (DIRECT) {
+#pragma unroll
+      for (int i = 0; i < BREG; ++i) {
+        const int lim = st_n[KS == 3 ? i / NQ : 0] >= 0 ? st_ckv : 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) rb[i][e] = st_channel(i, e) < lim ? rb[i][e] : 0.f;
+      }
+    }
 #pragma unroll
     for (int i = 0; i < A_PER_T; ++i) {
       const int idx = tid + i * NT;
@@ -514,99 +538,74 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
   };
 
   for (; k_skip > 0 && cs < a.num_srcs; --k_skip) chunk_advance();      // (split-K: this split's first chunk)
-  // DIRECT: which fragment loads are issued.  A load is issued only for a step whose MFMAs run: a chunk that exists in this
-  // launch's (this split's) K range -- every load of a chunk sits behind the chunk_valid() that admits the chunk -- and in
-  // it a quad pair with live channels, the `live` test of the MFMAs themselves.  A skipped quad pair (a 1x1 chunk of at most
-  // 8 channels: the end of a source) is not in the packed tensor at all -- its address is the next source's first quad pair,
-  // or past the tensor at the last source.  Inside a live quad pair, channels past the source's end (a source of 3 or 12
-  // channels) are the zero rows dm_conv_pack_weight writes up to the next multiple of 8; their B values are staged as zeros.
-  dm_f32x4 avn[DIRECT ? WM : 1];      // DIRECT: step 0's A fragment of the next chunk, loaded under the current chunk's last step
-  if (chunk_valid()) {
-    prefetch();
-    if (DIRECT) load_a(ckq, 0, avn);
-  }
-  while (chunk_valid()) {
-    const int ckv_cur = min(CK, curC - cc0);
-    const int ngroups = (ckv_cur + 7) / 8;   // quad pairs holding live channels
-    const int ckq_cur = ckq;                 // DIRECT: the chunk the MFMAs below multiply (ckq moves on to the next one)
-    commit();
-    __syncthreads();
-    chunk_advance();
-    --k_left;
-    dm_f32x4 av[2][WM + (TAIL ? 1 : 0)], bv[2][WN];      // the exact builds' operand fragments
-    if (DIRECT && !PREC) {
-      // step 1's fragment in front of the next chunk's staging loads: loads return in order, and so its wait does not
-      // include theirs (step 0's is in avn)
-      if (TAPS * NGD > 1 && (NGD == 1 || 1 < ngroups)) load_a(ckq_cur, 1, av[1]);
-    }
-    if (chunk_valid()) prefetch();
-
-    // ---- MFMA over the committed chunk ---------------------------------------
-    // Operand fragments are double-buffered in registers: the ds_reads of step s+1 are
-    // issued before the 4 x WM x WN MFMAs of step s, so LDS latency never stalls the
-    // matrix pipe (the compiler alone re-uses one register set and issues them late).
-    if (PREC) {
-      // one step per tap: the chunk's 16 channels are ONE k of v_mfma_f32_32x32x16_bf16 (lane half hi = channels 8 hi ..)
-      auto load_frag = [&](int tap, dm_f32x4 (*av)[3], dm_f32x4 (*bv)[3]) {
-        const int tapoff = (KS == 3) ? ((tap / 3) * Wp + (tap % 3)) : 0;
+  if constexpr (DIRECT) {
+    // ---- the K loop of the builds without an A image --------------------------------------------------------------------
+    // One stream of steps runs on through the chunks (STEPS per chunk; a dead quad pair of a ragged 1x1 chunk keeps its
+    // place in the stream, its MFMAs are skipped).  Issued under step s: the ds_reads of step s + 1's B fragments, the A
+    // fragment load of step s + D into the ring's free set, the next chunk's staging loads of this step (LPS dwords of the
+    // chunk's NLD) -- one by one between the step's MFMAs on the ring's oldest set.  Loads return in order, so the wait in
+    // front of step s's MFMAs is for a fragment with the younger fragment loads and staging loads behind it, which stay in
+    // flight -- and the compiler can count them: nothing in the loop is predicated.  (Steps 2 .. 8 of a chunk, in the ISA;
+    // step 0's wait is vmcnt(2) behind step 2's fragment load, which lands step 1's fragment a step early, and step 1 has
+    // none.)  Where there is no next chunk the cursors stay on the current one (its values are loaded once more and
+    // dropped), so the last chunk is not a special case. Split-K starts the stream at its first chunk; a source change only
+    // moves the cursors. (Measured and not kept, profiles/conv_fragment_ring.txt: a ring one set deeper, the staging loads
+    // under the first four steps only, and a step's memory instructions all in front of its MFMAs -- 5 % slower than the
+    // loop this one replaced.)
+    constexpr int STEPS = TAPS * NGD;
+    constexpr int D = 2;                                  // ring depth: the 24 registers the loop had (1x1: one chunk ahead)
+    constexpr int NLD = BREG * 4;                         // staging dwords per thread and chunk
+    constexpr int LPS = (NLD + STEPS - 1) / STEPS;        // ... issued under a step
+    static_assert(D <= STEPS, "the fragment of step s + D is the current chunk's or the next one's");
+    dm_f32x4 aq[D + 1][WM];      // the ring, oldest first: aq[0] is the step the MFMAs run, aq[D] the set being loaded
+    auto stage_cursor = [&]() {      // the staging cursor moves to the chunk at (cs, cc0)
+      if (b_src != cs) {
+        const size_t bs = (size_t)a.src_bs[cs];
 #pragma unroll
-        for (int i = 0; i < WM; ++i)
-#pragma unroll
-          for (int p_ = 0; p_ < 3; ++p_) av[i][p_] = ldsA[(tap * NWC + 3 * hi + p_) * TMA + (wave_m * WM + i) * 32 + l31];
-#pragma unroll
-        for (int j = 0; j < WN; ++j)
-#pragma unroll
-          for (int p_ = 0; p_ < 3; ++p_) bv[j][p_] = ldsB[p_ * plane + lane_base[j] + tapoff];
-      };
-      auto mfma = [&](const dm_f32x4& x, const dm_f32x4& y, dm_f32x16& c) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(dm_bf16x8, x), __builtin_bit_cast(dm_bf16x8, y), c, 0, 0, 0);
-      };
-      dm_f32x4 av[2][WM][3], bv[2][WN][3];
-      load_frag(0, av[0], bv[0]);
-#pragma unroll
-      for (int st = 0; st < TAPS; ++st) {
-        const int cur = st & 1;
-        if (st + 1 < TAPS) load_frag(st + 1, av[cur ^ 1], bv[cur ^ 1]);
-#pragma unroll
-        for (int i = 0; i < WM; ++i)
-#pragma unroll
-          for (int j = 0; j < WN; ++j) {
-            // (A part, B part), smallest terms first: the same order in every launch, hence the same bits every run.  The
-            // five correction terms go to an accumulator of their own (~2^-8 of the main one: its roundings are that much
-            // smaller), added to hi*hi's once, before the epilogue.
-            mfma(av[cur][i][2], bv[cur][j][0], accx[i][j]);
-            mfma(av[cur][i][1], bv[cur][j][1], accx[i][j]);
-            mfma(av[cur][i][0], bv[cur][j][2], accx[i][j]);
-            mfma(av[cur][i][1], bv[cur][j][0], accx[i][j]);
-            mfma(av[cur][i][0], bv[cur][j][1], accx[i][j]);
-            mfma(av[cur][i][0], bv[cur][j][0], acc[i][j]);
-          }
+        for (int k = 0; k < NPOS; ++k) b_off[k] = (size_t)max(st_n[k], 0) * bs + st_pix[k];
+        b_src = cs;
       }
-    } else {
-      constexpr int NG = NQ / 2;
-      constexpr int STEPS = TAPS * NG;
-      auto load_frag = [&](int st, dm_f32x4* av, dm_f32x4* bv) {
-        const int tap = st / NG, g = st - tap * NG;
-        const int tapoff = (KS == 3) ? ((tap / 3) * Wp + (tap % 3)) : 0;
+      st_base = a.src[cs] + (size_t)cc0 * HW;
+      st_ckv = min(CK, curC - cc0);
+    };
+    auto stage = [&](int l) {      // staging dword l of the cursor's chunk
+      const int i = l / 4, e = l % 4;
+      rb[i][e] = st_base[(size_t)min(st_channel(i, e), st_ckv - 1) * HW + b_off[KS == 3 ? i / NQ : 0]];
+    };
+    auto load_b = [&](int st, dm_f32x4* bv) {
+      const int tap = st / NGD, g = st - tap * NGD;
+      const int tapoff = (KS == 3) ? ((tap / 3) * Wp + (tap % 3)) : 0;
 #pragma unroll
-        for (int i = 0; i < WM; ++i)
-          if (!DIRECT) av[i] = ldsA[(tap * NQ + 2 * g + hi) * TMA + (wave_m * WM + i) * 32 + l31];
-        if (TAIL) av[WM] = ldsA[(tap * NQ + 2 * g + hi) * TMA + TM + (lane & 3)];
+      for (int j = 0; j < WN; ++j) bv[j] = ldsB[(2 * g) * plane + lane_base[j] + tapoff];
+    };
+    if (chunk_valid()) {
+      stage_cursor();
 #pragma unroll
-        for (int j = 0; j < WN; ++j) bv[j] = ldsB[(2 * g) * plane + lane_base[j] + tapoff];
-      };
-      load_frag(0, av[0], bv[0]);
+      for (int l = 0; l < NLD; ++l) stage(l);
+#pragma unroll
+      for (int d = 0; d < D; ++d) load_a(ckq, (st_ckv + 7) / 8, d, aq[d]);
+    }
+    while (chunk_valid()) {
+      const int ngroups = (st_ckv + 7) / 8;   // quad pairs holding live channels
+      const int ckq_cur = ckq;
+      commit();
+      __syncthreads();
+      chunk_advance();
+      --k_left;
+      const bool more = chunk_valid();
+      if (more) stage_cursor();
+      const int ckq_nxt = more ? ckq : ckq_cur, ng_nxt = (st_ckv + 7) / 8;
+      dm_f32x4 bv[2][WN];
+      load_b(0, bv[0]);
 #pragma unroll
       for (int st = 0; st < STEPS; ++st) {
         const int cur = st & 1;
-        // quad pairs beyond the chunk's live channels hold zeros (1x1, ragged sources): skip them
-        const bool live = (NG == 1) || ((st % NG) < ngroups);
-        if (st + 1 < STEPS) load_frag(st + 1, av[cur ^ 1], bv[cur ^ 1]);
-        if (DIRECT) {
-          // one step ahead (step 1: above); under the last step, step 0 of the next chunk -- (cs, ckq) are the next chunk's
-          if (st >= 1 && st + 1 < STEPS && (NG == 1 || ((st + 1) % NG) < ngroups)) load_a(ckq_cur, st + 1, av[cur ^ 1]);
-          if (st + 1 == STEPS && chunk_valid()) load_a(ckq, 0, avn);      // (step 0 read avn, not av[0]: STEPS > 1)
-        }
+        const bool live = (NGD == 1) || ((st % NGD) < ngroups);
+        if (st + 1 < STEPS) load_b(st + 1, bv[cur ^ 1]);
+        if (st + D < STEPS) load_a(ckq_cur, ngroups, st + D, aq[D]);
+        else load_a(ckq_nxt, ng_nxt, st + D - STEPS, aq[D]);
+#pragma unroll
+        for (int l = st * LPS; l < (st + 1) * LPS && l < NLD; ++l) stage(l);
         if (live) {
           // (s_setprio 1 around this cluster: +4 % in tools/micro/mfma_mix.hip, -3.5 % on the headline -- with three workgroups
           // per CU the prioritised waves starve the ones staging the next chunk)
@@ -616,18 +615,131 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
             for (int i = 0; i < WM; ++i)
 #pragma unroll
               for (int j = 0; j < WN; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32((DIRECT && st == 0 ? avn : av[cur])[i][e], bv[cur][j][e], acc[i][j], 0, 0, 0);
-          if (TAIL) {
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(aq[0][i][e], bv[cur][j][e], acc[i][j], 0, 0, 0);
+        }
+#pragma unroll
+        for (int d = 0; d < D; ++d)
+#pragma unroll
+          for (int i = 0; i < WM; ++i) aq[d][i] = aq[d + 1][i];
+        // The scheduler, left alone, sinks the staging loads to the chunk's end and the fragment loads to one step ahead.  So
+        // each step is a scheduling region of its own, and in it the memory instructions (NV loads, ND ds_reads) go one by one
+        // between equal groups of the step's MFMAs.  (The builtin takes literal counts: hence the switch.)
+        {
+          const int NV = WM + max(0, min(LPS, NLD - st * LPS)), ND = st + 1 < STEPS ? WN : 0;
+#pragma unroll
+          for (int k = 0; k < NV + ND; ++k) {
+            switch ((4 * WM * WN) / (NV + ND)) {
+              case 0: case 1: __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); break;
+              case 2: __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); break;
+              case 3: __builtin_amdgcn_sched_group_barrier(0x008, 3, 0); break;
+              case 4: __builtin_amdgcn_sched_group_barrier(0x008, 4, 0); break;
+              default: __builtin_amdgcn_sched_group_barrier(0x008, 5, 0); break;
+            }
+            if (k < NV) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);      // VMEM read
+            else __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);             // DS read
+          }
+          __builtin_amdgcn_sched_group_barrier(0x008, 4 * WM * WN, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      __syncthreads();
+    }
+  } else {
+    if (chunk_valid()) prefetch();
+    while (chunk_valid()) {
+      const int ckv_cur = min(CK, curC - cc0);
+      const int ngroups = (ckv_cur + 7) / 8;   // quad pairs holding live channels
+      commit();
+      __syncthreads();
+      chunk_advance();
+      --k_left;
+      dm_f32x4 av[2][WM + (TAIL ? 1 : 0)], bv[2][WN];      // the exact builds' operand fragments
+      if (chunk_valid()) prefetch();
+
+      // ---- MFMA over the committed chunk ---------------------------------------
+      // Operand fragments are double-buffered in registers: the ds_reads of step s+1 are
+      // issued before the 4 x WM x WN MFMAs of step s, so LDS latency never stalls the
+      // matrix pipe (the compiler alone re-uses one register set and issues them late).
+      if (PREC) {
+        // one step per tap: the chunk's 16 channels are ONE k of v_mfma_f32_32x32x16_bf16 (lane half hi = channels 8 hi ..)
+        auto load_frag = [&](int tap, dm_f32x4 (*av)[3], dm_f32x4 (*bv)[3]) {
+          const int tapoff = (KS == 3) ? ((tap / 3) * Wp + (tap % 3)) : 0;
+#pragma unroll
+          for (int i = 0; i < WM; ++i)
+#pragma unroll
+            for (int p_ = 0; p_ < 3; ++p_) av[i][p_] = ldsA[(tap * NWC + 3 * hi + p_) * TMA + (wave_m * WM + i) * 32 + l31];
+#pragma unroll
+          for (int j = 0; j < WN; ++j)
+#pragma unroll
+            for (int p_ = 0; p_ < 3; ++p_) bv[j][p_] = ldsB[p_ * plane + lane_base[j] + tapoff];
+        };
+        auto mfma = [&](const dm_f32x4& x, const dm_f32x4& y, dm_f32x16& c) {
+          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(dm_bf16x8, x), __builtin_bit_cast(dm_bf16x8, y), c, 0, 0, 0);
+        };
+        dm_f32x4 av[2][WM][3], bv[2][WN][3];
+        load_frag(0, av[0], bv[0]);
+#pragma unroll
+        for (int st = 0; st < TAPS; ++st) {
+          const int cur = st & 1;
+          if (st + 1 < TAPS) load_frag(st + 1, av[cur ^ 1], bv[cur ^ 1]);
+#pragma unroll
+          for (int i = 0; i < WM; ++i)
+#pragma unroll
+            for (int j = 0; j < WN; ++j) {
+              // (A part, B part), smallest terms first: the same order in every launch, hence the same bits every run.  The
+              // five correction terms go to an accumulator of their own (~2^-8 of the main one: its roundings are that much
+              // smaller), added to hi*hi's once, before the epilogue.
+              mfma(av[cur][i][2], bv[cur][j][0], accx[i][j]);
+              mfma(av[cur][i][1], bv[cur][j][1], accx[i][j]);
+              mfma(av[cur][i][0], bv[cur][j][2], accx[i][j]);
+              mfma(av[cur][i][1], bv[cur][j][0], accx[i][j]);
+              mfma(av[cur][i][0], bv[cur][j][1], accx[i][j]);
+              mfma(av[cur][i][0], bv[cur][j][0], acc[i][j]);
+            }
+        }
+      } else {
+        constexpr int NG = NQ / 2;
+        constexpr int STEPS = TAPS * NG;
+        auto load_frag = [&](int st, dm_f32x4* av, dm_f32x4* bv) {
+          const int tap = st / NG, g = st - tap * NG;
+          const int tapoff = (KS == 3) ? ((tap / 3) * Wp + (tap % 3)) : 0;
+#pragma unroll
+          for (int i = 0; i < WM; ++i)
+            av[i] = ldsA[(tap * NQ + 2 * g + hi) * TMA + (wave_m * WM + i) * 32 + l31];
+          if (TAIL) av[WM] = ldsA[(tap * NQ + 2 * g + hi) * TMA + TM + (lane & 3)];
+#pragma unroll
+          for (int j = 0; j < WN; ++j) bv[j] = ldsB[(2 * g) * plane + lane_base[j] + tapoff];
+        };
+        load_frag(0, av[0], bv[0]);
+#pragma unroll
+        for (int st = 0; st < STEPS; ++st) {
+          const int cur = st & 1;
+          // quad pairs beyond the chunk's live channels hold zeros (1x1, ragged sources): skip them
+          const bool live = (NG == 1) || ((st % NG) < ngroups);
+          if (st + 1 < STEPS) load_frag(st + 1, av[cur ^ 1], bv[cur ^ 1]);
+          if (live) {
+            // (s_setprio 1 around this cluster: +4 % in tools/micro/mfma_mix.hip, -3.5 % on the headline -- with three workgroups
+            // per CU the prioritised waves starve the ones staging the next chunk)
 #pragma unroll
             for (int e = 0; e < 4; ++e)
 #pragma unroll
-              for (int j = 0; j < WN; ++j)
-                acct[j] = __builtin_amdgcn_mfma_f32_4x4x1f32(av[cur][WM][e], bv[cur][j][e], acct[j], 0, 0, 0);
+              for (int i = 0; i < WM; ++i)
+#pragma unroll
+                for (int j = 0; j < WN; ++j)
+                  acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[cur][i][e], bv[cur][j][e], acc[i][j], 0, 0, 0);
+            if (TAIL) {
+#pragma unroll
+              for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int j = 0; j < WN; ++j)
+                  acct[j] = __builtin_amdgcn_mfma_f32_4x4x1f32(av[cur][WM][e], bv[cur][j][e], acct[j], 0, 0, 0);
+            }
           }
         }
       }
+      __syncthreads();
     }
-    __syncthreads();
+
   }
 
   if (PREC) {
