@@ -35,12 +35,20 @@
 
 namespace {
 
-// dm_conv2d_plan's recorder (host side): launch_conv_mp writes one record per launch it would make and launches nothing.
+// dm_conv2d_plan's / dm_conv2d_group_plan's recorder (host side): conv_emit writes one record per problem of each launch it
+// would make, and nothing is launched.
 // A record is DM_CONV_PLAN_INTS ints in the order the header documents.
 struct ConvPlan {
+  int cap;             // records the caller's array holds: DM_CONV_PLAN_MAX_LAUNCHES (lone) or DM_CONV_GROUP_PLAN_MAX
   int count = 0;
-  int rec[DM_CONV_PLAN_MAX_LAUNCHES][DM_CONV_PLAN_INTS];
+  int rec[DM_CONV_GROUP_PLAN_MAX][DM_CONV_PLAN_INTS];
+  int copy_to(int* records) const {      // -> the number of records
+    for (int l = 0; l < count; ++l)
+      for (int i = 0; i < DM_CONV_PLAN_INTS; ++i) records[l * DM_CONV_PLAN_INTS + i] = rec[l][i];
+    return count;
+  }
 };
+static_assert(DM_CONV_GROUP_PLAN_MAX >= DM_CONV_PLAN_MAX_LAUNCHES, "one array holds either plan");
 
 struct ConvArgs {
   const float* src[DM_MAX_SOURCES];
@@ -1114,11 +1122,75 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_group_kernel(ReduceGro
   splitk_reduce_body<V4>(r.ws[p], splits, stride, NB, Cout, HW, r.bias[p], flags, r.out[p], Cout, 0, nullptr);
 }
 
+// The constants of one build of the kernel: a workgroup of NT threads computes TM (+ TAIL) couts x TN pixels and walks K in
+// chunks of NWC 16-byte words per cout / plane position.  The launchers, and nothing else, read it.
+template <int KS_, int WGM_, int WGN_, int WM_, int WN_, int CK_, int TAIL_, int PREC_>
+struct ConvBuild {
+  static constexpr int KS = KS_, WGM = WGM_, WGN = WGN_, WM = WM_, WN = WN_, CK = CK_, TAIL = TAIL_, PREC = PREC_;
+  static constexpr int TM = WGM * WM * 32, TN = WGN * WN * 32, NT = WGM * WGN * 64, NWC = PREC ? 6 : CK / 4;
+  static constexpr bool DIRECT = conv_direct_a<KS, WGM, WGN, WM, WN, CK, TAIL, PREC>();      // no A image: the B planes only
+  static constexpr size_t lds_bytes(int plane) {
+    return 16 * ((DIRECT ? 0 : (size_t)KS * KS * NWC * (TM + TAIL)) + (size_t)NWC * plane);
+  }
+  // (the fragment loads of a DIRECT build address the packed weights through a buffer descriptor with 32-bit byte offsets)
+  static bool weights_addressable(const ConvArgs& a) { return !DIRECT || (long long)KS * KS * a.KQ * a.CoutP * 16 <= 0x7fffffffLL; }
+};
+
+// Positions of the plane a 3x3 workgroup stages for a tile of TN flat pixels: the rows the tile's pixels touch plus a halo
+// row above and below each image segment of the tile, each row W + 2 wide
+int conv_plane(int TN, int H, int W) {
+  const int nsegmax = dm_ceil_div(TN - 1, H * W) + 1;
+  return (dm_ceil_div(TN - 1, W) + 1 + 2 * nsegmax) * (W + 2);
+}
+
+// The geometry of problems a[0 .. n) under build B (MT, Wp, plane), then f(MAXPOS) for the build that stages a[0]'s plane
+// with B's NT threads: 1, 2 or 4 positions per thread (1x1: no plane, 1).  bf16x3: one position per thread only (maps up
+// to ~16 x 16); wider maps would need more than 80 KB of LDS.
+template <class B, class F>
+int conv_with_maxpos(ConvArgs* a, int n, F&& f) {
+  for (int i = 0; i < n; ++i) {
+    a[i].MT = B::TAIL ? 1 : dm_ceil_div(a[i].CoutP, B::TM);
+    a[i].Wp = B::KS == 3 ? a[i].W + 2 : 0;
+    a[i].plane = B::KS == 3 ? conv_plane(B::TN, a[i].H, a[i].W) : B::TN;
+  }
+  const int plane = a[0].plane;
+  if (B::KS == 1 || plane <= B::NT) return f(std::integral_constant<int, 1>());
+  if constexpr (B::KS == 3 && B::PREC == 0) {
+    if (plane <= 2 * B::NT) return f(std::integral_constant<int, 2>());
+    if (plane <= 4 * B::NT) return f(std::integral_constant<int, 4>());
+  }
+  return DM_ERR_UNSUPPORTED;
+}
+// (The exact 1x1 builds at 2 and 4 positions per thread: no launch reaches them -- a 1x1 tile has no plane -- but the ladder
+// used to instantiate them, and they stay in the code object until a change that measures the library without them.)
+#define DM_CONV_UNREACHED(...) \
+  template __global__ void conv_igemm_kernel<1, __VA_ARGS__, 2>(ConvArgs); \
+  template __global__ void conv_igemm_kernel<1, __VA_ARGS__, 4>(ConvArgs)
+DM_CONV_UNREACHED(1, 4, 1, 1, 32);
+DM_CONV_UNREACHED(2, 2, 1, 2, 16);
+DM_CONV_UNREACHED(2, 2, 2, 2, 16);
+DM_CONV_UNREACHED(4, 1, 1, 1, 32);
+#undef DM_CONV_UNREACHED
+
+// Launches that do not fill the chip take 128 x 32 tiles instead of 128 x 128 (3x3, Cout > 64): up to one 128 x 128 tile per
+// CU costs a lone workgroup's 0.18 ms however few there are, up to two 0.31 ms; 128 x 32 tiles cost 0.04 + 0.046 ms per
+// tile-per-CU (16 RoIs of 14 x 14: 0.175 -> 0.077 ms, 100 RoIs: 0.322 -> 0.275 ms).  wgs: the launch's 128 x 128 tiles.
+bool conv_small_launch(int wgs, int cus) { return wgs * 10 <= cus * 7 || (wgs > cus && wgs * 20 <= cus * 29); }
+
+// K chunks of CK channels a launch walks: every source is padded to whole chunks
+int conv_chunks(int num_srcs, const int* src_c, int CK) {
+  int chunks = 0;
+  for (int s = 0; s < num_srcs; ++s) chunks += dm_ceil_div(src_c[s], CK);
+  return chunks;
+}
+
 // How many K splits pay for a launch that leaves most of the chip idle (1: none).  A launch of one round walks its chunks
 // one after the other at ~2.1 us (3x3) / ~1.5 us (1x1) per chunk whatever the RoI count (tools/small_n.py: conv14 64-71 us
 // for 32 chunks, fuse14 50 us for 33); S splits save (1 - 1/S) of that and cost a second launch (~5 us) that reads S and
 // writes one copy of the output at ~4 TB/s; at least 8 us of net gain.
-static int conv_split_choice(int chunks, bool k3, int Smax, long long out_floats) {
+// (Without this test the 1x1 convolutions of the 28 x 28 / 56 x 56 stages split too: 17.7 reduce launches of 15.7 us
+// each per 100-detection call, more than the splits saved.)
+int conv_split_choice(int chunks, bool k3, int Smax, long long out_floats) {
   const double chain_us = chunks * (k3 ? 2.1 : 1.5), out_mb = (double)out_floats * 4e-6;
   double best = 8.0;
   int S = 1;
@@ -1129,217 +1201,203 @@ static int conv_split_choice(int chunks, bool k3, int Smax, long long out_floats
   return S;
 }
 
-template <int KS, int WGM, int WGN, int WM, int WN, int CK, int MAXPOS, int TAIL = 0, int PREC = 0, int POST = 0>
+// The splits `wgs` workgroups have room for on `slots` resident workgroups (slots per CU differ by build and caller, on purpose)
+int conv_split_max(long long wgs, long long slots, int cap = 8) { return (int)min((long long)cap, slots / max(wgs, 1LL)); }
+
+// The K split of a launch: S, the cost model's choice among the splits there is room for -- slots, at least four chunks per
+// split, one out_floats-sized slice of the ws_floats workspace per split -- run as kchunks = ceil(chunks / S) chunks per split
+// in ksplit = ceil(chunks / kchunks) <= S workgroups per tile (the workspace is laid out for S).
+struct ConvSplit { int S = 1, ksplit = 1, kchunks = 0; };
+ConvSplit conv_split(int chunks, bool k3, long long wgs, long long slots, long long ws_floats, long long out_floats, int cap = 8) {
+  long long Smax = min(conv_split_max(wgs, slots, cap), chunks / 4);
+  if (out_floats > 0) Smax = min(Smax, ws_floats / out_floats);
+  ConvSplit k;
+  k.S = conv_split_choice(chunks, k3, (int)Smax, out_floats);
+  if (k.S >= 2) {
+    k.kchunks = dm_ceil_div(chunks, k.S);
+    k.ksplit = dm_ceil_div(chunks, k.kchunks);
+  }
+  return k;
+}
+
+// The one place a convolution kernel is enqueued -- or, under a recorder (dm_conv2d_plan / dm_conv2d_group_plan), written
+// down instead: problems a[0 .. count) of build B in ONE launch, problem i on workgroups [end[i - 1], end[i]) of grid x,
+// grid y the K split they share.  One record per problem, DM_CONV_PLAN_INTS ints in the order the header documents.
+template <class B, int MAXPOS, int POST, class Enqueue>
+int conv_emit(const ConvArgs* a, const int* end, int count, Enqueue&& enqueue) {
+  const int splits = a[0].ksplit;
+  if (ConvPlan* plan = a[0].plan) {
+    if (plan->count + count > plan->cap) return DM_ERR_INVALID_ARG;
+    for (int i = 0; i < count; ++i) {
+      const int rec[DM_CONV_PLAN_INTS] = {B::KS, B::WGM, B::WGN, B::WM, B::WN, B::CK, B::TAIL, B::PREC, POST, MAXPOS,
+                                          splits, splits > 1 ? a[i].kchunks : 0, a[i].q_begin, a[i].Q,
+                                          end[i] - (i ? end[i - 1] : 0), splits, (a[i].relu & 4) ? 1 : 0};
+      for (int k = 0; k < DM_CONV_PLAN_INTS; ++k) plan->rec[plan->count][k] = rec[k];
+      plan->count++;
+    }
+    return DM_OK;
+  }
+  enqueue(dim3((unsigned)end[count - 1], (unsigned)splits));
+  return dm_check_launch();
+}
+
+// The reduce after a split launch of `count` problems whose bare sums lie at r.ws[p]: conv_splitk_reduce_group_kernel
+// (grouped: bias and ReLU only, outputs of their own) or conv_splitk_reduce_kernel (one problem, with a's output slice and mask)
+int launch_splitk_reduce(const ReduceGroup& r, int count, bool grouped, const ConvArgs& a, int flags, hipStream_t st) {
+  const long long per = a.ws_stride;
+  uintptr_t addr = (uintptr_t)a.mask;
+  for (int p = 0; p < count; ++p) addr |= (uintptr_t)r.ws[p] | (uintptr_t)r.out[p];
+  // four outputs per thread where a quad never straddles a channel plane and everything is 16-byte aligned
+  const bool v4 = (a.HW & 3) == 0 && (per & 3) == 0 && per < 0x7fffffffLL && (addr & 15) == 0;
+  const dim3 grid((unsigned)min((long long)4096, ((v4 ? per / 4 : per) + 255) / 256), grouped ? (unsigned)count : 1u);
+  auto enqueue = [&](auto V4) {
+    if (grouped)
+      DM_LAUNCH(conv_splitk_reduce_group_kernel<decltype(V4)::value>, grid, dim3(256), 0, st, r, a.ksplit, per, a.NB, a.Cout, a.HW, flags);
+    else
+      DM_LAUNCH(conv_splitk_reduce_kernel<decltype(V4)::value>, grid, dim3(256), 0, st, r.ws[0], a.ksplit, per, a.NB, a.Cout, a.HW, r.bias[0],
+                flags, r.out[0], a.out_ch_total, a.out_ch_offset, a.mask);
+  };
+  v4 ? enqueue(std::true_type()) : enqueue(std::false_type());
+  return dm_check_launch();
+}
+
+// One lone launch of build B at MAXPOS positions per thread: the LDS of the build, the K split (a caller-provided workspace,
+// one launch per call), the launch and its reduce
+template <class B, int MAXPOS, int POST>
 int launch_conv_mp(ConvArgs& a, hipStream_t st) {
-  constexpr int TM = WGM * WM * 32;
-  constexpr int TN = WGN * WN * 32;
-  constexpr int NT = WGM * WGN * 64;
-  const int NTiles = dm_ceil_div(a.Q - a.q_begin, TN);
-  constexpr int NWC = PREC ? 6 : CK / 4;
-  constexpr bool DIRECT = conv_direct_a<KS, WGM, WGN, WM, WN, CK, TAIL, PREC>();      // no A image: the B planes only
-  const size_t lds_bytes = 16 * ((DIRECT ? 0 : (size_t)KS * KS * NWC * (TM + TAIL)) + (size_t)NWC * a.plane);
-  // (the fragment loads address the packed weights through a buffer descriptor with 32-bit byte offsets)
-  if (DIRECT && (long long)KS * KS * a.KQ * a.CoutP * 16 > 0x7fffffffLL) return DM_ERR_UNSUPPORTED;
+  const int wgs = a.MT * dm_ceil_div(a.Q - a.q_begin, B::TN);
+  const size_t lds_bytes = B::lds_bytes(a.plane);
+  if (!B::weights_addressable(a)) return DM_ERR_UNSUPPORTED;
   if (lds_bytes > 64 * 1024) {
     // (the bf16x3 3x3 build: 54 KB of A image + 21 KB of plane at 14 x 14; two workgroups per CU.  The exact 128-cout 3x3
     // builds whose plane holds more than 896 positions -- 36 KB of A image + 32 bytes per position: maps 148 .. 168 wide,
     // and narrower single-row ones, 1 x 100: 9 rows of 102 -- while the 64- and 32-cout builds stage every plane up to the
-    // 1024-position limit in 64 KB: whether a map can be staged must not depend on Cout)
+    // 1024-position limit in 64 KB: whether a map can be staged must not depend on Cout.  launch_group_mp raises no limit:
+    // a grouped launch of such a plane is refused.)
     if (lds_bytes > 80 * 1024) return DM_ERR_UNSUPPORTED;
     if (!a.plan) {
       static bool raised[DM_MAX_DEVICES] = {false};
-      const int rc = dm_ensure_lds_limit(reinterpret_cast<const void*>(&conv_igemm_kernel<KS, WGM, WGN, WM, WN, CK, MAXPOS, TAIL, PREC, POST>),
-                                         80 * 1024, raised);
+      const int rc = dm_ensure_lds_limit(
+          reinterpret_cast<const void*>(&conv_igemm_kernel<B::KS, B::WGM, B::WGN, B::WM, B::WN, B::CK, MAXPOS, B::TAIL, B::PREC, POST>),
+          80 * 1024, raised);
       if (rc != DM_OK) return rc;
     }
   }
-  // ---- split-K for launches that leave most of the chip idle (a caller-provided workspace, one launch per call)
+  // ---- split-K for launches that leave most of the chip idle, on three slots per CU or as far as conv2d_launch decided
   a.ksplit = 1;
   if (a.ws && a.shuffle == 0 && a.q_begin == 0 && !POST) {
-    constexpr int CKS = CK;
-    int chunks = 0;
-    for (int s_ = 0; s_ < a.num_srcs; ++s_) chunks += dm_ceil_div(a.src_c[s_], CKS);
-    const int wgs = a.MT * NTiles, cus = dm_num_cus();
     const long long per = (long long)a.NB * a.Cout * a.HW;
-    int Smax = a.want_split > 0 ? min(a.want_split, chunks / 4) : min(min(8, (3 * cus) / max(wgs, 1)), chunks / 4);
-    if (per > 0) Smax = (int)min((long long)Smax, a.ws_floats / per);
-    // worth it?  A launch of one round walks its chunks one after the other at ~2.1 us (3x3) / ~1.5 us (1x1) per chunk
-    // whatever the RoI count (tools/small_n.py: conv14 64-71 us for 32 chunks, fuse14 50 us for 33); S splits save
-    // (1 - 1/S) of that and cost a second launch (~5 us) that reads S and writes one copy of the output at ~4 TB/s.
-    // (Without this test the 1x1 convolutions of the 28 x 28 / 56 x 56 stages split too: 17.7 reduce launches of 15.7 us
-    // each per 100-detection call, more than the splits saved.)
-    const int S = conv_split_choice(chunks, KS == 3, Smax, per);
-    if (S >= 2) {
-      a.kchunks = dm_ceil_div(chunks, S);
-      a.ksplit = dm_ceil_div(chunks, a.kchunks);
+    const ConvSplit k = conv_split(conv_chunks(a.num_srcs, a.src_c, B::CK), B::KS == 3, wgs, 3LL * dm_num_cus(), a.ws_floats, per,
+                                   a.want_split > 0 ? a.want_split : 8);
+    if (k.S >= 2) {
+      a.kchunks = k.kchunks;
+      a.ksplit = k.ksplit;
       a.ws_stride = per;
     }
   }
-  if (a.plan) {
-    // (dm_conv2d_plan) what the launches below would be given, and nothing launched
-    if (a.plan->count >= DM_CONV_PLAN_MAX_LAUNCHES) return DM_ERR_INVALID_ARG;
-    const int rec[DM_CONV_PLAN_INTS] = {KS, WGM, WGN, WM, WN, CK, TAIL, PREC, POST, MAXPOS, a.ksplit, a.ksplit > 1 ? a.kchunks : 0,
-                                        a.q_begin, a.Q, a.MT * NTiles, a.ksplit, (a.relu & 4) ? 1 : 0};
-    for (int i = 0; i < DM_CONV_PLAN_INTS; ++i) a.plan->rec[a.plan->count][i] = rec[i];
-    a.plan->count++;
-    return DM_OK;
-  }
-  if (a.ksplit > 1) {
-    const float* bias = a.bias;
-    const float* mask = a.mask;
-    float* out = a.out;
-    const int flags = a.relu, oct = a.out_ch_total, oco = a.out_ch_offset;
-    DM_LAUNCH((conv_igemm_kernel<KS, WGM, WGN, WM, WN, CK, MAXPOS, TAIL, PREC, POST>), dim3(a.MT * NTiles, a.ksplit), dim3(NT), lds_bytes, st, a);
-    int rc = dm_check_launch();
-    if (rc != DM_OK) return rc;
-    const long long total = a.ws_stride;
-    const bool v4 = (a.HW & 3) == 0 && (total & 3) == 0 && total < 0x7fffffffLL &&
-                    ((((uintptr_t)a.ws) | ((uintptr_t)out) | ((uintptr_t)mask)) & 15) == 0;
-    if (v4)
-      DM_LAUNCH(conv_splitk_reduce_kernel<true>, dim3((unsigned)min((long long)4096, (total / 4 + 255) / 256)), dim3(256), 0, st, a.ws,
-                a.ksplit, a.ws_stride, a.NB, a.Cout, a.HW, bias, flags, out, oct, oco, mask);
-    else
-      DM_LAUNCH(conv_splitk_reduce_kernel<false>, dim3((unsigned)min((long long)4096, (total + 255) / 256)), dim3(256), 0, st, a.ws,
-                a.ksplit, a.ws_stride, a.NB, a.Cout, a.HW, bias, flags, out, oct, oco, mask);
-    return dm_check_launch();
-  }
-  DM_LAUNCH((conv_igemm_kernel<KS, WGM, WGN, WM, WN, CK, MAXPOS, TAIL, PREC, POST>), dim3(a.MT * NTiles), dim3(NT), lds_bytes, st, a);
-  return dm_check_launch();
+  const int rc = conv_emit<B, MAXPOS, POST>(&a, &wgs, 1, [&](dim3 grid) {
+    DM_LAUNCH((conv_igemm_kernel<B::KS, B::WGM, B::WGN, B::WM, B::WN, B::CK, MAXPOS, B::TAIL, B::PREC, POST>), grid, dim3(B::NT),
+              lds_bytes, st, a);
+  });
+  if (rc != DM_OK || a.plan || a.ksplit < 2) return rc;
+  const ReduceGroup r = {{a.ws}, {a.bias}, {a.out}};
+  return launch_splitk_reduce(r, 1, false, a, a.relu, st);
 }
 
 template <int KS, int WGM, int WGN, int WM, int WN, int CK, int TAIL = 0, int PREC = 0, int POST = 0>
 int launch_conv(ConvArgs& a, hipStream_t st) {
-  constexpr int TM = WGM * WM * 32;
-  constexpr int TN = WGN * WN * 32;
-  constexpr int NT = WGM * WGN * 64;
-  a.MT = TAIL ? 1 : dm_ceil_div(a.CoutP, TM);
-  if (KS == 3) {
-    a.Wp = a.W + 2;
-    const int nsegmax = dm_ceil_div(TN - 1, a.HW) + 1;
-    const int rmax = dm_ceil_div(TN - 1, a.W) + 1 + 2 * nsegmax;
-    a.plane = rmax * a.Wp;
-    if constexpr (PREC != 0) {
-      // bf16x3: one plane position per thread (maps up to ~16 x 16); wider maps would need more than 80 KB of LDS
-      if (a.plane <= NT) return launch_conv_mp<KS, WGM, WGN, WM, WN, CK, 1, TAIL, PREC>(a, st);
-      return DM_ERR_UNSUPPORTED;
-    } else {
-      if (a.plane <= NT) return launch_conv_mp<KS, WGM, WGN, WM, WN, CK, 1, TAIL>(a, st);
-      if (a.plane <= 2 * NT) return launch_conv_mp<KS, WGM, WGN, WM, WN, CK, 2, TAIL>(a, st);
-      if (a.plane <= 4 * NT) return launch_conv_mp<KS, WGM, WGN, WM, WN, CK, 4, TAIL>(a, st);
-      return DM_ERR_UNSUPPORTED;
-    }
-  }
-  a.Wp = 0;
-  a.plane = TN;
-  return launch_conv_mp<KS, WGM, WGN, WM, WN, CK, 1, TAIL, PREC, POST>(a, st);
+  using B = ConvBuild<KS, WGM, WGN, WM, WN, CK, TAIL, PREC>;
+  return conv_with_maxpos<B>(&a, 1, [&](auto mp) { return launch_conv_mp<B, decltype(mp)::value, POST>(a, st); });
 }
 
-// One grouped launch (dm_conv2d_group_fwd / dm_deconv2x2_group_fwd) of the problems g.a[0 .. count): the per-problem
-// geometry launch_conv / launch_conv_mp derive, each problem in its own range of the grid, and -- S >= 2, shuffle == 0 --
-// the K loop split over S workgroups per tile exactly as launch_conv_mp splits a lone launch (kchunks = ceil(chunks / S)
-// chunks of CK channels each), with problem p's bare sums at ws + p * S * per, reduced by ONE conv_splitk_reduce_group_kernel.
-template <int KS, int WGM, int WGN, int WM, int WN, int CK, int MAXPOS>
-int launch_group_mp(ConvGroup& g, int count, int S, float* ws, hipStream_t st) {
-  constexpr int TN = WGN * WN * 32;
-  constexpr int TM = WGM * WM * 32;
+// One grouped launch (dm_conv2d_group_fwd / dm_deconv2x2_group_fwd / dm_conv1x1_group_fwd) of the problems g.a[0 .. count),
+// each in its own range of the grid, and -- k.S >= 2, problems of one shape, shuffle == 0 -- the K loop split over k.ksplit
+// workgroups per tile exactly as launch_conv_mp splits a lone launch, with problem p's bare sums at ws + p * k.S * per,
+// reduced by ONE conv_splitk_reduce_group_kernel.
+template <class B, int MAXPOS>
+int launch_group_mp(ConvGroup& g, int count, const ConvSplit& k, float* ws, hipStream_t st) {
   const ConvArgs& a0 = g.a[0];
-  constexpr bool DIRECT = conv_direct_a<KS, WGM, WGN, WM, WN, CK, 0, 0>();      // (as in launch_conv_mp)
-  const size_t lds_bytes = 16 * ((DIRECT ? 0 : (size_t)KS * KS * (CK / 4) * TM) + (size_t)(CK / 4) * a0.plane);
-  if (DIRECT && (long long)KS * KS * a0.KQ * a0.CoutP * 16 > 0x7fffffffLL) return DM_ERR_UNSUPPORTED;
-  if (lds_bytes > 64 * 1024) return DM_ERR_UNSUPPORTED;
-  int chunks = dm_ceil_div(a0.src_c[0], CK);
+  const size_t lds_bytes = B::lds_bytes(a0.plane);
+  for (int i = 0; i < count; ++i)
+    if (!B::weights_addressable(g.a[i])) return DM_ERR_UNSUPPORTED;
+  if (lds_bytes > 64 * 1024) return DM_ERR_UNSUPPORTED;      // (where launch_conv_mp raises the limit: its comment)
   const long long per = (long long)a0.NB * a0.Cout * a0.HW;
   int total = 0;
   for (int i = 0; i < 3; ++i) {
     ConvArgs& a = g.a[i];
-    a.ksplit = 1;
-    if (S >= 2) {
-      a.kchunks = dm_ceil_div(chunks, S);
-      a.ksplit = dm_ceil_div(chunks, a.kchunks);
-      a.ws = ws + (size_t)min(i, count - 1) * S * per;
+    a.ksplit = k.ksplit;
+    if (k.S >= 2) {
+      a.kchunks = k.kchunks;
+      a.ws = ws + (size_t)min(i, count - 1) * k.S * per;
       a.ws_stride = per;
-      a.ws_floats = (long long)S * per;
+      a.ws_floats = (long long)k.S * per;
     }
-    if (i < count) total += a.MT * dm_ceil_div(a.Q, TN);
+    if (i < count) total += a.MT * dm_ceil_div(a.Q, B::TN);
     g.end[i] = total;
   }
-  const int splits = g.a[0].ksplit;
-  DM_LAUNCH((conv_igemm_group_kernel<KS, WGM, WGN, WM, WN, CK, MAXPOS>), dim3((unsigned)total, (unsigned)splits), dim3(WGM * WGN * 64),
-            lds_bytes, st, g);
-  int rc = dm_check_launch();
-  if (rc != DM_OK || splits < 2) return rc;
+  const int rc = conv_emit<B, MAXPOS, 0>(g.a, g.end, count, [&](dim3 grid) {
+    DM_LAUNCH((conv_igemm_group_kernel<B::KS, B::WGM, B::WGN, B::WM, B::WN, B::CK, MAXPOS, B::PREC>), grid, dim3(B::NT), lds_bytes, st, g);
+  });
+  if (rc != DM_OK || a0.plan || a0.ksplit < 2) return rc;
   ReduceGroup r;
   for (int i = 0; i < 3; ++i) {
     const ConvArgs& a = g.a[min(i, count - 1)];
     r.ws[i] = a.ws; r.bias[i] = a.bias; r.out[i] = a.out;
   }
-  bool v4 = (a0.HW & 3) == 0 && (per & 3) == 0 && per < 0x7fffffffLL && (((uintptr_t)ws) & 15) == 0 && (S * per & 3) == 0;
-  for (int i = 0; i < count; ++i) v4 = v4 && (((uintptr_t)g.a[i].out) & 15) == 0;
-  const int flags = a0.relu & 1;
-  if (v4)
-    DM_LAUNCH(conv_splitk_reduce_group_kernel<true>, dim3((unsigned)min((long long)4096, (per / 4 + 255) / 256), (unsigned)count),
-              dim3(256), 0, st, r, splits, per, a0.NB, a0.Cout, a0.HW, flags);
-  else
-    DM_LAUNCH(conv_splitk_reduce_group_kernel<false>, dim3((unsigned)min((long long)4096, (per + 255) / 256), (unsigned)count),
-              dim3(256), 0, st, r, splits, per, a0.NB, a0.Cout, a0.HW, flags);
-  return dm_check_launch();
+  return launch_splitk_reduce(r, count, true, a0, a0.relu & 1, st);
 }
 
-// launch_conv's plane geometry for every problem, then launch_group_mp with the MAXPOS build the plane needs
-template <int KS, int WGM, int WGN, int WM, int WN, int CK>
-int launch_group(ConvGroup& g, int count, int S, float* ws, hipStream_t st) {
-  constexpr int TM = WGM * WM * 32;
-  constexpr int TN = WGN * WN * 32;
-  constexpr int NT = WGM * WGN * 64;
-  for (int i = 0; i < 3; ++i) {
-    ConvArgs& a = g.a[i];
-    a.MT = dm_ceil_div(a.CoutP, TM);
-    if (KS == 3) {
-      a.Wp = a.W + 2;
-      const int nsegmax = dm_ceil_div(TN - 1, a.HW) + 1;
-      a.plane = (dm_ceil_div(TN - 1, a.W) + 1 + 2 * nsegmax) * a.Wp;
-    } else {
-      a.Wp = 0;
-      a.plane = TN;
-    }
-  }
-  const int plane = g.a[0].plane;
-  if constexpr (KS == 1) {
-    return launch_group_mp<KS, WGM, WGN, WM, WN, CK, 1>(g, count, S, ws, st);
-  } else {
-    if (plane <= NT) return launch_group_mp<KS, WGM, WGN, WM, WN, CK, 1>(g, count, S, ws, st);
-    if (plane <= 2 * NT) return launch_group_mp<KS, WGM, WGN, WM, WN, CK, 2>(g, count, S, ws, st);
-    if (plane <= 4 * NT) return launch_group_mp<KS, WGM, WGN, WM, WN, CK, 4>(g, count, S, ws, st);
-    return DM_ERR_UNSUPPORTED;
-  }
+template <int KS, int WGM, int WGN, int WM, int WN, int CK, int PREC = 0>
+int launch_group(ConvGroup& g, int count, const ConvSplit& k, float* ws, hipStream_t st) {
+  using B = ConvBuild<KS, WGM, WGN, WM, WN, CK, 0, PREC>;
+  return conv_with_maxpos<B>(g.a, 3, [&](auto mp) { return launch_group_mp<B, decltype(mp)::value>(g, count, k, ws, st); });
 }
 
-// The K splits of a grouped 3x3 launch (1: none) for a workspace of ws_floats: the decision conv2d_launch / launch_conv_mp
-// make for ONE problem of this shape, taken on the grouped workgroup count -- a grouped launch fills more of the chip and
-// splits less.  The cost model is the lone launch's (per-problem output size), so a lone dm_conv2d_fwd_ws given S
-// problem-sized workspaces picks the same S (its Smax is then S, and S is the first maximum of the model below any larger
-// Smax).  1x1 problems never split here.
-int group_split_choice(int count, int NB, int H, int W, int Cin, int Cout, int ksize, long long ws_floats) {
-  if (ksize != 3 || NB <= 0 || ws_floats <= 0) return 1;
+// The K split of a grouped 3x3 launch for a workspace of ws_floats: the decision conv2d_launch / launch_conv_mp make for ONE
+// problem of this shape, taken on the grouped workgroup count -- a grouped launch fills more of the chip and splits less.
+// The cost model is the lone launch's (per-problem output size, each problem's share of the workspace), so a lone
+// dm_conv2d_fwd_ws given S problem-sized workspaces picks the same S (its Smax is then S, and S is the first maximum of
+// the model below any larger Smax).  1x1 problems never split here.
+ConvSplit group_split(int count, int NB, int H, int W, int Cin, int Cout, int ksize, long long ws_floats) {
+  if (ksize != 3 || NB <= 0 || ws_floats <= 0) return ConvSplit();
   const long long per = (long long)NB * Cout * H * W;
   const long long Q = (long long)NB * H * W;
-  const int chunks = dm_ceil_div(Cin, 8);
   const int cus = dm_num_cus();
-  long long wgs, slots;
-  if (Cout > 64) {
-    slots = 2LL * cus;        // (the grouped 128 x 128 build runs two workgroups per CU: conv_igemm_group_kernel's bounds)
-    wgs = (long long)count * dm_ceil_div((Cout + 31) / 32 * 32, 128) * dm_ceil_div(Q, 128);
-    if (wgs >= slots) return 1;
-  } else {
-    slots = 3LL * cus;
-    wgs = (long long)count * dm_ceil_div(Q, 128);
-  }
-  long long Smax = min(8LL, slots / max(wgs, 1LL));
-  Smax = min(Smax, ws_floats / ((long long)count * per));
-  Smax = min(Smax, (long long)(chunks / 4));
-  if (Smax < 2) return 1;
-  return conv_split_choice(chunks, true, (int)Smax, per);
+  // (the grouped 128 x 128 build runs two workgroups per CU: conv_igemm_group_kernel's bounds; the 64 / 32 x 128 builds three)
+  const long long slots = Cout > 64 ? 2LL * cus : 3LL * cus;
+  const long long wgs = (long long)count * (Cout > 64 ? dm_ceil_div(dm_conv_packed_cout(Cout), 128) : 1) * dm_ceil_div(Q, 128);
+  return conv_split(dm_ceil_div(Cin, 8), true, wgs, slots, ws_floats / count, per);
 }
+
+// Fills a: the arguments of one convolution as the kernel reads them, for every entry point -- the sources (src_bs null:
+// dense), the map, the packed weights (bf16x3: that layout) and the `couts` packed columns, the flags as the kernel takes
+// them, the output slice, the deconv's shuffle.  Everything else keeps ConvArgs' defaults.
+int conv_fill(ConvArgs& a, const float* const* srcs, const int* src_c, const long long* src_bs, int num_srcs, int NB, int H, int W,
+              const float* wq, bool bf16x3, const float* bias, int couts, int flags, float* out, int out_ch_total,
+              int out_ch_offset, int shuffle) {
+  a = ConvArgs();          // (zeroes: the sources past num_srcs are null and empty)
+  a.off32 = 1;
+  for (int s = 0; s < num_srcs; ++s) {
+    if (!srcs[s] || src_c[s] <= 0) return DM_ERR_INVALID_ARG;
+    a.src[s] = srcs[s];
+    a.src_c[s] = src_c[s];
+    a.src_bs[s] = src_bs ? src_bs[s] : (long long)src_c[s] * H * W;
+    if (a.src_bs[s] < (long long)src_c[s] * H * W) return DM_ERR_INVALID_ARG;
+    if ((long long)NB * a.src_bs[s] * 4 >= (1LL << 32)) a.off32 = 0;
+  }
+  a.num_srcs = num_srcs;
+  a.KQ = bf16x3 ? packed_words_bf16x3(num_srcs, src_c) : packed_quads(num_srcs, src_c);
+  a.NB = NB; a.H = H; a.W = W; a.HW = H * W; a.Q = NB * H * W;
+  a.wq = wq; a.bias = bias; a.Cout = couts; a.CoutP = dm_conv_packed_cout(couts);
+  a.relu = flags; a.out = out; a.out_ch_total = out_ch_total; a.out_ch_offset = out_ch_offset;
+  a.shuffle = shuffle;
+  return DM_OK;
+}
+
+// outputs that cannot stay in the 256 MB Infinity Cache next to their consumer's other traffic are
+// written with nontemporal stores (measured: -10 % on the 1.85 GB column-gradient GEMM, neutral
+// below): the launchers' own flag bit 2
+int conv_store_policy(int NB, int Cout, int H, int W) { return (long long)NB * Cout * H * W * 4 > (192LL << 20) ? 4 : 0; }
 
 int run_pack_bf16x3(PackArgs& p, hipStream_t st) {
   const long long total = (long long)p.kk * (p.KQ / 3) * p.colsP;
@@ -1427,7 +1485,117 @@ static int conv2d_launch(const float* const* srcs, const int* src_channels, cons
                          int num_srcs, int NB, int H, int W,
                          const float* w_packed, const float* bias, int Cout, int ksize, int relu, float* out,
                          int out_ch_total, int out_ch_offset, const float* mask, dm_stream_t stream, float* ws = nullptr,
-                         long long ws_floats = 0, const float* addend = nullptr, ConvPlan* plan = nullptr);
+                         long long ws_floats = 0, const float* addend = nullptr, ConvPlan* plan = nullptr) {
+  if (mask && (relu & 16)) return DM_ERR_UNSUPPORTED;      // (no bf16x3 build of the data-gradient launches)
+  if (!srcs || !src_channels || num_srcs < 1 || num_srcs > DM_MAX_SOURCES || !w_packed || !out) return DM_ERR_INVALID_ARG;
+  if (NB < 0 || H <= 0 || W <= 0 || Cout <= 0 || (ksize != 1 && ksize != 3)) return DM_ERR_INVALID_ARG;
+  if (out_ch_offset < 0 || out_ch_offset + Cout > out_ch_total) return DM_ERR_INVALID_ARG;
+  if ((long long)NB * H * W > 0x7fffffffLL) return DM_ERR_INVALID_ARG;
+  if (NB == 0) return DM_OK;
+  if (relu & ~(1 | 2 | 8 | 16)) return DM_ERR_INVALID_ARG;      // (bit 2 is the launcher's own store-policy bit; bit 5 selected a bf16-split layout of ABI 18-21: removed)
+  const bool bf16x3 = (relu & 16) != 0;          // (ABI 28) w_packed is the bf16x3 layout (dm_conv_pack_weight_bf16x3)
+  ConvArgs a;
+  const int rc = conv_fill(a, srcs, src_channels, src_batch_strides, num_srcs, NB, H, W, w_packed, bf16x3, bias, Cout, relu & 3, out,
+                           out_ch_total, out_ch_offset, 0);
+  if (rc != DM_OK) return rc;
+  a.plan = plan;
+  a.mask = mask;
+  a.ws = (ws && ws_floats > 0) ? ws : nullptr;
+  a.ws_floats = ws_floats;
+  // (accumulating launches read the destination and keep the default store policy)
+  if (!(relu & 2)) a.relu |= conv_store_policy(NB, Cout, H, W);
+  hipStream_t st = (hipStream_t)stream;
+  if (addend) {
+    // (K26) the POST builds: exact fp32 1x1, flags ReLU only, no split, default store policy
+    if (ksize != 1 || bf16x3) return DM_ERR_UNSUPPORTED;
+    if ((relu & ~1) || mask) return DM_ERR_INVALID_ARG;
+    a.addend = addend;
+    a.relu = relu & 1;
+    a.ws = nullptr;
+  }
+  if (bf16x3) {
+    // one build per kernel size: 64 couts x 128 pixels, four waves of 32 x 64 (see the kernel's header); a workspace
+    // lets it split K as the exact launches do (conv_split's cost model, 16-channel chunks)
+    if (ksize == 3) return launch_conv<3, 2, 2, 1, 2, 16, 0, 1>(a, st);
+    return launch_conv<1, 2, 2, 1, 2, 16, 0, 1>(a, st);
+  }
+  if (ksize == 3) {
+    if (Cout > 64) {
+      // 128 x 128 tiles run two or three to a CU: a launch is a sequence of rounds of 512 / 768 workgroups,
+      // and a last round with few workgroups takes as long as a lone workgroup (measured at two per CU:
+      // 501 RoIs of 14 x 14 = 1536 workgroups 0.916 ms, 502 RoIs 1.059 ms).  The pixels of an underfull last round go to a
+      // second launch with 128 x 32 tiles: four times the workgroups, a quarter of the time each.
+      // The split depends on the launch shape only, and both variants add an output's products
+      // in the same order (chunk, tap, channel pair), so results do not depend on it.  A caller that
+      // keeps a second stream busy (flag bit 3) has that stream's workgroups fill the last round;
+      // the extra dependent launch then only delays its own stream (measured: 250 vs 241 img/s).
+      // Worth it while the last round is at most ~0.6 full (measured at 0.01 .. 0.99); DM_CONV_TAIL=0
+      // turns it off (A/B measurements).
+      static const int tail_mode = getenv("DM_CONV_TAIL") ? atoi(getenv("DM_CONV_TAIL")) : 1;
+      const int MT = dm_ceil_div(a.CoutP, 128), NTiles = dm_ceil_div(a.Q, 128);
+      const int wgs = MT * NTiles, cus = dm_num_cus();
+      // workgroups per CU: 3 when the staged plane needs one position per thread (the 168-VGPR build
+      // of the kernel; 14 x 14 maps), else 2
+      const int plane128 = conv_plane(128, H, W);
+      const int slots = (plane128 <= 256 ? 3 : 2) * cus;
+      // A 128-pixel tile whose plane no build can stage (more than 4 x 256 positions: 1 x 1 maps, a tile of 128 images)
+      // while the 32-pixel tile's fits: the whole launch takes the 128 x 32 build, whatever its size -- the answer must
+      // not depend on NB.  (Maps wider than 168 fit neither: conv_with_maxpos refuses them.)
+      if (plane128 > 4 * 256) return launch_conv<3, 4, 1, 1, 1, 8>(a, st);
+      // with a workspace: the 128 x 128 tiles (the efficient build) and as many K splits as fill ONE round of slots
+      // (100 RoIs of 14 x 14: 306 tiles x 2 splits on 768 slots; the 128 x 32 tiles without a split: 0.233 ms)
+      if (a.ws && wgs < slots) {
+        // (the split is DECIDED here, with launch_conv_mp's own cost model, before the tile build is chosen --
+        // a launch the model then declined to split used to run the 128 x 128 tiles unsplit instead of the 128 x 32 ones)
+        const ConvSplit k = conv_split(conv_chunks(num_srcs, src_channels, 8), true, wgs, slots, a.ws_floats, (long long)NB * Cout * H * W);
+        if (k.S >= 2) {
+          a.want_split = k.S;
+          return launch_conv<3, 2, 2, 2, 2, 8>(a, st);
+        }
+      }
+      if (tail_mode && conv_small_launch(wgs, cus)) return launch_conv<3, 4, 1, 1, 1, 8>(a, st);
+      const int full_rounds = wgs / slots;
+      const int rem = wgs - full_rounds * slots;
+      if (tail_mode && !(relu & 8) && full_rounds >= 1 && rem > 0 && rem * 5 <= 3 * slots) {
+        const int n_main = full_rounds * slots / MT;
+        const int Q = a.Q;
+        a.Q = n_main * 128;
+        const int rc_main = launch_conv<3, 2, 2, 2, 2, 8>(a, st);
+        if (rc_main != DM_OK) return rc_main;
+        a.q_begin = a.Q;
+        a.Q = Q;
+        return launch_conv<3, 4, 1, 1, 1, 8>(a, st);
+      }
+      return launch_conv<3, 2, 2, 2, 2, 8>(a, st);
+    }
+    if (Cout > 32 && Cout <= 36 && !(relu & 2)) return launch_conv<3, 1, 4, 1, 1, 8, 4>(a, st);   // DCN offset convs: 32 + 4
+    if (Cout > 32) return launch_conv<3, 1, 4, 2, 1, 8>(a, st);
+    return launch_conv<3, 1, 4, 1, 1, 8>(a, st);
+  }
+  if (Cout > 64) {
+    // A launch of few 128 x 128 tiles (the <= 100-RoI inference calls: 25-307 workgroups for 256 CUs) is a chain of K
+    // chunks per workgroup, and next to another stream's 3x3 launch -- the two RoI chains of a 100-detection call -- each
+    // chunk's 32 MFMAs per wave queue behind the neighbour's.  Up to 1.25 tiles per CU the launch takes 128 couts x 32
+    // pixels instead: four times the workgroups, 8 MFMAs per wave and chunk.  Same products in the same order (a
+    // 32-channel chunk walks its quad pairs in the order two 16-channel chunks do), so rows do not depend on the launch
+    // size (tests/test_ops_gpu.py).  Measured (profiles/r06_infer_notes.txt (5)): 100 / 64 / 32 / 16 detections
+    // 1.941 / 1.407 / 0.901 / 0.608 -> 1.879 / 1.360 / 0.884 / 0.584 ms; thresholds 100 / 160 / 320 / 640 / 1300 tiles:
+    // 1.923 / 1.896 / 1.879-1.891 / 1.883 / 1.887 at 100 detections; 128 x 64 tiles for the next 320-1300 and 64 x 64 tiles
+    // for the 64-cout build: inside the noise, not kept.  DM_CONV1_SMALL_WGS: the threshold in tiles (0: off), for A/B runs.
+    static const int small_env = getenv("DM_CONV1_SMALL_WGS") ? atoi(getenv("DM_CONV1_SMALL_WGS")) : -1;
+    const int small_wgs = small_env >= 0 ? small_env : (5 * dm_num_cus()) / 4;
+    // (the POST builds take the tiles the plain launch of the shape takes: the same products in the same order)
+    if (!(relu & 2) && !mask && dm_ceil_div(a.CoutP, 128) * dm_ceil_div(a.Q, 128) <= small_wgs)
+      return addend ? launch_conv<1, 4, 1, 1, 1, 32, 0, 0, 1>(a, st) : launch_conv<1, 4, 1, 1, 1, 32>(a, st);
+    return addend ? launch_conv<1, 2, 2, 2, 2, 16, 0, 0, 1>(a, st) : launch_conv<1, 2, 2, 2, 2, 16>(a, st);
+  }
+  if (Cout > 32) {
+    // 64 couts x 128 px as 4 waves of 32 x 64: 0.437 -> 0.379 ms on 576 -> 64 @56^2 x 128 RoIs, 0.098 -> 0.089 ms on
+    // 64 -> 64 x 256 (the other tilings tried: docs/HISTORY.md, round 3); one k order per output.
+    return addend ? launch_conv<1, 2, 2, 1, 2, 16, 0, 0, 1>(a, st) : launch_conv<1, 2, 2, 1, 2, 16>(a, st);
+  }
+  return addend ? launch_conv<1, 1, 4, 1, 1, 32, 0, 0, 1>(a, st) : launch_conv<1, 1, 4, 1, 1, 32>(a, st);
+}
 
 extern "C" int dm_conv2d_fwd(const float* const* srcs, const int* src_channels, const long long* src_batch_strides,
                              int num_srcs, int NB, int H, int W,
@@ -1446,14 +1614,11 @@ extern "C" long long dm_conv2d_splitk_floats(int NB, int H, int W, int Cout, int
   const long long px = (long long)NB * H * W;
   // tiles of the smallest configuration the launcher would pick: 128 couts x 32 pixels (3x3, Cout > 64), else >= 64 x 128
   const long long wgs = (long long)dm_ceil_div(Cout, 128) * dm_ceil_div(px, 128);
-  if (ksize == 3 && Cout > 64) {
-    // 128 x 128 tiles, two or three workgroups per CU: split while the tiles do not fill half a round of slots
-    const long long slots = 3LL * dm_num_cus();
-    if (wgs * 2 > slots) return 0;
-    return min(8LL, slots / wgs) * NB * Cout * H * W;
-  }
-  if (wgs * 2 > 3LL * dm_num_cus()) return 0;
-  return 8LL * NB * Cout * H * W;
+  // split while the tiles do not fill half a round of three slots per CU; the 3x3 launches of 128 x 128 tiles (two or three
+  // workgroups per CU) as far as the slots go, the others as far as the chunk count will let them
+  const int Smax = conv_split_max(wgs, 3LL * dm_num_cus());
+  if (Smax < 2) return 0;
+  return (ksize == 3 && Cout > 64 ? Smax : 8) * px * Cout;
 }
 
 extern "C" int dm_conv2d_fwd_ws(const float* const* srcs, const int* src_channels, const long long* src_batch_strides,
@@ -1495,158 +1660,11 @@ extern "C" int dm_conv2d_plan(const int* src_channels, const long long* src_batc
   if (has_mask && has_addend) return DM_ERR_INVALID_ARG;
   static float dummy[4];
   const float* srcs[DM_MAX_SOURCES] = {dummy, dummy, dummy, dummy};
-  ConvPlan plan;
+  ConvPlan plan = {DM_CONV_PLAN_MAX_LAUNCHES};
   const int rc = conv2d_launch(srcs, src_channels, src_batch_strides, num_srcs, NB, H, W, dummy, nullptr, Cout, ksize, relu, dummy,
                                out_ch_total, out_ch_offset, has_mask ? dummy : nullptr, nullptr,
                                workspace_floats > 0 ? dummy : nullptr, workspace_floats, has_addend ? dummy : nullptr, &plan);
-  if (rc != DM_OK) return rc;
-  for (int l = 0; l < plan.count; ++l)
-    for (int i = 0; i < DM_CONV_PLAN_INTS; ++i) records[l * DM_CONV_PLAN_INTS + i] = plan.rec[l][i];
-  return plan.count;
-}
-
-static int conv2d_launch(const float* const* srcs, const int* src_channels, const long long* src_batch_strides,
-                         int num_srcs, int NB, int H, int W,
-                         const float* w_packed, const float* bias, int Cout, int ksize, int relu, float* out,
-                         int out_ch_total, int out_ch_offset, const float* mask, dm_stream_t stream, float* ws,
-                         long long ws_floats, const float* addend, ConvPlan* plan) {
-  if (mask && (relu & 16)) return DM_ERR_UNSUPPORTED;      // (no bf16x3 build of the data-gradient launches)
-  if (!srcs || !src_channels || num_srcs < 1 || num_srcs > DM_MAX_SOURCES || !w_packed || !out) return DM_ERR_INVALID_ARG;
-  if (NB < 0 || H <= 0 || W <= 0 || Cout <= 0 || (ksize != 1 && ksize != 3)) return DM_ERR_INVALID_ARG;
-  if (out_ch_offset < 0 || out_ch_offset + Cout > out_ch_total) return DM_ERR_INVALID_ARG;
-  if ((long long)NB * H * W > 0x7fffffffLL) return DM_ERR_INVALID_ARG;
-  if (NB == 0) return DM_OK;
-  ConvArgs a;
-  a.plan = plan;
-  for (int s = 0; s < DM_MAX_SOURCES; ++s) {
-    a.src[s] = s < num_srcs ? srcs[s] : nullptr;
-    a.src_c[s] = s < num_srcs ? src_channels[s] : 0;
-    a.src_bs[s] = 0;
-    if (s < num_srcs) {
-      if (!srcs[s] || src_channels[s] <= 0) return DM_ERR_INVALID_ARG;
-      a.src_bs[s] = src_batch_strides ? src_batch_strides[s] : (long long)src_channels[s] * H * W;
-      if (a.src_bs[s] < (long long)src_channels[s] * H * W) return DM_ERR_INVALID_ARG;
-    }
-  }
-  a.num_srcs = num_srcs;
-  if (relu & ~(1 | 2 | 8 | 16)) return DM_ERR_INVALID_ARG;      // (bit 2 is the launcher's own store-policy bit; bit 5 selected a bf16-split layout of ABI 18-21: removed)
-  const bool bf16x3 = (relu & 16) != 0;          // (ABI 28) w_packed is the bf16x3 layout (dm_conv_pack_weight_bf16x3)
-  a.KQ = bf16x3 ? packed_words_bf16x3(num_srcs, src_channels) : packed_quads(num_srcs, src_channels);
-  a.NB = NB; a.H = H; a.W = W; a.HW = H * W; a.Q = NB * H * W;
-  a.wq = w_packed; a.bias = bias; a.Cout = Cout; a.CoutP = dm_conv_packed_cout(Cout);
-  a.relu = relu & 3; a.out = out; a.out_ch_total = out_ch_total; a.out_ch_offset = out_ch_offset;
-  a.shuffle = 0;
-  a.q_begin = 0;
-  a.mask = mask;
-  a.ws = (ws && ws_floats > 0) ? ws : nullptr;
-  a.ws_floats = ws_floats;
-  a.off32 = 1;
-  for (int s = 0; s < num_srcs; ++s)
-    if ((long long)NB * a.src_bs[s] * 4 >= (1LL << 32)) a.off32 = 0;
-  // outputs that cannot stay in the 256 MB Infinity Cache next to their consumer's other traffic are
-  // written with nontemporal stores (measured: -10 % on the 1.85 GB column-gradient GEMM, neutral
-  // below); accumulating launches read the destination and keep the default policy
-  if (!(relu & 2) && (long long)NB * Cout * H * W * 4 > (192LL << 20)) a.relu |= 4;
-  hipStream_t st = (hipStream_t)stream;
-  if (addend) {
-    // (K26) the POST builds: exact fp32 1x1, flags ReLU only, no split, default store policy
-    if (ksize != 1 || bf16x3) return DM_ERR_UNSUPPORTED;
-    if ((relu & ~1) || mask) return DM_ERR_INVALID_ARG;
-    a.addend = addend;
-    a.relu = relu & 1;
-    a.ws = nullptr;
-  }
-  if (bf16x3) {
-    // one build per kernel size: 64 couts x 128 pixels, four waves of 32 x 64 (see the kernel's header); a workspace
-    // lets it split K as the exact launches do (launch_conv_mp's cost model, 16-channel chunks)
-    if (ksize == 3) return launch_conv<3, 2, 2, 1, 2, 16, 0, 1>(a, st);
-    return launch_conv<1, 2, 2, 1, 2, 16, 0, 1>(a, st);
-  }
-  if (ksize == 3) {
-    if (Cout > 64) {
-      // 128 x 128 tiles run two or three to a CU: a launch is a sequence of rounds of 512 / 768 workgroups,
-      // and a last round with few workgroups takes as long as a lone workgroup (measured at two per CU:
-      // 501 RoIs of 14 x 14 = 1536 workgroups 0.916 ms, 502 RoIs 1.059 ms).  The pixels of an underfull last round go to a
-      // second launch with 128 x 32 tiles: four times the workgroups, a quarter of the time each.
-      // The split depends on the launch shape only, and both variants add an output's products
-      // in the same order (chunk, tap, channel pair), so results do not depend on it.  A caller that
-      // keeps a second stream busy (flag bit 3) has that stream's workgroups fill the last round;
-      // the extra dependent launch then only delays its own stream (measured: 250 vs 241 img/s).
-      // Worth it while the last round is at most ~0.6 full (measured at 0.01 .. 0.99); DM_CONV_TAIL=0
-      // turns it off (A/B measurements).
-      static const int tail_mode = getenv("DM_CONV_TAIL") ? atoi(getenv("DM_CONV_TAIL")) : 1;
-      const int MT = dm_ceil_div(a.CoutP, 128), NTiles = dm_ceil_div(a.Q, 128);
-      // workgroups per CU: 3 when the staged plane needs one position per thread (the 168-VGPR build
-      // of the kernel; 14 x 14 maps), else 2
-      const int rmax128 = dm_ceil_div(127, a.W) + 1 + 2 * (dm_ceil_div(127, a.HW) + 1);
-      const int slots = (rmax128 * (a.W + 2) <= 256 ? 3 : 2) * dm_num_cus();
-      // A 128-pixel tile whose plane no build can stage (more than 4 x 256 positions: 1 x 1 maps, a tile of 128 images)
-      // while the 32-pixel tile's fits: the whole launch takes the 128 x 32 build, whatever its size -- the answer must
-      // not depend on NB.  (Maps wider than 168 fit neither: launch_conv refuses them.)
-      if (rmax128 * (a.W + 2) > 4 * 256) return launch_conv<3, 4, 1, 1, 1, 8>(a, st);
-      const int full_rounds = (MT * NTiles) / slots;
-      const int rem = MT * NTiles - full_rounds * slots;
-      // Launches that do not fill the chip: up to one 128 x 128 tile per CU costs a lone workgroup's
-      // 0.18 ms however few there are, up to two 0.31 ms; 128 x 32 tiles cost 0.04 + 0.046 ms per
-      // tile-per-CU (16 RoIs of 14 x 14: 0.175 -> 0.077 ms, 100 RoIs: 0.322 -> 0.275 ms).
-      {
-        const int wgs = MT * NTiles, cus = dm_num_cus();
-        // with a workspace: the 128 x 128 tiles (the efficient build) and as many K splits as fill ONE round of slots
-        // (100 RoIs of 14 x 14: 306 tiles x 2 splits on 768 slots; the 128 x 32 tiles without a split: 0.233 ms)
-        if (a.ws && wgs < slots) {
-          const long long per = (long long)NB * Cout * H * W;
-          // (the split is DECIDED here, with launch_conv_mp's own cost model, before the tile build is chosen --
-          // a launch the model then declined to split used to run the 128 x 128 tiles unsplit instead of the 128 x 32 ones)
-          int chunks = 0;
-          for (int s_ = 0; s_ < num_srcs; ++s_) chunks += dm_ceil_div(src_channels[s_], 8);
-          int Smax = (int)min((long long)min(8, slots / wgs), per > 0 ? a.ws_floats / per : 0LL);
-          Smax = min(Smax, chunks / 4);
-          if (conv_split_choice(chunks, true, Smax, per) >= 2) {
-            a.want_split = Smax;
-            return launch_conv<3, 2, 2, 2, 2, 8>(a, st);
-          }
-        }
-        if (tail_mode && (wgs * 10 <= cus * 7 || (wgs > cus && wgs * 20 <= cus * 29))) return launch_conv<3, 4, 1, 1, 1, 8>(a, st);
-      }
-      if (tail_mode && !(relu & 8) && full_rounds >= 1 && rem > 0 && rem * 5 <= 3 * slots) {
-        const int n_main = full_rounds * slots / MT;
-        const int Q = a.Q;
-        a.Q = n_main * 128;
-        int rc = launch_conv<3, 2, 2, 2, 2, 8>(a, st);
-        if (rc != DM_OK) return rc;
-        a.q_begin = a.Q;
-        a.Q = Q;
-        return launch_conv<3, 4, 1, 1, 1, 8>(a, st);
-      }
-      return launch_conv<3, 2, 2, 2, 2, 8>(a, st);
-    }
-    if (Cout > 32 && Cout <= 36 && !(relu & 2)) return launch_conv<3, 1, 4, 1, 1, 8, 4>(a, st);   // DCN offset convs: 32 + 4
-    if (Cout > 32) return launch_conv<3, 1, 4, 2, 1, 8>(a, st);
-    return launch_conv<3, 1, 4, 1, 1, 8>(a, st);
-  }
-  if (Cout > 64) {
-    // A launch of few 128 x 128 tiles (the <= 100-RoI inference calls: 25-307 workgroups for 256 CUs) is a chain of K
-    // chunks per workgroup, and next to another stream's 3x3 launch -- the two RoI chains of a 100-detection call -- each
-    // chunk's 32 MFMAs per wave queue behind the neighbour's.  Up to 1.25 tiles per CU the launch takes 128 couts x 32
-    // pixels instead: four times the workgroups, 8 MFMAs per wave and chunk.  Same products in the same order (a
-    // 32-channel chunk walks its quad pairs in the order two 16-channel chunks do), so rows do not depend on the launch
-    // size (tests/test_ops_gpu.py).  Measured (profiles/r06_infer_notes.txt (5)): 100 / 64 / 32 / 16 detections
-    // 1.941 / 1.407 / 0.901 / 0.608 -> 1.879 / 1.360 / 0.884 / 0.584 ms; thresholds 100 / 160 / 320 / 640 / 1300 tiles:
-    // 1.923 / 1.896 / 1.879-1.891 / 1.883 / 1.887 at 100 detections; 128 x 64 tiles for the next 320-1300 and 64 x 64 tiles
-    // for the 64-cout build: inside the noise, not kept.  DM_CONV1_SMALL_WGS: the threshold in tiles (0: off), for A/B runs.
-    static const int small_env = getenv("DM_CONV1_SMALL_WGS") ? atoi(getenv("DM_CONV1_SMALL_WGS")) : -1;
-    const int small_wgs = small_env >= 0 ? small_env : (5 * dm_num_cus()) / 4;
-    // (the POST builds take the tiles the plain launch of the shape takes: the same products in the same order)
-    if (!(relu & 2) && !mask && dm_ceil_div(a.CoutP, 128) * dm_ceil_div(a.Q, 128) <= small_wgs)
-      return addend ? launch_conv<1, 4, 1, 1, 1, 32, 0, 0, 1>(a, st) : launch_conv<1, 4, 1, 1, 1, 32>(a, st);
-    return addend ? launch_conv<1, 2, 2, 2, 2, 16, 0, 0, 1>(a, st) : launch_conv<1, 2, 2, 2, 2, 16>(a, st);
-  }
-  if (Cout > 32) {
-    // 64 couts x 128 px as 4 waves of 32 x 64: 0.437 -> 0.379 ms on 576 -> 64 @56^2 x 128 RoIs, 0.098 -> 0.089 ms on
-    // 64 -> 64 x 256 (the other tilings tried: docs/HISTORY.md, round 3); one k order per output.
-    return addend ? launch_conv<1, 2, 2, 1, 2, 16, 0, 0, 1>(a, st) : launch_conv<1, 2, 2, 1, 2, 16>(a, st);
-  }
-  return addend ? launch_conv<1, 1, 4, 1, 1, 32, 0, 0, 1>(a, st) : launch_conv<1, 1, 4, 1, 1, 32>(a, st);
+  return rc != DM_OK ? rc : plan.copy_to(records);
 }
 
 // ---------------------------------------------------------------------------
@@ -1688,12 +1706,8 @@ extern "C" int dm_deconv2x2_fwd(const float* x, int NB, int C, int H, int W, con
   if (NB == 0) return DM_OK;
   const bool bf16x3 = (relu & 16) != 0;          // (ABI 28) w_packed is dm_deconv_pack_weight_bf16x3's layout
   ConvArgs a;
-  for (int s = 0; s < DM_MAX_SOURCES; ++s) { a.src[s] = nullptr; a.src_c[s] = 0; a.src_bs[s] = 0; }
-  a.src[0] = x; a.src_c[0] = C; a.src_bs[0] = (long long)C * H * W; a.num_srcs = 1;
-  a.KQ = bf16x3 ? packed_words_bf16x3(1, a.src_c) : packed_quads(1, a.src_c);
-  a.NB = NB; a.H = H; a.W = W; a.HW = H * W; a.Q = NB * H * W;
-  a.wq = w_packed; a.bias = bias; a.Cout = 4 * Cout; a.CoutP = dm_conv_packed_cout(4 * Cout);
-  a.relu = relu & ~16; a.out = out; a.out_ch_total = 0; a.out_ch_offset = 0; a.shuffle = Cout; a.q_begin = 0;
+  const int rc = conv_fill(a, &x, &C, nullptr, 1, NB, H, W, w_packed, bf16x3, bias, 4 * Cout, relu & ~16, out, 0, 0, Cout);
+  if (rc != DM_OK) return rc;
   if (bf16x3) return launch_conv<1, 2, 2, 1, 2, 16, 0, 1>(a, (hipStream_t)stream);
   return launch_conv<1, 2, 2, 2, 2, 16>(a, (hipStream_t)stream);
 }
@@ -1711,33 +1725,16 @@ extern "C" int dm_conv1x1_group_fwd(int count, const float* const* x, const int*
   const bool bf16x3 = (relu & 16) != 0;          // (ABI 28) every w_packed[i] is the bf16x3 layout
   if (NB == 0) return DM_OK;
   ConvGroup g;
-  int total = 0;
-  constexpr int TM = 64, TN = 128;
   for (int i = 0; i < 3; ++i) {
     const int j = i < count ? i : count - 1;          // unused slots repeat the last problem (never selected: end[] stops)
     if (!x[j] || !w_packed[j] || !out[j] || Cin[j] <= 0 || H[j] <= 0 || W[j] <= 0 || Cout[j] <= 0) return DM_ERR_INVALID_ARG;
     if ((long long)NB * H[j] * W[j] > 0x7fffffffLL) return DM_ERR_INVALID_ARG;
-    ConvArgs& a = g.a[i];
-    for (int s = 0; s < DM_MAX_SOURCES; ++s) { a.src[s] = nullptr; a.src_c[s] = 0; a.src_bs[s] = 0; }
-    a.src[0] = x[j]; a.src_c[0] = Cin[j]; a.src_bs[0] = (long long)Cin[j] * H[j] * W[j]; a.num_srcs = 1;
-    a.KQ = bf16x3 ? packed_words_bf16x3(1, a.src_c) : packed_quads(1, a.src_c);
-    a.NB = NB; a.H = H[j]; a.W = W[j]; a.HW = H[j] * W[j]; a.Q = NB * H[j] * W[j];
-    a.wq = w_packed[j]; a.bias = bias[j]; a.Cout = Cout[j]; a.CoutP = dm_conv_packed_cout(Cout[j]);
-    a.relu = relu & 1; a.out = out[j]; a.out_ch_total = Cout[j]; a.out_ch_offset = 0;
-    a.shuffle = 0; a.q_begin = 0; a.mask = nullptr; a.ws = nullptr; a.ksplit = 1;
-    a.off32 = ((long long)NB * a.src_bs[0] * 4 < (1LL << 32)) ? 1 : 0;
-    a.MT = dm_ceil_div(a.CoutP, TM);
-    a.Wp = 0; a.plane = TN;
-    if (i < count) total += a.MT * dm_ceil_div(a.Q, TN);
-    g.end[i] = total;
+    const int rc = conv_fill(g.a[i], &x[j], &Cin[j], nullptr, 1, NB, H[j], W[j], w_packed[j], bf16x3, bias[j], Cout[j], relu & 1,
+                             out[j], Cout[j], 0, 0);
+    if (rc != DM_OK) return rc;
   }
-  const size_t nwc = bf16x3 ? 6 : 16 / 4;
-  const size_t lds_bytes = 16 * (nwc * TM + nwc * TN);
-  if (bf16x3)
-    DM_LAUNCH((conv_igemm_group_kernel<1, 2, 2, 1, 2, 16, 1, 1>), dim3((unsigned)total), dim3(256), lds_bytes, (hipStream_t)stream, g);
-  else
-    DM_LAUNCH((conv_igemm_group_kernel<1, 2, 2, 1, 2, 16, 1>), dim3((unsigned)total), dim3(256), lds_bytes, (hipStream_t)stream, g);
-  return dm_check_launch();
+  if (bf16x3) return launch_group<1, 2, 2, 1, 2, 16, 1>(g, count, ConvSplit(), nullptr, (hipStream_t)stream);
+  return launch_group<1, 2, 2, 1, 2, 16>(g, count, ConvSplit(), nullptr, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -1751,9 +1748,12 @@ extern "C" int dm_conv1x1_group_fwd(int count, const float* const* x, const int*
 // With a K split, chunk c of a problem goes to split c / kchunks exactly as in a lone split launch of the same split count,
 // and the splits are added in index order by the same reduction arithmetic.  The 36-cout tail build (the DCN offset
 // convolutions: v_mfma_f32_4x4x1 rows) has no grouped form: 32 < Cout <= 36 with ksize 3 is refused.
-static int conv2d_group_setup(int count, const float* const* x, int NB, int H, int W, int Cin, int Cout, int ksize,
-                              const float* const* w_packed, const float* const* bias, int relu, float* const* out, int shuffle,
-                              ConvGroup& g) {
+// shuffle != 0: the grouped deconv 2x2/s2 instead (dm_deconv2x2_fwd's GEMM per problem: 4 * Cout packed columns of a 1x1,
+// 128 x 128 tiles, the pixel-shuffling epilogue; no workspace).
+static int conv2d_group_launch(int count, const float* const* x, int NB, int H, int W, int Cin, int Cout, int ksize,
+                               const float* const* w_packed, const float* const* bias, int relu, float* const* out, int shuffle,
+                               float* workspace, long long workspace_floats, dm_stream_t stream, ConvPlan* plan) {
+  if (ksize != 1 && ksize != 3) return DM_ERR_INVALID_ARG;
   if (count < 1 || count > 3 || !x || !w_packed || !out || NB < 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0)
     return DM_ERR_INVALID_ARG;
   if ((long long)NB * H * W > 0x7fffffffLL) return DM_ERR_INVALID_ARG;
@@ -1761,74 +1761,72 @@ static int conv2d_group_setup(int count, const float* const* x, int NB, int H, i
   if (relu & 16) return DM_ERR_UNSUPPORTED;        // exact fp32 only: the bf16x3 mode runs the per-stage path
   for (int i = 0; i < count && NB > 0; ++i)        // (NB == 0: empty tensors may have null addresses; nothing is read)
     if (!x[i] || !w_packed[i] || !out[i]) return DM_ERR_INVALID_ARG;
-  const int couts = shuffle ? 4 * Cout : Cout;
+  if (ksize == 3 && Cout > 32 && Cout <= 36) return DM_ERR_UNSUPPORTED;
+  if (workspace_floats < 0 || (workspace_floats > 0 && !workspace)) return DM_ERR_INVALID_ARG;
+  if (NB == 0) return DM_OK;
+  ConvGroup g;
+  const int flags = (relu & 1) | (shuffle ? 0 : conv_store_policy(NB, Cout, H, W));
   for (int i = 0; i < 3; ++i) {
     const int j = i < count ? i : count - 1;          // unused slots repeat the last problem (never selected: end[] stops)
-    ConvArgs& a = g.a[i];
-    for (int s = 0; s < DM_MAX_SOURCES; ++s) { a.src[s] = nullptr; a.src_c[s] = 0; a.src_bs[s] = 0; }
-    a.src[0] = x[j]; a.src_c[0] = Cin; a.src_bs[0] = (long long)Cin * H * W; a.num_srcs = 1;
-    a.KQ = packed_quads(1, a.src_c);
-    a.NB = NB; a.H = H; a.W = W; a.HW = H * W; a.Q = NB * H * W;
-    a.wq = w_packed[j]; a.bias = bias ? bias[j] : nullptr; a.Cout = couts; a.CoutP = dm_conv_packed_cout(couts);
-    a.relu = relu & 1;
-    if (!shuffle && (long long)NB * Cout * H * W * 4 > (192LL << 20)) a.relu |= 4;     // (conv2d_launch's store policy)
-    a.out = out[j]; a.out_ch_total = shuffle ? 0 : Cout; a.out_ch_offset = 0;
-    a.shuffle = shuffle; a.q_begin = 0; a.mask = nullptr; a.ws = nullptr; a.ws_floats = 0; a.ws_stride = 0;
-    a.ksplit = 1; a.kchunks = 0; a.want_split = 0;
-    a.off32 = ((long long)NB * a.src_bs[0] * 4 < (1LL << 32)) ? 1 : 0;
+    const int rc = conv_fill(g.a[i], &x[j], &Cin, nullptr, 1, NB, H, W, w_packed[j], false, bias ? bias[j] : nullptr,
+                             shuffle ? 4 * Cout : Cout, flags, out[j], shuffle ? 0 : Cout, 0, shuffle);
+    if (rc != DM_OK) return rc;
+    g.a[i].plan = plan;
   }
-  return DM_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (shuffle) return launch_group<1, 2, 2, 2, 2, 16>(g, count, ConvSplit(), nullptr, st);
+  const ConvSplit k = workspace ? group_split(count, NB, H, W, Cin, Cout, ksize, workspace_floats) : ConvSplit();
+  if (ksize == 3) {
+    if (Cout > 64) {
+      const int wgs = count * dm_ceil_div(g.a[0].CoutP, 128) * dm_ceil_div(g.a[0].Q, 128);
+      if (k.S < 2 && conv_small_launch(wgs, dm_num_cus())) return launch_group<3, 4, 1, 1, 1, 8>(g, count, ConvSplit(), nullptr, st);
+      return launch_group<3, 2, 2, 2, 2, 8>(g, count, k, workspace, st);
+    }
+    if (Cout > 32) return launch_group<3, 1, 4, 2, 1, 8>(g, count, k, workspace, st);
+    return launch_group<3, 1, 4, 1, 1, 8>(g, count, k, workspace, st);
+  }
+  if (Cout > 64) return launch_group<1, 2, 2, 2, 2, 16>(g, count, ConvSplit(), nullptr, st);
+  if (Cout > 32) return launch_group<1, 2, 2, 1, 2, 16>(g, count, ConvSplit(), nullptr, st);
+  return launch_group<1, 1, 4, 1, 1, 32>(g, count, ConvSplit(), nullptr, st);
 }
 
 extern "C" int dm_conv2d_group_splits(int count, int NB, int H, int W, int Cin, int Cout, int ksize, long long workspace_floats) {
   if (count < 1 || count > 3 || NB < 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (ksize != 1 && ksize != 3)) return -1;
-  return group_split_choice(count, NB, H, W, Cin, Cout, ksize, workspace_floats);
+  return group_split(count, NB, H, W, Cin, Cout, ksize, workspace_floats).S;
 }
 
 extern "C" long long dm_conv2d_group_splitk_floats(int count, int NB, int H, int W, int Cin, int Cout, int ksize) {
   if (count < 1 || count > 3 || NB <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || ksize != 3) return 0;
   const long long per = (long long)NB * Cout * H * W;
-  const int S = group_split_choice(count, NB, H, W, Cin, Cout, ksize, 8LL * count * per);
+  const int S = group_split(count, NB, H, W, Cin, Cout, ksize, 8LL * count * per).S;
   return S >= 2 ? (long long)S * count * per : 0;
 }
 
 extern "C" int dm_conv2d_group_fwd(int count, const float* const* x, int NB, int H, int W, int Cin, int Cout, int ksize,
                                    const float* const* w_packed, const float* const* bias, int relu, float* const* out,
                                    float* workspace, long long workspace_floats, dm_stream_t stream) {
-  if (ksize != 1 && ksize != 3) return DM_ERR_INVALID_ARG;
-  ConvGroup g;
-  const int rc = conv2d_group_setup(count, x, NB, H, W, Cin, Cout, ksize, w_packed, bias, relu, out, 0, g);
-  if (rc != DM_OK) return rc;
-  if (ksize == 3 && Cout > 32 && Cout <= 36) return DM_ERR_UNSUPPORTED;
-  if (workspace_floats < 0 || (workspace_floats > 0 && !workspace)) return DM_ERR_INVALID_ARG;
-  if (NB == 0) return DM_OK;
-  hipStream_t st = (hipStream_t)stream;
-  const int S = workspace ? group_split_choice(count, NB, H, W, Cin, Cout, ksize, workspace_floats) : 1;
-  if (ksize == 3) {
-    if (Cout > 64) {
-      const int cus = dm_num_cus();
-      const int wgs = count * dm_ceil_div(g.a[0].CoutP, 128) * dm_ceil_div(g.a[0].Q, 128);
-      if (S < 2 && (wgs * 10 <= cus * 7 || (wgs > cus && wgs * 20 <= cus * 29)))
-        return launch_group<3, 4, 1, 1, 1, 8>(g, count, 1, nullptr, st);
-      return launch_group<3, 2, 2, 2, 2, 8>(g, count, S, workspace, st);
-    }
-    if (Cout > 32) return launch_group<3, 1, 4, 2, 1, 8>(g, count, S, workspace, st);
-    return launch_group<3, 1, 4, 1, 1, 8>(g, count, S, workspace, st);
-  }
-  if (Cout > 64) return launch_group<1, 2, 2, 2, 2, 16>(g, count, 1, nullptr, st);
-  if (Cout > 32) return launch_group<1, 2, 2, 1, 2, 16>(g, count, 1, nullptr, st);
-  return launch_group<1, 1, 4, 1, 1, 32>(g, count, 1, nullptr, st);
+  return conv2d_group_launch(count, x, NB, H, W, Cin, Cout, ksize, w_packed, bias, relu, out, 0, workspace, workspace_floats, stream,
+                             nullptr);
 }
 
-// (added to ABI 28) 1 to 3 deconv 2x2/s2 problems of one shape in one launch: dm_deconv2x2_fwd's GEMM (4 * Cout packed
-// columns, 128 x 128 tiles, the pixel-shuffling epilogue) per problem, in its own range of the grid -- the same build on
-// the same operands, so each output has the bits of its own dm_deconv2x2_fwd.
+// (added to ABI 28) What dm_conv2d_group_fwd would launch for these host arguments: dm_conv2d_plan's recorder on the grouped
+// launcher, one record per problem (the header has the layout); no pointer below is read.
+extern "C" int dm_conv2d_group_plan(int count, int NB, int H, int W, int Cin, int Cout, int ksize, int relu,
+                                    long long workspace_floats, int* records, int max_records) {
+  if (!records || max_records < DM_CONV_GROUP_PLAN_MAX || workspace_floats < 0) return DM_ERR_INVALID_ARG;
+  static float dummy[4];
+  const float* in[3] = {dummy, dummy, dummy};
+  float* out[3] = {dummy, dummy, dummy};
+  ConvPlan plan = {DM_CONV_GROUP_PLAN_MAX};
+  const int rc = conv2d_group_launch(count, in, NB, H, W, Cin, Cout, ksize, in, nullptr, relu, out, 0,
+                                     workspace_floats > 0 ? dummy : nullptr, workspace_floats, nullptr, &plan);
+  return rc != DM_OK ? rc : plan.copy_to(records);
+}
+
+// (added to ABI 28) 1 to 3 deconv 2x2/s2 problems of one shape in one launch: dm_deconv2x2_fwd's GEMM per problem, in its
+// own range of the grid -- the same build on the same operands, so each output has the bits of its own dm_deconv2x2_fwd.
 extern "C" int dm_deconv2x2_group_fwd(int count, const float* const* x, int NB, int C, int H, int W,
                                       const float* const* w_packed, const float* const* bias, int Cout, int relu,
                                       float* const* out, dm_stream_t stream) {
-  ConvGroup g;
-  const int rc = conv2d_group_setup(count, x, NB, H, W, C, Cout, 1, w_packed, bias, relu & ~8, out, Cout, g);
-  if (rc != DM_OK) return rc;
-  if (NB == 0) return DM_OK;
-  return launch_group<1, 2, 2, 2, 2, 16>(g, count, 1, nullptr, (hipStream_t)stream);
+  return conv2d_group_launch(count, x, NB, H, W, C, Cout, 1, w_packed, bias, relu, out, Cout, nullptr, 0, stream, nullptr);
 }

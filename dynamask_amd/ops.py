@@ -2295,6 +2295,27 @@ def conv2d_group_splits(count, NB, H, W, cin, cout, ksize, workspace_floats):
                                             int(workspace_floats)))
 
 
+def conv2d_group_plan_raw(count, NB, H, W, cin, cout, ksize, flags=0, workspace_floats=0):
+    """dm_conv2d_group_plan: (return code, records).  The code is the number of records (one per problem of the one launch)
+    or the (negative) error the dm_conv2d_group_fwd call with these arguments would return.  Host only."""
+    consts = _abi.load()[1]
+    n, cap = consts['DM_CONV_PLAN_INTS'], consts['DM_CONV_GROUP_PLAN_MAX']
+    rec = (ctypes.c_int * (n * cap))(*([-1] * (n * cap)))
+    rc = lib().dm_conv2d_group_plan(int(count), int(NB), int(H), int(W), int(cin), int(cout), int(ksize), int(flags),
+                                    int(workspace_floats), rec, cap)
+    return rc, [dict(zip(CONV_PLAN_FIELDS, rec[i * n:(i + 1) * n])) for i in range(max(rc, 0))]
+
+
+def conv2d_group_plan(count, NB, H, W, cin, cout, ksize, relu=False, workspace_floats=0):
+    """The launch ``conv2d_group`` would make for ``count`` problems of this shape, as the launcher reports it: one dict
+    per problem with the keys CONV_PLAN_FIELDS (``grid_x``: the problem's share of the grid; the split is shared).
+    Raises where the call would fail."""
+    rc, recs = conv2d_group_plan_raw(count, NB, H, W, cin, cout, ksize, 1 if relu else 0, workspace_floats)
+    if rc < 0:
+        check(rc, 'dm_conv2d_group_plan')
+    return recs
+
+
 def conv2d_group(xs, w_packeds, biases, cout, ksize, relu=False, outs=None, split=None):
     """1 to 3 independent single-source "same" convolutions of one shape (+ bias, + ReLU) as ONE launch
     (dm_conv2d_group_fwd); several ``xs`` may be one tensor.  ``split`` (default: CONV_SPLITK): a 3x3 launch of few

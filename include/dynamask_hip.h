@@ -61,7 +61,7 @@ const char* dm_error_string(int code);
  * multi-row scatter (section K24); Cascade Mask R-CNN's stage-grouped convolutions / deconvolutions and stage step
  * (section K25); Hybrid Task Cascade's resize, post-activation addend and RoIAlign-add (section K26); Grid R-CNN's
  * GroupNorm, neighbour fusion, grouped 4x4 stride-2 deconvolution and box vote (section K27); the convolution launcher's
- * own report of its launches, dm_conv2d_plan (section K5/K6). */
+ * own report of its launches, dm_conv2d_plan (section K5/K6) and dm_conv2d_group_plan (section K25). */
 #define DM_ABI_VERSION 28 /* the one definition: dm_abi_version(), dm_build_info() and _lib.ABI_VERSION read it */
 int dm_abi_version(void);
 /* "libdynamask_hip abi=N arch=gfx950 compiler=<clang version> flags=<the product-wide flags of dynamask_amd/build.py>"
@@ -984,6 +984,13 @@ int dm_point_scatter_rows(const float* vals, const int* idx, int n, int C, int P
  * floats (S = 1: of dm_conv2d_fwd).  dm_conv2d_group_splitk_floats: the workspace that lets the call split as far as it
  * would (0: it would not).  NB == 0 enqueues nothing.
  *
+ * dm_conv2d_group_plan: the launch dm_conv2d_group_fwd would make for these HOST arguments, reported by the launcher itself
+ * as dm_conv2d_plan reports a lone call's (the same code with a recorder: nothing is launched, no device is needed).
+ * records: HOST array of max_records (>= DM_CONV_GROUP_PLAN_MAX) x DM_CONV_PLAN_INTS ints.  Returns the number of records --
+ * `count`, ONE PER PROBLEM of the one launch, in dm_conv2d_plan's layout: grid x is that problem's share of the grid, grid
+ * y / ksplit / kchunks the split all problems share, q_begin 0 -- 0 for NB = 0, or the error code the call would return,
+ * and then writes nothing.
+ *
  * dm_deconv2x2_group_fwd: count (1..3) dm_deconv2x2_fwd problems of one shape in one launch (weights of
  * dm_deconv_pack_weight; relu bit 0 ReLU, bit 4 DM_ERR_UNSUPPORTED); each out[i] has the bits of its dm_deconv2x2_fwd.
  *
@@ -1001,6 +1008,9 @@ long long dm_conv2d_group_splitk_floats(int count, int NB, int H, int W, int Cin
 int dm_conv2d_group_fwd(int count, const float* const* x, int NB, int H, int W, int Cin, int Cout, int ksize,
                         const float* const* w_packed, const float* const* bias, int relu, float* const* out, float* workspace,
                         long long workspace_floats, dm_stream_t stream);
+#define DM_CONV_GROUP_PLAN_MAX 3
+int dm_conv2d_group_plan(int count, int NB, int H, int W, int Cin, int Cout, int ksize, int relu, long long workspace_floats,
+                         int* records, int max_records);
 int dm_deconv2x2_group_fwd(int count, const float* const* x, int NB, int C, int H, int W, const float* const* w_packed,
                            const float* const* bias, int Cout, int relu, float* const* out, dm_stream_t stream);
 int dm_cascade_refine(const float* rois, const float* cls_score, const float* bbox_pred, int n, int num_classes,

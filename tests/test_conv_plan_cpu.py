@@ -285,3 +285,173 @@ def test_accepted_flag_bits_are_0_1_3_4():
         assert ops.conv2d_plan_raw([256], 7, 14, 14, 256, 3, flags)[0] == INVALID, flags
     one, = ops.conv2d_plan([256], 7, 14, 14, 256, 3, bf16x3=True)
     _is(one, dict(KS=3, WGM=2, WGN=2, WM=1, WN=2, CK=16, TAIL=0, PREC=1, POST=0), MAXPOS=1)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# dm_conv2d_group_plan: the grouped launcher (dm_conv2d_group_fwd) under the same recorder -- one record per problem of the
+# ONE launch: grid_x the problem's share of the grid, the split shared.  Worked out from dm_conv2d_group_fwd by hand.
+N_GREC = CONSTS['DM_CONV_GROUP_PLAN_MAX']
+
+
+def _gplan(count, NB, H, W, cin, cout, ksize, ws=0, **kw):
+    """The records of a grouped call, after the properties every grouped plan has: `count` equal records, no seam, the
+    split dm_conv2d_group_splits reports for the same arguments."""
+    recs = ops.conv2d_group_plan(count, NB, H, W, cin, cout, ksize, workspace_floats=ws, **kw)
+    assert len(recs) == count and all(r == recs[0] for r in recs)
+    S = _lib.lib().dm_conv2d_group_splits(count, NB, H, W, cin, cout, ksize, ws)
+    r = recs[0]
+    assert r['ksplit'] == r['grid_y'] == S and r['q_begin'] == 0 and r['Q'] == NB * H * W
+    assert (r['kchunks'] > 0) == (S > 1)
+    return r
+
+
+def test_group_record_room():
+    assert N_GREC == 3 and N_GREC >= N_REC
+    assert ops.conv2d_group_plan(3, 0, 14, 14, 256, 256, 3) == []          # NB = 0: DM_OK, nothing launched
+
+
+@needs_256
+def test_group_3x3_splits_on_the_grouped_workgroup_count():
+    L = _lib.lib()
+    per = 16 * 256 * 196              # 802816 floats = 3.21 MB per problem
+    # 16 RoIs, 256 -> 256 @14: Q = 3136 = 25 tiles of 128 px (24.5) x MT 2 = 50 workgroups per problem; plane 15 x 16 = 240:
+    # MAXPOS 1.  The grouped 128 x 128 build runs two per CU: 512 slots.  32 chunks of 8 channels, 32 / 4 = 8 splits at most.
+    # count 3: 150 workgroups, 512 / 150 = 3 splits; the model: 67.2 us x 2/3 = 44.8 saved, 5 + 4 x 3.21 MB x 0.25 = 8.2 paid:
+    # 36.6 us, above two splits' 33.6 - 7.4 = 26.2 -> 3 splits of ceil(32 / 3) = 11 chunks
+    assert L.dm_conv2d_group_splitk_floats(3, 16, 14, 14, 256, 256, 3) == 3 * 3 * per
+    _is(_gplan(3, 16, 14, 14, 256, 256, 3, ws=9 * per), B128, MAXPOS=1, ksplit=3, kchunks=11, grid_x=50, grid_y=3, nontemporal=0)
+    assert _gplan(3, 16, 14, 14, 256, 256, 3, ws=1 << 40) == _gplan(3, 16, 14, 14, 256, 256, 3, ws=9 * per)
+    # one float less: room for two splits per problem -> 2 splits of 16
+    _is(_gplan(3, 16, 14, 14, 256, 256, 3, ws=9 * per - 1), B128, ksplit=2, kchunks=16, grid_x=50, grid_y=2)
+    # count 1: 50 workgroups, min(8, 512 / 50) = 8; the gain grows up to 8 (58.8 - 12.2 = 46.6 us): 8 splits of 4
+    assert L.dm_conv2d_group_splitk_floats(1, 16, 14, 14, 256, 256, 3) == 8 * per
+    _is(_gplan(1, 16, 14, 14, 256, 256, 3, ws=8 * per), B128, MAXPOS=1, ksplit=8, kchunks=4, grid_x=50, grid_y=8)
+    # no workspace, or one too small for two splits: no split, and 150 (50) x 10 <= 1792 -> the 128 x 32 build, 98 tiles of
+    # 32 px x MT 2 = 196 workgroups per problem, plane (3 + 1 + 4) x 16 = 128: MAXPOS 1
+    for count, ws in ((3, 0), (1, 0), (3, 6 * per - 1), (1, 2 * per - 1)):
+        _is(_gplan(count, 16, 14, 14, 256, 256, 3, ws=ws), B32, MAXPOS=1, ksplit=1, kchunks=0, grid_x=196, grid_y=1)
+    # a grid that fills the slots does not split: NB 100, count 3: 3 x 308 = 924 >= 512
+    assert L.dm_conv2d_group_splitk_floats(3, 100, 14, 14, 256, 256, 3) == 0
+    _is(_gplan(3, 100, 14, 14, 256, 256, 3, ws=1 << 40), B128, ksplit=1, grid_x=308)
+
+
+@needs_256
+def test_group_small_launch_rule_both_clauses():
+    # count x MT x tiles workgroups against 256 CUs.  First clause: wgs x 10 <= 1792 <=> wgs <= 179.
+    # count 1 (the lone launch's numbers): NB 58: 89 tiles, 178 -> 128 x 32 (356 tiles of 32 px x 2); NB 59: 91 tiles, 182 -> 128 x 128
+    _is(_gplan(1, 58, 14, 14, 256, 256, 3), B32, grid_x=712)
+    _is(_gplan(1, 59, 14, 14, 256, 256, 3), B128, grid_x=182)
+    # count 3: NB 18: 3528 px = 28 tiles (27.6), 3 x 56 = 168 -> 128 x 32 (111 tiles x 2); NB 19: 3724 px = 30 tiles, 180 -> 128 x 128
+    _is(_gplan(3, 18, 14, 14, 256, 256, 3), B32, grid_x=222)
+    _is(_gplan(3, 19, 14, 14, 256, 256, 3), B128, grid_x=60)
+    # second clause: 256 < wgs and wgs x 20 <= 7424 <=> wgs <= 371.  count 1: NB 100: 308 -> 128 x 32 (613 x 2); NB 122: 374 -> 128 x 128
+    _is(_gplan(1, 100, 14, 14, 256, 256, 3), B32, grid_x=1226)
+    _is(_gplan(1, 122, 14, 14, 256, 256, 3), B128, grid_x=374)
+    # count 3: NB 39: 7644 px = 60 tiles (59.7), 360 -> 128 x 32 (239 tiles x 2); NB 40: 7840 px = 62 tiles (61.25), 372 -> 128 x 128
+    _is(_gplan(3, 39, 14, 14, 256, 256, 3), B32, grid_x=478)
+    _is(_gplan(3, 40, 14, 14, 256, 256, 3), B128, grid_x=124)
+    # between the clauses (179 < wgs <= 256): 128 x 128.  count 2, NB 25: 4900 px = 39 tiles (38.3), 156 -> 128 x 32;
+    # NB 32: 6272 px = 49 tiles, 196 -> 128 x 128
+    _is(_gplan(2, 25, 14, 14, 256, 256, 3), B32, grid_x=2 * 154)
+    _is(_gplan(2, 32, 14, 14, 256, 256, 3), B128, grid_x=98)
+
+
+@needs_256
+def test_group_3x3_builds_by_cout_and_staged_depth():
+    for cout, build in ((37, B64), (64, B64), (1, B32C), (32, B32C)):
+        _is(_gplan(2, 3, 14, 14, 20, cout, 3), build, MAXPOS=1, grid_x=5, Q=588)
+        _is(_gplan(2, 3, 14, 14, 20, cout, 3, ws=1 << 40), build, ksplit=1)         # 3 chunks: 3 / 4 = 0 splits
+    # the 32 + 4 tail build has no grouped form
+    for cout in (33, 34, 35, 36):
+        assert ops.conv2d_group_plan_raw(2, 3, 14, 14, 20, cout, 3) == (UNSUPPORTED, [])
+        _is(_gplan(2, 3, 14, 14, 20, cout, 1), P1_64)
+    # staged depth (the planes of test_3x3_builds_by_cout_and_staged_depth): 14 x 14: 240 -> 1; 56 x 56: 464 -> 2; 5 x 120: 854 -> 4
+    for (H, W), mp, tiles in (((14, 14), 1, 4), ((56, 56), 2, 49), ((5, 120), 4, 10)):
+        for cout, build in ((64, B64), (32, B32C)):
+            _is(_gplan(3, 2, H, W, 20, cout, 3), build, MAXPOS=mp, grid_x=tiles)
+    # the 128 x 128 build on 28 x 28 maps: 10 rows of 30 = 300 -> MAXPOS 2; 16 x 784 px = 98 tiles x MT 2, 3 x 196 = 588 workgroups
+    _is(_gplan(3, 16, 28, 28, 256, 256, 3), B128, MAXPOS=2, grid_x=196)
+    # the 128 x 32 build (few workgroups): 9 x 112: (1 + 1 + 4) x 114 = 684 -> 4; 2016 px = 63 tiles x MT 1
+    _is(_gplan(1, 2, 9, 112, 12, 65, 3), B32, MAXPOS=4, grid_x=63)
+    # 64-cout launches split on three slots per CU (768): 256 -> 64 @14 x 16 RoIs, count 3: 3 x 25 = 75 workgroups, min(8, 10, 32 / 4)
+    # = 8 splits; per = 16 x 64 x 196 = 200704 floats = 0.80 MB: the gain grows up to 8 (58.8 - 5 - 9 x 0.2 = 52.0 us)
+    _is(_gplan(3, 16, 14, 14, 256, 64, 3, ws=1 << 40), B64, ksplit=8, kchunks=4, grid_x=25, grid_y=8)
+    assert _lib.lib().dm_conv2d_group_splitk_floats(3, 16, 14, 14, 256, 64, 3) == 8 * 3 * 200704
+
+
+@needs_256
+def test_group_128x32_plane_is_held_to_64_kb():
+    # The 128 x 32 build keeps an A image of 9 x 2 x 128 words (36 KB) beside the plane's 32 bytes per position: more than 896
+    # positions need more than 64 KB.  The lone launcher raises that build's limit to 80 KB (test_maps_168_wide_...); the
+    # grouped launcher refuses.  1 x 147: (1 + 1 + 2 x 2) x 149 = 894 positions; 1 x 148: 6 x 150 = 900; 1 x 168: 1020.
+    _is(_gplan(2, 2, 1, 147, 8, 256, 3), B32, MAXPOS=4, grid_x=2 * 10)           # 294 px = 10 tiles of 32 (9.2)
+    for W in (148, 168):
+        assert ops.conv2d_group_plan_raw(2, 2, 1, W, 8, 256, 3) == (UNSUPPORTED, [])
+        assert ops.conv2d_plan_raw([8], 2, 1, W, 256, 3)[0] == 1
+    # the 128 x 128 build of the same maps has no A image: 2 x 16 x 1020 bytes
+    _is(_gplan(3, 150, 1, 168, 8, 256, 3), B128, MAXPOS=4, grid_x=394)
+    assert ops.conv2d_group_plan_raw(3, 150, 1, 169, 8, 256, 3) == (UNSUPPORTED, [])
+
+
+@needs_256
+def test_group_1x1_builds_never_split():
+    # 3 x 196 = 588 px = 5 tiles of 128; Cout 130 -> CoutP 160 -> MT 2 of the 128-cout build; no small build in a grouped launch
+    for ws in (0, 1 << 40):
+        _is(_gplan(2, 3, 14, 14, 72, 130, 1, ws=ws), P1_128, MAXPOS=1, ksplit=1, kchunks=0, grid_x=10, grid_y=1)
+        _is(_gplan(3, 3, 14, 14, 72, 65, 1, ws=ws), P1_128, grid_x=5)
+        for cout, build in ((33, P1_64), (64, P1_64), (1, P1_32), (32, P1_32)):
+            _is(_gplan(3, 3, 14, 14, 72, cout, 1, ws=ws), build, MAXPOS=1, ksplit=1, kchunks=0, grid_x=5, grid_y=1)
+        _is(_gplan(1, 16, 14, 14, 256, 256, 1, ws=ws), P1_128, ksplit=1, grid_x=50)
+    assert _lib.lib().dm_conv2d_group_splitk_floats(1, 16, 14, 14, 256, 256, 1) == 0
+
+
+@needs_256
+def test_group_nontemporal_bit_above_192_mb_of_output():
+    # per problem, as test_nontemporal_bit_above_192_mb_of_output: 64 x 56 x 56 x NB 250 below, NB 251 above
+    assert _gplan(2, 250, 56, 56, 8, 64, 1)['nontemporal'] == 0
+    assert _gplan(2, 251, 56, 56, 8, 64, 1)['nontemporal'] == 1
+    assert _gplan(2, 251, 56, 56, 8, 64, 3)['nontemporal'] == 1
+
+
+def _graw(count=3, NB=16, H=14, W=14, cin=256, cout=256, ksize=3, flags=0, ws=0, cap=N_GREC, null=False):
+    """dm_conv2d_group_plan straight through ctypes, the record array filled with a canary."""
+    rec = (ctypes.c_int * (N_INTS * N_GREC))(*([-77] * (N_INTS * N_GREC)))
+    rc = _lib.lib().dm_conv2d_group_plan(count, NB, H, W, cin, cout, ksize, flags, ws, None if null else rec, cap)
+    return rc, list(rec)
+
+
+GROUP_ERRORS = [
+    ('no problem', dict(count=0), INVALID),
+    ('four problems', dict(count=4), INVALID),
+    ('NB < 0', dict(NB=-1), INVALID),
+    ('H = 0', dict(H=0), INVALID),
+    ('W = 0', dict(W=0), INVALID),
+    ('Cin = 0', dict(cin=0), INVALID),
+    ('Cout = 0', dict(cout=0), INVALID),
+    ('ksize 2', dict(ksize=2), INVALID),
+    ('ksize 5', dict(ksize=5), INVALID),
+    ('2^31 pixels', dict(NB=1 << 20, H=64, W=32), INVALID),
+    ('accumulate', dict(flags=2), INVALID),
+    ('flag bit 2', dict(flags=4), INVALID),
+    ('flag bit 5', dict(flags=32), INVALID),
+    ('bf16x3', dict(flags=16), UNSUPPORTED),
+    ('bf16x3 on 1x1', dict(flags=17, ksize=1), UNSUPPORTED),
+    ('the tail build', dict(cout=34), UNSUPPORTED),
+    ('negative workspace', dict(ws=-1), INVALID),
+    ('map 169 wide', dict(W=169), UNSUPPORTED),
+    ('128 x 32 plane above 64 KB', dict(NB=2, H=1, W=168), UNSUPPORTED),
+    ('64 couts on 1x1 maps', dict(H=1, W=1, cout=64), UNSUPPORTED),
+    ('two records of room', dict(cap=2), INVALID),
+    ('null record array', dict(null=True), INVALID),
+]
+
+
+@pytest.mark.parametrize('name,change,code', GROUP_ERRORS, ids=[e[0] for e in GROUP_ERRORS])
+def test_group_error_paths_return_their_code_and_write_nothing(name, change, code):
+    ok, rec = _graw()
+    assert ok == 3 and rec[0] == 3 and -77 not in rec                       # the base call is a valid one
+    ok, rec = _graw(count=1, flags=1 | 8)                                    # (ReLU, and the ignored stream hint)
+    assert ok == 1 and rec[N_INTS:] == [-77] * (2 * N_INTS)
+    rc, rec = _graw(**change)
+    assert rc == code, name
+    assert rec == [-77] * (N_INTS * N_GREC), 'a partial record was left behind'

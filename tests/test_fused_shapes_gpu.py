@@ -413,6 +413,30 @@ def test_conv1x1_group_sweep_equals_its_own_launches_and_matches_f64(ops, gi, NB
             assert_close_via_f64(g_, r32, r64, f'group {gi} problem {i} NB={NB} relu={relu}')
 
 
+@pytest.mark.parametrize('precision', ['fp32', 'bf16x3'])
+def test_conv1x1_group_on_the_shared_launcher_equals_lone_conv2d(ops, precision):
+    """dm_conv1x1_group_fwd goes through the grouped launcher every grouped entry point uses (its geometry, LDS size and
+    grid ranges are no longer set up by hand): for 1, 2 and 3 problems of different shapes -- Cin that is no multiple of
+    the 16-channel chunk, Cout of one 64-cout tile and a bit, of exactly one, and of three (the last ragged), maps of
+    less and more than one 128-pixel tile -- every output has the bits of its own lone conv2d, in the exact and in the
+    bf16x3 layout.  The sweep above already holds the exact layout to this; what this test adds is the bf16x3 layout
+    (held elsewhere for three problems of one image only) and every problem leading a group."""
+    NB, probs = 3, [(20, 33, 7, 9), (16, 64, 14, 14), (40, 130, 3, 5)]
+    gen = _g(8200)
+    xs = [_dev(torch.randn(NB, cin, h, w, generator=gen)) for cin, _, h, w in probs]
+    wq = [ops.pack_conv_weight(_dev(torch.randn(co, cin, 1, 1, generator=gen) / cin ** 0.5), precision=precision) for cin, co, _, _ in probs]
+    bs = [_dev(torch.randn(co, generator=gen)) for _, co, _, _ in probs]
+    couts = [co for _, co, _, _ in probs]
+    lone = [ops.conv2d(x, q, b, co, 1, relu=True) for x, q, b, co in zip(xs, wq, bs, couts)]
+    for k in (1, 2, 3):
+        for first in range(0, 3 - k + 1):                       # every problem leads a group once
+            sl = slice(first, first + k)
+            got = ops.conv1x1_group(xs[sl], wq[sl], bs[sl], couts[sl], relu=True)
+            assert len(got) == k
+            for g_, r_ in zip(got, lone[sl]):
+                assert torch.equal(g_, r_), (precision, k, first)
+
+
 def test_conv1x1_group_refuses_bad_counts_and_oversized_maps(ops):
     """The entry point's own refusals (ops.conv1x1_group asserts 1 <= count <= 3 before it gets there): nothing written."""
     from dynamask_amd._lib import lib
