@@ -9,7 +9,10 @@ connected layers run on ``dm_fc_fwd`` (fp32 MFMA GEMM with split-K over the long
 Training (second half): ``get_targets`` (bbox2delta = ``dm_bbox_encode``),
 ``loss`` (softmax CE + accuracy = ``dm_softmax_ce_fwd_bwd``, L1 on the positive rows' class
 columns = ``dm_l1_loss_fwd_bwd``) and the backward of the FC stack (``BBoxHeadFn``: data and
-weight gradients as fp32-MFMA GEMMs through the implicit-GEMM kernels on [N, C, 1, 1] tensors)."""
+weight gradients as fp32-MFMA GEMMs through the implicit-GEMM kernels on [N, C, 1, 1] tensors).
+``DoubleConvFCBBoxHead`` (roi_heads/bbox_heads/double_bbox_head.py, inference): the regression from a convolution branch
+-- ``BasicResBlock``, ResNet ``Bottleneck``s with eval-mode BatchNorm folded into the exact-fp32 convolutions (``fold_bn``),
+a global average pool (``dm_global_avg_pool_fwd``) -- the classification from fully connected layers."""
 import numpy as np
 import torch
 import torch.nn as nn
@@ -200,6 +203,205 @@ class Shared2FCBBoxHead(nn.Module):
             return bboxes, scores
         return multiclass_nms(bboxes, scores, cfg.score_thr, cfg.nms, cfg.max_per_img)
 
+
+
+# ---------------------------------------------------------------- Double-Head R-CNN (bbox_heads/double_bbox_head.py)
+def fold_bn(pairs):
+    """Eval-mode BatchNorm folded into the convolution in front of it: ``pairs`` = [(conv weight [Cout, Cin_i, k, k], bn),
+    ...] -> (w' [Cout, sum Cin_i, k, k], b' [Cout]) with, per pair, s = gamma / sqrt(running_var + eps),
+    w' = w * s[:, None, None, None], b' = beta - running_mean * s.  Several pairs are the summed outputs of convolutions
+    of different inputs as ONE convolution of their concatenation: the weights side by side along Cin, the biases added.
+    All of it in float64, rounded once to float32."""
+    ws, b = [], None
+    for w, bn in pairs:
+        s = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
+        ws.append(w.detach().double() * s[:, None, None, None])
+        bi = bn.bias.detach().double() - bn.running_mean.detach().double() * s
+        b = bi if b is None else b + bi
+    return torch.cat(ws, 1).float().contiguous(), b.float().contiguous()
+
+
+class _FoldedConv:
+    """Packed folded weights + bias of one launch, cached like ``_Packed`` caches packed weights: made again when any of
+    the convolution weights, BatchNorm parameters or running statistics changes (``load_state_dict`` copies in place and
+    moves their versions; a move to another device changes their addresses)."""
+
+    def __init__(self, pairs, src_channels):
+        from .mask_heads import _Packed
+        self.modules, self.src_channels = pairs, list(src_channels)      # [(convolution holder, BatchNorm holder), ...]
+        self._pk = _Packed()
+
+    def _pairs(self):
+        return [(conv.weight, bn) for conv, bn in self.modules]
+
+    def _tensors(self):
+        return [t for w, bn in self._pairs() for t in (w, bn.weight, bn.bias, bn.running_mean, bn.running_var)]
+
+    def folded(self):
+        """(w', b') in torch's layout, on the parameters' device (CPU included)."""
+        return self._pk.get_multi('fold', self._tensors(), lambda: fold_bn(self._pairs()))
+
+    def packed(self):
+        """(packed w', b') for ops.conv2d: always the exact fp32 layout, whatever the precision mode."""
+        def make():
+            w, b = self.folded()
+            return ops.pack_conv_weight(w, src_channels=self.src_channels), b
+        return self._pk.get_multi('pack', self._tensors(), make)
+
+
+def _conv_weight(cout, cin, k):
+    """nn.Conv2d(bias=False) parameter holder: the key is ``weight`` alone."""
+    from .mask_heads import _Conv
+    return _Conv(cin, cout, k, bias=False)
+
+
+class BNConvModule(nn.Module):
+    """mmcv ConvModule(bias=False, norm_cfg=dict(type='BN')): keys ``conv.weight``, ``bn.*``.  A parameter holder: the
+    block that owns it folds the BatchNorm and launches."""
+
+    def __init__(self, in_channels, out_channels, kernel_size):
+        super().__init__()
+        from .roi_head import _BN
+        self.conv = _conv_weight(out_channels, in_channels, kernel_size)
+        self.bn = _BN(out_channels)
+
+
+class BasicResBlock(nn.Module):
+    """double_bbox_head.py:9-68 in eval mode: relu(bn(conv2(relu(bn(conv1 3x3(x))))) + bn(conv_identity(x))) as two
+    launches -- conv1 + ReLU, then ONE two-source 1x1 convolution of [conv1 output, x] by [W2' | Wid'] with bias
+    b2' + bid' and ReLU."""
+
+    def __init__(self, in_channels, out_channels):
+        super().__init__()
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.conv1 = BNConvModule(in_channels, in_channels, 3)
+        self.conv2 = BNConvModule(in_channels, out_channels, 1)
+        self.conv_identity = BNConvModule(in_channels, out_channels, 1)
+        self._f1 = _FoldedConv([(self.conv1.conv, self.conv1.bn)], [in_channels])
+        self._f2 = _FoldedConv([(self.conv2.conv, self.conv2.bn), (self.conv_identity.conv, self.conv_identity.bn)],
+                               [in_channels, in_channels])
+
+    def forward(self, x):
+        w1, b1 = self._f1.packed()
+        h = ops.conv2d(x, w1, b1, self.in_channels, 3, relu=True)
+        w2, b2 = self._f2.packed()
+        return ops.conv2d([h, x], w2, b2, self.out_channels, 1, relu=True)
+
+
+class Bottleneck(nn.Module):
+    """backbones/resnet.py:95-300 (stride 1, no downsample, style 'pytorch') in eval mode; keys ``conv{1,2,3}.weight``,
+    ``bn{1,2,3}.*``.  Three launches: 1x1 + ReLU, 3x3 + ReLU, then the 1x1 back to ``inplanes`` with the ``accumulate |
+    ReLU`` epilogue -- relu(x + conv + bias), the residual sum before the activation -- written IN PLACE into ``x``."""
+    expansion = 4
+
+    def __init__(self, inplanes, planes):
+        super().__init__()
+        from .roi_head import _BN
+        if inplanes != planes * self.expansion:
+            raise NotImplementedError('Bottleneck: no downsample path (DoubleConvFCBBoxHead: planes = inplanes / 4)')
+        self.inplanes, self.planes = inplanes, planes
+        self.conv1, self.bn1 = _conv_weight(planes, inplanes, 1), _BN(planes)
+        self.conv2, self.bn2 = _conv_weight(planes, planes, 3), _BN(planes)
+        self.conv3, self.bn3 = _conv_weight(inplanes, planes, 1), _BN(inplanes)
+        self._f = [_FoldedConv([(c, bn)], [c.in_channels])
+                   for c, bn in ((self.conv1, self.bn1), (self.conv2, self.bn2), (self.conv3, self.bn3))]
+
+    def forward(self, x):
+        """``x`` [N, inplanes, H, W] is overwritten with the block's output and returned."""
+        (w1, b1), (w2, b2), (w3, b3) = (f.packed() for f in self._f)
+        h = ops.conv2d(x, w1, b1, self.planes, 1, relu=True)
+        h = ops.conv2d(h, w2, b2, self.planes, 3, relu=True)
+        return ops.conv2d(h, w3, b3, self.inplanes, 1, relu=True, out=x, accumulate=True)
+
+
+@HEADS.register_module()
+class DoubleConvFCBBoxHead(nn.Module):
+    """``DoubleConvFCBBoxHead`` -- bbox_heads/double_bbox_head.py:71-172 on BBoxHead (bbox_head.py:13-60), inference: the
+    regression from a convolution branch (BasicResBlock, ``num_convs`` Bottlenecks, global average pool, ``fc_reg``) on the
+    RoI features of the enlarged box, the classification from ``num_fcs`` fully connected layers on the plain ones.
+    ``state_dict`` keys as the reference's.  BatchNorm runs in eval mode, folded into the convolutions (``fold_bn``); every
+    launch is exact fp32 in every precision mode.  Training is not built."""
+
+    def __init__(self, num_convs=0, num_fcs=0, conv_out_channels=1024, fc_out_channels=1024, conv_cfg=None,
+                 norm_cfg=dict(type='BN'), with_avg_pool=True, with_cls=True, with_reg=True, roi_feat_size=7, in_channels=256,
+                 num_classes=80, bbox_coder=dict(type='DeltaXYWHBBoxCoder', target_means=[0., 0., 0., 0.],
+                                                 target_stds=[0.1, 0.1, 0.2, 0.2]),
+                 reg_class_agnostic=False, reg_decoded_bbox=False, loss_cls=None, loss_bbox=None):
+        super().__init__()
+        assert with_avg_pool
+        assert num_convs > 0
+        assert num_fcs > 0
+        assert with_cls or with_reg           # (bbox_head.py:29; both branches are built whatever the flags say, as there)
+        if conv_cfg is not None:
+            raise NotImplementedError('DoubleConvFCBBoxHead: conv_cfg is None in configs/double_heads')
+        if not isinstance(norm_cfg, dict) or norm_cfg.get('type') != 'BN' or set(norm_cfg) - {'type', 'requires_grad'}:
+            raise NotImplementedError("DoubleConvFCBBoxHead: norm_cfg is dict(type='BN') in configs/double_heads (the "
+                                      'eval-mode fold is BatchNorm\'s)')
+        if reg_decoded_bbox:
+            raise NotImplementedError('reg_decoded_bbox=False in configs/double_heads')
+        if conv_out_channels % 4 != 0:
+            raise ValueError('conv_out_channels must be a multiple of 4 (Bottleneck planes = conv_out_channels / 4)')
+        self.with_avg_pool, self.with_cls, self.with_reg = True, with_cls, with_reg
+        self.roi_feat_size = (roi_feat_size, roi_feat_size) if isinstance(roi_feat_size, int) else tuple(roi_feat_size)
+        self.roi_feat_area = self.roi_feat_size[0] * self.roi_feat_size[1]
+        self.in_channels, self.num_classes, self.reg_class_agnostic = in_channels, num_classes, reg_class_agnostic
+        self.num_convs, self.num_fcs = num_convs, num_fcs
+        self.conv_out_channels, self.fc_out_channels = conv_out_channels, fc_out_channels
+        self.conv_cfg, self.norm_cfg = conv_cfg, norm_cfg
+        self.bbox_coder = build_bbox_coder(bbox_coder)
+        self.reg_decoded_bbox = reg_decoded_bbox
+        self.loss_cls_cfg, self.loss_bbox_cfg = loss_cls, loss_bbox
+        from .registry import build_loss
+        self.loss_cls = build_loss(loss_cls) if loss_cls is not None else None
+        self.loss_bbox = build_loss(loss_bbox) if loss_bbox is not None else None
+        self.res_block = BasicResBlock(in_channels, conv_out_channels)
+        self.conv_branch = nn.ModuleList([Bottleneck(conv_out_channels, conv_out_channels // 4) for _ in range(num_convs)])
+        self.fc_branch = nn.ModuleList([_FC(in_channels * self.roi_feat_area if i == 0 else fc_out_channels, fc_out_channels)
+                                        for i in range(num_fcs)])
+        self.fc_reg = _FC(conv_out_channels, 4 if reg_class_agnostic else 4 * num_classes)
+        self.fc_cls = _FC(fc_out_channels, num_classes + 1)
+
+    def init_weights(self):
+        """double_bbox_head.py:143-150 (the convolutions keep their constructors' initialisation)."""
+        nn.init.normal_(self.fc_cls.weight, 0, 0.01)
+        nn.init.constant_(self.fc_cls.bias, 0)
+        nn.init.normal_(self.fc_reg.weight, 0, 0.001)
+        nn.init.constant_(self.fc_reg.bias, 0)
+        for fc in self.fc_branch:
+            nn.init.xavier_uniform_(fc.weight)
+            nn.init.constant_(fc.bias, 0)
+
+    def conv_features(self, x_reg):
+        """res_block + conv_branch + the average pool of double_bbox_head.py:154-162 -> [N, conv_out_channels]."""
+        if tuple(x_reg.shape[2:]) != self.roi_feat_size:
+            raise ValueError(f'x_reg: {self.roi_feat_size} RoI features expected (AvgPool2d(roi_feat_size) then gives one '
+                             f'value per channel), got {tuple(x_reg.shape[2:])}')
+        x = self.res_block(x_reg.contiguous())
+        for block in self.conv_branch:
+            x = block(x)
+        return ops.global_avg_pool(x)
+
+    def forward(self, x_cls, x_reg):
+        """double_bbox_head.py:152-172 -> (cls_score, bbox_pred)."""
+        if torch.is_grad_enabled() and (x_cls.requires_grad or x_reg.requires_grad
+                                        or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError('DoubleConvFCBBoxHead: training (BatchNorm in train mode, the backward of the conv '
+                                      'branch) is not built; run inference under torch.no_grad()')
+        if x_cls.shape[0] != x_reg.shape[0]:
+            raise ValueError(f'x_cls has {x_cls.shape[0]} RoIs, x_reg {x_reg.shape[0]}')
+        if x_cls.shape[0] == 0:         # no RoI: nothing is launched
+            return (x_cls.new_zeros((0, self.fc_cls.out_features)), x_cls.new_zeros((0, self.fc_reg.out_features)))
+        bbox_pred = self.fc_reg.run(self.conv_features(x_reg))
+        x_fc = x_cls.flatten(1)
+        for fc in self.fc_branch:
+            x_fc = fc.run(x_fc, relu=True)
+        return self.fc_cls.run(x_fc), bbox_pred
+
+    # get_bboxes, the targets and the loss are BBoxHead's: the code Shared2FCBBoxHead runs
+    get_bboxes = Shared2FCBBoxHead.get_bboxes
+    _get_target_single = Shared2FCBBoxHead._get_target_single
+    get_targets = Shared2FCBBoxHead.get_targets
+    loss = Shared2FCBBoxHead.loss
 
 
 class BBoxHeadFn(torch.autograd.Function):

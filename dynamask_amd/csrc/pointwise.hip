@@ -1274,3 +1274,35 @@ extern "C" int dm_pixel_unshuffle2x(const float* in, int NB, int C, int H, int W
   DM_LAUNCH(unshuffle2x_kernel, dim3((unsigned)dm_ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, in, NB, C, H, W, out);
   return dm_check_launch();
 }
+
+// (K28) Double-Head R-CNN: nn.AvgPool2d(roi_feat_size) on a map of exactly that size = the mean of every [H, W] plane.
+// One wave per plane: lane l adds the elements l, l + 64, ... in that order, a xor butterfly adds the 64 partial sums, one
+// division by HW.  The order depends on HW alone, so a RoI's bits do not depend on the other RoIs of the call.
+namespace {
+__global__ __launch_bounds__(256) void global_avg_pool_kernel(const float* __restrict__ x, long long rows, int HW,
+                                                              float* __restrict__ out) {
+  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;       // (whole waves leave: the shuffles below have all their lanes)
+  const int lane = threadIdx.x & 63;
+  const float* p = x + row * HW;
+  float s = 0.f;
+  for (int i = lane; i < HW; i += 64) s += p[i];
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+  if (lane == 0) out[row] = s / (float)HW;
+}
+}  // namespace
+
+extern "C" int dm_global_avg_pool_supported(int N, int C, int HW) {
+  if (N < 0 || C < 1 || HW < 1 || HW > (1 << 24)) return 0;
+  return ((long long)N * C <= 0x7fffffffLL) ? 1 : 0;        // (a quarter of the rows is the grid)
+}
+
+extern "C" int dm_global_avg_pool_fwd(const float* x, int N, int C, int HW, float* out, dm_stream_t stream) {
+  if (!dm_global_avg_pool_supported(N, C, HW)) return DM_ERR_UNSUPPORTED;
+  if (N == 0) return DM_OK;
+  if (!x || !out) return DM_ERR_INVALID_ARG;
+  const long long rows = (long long)N * C;
+  DM_LAUNCH(global_avg_pool_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, rows, HW, out);
+  return dm_check_launch();
+}

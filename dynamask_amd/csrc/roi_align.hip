@@ -25,6 +25,7 @@ struct RoiArgs {
   const float* rois;
   int N, P, sr;
   float finest;
+  float rsf = 1.0f;    // forward: RoIs rescaled about their centres by this factor AFTER the level map (dm_roi_align_scaled_fwd)
   float* out;          // fwd: output; bwd: unused
   const float* gout;   // bwd: grad of output
   int32_t* levels;
@@ -114,6 +115,18 @@ __device__ __forceinline__ int roi_level(float x1, float y1, float x2, float y2,
   for (int k = 1; k < 8; ++k)
     if (k < L && t >= __uint_as_float(T[k])) lvl = k;
   return lvl;
+}
+
+// base_roi_extractor.py:57-80 (roi_rescale) in its float32 order: cx = (x1 + x2) * 0.5, w = x2 - x1, new_w = w * f,
+// x1' = cx - new_w * 0.5, x2' = cx + new_w * 0.5.  The products by 0.5 are exact, so a contraction of the last step to an
+// fma rounds as the separate operations do: the bits of the host-side rescale.
+__device__ __forceinline__ void roi_rescale(float f, float& x1, float& y1, float& x2, float& y2) {
+  const float cx = (x1 + x2) * 0.5f, cy = (y1 + y2) * 0.5f;
+  const float nw = (x2 - x1) * f, nh = (y2 - y1) * f;
+  x1 = cx - nw * 0.5f;
+  x2 = cx + nw * 0.5f;
+  y1 = cy - nh * 0.5f;
+  y2 = cy + nh * 0.5f;
 }
 
 // Source window: the samples are read from a [FH][pitch] tile whose origin is
@@ -278,9 +291,10 @@ __global__ __launch_bounds__(256) void roi_align_kernel(RoiArgs a) {
 
   const float* r = a.rois + (size_t)k * 5;
   const int b = (int)r[0];
-  const float x1 = r[1], y1 = r[2], x2 = r[3], y2 = r[4];
+  float x1 = r[1], y1 = r[2], x2 = r[3], y2 = r[4];
   const int lvl = (a.L > 1) ? roi_level(x1, y1, x2, y2, a.finest, a.L) : 0;
   if (!BWD && a.levels && chunk == 0 && threadIdx.x == 0) a.levels[k] = lvl;
+  if (!BWD && a.rsf != 1.0f) roi_rescale(a.rsf, x1, y1, x2, y2);      // (the level above is the unscaled box's)
   const bool bad_batch = (b < 0 || b >= a.B);   // malformed batch index -> zeros, never an OOB read
   const int Hl = a.H[lvl], Wl = a.W[lvl];
   const float sc = a.scale[lvl];
@@ -795,7 +809,7 @@ __global__ __launch_bounds__(256, MODE == 2 ? 2 : 4) void roi_align_tile_kernel(
   // the k-th RoI of that order; its record carries the RoI's own index and its level)
   const float* r = a.sorted ? a.sorted + (size_t)k * 8 : a.rois + (size_t)k * 5;
   const int b = (int)r[0];
-  const float x1 = r[1], y1 = r[2], x2 = r[3], y2 = r[4];
+  float x1 = r[1], y1 = r[2], x2 = r[3], y2 = r[4];
   int lvl;
   if (a.sorted) {
     k = (int)r[5];
@@ -804,6 +818,7 @@ __global__ __launch_bounds__(256, MODE == 2 ? 2 : 4) void roi_align_tile_kernel(
     lvl = (a.L > 1) ? roi_level(x1, y1, x2, y2, a.finest, a.L) : 0;
     if (a.levels && chunk == 0 && threadIdx.x == 0) a.levels[k] = lvl;
   }
+  if (a.rsf != 1.0f) roi_rescale(a.rsf, x1, y1, x2, y2);      // (the level above is the unscaled box's)
   const bool bad_batch = (b < 0 || b >= a.B);
   int Hl = a.H[0], Wl = a.W[0];
   float sc = a.scale[0];
@@ -1079,9 +1094,10 @@ __global__ __launch_bounds__(256, WPC) void roi_align_band_kernel(RoiArgs a) {
   const int c1 = min(c0 + a.CT, a.C);
   const float* r = a.rois + (size_t)k * 5;
   const int b = (int)r[0];
-  const float x1 = r[1], y1 = r[2], x2 = r[3], y2 = r[4];
+  float x1 = r[1], y1 = r[2], x2 = r[3], y2 = r[4];
   const int lvl = (a.L > 1) ? roi_level(x1, y1, x2, y2, a.finest, a.L) : 0;
   if (a.levels && chunk == 0 && threadIdx.x == 0) a.levels[k] = lvl;
+  if (a.rsf != 1.0f) roi_rescale(a.rsf, x1, y1, x2, y2);      // (the level above is the unscaled box's)
   const bool bad_batch = (b < 0 || b >= a.B);
   int Hl = a.H[0], Wl = a.W[0];
   float sc = a.scale[0];
@@ -1410,6 +1426,7 @@ int fill_args(RoiArgs& a, const int* H, const int* W, const float* spatial_scale
     return DM_ERR_INVALID_ARG;
   a.L = num_levels; a.B = B; a.C = C; a.rois = rois; a.N = N; a.P = P; a.sr = sampling_ratio;
   a.finest = finest_scale;
+  a.rsf = 1.0f;
   for (int l = 0; l < DM_MAX_LEVELS; ++l) {
     a.H[l] = l < num_levels ? H[l] : 0;
     a.W[l] = l < num_levels ? W[l] : 0;
@@ -1438,10 +1455,11 @@ namespace {
 int roi_align_fwd_impl(const float* const* feats, const int* H, const int* W, const float* spatial_scales,
                        int num_levels, int B, int C, const float* rois, int N, int P, int sampling_ratio,
                        float finest_scale, float* out, int32_t* levels_out, void* workspace, long long workspace_bytes,
-                       dm_stream_t stream) {
+                       dm_stream_t stream, float roi_scale_factor = 1.0f) {
   RoiArgs a;
   int rc = fill_args(a, H, W, spatial_scales, num_levels, B, C, rois, N, P, sampling_ratio, finest_scale);
   if (rc != DM_OK) return rc;
+  a.rsf = roi_scale_factor;
   if (N == 0) return DM_OK;
   if (!feats || !out) return DM_ERR_INVALID_ARG;
   for (int l = 0; l < num_levels; ++l) {
@@ -1514,6 +1532,18 @@ extern "C" int dm_roi_align_fwd(const float* const* feats, const int* H, const i
                                 float finest_scale, float* out, int32_t* levels_out, dm_stream_t stream) {
   return roi_align_fwd_impl(feats, H, W, spatial_scales, num_levels, B, C, rois, N, P, sampling_ratio, finest_scale, out,
                             levels_out, nullptr, 0, stream);
+}
+
+// (K28) Double-Head R-CNN's regression extraction: the level from the box as given, the samples from the box rescaled
+// about its centre (single_level_roi_extractor.py:69-71: map_roi_levels, then roi_rescale).  A factor of 1 is
+// dm_roi_align_fwd itself: the kernels skip the rescale, whose (x1 + x2) * 0.5 - (x2 - x1) * 0.5 need not give x1 back.
+extern "C" int dm_roi_align_scaled_fwd(const float* const* feats, const int* H, const int* W, const float* spatial_scales,
+                                       int num_levels, int B, int C, const float* rois, int N, int P, int sampling_ratio,
+                                       float finest_scale, float roi_scale_factor, float* out, int32_t* levels_out,
+                                       dm_stream_t stream) {
+  if (!(roi_scale_factor > 0.f) || !(roi_scale_factor <= 3.4e38f)) return DM_ERR_INVALID_ARG;      // (<= 0, NaN, inf)
+  return roi_align_fwd_impl(feats, H, W, spatial_scales, num_levels, B, C, rois, N, P, sampling_ratio, finest_scale, out,
+                            levels_out, nullptr, 0, stream, roi_scale_factor);
 }
 
 // (K26) the RoIAlign of ONE map added into RoI features, no [N, C, P, P] intermediate.  The launch is dm_roi_align_fwd's

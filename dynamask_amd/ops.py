@@ -101,13 +101,33 @@ ROI_WORKSPACE = True          # (tests compare with the unordered kernel by clea
 ROI_WORKSPACE_MIN = int(os.environ.get('DM_ROI_SORT_MIN', '192'))
 
 
-def roi_align(feats, rois, output_size, spatial_scales, sampling_ratio=0, finest_scale=56.0, return_levels=False):
+def roi_align(feats, rois, output_size, spatial_scales, sampling_ratio=0, finest_scale=56.0, return_levels=False,
+              roi_scale_factor=None, out=None):
+    """``roi_scale_factor`` (a float > 0; None: not given): the FPN level -- and ``levels`` -- is the box's as given, the
+    samples are those of the box rescaled about its centre (dm_roi_align_scaled_fwd: SingleRoIExtractor.forward's
+    ``map_roi_levels`` before ``roi_rescale``).  ``out``: the [N, C, P, P] tensor to write (default: a new one)."""
     feats = [_chk(f, 'feat') for f in feats]
     _chk(rois, 'rois')
     B, C = feats[0].shape[:2]
     N = rois.shape[0]
-    out = torch.empty((N, C, output_size, output_size), device=rois.device, dtype=torch.float32)
+    if roi_scale_factor is not None:
+        if isinstance(roi_scale_factor, bool) or not isinstance(roi_scale_factor, (int, float)):
+            raise TypeError(f'roi_scale_factor: a number expected, got {type(roi_scale_factor).__name__}')
+        if not 0.0 < float(roi_scale_factor) < float('inf'):
+            raise ValueError(f'roi_scale_factor must be a finite number > 0, got {roi_scale_factor}')
+    if out is None:
+        out = torch.empty((N, C, output_size, output_size), device=rois.device, dtype=torch.float32)
+    else:
+        _chk(out, 'out')
+        assert tuple(out.shape) == (N, C, output_size, output_size)
     levels = torch.zeros((N,), device=rois.device, dtype=torch.int32) if return_levels else None
+    if roi_scale_factor is not None:
+        rc = lib().dm_roi_align_scaled_fwd(_ptr_array(feats), _int_array([f.shape[2] for f in feats]),
+                                           _int_array([f.shape[3] for f in feats]), _float_array(spatial_scales), len(feats),
+                                           B, C, _p(rois), N, output_size, sampling_ratio, finest_scale,
+                                           float(roi_scale_factor), _p(out), _p(levels), _stream())
+        check(rc, 'dm_roi_align_scaled_fwd')
+        return (out, levels) if return_levels else out
     if ROI_WORKSPACE and N >= ROI_WORKSPACE_MIN:
         # 14x14 / 7x7 extraction with a workspace: the RoIs are first ordered by level and position (one extra launch:
         # neighbouring workgroups then share their footprints in the L2; same results).
@@ -2655,3 +2675,27 @@ def grid_get_bboxes(heat, det_bboxes, sub_regions, out=None, return_cells=False)
                                    _int_array([r[0] for r in sub_regions]), _int_array([r[1] for r in sub_regions]),
                                    _p(out), _p(cells), _stream()), 'dm_grid_get_bboxes')
     return (out, cells) if return_cells else out
+
+
+# ------------------------------------------------ Double-Head R-CNN (section K28 of the header)
+def global_avg_pool_supported(x):
+    N, C, H, W = x.shape
+    return bool(lib().dm_global_avg_pool_supported(N, C, H * W))
+
+
+def global_avg_pool(x, out=None):
+    """x [N, C, H, W] -> [N, C], the mean of every plane (dm_global_avg_pool_fwd): ``nn.AvgPool2d(H)`` on an H x H map,
+    flattened.  The summation order is fixed by H * W alone: a sample's bits do not depend on the rest of the batch."""
+    _chk(x, 'x')
+    if x.dim() != 4:
+        raise ValueError(f'x: [N, C, H, W] expected, got {list(x.shape)}')
+    N, C, H, W = x.shape
+    if C < 1 or H * W < 1:
+        raise ValueError(f'x: an empty plane has no mean, got {list(x.shape)}')
+    if out is None:
+        out = torch.empty((N, C), device=x.device, dtype=torch.float32)
+    else:
+        _chk(out, 'out')
+        assert out.shape == (N, C)
+    check(lib().dm_global_avg_pool_fwd(_p(x), N, C, H * W, _p(out), _stream()), 'dm_global_avg_pool_fwd')
+    return out

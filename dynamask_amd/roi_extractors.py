@@ -52,6 +52,16 @@ class BaseRoIExtractor(nn.Module):
     def init_weights(self):
         pass
 
+    @staticmethod
+    def roi_rescale(rois, scale_factor):
+        """base_roi_extractor.py:57-80: RoIs [n, 5] scaled about their centres, one float32 rounding per operation in the
+        reference's order -- centre = (lo + hi) * 0.5, half = ((hi - lo) * scale_factor) * 0.5, centre -/+ half.  The
+        extraction does this inside its launch (dm_roi_align_scaled_fwd); this is the host form of the same arithmetic."""
+        lo, hi = rois[:, 1:3], rois[:, 3:5]
+        centre = (lo + hi) * 0.5
+        half = ((hi - lo) * scale_factor) * 0.5
+        return torch.cat([rois[:, :1], centre - half, centre + half], dim=1)
+
     def build_roi_layers(self, layer_cfg, featmap_strides):
         cfg = layer_cfg.copy()
         layer_type = cfg.pop('type')
@@ -81,8 +91,8 @@ class SingleRoIExtractor(BaseRoIExtractor):
         return lv.long()
 
     def forward(self, feats, rois, roi_scale_factor=None):
-        if roi_scale_factor is not None:
-            raise NotImplementedError('roi_scale_factor is not used by the DynaMask path')
+        """``roi_scale_factor`` (single_level_roi_extractor.py:69-71): the levels come from ``rois`` as given, the samples
+        from the boxes rescaled about their centres (base_roi_extractor.py:57-80), inside the same launch."""
         lay = self.roi_layers[0]
         P = lay.output_size[0]
         feats = list(feats)[:self.num_inputs]
@@ -91,7 +101,10 @@ class SingleRoIExtractor(BaseRoIExtractor):
         if rois.shape[0] == 0:
             return feats[0].new_zeros((0, self.out_channels, P, P))
         scales = [l.spatial_scale for l in self.roi_layers]
-        return ops.roi_align(feats, rois, P, scales, lay.sampling_ratio, float(self.finest_scale))
+        if self.num_inputs == 1:
+            roi_scale_factor = None       # single_level_roi_extractor.py:64-67 returns before the rescale: one level ignores it
+        return ops.roi_align(feats, rois, P, scales, lay.sampling_ratio, float(self.finest_scale),
+                             roi_scale_factor=roi_scale_factor)
 
 
 @ROI_LAYERS.register_module()

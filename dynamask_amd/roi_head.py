@@ -1,6 +1,6 @@
 """The RoI heads behind the reference's HEADS registry, in the reference's class tree: ``StandardRoIHead``
 (standard_roi_head.py + test_mixins.py) is the base of ``DynaMaskRoIHead``, ``RefineRoIHead``, ``PointRendRoIHead``,
-``MaskScoringRoIHead``, ``PointRefineRoIHead``, ``GridRoIHead`` and ``CascadeRoIHead``.
+``MaskScoringRoIHead``, ``PointRefineRoIHead``, ``GridRoIHead``, ``DoubleHeadRoIHead`` and ``CascadeRoIHead``.
 
 The base holds the constructor (incl. ``base_roi_head.py:10-58``'s MaskPre, Quirk Q4), the assigner / sampler, the bbox
 branch, the one-image / batched / test-time-augmentation entry points and one mask-test template over a head's
@@ -1405,6 +1405,34 @@ class GridRoIHead(StandardRoIHead):
         segm_results = self.batch_simple_test_mask(x, img_metas, [d for d, _ in dets], [l for _, l in dets],
                                                    rescale=rescale, encode=encode, _labels_host=labels_h)
         return list(zip(bbox_results, segm_results))
+
+
+@HEADS.register_module()
+class DoubleHeadRoIHead(StandardRoIHead):
+    """``DoubleHeadRoIHead`` -- mmdet/models/roi_heads/double_roi_head.py, inference: the RoI head of configs/double_heads,
+    a ``StandardRoIHead`` whose bbox head (``DoubleConvFCBBoxHead``) classifies from the RoI features of the proposals and
+    regresses from those of the proposals enlarged by ``reg_roi_scale_factor`` about their centres (the FPN level is the
+    proposal's own in both).  Only ``_bbox_forward`` differs: ``simple_test``, ``batch_simple_test``, ``aug_test`` and a
+    configured mask branch are the base class's.  Training raises."""
+
+    def __init__(self, reg_roi_scale_factor, **kwargs):
+        super().__init__(**kwargs)
+        if not self.with_bbox:
+            raise ValueError('DoubleHeadRoIHead needs a bbox branch')
+        self.reg_roi_scale_factor = reg_roi_scale_factor
+
+    def forward_train(self, x, img_metas, proposal_list, gt_bboxes, gt_labels, gt_bboxes_ignore=None, gt_masks=None):
+        raise NotImplementedError('DoubleHeadRoIHead.forward_train: Double-Head R-CNN training (BatchNorm in train mode, the '
+                                  'backward of the conv branch) is the follow-up to inference')
+
+    def _bbox_forward(self, x, rois):
+        """double_roi_head.py:16-33; ``bbox_feats`` are the classification features."""
+        ext = self.bbox_roi_extractor
+        rois = rois.contiguous()
+        bbox_cls_feats = ext(x[:ext.num_inputs], rois)
+        bbox_reg_feats = ext(x[:ext.num_inputs], rois, roi_scale_factor=self.reg_roi_scale_factor)
+        cls_score, bbox_pred = self.bbox_head(bbox_cls_feats, bbox_reg_feats)
+        return dict(cls_score=cls_score, bbox_pred=bbox_pred, bbox_feats=bbox_cls_feats)
 
 
 @HEADS.register_module()

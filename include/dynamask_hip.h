@@ -61,7 +61,8 @@ const char* dm_error_string(int code);
  * multi-row scatter (section K24); Cascade Mask R-CNN's stage-grouped convolutions / deconvolutions and stage step
  * (section K25); Hybrid Task Cascade's resize, post-activation addend and RoIAlign-add (section K26); Grid R-CNN's
  * GroupNorm, neighbour fusion, grouped 4x4 stride-2 deconvolution and box vote (section K27); the convolution launcher's
- * own report of its launches, dm_conv2d_plan (section K5/K6) and dm_conv2d_group_plan (section K25). */
+ * own report of its launches, dm_conv2d_plan (section K5/K6) and dm_conv2d_group_plan (section K25); Double-Head R-CNN's
+ * rescaled RoIAlign and global average pool (section K28). */
 #define DM_ABI_VERSION 28 /* the one definition: dm_abi_version(), dm_build_info() and _lib.ABI_VERSION read it */
 int dm_abi_version(void);
 /* "libdynamask_hip abi=N arch=gfx950 compiler=<clang version> flags=<the product-wide flags of dynamask_amd/build.py>"
@@ -1102,6 +1103,30 @@ int dm_deconv4x4_s2_grouped_fwd(const float* x, int N, int G, int ci, int co, in
 int dm_grid_get_bboxes_supported(int n, int P, int HS, int D);
 int dm_grid_get_bboxes(const float* heat, int n, int P, int HS, const float* det, int D, const int* sub_x, const int* sub_y,
                        float* out, int* cells, dm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * K28  Double-Head R-CNN inference (mmdet/models/roi_heads/double_roi_head.py, bbox_heads/double_bbox_head.py).  The
+ *      head's convolutions are dm_conv2d_fwd launches (BatchNorm in eval mode folded into weights and bias on the host),
+ *      its fully connected layers dm_fc_fwd; these two entry points are what it adds.  Exact fp32, deterministic.
+ *
+ * dm_roi_align_scaled_fwd: dm_roi_align_fwd with the RoIs rescaled about their centres by roi_scale_factor
+ * (base_roi_extractor.py:57-80) AFTER the level map (single_level_roi_extractor.py:69-71): the FPN level -- and
+ * levels_out -- is the box's as given; the samples are those of
+ *   cx = (x1 + x2) * 0.5, w = x2 - x1, new_w = w * roi_scale_factor, x1' = cx - new_w * 0.5, x2' = cx + new_w * 0.5
+ * (the same in y), one fp32 rounding per operation: per RoI the bits of dm_roi_align_fwd with num_levels == 1 on that
+ * level's map and the box rescaled on the host.  roi_scale_factor == 1 skips the rescale: dm_roi_align_fwd's bits.
+ * roi_scale_factor <= 0 (or not finite): DM_ERR_INVALID_ARG.  No workspace form: the RoIs are walked in their own order.
+ *
+ * dm_global_avg_pool_fwd: out [N, C] = the mean of every plane of x [N, C, HW] (nn.AvgPool2d(S) on an S x S map).  One
+ * wave per plane: lane l adds the elements l, l + 64, ... in order, a xor butterfly adds the 64 partial sums, one division
+ * by HW -- an order fixed by HW alone: a sample's bits do not depend on the other samples of the call.
+ * dm_global_avg_pool_supported: 1 exactly when N >= 0, C >= 1, 1 <= HW <= 2^24 and N * C < 2^31.  N == 0 enqueues nothing.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int dm_roi_align_scaled_fwd(const float* const* feats, const int* H, const int* W, const float* spatial_scales,
+                            int num_levels, int B, int C, const float* rois, int N, int P, int sampling_ratio,
+                            float finest_scale, float roi_scale_factor, float* out, int32_t* levels_out, dm_stream_t stream);
+int dm_global_avg_pool_supported(int N, int C, int HW);
+int dm_global_avg_pool_fwd(const float* x, int N, int C, int HW, float* out, dm_stream_t stream);
 
 #ifdef __cplusplus
 }
