@@ -1209,27 +1209,57 @@ __global__ __launch_bounds__(256) void dcn_splitk_reduce_kernel(const float* __r
   }
 }
 
-// Split-K for a launch of ``wgs`` workgroups on ``slots`` slots (caller-owned workspace of ws_floats floats): a workgroup
+// ---- host side: validate, route, emit ---------------------------------------------------------------------------------
+// dcn_route decides everything about the launches of a call from numbers alone (no pointer, no HIP call); dcn_emit enqueues
+// exactly what the route says; dm_deform_conv_plan reports the same value.  Every variant runs 4-wave workgroups, two per
+// CU (8-wave tiles run alone on their CU and lose: 128 x 128 from global memory 1.81 vs 1.59 ms at 256 channels, 256 x 128
+// from LDS -1 % in the two-stream step), so a launch has 2 x CUs slots per round.  Same products in the same order in every
+// variant: results do not depend on the route (except by the association of the channel sums where the K loop is split).
+
+enum { DCN_GENERIC = 0, DCN_LDS = 1, DCN_C256 = 2, DCN_BAND = 3 };      // DcnLaunch::kernel, as the header numbers them
+constexpr int DCN_BAND_ROWS = 16;                                       // rows of the band kernel's LDS band
+
+struct DcnCall {            // what a route depends on
+  int NB, C, H, W, Cout, dg, flags;
+  long long ws_floats;      // the caller's workspace (0: none)
+  int M2;                   // > 0: the chained 1x1 of dm_deform_conv_tout_fwd
+  int cus;
+  bool seam;                // an underfull last round may go to a second launch (DM_DCN_TAIL, flag bit 3)
+};
+
+// One launch: the ints of dm_deform_conv_plan's record, in its order (the record's last int is DcnRoute::reduce)
+struct DcnLaunch {
+  int kernel, p[4], threads, MT, q_begin, Q, grid_x, grid_y, ksplit, kchan, lds_bytes;
+};
+
+struct DcnRoute {
+  int rc = DM_OK;
+  int count = 0;            // launches (0: NB = 0)
+  DcnLaunch launch[DM_DCN_PLAN_MAX_LAUNCHES];
+  bool reduce = false;      // launch[0] split its K loop: dcn_splitk_reduce_kernel follows
+};
+
+// Split-K for launch l of l.grid_x workgroups (a caller-owned workspace): a workgroup
 // walks its chunks of 8 channels one after the other at ~3.5 us each whatever the RoI count (tools/small_n.py: dcn14 105-115 us
 // for 32 chunks at 8-16 RoIs); S splits save (1 - 1/S) of that and cost a second launch that reads S and writes one copy of
-// the output.  Sets a.ksplit / kchan / ws_stride; a.ksplit stays 1 when it does not pay.
-static void dcn_choose_split(DcnArgs& a, long long wgs, long long slots, long long ws_floats, bool lds_tiles = false) {
-  a.ksplit = 1;
-  if (!a.ws || a.q_begin != 0 || wgs <= 0) return;
-  const int chunks = a.C / 8;
-  const long long per = (long long)a.NB * a.Cout * a.HW;
+// the output.  Sets l.ksplit / kchan / grid_y; l.ksplit stays 1 when it does not pay.
+static void dcn_choose_split(const DcnCall& c, bool lds_tiles, DcnLaunch& l) {
+  const long long wgs = l.grid_x, slots = 2LL * c.cus;
+  if (c.ws_floats <= 0 || wgs <= 0) return;
+  const int chunks = c.C / 8;
+  const long long per = (long long)c.NB * c.Cout * (c.H * c.W);
   int S = 1;
-  if (a.NB <= 24) {
+  if (c.NB <= 24) {
     // a handful of RoIs: the cost model (13 % / 3 % on the full head at 8 / 16 RoIs)
     long long Smax = min(min(8LL, slots / wgs), (long long)chunks / 2);
-    if (per > 0) Smax = min(Smax, ws_floats / per);
+    if (per > 0) Smax = min(Smax, c.ws_floats / per);
     const double chain_us = chunks * 3.5, out_mb = (double)per * 4e-6;
     double best = 8.0;
-    for (int c = 2; c <= Smax; ++c) {
-      const double g = chain_us * (1.0 - 1.0 / c) - (5.0 + (c + 1) * out_mb * 0.25);
-      if (g > best) { best = g; S = c; }
+    for (int s_ = 2; s_ <= Smax; ++s_) {
+      const double g = chain_us * (1.0 - 1.0 / s_) - (5.0 + (s_ + 1) * out_mb * 0.25);
+      if (g > best) { best = g; S = s_; }
     }
-  } else if (lds_tiles && wgs < slots && chunks >= 12 && per > 0 && ws_floats / per >= 3) {
+  } else if (lds_tiles && wgs < slots && chunks >= 12 && per > 0 && c.ws_floats / per >= 3) {
     // 25 .. 128 RoIs of 14 x 14 on the 128 x 128 LDS kernel (round 5, tools/small_n.py with forced splits): the launch is
     // less than one round of workgroups, each walking 32 chunks alone on its CU -- three splits: 32 / 50 / 64 / 100 RoIs
     // 0.179 / 0.198 / 0.200 / 0.332 -> 0.157 / 0.138 / 0.197 / 0.248 ms (two: 0.177 / 0.181 / 0.183 / 0.279).  The band
@@ -1238,104 +1268,195 @@ static void dcn_choose_split(DcnArgs& a, long long wgs, long long slots, long lo
   }
   if (S >= 2) {
     const int per_split = dm_ceil_div(chunks, S);
-    a.kchan = per_split * 8;
-    a.ksplit = dm_ceil_div(chunks, per_split);
-    a.ws_stride = per;
+    l.kchan = per_split * 8;
+    l.ksplit = l.grid_y = dm_ceil_div(chunks, per_split);
   }
 }
 
-static int dcn_finish_split(const DcnArgs& a, int relu, float* out, hipStream_t st) {
-  if (a.ksplit <= 1) return dm_check_launch();
-  int rc = dm_check_launch();
-  if (rc != DM_OK) return rc;
-  const long long total = a.ws_stride;
-  const bool v4 = (total & 3) == 0 && ((((uintptr_t)a.ws) | ((uintptr_t)out)) & 15) == 0;
-  DM_LAUNCH(dcn_splitk_reduce_kernel, dim3((unsigned)min((long long)4096, ((v4 ? total / 4 : total) + 255) / 256)), dim3(256), 0, st, a.ws,
-            v4 ? a.ksplit : -a.ksplit, a.ws_stride, total, relu, out);
-  return dm_check_launch();
+// deform_conv_kernel<WGM, WGN, WM, WN> on the flat pixels [q_begin, Q): 32 WGM WM couts x 32 WGN WN pixels per workgroup
+static DcnLaunch dcn_generic(int WGM, int WGN, int WM, int WN, int CoutP, int q_begin, int Q) {
+  const int TM = WGM * WM * 32, TN = WGN * WN * 32, MT = dm_ceil_div(CoutP, TM);
+  return {DCN_GENERIC, {WGM, WGN, WM, WN}, WGM * WGN * 64, MT, q_begin, Q, MT * dm_ceil_div(Q - q_begin, TN), 1, 1, 0,
+          16 * (9 * 2 * TM + 2 * 9 * TN)};
 }
 
-template <int WM, int WGM, int XR>
-int launch_dcn_band(DcnArgs& a, hipStream_t st) {
-  const int BR = 16;
-  if (8 * BR * a.W / 4 > XR * 256 || a.H < BR) return DM_ERR_UNSUPPORTED;      // the staging registers must cover the band planes
-  const int tiles = dm_ceil_div(a.HW, (4 / WGM) * 32);
-  const size_t lds_bytes = 16 * (size_t)(9 * 2 * WM * WGM * 32) + 4 * (size_t)8 * BR * a.W;
-  if (a.w2t) {
-    // the chained 1x1: this wave layout only (a wave holds every cout of its pixels), its weights must fit the kernel's LDS
-    if (WGM != 1 || a.w2_ld != dm_ceil_div(a.M2, 32) * 32 || a.w2_ld > (WM + 1) / 2 * 32 || (size_t)a.Cout * a.w2_ld * 4 > lds_bytes ||
-        a.Cout != WM * 32)
-      return DM_ERR_UNSUPPORTED;
-    a.ws = nullptr;                            // (no split-K: the second GEMM needs the complete channel sums)
+// Large maps: the consuming wave gathers from an LDS band of 16 rows.  The 8 band planes of a chunk must fit the 7 float4 per
+// thread of the widest staging build (W <= 56), and the rows a 128-pixel tile can span plus DCN_NEAR_ROWS each side the
+// band.  Every launch size of an eligible shape takes this kernel (rows must not depend on the batch); which build
+// <WM, WGM, XR> of it, this says too.  false: not a band map.
+static bool dcn_band_build(const DcnCall& c, int& WM, int& WGM, int& XR) {
+  if (c.W <= 0 || c.H < DCN_BAND_ROWS || (c.W & 3) != 0 || 8 * DCN_BAND_ROWS * c.W / 4 > 7 * 256 || c.Cout <= 32) return false;
+  const int max_rows = (c.W - 1 + 128 + c.W - 1) / c.W;                     // rows a 128-pixel tile can span
+  const long long HW = (long long)c.H * c.W;
+  const int CoutP = dm_conv_packed_cout(c.Cout);
+  if ((DCN_BAND_ROWS - max_rows) / 2 < DCN_NEAR_ROWS || HW <= 256 || HW >= 65536 || (CoutP != 64 && CoutP != 128)) return false;
+  const bool narrow = 8 * DCN_BAND_ROWS * c.W / 4 <= 4 * 256;               // band planes fit 4 float4 per thread
+  // a handful of RoIs (real inference): the launch is bound by the time of one workgroup -- one cout tile per
+  // wave, the waves sharing a pixel column (2-4 x the workgroups, 1/2-1/4 of the K-loop time each; same bits)
+  bool few = (long long)c.NB * dm_ceil_div(HW, 128) * 4 < (long long)c.cus * 3;
+  // ... unless the caller brought a workspace: a workgroup's time is its number of chunks times a load round trip
+  // (~3.5 us) whatever it computes per chunk, so the full layout (every cout of 128 pixels: one gather per sample, four
+  // times the MFMAs per round trip) with the K loop split (dcn_choose_split's cost model, <= 24 RoIs) beats it:
+  // 16 / 24 detections 0.5845 / 0.733 -> 0.578 / 0.712 ms (profiles/r06_infer_notes.txt (6))
+  if (c.ws_floats > 0 && c.NB <= 24) few = false;
+  XR = narrow ? 4 : 7;
+  if (few) { WM = 1; WGM = CoutP / 32; }
+  else if (CoutP == 128 && !narrow) { WM = 2; WGM = 2; }                    // two waves share a pixel column
+  else { WM = CoutP / 32; WGM = 1; }                                        // a wave holds every cout of its 32 pixels
+  return true;
+}
+
+// Small maps (14 x 14): the planes of two images fit in LDS beside the operand rings (deform_conv_lds_kernel, .._c256_kernel)
+static bool dcn_lds_map(int HW) { return HW >= 128 && HW <= 256 && (HW & 3) == 0; }
+
+// A handful of RoIs: launches that leave most of the chip idle are bound by the time of one workgroup, and 64 x 64 tiles
+// give four times the workgroups of the 128 x 128 LDS kernel (14 x 14, 8 RoIs: 0.208 -> 0.108 ms, 32 RoIs: 0.213 -> 0.168 ms;
+// from 64 RoIs on the big tiles win); same for the 128 x 64 tiles (28 x 28, 8 RoIs: 0.081 -> 0.056 ms)
+static bool dcn_small_launch(const DcnCall& c, int CoutP, int Q) {
+  return (long long)dm_ceil_div(CoutP, 128) * dm_ceil_div(Q, 128) * 20 <= (long long)c.cus * 9;
+}
+
+// Rounds (see conv_igemm.hip): r.launch[0] covers the batch in tiles of tile_px pixels, two workgroups per CU.  From one
+// full round on, the pixels of a nearly empty last round go to a second launch with 64 x 64 tiles (same bits): 512 RoIs
+// 1.24 -> 1.19 ms.  Only for small remainders (the 64 x 64 build is slower per pixel: at 0.5 of a round the split loses).
+static void dcn_seam(const DcnCall& c, int CoutP, int tile_px, DcnRoute& r) {
+  DcnLaunch& m = r.launch[0];
+  const int slots = 2 * c.cus, full_rounds = m.grid_x / slots, rem = m.grid_x - full_rounds * slots;
+  if (!(full_rounds >= 1 && rem > 0 && rem * 20 <= 3 * slots)) return;
+  const int n_main = full_rounds * slots / m.MT, Q = m.Q;
+  m.grid_x = m.MT * n_main;
+  m.Q = n_main * tile_px;
+  r.launch[r.count++] = dcn_generic(2, 2, 1, 1, CoutP, m.Q, Q);
+}
+
+static DcnRoute dcn_route(const DcnCall& c) {
+  DcnRoute r;
+  auto refuse = [&r](int rc) { r.rc = rc; return r; };
+  if (c.flags & 16) return refuse(DM_ERR_UNSUPPORTED);      // (flag bit 4, the bf16x3 mode of dm_conv2d_fwd: the DCN stays exact fp32)
+  int WM = 0, WGM = 0, XR = 0;
+  if (c.M2 > 0) {
+    // the chained 1x1 answers for its shape before its arguments: only the band build in which a wave holds every cout of
+    // its pixels can chain it, and its weights ([Cout][32-padded M2]) must fit the LDS the kernel has
+    if (c.NB == 0) return r;
+    if (c.Cout != c.C || !dcn_band_build(c, WM, WGM, XR) || WGM != 1 || c.Cout != WM * 32 || dm_ceil_div(c.M2, 32) > (WM + 1) / 2)
+      return refuse(DM_ERR_UNSUPPORTED);
   }
-  dcn_choose_split(a, (long long)a.NB * tiles, 2LL * dm_num_cus(), a.ws_floats);
-  DM_LAUNCH((deform_conv_band_kernel<WM, WGM, XR>), dim3((unsigned)(a.NB * tiles), (unsigned)a.ksplit), dim3(256), lds_bytes, st, a, tiles, BR);
-  return dcn_finish_split(a, a.relu, a.out, st);
+  if (c.NB < 0 || c.C <= 0 || c.H <= 0 || c.W <= 0 || c.Cout <= 0 || c.dg <= 0 || c.C % c.dg != 0) return refuse(DM_ERR_INVALID_ARG);
+  if ((long long)c.NB * c.H * c.W > 0x7fffffffLL) return refuse(DM_ERR_INVALID_ARG);
+  if ((c.C / c.dg) % 8 != 0) return refuse(DM_ERR_UNSUPPORTED);   // channel chunk must not straddle a deformable group
+  if (c.W < 2) return refuse(DM_ERR_UNSUPPORTED);                 // the gather loads row pairs
+  if (c.NB == 0) return r;
+  const int HW = c.H * c.W, Q = c.NB * HW, CoutP = dm_conv_packed_cout(c.Cout);
+  DcnLaunch& l = r.launch[0];
+  r.count = 1;
+  if (dcn_band_build(c, WM, WGM, XR)) {
+    // 128 / WGM pixels per workgroup, tiles per image; operand rings + the 8 band planes.  (The chained 1x1 never splits: the
+    // second GEMM needs the complete channel sums -- its call has no workspace.)
+    l = {DCN_BAND, {WM, WGM, XR, 0}, 256, 1, 0, Q, c.NB * dm_ceil_div(HW, (4 / WGM) * 32), 1, 1, 0,
+         16 * (9 * 2 * WM * WGM * 32) + 4 * 8 * DCN_BAND_ROWS * c.W};
+    dcn_choose_split(c, false, l);
+  } else if (c.Cout > 64 && dcn_lds_map(HW) && (c.ws_floats > 0 || !dcn_small_launch(c, CoutP, Q))) {
+    // 128 couts x 128 pixels: A ring + B ring (2 x 3 taps x 2 quads x 128 float4 each) + 2 plane buffers of 2 images x 8
+    // channels.  With a workspace this kernel takes the small launches too: its K loop split (up to 8 ways at <= 24 RoIs, 3
+    // above) fills the chip faster than 64 x 64 tiles (round 6: the 16- / 32-detection inference calls 0.652 / 0.949 ->
+    // 0.626 / 0.918 ms; the 14 x 14 DCN was their largest launch, 90 us at 16 RoIs).
+    const int MT = dm_ceil_div(CoutP, 128);
+    l = {DCN_LDS, {0, 0, 0, 0}, 256, MT, 0, Q, MT * dm_ceil_div(Q, 128), 1, 1, 0, 16 * (2 * 2 * 3 * 2 * 128) + 4 * 2 * 2 * 8 * HW};
+    dcn_choose_split(c, true, l);
+    if (l.ksplit == 1) {
+      // 256 couts: one workgroup per 64 pixels holds every cout (deform_conv_c256_kernel: each sample gathered once; the
+      // waves own different couts and read their weights straight from L2).  B ring (2 x 3 taps x 2 quads x 64 float4) + the
+      // plane buffers: 37 KB at 14 x 14, 44 KB at H*W = 256.  Launches that split their K loop stay on the LDS kernel.
+      if (CoutP == 256) l = {DCN_C256, {0, 0, 0, 0}, 256, 1, 0, Q, dm_ceil_div(Q, 64), 1, 1, 0, 16 * (2 * 3 * 2 * 64) + 4 * 2 * 2 * 8 * HW};
+      if (c.seam) dcn_seam(c, CoutP, CoutP == 256 ? 64 : 128, r);
+    }
+  } else {
+    // gather from global memory: a wave holds 64 accumulator registers, so 128 couts x 64 px (2.57 -> 2.28 ms at 64 channels,
+    // 56 x 56, for the 64 x 64 tiles), or 32 x 128
+    l = c.Cout > 64 ? (dcn_small_launch(c, CoutP, Q) ? dcn_generic(2, 2, 1, 1, CoutP, 0, Q) : dcn_generic(2, 2, 2, 1, CoutP, 0, Q))
+                    : c.Cout > 32 ? dcn_generic(2, 2, 1, 1, CoutP, 0, Q) : dcn_generic(1, 4, 1, 1, CoutP, 0, Q);
+    dcn_choose_split(c, false, l);
+  }
+  r.reduce = l.ksplit > 1;
+  return r;
 }
 
-template <int WGM, int WGN, int WM, int WN>
-int launch_dcn(DcnArgs& a, hipStream_t st) {
-  constexpr int TM = WGM * WM * 32;
-  constexpr int TN = WGN * WN * 32;
-  constexpr int NT = WGM * WGN * 64;
-  a.MT = dm_ceil_div(a.CoutP, TM);
-  const int NTiles = dm_ceil_div(a.Q - a.q_begin, TN);
-  const size_t lds_bytes = 16 * ((size_t)9 * 2 * TM + (size_t)2 * 9 * TN);
-  static bool attr_set[DM_MAX_DEVICES] = {false};
-  if (lds_bytes > 64 * 1024 &&
-      dm_ensure_lds_limit(reinterpret_cast<const void*>(&deform_conv_kernel<WGM, WGN, WM, WN>), (int)lds_bytes, attr_set) != DM_OK)
-    return DM_ERR_LAUNCH;
-  dcn_choose_split(a, (long long)a.MT * NTiles, (NT == 256 ? 2LL : 1LL) * dm_num_cus(), a.ws_floats);
-  DM_LAUNCH((deform_conv_kernel<WGM, WGN, WM, WN>), dim3(a.MT * NTiles, a.ksplit), dim3(NT), lds_bytes, st, a);
-  return dcn_finish_split(a, a.relu, a.out, st);
+static DcnCall dcn_call(int NB, int C, int H, int W, int Cout, int dg, int flags, long long ws_floats, int M2) {
+  // (flag bit 3, the caller overlaps launches on a second stream: no seam -- measured 259 vs 251 img/s)
+  static const int tail_mode = getenv("DM_DCN_TAIL") ? atoi(getenv("DM_DCN_TAIL")) : 1;
+  return {NB, C, H, W, Cout, dg, flags, ws_floats > 0 ? ws_floats : 0, M2, dm_num_cus(), tail_mode && !(flags & 8)};
 }
 
-// deform_conv_c256_kernel: CoutP == 256, 128 <= H*W <= 256, no split-K.  Two workgroups per CU; with ``tail`` the pixels
-// of a nearly empty last round go to a second launch with 64 x 64 tiles (same bits), as for the 128 x 128 kernel.
-int launch_dcn_c256(DcnArgs& a, bool tail, hipStream_t st) {
-  // B ring (2 x 3 taps x 2 quads x 64 float4) + 2 plane buffers of 2 images x 8 channels: 37 KB at 14 x 14, 44 KB at H*W = 256
-  const size_t lds_bytes = 16 * ((size_t)2 * 3 * 2 * 64) + (size_t)4 * 2 * 2 * 8 * a.HW;
-  const int NTiles = dm_ceil_div(a.Q, 64);
-  const int slots = 2 * dm_num_cus();
-  const int full_rounds = NTiles / slots;
-  const int rem = NTiles - full_rounds * slots;
-  a.ksplit = 1;
-  if (tail && full_rounds >= 1 && rem > 0 && rem * 20 <= 3 * slots) {
-    const int n_main = full_rounds * slots;
-    const int Q = a.Q;
-    a.Q = n_main * 64;
-    DM_LAUNCH(deform_conv_c256_kernel, dim3(n_main), dim3(256), lds_bytes, st, a);
-    int rc = dm_check_launch();
+constexpr int dcn_build(int kernel, int p0, int p1, int p2, int p3) { return (((kernel * 8 + p0) * 8 + p1) * 8 + p2) * 8 + p3; }
+#define DCN_GENERIC_CASE(A, B, C, D) \
+  case dcn_build(DCN_GENERIC, A, B, C, D): DM_LAUNCH((deform_conv_kernel<A, B, C, D>), grid, block, lds, st, a); break
+#define DCN_BAND_CASE(A, B, C) \
+  case dcn_build(DCN_BAND, A, B, C, 0): DM_LAUNCH((deform_conv_band_kernel<A, B, C>), grid, block, lds, st, a, tiles, DCN_BAND_ROWS); break
+
+// The one place a DCN forward kernel is enqueued: the launches of route r, each with its slice of the arguments
+static int dcn_emit(const DcnRoute& r, DcnArgs a, hipStream_t st) {
+  for (int i = 0; i < r.count; ++i) {
+    const DcnLaunch& l = r.launch[i];
+    a.MT = l.MT; a.q_begin = l.q_begin; a.Q = l.Q; a.ksplit = l.ksplit; a.kchan = l.kchan;
+    a.ws_stride = l.ksplit > 1 ? (long long)a.NB * a.Cout * a.HW : 0;
+    if (l.kernel == DCN_LDS) {
+      // the one build above 64 KB of LDS: raised once per device, to what the largest map it takes (H*W = 256) needs
+      static bool raised[DM_MAX_DEVICES] = {false};
+      if (dm_ensure_lds_limit(reinterpret_cast<const void*>(&deform_conv_lds_kernel), 16 * 2 * 2 * 3 * 2 * 128 + 4 * 2 * 2 * 8 * 256,
+                              raised) != DM_OK)
+        return DM_ERR_LAUNCH;
+    }
+    const dim3 grid((unsigned)l.grid_x, (unsigned)l.grid_y), block((unsigned)l.threads);
+    const size_t lds = (size_t)l.lds_bytes;
+    const int tiles = l.grid_x / a.NB;                                    // (band kernel: tiles per image)
+    switch (dcn_build(l.kernel, l.p[0], l.p[1], l.p[2], l.p[3])) {
+      DCN_GENERIC_CASE(2, 2, 1, 1);
+      case dcn_build(DCN_LDS, 0, 0, 0, 0): DM_LAUNCH(deform_conv_lds_kernel, grid, block, lds, st, a); break;
+      case dcn_build(DCN_C256, 0, 0, 0, 0): DM_LAUNCH(deform_conv_c256_kernel, grid, block, lds, st, a); break;
+      DCN_BAND_CASE(1, 2, 4); DCN_BAND_CASE(1, 2, 7); DCN_BAND_CASE(2, 1, 4); DCN_BAND_CASE(2, 1, 7);
+      DCN_BAND_CASE(1, 4, 4); DCN_BAND_CASE(1, 4, 7); DCN_BAND_CASE(4, 1, 4); DCN_BAND_CASE(2, 2, 7);
+      DCN_GENERIC_CASE(2, 2, 2, 1); DCN_GENERIC_CASE(1, 4, 1, 1);
+      default: return DM_ERR_UNSUPPORTED;                                 // (a route that names no build: a bug in dcn_route)
+    }
+    const int rc = dm_check_launch();
     if (rc != DM_OK) return rc;
-    a.q_begin = a.Q;
-    a.Q = Q;
-    return launch_dcn<2, 2, 1, 1>(a, st);
   }
-  DM_LAUNCH(deform_conv_c256_kernel, dim3(NTiles), dim3(256), lds_bytes, st, a);
+  if (!r.reduce) return DM_OK;
+  // out = relu?(the splits of launch[0], added in index order); four per thread where everything is 16-byte aligned
+  const long long total = a.ws_stride;
+  const bool v4 = (total & 3) == 0 && ((((uintptr_t)a.ws) | ((uintptr_t)a.out)) & 15) == 0;
+  DM_LAUNCH(dcn_splitk_reduce_kernel, dim3((unsigned)min((long long)4096, ((v4 ? total / 4 : total) + 255) / 256)), dim3(256), 0, st, a.ws,
+            v4 ? a.ksplit : -a.ksplit, a.ws_stride, total, a.relu, a.out);
   return dm_check_launch();
+}
+
+// a: DcnArgs() or, for the chained 1x1, its members filled in (dm_deform_conv_tout_fwd)
+static int deform_conv_fwd_impl(DcnArgs a, const float* x, const float* offset, int NB, int C, int H, int W, const float* w_packed,
+                                int Cout, int deform_groups, int relu, float* out, float* ws, long long ws_floats, dm_stream_t stream) {
+  const bool null_arg = !x || !offset || !w_packed || !out;
+  if (null_arg && a.M2 == 0) return DM_ERR_INVALID_ARG;       // (the chained call answers for its shape first: dcn_route)
+  const DcnRoute r = dcn_route(dcn_call(NB, C, H, W, Cout, deform_groups, relu, ws ? ws_floats : 0, a.M2));
+  if (r.rc != DM_OK || r.count == 0) return r.rc;
+  if (null_arg) return DM_ERR_INVALID_ARG;
+  a.x = x; a.offset = offset; a.NB = NB; a.C = C; a.H = H; a.W = W; a.HW = H * W; a.Q = NB * H * W;
+  a.wp = w_packed; a.Cout = Cout; a.CoutP = dm_conv_packed_cout(Cout); a.KQ = (C + 7) / 8 * 2; a.dg = deform_groups;
+  a.relu = relu & 1; a.out = out;
+  a.ws = (ws && ws_floats > 0) ? ws : nullptr;
+  a.ws_floats = a.ws ? ws_floats : 0;
+  return dcn_emit(r, a, (hipStream_t)stream);
 }
 
 }  // namespace
 
-struct DcnTout {      // the chained 1x1 (nullptr members: plain DCN)
-  const float* w2t = nullptr;
-  const float* b2 = nullptr;
-  float* out2 = nullptr;
-  int M2 = 0, out2_ct = 0;
-};
-static int deform_conv_fwd_impl(const float* x, const float* offset, int NB, int C, int H, int W,
-                                const float* w_packed, int Cout, int deform_groups, int relu, float* out, float* ws,
-                                long long ws_floats, dm_stream_t stream, const DcnTout* tout = nullptr);
-
 extern "C" int dm_deform_conv_fwd(const float* x, const float* offset, int NB, int C, int H, int W,
                                   const float* w_packed, int Cout, int deform_groups, int relu, float* out,
                                   dm_stream_t stream) {
-  return deform_conv_fwd_impl(x, offset, NB, C, H, W, w_packed, Cout, deform_groups, relu, out, nullptr, 0, stream);
+  return deform_conv_fwd_impl(DcnArgs(), x, offset, NB, C, H, W, w_packed, Cout, deform_groups, relu, out, nullptr, 0, stream);
 }
 
-// (ABI 21) dm_deform_conv_fwd with a caller-owned workspace: a launch that leaves most of the chip idle (the <= 100-RoI
-// inference calls) splits its channel loop over up to eight workgroups per tile; a second kernel adds the splits in index
-// order (+ ReLU).  Same bits every run; they differ from dm_deform_conv_fwd's by the association of the channel sums.
+// (ABI 21) dm_deform_conv_fwd with a caller-owned workspace: dcn_route may split the channel loop (dcn_choose_split).
+// dm_deform_conv_splitk_floats: an upper bound on what a split of this shape uses, which the route honours (0: no launch of
+// this shape splits; tests/test_dcn_plan_cpu.py holds the route to both).
 extern "C" long long dm_deform_conv_splitk_floats(int NB, int C, int H, int W, int Cout) {
   if (NB <= 0 || C < 32 || H <= 0 || W <= 0 || Cout <= 0) return 0;
   const long long wgs = (long long)dm_ceil_div(Cout, 128) * dm_ceil_div((long long)NB * H * W, 128);
@@ -1346,153 +1467,42 @@ extern "C" long long dm_deform_conv_splitk_floats(int NB, int C, int H, int W, i
 extern "C" int dm_deform_conv_fwd_ws(const float* x, const float* offset, int NB, int C, int H, int W,
                                      const float* w_packed, int Cout, int deform_groups, int relu, float* out,
                                      float* workspace, long long workspace_floats, dm_stream_t stream) {
-  return deform_conv_fwd_impl(x, offset, NB, C, H, W, w_packed, Cout, deform_groups, relu, out, workspace, workspace_floats, stream);
+  return deform_conv_fwd_impl(DcnArgs(), x, offset, NB, C, H, W, w_packed, Cout, deform_groups, relu, out, workspace, workspace_floats, stream);
 }
 
-// Does this shape take the band kernel in the wave layout that can chain the 1x1 (a wave = 32 pixels x all couts)?
-static bool dcn_tout_shape_ok(int NB, int C, int H, int W, int Cout, int M2) {
-  if (NB <= 0 || C <= 0 || H <= 0 || W <= 0 || Cout != C || M2 <= 0) return false;
-  const int HW = H * W, CoutP = dm_conv_packed_cout(Cout);
-  const int max_rows = (W - 1 + 128 + W - 1) / W;
-  if (!(H >= 16 && (W & 3) == 0 && 8 * 16 * W / 4 <= 7 * 256 && (16 - max_rows) / 2 >= DCN_NEAR_ROWS && HW > 256 && HW < 65536 &&
-        (CoutP == 64 || CoutP == 128) && Cout > 32 && Cout == CoutP))
-    return false;
-  const bool narrow = 8 * 16 * W / 4 <= 4 * 256;
-  const bool few = (long long)NB * dm_ceil_div(HW, 128) * 4 < (long long)dm_num_cus() * 3;
-  if (few) return false;                                   // (one cout tile per wave there: 2-4 x the workgroups, worth more)
-  if (CoutP == 128 && !narrow) return false;               // <2, 2, 7>: two waves share a pixel column
-  return dm_ceil_div(M2, 32) <= (CoutP / 32 + 1) / 2;
+// (added to ABI 28) What the three entry points here would launch for these host arguments: dcn_route's own value, the one
+// dcn_emit enqueues (the header has the record layout).  Nothing below touches HIP but dm_num_cus().
+extern "C" int dm_deform_conv_plan(int NB, int C, int H, int W, int Cout, int deform_groups, int relu, long long workspace_floats,
+                                   int M2, int* records, int max_records) {
+  if (!records || max_records < DM_DCN_PLAN_MAX_LAUNCHES || workspace_floats < 0 || M2 < 0) return DM_ERR_INVALID_ARG;
+  if (M2 > 0 && workspace_floats > 0) return DM_ERR_INVALID_ARG;          // (the chained call takes no workspace)
+  const DcnRoute r = dcn_route(dcn_call(NB, C, H, W, Cout, deform_groups, M2 > 0 ? 1 : relu, workspace_floats, M2));
+  if (r.rc != DM_OK) return r.rc;
+  for (int l = 0; l < r.count; ++l) {
+    const DcnLaunch& m = r.launch[l];
+    const int rec[DM_DCN_PLAN_INTS] = {m.kernel, m.p[0], m.p[1], m.p[2], m.p[3], m.threads, m.MT, m.q_begin, m.Q, m.grid_x, m.grid_y,
+                                       m.ksplit, m.kchan, m.lds_bytes, r.reduce ? 1 : 0};
+    for (int i = 0; i < DM_DCN_PLAN_INTS; ++i) records[l * DM_DCN_PLAN_INTS + i] = rec[i];
+  }
+  return r.count;
 }
 
+// Does this shape take the band build that can chain the 1x1 (a wave = 32 pixels x all couts)?  Route it and see.
 extern "C" int dm_deform_conv_tout_supported(int NB, int C, int H, int W, int Cout, int M2) {
-  return dcn_tout_shape_ok(NB, C, H, W, Cout, M2) ? 1 : 0;
+  if (M2 <= 0) return 0;
+  const DcnRoute r = dcn_route(dcn_call(NB, C, H, W, Cout, 1, 1, 0, M2));
+  return (r.rc == DM_OK && r.count == 1) ? 1 : 0;
 }
 
-// (ABI 27) DCN 3x3 + ReLU + the 1x1 convolution + bias + ReLU behind it (SFMStage.fuse_conv[1] -> fuse_transform_out,
-// mmdet/models/roi_heads/mask_heads/dynamask_head.py:117-121) in ONE launch: out2[:, :M2] of a tensor with out2_ch_total
-// channels; w2t = the 1x1 weight transposed to [Cout][32-padded M2] (zeros in the padding); out_dcn: NULL (inference: the
-// DCN output is never written) or [NB, Cout, H, W] to keep relu(DCN) as well.  DM_ERR_UNSUPPORTED when
-// dm_deform_conv_tout_supported() says 0 -- the caller then launches the two operators.  Same bits as those two launches.
+// (ABI 27) DCN 3x3 + ReLU + the 1x1 convolution + bias + ReLU behind it in ONE launch (the header has the contract).
+// DM_ERR_UNSUPPORTED where dm_deform_conv_tout_supported() says 0 -- the caller then launches the two operators.
 extern "C" int dm_deform_conv_tout_fwd(const float* x, const float* offset, int NB, int C, int H, int W, const float* w_packed,
                                        int Cout, int deform_groups, const float* w2t, const float* b2, int M2, float* out2,
                                        int out2_ch_total, float* out_dcn, dm_stream_t stream) {
   if (!w2t || !b2 || !out2 || M2 <= 0 || M2 > out2_ch_total) return DM_ERR_INVALID_ARG;
-  if (NB == 0) return DM_OK;
-  if (!dcn_tout_shape_ok(NB, C, H, W, Cout, M2)) return DM_ERR_UNSUPPORTED;
-  DcnTout t;
-  t.w2t = w2t; t.b2 = b2; t.out2 = out2; t.M2 = M2; t.out2_ct = out2_ch_total;
-  // (out == NULL is the "do not store" request; the implementation needs a non-null pointer to get past its checks)
-  return deform_conv_fwd_impl(x, offset, NB, C, H, W, w_packed, Cout, deform_groups, 1, out_dcn ? out_dcn : out2, nullptr, 0, stream,
-                              &t) ;
-}
-
-static int deform_conv_fwd_impl(const float* x, const float* offset, int NB, int C, int H, int W,
-                                const float* w_packed, int Cout, int deform_groups, int relu, float* out, float* ws,
-                                long long ws_floats, dm_stream_t stream, const DcnTout* tout) {
-  if (!x || !offset || !w_packed || !out) return DM_ERR_INVALID_ARG;
-  if (relu & 16) return DM_ERR_UNSUPPORTED;      // (flag bit 4, the bf16x3 mode of dm_conv2d_fwd: the DCN stays exact fp32)
-  if (NB < 0 || C <= 0 || H <= 0 || W <= 0 || Cout <= 0 || deform_groups <= 0 || C % deform_groups != 0)
-    return DM_ERR_INVALID_ARG;
-  if ((long long)NB * H * W > 0x7fffffffLL) return DM_ERR_INVALID_ARG;
-  if ((C / deform_groups) % 8 != 0) return DM_ERR_UNSUPPORTED;  // channel chunk must not straddle a deformable group
-  if (W < 2) return DM_ERR_UNSUPPORTED;                         // the gather loads row pairs
-  if (NB == 0) return DM_OK;
   DcnArgs a;
-  a.x = x; a.offset = offset; a.NB = NB; a.C = C; a.H = H; a.W = W; a.HW = H * W; a.Q = NB * H * W;
-  a.wp = w_packed; a.Cout = Cout; a.CoutP = dm_conv_packed_cout(Cout); a.KQ = (C + 7) / 8 * 2; a.dg = deform_groups;
-  a.relu = relu & 1; a.out = out;
-  a.ws = (ws && ws_floats > 0) ? ws : nullptr;
-  a.ws_floats = a.ws ? ws_floats : 0;
-  if (tout) {
-    a.w2t = tout->w2t; a.b2 = tout->b2; a.out2 = tout->out2; a.M2 = tout->M2; a.w2_ld = dm_ceil_div(tout->M2, 32) * 32;
-    a.out2_ct = tout->out2_ct;
-    a.store_out = (out != tout->out2) ? 1 : 0;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  // Tiles.  Every variant runs 4-wave workgroups, two per CU (8-wave tiles run alone on their CU and lose: 128 x 128 from
-  // global memory 1.81 vs 1.59 ms at 256 channels, 256 x 128 from LDS -1 % in the two-stream step).  A wave holds 64
-  // accumulator registers, so a workgroup covers 128 couts x 128 pixels, or 128 x 64 where the gather runs from global
-  // memory -- or 256 couts x 64 pixels on the small maps (deform_conv_c256_kernel: every cout of a pixel in one
-  // workgroup, a sample gathered once; the waves own different couts and read their weights straight from L2).
-  // Launches that leave most of the chip idle (a handful of RoIs: real inference) are bound by the time
-  // of one workgroup; 64 x 64 tiles give four times the workgroups of the 128 x 128 LDS kernel
-  // (14 x 14, 8 RoIs: 0.208 -> 0.108 ms, 32 RoIs: 0.213 -> 0.168 ms; from 64 RoIs on the big tiles win).
-  // Same products in the same order in every variant: results do not depend on the choice.
-  {
-    // large maps: gather in the consuming wave from an LDS band of 16 rows (the 8 band planes of a chunk must fit the
-    // 7 float4 per thread of the widest staging build: W <= 56).
-    // Every launch size of an eligible shape takes this kernel (rows must not depend on the batch).
-    const int max_rows = (W - 1 + 128 + W - 1) / W;                         // rows a 128-pixel tile can span
-    if (H >= 16 && (W & 3) == 0 && 8 * 16 * W / 4 <= 7 * 256 && (16 - max_rows) / 2 >= DCN_NEAR_ROWS && a.HW > 256 &&
-        a.HW < 65536 && (a.CoutP == 64 || a.CoutP == 128) && Cout > 32) {
-      const bool narrow = 8 * 16 * W / 4 <= 4 * 256;                        // band planes fit 4 float4 per thread
-      // a handful of RoIs (real inference): the launch is bound by the time of one workgroup -- one cout tile per
-      // wave, the waves sharing a pixel column (2-4 x the workgroups, 1/2-1/4 of the K-loop time each; same bits)
-      bool few = (long long)NB * dm_ceil_div(a.HW, 128) * 4 < (long long)dm_num_cus() * 3;
-      // ... unless the caller brought a workspace: a workgroup's time is its number of chunks times a load round trip
-      // (~3.5 us) whatever it computes per chunk, so the full layout (every cout of 128 pixels: one gather per sample, four
-      // times the MFMAs per round trip) with the K loop split (dcn_choose_split's cost model, <= 24 RoIs) beats it:
-      // 16 / 24 detections 0.5845 / 0.733 -> 0.578 / 0.712 ms (profiles/r06_infer_notes.txt (6))
-      if (few && a.ws && NB <= 24 && !tout) few = false;
-      if (a.CoutP == 64) {
-        if (few) return narrow ? launch_dcn_band<1, 2, 4>(a, st) : launch_dcn_band<1, 2, 7>(a, st);
-        return narrow ? launch_dcn_band<2, 1, 4>(a, st) : launch_dcn_band<2, 1, 7>(a, st);
-      }
-      if (few) return narrow ? launch_dcn_band<1, 4, 4>(a, st) : launch_dcn_band<1, 4, 7>(a, st);
-      return narrow ? launch_dcn_band<4, 1, 4>(a, st) : launch_dcn_band<2, 2, 7>(a, st);
-    }
-  }
-  if (tout) return DM_ERR_UNSUPPORTED;                      // (dcn_tout_shape_ok mirrors the conditions above)
-  // A handful of RoIs: 64 x 64 tiles (four times the workgroups of the 128 x 128 LDS kernel) -- unless the caller brought a
-  // workspace and the map takes the LDS kernel: then that kernel with its K loop split (dcn_choose_split: up to 8 ways at
-  // <= 24 RoIs, 3 above) is the faster way to fill the chip (round 6: the 16- / 32-detection inference calls 0.652 / 0.949 ->
-  // 0.626 / 0.918 ms; the 14 x 14 DCN was their largest launch, 90 us at 16 RoIs).
-  const bool lds_split = a.ws && Cout > 64 && a.HW >= 128 && a.HW <= 256 && (a.HW & 3) == 0;
-  if (!lds_split && Cout > 64 &&
-      (long long)dm_ceil_div(a.CoutP, 128) * dm_ceil_div(a.Q, 128) * 20 <= (long long)dm_num_cus() * 9)
-    return launch_dcn<2, 2, 1, 1>(a, st);
-  if (Cout > 64 && a.HW >= 128 && a.HW <= 256 && (a.HW & 3) == 0 && (C / deform_groups) % 8 == 0) {
-    // small maps (14x14): planes in LDS, 128 x 128 tile
-    a.MT = dm_ceil_div(a.CoutP, 128);
-    const int NTiles = dm_ceil_div(a.Q, 128);
-    // A ring + B ring (2 x 3 taps x 2 quads x 128 float4 each) + 2 plane buffers of 2 images x 8 channels
-    const size_t lds_bytes = 16 * ((size_t)2 * 2 * 3 * 2 * 128) + (size_t)4 * 2 * 2 * 8 * a.HW;
-    static bool attr_lds[DM_MAX_DEVICES] = {false};      // once per device, for the largest map this path takes (H*W = 256)
-    if (dm_ensure_lds_limit(reinterpret_cast<const void*>(&deform_conv_lds_kernel), 16 * 2 * 2 * 3 * 2 * 128 + 4 * 2 * 2 * 8 * 256,
-                            attr_lds) != DM_OK)
-      return DM_ERR_LAUNCH;
-    // rounds (see conv_igemm.hip): the LDS kernel runs two workgroups per CU; the pixels of a nearly empty
-    // last round go to a second launch with 64 x 64 tiles (same bits): 512 RoIs 1.24 -> 1.19 ms.  Only
-    // for small remainders (the 64 x 64 build is slower per pixel: at 0.5 of a round the split loses), and
-    // not when the caller overlaps launches on a second stream (flag bit 3: measured 259 vs 251 img/s).
-    static const int tail_mode = getenv("DM_DCN_TAIL") ? atoi(getenv("DM_DCN_TAIL")) : 1;
-    const int slots = 2 * dm_num_cus();
-    if (a.CoutP == 256) {
-      // 256 couts: one workgroup per 64 pixels holds every cout (deform_conv_c256_kernel: each sample gathered once).
-      // Launches that split their K loop (a caller's workspace and less than one round of tiles) stay on the kernel below.
-      dcn_choose_split(a, (long long)a.MT * NTiles, slots, a.ws_floats, true);
-      if (a.ksplit == 1) return launch_dcn_c256(a, tail_mode && !(relu & 8), st);
-    }
-    const int full_rounds = (a.MT * NTiles) / slots;
-    const int rem = a.MT * NTiles - full_rounds * slots;
-    if (tail_mode && !(relu & 8) && full_rounds >= 1 && rem > 0 && rem * 20 <= 3 * slots) {
-      const int n_main = full_rounds * slots / a.MT;
-      const int Q = a.Q;
-      a.Q = n_main * 128;
-      DM_LAUNCH(deform_conv_lds_kernel, dim3(a.MT * n_main), dim3(256), lds_bytes, st, a);
-      int rc = dm_check_launch();
-      if (rc != DM_OK) return rc;
-      a.q_begin = a.Q;
-      a.Q = Q;
-      return launch_dcn<2, 2, 1, 1>(a, st);
-    }
-    dcn_choose_split(a, (long long)a.MT * NTiles, slots, a.ws_floats, true);
-    DM_LAUNCH(deform_conv_lds_kernel, dim3(a.MT * NTiles, a.ksplit), dim3(256), lds_bytes, st, a);
-    return dcn_finish_split(a, a.relu, a.out, st);
-  }
-  if (Cout > 64 && (long long)dm_ceil_div(a.CoutP, 128) * dm_ceil_div(a.Q, 64) * 20 <= (long long)dm_num_cus() * 9)
-    return launch_dcn<2, 2, 1, 1>(a, st);                 // same rule for the 128 x 64 tiles (28 x 28, 8 RoIs: 0.081 -> 0.056 ms)
-  if (Cout > 64) return launch_dcn<2, 2, 2, 1>(a, st);    // 128 couts x 64 px
-  if (Cout > 32) return launch_dcn<2, 2, 1, 1>(a, st);    // 64 x 64 (2.57 -> 2.28 ms at 64 channels, 56x56)
-  return launch_dcn<1, 4, 1, 1>(a, st);                   // 32 x 128 (4 waves)
+  a.w2t = w2t; a.b2 = b2; a.out2 = out2; a.M2 = M2; a.w2_ld = dm_ceil_div(M2, 32) * 32; a.out2_ct = out2_ch_total;
+  // (out_dcn == NULL is the "do not store" request: the kernel gets out2 as a stand-in and store_out = 0)
+  a.store_out = (out_dcn && out_dcn != out2) ? 1 : 0;
+  return deform_conv_fwd_impl(a, x, offset, NB, C, H, W, w_packed, Cout, deform_groups, 1, out_dcn ? out_dcn : out2, nullptr, 0, stream);
 }

@@ -977,6 +977,35 @@ def deform_conv(x, offset, w_packed, cout, deform_groups, relu=False, out=None):
     return out
 
 
+DCN_PLAN_FIELDS = ('kernel', 'P0', 'P1', 'P2', 'P3', 'threads', 'MT', 'q_begin', 'Q', 'grid_x', 'grid_y', 'ksplit', 'kchan',
+                   'lds_bytes', 'reduce')
+DCN_KERNELS = ('generic', 'lds', 'c256', 'band')          # field 'kernel' of a plan record
+
+
+def deform_conv_plan_raw(NB, C, H, W, cout, deform_groups, flags=0, workspace_floats=0, m2=0):
+    """dm_deform_conv_plan: (return code, records).  The code is the number of launches or the (negative) error the call
+    with these arguments would return; ``flags`` are dm_deform_conv_fwd's.  Host only: no tensor, no device."""
+    consts = _abi.load()[1]
+    n, cap = consts['DM_DCN_PLAN_INTS'], consts['DM_DCN_PLAN_MAX_LAUNCHES']
+    assert len(DCN_PLAN_FIELDS) == n
+    rec = (ctypes.c_int * (n * cap))(*([-1] * (n * cap)))
+    rc = lib().dm_deform_conv_plan(int(NB), int(C), int(H), int(W), int(cout), int(deform_groups), int(flags),
+                                   int(workspace_floats), int(m2), rec, cap)
+    return rc, [dict(zip(DCN_PLAN_FIELDS, rec[i * n:(i + 1) * n])) for i in range(max(rc, 0))]
+
+
+def deform_conv_plan(NB, C, H, W, cout, deform_groups, relu=False, overlapped=False, workspace_floats=0, m2=0):
+    """The launches ``deform_conv`` (``m2`` > 0: ``deform_conv_tout``) would make for this shape, as the launcher's own
+    route says (include/dynamask_hip.h, dm_deform_conv_plan): a list of one or two dicts with the keys DCN_PLAN_FIELDS
+    (two: a launch whose underfull last round goes to a second launch).  Raises where the call would fail.
+    ``workspace_floats`` > 0: the dm_deform_conv_fwd_ws call."""
+    rc, recs = deform_conv_plan_raw(NB, C, H, W, cout, deform_groups, (1 if relu else 0) | (8 if overlapped else 0),
+                                    workspace_floats, m2)
+    if rc < 0:
+        check(rc, 'dm_deform_conv_plan')
+    return recs
+
+
 def deform_conv_tout_supported(x, cout, m2):
     """Can ``deform_conv_tout`` take this shape (else: ``deform_conv`` + ``conv2d``)?"""
     NB, C, H, W = x.shape

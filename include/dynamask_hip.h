@@ -62,7 +62,8 @@ const char* dm_error_string(int code);
  * (section K25); Hybrid Task Cascade's resize, post-activation addend and RoIAlign-add (section K26); Grid R-CNN's
  * GroupNorm, neighbour fusion, grouped 4x4 stride-2 deconvolution and box vote (section K27); the convolution launcher's
  * own report of its launches, dm_conv2d_plan (section K5/K6) and dm_conv2d_group_plan (section K25); Double-Head R-CNN's
- * rescaled RoIAlign and global average pool (section K28). */
+ * rescaled RoIAlign and global average pool (section K28); the DCN forward launcher's route, dm_deform_conv_plan
+ * (section K8). */
 #define DM_ABI_VERSION 28 /* the one definition: dm_abi_version(), dm_build_info() and _lib.ABI_VERSION read it */
 int dm_abi_version(void);
 /* "libdynamask_hip abi=N arch=gfx950 compiler=<clang version> flags=<the product-wide flags of dynamask_amd/build.py>"
@@ -312,11 +313,33 @@ int dm_deform_conv_tout_fwd(const float* x, const float* offset, int NB, int C, 
 /* (ABI 21) dm_deform_conv_fwd with a caller-owned workspace: a launch that leaves most of the chip idle (the <= 100-RoI
  * inference calls) splits its channel loop over up to eight workgroups per tile; a second kernel adds the splits in index
  * order (+ ReLU).  Same bits every run; they differ from dm_deform_conv_fwd's by the association of the channel sums.
- * dm_deform_conv_splitk_floats: the workspace with which this shape may split as far as it wants to (0: it would not). */
+ * dm_deform_conv_splitk_floats: an upper bound on the workspace a split of this shape uses, which dm_deform_conv_plan honours
+ * (0: no launch of this shape splits; more than this changes nothing). */
 long long dm_deform_conv_splitk_floats(int NB, int C, int H, int W, int Cout);
 int dm_deform_conv_fwd_ws(const float* x, const float* offset, int NB, int C, int H, int W, const float* w_packed, int Cout,
                           int deform_groups, int relu, float* out, float* workspace, long long workspace_floats,
                           dm_stream_t stream);
+
+/* (added to ABI 28) The launches dm_deform_conv_fwd / dm_deform_conv_fwd_ws / dm_deform_conv_tout_fwd would make for these
+ * HOST arguments: the route the launcher decides on, the very value it then enqueues (nothing is launched, no device is
+ * needed -- without one the compute-unit count is taken as 256).  Arguments as dm_deform_conv_fwd_ws's, without the
+ * pointers: workspace_floats = 0 for the call without a workspace; M2 = 0: the plain DCN, M2 > 0: the dm_deform_conv_tout_fwd
+ * call with that M2 (it has neither flags nor a workspace: `relu` is ignored, DM_ERR_INVALID_ARG with a workspace).  The
+ * DM_DCN_TAIL knob applies as it does to launches (read once per process).
+ * records: HOST array of max_records (>= DM_DCN_PLAN_MAX_LAUNCHES) x DM_DCN_PLAN_INTS ints.  Returns the number of launches
+ * (0: NB = 0; 1; 2: a launch on a 14 x 14-sized map that sends its underfull last round of workgroups to a second launch) or
+ * the error code the call would return, and then writes nothing.  Record l, ints [l * DM_DCN_PLAN_INTS ..):
+ *   0 kernel: 0 deform_conv_kernel, 1 deform_conv_lds_kernel, 2 deform_conv_c256_kernel, 3 deform_conv_band_kernel;
+ *   1 .. 4 its template parameters: WGM, WGN, WM, WN (kernel 0); WM, WGM, XR, 0 (kernel 3); zeros (kernels 1, 2);
+ *   5 threads per workgroup;  6 MT: cout tiles (1 where a workgroup holds every cout: kernels 2 and 3);
+ *   7 q_begin, 8 Q: the flat pixels [q_begin, Q) of the batch this launch covers;
+ *   9 grid x (cout tiles x pixel tiles), 10 grid y (= ksplit);
+ *   11 ksplit, 12 kchan: K splits (1: none) and channels per split (0 without a split);
+ *   13 dynamic LDS bytes;  14: 1 when the split-K reduction follows this launch. */
+#define DM_DCN_PLAN_INTS 15
+#define DM_DCN_PLAN_MAX_LAUNCHES 2
+int dm_deform_conv_plan(int NB, int C, int H, int W, int Cout, int deform_groups, int relu, long long workspace_floats, int M2,
+                        int* records, int max_records);
 
 /* ---------------------------------------------------------------------------
  * K11  x2 bilinear upsampling.

@@ -1,7 +1,8 @@
 """deform_conv_c256_kernel: the 14 x 14 DCN with every one of its 256 output channels in one workgroup (256 couts x 64
 flat pixels, four waves that own 64 couts each and read their weights from global memory).  It takes the launches of
-maps with 128 <= H*W <= 256 and 225..256 output channels from the batch size on at which the 64 x 64 tiles stop:
-    2 * ceil(NB * H * W / 128) * 20 > 9 * compute units        (38 RoIs of 14 x 14 on 256 CUs)
+maps with 128 <= H*W <= 256 and 225..256 output channels from the batch size on at which the 64 x 64 tiles stop -- which
+batch that is, and where a launch is cut in two, the tests ask the launcher (ops.deform_conv_plan: its own route; 38 RoIs
+of 14 x 14 on 256 CUs).
 Every variant of the DCN forms the same products in the same order, so its rows are compared bit for bit with those
 of launches small enough for the 64 x 64 kernel, and with the float64 oracle through the fp64 triangle."""
 import pytest
@@ -29,20 +30,23 @@ def ops():
     return o
 
 
-def _cus():
-    return torch.cuda.get_device_properties(0).multi_processor_count
+def _plan(ops, n, H, W, cout=C):
+    return ops.deform_conv_plan(n, C, H, W, cout, 1)
 
 
-def _takes_small_tiles(n, H, W):
-    return 2 * -(-n * H * W // 128) * 20 <= 9 * _cus()
+def _is_64x64(rec):
+    return (rec['kernel'], rec['P0'], rec['P1'], rec['P2'], rec['P3']) == (0, 2, 2, 1, 1)
 
 
-def _threshold(H, W):
-    """Smallest batch the routing rule of deform_conv_fwd_impl gives to the new kernel (no workspace, CoutP = 256)."""
+def _threshold(ops, H, W, cout=C):
+    """Smallest batch the launcher gives to the c256 kernel (no workspace); SMALL and 3 RoIs take the 64 x 64 build."""
     n = 1
-    while _takes_small_tiles(n, H, W):
+    while ops.DCN_KERNELS[_plan(ops, n, H, W, cout)[0]['kernel']] != 'c256':
         n += 1
-    assert _takes_small_tiles(SMALL, H, W) and _takes_small_tiles(3, H, W)
+    for small in (SMALL, 3):
+        one, = _plan(ops, small, H, W, cout)
+        assert _is_64x64(one) and one['ksplit'] == 1
+    assert n > SMALL
     return n
 
 
@@ -69,7 +73,7 @@ def test_c256_rows_have_the_bits_of_the_64x64_kernel_and_match_f64(ops, H, W, dg
     images and the last tile is ragged; 256: the LDS maximum, tiles end with the image), deformable groups 1, 2 and 4: EVERY
     row equals the row of a 16-RoI launch, the first rows those of a 3-RoI launch; the first and the last RoI (void
     taps, border clamps) against the oracle in float64, and with zero offsets against F.conv2d."""
-    T = _threshold(H, W)
+    T = _threshold(ops, H, W)
     x, off, w = _inputs(T + 1, H, W, dg)
     xd, offd = x.cuda(), off.cuda()
     wq = ops.pack_conv_weight(w.cuda())
@@ -93,15 +97,17 @@ def test_c256_last_round_goes_to_a_second_launch_with_the_same_bits(ops):
     second launch of 64 x 64 tiles that starts in the middle of the batch: the smallest such batch of 14 x 14 maps,
     rows from the first tile, around the seam and from the end against small launches."""
     H = W = 14
-    slots = 2 * _cus()
-    N = -(-slots * 64 // (H * W))
-    while not 0 < -(-N * H * W // 64) % slots <= 3 * slots // 20:
+    N = _threshold(ops, H, W)
+    while len(_plan(ops, N, H, W)) != 2:
         N += 1
+    main, tail = _plan(ops, N, H, W)
+    assert ops.DCN_KERNELS[main['kernel']] == 'c256' and _is_64x64(tail)
+    assert main['q_begin'] == 0 and main['Q'] == tail['q_begin'] and tail['Q'] == N * H * W
     x, off, w = _inputs(N, H, W, 2, seed=10)
     xd, offd = x.cuda(), off.cuda()
     wq = ops.pack_conv_weight(w.cuda())
     big = ops.deform_conv(xd, offd, wq, C, 2, relu=True)
-    seam = (-(-N * H * W // 64) // slots) * slots * 64 // (H * W)          # the RoI the second launch starts in
+    seam = tail['q_begin'] // (H * W)                     # the RoI the second launch starts in
     for lo in (0, max(0, seam - 8), N - SMALL):
         hi = min(N, lo + SMALL)
         assert torch.equal(big[lo:hi], ops.deform_conv(xd[lo:hi].contiguous(), offd[lo:hi].contiguous(), wq, C, 2, relu=True)), lo
@@ -114,7 +120,7 @@ def test_c256_stores_nothing_outside_its_rows(ops, H, W):
     of a padding row would land in the next RoI's first channels)."""
     cout, dg = 250, 2
     assert ops.packed_cout(cout) == 256
-    N = _threshold(H, W) + 1
+    N = _threshold(ops, H, W, cout) + 1
     x, off, w = _inputs(N, H, W, dg, cout=cout, seed=20)
     xd, offd = x.cuda(), off.cuda()
     wq = ops.pack_conv_weight(w.cuda())
