@@ -1407,10 +1407,7 @@ int env_int(const char* name, int dflt, int lo, int hi) {
 }
 
 void roi_load_knobs() {
-  RoiKnobs k;
-  k.sort = env_int("DM_ROI_SORT", 1, 0, 1);
-  k.sort_min = env_int("DM_ROI_SORT_MIN", 192, 1, 1024);
-  g_roi_knobs = k;
+  g_roi_knobs = {env_int("DM_ROI_SORT", 1, 0, 1), env_int("DM_ROI_SORT_MIN", 192, 1, 1024)};
   g_roi_knobs_loaded = true;
 }
 
@@ -1419,29 +1416,174 @@ const RoiKnobs& roi_knobs() {
   return g_roi_knobs;
 }
 
-int fill_args(RoiArgs& a, const int* H, const int* W, const float* spatial_scales, int num_levels, int B, int C,
-              const float* rois, int N, int P, int sampling_ratio, float finest_scale) {
-  if (!H || !W || !spatial_scales || (!rois && N > 0)) return DM_ERR_INVALID_ARG;
-  if (num_levels < 1 || num_levels > DM_MAX_LEVELS || B <= 0 || C <= 0 || N < 0 || P <= 0 || sampling_ratio < 0)
-    return DM_ERR_INVALID_ARG;
-  a.L = num_levels; a.B = B; a.C = C; a.rois = rois; a.N = N; a.P = P; a.sr = sampling_ratio;
-  a.finest = finest_scale;
-  a.rsf = 1.0f;
-  for (int l = 0; l < DM_MAX_LEVELS; ++l) {
-    a.H[l] = l < num_levels ? H[l] : 0;
-    a.W[l] = l < num_levels ? W[l] : 0;
-    a.scale[l] = l < num_levels ? spatial_scales[l] : 0.f;
-    a.feat[l] = nullptr;
-    a.gfeat[l] = nullptr;
-    if (l < num_levels && (H[l] <= 0 || W[l] <= 0)) return DM_ERR_INVALID_ARG;
+// ---- host side: validate, route, emit ---------------------------------------------------------------------------------
+// roi_route decides everything about the launches of a call from numbers alone (no pointer but the HOST arrays of map sizes,
+// no HIP call, no global but the knobs above); roi_emit enqueues exactly what the route says; dm_roi_align_plan reports the
+// same value.  Every kernel runs 256-thread workgroups, one per (RoI, chunk of CT channels) -- the order kernel one per 16
+// RoIs.  Same products in the same order whatever the route, except the tile kernel at 32 against 16 channels per workgroup
+// (bins of sampling grids above 4 x 4 differ in the last bit: dm_roi_align_add_fwd follows the forward for that reason).
+
+enum { ROI_ORDER = 0, ROI_TILE = 1, ROI_BAND = 2, ROI_GENERIC = 3, ROI_GATHER = 4 };      // RoiLaunch::kernel, as the header numbers them
+enum { ROI_FWD = 0, ROI_ADD = 1, ROI_BWD = 2 };                                           // RoiCall::entry, as the header numbers them
+
+struct RoiCall {            // what a route depends on
+  int entry, pool, L;       // pool: ROI_ADD only (1: the bins are added, 2: their 2 x 2 block means)
+  const int *H, *W;         // HOST arrays of L map sizes
+  int B, C, N, P, sr;
+  long long ws_bytes;       // the caller's workspace (0: none)
+  bool ws_aligned;          // ... is there and 16-byte aligned
+};
+
+// One launch: the ints of dm_roi_align_plan's record, in its order, and the build they name (null: roi_order_kernel, which
+// takes the workspace too)
+using RoiKernel = void (*)(RoiArgs);
+struct RoiLaunch { int kernel, p[2], grid, threads, lds_bytes, CT, order, lds_floats, levels; RoiKernel fn; };
+
+struct RoiRoute {
+  int rc = DM_OK;
+  int count = 0;            // launches (0: N = 0)
+  RoiLaunch launch[DM_ROI_PLAN_MAX_LAUNCHES];
+};
+
+// The tile kernel: a RoI's P x P bins on the 256 lanes, channels in quads, 32-bit staging offsets into every level's map
+bool roi_tile_bins(int P) { return P >= 2 && P * P <= 256; }
+bool roi_maps_fit(const RoiCall& c, int max_w) {
+  for (int l = 0; l < c.L; ++l)
+    if ((long long)c.H[l] * c.W[l] > (1 << 23) || c.W[l] >= max_w) return false;
+  return true;
+}
+bool roi_tile_ok(const RoiCall& c) { return roi_tile_bins(c.P) && c.C % 4 == 0 && roi_maps_fit(c, 0x7fffffff); }
+// The band kernel packs a map column into 20 bits
+bool roi_band_ok(const RoiCall& c) { return c.P > 16 && c.P <= 64 && c.C % 4 == 0 && roi_maps_fit(c, 1 << 20); }
+
+// Is ranking N RoIs of P x P bins worth its launch (the knobs)?  A call that says yes orders them where it takes the tile
+// kernel and has roi_order_bytes(N) of aligned workspace.
+bool roi_orders(int N, int P) {
+  const RoiKnobs& kn = roi_knobs();
+  return kn.sort && P * P >= 128 && N >= kn.sort_min && N <= kOrderMaxRois;
+}
+long long roi_order_bytes(int N) { return (long long)N * 32; }      // ordered RoI records (roi_order_kernel)
+
+// roi_unit's order 1 deals the chunks to the 8 XCDs: only where they divide evenly
+int roi_xcd_order(int C, int CT) { return dm_ceil_div(C, CT) % 8 == 0 ? 1 : 0; }
+
+// Adds the launch of one workgroup per (RoI, chunk of CT channels) to r; a grid beyond 2^31 - 1 refuses the call
+void roi_push(RoiRoute& r, const RoiCall& c, int kernel, int p0, int p1, RoiKernel fn, int CT, int order, int lds_floats,
+              size_t lds_bytes, bool levels) {
+  const long long grid = (long long)c.N * dm_ceil_div(c.C, CT);
+  if (grid > 0x7fffffffLL) r.rc = DM_ERR_UNSUPPORTED;
+  if (r.rc == DM_OK) r.launch[r.count++] = {kernel, {p0, p1}, (int)grid, 256, (int)lds_bytes, CT, order, lds_floats, levels, fn};
+}
+
+RoiRoute roi_route(const RoiCall& c) {
+  RoiRoute r;
+  auto refuse = [&r](int rc) { r.rc = rc; return r; };
+  if (c.entry == ROI_ADD && c.pool != 1 && c.pool != 2) return refuse(DM_ERR_INVALID_ARG);
+  if (!c.H || !c.W || c.L < 1 || c.L > DM_MAX_LEVELS || c.B <= 0 || c.C <= 0 || c.N < 0 || c.P <= 0 || c.sr < 0)
+    return refuse(DM_ERR_INVALID_ARG);
+  for (int l = 0; l < c.L; ++l)
+    if (c.H[l] <= 0 || c.W[l] <= 0) return refuse(DM_ERR_INVALID_ARG);
+  if (c.N == 0) return r;
+  const size_t tile_lds = (kTileFloats4 + 64) * sizeof(float4);
+  if (c.entry == ROI_FWD && roi_tile_ok(c)) {
+    // RoIs walked by level and position (roi_order_kernel, which then writes the levels), 32 channels per workgroup; else
+    // 16 channels per workgroup.  Both in the XCD-aware order (roi_unit): XCD x walks the chunks c = x (mod 8) chunk-major,
+    // so the planes it is staging from stay in its L2 across the RoIs that share them.  16 channels: same time as round 2's
+    // 32 channels in launch order (16 .. 256 channels swept at 128 .. 2048 RoIs), 29 % fewer bytes fetched from
+    // the fabric (FETCH_SIZE 113.6 -> 81.2 MB per launch, round 3's ceiling measurement).
+    const bool ordered = roi_orders(c.N, c.P) && c.ws_aligned && c.ws_bytes >= roi_order_bytes(c.N);
+    if (ordered) r.launch[r.count++] = {ROI_ORDER, {0, 0}, dm_ceil_div(c.N, 256 / kOrderTpr), 256, 0, 0, 0, 0, 1, nullptr};
+    const int CT = ordered ? 32 : 16;
+    roi_push(r, c, ROI_TILE, 0, 0, roi_align_tile_kernel<0>, CT, roi_xcd_order(c.C, CT), 0, tile_lds, !ordered);
+  } else if (c.entry == ROI_FWD && roi_band_ok(c)) {
+    // one channel quad per workgroup (swept 4 .. 32 at 128 RoIs on P2: 0.32 / 0.45 / 0.79 / 1.5 ms; roi_band_fwd is written
+    // for exactly one): the bands of a large RoI are a long chain of dependent staging round trips, so the parallelism has
+    // to come from the number of workgroups.  Full-height bands in launch order (XCD-aware chunk-major and shorter bands
+    // measured slower, round 4; a 28 KB tile with five workgroups per CU -- 96 VGPRs, 92 bytes of scratch -- too: 202 vs 188 us)
+    roi_push(r, c, ROI_BAND, kTileFloats4, 4, roi_align_band_kernel<kTileFloats4, 4>, 4, 0, 0,
+             (kTileFloats4 + kBandTabFloats4) * sizeof(float4), true);
+  } else if (c.entry == ROI_FWD) {
+    // Large output grids (C % 4 != 0, P > 64): planar LDS staging where the footprint fits, direct global taps otherwise;
+    // two launches partition the RoIs by sampling-grid class.
+    const int CT = c.P * c.P >= 1024 ? 8 : 16, tile = 6 * 1024;
+    roi_push(r, c, ROI_GENERIC, 0, 1, roi_align_kernel<false, 1>, CT, 0, tile, tile * sizeof(float), true);
+    roi_push(r, c, ROI_GENERIC, 0, 2, roi_align_kernel<false, 2>, CT, 0, tile, tile * sizeof(float), true);
+  } else if (c.entry == ROI_ADD) {
+    // the tile launch of the forward of these RoIs with the workspace it asks for (the header's promise: that call's
+    // channels per workgroup), MODE 1 / 2 adding where it stores; no other kernel has the adding modes
+    if (c.pool == 2 && (c.P & 1)) return refuse(DM_ERR_UNSUPPORTED);
+    RoiCall f = c;
+    f.entry = ROI_FWD; f.ws_bytes = dm_roi_align_workspace_bytes(c.N, c.P); f.ws_aligned = true;
+    const RoiRoute fwd = roi_route(f);
+    if (fwd.rc != DM_OK) return refuse(fwd.rc);
+    const RoiLaunch& t = fwd.launch[fwd.count - 1];
+    if (t.kernel != ROI_TILE) return refuse(DM_ERR_UNSUPPORTED);
+    roi_push(r, c, ROI_TILE, c.pool, 0, c.pool == 1 ? roi_align_tile_kernel<1> : roi_align_tile_kernel<2>, t.CT, t.order, 0, tile_lds, false);
+  } else if (c.P > 16 && c.P <= 64 && c.C % 4 == 0 && (long long)c.N * (c.C / 4) <= 0x7fffffffLL) {
+    // backward, larger output grids (the 56 x 56 extraction in front of MaskPre): gather form, one atomic per footprint cell,
+    // a channel quad per workgroup
+    roi_push(r, c, ROI_GATHER, 0, 0, roi_align_bwd_gather_kernel, 4, 0, 0, roi_adj_lds_bytes(c.P), false);
+  } else {
+    // backward, scatter form; channels per workgroup: enough workgroups to fill 256 CUs several times over
+    roi_push(r, c, ROI_GENERIC, 1, 0, roi_align_kernel<true, 0>, c.P * c.P >= 1024 ? 4 : 16, 0, 0, 0, false);
   }
-  // channels per workgroup: enough workgroups to fill 256 CUs several times over
-  a.CT = (P * P >= 1024) ? 4 : 16;
-  a.lds_floats = 0;
-  a.order = 0;
-  a.abl = 0;
-  a.out = nullptr; a.gout = nullptr; a.levels = nullptr;
+  return r;
+}
+
+// The one place a RoIAlign kernel is enqueued: the launches of route r, each with its slice of the arguments.  levels: the
+// call's levels_out, for the launch the route says writes it; sorted: the workspace of an ordered call.
+int roi_emit(const RoiRoute& r, RoiArgs a, int32_t* levels, float* sorted, hipStream_t st) {
+  for (int i = 0; i < r.count; ++i) {
+    const RoiLaunch& l = r.launch[i];
+    a.CT = l.CT; a.order = l.order; a.lds_floats = l.lds_floats;
+    a.levels = l.levels ? levels : nullptr;
+    const dim3 grid((unsigned)l.grid), block((unsigned)l.threads);
+    // the gather backward is above 64 KB of LDS from P = 49 on: raised once per device, to what the largest P it takes needs
+    // (not to the first call's own need: a 28 x 28 call in front of a 56 x 56 one left the limit where it was)
+    static bool raised[DM_MAX_DEVICES] = {false};
+    if (l.kernel == ROI_GATHER && dm_ensure_lds_limit(reinterpret_cast<const void*>(l.fn), (int)roi_adj_lds_bytes(64), raised) != DM_OK)
+      return DM_ERR_LAUNCH;
+    if (l.kernel == ROI_ORDER) {
+      DM_LAUNCH(roi_order_kernel, grid, block, 0, st, a, sorted);
+      a.sorted = sorted;                                        // (the tile launch behind it walks them)
+    } else {
+      DM_LAUNCH(l.fn, grid, block, (size_t)l.lds_bytes, st, a);
+    }
+    const int rc = dm_check_launch();
+    if (rc != DM_OK) return rc;
+  }
   return DM_OK;
+}
+
+// Every entry point: route, answer for the numbers, then for the tensors, fill in and emit.  a: the call's rois, out / gout
+// and scalars in place; feats or gfeats: its per-level maps (HOST array, the other null).  N == 0 is DM_OK whatever the
+// tensors are
+int roi_run(const RoiCall& c, const float* spatial_scales, const float* const* feats, float* const* gfeats, RoiArgs a,
+            int32_t* levels, void* workspace, dm_stream_t stream) {
+  if (!spatial_scales) return DM_ERR_INVALID_ARG;
+  const RoiRoute r = roi_route(c);
+  if (r.rc == DM_ERR_INVALID_ARG || (r.rc == DM_OK && r.count == 0)) return r.rc;
+  bool null_arg = !a.rois || (!a.out && !a.gout) || (!feats && !gfeats);
+  for (int l = 0; l < c.L && !null_arg; ++l) {
+    a.H[l] = c.H[l]; a.W[l] = c.W[l]; a.scale[l] = spatial_scales[l];
+    if (feats) a.feat[l] = feats[l]; else a.gfeat[l] = gfeats[l];
+    null_arg = !a.feat[l] && !a.gfeat[l];
+  }
+  if (null_arg) return DM_ERR_INVALID_ARG;
+  if (r.rc != DM_OK) return r.rc;
+  a.L = c.L; a.B = c.B; a.C = c.C; a.N = c.N; a.P = c.P; a.sr = c.sr;
+  return roi_emit(r, a, levels, reinterpret_cast<float*>(workspace), (hipStream_t)stream);
+}
+
+int roi_align_fwd_impl(const float* const* feats, const int* H, const int* W, const float* spatial_scales,
+                       int num_levels, int B, int C, const float* rois, int N, int P, int sampling_ratio,
+                       float finest_scale, float* out, int32_t* levels_out, void* workspace, long long workspace_bytes,
+                       dm_stream_t stream, float roi_scale_factor = 1.0f) {
+  RoiArgs a{};
+  a.rois = rois; a.finest = finest_scale; a.rsf = roi_scale_factor; a.out = out;
+  const RoiCall c = {ROI_FWD, 0, num_levels, H, W, B, C, N, P, sampling_ratio, workspace ? workspace_bytes : 0,
+                     workspace && (((uintptr_t)workspace) & 15) == 0};
+  return roi_run(c, spatial_scales, feats, nullptr, a, levels_out, workspace, stream);
 }
 
 }  // namespace
@@ -1450,82 +1592,6 @@ extern "C" int dm_reload_env_knobs(void) {
   roi_load_knobs();
   return DM_OK;
 }
-
-namespace {
-int roi_align_fwd_impl(const float* const* feats, const int* H, const int* W, const float* spatial_scales,
-                       int num_levels, int B, int C, const float* rois, int N, int P, int sampling_ratio,
-                       float finest_scale, float* out, int32_t* levels_out, void* workspace, long long workspace_bytes,
-                       dm_stream_t stream, float roi_scale_factor = 1.0f) {
-  RoiArgs a;
-  int rc = fill_args(a, H, W, spatial_scales, num_levels, B, C, rois, N, P, sampling_ratio, finest_scale);
-  if (rc != DM_OK) return rc;
-  a.rsf = roi_scale_factor;
-  if (N == 0) return DM_OK;
-  if (!feats || !out) return DM_ERR_INVALID_ARG;
-  for (int l = 0; l < num_levels; ++l) {
-    if (!feats[l]) return DM_ERR_INVALID_ARG;
-    a.feat[l] = feats[l];
-  }
-  if (N == 0) return DM_OK;
-  a.out = out;
-  a.levels = levels_out;
-  const RoiKnobs& kn = roi_knobs();
-  bool tile_ok = P * P <= 256 && P >= 2 && C % 4 == 0;
-  for (int l = 0; l < num_levels; ++l) tile_ok = tile_ok && (long long)H[l] * W[l] <= (1 << 23);   // 32-bit staging offsets
-  if (tile_ok && kn.sort && P * P >= 128 && workspace && N >= kn.sort_min && N <= kOrderMaxRois && workspace_bytes >= (long long)N * 32 &&
-      (((uintptr_t)workspace) & 15) == 0) {
-    // RoIs walked by level and position (roi_order_kernel), 32 channels per workgroup, XCD-aware chunk-major order
-    float* sorted = reinterpret_cast<float*>(workspace);
-    DM_LAUNCH(roi_order_kernel, dim3(dm_ceil_div(N, 256 / kOrderTpr)), dim3(256), 0, (hipStream_t)stream, a, sorted);
-    int rco = dm_check_launch();
-    if (rco != DM_OK) return rco;
-    a.levels = nullptr;
-    a.sorted = sorted;
-    a.CT = 32;
-    a.order = 1;
-    int chunks = dm_ceil_div(C, a.CT);
-    if (chunks % 8 != 0) a.order = 0;
-    DM_LAUNCH(roi_align_tile_kernel<0>, dim3(N * chunks), dim3(256), (kTileFloats4 + 64) * sizeof(float4), (hipStream_t)stream, a);
-    return dm_check_launch();
-  }
-  if (tile_ok) {
-    // 16 channels per workgroup in the XCD-aware order (roi_unit): XCD x walks the chunks c = x (mod 8) chunk-major,
-    // so the planes it is staging from stay in its L2 across the RoIs that share them.  Same time as round 2's 32
-    // channels in launch order (16 .. 256 channels swept at 128 .. 2048 RoIs), 29 % fewer bytes fetched from
-    // the fabric (FETCH_SIZE 113.6 -> 81.2 MB per launch, round 3's ceiling measurement).
-    a.CT = 16;
-    a.order = 1;
-    int chunks = dm_ceil_div(C, a.CT);
-    if (chunks % 8 != 0) a.order = 0;
-    DM_LAUNCH(roi_align_tile_kernel<0>, dim3(N * chunks), dim3(256), (kTileFloats4 + 64) * sizeof(float4), (hipStream_t)stream, a);
-    return dm_check_launch();
-  }
-  bool band_ok = P > 16 && P <= 64 && C % 4 == 0;
-  for (int l = 0; l < num_levels; ++l) band_ok = band_ok && (long long)H[l] * W[l] <= (1 << 23) && W[l] < (1 << 20);      // (the band kernel packs a map column into 20 bits)
-  if (band_ok) {
-    // one channel quad per workgroup (swept 4 .. 32 at 128 RoIs on P2: 0.32 / 0.45 / 0.79 / 1.5 ms): the
-    // bands of a large RoI are a long chain of dependent staging round trips, so the parallelism has to
-    // come from the number of workgroups
-    a.CT = 4;            // (roi_band_fwd is written for exactly one quad)
-    const int chunks = dm_ceil_div(C, a.CT);
-    a.order = 0;                  // full-height bands in launch order (XCD-aware chunk-major and shorter bands measured slower, round 4)
-    // (a 28 KB tile with five workgroups per CU -- 96 VGPRs, 92 bytes of scratch -- measured slower: 202 vs 188 us)
-    DM_LAUNCH((roi_align_band_kernel<kTileFloats4, 4>), dim3(N * chunks), dim3(256),
-              (kTileFloats4 + kBandTabFloats4) * sizeof(float4), (hipStream_t)stream, a);
-    return dm_check_launch();
-  }
-  // Large output grids (56x56 extraction): planar LDS staging where the footprint fits,
-  // direct global taps otherwise; two launches partition the RoIs by sampling-grid class.
-  a.CT = (P * P >= 1024) ? 8 : 16;
-  a.lds_floats = 6 * 1024;
-  const int chunks = dm_ceil_div(C, a.CT);
-  DM_LAUNCH((roi_align_kernel<false, 1>), dim3(N * chunks), dim3(256), a.lds_floats * sizeof(float), (hipStream_t)stream, a);
-  int rc1 = dm_check_launch();
-  if (rc1 != DM_OK) return rc1;
-  DM_LAUNCH((roi_align_kernel<false, 2>), dim3(N * chunks), dim3(256), a.lds_floats * sizeof(float), (hipStream_t)stream, a);
-  return dm_check_launch();
-}
-}  // namespace
 
 extern "C" int dm_roi_align_fwd(const float* const* feats, const int* H, const int* W, const float* spatial_scales,
                                 int num_levels, int B, int C, const float* rois, int N, int P, int sampling_ratio,
@@ -1546,36 +1612,18 @@ extern "C" int dm_roi_align_scaled_fwd(const float* const* feats, const int* H, 
                             levels_out, nullptr, 0, stream, roi_scale_factor);
 }
 
-// (K26) the RoIAlign of ONE map added into RoI features, no [N, C, P, P] intermediate.  The launch is dm_roi_align_fwd's
-// tile launch (16 channels per workgroup, the XCD-aware order): MODE 1 adds where that launch stores, the same bins.
+// (K26) the RoIAlign of ONE map added into RoI features, no [N, C, P, P] intermediate: roi_route's ROI_ADD
 extern "C" int dm_roi_align_add_fwd(const float* feat, int B, int C, int H, int W, float spatial_scale, const float* rois,
                                     int N, int P, int sampling_ratio, int pool, float* out, dm_stream_t stream) {
-  RoiArgs a;
-  if (pool != 1 && pool != 2) return DM_ERR_INVALID_ARG;
-  int rc = fill_args(a, &H, &W, &spatial_scale, 1, B, C, rois, N, P, sampling_ratio, 56.f);
-  if (rc != DM_OK) return rc;
-  if (N == 0) return DM_OK;
-  if (!feat || !out) return DM_ERR_INVALID_ARG;
-  if (P * P > 256 || P < 2 || C % 4 != 0 || (long long)H * W > (1 << 23) || (pool == 2 && (P & 1))) return DM_ERR_UNSUPPORTED;
-  a.feat[0] = feat;
-  a.out = out;
-  // the channels per workgroup of the launch the host binding's RoIAlign of these RoIs takes (32 where it orders them)
-  const RoiKnobs& kn = roi_knobs();
-  a.CT = (kn.sort && P * P >= 128 && N >= kn.sort_min && N <= kOrderMaxRois) ? 32 : 16;
-  a.order = 1;
-  const int chunks = dm_ceil_div(C, a.CT);
-  if (chunks % 8 != 0) a.order = 0;
-  if ((long long)N * chunks > 0x7fffffffLL) return DM_ERR_UNSUPPORTED;
-  if (pool == 1)
-    DM_LAUNCH(roi_align_tile_kernel<1>, dim3(N * chunks), dim3(256), (kTileFloats4 + 64) * sizeof(float4), (hipStream_t)stream, a);
-  else
-    DM_LAUNCH(roi_align_tile_kernel<2>, dim3(N * chunks), dim3(256), (kTileFloats4 + 64) * sizeof(float4), (hipStream_t)stream, a);
-  return dm_check_launch();
+  RoiArgs a{};
+  a.rois = rois; a.finest = 56.f; a.out = out;
+  const RoiCall c = {ROI_ADD, pool, 1, &H, &W, B, C, N, P, sampling_ratio, 0, false};
+  return roi_run(c, &spatial_scale, &feat, nullptr, a, nullptr, nullptr, stream);
 }
 
+// 0: no call with these N, P orders its RoIs (the knobs, the tile kernel's bins); else what the ordering takes
 extern "C" long long dm_roi_align_workspace_bytes(int N, int P) {
-  if (N <= 0 || P < 2 || P * P > 256) return 0;
-  return (long long)N * 32;      // ordered RoI records (roi_order_kernel)
+  return roi_tile_bins(P) && roi_orders(N, P) ? roi_order_bytes(N) : 0;
 }
 
 extern "C" int dm_roi_align_fwd_ws(const float* const* feats, const int* H, const int* W, const float* spatial_scales,
@@ -1590,26 +1638,27 @@ extern "C" int dm_roi_align_fwd_ws(const float* const* feats, const int* H, cons
 extern "C" int dm_roi_align_bwd(const float* grad_out, float* const* grad_feats, const int* H, const int* W,
                                 const float* spatial_scales, int num_levels, int B, int C, const float* rois, int N,
                                 int P, int sampling_ratio, float finest_scale, dm_stream_t stream) {
-  RoiArgs a;
-  int rc = fill_args(a, H, W, spatial_scales, num_levels, B, C, rois, N, P, sampling_ratio, finest_scale);
-  if (rc != DM_OK) return rc;
-  if (N == 0) return DM_OK;
-  if (!grad_feats || !grad_out) return DM_ERR_INVALID_ARG;
-  for (int l = 0; l < num_levels; ++l) {
-    if (!grad_feats[l]) return DM_ERR_INVALID_ARG;
-    a.gfeat[l] = grad_feats[l];
-  }
-  if (N == 0) return DM_OK;
-  a.gout = grad_out;
-  if (P > 16 && P <= 64 && C % 4 == 0 && (long long)N * (C / 4) <= 0x7fffffffLL) {
-    // larger output grids (the 56 x 56 extraction in front of MaskPre): gather form, one atomic per footprint cell
-    static bool raised[DM_MAX_DEVICES] = {false};
-    const size_t lds = roi_adj_lds_bytes(P);
-    if (dm_ensure_lds_limit(reinterpret_cast<const void*>(&roi_align_bwd_gather_kernel), (int)lds, raised) != DM_OK) return DM_ERR_LAUNCH;
-    DM_LAUNCH(roi_align_bwd_gather_kernel, dim3((unsigned)(N * (C / 4))), dim3(256), lds, (hipStream_t)stream, a);
-    return dm_check_launch();
-  }
-  const int chunks = dm_ceil_div(C, a.CT);
-  DM_LAUNCH((roi_align_kernel<true, 0>), dim3(N * chunks), dim3(256), 0, (hipStream_t)stream, a);
-  return dm_check_launch();
+  RoiArgs a{};
+  a.rois = rois; a.finest = finest_scale; a.gout = grad_out;
+  const RoiCall c = {ROI_BWD, 0, num_levels, H, W, B, C, N, P, sampling_ratio, 0, false};
+  return roi_run(c, spatial_scales, nullptr, grad_feats, a, nullptr, nullptr, stream);
 }
+
+// (ABI 29) What the entry points here would launch for these host arguments: roi_route's own value, the one roi_emit
+// enqueues (the header has the record layout).  Nothing below touches HIP.
+extern "C" int dm_roi_align_plan(int entry, int pool, int num_levels, const int* H, const int* W, int B, int C, int N, int P,
+                                 int sampling_ratio, long long workspace_bytes, int workspace, int* records, int max_records) {
+  if (!records || max_records < DM_ROI_PLAN_MAX_LAUNCHES || entry < ROI_FWD || entry > ROI_BWD) return DM_ERR_INVALID_ARG;
+  if (workspace < 0 || workspace > 2 || (entry != ROI_FWD && (workspace != 0 || workspace_bytes != 0))) return DM_ERR_INVALID_ARG;
+  if (entry == ROI_ADD && num_levels != 1) return DM_ERR_INVALID_ARG;                                  // (its one map)
+  if (workspace_bytes < 0 || (workspace_bytes > 0 && workspace == 0)) return DM_ERR_INVALID_ARG;      // (dm_roi_align_fwd_ws's own)
+  const RoiRoute r = roi_route({entry, pool, num_levels, H, W, B, C, N, P, sampling_ratio, workspace ? workspace_bytes : 0, workspace == 1});
+  if (r.rc != DM_OK) return r.rc;
+  for (int l = 0; l < r.count; ++l) {
+    const RoiLaunch& m = r.launch[l];
+    const int rec[DM_ROI_PLAN_INTS] = {m.kernel, m.p[0], m.p[1], m.grid, m.threads, m.lds_bytes, m.CT, m.order, m.lds_floats, m.levels};
+    for (int i = 0; i < DM_ROI_PLAN_INTS; ++i) records[l * DM_ROI_PLAN_INTS + i] = rec[i];
+  }
+  return r.count;
+}
+

@@ -94,11 +94,10 @@ def _float_array(vals):
 
 
 # ------------------------------------------------------------------ RoIAlign
-# 14x14 / 7x7 extractions of 192 RoIs or more go through dm_roi_align_fwd_ws with a scratch buffer (ROI_WORKSPACE below):
-# the library orders the RoIs by level and position on the device first (DM_ROI_SORT, default on: 57 -> 50.7 us for 512 RoIs,
-# the same bits)
+# Extractions go through dm_roi_align_fwd_ws with the scratch buffer dm_roi_align_workspace_bytes asks for (ROI_WORKSPACE
+# below): where it asks for one (14x14 extractions of 192 .. 1024 RoIs by default) the library orders the RoIs by level and
+# position on the device first (DM_ROI_SORT, default on: 57 -> 50.7 us for 512 RoIs, the same bits)
 ROI_WORKSPACE = True          # (tests compare with the unordered kernel by clearing it)
-ROI_WORKSPACE_MIN = int(os.environ.get('DM_ROI_SORT_MIN', '192'))
 
 
 def roi_align(feats, rois, output_size, spatial_scales, sampling_ratio=0, finest_scale=56.0, return_levels=False,
@@ -122,29 +121,51 @@ def roi_align(feats, rois, output_size, spatial_scales, sampling_ratio=0, finest
         assert tuple(out.shape) == (N, C, output_size, output_size)
     levels = torch.zeros((N,), device=rois.device, dtype=torch.int32) if return_levels else None
     if roi_scale_factor is not None:
-        rc = lib().dm_roi_align_scaled_fwd(_ptr_array(feats), _int_array([f.shape[2] for f in feats]),
-                                           _int_array([f.shape[3] for f in feats]), _float_array(spatial_scales), len(feats),
-                                           B, C, _p(rois), N, output_size, sampling_ratio, finest_scale,
-                                           float(roi_scale_factor), _p(out), _p(levels), _stream())
-        check(rc, 'dm_roi_align_scaled_fwd')
-        return (out, levels) if return_levels else out
-    if ROI_WORKSPACE and N >= ROI_WORKSPACE_MIN:
-        # 14x14 / 7x7 extraction with a workspace: the RoIs are first ordered by level and position (one extra launch:
-        # neighbouring workgroups then share their footprints in the L2; same results).
-        wsb = int(lib().dm_roi_align_workspace_bytes(N, output_size))
+        name, tail = 'dm_roi_align_scaled_fwd', (float(roi_scale_factor), _p(out), _p(levels))
+    else:
+        # where the library says ordering pays, a workspace: the RoIs are first ordered by level and position (one extra
+        # launch: neighbouring workgroups then share their footprints in the L2; same results)
+        wsb = int(lib().dm_roi_align_workspace_bytes(N, output_size)) if ROI_WORKSPACE else 0
         ws = torch.empty(((wsb + 15) // 16 * 4,), device=rois.device, dtype=torch.int32) if wsb > 0 else None
-        rc = lib().dm_roi_align_fwd_ws(_ptr_array(feats), _int_array([f.shape[2] for f in feats]),
-                                       _int_array([f.shape[3] for f in feats]), _float_array(spatial_scales), len(feats),
-                                       B, C, _p(rois), N, output_size, sampling_ratio, finest_scale, _p(out), _p(levels),
-                                       _p(ws), wsb, _stream())
-        check(rc, 'dm_roi_align_fwd_ws')
-        return (out, levels) if return_levels else out
-    rc = lib().dm_roi_align_fwd(_ptr_array(feats), _int_array([f.shape[2] for f in feats]),
-                                _int_array([f.shape[3] for f in feats]), _float_array(spatial_scales), len(feats),
-                                B, C, _p(rois), N, output_size, sampling_ratio, finest_scale, _p(out), _p(levels),
-                                _stream())
-    check(rc, 'dm_roi_align_fwd')
+        name, tail = 'dm_roi_align_fwd_ws', (_p(out), _p(levels), _p(ws), wsb)
+    rc = getattr(lib(), name)(_ptr_array(feats), _int_array([f.shape[2] for f in feats]), _int_array([f.shape[3] for f in feats]),
+                              _float_array(spatial_scales), len(feats), B, C, _p(rois), N, output_size, sampling_ratio,
+                              finest_scale, *tail, _stream())
+    check(rc, name)
     return (out, levels) if return_levels else out
+
+
+ROI_PLAN_FIELDS = ('kernel', 'P0', 'P1', 'grid', 'threads', 'lds_bytes', 'CT', 'order', 'lds_floats', 'levels')
+ROI_KERNELS = ('order', 'tile', 'band', 'generic', 'bwd_gather')          # field 'kernel' of a plan record
+ROI_ENTRIES = ('forward', 'add', 'backward')                              # dm_roi_align_plan's `entry`
+
+
+def roi_align_plan_raw(entry, map_sizes, B, C, N, output_size, sampling_ratio=0, workspace_bytes=0, workspace=0, pool=0):
+    """dm_roi_align_plan: (return code, records).  The code is the number of launches or the (negative) error the call with
+    these numbers would return.  ``entry``: one of ROI_ENTRIES; ``map_sizes``: the (H, W) of every level; ``workspace``: 0
+    none, 1 a 16-byte aligned pointer, 2 a misaligned one.  Host only: no tensor, no device."""
+    consts = _abi.load()[1]
+    n, cap = consts['DM_ROI_PLAN_INTS'], consts['DM_ROI_PLAN_MAX_LAUNCHES']
+    assert len(ROI_PLAN_FIELDS) == n
+    rec = (ctypes.c_int * (n * cap))(*([-1] * (n * cap)))
+    rc = lib().dm_roi_align_plan(ROI_ENTRIES.index(entry), int(pool), len(map_sizes), _int_array([s[0] for s in map_sizes]),
+                                 _int_array([s[1] for s in map_sizes]), int(B), int(C), int(N), int(output_size),
+                                 int(sampling_ratio), int(workspace_bytes), int(workspace), rec, cap)
+    return rc, [dict(zip(ROI_PLAN_FIELDS, rec[i * n:(i + 1) * n])) for i in range(max(rc, 0))]
+
+
+def roi_align_plan(entry, map_sizes, B, C, N, output_size, sampling_ratio=0, workspace=None, pool=0):
+    """The launches ``roi_align`` ('forward'), ``roi_align_add_`` ('add', with its ``pool``) or ``roi_align_backward``
+    ('backward') would make for these numbers, as the launcher's own route says (include/dynamask_hip.h, dm_roi_align_plan):
+    a list of up to two dicts with the keys ROI_PLAN_FIELDS (two: the order kernel in front of the tile kernel, or the two
+    sampling-grid classes of the generic kernel).  Raises where the call would fail.  ``workspace`` (forward): None = what
+    ``roi_align`` itself passes (the bytes the library asks for, unless ROI_WORKSPACE is cleared), else a byte count."""
+    if workspace is None:
+        workspace = int(lib().dm_roi_align_workspace_bytes(N, output_size)) if ROI_WORKSPACE and entry == 'forward' else 0
+    rc, recs = roi_align_plan_raw(entry, map_sizes, B, C, N, output_size, sampling_ratio, workspace, 1 if workspace > 0 else 0, pool)
+    if rc < 0:
+        check(rc, 'dm_roi_align_plan')
+    return recs
 
 
 def roi_align_backward(grad_out, feat_shapes, rois, output_size, spatial_scales, sampling_ratio=0, finest_scale=56.0):

@@ -55,7 +55,7 @@ extern "C" {
 typedef void* dm_stream_t; /* hipStream_t */
 
 const char* dm_error_string(int code);
-/* ABI version: bumped whenever a signature or the meaning of an argument changes (8: flag bit 3 of dm_conv2d_fwd; 9: RoI assignment / bbox training entry points; 10: dm_detail_target takes the fuse weights from device memory; 11: FCNMaskHead upsample backward; 12: dm_fc_fwd takes a scratch slab, deterministic split-K; 13: dm_deform_coord_grad / dm_deform_col2im, dm_conv2d_fwd_masked, dm_scale, dm_polygon_mask_targets, dm_ignore_columns, dm_upsample2x_bilinear_bwd overwrites; 14: dm_random_sample, dm_bn_relu_maxpool_argmax, the *_fx deterministic accumulators + dm_fx_to_float, dm_mask_loss_fwd_bwd takes a scratch, dm_conv2d_wgrad takes the bias gradient, dm_conv_pack_weight_batch, dm_mask_loss_stage; 15: dm_class_logits_up2x_fwd; 16: dm_conv2d_wgrad_slab / dm_conv2d_wgrad_scratch_floats; 17: dm_class_logits_bwd_slab / dm_class_logits_bwd_scratch_floats; 18: dm_reload_env_knobs, dm_roi_align_fwd_ws / dm_roi_align_workspace_bytes, dm_conv_pack_weight_split / dm_conv_packed_floats_split and flag bits 4, 5 of dm_conv2d_fwd; 19: dm_dcn_bwd_data_fused and its pack; 20: dm_conv2d_fwd_ws / dm_conv2d_splitk_floats; 21: dm_deform_conv_fwd_ws / dm_deform_conv_splitk_floats; 22: the bf16-split layouts (dm_conv_pack_weight_split, dm_conv_packed_floats_split, flag bits 4 / 5 of dm_conv2d_fwd) and the one-kernel DCN data gradient (dm_dcn_bwd_*) REMOVED -- measured, never the parity path, see docs/HISTORY.md; 23: dm_bn_stats takes mean_shift, dm_roi_align_bwd takes the gather form for 16 < P <= 64; 24: dm_build_info; 25: dm_boundary_merge_chain, dm_stage_head_fwd; 26: dm_conv1x1_group_fwd; 27: dm_deform_conv_tout_fwd / dm_deform_conv_tout_supported; 28: the opt-in bf16x3 mode -- dm_conv_pack_weight_bf16x3 / dm_conv_packed_floats_bf16x3 and flag bit 4 of dm_conv2d_fwd, dm_conv2d_fwd_ws and dm_conv1x1_group_fwd; dm_deconv_pack_weight_bf16x3 and flag bit 4 of dm_deconv2x2_fwd).  Entry points ADDED without a signature or meaning change leave the number as it is (the loader resolves every symbol of _lib.SIGNATURES by name, so an older library fails at load; that table is derived from this file, dynamask_amd/_abi.py): the multi-image post-processing dm_nms_mask_segmented / dm_nms_reduce_segmented, dm_paste_masks_multi, dm_paste_rle_multi / dm_rle_multi_scratch_ints; the test-time augmentation dm_bbox_mapping_multi, dm_merge_aug_bboxes, dm_merge_aug_masks; RefineMask's dilated / any-width 3x3 convolutions and the sigmoid of its semantic map (section K21); PointRend's point
+/* ABI version: bumped whenever a signature or the meaning of an argument changes (8: flag bit 3 of dm_conv2d_fwd; 9: RoI assignment / bbox training entry points; 10: dm_detail_target takes the fuse weights from device memory; 11: FCNMaskHead upsample backward; 12: dm_fc_fwd takes a scratch slab, deterministic split-K; 13: dm_deform_coord_grad / dm_deform_col2im, dm_conv2d_fwd_masked, dm_scale, dm_polygon_mask_targets, dm_ignore_columns, dm_upsample2x_bilinear_bwd overwrites; 14: dm_random_sample, dm_bn_relu_maxpool_argmax, the *_fx deterministic accumulators + dm_fx_to_float, dm_mask_loss_fwd_bwd takes a scratch, dm_conv2d_wgrad takes the bias gradient, dm_conv_pack_weight_batch, dm_mask_loss_stage; 15: dm_class_logits_up2x_fwd; 16: dm_conv2d_wgrad_slab / dm_conv2d_wgrad_scratch_floats; 17: dm_class_logits_bwd_slab / dm_class_logits_bwd_scratch_floats; 18: dm_reload_env_knobs, dm_roi_align_fwd_ws / dm_roi_align_workspace_bytes, dm_conv_pack_weight_split / dm_conv_packed_floats_split and flag bits 4, 5 of dm_conv2d_fwd; 19: dm_dcn_bwd_data_fused and its pack; 20: dm_conv2d_fwd_ws / dm_conv2d_splitk_floats; 21: dm_deform_conv_fwd_ws / dm_deform_conv_splitk_floats; 22: the bf16-split layouts (dm_conv_pack_weight_split, dm_conv_packed_floats_split, flag bits 4 / 5 of dm_conv2d_fwd) and the one-kernel DCN data gradient (dm_dcn_bwd_*) REMOVED -- measured, never the parity path, see docs/HISTORY.md; 23: dm_bn_stats takes mean_shift, dm_roi_align_bwd takes the gather form for 16 < P <= 64; 24: dm_build_info; 25: dm_boundary_merge_chain, dm_stage_head_fwd; 26: dm_conv1x1_group_fwd; 27: dm_deform_conv_tout_fwd / dm_deform_conv_tout_supported; 28: the opt-in bf16x3 mode -- dm_conv_pack_weight_bf16x3 / dm_conv_packed_floats_bf16x3 and flag bit 4 of dm_conv2d_fwd, dm_conv2d_fwd_ws and dm_conv1x1_group_fwd; dm_deconv_pack_weight_bf16x3 and flag bit 4 of dm_deconv2x2_fwd; 29: dm_roi_align_workspace_bytes answers 0 wherever no call with these N, P orders its RoIs, dm_roi_align_plan).  Entry points ADDED without a signature or meaning change leave the number as it is (the loader resolves every symbol of _lib.SIGNATURES by name, so an older library fails at load; that table is derived from this file, dynamask_amd/_abi.py): the multi-image post-processing dm_nms_mask_segmented / dm_nms_reduce_segmented, dm_paste_masks_multi, dm_paste_rle_multi / dm_rle_multi_scratch_ints; the test-time augmentation dm_bbox_mapping_multi, dm_merge_aug_bboxes, dm_merge_aug_masks; RefineMask's dilated / any-width 3x3 convolutions and the sigmoid of its semantic map (section K21); PointRend's point
  * selection, point gather, point MLP and scatter (section K22); Mask Scoring R-CNN's stride-2 3x3 convolution, IoU-head
  * input and mask scores (section K23); PointRefine's descending point selection, point-feature gather, point MLP and
  * multi-row scatter (section K24); Cascade Mask R-CNN's stage-grouped convolutions / deconvolutions and stage step
@@ -64,7 +64,7 @@ const char* dm_error_string(int code);
  * own report of its launches, dm_conv2d_plan (section K5/K6) and dm_conv2d_group_plan (section K25); Double-Head R-CNN's
  * rescaled RoIAlign and global average pool (section K28); the DCN forward launcher's route, dm_deform_conv_plan
  * (section K8). */
-#define DM_ABI_VERSION 28 /* the one definition: dm_abi_version(), dm_build_info() and _lib.ABI_VERSION read it */
+#define DM_ABI_VERSION 29 /* the one definition: dm_abi_version(), dm_build_info() and _lib.ABI_VERSION read it */
 int dm_abi_version(void);
 /* "libdynamask_hip abi=N arch=gfx950 compiler=<clang version> flags=<the product-wide flags of dynamask_amd/build.py>"
  * (static storage).  The library must be compiled WITHOUT packed fp32 instructions (flag "-packed-fp32-ops", see
@@ -94,7 +94,10 @@ int dm_roi_align_fwd(const float* const* feats, const int* H, const int* W, cons
                      float finest_scale, float* out, int32_t* levels_out, dm_stream_t stream);
 
 /* The same extraction with a caller-provided workspace of dm_roi_align_workspace_bytes(N, P) bytes (device memory,
- * 16-byte aligned, contents irrelevant before and after the call; 0 bytes = no faster path exists for this P).  For the
+ * 16-byte aligned, contents irrelevant before and after the call).  0 bytes = no call with these N, P orders its RoIs:
+ * DM_ROI_SORT off, P * P < 128 or > 256, N below DM_ROI_SORT_MIN or above 1024 (ABI 29; before, 0 only for N <= 0, P < 2
+ * or P * P > 256 -- the one deliberate narrowing of an answer: a caller allocates exactly where it pays).  It stays an
+ * upper bound on what the call uses; a call that would order may still not (C % 4 != 0, a map above 2^23 pixels).  For the
  * 14x14 extraction of 192 .. 1024 RoIs a first kernel ranks the RoIs by (image, level, 32-pixel row, column) into the
  * workspace and the extraction walks them in that order -- workgroups that run side by side then share their footprints
  * in the XCD's L2 (fabric traffic 261 -> 193 MB per 512 RoIs, 57 -> 50.7 us with the ranking kernel) -- and writes every
@@ -111,6 +114,30 @@ int dm_roi_align_fwd_ws(const float* const* feats, const int* H, const int* W, c
 int dm_roi_align_bwd(const float* grad_out, float* const* grad_feats, const int* H, const int* W,
                      const float* spatial_scales, int num_levels, int B, int C, const float* rois, int N,
                      int P, int sampling_ratio, float finest_scale, dm_stream_t stream);
+
+/* (ABI 29) The launches dm_roi_align_fwd / dm_roi_align_scaled_fwd / dm_roi_align_fwd_ws (entry 0), dm_roi_align_add_fwd
+ * (entry 1, with its `pool`; H and W then point at its one map's sizes, num_levels = 1) or dm_roi_align_bwd (entry 2) would
+ * make for these HOST arguments: the route the launcher decides on, the very value it then enqueues.  Nothing is launched
+ * and no device is needed: unlike the DCN route, nothing in this one reads the compute-unit count.  Arguments as the
+ * entry's, without the device pointers, the scales and roi_scale_factor (none enters the route).  workspace: 0 = none
+ * (NULL), 1 = a 16-byte aligned pointer, 2 = a misaligned one, with workspace_bytes behind it; entries 1 and 2 take none
+ * (DM_ERR_INVALID_ARG otherwise); `pool` is read for entry 1 only.  The DM_ROI_SORT / DM_ROI_SORT_MIN knobs apply as they do
+ * to launches (dm_reload_env_knobs re-reads them).
+ * records: HOST array of max_records (>= DM_ROI_PLAN_MAX_LAUNCHES) x DM_ROI_PLAN_INTS ints.  Returns the number of launches
+ * (0: N = 0; 1; 2: the order kernel + the tile kernel that walks its records, or roi_align_kernel<false, 1> + <false, 2>) or
+ * the error code the call would return for these numbers, and then writes nothing.  Record l, ints [l * DM_ROI_PLAN_INTS ..):
+ *   0 kernel: 0 roi_order_kernel, 1 roi_align_tile_kernel, 2 roi_align_band_kernel, 3 roi_align_kernel,
+ *     4 roi_align_bwd_gather_kernel;
+ *   1, 2 its template parameters: MODE, 0 (kernel 1: 0 stores, 1 adds, 2 adds the 2 x 2 block means); TB, WPC (kernel 2);
+ *     BWD, GCLS (kernel 3); zeros (kernels 0, 4);
+ *   3 grid x (RoIs x channel chunks; kernel 0: ceil(N / 16));  4 threads per workgroup;  5 dynamic LDS bytes;
+ *   6 CT: channels per workgroup (0: kernel 0);  7 order: 1 = the XCD-aware workgroup order (kernel 1 with a multiple of 8
+ *     chunks);  8 lds_floats: LDS budget of roi_align_kernel's planar tile (0: every other launch);
+ *   9 levels: 1 when this launch is the one that writes levels_out (an ordered call: the order kernel, not the tile kernel). */
+#define DM_ROI_PLAN_INTS 10
+#define DM_ROI_PLAN_MAX_LAUNCHES 2
+int dm_roi_align_plan(int entry, int pool, int num_levels, const int* H, const int* W, int B, int C, int N, int P,
+                      int sampling_ratio, long long workspace_bytes, int workspace, int* records, int max_records);
 
 /* ---------------------------------------------------------------------------
  * Weight packing for the implicit-GEMM convolutions: OIHW [Cout, Cin, k, k] ->
@@ -1064,7 +1091,8 @@ int dm_cascade_refine(const float* rois, const float* cls_score, const float* bb
  *   pool == 1: out [N, C, P, P]         out[n, c, y, x] += bin(n, c, y, x)   -- the bits of the extraction + an fp32 add,
  *              the extraction being dm_roi_align_fwd_ws with the workspace it asks for where that call orders the RoIs
  *              (P * P >= 128, DM_ROI_SORT_MIN <= N <= 1024), else dm_roi_align_fwd: the launch takes that call's channels
- *              per workgroup, because bins of sampling grids above 4 x 4 differ in the last bit between the two;
+ *              per workgroup (the launcher asks its own forward route: dm_roi_align_plan entry 1 against entry 0), because
+ *              bins of sampling grids above 4 x 4 differ in the last bit between the two;
  *   pool == 2: out [N, C, P / 2, P / 2]  out[n, c, y, x] += ((b00 + b01) + (b10 + b11)) * 0.25 of the 2 x 2 block of bins
  *              (adaptive_avg_pool2d P -> P / 2, P even): bin averages first, then the block mean, then the add.
  * rois [N, 5] as dm_roi_align_fwd's (the batch column picks the image of feat; an index outside [0, B) adds zeros).

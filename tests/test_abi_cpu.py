@@ -109,9 +109,9 @@ def test_pack_job_layout_matches_the_compiled_header(tmp_path):
 
 def test_the_abi_number_has_one_definition():
     from dynamask_amd import ops
-    assert _lib.ABI_VERSION == 28
-    assert len(re.findall(r'^#define DM_ABI_VERSION 28\b', open(HEADER).read(), flags=re.M)) == 1
+    assert _lib.ABI_VERSION == 29
+    assert len(re.findall(r'^#define DM_ABI_VERSION 29\b', open(HEADER).read(), flags=re.M)) == 1
     src = open(API_MISC).read()
-    assert src.count('DM_ABI_VERSION') == 2 and '28' not in src       # dm_abi_version() and the dm_build_info() string
+    assert src.count('DM_ABI_VERSION') == 2 and '29' not in src       # dm_abi_version() and the dm_build_info() string
     assert not re.search(r'^ABI_VERSION\s*=', open(_lib.__file__).read(), flags=re.M)
     assert ops.AUG_VIEW_FLOATS == 8 and not re.search(r'^AUG_VIEW_FLOATS\s*=\s*\d', open(ops.__file__).read(), flags=re.M)

@@ -829,20 +829,24 @@ def test_roi_align_ordered_walk_gives_the_bits_and_levels_of_the_unordered_kerne
         rois[8, 1:] = float('nan')
     rois = rois.contiguous()
     scales = (0.25, 0.125, 0.0625, 0.03125)
-    was = (ops.ROI_WORKSPACE, ops.ROI_WORKSPACE_MIN)
+    import os
+    maps, C = [tuple(f.shape[2:]) for f in feats], feats[0].shape[1]
+    route = lambda: [ops.ROI_KERNELS[r['kernel']] for r in ops.roi_align_plan('forward', maps, B, C, n, P)]      # noqa: E731
+    was = ops.ROI_WORKSPACE
     try:
-        ops.ROI_WORKSPACE = False
-        ref, lv_ref = ops.roi_align(feats, _dev(rois), P, scales, return_levels=True)
-        ops.ROI_WORKSPACE, ops.ROI_WORKSPACE_MIN = True, 1
-        import os
-        os.environ['DM_ROI_SORT_MIN'] = '1'
+        os.environ['DM_ROI_SORT_MIN'] = '1'                               # the one switch: the library's own threshold
         ops.lib().dm_reload_env_knobs()
+        ops.ROI_WORKSPACE = False
+        assert route() == ['tile'], 'the reference call must not order'
+        ref, lv_ref = ops.roi_align(feats, _dev(rois), P, scales, return_levels=True)
+        ops.ROI_WORKSPACE = True
+        assert route() == (['order', 'tile'] if P == 14 else ['tile']), 'the compared call must order (14 x 14 only)'
         out, lv = ops.roi_align(feats, _dev(rois), P, scales, return_levels=True)
         out2, _ = ops.roi_align(feats, _dev(rois), P, scales, return_levels=True)
     finally:
         os.environ.pop('DM_ROI_SORT_MIN', None)
         ops.lib().dm_reload_env_knobs()
-        ops.ROI_WORKSPACE, ops.ROI_WORKSPACE_MIN = was
+        ops.ROI_WORKSPACE = was
     assert torch.equal(lv, lv_ref)
     nan_ref = torch.isnan(ref)
     assert torch.equal(torch.isnan(out), nan_ref)

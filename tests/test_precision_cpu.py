@@ -55,13 +55,13 @@ def test_environment_variable_is_read_at_import():
 
 def test_symbols_exported_and_abi():
     from dynamask_amd import _lib, hazard
-    assert _lib.ABI_VERSION == 28
+    assert _lib.ABI_VERSION == 29
     for name in ('dm_conv_pack_weight_bf16x3', 'dm_conv_packed_floats_bf16x3'):
         assert name in _lib.SIGNATURES
     roles = hazard.parse_header()
     assert roles['dm_conv_pack_weight_bf16x3'][0] == 'in' and roles['dm_conv_pack_weight_bf16x3'][7] == 'out'
     header = open(os.path.join(ROOT, 'include', 'dynamask_hip.h')).read()
-    assert '28: the opt-in bf16x3 mode' in header and '#define DM_ABI_VERSION 28' in header
+    assert '28: the opt-in bf16x3 mode' in header and '#define DM_ABI_VERSION 29' in header
     src = open(os.path.join(ROOT, 'dynamask_amd', 'csrc', 'api_misc.hip')).read()
     assert 'dm_abi_version(void) { return DM_ABI_VERSION; }' in src
 
