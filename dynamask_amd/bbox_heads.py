@@ -12,7 +12,9 @@ columns = ``dm_l1_loss_fwd_bwd``) and the backward of the FC stack (``BBoxHeadFn
 weight gradients as fp32-MFMA GEMMs through the implicit-GEMM kernels on [N, C, 1, 1] tensors).
 ``DoubleConvFCBBoxHead`` (roi_heads/bbox_heads/double_bbox_head.py, inference): the regression from a convolution branch
 -- ``BasicResBlock``, ResNet ``Bottleneck``s with eval-mode BatchNorm folded into the exact-fp32 convolutions (``fold_bn``),
-a global average pool (``dm_global_avg_pool_fwd``) -- the classification from fully connected layers."""
+a global average pool (``dm_global_avg_pool_fwd``) -- the classification from fully connected layers.
+``BBoxHead`` (roi_heads/bbox_heads/bbox_head.py, inference): the two fully connected layers alone, behind the average pool in
+the C4 configs; its ``Bottleneck`` sibling with a ``downsample`` path is the first block of shared_heads.ResLayer."""
 import numpy as np
 import torch
 import torch.nn as nn
@@ -291,26 +293,40 @@ class BasicResBlock(nn.Module):
 class Bottleneck(nn.Module):
     """backbones/resnet.py:95-300 (stride 1, no downsample, style 'pytorch') in eval mode; keys ``conv{1,2,3}.weight``,
     ``bn{1,2,3}.*``.  Three launches: 1x1 + ReLU, 3x3 + ReLU, then the 1x1 back to ``inplanes`` with the ``accumulate |
-    ReLU`` epilogue -- relu(x + conv + bias), the residual sum before the activation -- written IN PLACE into ``x``."""
+    ReLU`` epilogue -- relu(x + conv + bias), the residual sum before the activation -- written IN PLACE into ``x``.
+    ``downsample=True`` (the first block of a ResNet layer, shared_heads.ResLayer): the identity path is
+    ``downsample.0`` (1x1, ``inplanes`` -> 4 ``planes``) + ``downsample.1`` (BatchNorm), and the block is three launches
+    too -- conv1, conv2, then ONE two-source 1x1 of [conv2 output, x] by [W3' | Wd'] with bias b3' + bd' and ReLU (the
+    BasicResBlock pattern) into a NEW tensor: ``x`` is not written.  A stride (style 'caffe': in conv1 and
+    ``downsample.0``, both 1x1) is the caller's subsampling of ``x``."""
     expansion = 4
 
-    def __init__(self, inplanes, planes):
+    def __init__(self, inplanes, planes, downsample=False):
         super().__init__()
         from .roi_head import _BN
-        if inplanes != planes * self.expansion:
+        if not downsample and inplanes != planes * self.expansion:
             raise NotImplementedError('Bottleneck: no downsample path (DoubleConvFCBBoxHead: planes = inplanes / 4)')
         self.inplanes, self.planes = inplanes, planes
+        out = planes * self.expansion
         self.conv1, self.bn1 = _conv_weight(planes, inplanes, 1), _BN(planes)
         self.conv2, self.bn2 = _conv_weight(planes, planes, 3), _BN(planes)
-        self.conv3, self.bn3 = _conv_weight(inplanes, planes, 1), _BN(inplanes)
-        self._f = [_FoldedConv([(c, bn)], [c.in_channels])
-                   for c, bn in ((self.conv1, self.bn1), (self.conv2, self.bn2), (self.conv3, self.bn3))]
+        self.conv3, self.bn3 = _conv_weight(out, planes, 1), _BN(out)
+        self._f = [_FoldedConv([(c, bn)], [c.in_channels]) for c, bn in ((self.conv1, self.bn1), (self.conv2, self.bn2))]
+        if downsample:
+            self.downsample = nn.Sequential(_conv_weight(out, inplanes, 1), _BN(out))
+            self._f.append(_FoldedConv([(self.conv3, self.bn3), (self.downsample[0], self.downsample[1])], [planes, inplanes]))
+        else:
+            self.downsample = None
+            self._f.append(_FoldedConv([(self.conv3, self.bn3)], [planes]))
 
     def forward(self, x):
-        """``x`` [N, inplanes, H, W] is overwritten with the block's output and returned."""
+        """Without ``downsample``: ``x`` [N, inplanes, H, W] is overwritten with the block's output and returned.  With
+        it: a new [N, 4 planes, H, W] tensor."""
         (w1, b1), (w2, b2), (w3, b3) = (f.packed() for f in self._f)
         h = ops.conv2d(x, w1, b1, self.planes, 1, relu=True)
         h = ops.conv2d(h, w2, b2, self.planes, 3, relu=True)
+        if self.downsample is not None:
+            return ops.conv2d([h, x], w3, b3, self.planes * self.expansion, 1, relu=True)
         return ops.conv2d(h, w3, b3, self.inplanes, 1, relu=True, out=x, accumulate=True)
 
 
@@ -398,6 +414,65 @@ class DoubleConvFCBBoxHead(nn.Module):
         return self.fc_cls.run(x_fc), bbox_pred
 
     # get_bboxes, the targets and the loss are BBoxHead's: the code Shared2FCBBoxHead runs
+    get_bboxes = Shared2FCBBoxHead.get_bboxes
+    _get_target_single = Shared2FCBBoxHead._get_target_single
+    get_targets = Shared2FCBBoxHead.get_targets
+    loss = Shared2FCBBoxHead.loss
+
+
+@HEADS.register_module()
+class BBoxHead(nn.Module):
+    """``BBoxHead`` -- bbox_heads/bbox_head.py:13-82, inference: the two fully connected layers ``fc_cls`` / ``fc_reg``
+    (dm_fc_fwd) on the RoI features, averaged over the RoI first with ``with_avg_pool`` (dm_global_avg_pool_fwd; the C4
+    configs, on the shared head's [N, 2048, 7, 7]) or flattened.  ``state_dict`` keys: fc_cls.*, fc_reg.*."""
+
+    def __init__(self, with_avg_pool=False, with_cls=True, with_reg=True, roi_feat_size=7, in_channels=256, num_classes=80,
+                 bbox_coder=dict(type='DeltaXYWHBBoxCoder', target_means=[0., 0., 0., 0.], target_stds=[0.1, 0.1, 0.2, 0.2]),
+                 reg_class_agnostic=False, reg_decoded_bbox=False, loss_cls=None, loss_bbox=None):
+        super().__init__()
+        assert with_cls or with_reg
+        if reg_decoded_bbox:
+            raise NotImplementedError('BBoxHead: reg_decoded_bbox=True is not built (False in the C4 configs)')
+        self.with_avg_pool, self.with_cls, self.with_reg = with_avg_pool, with_cls, with_reg
+        self.roi_feat_size = (roi_feat_size, roi_feat_size) if isinstance(roi_feat_size, int) else tuple(roi_feat_size)
+        self.roi_feat_area = self.roi_feat_size[0] * self.roi_feat_size[1]
+        self.in_channels, self.num_classes, self.reg_class_agnostic = in_channels, num_classes, reg_class_agnostic
+        self.reg_decoded_bbox = reg_decoded_bbox
+        self.bbox_coder = build_bbox_coder(bbox_coder)
+        self.loss_cls_cfg, self.loss_bbox_cfg = loss_cls, loss_bbox
+        from .registry import build_loss
+        self.loss_cls = build_loss(loss_cls) if loss_cls is not None else None
+        self.loss_bbox = build_loss(loss_bbox) if loss_bbox is not None else None
+        fc_in = in_channels if with_avg_pool else in_channels * self.roi_feat_area
+        if with_cls:
+            self.fc_cls = _FC(fc_in, num_classes + 1)
+        if with_reg:
+            self.fc_reg = _FC(fc_in, 4 if reg_class_agnostic else 4 * num_classes)
+
+    def init_weights(self):
+        """bbox_head.py:66-73."""
+        if self.with_cls:
+            nn.init.normal_(self.fc_cls.weight, 0, 0.01)
+            nn.init.constant_(self.fc_cls.bias, 0)
+        if self.with_reg:
+            nn.init.normal_(self.fc_reg.weight, 0, 0.001)
+            nn.init.constant_(self.fc_reg.bias, 0)
+
+    def forward(self, x):
+        """bbox_head.py:75-82 -> (cls_score or None, bbox_pred or None)."""
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError('BBoxHead: training is not built; run inference under torch.no_grad()')
+        if self.with_avg_pool and tuple(x.shape[2:]) != self.roi_feat_size:
+            raise ValueError(f'x: {self.roi_feat_size} RoI features expected (AvgPool2d(roi_feat_size) then gives one value '
+                             f'per channel), got {tuple(x.shape[2:])}')
+        n = x.shape[0]
+        if n == 0:          # no RoI: nothing is launched
+            return (x.new_zeros((0, self.fc_cls.out_features)) if self.with_cls else None,
+                    x.new_zeros((0, self.fc_reg.out_features)) if self.with_reg else None)
+        x = ops.global_avg_pool(x.contiguous()) if self.with_avg_pool else x.flatten(1)
+        return (self.fc_cls.run(x) if self.with_cls else None), (self.fc_reg.run(x) if self.with_reg else None)
+
+    # get_bboxes, the targets and the loss are the shared code, as DoubleConvFCBBoxHead takes them
     get_bboxes = Shared2FCBBoxHead.get_bboxes
     _get_target_single = Shared2FCBBoxHead._get_target_single
     get_targets = Shared2FCBBoxHead.get_targets

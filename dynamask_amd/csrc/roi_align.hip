@@ -35,6 +35,7 @@ struct RoiArgs {
                        // 1 = XCD-aware (see roi_unit)
   int abl;             // ablation bits of the tile kernel (tools/micro/roi_tile_ablate.hip only, see DM_ABL)
   const float* sorted = nullptr;   // tile kernel: RoI records in processing order (roi_order_kernel), 8 floats each
+  int step = 1;        // tile kernel MODE 3 (dm_roi_align_strided_fwd): only bins (i * step, j * step) are produced
 };
 
 // Ablations of the 14x14 tile kernel for the ceiling measurement (profiles/r04_roialign_ceiling.txt): the micro
@@ -209,6 +210,8 @@ __device__ __forceinline__ void roi_bin_fast(const RoiArgs& a, const float* __re
 // block of bins to out[k, c, ph / 2, pw / 2] (out [N, C, P / 2, P / 2]: adaptive_avg_pool2d P -> P / 2 of the bins, then
 // the add).  In MODE 2 thread t holds bin (2 (o / (P / 2)) + (s >> 1), 2 (o % (P / 2)) + (s & 1)), o = t >> 2, s = t & 3:
 // the four bins of a block sit in four neighbouring lanes and are summed as (a + b) + (c + d) by two lane exchanges.
+// MODE 3 (K29, dm_roi_align_strided_fwd) stores, like MODE 0, but only the bins (i * step, j * step): out is
+// [N, C, Po, Po] with Po = ceil(P / step), and no other bin is sampled.  A kept bin's arithmetic is MODE 0's.
 template <int MODE>
 __device__ __forceinline__ void roi_bin_of_thread(int t, int P, int& ph, int& pw) {
   if (MODE == 2) {
@@ -239,8 +242,10 @@ __device__ __forceinline__ void roi_bin_generic(const RoiArgs& a, const float* _
                                                 float inv_count, int ph, int pw, int k, int c0, int c1) {
   const size_t plane = (size_t)Hl * Wl;
   const int P = a.P;
+  const int Po = MODE == 3 ? (P + a.step - 1) / a.step : P;      // (MODE 3: ph, pw are multiples of the step)
   for (int c = c0; c < c1; ++c) {
-    const size_t oidx = (((size_t)k * a.C + c) * P + ph) * P + pw;
+    const size_t oidx = MODE == 3 ? (((size_t)k * a.C + c) * Po + ph / a.step) * Po + pw / a.step
+                                  : (((size_t)k * a.C + c) * P + ph) * P + pw;
     const float* fc = BWD ? nullptr : f + (size_t)c * plane;
     float* gc = BWD ? gf + (size_t)c * plane : nullptr;
     const float g = BWD ? a.gout[oidx] * inv_count : 0.f;
@@ -266,7 +271,7 @@ __device__ __forceinline__ void roi_bin_generic(const RoiArgs& a, const float* _
       }
     }
     if (!BWD) {
-      if (MODE == 0) a.out[oidx] = acc * inv_count;
+      if (MODE == 0 || MODE == 3) a.out[oidx] = acc * inv_count;
       else if (MODE == 1) a.out[oidx] = a.out[oidx] + roi_mul_rn(acc, inv_count);
       else {
         const float m = roi_block_mean(roi_mul_rn(acc, inv_count));
@@ -497,16 +502,31 @@ __device__ __forceinline__ void roi_tile_fwd(const RoiArgs& a, const float* __re
   constexpr int S = G + 1;                            // merged stencil is S x S (G == 0: run-time grid)
   const int tid = threadIdx.x;
   const int P = a.P, PP = P * P;
-  const bool active = tid < PP;
+  // MODE 3: lane = (kept bin o, slice qs of NS): the Po * Po kept bins leave most of the 256 lanes free, so the channel
+  // quads of a batch are dealt to NS slices of lanes (quad q to slice q % NS; a workgroup holds 4 quads).  Which lane
+  // computes a (bin, channel) changes nothing in its sum.
+  const int Po = MODE == 3 ? (P + a.step - 1) / a.step : P;
+  const int NS = MODE == 3 ? min(256 / (Po * Po), 4) : 1;
+  const bool active = MODE == 3 ? tid < Po * Po * NS : tid < PP;
   int ph = active ? (int)__umulhi((unsigned)tid, 0xFFFFFFFFu / (unsigned)P + 1u) : 0;      // tid / P (P >= 2)
   int pw = active ? tid - ph * P : 0;
   if (MODE == 2 && active) roi_bin_of_thread<2>(tid, P, ph, pw);
-  // MODE 0 / 1: the bin's place in the output plane is tid; MODE 2: the block's place in the pooled plane
-  const int PPo = MODE == 2 ? PP >> 2 : PP;
+  int qs = 0, obin = tid;
+  if (MODE == 3) {
+    const int t3 = active ? tid : 0;
+    qs = t3 / (Po * Po);
+    obin = t3 - qs * Po * Po;
+    const int oh = obin / Po;
+    ph = oh * a.step;
+    pw = (obin - oh * Po) * a.step;
+  }
+  // MODE 0 / 1: the bin's place in the output plane is tid; MODE 2: the block's place in the pooled plane; MODE 3: the
+  // kept bin's place in the strided plane
+  const int PPo = MODE == 2 ? PP >> 2 : (MODE == 3 ? Po * Po : PP);
   const bool writes = MODE != 2 || (tid & 3) == 0;
-  // one value of a channel plane: store (MODE 0), add (MODE 1), or block mean and add (MODE 2)
+  // one value of a channel plane: store (MODE 0 / 3), add (MODE 1), or block mean and add (MODE 2)
   auto emit = [&](float v, char* plane_ptr) {
-    if (MODE == 0) {
+    if (MODE == 0 || MODE == 3) {
       __builtin_nontemporal_store(v, reinterpret_cast<float*>(plane_ptr));
     } else {
       if (MODE == 2) v = roi_block_mean(v);
@@ -626,11 +646,17 @@ __device__ __forceinline__ void roi_tile_fwd(const RoiArgs& a, const float* __re
       const float4* t = lds + buf * kBufPx;
       // (uniform base + 32-bit lane offset; C % 4 == 0 and CT % 4 == 0: a quad is never cut by c1)
       char* const ob = reinterpret_cast<char*>(a.out + ((size_t)k * a.C + cb) * PPo);
-      const unsigned ot = (unsigned)(MODE == 2 ? tid >> 2 : tid) << 2;
+      const unsigned ot = (unsigned)(MODE == 2 ? tid >> 2 : (MODE == 3 ? obin : tid)) << 2;
       const size_t PB = (size_t)PPo * 4;
+      // (MODE 3: this lane's quads are qs, qs + NS, ...: nql of them; the j-th is quad(j))
+      const int nql = MODE == 3 ? (nq > qs ? (nq - qs + NS - 1) / NS : 0) : nq;
+      auto quad = [&](int j) { return MODE == 3 ? qs + j * NS : j; };
       if (G == 0) {
         // run-time grid (slivers): samples outermost, groups of 4 channel quads accumulate per sample
-        for (int q0 = 0; q0 < nq; q0 += 4) {
+        // (MODE 3: slice 0 alone takes all the quads here, four at a time like MODE 0 -- the very loop of the dense call, so
+        // that the compiler contracts its sums the same way; these RoIs are rare slivers)
+        const int nq0 = (MODE == 3 && qs != 0) ? 0 : nq;
+        for (int q0 = 0; q0 < nq0; q0 += 4) {
           float4 acc[4];
 #pragma unroll
           for (int u = 0; u < 4; ++u) acc[u] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -662,7 +688,7 @@ __device__ __forceinline__ void roi_tile_fwd(const RoiArgs& a, const float* __re
             const int q = q0 + u;
             if (q < nq) {
               char* const oq = ob + (size_t)(4 * q) * PB;
-              if (MODE == 0) {
+              if (MODE == 0 || MODE == 3) {
                 *reinterpret_cast<float*>(oq + ot) = acc[u].x;
                 *reinterpret_cast<float*>(oq + PB + ot) = acc[u].y;
                 *reinterpret_cast<float*>(oq + 2 * PB + ot) = acc[u].z;
@@ -679,7 +705,8 @@ __device__ __forceinline__ void roi_tile_fwd(const RoiArgs& a, const float* __re
       } else {
         constexpr int kUnrollQ = (S >= 4) ? 1 : 2;
 #pragma unroll kUnrollQ
-        for (int q = 0; q < nq; ++q) {
+        for (int j = 0; j < nql; ++j) {
+          const int q = quad(j);
           float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
           const float4* tq = t + q * plane_px + base;
           if (DM_ABL(a, 2)) {
@@ -796,7 +823,8 @@ __global__ __launch_bounds__(256) void roi_order_kernel(RoiArgs a, float* __rest
 }
 
 // MODE 0: the RoIAlign; MODE 1 / 2 (K26, dm_roi_align_add_fwd): the same extraction, its bins added into the RoI features
-// or pooled 2 x 2 first (P even, so P * P is a multiple of 4 and the four lanes of a block are live together)
+// or pooled 2 x 2 first (P even, so P * P is a multiple of 4 and the four lanes of a block are live together); MODE 3 (K29,
+// dm_roi_align_strided_fwd): the extraction's bins (i * step, j * step) only
 template <int MODE>
 __global__ __launch_bounds__(256, MODE == 2 ? 2 : 4) void roi_align_tile_kernel(RoiArgs a) {      // (MODE 2: the block mean keeps more live values: no VGPR cap at 128, no scratch)
   extern __shared__ __attribute__((aligned(16))) float4 lds4[];
@@ -842,10 +870,11 @@ __global__ __launch_bounds__(256, MODE == 2 ? 2 : 4) void roi_align_tile_kernel(
   const float* fimg = flvl + (bad_batch ? 0 : (size_t)b * a.C * Hl * Wl);
   if (gh <= 0 || gw <= 0 || bad_batch) {
     // empty sampling grid (degenerate RoI) / malformed batch index -> zeros (MODE 1 / 2: the zeros are added, -0 -> +0)
-    const int PPo = MODE == 2 ? PP >> 2 : PP;
+    const int Po = MODE == 3 ? (P + a.step - 1) / a.step : P;
+    const int PPo = MODE == 2 ? PP >> 2 : (MODE == 3 ? Po * Po : PP);
     for (int i = threadIdx.x; i < (c1 - c0) * PPo; i += blockDim.x) {
       float* o = a.out + ((size_t)k * a.C + c0) * PPo + i;
-      *o = MODE == 0 ? 0.f : *o + 0.f;
+      *o = (MODE == 0 || MODE == 3) ? 0.f : *o + 0.f;
     }
     return;
   }
@@ -881,9 +910,11 @@ __global__ __launch_bounds__(256, MODE == 2 ? 2 : 4) void roi_align_tile_kernel(
     }
 #undef DM_ROI_TILE
   }
-  for (int pos = threadIdx.x; pos < PP; pos += blockDim.x) {
+  const int Pk = MODE == 3 ? (P + a.step - 1) / a.step : P;      // bins per axis this launch produces
+  for (int pos = threadIdx.x; pos < Pk * Pk; pos += blockDim.x) {
     int ph, pw;
-    roi_bin_of_thread<MODE>(pos, P, ph, pw);
+    roi_bin_of_thread<MODE>(pos, Pk, ph, pw);
+    if (MODE == 3) { ph *= a.step; pw *= a.step; }
     roi_bin_generic<false, MODE>(a, fimg, nullptr, Hl, Wl, sh, sw, bh, bw, gh, gw, inv_count, ph, pw, k, c0, c1);
   }
 }
@@ -1424,10 +1455,10 @@ const RoiKnobs& roi_knobs() {
 // (bins of sampling grids above 4 x 4 differ in the last bit: dm_roi_align_add_fwd follows the forward for that reason).
 
 enum { ROI_ORDER = 0, ROI_TILE = 1, ROI_BAND = 2, ROI_GENERIC = 3, ROI_GATHER = 4 };      // RoiLaunch::kernel, as the header numbers them
-enum { ROI_FWD = 0, ROI_ADD = 1, ROI_BWD = 2 };                                           // RoiCall::entry, as the header numbers them
+enum { ROI_FWD = 0, ROI_ADD = 1, ROI_BWD = 2, ROI_STRIDED = 3 };                                      // RoiCall::entry, as the header numbers them
 
 struct RoiCall {            // what a route depends on
-  int entry, pool, L;       // pool: ROI_ADD only (1: the bins are added, 2: their 2 x 2 block means)
+  int entry, pool, L;       // pool: ROI_ADD (1: the bins are added, 2: their 2 x 2 block means); ROI_STRIDED: its bin_step
   const int *H, *W;         // HOST arrays of L map sizes
   int B, C, N, P, sr;
   long long ws_bytes;       // the caller's workspace (0: none)
@@ -1454,6 +1485,8 @@ bool roi_maps_fit(const RoiCall& c, int max_w) {
 }
 bool roi_tile_ok(const RoiCall& c) { return roi_tile_bins(c.P) && c.C % 4 == 0 && roi_maps_fit(c, 0x7fffffff); }
 // The band kernel packs a map column into 20 bits
+// The strided extraction (MODE 3 of the tile kernel): wherever the dense call takes the tile kernel, any step inside the grid
+bool roi_strided_ok(const RoiCall& c) { return roi_tile_ok(c) && c.pool >= 1 && c.pool <= c.P; }
 bool roi_band_ok(const RoiCall& c) { return c.P > 16 && c.P <= 64 && c.C % 4 == 0 && roi_maps_fit(c, 1 << 20); }
 
 // Is ranking N RoIs of P x P bins worth its launch (the knobs)?  A call that says yes orders them where it takes the tile
@@ -1479,6 +1512,7 @@ RoiRoute roi_route(const RoiCall& c) {
   RoiRoute r;
   auto refuse = [&r](int rc) { r.rc = rc; return r; };
   if (c.entry == ROI_ADD && c.pool != 1 && c.pool != 2) return refuse(DM_ERR_INVALID_ARG);
+  if (c.entry == ROI_STRIDED && c.pool < 1) return refuse(DM_ERR_INVALID_ARG);
   if (!c.H || !c.W || c.L < 1 || c.L > DM_MAX_LEVELS || c.B <= 0 || c.C <= 0 || c.N < 0 || c.P <= 0 || c.sr < 0)
     return refuse(DM_ERR_INVALID_ARG);
   for (int l = 0; l < c.L; ++l)
@@ -1508,6 +1542,11 @@ RoiRoute roi_route(const RoiCall& c) {
     const int CT = c.P * c.P >= 1024 ? 8 : 16, tile = 6 * 1024;
     roi_push(r, c, ROI_GENERIC, 0, 1, roi_align_kernel<false, 1>, CT, 0, tile, tile * sizeof(float), true);
     roi_push(r, c, ROI_GENERIC, 0, 2, roi_align_kernel<false, 2>, CT, 0, tile, tile * sizeof(float), true);
+  } else if (c.entry == ROI_STRIDED) {
+    // the kept bins of the unordered dense call: its 16 channels per workgroup whatever N and the knobs say (the 32-channel
+    // ordered form differs in the last bit for sampling grids above 4 x 4), no ranking -- the callers' maps are one level
+    if (!roi_strided_ok(c)) return refuse(DM_ERR_UNSUPPORTED);
+    roi_push(r, c, ROI_TILE, 3, c.pool, roi_align_tile_kernel<3>, 16, roi_xcd_order(c.C, 16), 0, tile_lds, true);
   } else if (c.entry == ROI_ADD) {
     // the tile launch of the forward of these RoIs with the workspace it asks for (the header's promise: that call's
     // channels per workgroup), MODE 1 / 2 adding where it stores; no other kernel has the adding modes
@@ -1635,6 +1674,25 @@ extern "C" int dm_roi_align_fwd_ws(const float* const* feats, const int* H, cons
                             levels_out, workspace, workspace_bytes, stream);
 }
 
+// (K29) only the bins (i * bin_step, j * bin_step) of the P x P extraction: roi_route's ROI_STRIDED
+extern "C" int dm_roi_align_strided_supported(int num_levels, const int* H, const int* W, int C, int P, int bin_step) {
+  if (!H || !W || num_levels < 1 || num_levels > DM_MAX_LEVELS || C <= 0 || P <= 0) return 0;
+  for (int l = 0; l < num_levels; ++l)
+    if (H[l] <= 0 || W[l] <= 0) return 0;
+  const RoiCall c = {ROI_STRIDED, bin_step, num_levels, H, W, 1, C, 1, P, 0, 0, false};
+  return roi_strided_ok(c) ? 1 : 0;
+}
+
+extern "C" int dm_roi_align_strided_fwd(const float* const* feats, const int* H, const int* W, const float* spatial_scales,
+                                        int num_levels, int B, int C, const float* rois, int N, int P, int sampling_ratio,
+                                        float finest_scale, int bin_step, float* out, int32_t* levels_out,
+                                        dm_stream_t stream) {
+  RoiArgs a{};
+  a.rois = rois; a.finest = finest_scale; a.out = out; a.step = bin_step;
+  const RoiCall c = {ROI_STRIDED, bin_step, num_levels, H, W, B, C, N, P, sampling_ratio, 0, false};
+  return roi_run(c, spatial_scales, feats, nullptr, a, levels_out, nullptr, stream);
+}
+
 extern "C" int dm_roi_align_bwd(const float* grad_out, float* const* grad_feats, const int* H, const int* W,
                                 const float* spatial_scales, int num_levels, int B, int C, const float* rois, int N,
                                 int P, int sampling_ratio, float finest_scale, dm_stream_t stream) {
@@ -1648,7 +1706,7 @@ extern "C" int dm_roi_align_bwd(const float* grad_out, float* const* grad_feats,
 // enqueues (the header has the record layout).  Nothing below touches HIP.
 extern "C" int dm_roi_align_plan(int entry, int pool, int num_levels, const int* H, const int* W, int B, int C, int N, int P,
                                  int sampling_ratio, long long workspace_bytes, int workspace, int* records, int max_records) {
-  if (!records || max_records < DM_ROI_PLAN_MAX_LAUNCHES || entry < ROI_FWD || entry > ROI_BWD) return DM_ERR_INVALID_ARG;
+  if (!records || max_records < DM_ROI_PLAN_MAX_LAUNCHES || entry < ROI_FWD || entry > ROI_STRIDED) return DM_ERR_INVALID_ARG;
   if (workspace < 0 || workspace > 2 || (entry != ROI_FWD && (workspace != 0 || workspace_bytes != 0))) return DM_ERR_INVALID_ARG;
   if (entry == ROI_ADD && num_levels != 1) return DM_ERR_INVALID_ARG;                                  // (its one map)
   if (workspace_bytes < 0 || (workspace_bytes > 0 && workspace == 0)) return DM_ERR_INVALID_ARG;      // (dm_roi_align_fwd_ws's own)

@@ -101,8 +101,11 @@ ROI_WORKSPACE = True          # (tests compare with the unordered kernel by clea
 
 
 def roi_align(feats, rois, output_size, spatial_scales, sampling_ratio=0, finest_scale=56.0, return_levels=False,
-              roi_scale_factor=None, out=None):
-    """``roi_scale_factor`` (a float > 0; None: not given): the FPN level -- and ``levels`` -- is the box's as given, the
+              roi_scale_factor=None, out=None, bin_step=None):
+    """``bin_step`` (an int >= 1; None: the dense extraction): only the bins (i * bin_step, j * bin_step) are sampled and
+    stored, out [N, C, Po, Po] with Po = ceil(output_size / bin_step) (dm_roi_align_strided_fwd): the bits of the dense call
+    without a workspace at those bins.  Not together with ``roi_scale_factor``.
+    ``roi_scale_factor`` (a float > 0; None: not given): the FPN level -- and ``levels`` -- is the box's as given, the
     samples are those of the box rescaled about its centre (dm_roi_align_scaled_fwd: SingleRoIExtractor.forward's
     ``map_roi_levels`` before ``roi_rescale``).  ``out``: the [N, C, P, P] tensor to write (default: a new one)."""
     feats = [_chk(f, 'feat') for f in feats]
@@ -114,13 +117,24 @@ def roi_align(feats, rois, output_size, spatial_scales, sampling_ratio=0, finest
             raise TypeError(f'roi_scale_factor: a number expected, got {type(roi_scale_factor).__name__}')
         if not 0.0 < float(roi_scale_factor) < float('inf'):
             raise ValueError(f'roi_scale_factor must be a finite number > 0, got {roi_scale_factor}')
+    out_size = output_size
+    if bin_step is not None:
+        if isinstance(bin_step, bool) or not isinstance(bin_step, int):
+            raise TypeError(f'bin_step: an int expected, got {type(bin_step).__name__}')
+        if bin_step < 1:
+            raise ValueError(f'bin_step must be >= 1, got {bin_step}')
+        if roi_scale_factor is not None:
+            raise NotImplementedError('roi_align: bin_step together with roi_scale_factor is not built')
+        out_size = -(-output_size // bin_step)
     if out is None:
-        out = torch.empty((N, C, output_size, output_size), device=rois.device, dtype=torch.float32)
+        out = torch.empty((N, C, out_size, out_size), device=rois.device, dtype=torch.float32)
     else:
         _chk(out, 'out')
-        assert tuple(out.shape) == (N, C, output_size, output_size)
+        assert tuple(out.shape) == (N, C, out_size, out_size)
     levels = torch.zeros((N,), device=rois.device, dtype=torch.int32) if return_levels else None
-    if roi_scale_factor is not None:
+    if bin_step is not None:
+        name, tail = 'dm_roi_align_strided_fwd', (int(bin_step), _p(out), _p(levels))
+    elif roi_scale_factor is not None:
         name, tail = 'dm_roi_align_scaled_fwd', (float(roi_scale_factor), _p(out), _p(levels))
     else:
         # where the library says ordering pays, a workspace: the RoIs are first ordered by level and position (one extra
@@ -135,9 +149,16 @@ def roi_align(feats, rois, output_size, spatial_scales, sampling_ratio=0, finest
     return (out, levels) if return_levels else out
 
 
+def roi_align_strided_supported(map_sizes, C, output_size, bin_step):
+    """dm_roi_align_strided_supported: does ``roi_align(..., bin_step=bin_step)`` take these maps?  Host only."""
+    return bool(lib().dm_roi_align_strided_supported(len(map_sizes), _int_array([s[0] for s in map_sizes]),
+                                                     _int_array([s[1] for s in map_sizes]), int(C), int(output_size), int(bin_step)))
+
+
 ROI_PLAN_FIELDS = ('kernel', 'P0', 'P1', 'grid', 'threads', 'lds_bytes', 'CT', 'order', 'lds_floats', 'levels')
 ROI_KERNELS = ('order', 'tile', 'band', 'generic', 'bwd_gather')          # field 'kernel' of a plan record
 ROI_ENTRIES = ('forward', 'add', 'backward')                              # dm_roi_align_plan's `entry`
+ROI_ENTRY_STRIDED = 'strided'                                             # ... and entry 3: roi_align(..., bin_step=), the step in `pool`
 
 
 def roi_align_plan_raw(entry, map_sizes, B, C, N, output_size, sampling_ratio=0, workspace_bytes=0, workspace=0, pool=0):
@@ -148,18 +169,20 @@ def roi_align_plan_raw(entry, map_sizes, B, C, N, output_size, sampling_ratio=0,
     n, cap = consts['DM_ROI_PLAN_INTS'], consts['DM_ROI_PLAN_MAX_LAUNCHES']
     assert len(ROI_PLAN_FIELDS) == n
     rec = (ctypes.c_int * (n * cap))(*([-1] * (n * cap)))
-    rc = lib().dm_roi_align_plan(ROI_ENTRIES.index(entry), int(pool), len(map_sizes), _int_array([s[0] for s in map_sizes]),
+    rc = lib().dm_roi_align_plan(len(ROI_ENTRIES) if entry == ROI_ENTRY_STRIDED else ROI_ENTRIES.index(entry), int(pool), len(map_sizes), _int_array([s[0] for s in map_sizes]),
                                  _int_array([s[1] for s in map_sizes]), int(B), int(C), int(N), int(output_size),
                                  int(sampling_ratio), int(workspace_bytes), int(workspace), rec, cap)
     return rc, [dict(zip(ROI_PLAN_FIELDS, rec[i * n:(i + 1) * n])) for i in range(max(rc, 0))]
 
 
-def roi_align_plan(entry, map_sizes, B, C, N, output_size, sampling_ratio=0, workspace=None, pool=0):
-    """The launches ``roi_align`` ('forward'), ``roi_align_add_`` ('add', with its ``pool``) or ``roi_align_backward``
+def roi_align_plan(entry, map_sizes, B, C, N, output_size, sampling_ratio=0, workspace=None, pool=0, bin_step=None):
+    """(``entry='strided'`` with ``bin_step``: what ``roi_align(..., bin_step=bin_step)`` would launch.)  The launches ``roi_align`` ('forward'), ``roi_align_add_`` ('add', with its ``pool``) or ``roi_align_backward``
     ('backward') would make for these numbers, as the launcher's own route says (include/dynamask_hip.h, dm_roi_align_plan):
     a list of up to two dicts with the keys ROI_PLAN_FIELDS (two: the order kernel in front of the tile kernel, or the two
     sampling-grid classes of the generic kernel).  Raises where the call would fail.  ``workspace`` (forward): None = what
     ``roi_align`` itself passes (the bytes the library asks for, unless ROI_WORKSPACE is cleared), else a byte count."""
+    if entry == ROI_ENTRY_STRIDED:
+        pool = 0 if bin_step is None else bin_step
     if workspace is None:
         workspace = int(lib().dm_roi_align_workspace_bytes(N, output_size)) if ROI_WORKSPACE and entry == 'forward' else 0
     rc, recs = roi_align_plan_raw(entry, map_sizes, B, C, N, output_size, sampling_ratio, workspace, 1 if workspace > 0 else 0, pool)

@@ -90,19 +90,36 @@ class SingleRoIExtractor(BaseRoIExtractor):
                               float(self.finest_scale), return_levels=True)
         return lv.long()
 
-    def forward(self, feats, rois, roi_scale_factor=None):
+    def supports_bin_step(self, feats, bin_step):
+        """Does ``forward(feats, rois, bin_step=bin_step)`` run (dm_roi_align_strided_supported)?  Host only."""
+        feats = list(feats)[:self.num_inputs]
+        return len(feats) == self.num_inputs and ops.roi_align_strided_supported(
+            [tuple(f.shape[2:]) for f in feats], feats[0].shape[1], self.roi_layers[0].output_size[0], bin_step)
+
+    def forward(self, feats, rois, roi_scale_factor=None, bin_step=None):
         """``roi_scale_factor`` (single_level_roi_extractor.py:69-71): the levels come from ``rois`` as given, the samples
-        from the boxes rescaled about their centres (base_roi_extractor.py:57-80), inside the same launch."""
+        from the boxes rescaled about their centres (base_roi_extractor.py:57-80), inside the same launch.
+        ``bin_step`` (extension; None: today's call): only the bins (i * bin_step, j * bin_step) of the extraction,
+        [N, C, ceil(P / bin_step), ceil(P / bin_step)] -- what a stride-``bin_step`` 1x1 convolution reads of it."""
         lay = self.roi_layers[0]
         P = lay.output_size[0]
         feats = list(feats)[:self.num_inputs]
         if len(feats) != self.num_inputs:
             raise ValueError(f'expected {self.num_inputs} feature maps, got {len(feats)}')
+        if self.num_inputs == 1:
+            roi_scale_factor = None       # single_level_roi_extractor.py:64-67 returns before the rescale: one level ignores it
+        if bin_step is not None:
+            if isinstance(bin_step, bool) or not isinstance(bin_step, int) or bin_step < 1:
+                raise ValueError(f'bin_step must be an int >= 1, got {bin_step!r}')
+            if roi_scale_factor is not None:
+                raise NotImplementedError('SingleRoIExtractor: bin_step together with roi_scale_factor is not built')
+            P = -(-P // bin_step)
         if rois.shape[0] == 0:
             return feats[0].new_zeros((0, self.out_channels, P, P))
         scales = [l.spatial_scale for l in self.roi_layers]
-        if self.num_inputs == 1:
-            roi_scale_factor = None       # single_level_roi_extractor.py:64-67 returns before the rescale: one level ignores it
+        if bin_step is not None:
+            return ops.roi_align(feats, rois, lay.output_size[0], scales, lay.sampling_ratio, float(self.finest_scale),
+                                 bin_step=bin_step)
         return ops.roi_align(feats, rois, P, scales, lay.sampling_ratio, float(self.finest_scale),
                              roi_scale_factor=roi_scale_factor)
 

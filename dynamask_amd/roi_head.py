@@ -152,6 +152,9 @@ class StandardRoIHead(nn.Module):
     mask branch is the stock one: ``_mask_forward(x, rois)`` -> ``{'mask_pred': [N, classes, 28, 28], 'mask_feats'}``.
     ``BaseRoIHead.__init__`` of the fork builds ``mask_predictor`` / ``semantic_roi_extractor`` for EVERY RoI head (Quirk
     Q4), so the ``state_dict`` carries the ``mask_predictor.*`` keys here too, as the reference's does.
+    ``shared_head=`` (the C4 configs: ``ResLayer``, ResNet layer4 per RoI) and ``mask_roi_extractor=None`` (the mask branch
+    shares the bbox extractor) follow standard_roi_head.py:28-44: ``_roi_feats`` runs extractor then shared head for both
+    branches, inference only.
     Training: ``forward_train`` follows standard_roi_head.py:70-134; its mask loss ends in ``FCNMaskHead.loss``, which
     the fork broke (Quirk Q5) -- it raises here as it does there, the bbox losses and the mask targets are computed."""
 
@@ -167,13 +170,25 @@ class StandardRoIHead(nn.Module):
             from . import bbox_heads  # noqa: F401  (registers Shared2FCBBoxHead)
             self.bbox_roi_extractor = build_roi_extractor(bbox_roi_extractor)
             self.bbox_head = build_head(bbox_head)
+        # standard_roi_head.py:28-44 / base_roi_head.py (shared_head): the C4 configs' per-RoI ResNet stage behind the
+        # extractor of both branches.  Only this class's own forward paths apply it (``_roi_feats``): a subclass with a
+        # mask or bbox path of its own refuses it here instead of ignoring it.
+        if not self._applies_shared_head() and (shared_head is not None or (mask_head is not None and mask_roi_extractor is None)):
+            raise NotImplementedError(f'{type(self).__name__}: shared_head / the shared RoI extractor (mask_roi_extractor=None) '
+                                      'are built for StandardRoIHead alone (the C4 configs)')
         if shared_head is not None:
-            raise NotImplementedError('shared_head is None in configs/dynamask')
+            from . import shared_heads  # noqa: F401  (registers ResLayer)
+            from .registry import SHARED_HEADS, build
+            self.shared_head = build(shared_head, SHARED_HEADS)
         if mask_head is not None:
-            if mask_roi_extractor is None:
-                raise NotImplementedError('configs/dynamask gives the mask branch its own RoI extractor')
-            self.mask_roi_extractor = build_roi_extractor(mask_roi_extractor)
-            self.share_roi_extractor = False
+            if mask_roi_extractor is not None:
+                self.mask_roi_extractor = build_roi_extractor(mask_roi_extractor)
+                self.share_roi_extractor = False
+            else:
+                if bbox_head is None:
+                    raise ValueError('mask_roi_extractor=None shares the bbox RoI extractor: a bbox branch is needed')
+                self.share_roi_extractor = True
+                self.mask_roi_extractor = self.bbox_roi_extractor
             self.mask_head = build_head(mask_head)
         self.init_assigner_sampler()
         # base_roi_head.py:53-58 (created for every RoI head: Quirk Q4)
@@ -199,6 +214,38 @@ class StandardRoIHead(nn.Module):
     @property
     def with_mask(self):
         return hasattr(self, 'mask_head') and self.mask_head is not None
+
+    @property
+    def with_shared_head(self):
+        return hasattr(self, 'shared_head') and self.shared_head is not None
+
+    # the methods of this class through which a shared head reaches both branches (``_roi_feats``)
+    _SHARED_HEAD_PATH = ('_bbox_forward', '_mask_forward', '_mask_logits', '_bbox_test_preds', '_mask_test_pred', 'simple_test')
+
+    @classmethod
+    def _applies_shared_head(cls):
+        """Are this class's forward paths the ones above?  A subclass that overrides one of them has a bbox or mask path
+        of its own, which does not apply a shared head."""
+        return all(getattr(cls, n) is getattr(StandardRoIHead, n) for n in StandardRoIHead._SHARED_HEAD_PATH)
+
+    def _roi_feats(self, extractor, x, rois):
+        """Extractor, then shared head (standard_roi_head.py:138-141, 204-207): the RoI features both branches' heads read.
+        A stride-2 shared head reads only the even rows and columns of the extraction, so where the extractor can produce
+        just those (``bin_step=2``) it does and the head runs on them (``forward_sampled``); else the dense extraction and
+        ``forward``.  Same bits either way."""
+        feats = x[:extractor.num_inputs]
+        if not self.with_shared_head:
+            return extractor(feats, rois)
+        if self.shared_head_strided_extraction(extractor, feats):
+            return self.shared_head.forward_sampled(extractor(feats, rois, bin_step=2))
+        return self.shared_head(extractor(feats, rois))
+
+    def shared_head_strided_extraction(self, extractor, feats):
+        """Does ``_roi_feats`` take the strided extraction for these maps?"""
+        return (self.STRIDED_EXTRACTION and getattr(self.shared_head, 'stride', 1) == 2 and hasattr(self.shared_head, 'forward_sampled')
+                and hasattr(extractor, 'supports_bin_step') and extractor.supports_bin_step(feats, 2))
+
+    STRIDED_EXTRACTION = True      # (tests compare with the dense extraction + ``forward`` by clearing it)
 
     def init_weights(self, pretrained=None):
         if self.with_mask:
@@ -226,6 +273,9 @@ class StandardRoIHead(nn.Module):
 
     def forward_train(self, x, img_metas, proposal_list, gt_bboxes, gt_labels, gt_bboxes_ignore=None, gt_masks=None):
         """standard_roi_head.py:70-134."""
+        if self.with_shared_head:
+            raise NotImplementedError(f'{type(self).__name__}.forward_train with a shared head: the backward through the '
+                                      'shared head (ResNet layer4) is not built; the C4 configs run inference')
         sampling_results = self._assign_and_sample(x, img_metas, proposal_list, gt_bboxes, gt_labels, gt_bboxes_ignore)
         losses = dict()
         bbox_results = None
@@ -258,8 +308,7 @@ class StandardRoIHead(nn.Module):
         """standard_roi_head.py:199-215."""
         assert (rois is not None) ^ (pos_inds is not None and bbox_feats is not None)
         if rois is not None:
-            ext = self.mask_roi_extractor
-            mask_feats = ext(x[:ext.num_inputs], rois.contiguous())
+            mask_feats = self._roi_feats(self.mask_roi_extractor, x, rois.contiguous())
         else:
             mask_feats = bbox_feats[pos_inds].contiguous()
         return dict(mask_pred=self.mask_head(mask_feats), mask_feats=mask_feats)
@@ -278,8 +327,8 @@ class StandardRoIHead(nn.Module):
 
     # ------------------------------------------------------------ bbox branch (inference)
     def _bbox_forward(self, x, rois):
-        """standard_roi_head.py:135-146."""
-        bbox_feats = self.bbox_roi_extractor(x[:self.bbox_roi_extractor.num_inputs], rois)
+        """standard_roi_head.py:135-146 (``bbox_feats``: what the shared head returns, where there is one)."""
+        bbox_feats = self._roi_feats(self.bbox_roi_extractor, x, rois)
         cls_score, bbox_pred = self.bbox_head(bbox_feats)
         return dict(cls_score=cls_score, bbox_pred=bbox_pred, bbox_feats=bbox_feats)
 
@@ -324,6 +373,8 @@ class StandardRoIHead(nn.Module):
         extractor's features, upsampled by its ``scale_factor``."""
         h = self.mask_head
         s = self.mask_roi_extractor.roi_layers[0].output_size[0]
+        if self.with_shared_head:
+            s = -(-s // self.shared_head.stride)        # (the C4 configs: 14 -> 7 features, 14 x 14 logits)
         return h.conv_logits.out_channels, int(s * (h.scale_factor if h.upsample is not None else 1))
 
     def _segm_num_classes(self):

@@ -128,6 +128,7 @@ int dm_roi_align_bwd(const float* grad_out, float* const* grad_feats, const int*
  * the error code the call would return for these numbers, and then writes nothing.  Record l, ints [l * DM_ROI_PLAN_INTS ..):
  *   0 kernel: 0 roi_order_kernel, 1 roi_align_tile_kernel, 2 roi_align_band_kernel, 3 roi_align_kernel,
  *     4 roi_align_bwd_gather_kernel;
+ *   (entry 3, dm_roi_align_strided_fwd with its bin_step in `pool`: section K29; kernel 1 with parameters 3, bin_step)
  *   1, 2 its template parameters: MODE, 0 (kernel 1: 0 stores, 1 adds, 2 adds the 2 x 2 block means); TB, WPC (kernel 2);
  *     BWD, GCLS (kernel 3); zeros (kernels 0, 4);
  *   3 grid x (RoIs x channel chunks; kernel 0: ceil(N / 16));  4 threads per workgroup;  5 dynamic LDS bytes;
@@ -1178,6 +1179,29 @@ int dm_roi_align_scaled_fwd(const float* const* feats, const int* H, const int* 
                             float finest_scale, float roi_scale_factor, float* out, int32_t* levels_out, dm_stream_t stream);
 int dm_global_avg_pool_supported(int N, int C, int HW);
 int dm_global_avg_pool_fwd(const float* x, int N, int C, int HW, float* out, dm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * K29  Mask R-CNN / Faster R-CNN C4 inference (configs/_base_/models/{mask,faster}_rcnn_r50_caffe_c4.py): the shared
+ *      head (ResNet layer4 per RoI, roi_heads/shared_heads/res_layer.py) is nine dm_conv2d_fwd launches with eval-mode
+ *      BatchNorm folded on the host, the plain BBoxHead dm_global_avg_pool_fwd + dm_fc_fwd.  With style='caffe' the
+ *      stride of layer4 sits in two 1x1 convolutions that read only the even rows and columns of the 14 x 14 RoI
+ *      features; this entry point produces only those bins.
+ *
+ * dm_roi_align_strided_fwd: the arguments of dm_roi_align_fwd and bin_step >= 1.  out [N, C, Po, Po], Po = ceil(P / bin_step):
+ * out[n, c, i, j] is bin (i * bin_step, j * bin_step) of the P x P extraction of RoI n, and no other bin is sampled or
+ * stored (no [N, C, P, P] intermediate).  A kept bin has the samples, products and summation order of dm_roi_align_fwd
+ * without a workspace (the tile kernel at 16 channels per workgroup): its bits do not depend on N, on the other RoIs of
+ * the call or on the DM_ROI_SORT* knobs.  The RoIs are walked in their own order.  levels_out as the forward's.
+ * dm_roi_align_strided_supported: 1 exactly where the call is taken: 1 <= num_levels <= 4, every map non-empty and of
+ * at most 2^23 pixels, C % 4 == 0, 2 <= P, P * P <= 256 (where dm_roi_align_fwd takes its tile kernel) and
+ * 1 <= bin_step <= P.  Anything else: DM_ERR_UNSUPPORTED (bin_step < 1: DM_ERR_INVALID_ARG).  N == 0 enqueues nothing.
+ * dm_roi_align_plan reports the launch under entry 3, with bin_step in `pool`: one record, kernel 1 with MODE 3 and
+ * bin_step as its parameters, CT 16, levels 1; it takes no workspace.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int dm_roi_align_strided_supported(int num_levels, const int* H, const int* W, int C, int P, int bin_step);
+int dm_roi_align_strided_fwd(const float* const* feats, const int* H, const int* W, const float* spatial_scales,
+                             int num_levels, int B, int C, const float* rois, int N, int P, int sampling_ratio,
+                             float finest_scale, int bin_step, float* out, int32_t* levels_out, dm_stream_t stream);
 
 #ifdef __cplusplus
 }
