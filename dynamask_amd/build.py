@@ -1,5 +1,6 @@
 """Build libdynamask_hip.so (gfx950) in-tree with hipcc.  No torch involved:
 the device code is HIP from the start, the library is a plain C-ABI .so."""
+import glob
 import os
 import subprocess
 import sys
@@ -37,15 +38,16 @@ def build_library(force=False, verbose=True, extra_flags=(), lib=LIB, objdir=Non
     """``extra_flags`` / ``lib`` / ``objdir``: a second build beside the product's (A/B measurements: tools/)."""
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    deps = srcs + [os.path.join(CSRC, 'common.h'), os.path.join(ROOT, 'include', 'dynamask_hip.h'), os.path.abspath(__file__)]
-    if not force and _newer(lib, deps):
+    # every object depends on every header of csrc/ (no per-file include scan), the C header and this file
+    common = sorted(glob.glob(os.path.join(CSRC, '*.h'))) + [os.path.join(ROOT, 'include', 'dynamask_hip.h'), os.path.abspath(__file__)]
+    if not force and _newer(lib, srcs + common):
         return lib
     objdir = objdir or os.path.join(HERE, 'build')
     os.makedirs(objdir, exist_ok=True)
     objs = []
     for s in srcs:
         o = os.path.join(objdir, os.path.basename(s) + '.o')
-        if force or not _newer(o, [s] + deps[-3:]):
+        if force or not _newer(o, [s] + common):
             # the flag set travels into the library (dm_build_info): _lib.py refuses one that lacks -packed-fp32-ops
             said = ' '.join([*FLAGS, *extra_flags]) or 'none'
             cmd = [hipcc, '--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', *FLAGS, *extra_flags, f'-DDM_BUILD_FLAGS="{said}"',

@@ -13,9 +13,8 @@
 // (8 + 2d) x (16 + 2d) positions, at most 24 x 32 = 768 at d = 8, whatever the map's width.  A tap (ky, kx) of
 // dilation d reads the plane at offset (ky d) Pw + kx d (Pw = 16 + 2d): the dilation is a runtime value.
 //
-// Workgroup: 256 threads, 4 waves as 2 (couts) x 2 (pixels), each wave 32 WM couts x 64 pixels.  TM = 64 (WM = 1, maps
-// of <= 64 couts) or 128 (WM = 2).  K is walked in chunks of 8 channels (two quads): the next chunk's global loads are
-// issued into registers before the MFMAs of the current one and written to LDS after them, as in conv_igemm.hip.
+// Workgroup and K walk are mfma_tile.h's (which also holds the weight operand and the B register staging); each
+// wave computes 32 WM couts x 64 pixels.  TM = 64 (WM = 1, maps of <= 64 couts) or 128 (WM = 2).
 // LDS: A 9 x 2 x TM float4 (36 KiB at TM = 128) + B 2 x 768 float4 (24 KiB): 60 KiB per workgroup.
 //
 // NBR = 3 (dm_conv3x3_multidil_fwd): MultiBranchFusion's  sum_b relu(conv_{d_b}(x) + bias_b)  in one launch.  The branches
@@ -23,18 +22,15 @@
 // accumulators go through bias + ReLU into a running sum in registers, then are cleared for the next branch.  The sum is
 // formed as ((t_1 + t_2) + t_3), the order in which the unfused sequence (three dm_conv3x3_dil_fwd, the second and third
 // with the "add into out" bit) adds: the fused and the unfused launches give the same bits.
-#include "common.h"
+#include "mfma_tile.h"
 
 namespace {
 
 constexpr int DIL_TH = 8, DIL_TW = 16;        // pixel block of a workgroup
 constexpr int DIL_TN = DIL_TH * DIL_TW;       // 128
-constexpr int DIL_NT = 256;                   // threads
-constexpr int DIL_CK = 8;                     // channels per K chunk
-constexpr int DIL_NQ = DIL_CK / 4;            // quads per chunk
 constexpr int DIL_MAXD = 8;
 constexpr int DIL_PLANE_MAX = (DIL_TH + 2 * DIL_MAXD) * (DIL_TW + 2 * DIL_MAXD);   // 768
-constexpr int DIL_MAXPOS = (DIL_PLANE_MAX + DIL_NT - 1) / DIL_NT;                  // 3
+constexpr int DIL_MAXPOS = (DIL_PLANE_MAX + DM_CONV_NT - 1) / DM_CONV_NT;          // 3
 
 // epilogue flags of the two entry points (dynamask_hip.h)
 constexpr int DIL_RELU = 1;
@@ -54,13 +50,12 @@ struct DilArgs {
 };
 
 template <int WM, int NBR>
-__global__ __launch_bounds__(DIL_NT) void conv3x3_dil_kernel(DilArgs a) {
+__global__ __launch_bounds__(DM_CONV_NT) void conv3x3_dil_kernel(DilArgs a) {
   constexpr int TM = 2 * WM * 32;
   constexpr int WN = 2;
-  constexpr int A_F4 = 9 * DIL_NQ * TM;
-  constexpr int A_PER_T = (A_F4 + DIL_NT - 1) / DIL_NT;
-  __shared__ dm_f32x4 ldsA[A_F4];
-  __shared__ dm_f32x4 ldsB[DIL_NQ * DIL_PLANE_MAX];
+  using WT = dm_wtile<TM, DM_CONV_NQ, DM_CONV_NT>;
+  __shared__ dm_f32x4 ldsA[WT::F4];
+  __shared__ dm_f32x4 ldsB[DM_CONV_NQ * DIL_PLANE_MAX];
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -106,7 +101,7 @@ __global__ __launch_bounds__(DIL_NT) void conv3x3_dil_kernel(DilArgs a) {
 
   dm_f32x16 acc[WM][WN];
   dm_f32x16 sum[NBR > 1 ? WM : 1][NBR > 1 ? WN : 1];
-  const int co_lane = m0 + wave_m * WM * 32 + 4 * hi;
+  const int co_wave = m0 + wave_m * WM * 32;
 
 #pragma unroll 1
   for (int b = 0; b < NBR; ++b) {
@@ -115,18 +110,13 @@ __global__ __launch_bounds__(DIL_NT) void conv3x3_dil_kernel(DilArgs a) {
     const int plane = (DIL_TH + 2 * d) * Pw;
     const float* wq = a.wq[b];
 
-#pragma unroll
-    for (int i = 0; i < WM; ++i)
-#pragma unroll
-      for (int j = 0; j < WN; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    dm_acc_clear(acc);
 
     // B staging: thread -> plane positions tid + k * 256; its source pixel (or -1: halo outside the map)
     int st_off[DIL_MAXPOS];
 #pragma unroll
     for (int k = 0; k < DIL_MAXPOS; ++k) {
-      const int pos = tid + k * DIL_NT;
+      const int pos = tid + k * DM_CONV_NT;
       st_off[k] = -1;
       if (pos < plane) {
         const int py = pos / Pw, px = pos - (pos / Pw) * Pw;
@@ -138,59 +128,40 @@ __global__ __launch_bounds__(DIL_NT) void conv3x3_dil_kernel(DilArgs a) {
 #pragma unroll
     for (int j = 0; j < WN; ++j) lane_base[j] = ty[j] * Pw + tx[j] + hi * plane;
 
-    dm_f32x4 ra[A_PER_T];
-    dm_f32x4 rb[DIL_MAXPOS * DIL_NQ];
+    dm_f32x4 ra[WT::PER_T];
+    dm_f32x4 rb[DIL_MAXPOS * DM_CONV_NQ];
     auto prefetch = [&](int c0) {
-      const float* abase = wq + (size_t)(c0 / 4) * a.CoutP * 4;
-#pragma unroll
-      for (int i = 0; i < A_PER_T; ++i) {
-        const int idx = tid + i * DIL_NT;
-        const int m = idx % TM, tq = idx / TM;
-        const int tap = tq / DIL_NQ, q = tq % DIL_NQ;
-        dm_f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (idx < A_F4 && m0 + m < a.CoutP)
-          v = *reinterpret_cast<const dm_f32x4*>(abase + (((size_t)tap * a.KQ + q) * a.CoutP + m0 + m) * 4);
-        ra[i] = v;
-      }
+      WT::fetch(ra, wq, c0 / 4, a.KQ, a.CoutP, m0, tid);
       const float* sp = xn + (size_t)c0 * HW;
 #pragma unroll
-      for (int k = 0; k < DIL_MAXPOS; ++k) {
-        if (st_off[k] >= 0) {
-          const float* gp = sp + st_off[k];
-#pragma unroll
-          for (int qd = 0; qd < DIL_NQ; ++qd)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) rb[k * DIL_NQ + qd][e] = gp[(size_t)(qd * 4 + e) * HW];
-        } else {
-#pragma unroll
-          for (int qd = 0; qd < DIL_NQ; ++qd) rb[k * DIL_NQ + qd] = dm_f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-      }
+      for (int k = 0; k < DIL_MAXPOS; ++k) dm_fetch_quads<DM_CONV_NQ>(rb + k * DM_CONV_NQ, sp, st_off[k], HW);
     };
     auto commit = [&]() {
-#pragma unroll
-      for (int i = 0; i < A_PER_T; ++i)
-        if (A_F4 % DIL_NT == 0 || tid + i * DIL_NT < A_F4) ldsA[tid + i * DIL_NT] = ra[i];
+      WT::commit(ldsA, ra, tid);
 #pragma unroll
       for (int k = 0; k < DIL_MAXPOS; ++k) {
-        const int pos = tid + k * DIL_NT;
+        const int pos = tid + k * DM_CONV_NT;
         if (pos < plane) {
 #pragma unroll
-          for (int qd = 0; qd < DIL_NQ; ++qd) ldsB[qd * plane + pos] = rb[k * DIL_NQ + qd];
+          for (int qd = 0; qd < DM_CONV_NQ; ++qd) ldsB[qd * plane + pos] = rb[k * DM_CONV_NQ + qd];
         }
       }
     };
 
     prefetch(0);
 #pragma unroll 1
-    for (int c0 = 0; c0 < a.C; c0 += DIL_CK) {
+    for (int c0 = 0; c0 < a.C; c0 += DM_CONV_CK) {
       commit();
       __syncthreads();
-      if (c0 + DIL_CK < a.C) prefetch(c0 + DIL_CK);
+      if (c0 + DM_CONV_CK < a.C) prefetch(c0 + DM_CONV_CK);
+      // The nine taps, fragments double-buffered one tap ahead: mfma_tile.h's dm_nine_taps written out, the one block this
+      // kernel does not share.  Routed through that function (or only its MFMA step through dm_mfma_quad) the compiler
+      // issues this kernel's LDS reads later (waits of lgkmcnt 1 / 0 where this form has 3 / 1) and the 256 x 512 map
+      // and the 64-cout RoI maps measure 0.3 .. 0.6 % slower.  A change to the loop goes into both.
       auto load_frag = [&](int tap, dm_f32x4* av, dm_f32x4* bv) {
         const int tapoff = (tap / 3) * d * Pw + (tap % 3) * d;
 #pragma unroll
-        for (int i = 0; i < WM; ++i) av[i] = ldsA[(tap * DIL_NQ + hi) * TM + (wave_m * WM + i) * 32 + l31];
+        for (int i = 0; i < WM; ++i) av[i] = ldsA[(tap * DM_CONV_NQ + hi) * TM + (wave_m * WM + i) * 32 + l31];
 #pragma unroll
         for (int j = 0; j < WN; ++j) bv[j] = ldsB[lane_base[j] + tapoff];
       };
@@ -218,7 +189,7 @@ __global__ __launch_bounds__(DIL_NT) void conv3x3_dil_kernel(DilArgs a) {
       for (int i = 0; i < WM; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int co = min(co_lane + i * 32 + (r & 3) + 8 * (r >> 2), a.Cout - 1);
+          const int co = min(co_wave + i * 32 + dm_dtile_row(r, hi), a.Cout - 1);
           const float bv_ = bias ? bias[co] : 0.f;
 #pragma unroll
           for (int j = 0; j < WN; ++j) {
@@ -238,7 +209,7 @@ __global__ __launch_bounds__(DIL_NT) void conv3x3_dil_kernel(DilArgs a) {
   for (int i = 0; i < WM; ++i)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int co = co_lane + i * 32 + (r & 3) + 8 * (r >> 2);
+      const int co = co_wave + i * 32 + dm_dtile_row(r, hi);
       if (co >= a.Cout) continue;
       const float bv_ = (NBR == 1 && a.bias[0]) ? a.bias[0][co] : 0.f;
 #pragma unroll
@@ -265,10 +236,9 @@ __global__ void sigmoid_kernel(const float* __restrict__ x, long long n, float* 
 }
 
 bool dil_shape_ok(int NB, int C, int H, int W, int Cout) {
-  if (NB < 1 || C < DIL_CK || C % DIL_CK != 0 || H < 1 || W < 1 || Cout < 1) return false;
+  if (!dm_conv3x3_shape_ok(NB, C, H, W, Cout)) return false;
   const long long tiles = (long long)NB * dm_ceil_div(H, DIL_TH) * dm_ceil_div(W, DIL_TW);
-  const long long mt = dm_ceil_div(dm_conv_packed_cout(Cout), Cout <= 64 ? 64 : 128);
-  return tiles * mt <= 0x7fffffffLL;
+  return tiles * dm_cout_tiles(Cout) <= 0x7fffffffLL;
 }
 
 int run_dil(DilArgs& a, hipStream_t st) {
@@ -278,8 +248,8 @@ int run_dil(DilArgs& a, hipStream_t st) {
   a.tiles_y = dm_ceil_div(a.H, DIL_TH);
   a.ntiles = a.NB * a.tiles_x * a.tiles_y;
   const bool narrow = a.Cout <= 64;
-  a.MT = dm_ceil_div(a.CoutP, narrow ? 64 : 128);
-  const dim3 grid((unsigned)((long long)a.MT * a.ntiles)), block(DIL_NT);
+  a.MT = dm_cout_tiles(a.Cout);
+  const dim3 grid((unsigned)((long long)a.MT * a.ntiles)), block(DM_CONV_NT);
   if (a.nbr == 1) {
     if (narrow) DM_LAUNCH((conv3x3_dil_kernel<1, 1>), grid, block, 0, st, a);
     else DM_LAUNCH((conv3x3_dil_kernel<2, 1>), grid, block, 0, st, a);
@@ -288,13 +258,6 @@ int run_dil(DilArgs& a, hipStream_t st) {
     else DM_LAUNCH((conv3x3_dil_kernel<2, 3>), grid, block, 0, st, a);
   }
   return dm_check_launch();
-}
-
-// flag bits the two entry points take: 0 (ReLU), 2 (add into out), 3 (dm_conv2d_fwd's scheduling hint, ignored)
-int dil_flags_check(int flags) {
-  if (flags & 16) return DM_ERR_UNSUPPORTED;          // bf16x3: exact fp32 only
-  if (flags & ~(DIL_RELU | DIL_ADD | 8)) return DM_ERR_INVALID_ARG;   // (bit 1, dm_conv2d_fwd's add-before-ReLU, is not one)
-  return DM_OK;
 }
 
 }  // namespace
@@ -306,7 +269,7 @@ extern "C" int dm_conv3x3_dil_supported(int NB, int C, int H, int W, int Cout, i
 extern "C" int dm_conv3x3_dil_fwd(const float* x, int NB, int C, int H, int W, const float* w_packed, const float* bias,
                                   int Cout, int dilation, int flags, float* out, dm_stream_t stream) {
   if (!x || !w_packed || !out) return DM_ERR_INVALID_ARG;
-  const int fc = dil_flags_check(flags);
+  const int fc = dm_flags_check(flags, DIL_RELU | DIL_ADD);   // (bit 1, dm_conv2d_fwd's add-before-ReLU, is not one)
   if (fc != DM_OK) return fc;
   if (!dm_conv3x3_dil_supported(NB, C, H, W, Cout, dilation)) return DM_ERR_UNSUPPORTED;
   DilArgs a = {};
@@ -327,7 +290,7 @@ extern "C" int dm_conv3x3_multidil_fwd(const float* x, int NB, int C, int H, int
                                        const float* const* bias, int Cout, int num_branches, const int* dilations, int flags,
                                        float* out, dm_stream_t stream) {
   if (!x || !w_packed || !out || !dilations) return DM_ERR_INVALID_ARG;
-  const int fc = dil_flags_check(flags);
+  const int fc = dm_flags_check(flags, DIL_RELU | DIL_ADD);   // (bit 1, dm_conv2d_fwd's add-before-ReLU, is not one)
   if (fc != DM_OK) return fc;
   if (!dm_conv3x3_multidil_supported(NB, C, H, W, Cout, num_branches, dilations)) return DM_ERR_UNSUPPORTED;
   DilArgs a = {};
@@ -346,7 +309,6 @@ extern "C" int dm_conv3x3_multidil_fwd(const float* x, int NB, int C, int H, int
 extern "C" int dm_sigmoid_fwd(const float* x, long long n, float* out, dm_stream_t stream) {
   if (n < 0 || (n > 0 && (!x || !out))) return DM_ERR_INVALID_ARG;
   if (n == 0) return DM_OK;
-  const int blocks = (int)(n / 256 + 1 < 4096 ? n / 256 + 1 : 4096);
-  DM_LAUNCH(sigmoid_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, n, out);
+  DM_LAUNCH(sigmoid_kernel, dim3(dm_grid_1d(n, 4096)), dim3(256), 0, (hipStream_t)stream, x, n, out);
   return dm_check_launch();
 }

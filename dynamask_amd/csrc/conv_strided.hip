@@ -7,12 +7,11 @@
 //                         one launch; it becomes the second source of the first conv (dm_conv2d_fwd), no torch.cat.
 //   dm_mask_iou_scores    mask_iou_pred[i, label_i] * det_bboxes[i, -1] (MaskIoUHead.get_mask_scores), one launch.
 //
-// GEMM view and operand layout of the convolution are conv_dilated.hip's (Out[co, pixel] = bias[co] + sum_k W[k, co]
-// X[k, pixel], k = (tap, channel), channels in quads, one ds_read_b128 per operand feeds four MFMAs), and so is the
-// weight layout: dm_conv_pack_weight(ksize 3, one source) -> [tap][KQ][CoutP][4], so a layer's _Packed cache is shared.
-// What differs is the pixel tile.  At the shapes that matter (7 x 7 outputs of 16 .. 100 RoIs: 784 .. 4 900 pixels) a
-// tile of one RoI would fill 49 of 64 pixel slots, and a plain tiling gives less than one round over the 256 CUs.  So
-// a workgroup's 64 output pixels are 64 CONSECUTIVE pixels of the flattened [NB, Ho, Wo] grid, across RoI boundaries,
+// GEMM view, weight operand (dm_conv_pack_weight(ksize 3, one source) -> [tap][KQ][CoutP][4], so a layer's _Packed cache
+// is shared), workgroup, K walk, tap loop and MFMA order are conv_dilated.hip's: the shared code is mfma_tile.h.
+// This kernel's own part is the pixel tile.  At the shapes that matter (7 x 7 outputs of 16 .. 100 RoIs: 784 .. 4 900
+// pixels) a tile of one RoI would fill 49 of 64 pixel slots, and a plain tiling gives less than one round over the
+// 256 CUs.  So a workgroup's 64 output pixels are 64 CONSECUTIVE pixels of the flattened [NB, Ho, Wo] grid, across RoI boundaries,
 // and its B operand is gathered im2col-style: per K chunk (8 channels) every (tap, pixel) slot loads the two channel
 // quads of its input position (stride 2, or zero outside the map) into LDS, [tap][quad][pixel].  An input position is
 // read by up to four output pixels of a tile (the windows overlap by one row / column); those loads hit the L2.
@@ -20,20 +19,15 @@
 // two workgroups on every CU, as many as its LDS and registers let reside): each split stores its bare sums to a workspace [split][NB][Cout][Ho Wo], and a
 // second kernel adds them in split order ((s0 + s1) + s2 ...) and then the bias: the same bits every run.
 //
-// Workgroup: 256 threads, 4 waves as 2 (couts) x 2 (pixels), each wave WM x 32 couts x 32 pixels.  TM = 64 (WM = 1,
-// maps of <= 64 couts) or 128 (WM = 2).  As in conv_dilated.hip, the next chunk's global loads are issued into registers
-// before the MFMAs of the current one and written to LDS after them.
+// Each wave computes WM x 32 couts x 32 pixels.  TM = 64 (WM = 1, maps of <= 64 couts) or 128 (WM = 2).
 // LDS: A 9 x 2 x TM float4 (36 KiB at TM = 128) + B 9 x 2 x 64 float4 (18 KiB): 54 KiB per workgroup.
-#include "common.h"
+#include "mfma_tile.h"
 
 namespace {
 
 constexpr int S2_TN = 64;                                  // output pixels per workgroup
-constexpr int S2_NT = 256;                                 // threads
-constexpr int S2_CK = 8;                                   // channels per K chunk
-constexpr int S2_NQ = S2_CK / 4;                           // quads per chunk
 constexpr int S2_SLOTS = 9 * S2_TN;                        // (tap, pixel) gather slots per chunk
-constexpr int S2_SPT = (S2_SLOTS + S2_NT - 1) / S2_NT;     // 3 per thread
+constexpr int S2_SPT = (S2_SLOTS + DM_CONV_NT - 1) / DM_CONV_NT;   // 3 per thread
 constexpr int S2_MAXSPLIT = 8;
 
 constexpr int S2_RELU = 1;
@@ -52,12 +46,11 @@ struct S2Args {
 };
 
 template <int WM>
-__global__ __launch_bounds__(S2_NT) void conv3x3_s2_kernel(S2Args a) {
+__global__ __launch_bounds__(DM_CONV_NT) void conv3x3_s2_kernel(S2Args a) {
   constexpr int TM = 2 * WM * 32;
-  constexpr int A_F4 = 9 * S2_NQ * TM;
-  constexpr int A_PER_T = (A_F4 + S2_NT - 1) / S2_NT;
-  __shared__ dm_f32x4 ldsA[A_F4];
-  __shared__ dm_f32x4 ldsB[9 * S2_NQ * S2_TN];
+  using WT = dm_wtile<TM, DM_CONV_NQ, DM_CONV_NT>;
+  __shared__ dm_f32x4 ldsA[WT::F4];
+  __shared__ dm_f32x4 ldsB[9 * DM_CONV_NQ * S2_TN];
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -82,7 +75,7 @@ __global__ __launch_bounds__(S2_NT) void conv3x3_s2_kernel(S2Args a) {
   long long st_off[S2_SPT];
 #pragma unroll
   for (int k = 0; k < S2_SPT; ++k) {
-    const int g = tid + k * S2_NT;
+    const int g = tid + k * DM_CONV_NT;
     st_off[k] = -1;
     if (g < S2_SLOTS) {
       const int tap = g / S2_TN, p = g % S2_TN;
@@ -97,51 +90,26 @@ __global__ __launch_bounds__(S2_NT) void conv3x3_s2_kernel(S2Args a) {
     }
   }
 
-  dm_f32x16 acc[WM];
-#pragma unroll
-  for (int i = 0; i < WM; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+  dm_f32x16 acc[WM][1];
+  dm_acc_clear(acc);
 
-  dm_f32x4 ra[A_PER_T];
-  dm_f32x4 rb[S2_SPT * S2_NQ];
+  dm_f32x4 ra[WT::PER_T];
+  dm_f32x4 rb[S2_SPT * DM_CONV_NQ];
   auto prefetch = [&](int c0) {
-    const float* abase = a.wq + (size_t)(c0 / 4) * a.CoutP * 4;
+    WT::fetch(ra, a.wq, c0 / 4, a.KQ, a.CoutP, m0, tid);
+    const float* sp = a.x + (size_t)c0 * HW;
 #pragma unroll
-    for (int i = 0; i < A_PER_T; ++i) {
-      const int idx = tid + i * S2_NT;
-      const int m = idx % TM, tq = idx / TM;
-      const int tap = tq / S2_NQ, q = tq % S2_NQ;
-      dm_f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (idx < A_F4 && m0 + m < a.CoutP)
-        v = *reinterpret_cast<const dm_f32x4*>(abase + (((size_t)tap * a.KQ + q) * a.CoutP + m0 + m) * 4);
-      ra[i] = v;
-    }
-#pragma unroll
-    for (int k = 0; k < S2_SPT; ++k) {
-      if (st_off[k] >= 0) {
-        const float* gp = a.x + st_off[k] + (size_t)c0 * HW;
-#pragma unroll
-        for (int qd = 0; qd < S2_NQ; ++qd)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) rb[k * S2_NQ + qd][e] = gp[(size_t)(qd * 4 + e) * HW];
-      } else {
-#pragma unroll
-        for (int qd = 0; qd < S2_NQ; ++qd) rb[k * S2_NQ + qd] = dm_f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-    }
+    for (int k = 0; k < S2_SPT; ++k) dm_fetch_quads<DM_CONV_NQ>(rb + k * DM_CONV_NQ, sp, st_off[k], HW);
   };
   auto commit = [&]() {
-#pragma unroll
-    for (int i = 0; i < A_PER_T; ++i)
-      if (A_F4 % S2_NT == 0 || tid + i * S2_NT < A_F4) ldsA[tid + i * S2_NT] = ra[i];
+    WT::commit(ldsA, ra, tid);
 #pragma unroll
     for (int k = 0; k < S2_SPT; ++k) {
-      const int g = tid + k * S2_NT;
+      const int g = tid + k * DM_CONV_NT;
       if (g < S2_SLOTS) {
         const int tap = g / S2_TN, p = g % S2_TN;
 #pragma unroll
-        for (int qd = 0; qd < S2_NQ; ++qd) ldsB[(tap * S2_NQ + qd) * S2_TN + p] = rb[k * S2_NQ + qd];
+        for (int qd = 0; qd < DM_CONV_NQ; ++qd) ldsB[(tap * DM_CONV_NQ + qd) * S2_TN + p] = rb[k * DM_CONV_NQ + qd];
       }
     }
   };
@@ -150,29 +118,14 @@ __global__ __launch_bounds__(S2_NT) void conv3x3_s2_kernel(S2Args a) {
   const int k_lo = (int)((long long)split * a.nchunks / a.splits);
   const int k_hi = (int)((long long)(split + 1) * a.nchunks / a.splits);
   const int pix = wave_n * 32 + l31;
-  prefetch(k_lo * S2_CK);
+  const int b_lane[1] = {hi * S2_TN + pix};       // B image [tap][quad][pixel]
+  prefetch(k_lo * DM_CONV_CK);
 #pragma unroll 1
   for (int kc = k_lo; kc < k_hi; ++kc) {
     commit();
     __syncthreads();
-    if (kc + 1 < k_hi) prefetch((kc + 1) * S2_CK);
-    auto load_frag = [&](int tap, dm_f32x4* av, dm_f32x4& bv) {
-#pragma unroll
-      for (int i = 0; i < WM; ++i) av[i] = ldsA[(tap * S2_NQ + hi) * TM + (wave_m * WM + i) * 32 + l31];
-      bv = ldsB[(tap * S2_NQ + hi) * S2_TN + pix];
-    };
-    dm_f32x4 av[2][WM], bv[2];
-    load_frag(0, av[0], bv[0]);
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-      const int cur = tap & 1;
-      if (tap + 1 < 9) load_frag(tap + 1, av[cur ^ 1], bv[cur ^ 1]);
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int i = 0; i < WM; ++i)
-          acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[cur][i][e], bv[cur][e], acc[i], 0, 0, 0);
-    }
+    if (kc + 1 < k_hi) prefetch((kc + 1) * DM_CONV_CK);
+    dm_nine_taps<WT>(acc, ldsA, ldsB, hi, l31, wave_m * WM, b_lane, [](int tap) { return tap * DM_CONV_NQ * S2_TN; });
     __syncthreads();
   }
 
@@ -181,22 +134,22 @@ __global__ __launch_bounds__(S2_NT) void conv3x3_s2_kernel(S2Args a) {
   if (P >= a.npix) return;
   const long long n = P / HoWo;
   const int r_pix = (int)(P - n * HoWo);
-  const int co_lane = m0 + wave_m * WM * 32 + 4 * hi;
+  const int co_wave = m0 + wave_m * WM * 32;
   const bool relu = (a.flags & S2_RELU) != 0;
   const size_t plane_stride = (size_t)a.NB * a.Cout * HoWo;
 #pragma unroll
   for (int i = 0; i < WM; ++i)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int co = co_lane + i * 32 + (r & 3) + 8 * (r >> 2);
+      const int co = co_wave + i * 32 + dm_dtile_row(r, hi);
       if (co >= a.Cout) continue;
       const size_t o = ((size_t)n * a.Cout + co) * HoWo + r_pix;
       if (a.splits == 1) {
-        float v = acc[i][r] + (a.bias ? a.bias[co] : 0.f);
+        float v = acc[i][0][r] + (a.bias ? a.bias[co] : 0.f);
         if (relu) v = fmaxf(v, 0.f);
         a.out[o] = v;
       } else {
-        a.ws[(size_t)split * plane_stride + o] = acc[i][r];
+        a.ws[(size_t)split * plane_stride + o] = acc[i][0][r];
       }
     }
 }
@@ -253,12 +206,6 @@ __global__ __launch_bounds__(256) void mask_iou_scores_kernel(const float* __res
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-bool s2_shape_ok(int NB, int C, int H, int W, int Cout) {
-  return NB >= 1 && C >= S2_CK && C % S2_CK == 0 && H >= 1 && W >= 1 && Cout >= 1;
-}
-
-int s2_mt(int Cout) { return dm_ceil_div(dm_conv_packed_cout(Cout), Cout <= 64 ? 64 : 128); }
-
 long long s2_tiles(int NB, int H, int W) {
   return ((long long)NB * ((H + 1) / 2) * ((W + 1) / 2) + S2_TN - 1) / S2_TN;
 }
@@ -266,9 +213,9 @@ long long s2_tiles(int NB, int H, int W) {
 // the split count a request resolves to: `splits` itself, or (0) the smallest of 1, 2, 4, 8 (<= C / 8) that puts two
 // workgroups on every CU (two reside per CU: 54 KiB of LDS, <= 256 registers); -1: not supported
 int s2_resolve(int NB, int C, int H, int W, int Cout, int splits) {
-  if (!s2_shape_ok(NB, C, H, W, Cout)) return -1;
-  const int nchunks = C / S2_CK;
-  const long long base = s2_tiles(NB, H, W) * s2_mt(Cout);
+  if (!dm_conv3x3_shape_ok(NB, C, H, W, Cout)) return -1;
+  const int nchunks = C / DM_CONV_CK;
+  const long long base = s2_tiles(NB, H, W) * dm_cout_tiles(Cout);
   int s = splits;
   if (s == 0) {
     s = 1;
@@ -280,6 +227,11 @@ int s2_resolve(int NB, int C, int H, int W, int Cout, int splits) {
   return s;
 }
 
+// the workspace of a resolved split count: nothing for one split, else a plane of bare sums per split
+long long s2_ws_floats(int s, int NB, int H, int W, int Cout) {
+  return s == 1 ? 0 : (long long)s * NB * Cout * ((H + 1) / 2) * ((W + 1) / 2);
+}
+
 }  // namespace
 
 extern "C" int dm_conv3x3_s2_supported(int NB, int C, int H, int W, int Cout, int splits) {
@@ -288,38 +240,35 @@ extern "C" int dm_conv3x3_s2_supported(int NB, int C, int H, int W, int Cout, in
 
 extern "C" long long dm_conv3x3_s2_workspace_floats(int NB, int C, int H, int W, int Cout, int splits) {
   const int s = s2_resolve(NB, C, H, W, Cout, splits);
-  if (s < 0) return -1;
-  return s == 1 ? 0 : (long long)s * NB * Cout * ((H + 1) / 2) * ((W + 1) / 2);
+  return s < 0 ? -1 : s2_ws_floats(s, NB, H, W, Cout);
 }
 
 extern "C" int dm_conv3x3_s2_fwd(const float* x, int NB, int C, int H, int W, const float* w_packed, const float* bias,
                                  int Cout, int splits, int flags, float* out, float* workspace, long long workspace_floats,
                                  dm_stream_t stream) {
   if (!x || !w_packed || !out) return DM_ERR_INVALID_ARG;
-  if (flags & 16) return DM_ERR_UNSUPPORTED;                   // bf16x3: exact fp32 only
-  if (flags & ~(S2_RELU | 8)) return DM_ERR_INVALID_ARG;
+  const int fc = dm_flags_check(flags, S2_RELU);
+  if (fc != DM_OK) return fc;
   const int s = s2_resolve(NB, C, H, W, Cout, splits);
   if (s < 0) return DM_ERR_UNSUPPORTED;
-  const long long need = dm_conv3x3_s2_workspace_floats(NB, C, H, W, Cout, splits);
-  if (s > 1 && (!workspace || workspace_floats < need)) return DM_ERR_INVALID_ARG;
+  if (s > 1 && (!workspace || workspace_floats < s2_ws_floats(s, NB, H, W, Cout))) return DM_ERR_INVALID_ARG;
   S2Args a = {};
   a.x = x; a.NB = NB; a.C = C; a.H = H; a.W = W;
   a.Ho = (H + 1) / 2; a.Wo = (W + 1) / 2;
   a.wq = w_packed; a.bias = bias;
-  a.Cout = Cout; a.CoutP = dm_conv_packed_cout(Cout); a.KQ = C / 4; a.MT = s2_mt(Cout);
-  a.ntiles = (int)s2_tiles(NB, H, W); a.splits = s; a.nchunks = C / S2_CK;
+  a.Cout = Cout; a.CoutP = dm_conv_packed_cout(Cout); a.KQ = C / 4; a.MT = dm_cout_tiles(Cout);
+  a.ntiles = (int)s2_tiles(NB, H, W); a.splits = s; a.nchunks = C / DM_CONV_CK;
   a.npix = (long long)NB * a.Ho * a.Wo;
   a.flags = flags; a.out = out; a.ws = s > 1 ? workspace : nullptr;
   const hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((unsigned)((long long)a.MT * a.ntiles * s)), block(S2_NT);
+  const dim3 grid((unsigned)((long long)a.MT * a.ntiles * s)), block(DM_CONV_NT);
   if (Cout <= 64) DM_LAUNCH((conv3x3_s2_kernel<1>), grid, block, 0, st, a);
   else DM_LAUNCH((conv3x3_s2_kernel<2>), grid, block, 0, st, a);
   int rc = dm_check_launch();
   if (rc != DM_OK || s == 1) return rc;
   const long long total = (long long)NB * Cout * a.Ho * a.Wo;
-  const int blocks = (int)(total / 256 + 1 < 4096 ? total / 256 + 1 : 4096);
-  DM_LAUNCH(conv3x3_s2_reduce_kernel, dim3(blocks), dim3(256), 0, st, workspace, s, total, Cout, a.Ho * a.Wo, bias,
-            (flags & S2_RELU) ? 1 : 0, out);
+  DM_LAUNCH(conv3x3_s2_reduce_kernel, dim3(dm_grid_1d(total, 4096)), dim3(256), 0, st, workspace, s, total, Cout,
+            a.Ho * a.Wo, bias, (flags & S2_RELU) ? 1 : 0, out);
   return dm_check_launch();
 }
 
@@ -334,9 +283,8 @@ extern "C" int dm_mask_iou_input(const float* mask_pred, int n, int C, int H, in
   if (!mask_pred || !out || (C > 1 && !labels)) return DM_ERR_INVALID_ARG;
   const int Ho = H / 2, Wo = W / 2;
   const long long total = (long long)n * Ho * Wo;
-  const int blocks = (int)(total / 256 + 1 < 4096 ? total / 256 + 1 : 4096);
-  DM_LAUNCH(mask_iou_input_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, mask_pred, (long long)n, C, H, W,
-            labels, Ho, Wo, out);
+  DM_LAUNCH(mask_iou_input_kernel, dim3(dm_grid_1d(total, 4096)), dim3(256), 0, (hipStream_t)stream, mask_pred,
+            (long long)n, C, H, W, labels, Ho, Wo, out);
   return dm_check_launch();
 }
 

@@ -20,7 +20,7 @@
 // point_sample is mmcv's: grid_sample(bilinear, zeros, align_corners=False) of points * 2 - 1.  The sample below
 // repeats the fp32 operations of PyTorch's CPU grid sampler (unnormalize (g + 1) * size / 2 - 0.5, weights from the
 // floor distances, corners added nw, ne, sw, se), with every product and sum rounded on its own (no contraction).
-#include "common.h"
+#include "mfma_tile.h"
 
 namespace {
 
@@ -220,15 +220,10 @@ __global__ __launch_bounds__(GAT_NT) void point_gather_kernel(GatherArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------ point MLP
-// Workgroup: 64 points of one RoI, 256 threads = 4 waves; wave w computes output channels [64 w, 64 w + 64) of a
-// layer for the 64 points as 2 x 2 tiles of 32 x 32 (v_mfma_f32_32x32x2_f32, the D layout puts the point on the lane).
-// The activations live in the LDS as [KQ][64 points][4 channels] (KQ = (C + NC) / 4 quads, 86 KB at 336 channels):
-// a layer reads all of them, then (after a barrier) writes its F = C outputs over the first C channels; the NC coarse
-// channels stay.  The weights are dm_conv_pack_weight's 1x1 layout [KQ][CoutP][4], read straight from the L2 (1 MB
-// for three layers, shared by every workgroup): one float4 per lane feeds four MFMAs, the next chunk's float4s are in
-// flight while the current chunk's MFMAs run.
-constexpr int MLP_TP = 64;
-constexpr int MLP_NT = 256;
+// Workgroup, activation image and hidden layers are mfma_tile.h's point MLP: wave w computes output channels [64 w,
+// 64 w + 64) of a layer for the 64 points as 2 x 2 tiles of 32 x 32.  KQ = (C + NC) / 4 quads (86 KB at 336 channels);
+// a layer writes its F = C outputs over the first C channels, the NC coarse channels stay (weights: 1 MB for three
+// layers).  This kernel's own is the last layer: the label row of fc_logits as a dot product per point.
 constexpr int MLP_F = 256;
 constexpr int MLP_MAXFC = 4;
 constexpr int MLP_MAXNC = 96;
@@ -247,103 +242,51 @@ struct MlpArgs {
   int HW;
 };
 
-__global__ __launch_bounds__(MLP_NT) void point_mlp_kernel(MlpArgs a) {
+__global__ __launch_bounds__(DM_MLP_NT) void point_mlp_kernel(MlpArgs a) {
   extern __shared__ dm_f32x4 lds[];            // [KQ][64] activations, then red[4][64], then the logits row
-  float* red = reinterpret_cast<float*>(lds + a.KQ * MLP_TP);
-  float* wrow = red + 4 * MLP_TP;
+  float* red = reinterpret_cast<float*>(lds + a.KQ * DM_MLP_TP);
+  float* wrow = red + 4 * DM_MLP_TP;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hi = lane >> 5, l31 = lane & 31;
-  const int roi = blockIdx.x / a.tiles, p0 = (blockIdx.x - roi * a.tiles) * MLP_TP;
-  const int np = min(MLP_TP, a.P - p0);
+  const int roi = blockIdx.x / a.tiles, p0 = (blockIdx.x - roi * a.tiles) * DM_MLP_TP;
+  const int np = min(DM_MLP_TP, a.P - p0);
   const int CT = a.C + a.NC;
   const float* xr = a.x + (size_t)roi * CT * a.P + p0;
 
-  for (int e = tid; e < a.KQ * MLP_TP; e += MLP_NT) {
-    const int q = e / MLP_TP, p = e - q * MLP_TP;
-    dm_f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (p < np) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) v[j] = xr[(size_t)(4 * q + j) * a.P + p];
-    }
-    lds[e] = v;
-  }
+  dm_mlp_stage(lds, xr, a.KQ, a.P, np, tid);
   int lab = (int)a.labels[roi];
   lab = lab < 0 ? 0 : (lab >= a.NCL ? a.NCL - 1 : lab);
-  for (int k = tid; k < CT; k += MLP_NT) wrow[k] = a.wl[(size_t)lab * CT + k];
+  for (int k = tid; k < CT; k += DM_MLP_NT) wrow[k] = a.wl[(size_t)lab * CT + k];
   __syncthreads();
 
   const int co_w = wave * 64;
 #pragma unroll 1
   for (int L = 0; L < a.nfc; ++L) {
     dm_f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    const dm_f32x4* wq = reinterpret_cast<const dm_f32x4*>(a.w[L]) + co_w + l31;
-    dm_f32x4 av[2], an[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) av[i] = wq[(size_t)hi * a.CoutP + i * 32];
-#pragma unroll 1
-    for (int q0 = 0; q0 < a.KQ; q0 += 2) {
-      const int qn = q0 + 2 < a.KQ ? q0 + 2 : q0;
-#pragma unroll
-      for (int i = 0; i < 2; ++i) an[i] = wq[(size_t)(qn + hi) * a.CoutP + i * 32];
-      dm_f32x4 bv[2];
-#pragma unroll
-      for (int j = 0; j < 2; ++j) bv[j] = lds[(q0 + hi) * MLP_TP + j * 32 + l31];
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i][e], bv[j][e], acc[i][j], 0, 0, 0);
-#pragma unroll
-      for (int i = 0; i < 2; ++i) av[i] = an[i];
-    }
-    __syncthreads();                           // every wave has read this layer's input
-    const float* bias = a.b[L];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int co = co_w + i * 32 + 8 * g + 4 * hi;      // rows co .. co + 3 of D, quad co / 4
-        dm_f32x4 bq = {0.f, 0.f, 0.f, 0.f};
-        if (bias) bq = *reinterpret_cast<const dm_f32x4*>(bias + co);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          dm_f32x4 v;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = fmaxf(acc[i][j][4 * g + r] + bq[r], 0.f);
-          lds[(co / 4) * MLP_TP + j * 32 + l31] = v;
-        }
-      }
-    __syncthreads();
+    dm_mlp_gemm(acc, a.w[L], a.CoutP, a.KQ, lds, co_w, 0, hi, l31);
+    dm_mlp_relu_store(acc, a.b[L], lds, co_w, 0, hi, l31);
   }
 
   // the label row of fc_logits: four partial sums per point over quarters of the quads, added in order
   {
-    const int p = tid & (MLP_TP - 1), part = tid >> 6;
+    const int p = tid & (DM_MLP_TP - 1), part = tid >> 6;
     const int qper = (a.KQ + 3) / 4, qa = part * qper, qb = min(a.KQ, qa + qper);
     float s = 0.f;
     for (int q = qa; q < qb; ++q) {
-      const dm_f32x4 v = lds[q * MLP_TP + p];
+      const dm_f32x4 v = lds[q * DM_MLP_TP + p];
 #pragma unroll
       for (int j = 0; j < 4; ++j) s = fmaf(wrow[4 * q + j], v[j], s);
     }
-    red[part * MLP_TP + p] = s;
+    red[part * DM_MLP_TP + p] = s;
   }
   __syncthreads();
   if (tid < np) {
-    const float v = ((red[tid] + red[MLP_TP + tid]) + red[2 * MLP_TP + tid]) + red[3 * MLP_TP + tid] + (a.bl ? a.bl[lab] : 0.f);
+    const float v = ((red[tid] + red[DM_MLP_TP + tid]) + red[2 * DM_MLP_TP + tid]) + red[3 * DM_MLP_TP + tid] + (a.bl ? a.bl[lab] : 0.f);
     const int cell = a.idx[(size_t)roi * a.P + p0 + tid];
     if (cell >= 0 && cell < a.HW) a.refined[(size_t)roi * a.HW + cell] = v;
   }
 }
 
-size_t mlp_lds_bytes(int KQ, int CT) { return (size_t)KQ * MLP_TP * 16 + 4 * MLP_TP * 4 + (size_t)CT * 4; }
+size_t mlp_lds_bytes(int KQ, int CT) { return (size_t)KQ * DM_MLP_TP * 16 + 4 * DM_MLP_TP * 4 + (size_t)CT * 4; }
 
 // ------------------------------------------------------------------------------------------------ scatter
 __global__ void point_scatter_kernel(const float* __restrict__ vals, const int* __restrict__ idx, long long total, int P,
@@ -391,21 +334,21 @@ extern "C" int dm_point_gather_fwd(const float* feat, int B, int C, int H, int W
 extern "C" int dm_point_mlp_supported(int n, int P, int C, int NC, int F, int num_fcs, int NCL, int HW) {
   if (n < 0 || P < 1 || P > HW || C != MLP_F || F != MLP_F || NC < 8 || NC % 8 != 0 || NC > MLP_MAXNC) return 0;
   if (num_fcs < 1 || num_fcs > MLP_MAXFC || NCL < 1) return 0;
-  return (long long)n * dm_ceil_div(P, MLP_TP) <= 0x7fffffffLL ? 1 : 0;
+  return (long long)n * dm_ceil_div(P, DM_MLP_TP) <= 0x7fffffffLL ? 1 : 0;
 }
 
 extern "C" int dm_point_mlp_fwd(const float* x, int n, int P, int C, int NC, int F, int num_fcs,
                                 const float* const* w_packed, const float* const* bias, const float* w_logits,
                                 const float* b_logits, int NCL, const long long* labels, const int* idx, int flags,
                                 float* refined, int HW, dm_stream_t stream) {
-  if (flags & 16) return DM_ERR_UNSUPPORTED;    // bf16x3: exact fp32 only
-  if (flags & ~8) return DM_ERR_INVALID_ARG;    // (bit 3, the scheduling hint of dm_conv2d_fwd, is accepted and ignored)
+  const int fc = dm_flags_check(flags, 0);
+  if (fc != DM_OK) return fc;
   if (!dm_point_mlp_supported(n, P, C, NC, F, num_fcs, NCL, HW)) return DM_ERR_UNSUPPORTED;
   if (n == 0) return DM_OK;
   if (!x || !w_packed || !w_logits || !labels || !idx || !refined) return DM_ERR_INVALID_ARG;
   MlpArgs a = {};
   a.x = x; a.n = n; a.P = P; a.C = C; a.NC = NC; a.KQ = (C + NC) / 4; a.CoutP = dm_conv_packed_cout(F);
-  a.nfc = num_fcs; a.tiles = dm_ceil_div(P, MLP_TP);
+  a.nfc = num_fcs; a.tiles = dm_ceil_div(P, DM_MLP_TP);
   for (int L = 0; L < num_fcs; ++L) {
     if (!w_packed[L]) return DM_ERR_INVALID_ARG;
     a.w[L] = w_packed[L];
@@ -416,7 +359,7 @@ extern "C" int dm_point_mlp_fwd(const float* x, int n, int P, int C, int NC, int
   static bool raised[DM_MAX_DEVICES] = {false};
   const int rc = dm_ensure_lds_limit((const void*)point_mlp_kernel, lds, raised);
   if (rc != DM_OK) return rc;
-  DM_LAUNCH(point_mlp_kernel, dim3((unsigned)((long long)n * a.tiles)), dim3(MLP_NT), lds, (hipStream_t)stream, a);
+  DM_LAUNCH(point_mlp_kernel, dim3((unsigned)((long long)n * a.tiles)), dim3(DM_MLP_NT), lds, (hipStream_t)stream, a);
   return dm_check_launch();
 }
 
@@ -501,13 +444,10 @@ __global__ __launch_bounds__(GAT_NT) void point_feat_gather_kernel(FeatGatherArg
 }
 
 // ------------------------------------------------------------------------------------------------ point MLP
-// Workgroup: 64 points of one RoI, 256 threads = 4 waves.  The C output channels x 64 points of a layer are C / 32 x 2
-// tiles of 32 x 32 (v_mfma_f32_32x32x2_f32, the point on the lane of D): C = 256 -- a wave owns two channel tiles x both
-// point tiles (dm_point_mlp_fwd's split); C = 128 -- one channel tile x both point tiles; C = 64 -- one channel tile x one
-// point tile.  The activations live in the LDS as [KQ][64 points][4 channels] (KQ = (C + NC) / 4: 104 KB at C = 256,
-// NC = 160); a hidden layer's outputs replace the first C channels after a barrier, the NC coarse channels stay.
+// mfma_tile.h's point MLP again.  The C output channels x 64 points of a layer are C / 32 x 2 tiles of 32 x 32:
+// C = 256 -- a wave owns two channel tiles x both point tiles (dm_point_mlp_fwd's split); C = 128 -- one channel tile x
+// both point tiles; C = 64 -- one channel tile x one point tile.  KQ = (C + NC) / 4: 104 KB at C = 256, NC = 160.
 // fc_logits is one more layer of the same shape whose outputs (+ bias, no ReLU) go to f at the selected cells.
-// The weights are dm_conv_pack_weight's 1x1 layout [KQ][CoutP][4], read straight from the L2.
 constexpr int RMLP_MAXNC = 160;
 constexpr int RMLP_MAXFC = 4;
 
@@ -522,7 +462,7 @@ struct RefineMlpArgs {
 };
 
 template <int C>
-__global__ __launch_bounds__(MLP_NT) void point_refine_mlp_kernel(RefineMlpArgs a) {
+__global__ __launch_bounds__(DM_MLP_NT) void point_refine_mlp_kernel(RefineMlpArgs a) {
   constexpr int NT32 = C / 32 * 2;              // 32 x 32 tiles of a layer
   constexpr int TW = NT32 / 4;                  // per wave
   constexpr int NJ = TW >= 2 ? 2 : 1;           // point tiles per wave
@@ -530,20 +470,12 @@ __global__ __launch_bounds__(MLP_NT) void point_refine_mlp_kernel(RefineMlpArgs 
   static_assert(NI * NJ * 4 == NT32, "tile split");
   extern __shared__ dm_f32x4 lds[];             // [KQ][64]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hi = lane >> 5, l31 = lane & 31;
-  const int roi = blockIdx.x / a.tiles, p0 = (blockIdx.x - roi * a.tiles) * MLP_TP;
-  const int np = min(MLP_TP, a.P - p0);
+  const int roi = blockIdx.x / a.tiles, p0 = (blockIdx.x - roi * a.tiles) * DM_MLP_TP;
+  const int np = min(DM_MLP_TP, a.P - p0);
   const int CT = C + a.NC;
   const float* xr = a.x + (size_t)roi * CT * a.P + p0;
 
-  for (int e = tid; e < a.KQ * MLP_TP; e += MLP_NT) {
-    const int q = e / MLP_TP, p = e - q * MLP_TP;
-    dm_f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (p < np) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) v[j] = xr[(size_t)(4 * q + j) * a.P + p];
-    }
-    lds[e] = v;
-  }
+  dm_mlp_stage(lds, xr, a.KQ, a.P, np, tid);
   __syncthreads();
 
   const int ci0 = NJ == 2 ? wave * NI : (wave >> 1);     // first channel tile of the wave
@@ -552,53 +484,10 @@ __global__ __launch_bounds__(MLP_NT) void point_refine_mlp_kernel(RefineMlpArgs 
 #pragma unroll 1
   for (int L = 0; L <= a.nfc; ++L) {
     dm_f32x16 acc[NI][NJ];
-#pragma unroll
-    for (int i = 0; i < NI; ++i)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    const dm_f32x4* wq = reinterpret_cast<const dm_f32x4*>(a.w[L]) + co_w + l31;
-    dm_f32x4 av[NI], an[NI];
-#pragma unroll
-    for (int i = 0; i < NI; ++i) av[i] = wq[(size_t)hi * a.CoutP + i * 32];
-#pragma unroll 1
-    for (int q0 = 0; q0 < a.KQ; q0 += 2) {
-      const int qn = q0 + 2 < a.KQ ? q0 + 2 : q0;
-#pragma unroll
-      for (int i = 0; i < NI; ++i) an[i] = wq[(size_t)(qn + hi) * a.CoutP + i * 32];
-      dm_f32x4 bv[NJ];
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) bv[j] = lds[(q0 + hi) * MLP_TP + (pj0 + j) * 32 + l31];
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int i = 0; i < NI; ++i)
-#pragma unroll
-          for (int j = 0; j < NJ; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i][e], bv[j][e], acc[i][j], 0, 0, 0);
-#pragma unroll
-      for (int i = 0; i < NI; ++i) av[i] = an[i];
-    }
+    dm_mlp_gemm(acc, a.w[L], a.CoutP, a.KQ, lds, co_w, pj0, hi, l31);
     const float* bias = a.b[L];
     if (L < a.nfc) {
-      __syncthreads();                         // every wave has read this layer's input
-#pragma unroll
-      for (int i = 0; i < NI; ++i)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int co = co_w + i * 32 + 8 * g + 4 * hi;    // rows co .. co + 3 of D, quad co / 4
-          dm_f32x4 bq = {0.f, 0.f, 0.f, 0.f};
-          if (bias) bq = *reinterpret_cast<const dm_f32x4*>(bias + co);
-#pragma unroll
-          for (int j = 0; j < NJ; ++j) {
-            dm_f32x4 v;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = fmaxf(acc[i][j][4 * g + r] + bq[r], 0.f);
-            lds[(co / 4) * MLP_TP + (pj0 + j) * 32 + l31] = v;
-          }
-        }
-      __syncthreads();
+      dm_mlp_relu_store(acc, bias, lds, co_w, pj0, hi, l31);
     } else {
       // fc_logits: every output row into the stage features at the point's cell
 #pragma unroll
@@ -612,7 +501,7 @@ __global__ __launch_bounds__(MLP_NT) void point_refine_mlp_kernel(RefineMlpArgs 
         for (int i = 0; i < NI; ++i)
 #pragma unroll
           for (int g = 0; g < 4; ++g) {
-            const int co = co_w + i * 32 + 8 * g + 4 * hi;
+            const int co = co_w + i * 32 + dm_dtile_row(4 * g, hi);
 #pragma unroll
             for (int r = 0; r < 4; ++r) dst[(size_t)(co + r) * a.HW] = acc[i][j][4 * g + r] + (bias ? bias[co + r] : 0.f);
           }
@@ -621,7 +510,7 @@ __global__ __launch_bounds__(MLP_NT) void point_refine_mlp_kernel(RefineMlpArgs 
   }
 }
 
-size_t refine_mlp_lds_bytes(int C, int NC) { return (size_t)((C + NC) / 4) * MLP_TP * 16; }
+size_t refine_mlp_lds_bytes(int C, int NC) { return (size_t)((C + NC) / 4) * DM_MLP_TP * 16; }
 
 template <int C>
 int launch_refine_mlp(const RefineMlpArgs& a, dm_stream_t stream) {
@@ -629,7 +518,7 @@ int launch_refine_mlp(const RefineMlpArgs& a, dm_stream_t stream) {
   static bool raised[DM_MAX_DEVICES] = {false};
   const int rc = dm_ensure_lds_limit((const void*)point_refine_mlp_kernel<C>, (int)refine_mlp_lds_bytes(C, RMLP_MAXNC), raised);
   if (rc != DM_OK) return rc;
-  DM_LAUNCH(point_refine_mlp_kernel<C>, dim3((unsigned)((long long)a.n * a.tiles)), dim3(MLP_NT),
+  DM_LAUNCH(point_refine_mlp_kernel<C>, dim3((unsigned)((long long)a.n * a.tiles)), dim3(DM_MLP_NT),
             (int)refine_mlp_lds_bytes(C, a.NC), (hipStream_t)stream, a);
   return dm_check_launch();
 }
@@ -687,20 +576,20 @@ extern "C" int dm_point_refine_mlp_supported(int n, int P, int C, int NC, int nu
   if (n < 0 || P < 1 || P > HW || (!has_idx && P != HW)) return 0;
   if (C != 64 && C != 128 && C != 256) return 0;
   if (NC < 8 || NC > RMLP_MAXNC || (C + NC) % 8 != 0 || num_fcs < 1 || num_fcs > RMLP_MAXFC) return 0;
-  return (long long)n * dm_ceil_div(P, MLP_TP) <= 0x7fffffffLL ? 1 : 0;
+  return (long long)n * dm_ceil_div(P, DM_MLP_TP) <= 0x7fffffffLL ? 1 : 0;
 }
 
 extern "C" int dm_point_refine_mlp(const float* x, int n, int P, int C, int NC, int num_fcs, const float* const* w_packed,
                                    const float* const* bias, const int* idx, int flags, float* feat, int HW,
                                    dm_stream_t stream) {
-  if (flags & 16) return DM_ERR_UNSUPPORTED;    // bf16x3: exact fp32 only
-  if (flags & ~8) return DM_ERR_INVALID_ARG;    // (bit 3, the scheduling hint of dm_conv2d_fwd, is accepted and ignored)
+  const int fc = dm_flags_check(flags, 0);
+  if (fc != DM_OK) return fc;
   if (!dm_point_refine_mlp_supported(n, P, C, NC, num_fcs, HW, idx ? 1 : 0)) return DM_ERR_UNSUPPORTED;
   if (n == 0) return DM_OK;
   if (!x || !w_packed || !feat) return DM_ERR_INVALID_ARG;
   RefineMlpArgs a = {};
   a.x = x; a.n = n; a.P = P; a.NC = NC; a.KQ = (C + NC) / 4; a.CoutP = dm_conv_packed_cout(C);
-  a.nfc = num_fcs; a.tiles = dm_ceil_div(P, MLP_TP);
+  a.nfc = num_fcs; a.tiles = dm_ceil_div(P, DM_MLP_TP);
   for (int L = 0; L <= num_fcs; ++L) {
     if (!w_packed[L]) return DM_ERR_INVALID_ARG;
     a.w[L] = w_packed[L];

@@ -84,6 +84,23 @@ def test_conv3x3_s2_without_relu_and_bias():
     assert_close_via_f64(got, r32, r64, 'conv3x3_s2 without ReLU / bias', rel=1e-5)
 
 
+@pytest.mark.parametrize('NB,C,H,W,cout', ((3, 16, 5, 7, 33), (2, 24, 14, 13, 130)))
+def test_conv3x3_s2_is_the_subsampled_dilation_1_conv(NB, C, H, W, cout):
+    """One split of the stride-2 kernel gives the bits of the stride-1 kernel (conv3x3_dil, d = 1) at the even pixels:
+    both walk K as 8-channel chunks x taps 0 .. 8 x the same quad order (the tap loop of csrc/mfma_tile.h, which the
+    dilated kernel holds written out), and padding contributes fma(0, w, acc) in both."""
+    from dynamask_amd import ops
+    g = _g(NB + C + H + W + cout)
+    x = torch.randn(NB, C, H, W, generator=g).cuda()
+    wq = ops.pack_conv_weight((torch.randn(cout, C, 3, 3, generator=g) * (2.0 / (9 * C)) ** 0.5).cuda())
+    b = (torch.randn(cout, generator=g) * 0.1).cuda()
+    for relu in (False, True):
+        with torch.no_grad():
+            s2 = ops.conv3x3_s2(x, wq, b, cout, relu=relu, splits=1)
+            d1 = ops.conv3x3_dil(x, wq, b, cout, 1, relu=relu)
+        assert torch.equal(s2, d1[..., ::2, ::2]), f'relu={relu}'
+
+
 def test_conv3x3_s2_refusals():
     from dynamask_amd._lib import lib
     L = lib()

@@ -2,9 +2,11 @@
 usage: python tools/resource_usage.py dynamask_amd/csrc/backward.hip [name-filter] ; add --json FILE to save, --diff FILE to compare."""
 import json, os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from dynamask_amd.build import FLAGS     # the product's flags: without them the table is another build's
 
 def usage(src):
-    cmd = ['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-I' + os.path.join(ROOT, 'include'),
+    cmd = ['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', *FLAGS, '-I' + os.path.join(ROOT, 'include'),
            '-I' + os.path.join(ROOT, 'dynamask_amd', 'csrc'), '-c', src, '-o', '/dev/null', '-Rpass-analysis=kernel-resource-usage']
     err = subprocess.run(cmd, capture_output=True, text=True).stderr
     out, name = {}, None
@@ -21,7 +23,8 @@ def usage(src):
     return out
 
 if __name__ == '__main__':
-    args = [a for a in sys.argv[1:] if not a.startswith('--')]
+    # positional arguments; sys.argv[i] is the word before a (the enumeration runs one behind): an option's value is none
+    args = [a for i, a in enumerate(sys.argv[1:]) if not a.startswith('--') and sys.argv[i] not in ('--json', '--diff')]
     u = usage(args[0])
     flt = args[1] if len(args) > 1 else ''
     if '--json' in sys.argv:
