@@ -2772,3 +2772,141 @@ def global_avg_pool(x, out=None):
         assert out.shape == (N, C)
     check(lib().dm_global_avg_pool_fwd(_p(x), N, C, H * W, _p(out), _stream()), 'dm_global_avg_pool_fwd')
     return out
+
+
+# ------------------------------------------------ RPN post-processing (section K30 of the header, csrc/rpn.hip)
+RPN_SEG_WORDS = _abi.load()[1]['DM_RPN_SEG_WORDS']
+RPN_SELECT_CHUNK = _abi.load()[1]['DM_RPN_SELECT_CHUNK']
+
+
+def rpn_select_supported(num_segments, max_candidates, total_candidates=None):
+    total = max_candidates if total_candidates is None else total_candidates
+    return bool(lib().dm_rpn_select_supported(int(num_segments), int(max_candidates), int(total)))
+
+
+def rpn_decode_supported(num_segments, max_rows, num_images=1):
+    return bool(lib().dm_rpn_decode_supported(int(num_segments), int(max_rows), int(num_images)))
+
+
+def rpn_merge_supported(num_images, num_levels, max_rows, nms_post):
+    return bool(lib().dm_rpn_merge_supported(int(num_images), int(num_levels), int(max_rows), int(nms_post)))
+
+
+def _chk_seg_map(t, name, channels=None):
+    """One segment's map: a dense [C, H, W] fp32 block on the device (it may be one image of a wider NCHW tensor)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 3:
+        raise TypeError(f'{name}: a [C, H, W] float32 tensor on the device expected')
+    C, H, W = t.shape
+    if t.numel() and (t.stride(2) != 1 or t.stride(1) != W or t.stride(0) != H * W):
+        raise ValueError(f'{name}: the [C, H, W] block must be dense')
+    if channels is not None and C != channels:
+        raise ValueError(f'{name}: {channels} channels expected, got {C}')
+    return t
+
+
+class RPNSegments:
+    """The segment table of the RPN entry points: segment s = image * num_levels + level reads ``logits[s]`` [A, H, W]
+    (and ``deltas[s]`` [4 A, H, W] for ``rpn_decode``).  ``nms_pre`` <= 0 keeps every candidate.  ``strides[s]`` =
+    (stride_x, stride_y), ``base_rows[s]`` = the level's first row of the base-anchor table, ``images[s]`` = its image.
+    Host lists: ``sizes`` (A H W), ``rows`` (K), ``row0``; ``tab`` is the device table (uploaded without a host wait).
+    The tensors are kept alive here: the table holds their addresses."""
+
+    def __init__(self, logits, nms_pre, deltas=None, strides=None, base_rows=None, images=None, num_levels=None):
+        S = len(logits)
+        self.logits = [_chk_seg_map(t, 'logits') for t in logits]
+        self.deltas = None if deltas is None else [_chk_seg_map(d, 'deltas', 4 * t.shape[0]) for d, t in zip(deltas, logits)]
+        if deltas is not None and (len(deltas) != S or any(d.shape[1:] != t.shape[1:] for d, t in zip(deltas, logits))):
+            raise ValueError('deltas: one [4 A, H, W] map per segment expected')
+        self.nms_pre = int(nms_pre)
+        self.num_levels = int(num_levels) if num_levels is not None else max(S, 1)
+        self.sizes = [int(t.numel()) for t in self.logits]
+        self.rows = [min(self.nms_pre, n) if self.nms_pre > 0 else n for n in self.sizes]
+        self.row0, self.key_off = [], []
+        r = k = 0
+        for n, m in zip(self.sizes, self.rows):
+            self.row0.append(r)
+            self.key_off.append(k)
+            r += m
+            k += n
+        self.total_rows, self.total_candidates = r, k
+        self.max_candidates = max(self.sizes, default=0)
+        self.max_rows = max(self.rows, default=0)
+        tab = []
+        for s, t in enumerate(self.logits):
+            A, H, W = t.shape
+            sx, sy = strides[s] if strides is not None else (0, 0)
+            tab.append([t.data_ptr(), self.deltas[s].data_ptr() if self.deltas is not None else 0, A, H, W, self.rows[s],
+                        self.key_off[s], self.row0[s], int(base_rows[s]) if base_rows is not None else 0, int(sx), int(sy),
+                        int(images[s]) if images is not None else s // self.num_levels])
+        self.device = self.logits[0].device if S else None
+        self.tab = _upload(tab, torch.int64, self.device) if S else None
+
+    def __len__(self):
+        return len(self.logits)
+
+
+def rpn_select(segs):
+    """Per segment, its ``rows`` candidates of largest ``sigmoid(logit)`` in descending order, the lower candidate
+    index first among equal scores (dm_rpn_select): (idx int32 [total rows], score [total rows]); segment s at
+    ``row0[s] : row0[s] + rows[s]``.  Candidate i = (h * W + w) * A + a."""
+    S = len(segs)
+    dev = segs.device if S else 'cuda'
+    idx = torch.empty((segs.total_rows,), device=dev, dtype=torch.int32)
+    score = torch.empty((segs.total_rows,), device=dev, dtype=torch.float32)
+    if S == 0 or segs.total_candidates == 0:
+        return idx, score
+    nbytes = int(lib().dm_rpn_select_workspace_bytes(S, segs.max_candidates, segs.total_candidates, segs.total_rows))
+    if nbytes < 0:
+        check(-3, 'dm_rpn_select')
+    ws = torch.empty(((nbytes + 7) // 8,), device=dev, dtype=torch.int64)
+    check(lib().dm_rpn_select(_p(segs.tab), S, segs.max_candidates, segs.total_candidates, segs.total_rows, segs.nms_pre,
+                              _p(ws), ws.numel() * 8, _p(idx), _p(score), _stream()), 'dm_rpn_select')
+    return idx, score
+
+
+def rpn_decode(segs, idx, base_anchors, img_tab, means=(0., 0., 0., 0.), stds=(1., 1., 1., 1.), wh_ratio_clip=16 / 1000):
+    """The boxes [total rows, 4] of the candidates ``idx`` (``rpn_select``'s): anchor = ``base_anchors[base_row + a]`` +
+    the grid shift, decoded by its four deltas and clipped to ``img_tab[image]`` (``image_shape_table``): the bits of
+    ``bbox_decode`` on the materialised anchors (dm_rpn_decode)."""
+    if segs.deltas is None:
+        raise ValueError('rpn_decode: the segments carry no deltas')
+    _chk(idx, 'idx', torch.int32)
+    _chk(base_anchors, 'base_anchors')
+    _chk(img_tab, 'img_tab')
+    if idx.shape != (segs.total_rows,):
+        raise ValueError(f'idx: [{segs.total_rows}] expected')
+    if base_anchors.dim() != 2 or base_anchors.shape[1] != 4:
+        raise ValueError('base_anchors: [R, 4] expected')
+    if img_tab.dim() != 2 or img_tab.shape[1] != 2 or img_tab.shape[0] < 1:
+        raise ValueError('img_tab: [B, 2] expected')
+    boxes = torch.empty((segs.total_rows, 4), device=idx.device, dtype=torch.float32)
+    if len(segs) == 0 or segs.total_rows == 0:
+        return boxes
+    check(lib().dm_rpn_decode(_p(segs.tab), len(segs), segs.max_rows, _p(idx), _p(base_anchors), _p(img_tab),
+                              int(img_tab.shape[0]), _float_array(means), _float_array(stds), float(wh_ratio_clip),
+                              _p(boxes), _stream()), 'dm_rpn_decode')
+    return boxes
+
+
+def rpn_merge(segs, keep, kept, boxes, score, nms_post):
+    """Per image, the first ``nms_post`` kept rows of its levels in descending score order (equal scores: the lower
+    level, then the earlier rank): (out [B, nms_post, 5] = (box, score), counts int32 [B]); rows past ``counts[b]`` are
+    not written (dm_rpn_merge).  ``keep`` / ``kept`` as ``nms_segmented`` returns them for ``segs.rows``."""
+    S, L = len(segs), segs.num_levels
+    if S % L:
+        raise ValueError(f'rpn_merge: {S} segments are no multiple of {L} levels')
+    B = S // L
+    _chk(keep, 'keep', torch.int32)
+    _chk(kept, 'kept', torch.int32)
+    _chk(boxes, 'boxes')
+    _chk(score, 'score')
+    if kept.shape != (S,) or keep.shape != (segs.total_rows,) or boxes.shape != (segs.total_rows, 4) or \
+            score.shape != (segs.total_rows,):
+        raise ValueError('rpn_merge: keep / boxes / score of the segments\' rows and one kept count per segment expected')
+    out = torch.empty((B, int(nms_post), 5), device=kept.device, dtype=torch.float32)
+    counts = torch.empty((B,), device=kept.device, dtype=torch.int32)
+    if B == 0:
+        return out, counts
+    check(lib().dm_rpn_merge(_p(segs.tab), B, L, segs.max_rows, _p(keep), _p(kept), _p(boxes), _p(score), int(nms_post),
+                             _p(out), _p(counts), _stream()), 'dm_rpn_merge')
+    return out, counts

@@ -74,6 +74,7 @@ HEADS = Registry('head')
 LOSSES = Registry('loss')
 ROI_LAYERS = Registry('roi_layer')       # stands in for getattr(mmcv.ops, type) (base_roi_extractor.py:49-55)
 UPSAMPLE_LAYERS = Registry('upsample')   # stands in for mmcv's build_upsample_layer
+ANCHOR_GENERATORS = Registry('anchor generator')   # mmdet/core/anchor/builder.py
 
 
 def build(cfg, registry, default_args=None):
@@ -92,6 +93,10 @@ def build_head(cfg):
 
 def build_loss(cfg):
     return build(cfg, LOSSES)
+
+
+def build_anchor_generator(cfg, default_args=None):
+    return build_from_cfg(cfg, ANCHOR_GENERATORS, default_args)
 
 
 class ConfigDict(dict):

@@ -1203,6 +1203,70 @@ int dm_roi_align_strided_fwd(const float* const* feats, const int* H, const int*
                              int num_levels, int B, int C, const float* rois, int N, int P, int sampling_ratio,
                              float finest_scale, int bin_step, float* out, int32_t* levels_out, dm_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * K30  RPN inference: the post-processing of RPNHead.get_bboxes (mmdet/models/dense_heads/rpn_head.py:79-168,
+ *      anchor_head.py:500-576), csrc/rpn.hip.  The head's convolutions are dm_conv2d_fwd launches, the suppression
+ *      dm_nms_mask_segmented + dm_nms_reduce_segmented; these entry points are what lies between and after.  Exact
+ *      fp32, integer arithmetic only after the scores, no atomics on floats: the same bits on every run.
+ *
+ * A SEGMENT is one (image, level).  All three entry points read one device table seg_tab [S][DM_RPN_SEG_WORDS] of 64-bit
+ * words, segment s = image * L + level:
+ *    0 logits   address of the segment's [A, H, W] logits (dense NCHW block), as rpn_cls writes them
+ *    1 deltas   address of its [4 A, H, W] deltas, as rpn_reg writes them
+ *    2 A  3 H  4 W
+ *    5 rows     K = min(nms_pre, A H W), or A H W when nms_pre <= 0: the segment's rows of idx / score / boxes
+ *    6 key_off  the sum of A H W over the segments before it
+ *    7 row0     the sum of `rows` over the segments before it
+ *    8 base_row the level's first row in base_anchors   9 stride_x   10 stride_y   11 image
+ * Candidate i = (h * W + w) * A + a is the reference's permute(1, 2, 0).reshape(-1) order.
+ *
+ * dm_rpn_select: per segment, the K candidates of largest key in descending key order, the lower i first among equal
+ * keys; key = 1 / (1 + expf(-logit)), the expression of dm_sigmoid_fwd (saturated logits tie as they do there; a NaN
+ * sorts first).  idx[row0 + r] = i and score[row0 + r] = key of rank r: bit for bit
+ * torch.sort(sigmoid(permuted logits), descending=True, stable=True) cut at K.  A segment is cut into chunks of
+ * DM_RPN_SELECT_CHUNK candidates, one workgroup each; the last pass ranks the K survivors by counting (K^2 / 256
+ * comparisons per workgroup of 256 survivors).  workspace: dm_rpn_select_workspace_bytes bytes, 8-byte aligned,
+ * contents undefined before and after.  max_candidates / total_candidates: the largest and the sum of A H W;
+ * total_rows: the sum of `rows`.
+ * dm_rpn_select_supported: 1 exactly when 0 <= num_segments <= 65535, 0 <= max_candidates <= 2^20 and
+ * 0 <= total_candidates <= num_segments * max_candidates; else DM_ERR_UNSUPPORTED.  No segment or no candidate
+ * enqueues nothing; an empty segment among others enqueues nothing for itself.
+ *
+ * dm_rpn_decode: boxes[row0 + r] = delta2bbox(anchor, deltas) clipped to the image, for every row r < rows of every
+ * segment: anchor = base_anchors[base_row + a] + (w stride_x, h stride_y, w stride_x, h stride_y) (the integer product
+ * converted to fp32, one fp32 add per coordinate: single_level_grid_anchors), deltas = channels 4a .. 4a + 3 at (h, w),
+ * i = idx[row0 + r]; the device function of dm_bbox_decode with the coder's means / stds / wh_ratio_clip, clipped to
+ * img_shapes[image] = (h, w) when w > 0: bit for bit dm_bbox_decode (class agnostic, no scores, scale 1) on the
+ * materialised anchors and gathered deltas.  An idx outside [0, A H W) gives a zero box.
+ * dm_rpn_decode_supported: 1 exactly when 0 <= num_segments <= 65535, 0 <= max_rows <= 2^20 and num_images >= 1.
+ * max_rows: the largest `rows`.  No segment or no row enqueues nothing.
+ *
+ * dm_rpn_merge: per image, the first nms_post of the union of its L kept lists in descending score order; equal scores:
+ * the lower level first, then the earlier rank (a NaN first; -0 == +0): bit for bit the concatenation of the kept rows
+ * and a stable descending sort cut at nms_post.  keep / kept as dm_nms_reduce_segmented leaves them for the same
+ * segments (keep[row0 + k] = the k-th kept row within the segment's rows, kept[s] their number); boxes [total rows, 4],
+ * score [total rows].  out [B, nms_post, 5] = (box, score), rows past counts[b] untouched; counts[b] =
+ * min(kept of the image, nms_post).
+ * dm_rpn_merge_supported: 1 exactly when 0 <= num_images <= 65535, 1 <= num_levels <= 64, 0 <= max_rows <= 2^20 and
+ * nms_post >= 1.  num_images == 0 enqueues nothing.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define DM_RPN_SEG_WORDS 12
+#define DM_RPN_SELECT_CHUNK 4096
+int dm_rpn_select_supported(int num_segments, int max_candidates, long long total_candidates);
+long long dm_rpn_select_workspace_bytes(int num_segments, int max_candidates, long long total_candidates,
+                                        long long total_rows);
+int dm_rpn_select(const long long* seg_tab, int num_segments, int max_candidates, long long total_candidates,
+                  long long total_rows, int nms_pre, void* workspace, long long workspace_bytes, int32_t* idx,
+                  float* score, dm_stream_t stream);
+int dm_rpn_decode_supported(int num_segments, int max_rows, int num_images);
+int dm_rpn_decode(const long long* seg_tab, int num_segments, int max_rows, const int32_t* idx,
+                  const float* base_anchors, const float* img_shapes, int num_images, const float* means,
+                  const float* stds, float wh_ratio_clip, float* boxes, dm_stream_t stream);
+int dm_rpn_merge_supported(int num_images, int num_levels, int max_rows, int nms_post);
+int dm_rpn_merge(const long long* seg_tab, int num_images, int num_levels, int max_rows, const int32_t* keep,
+                 const int32_t* kept, const float* boxes, const float* score, int nms_post, float* out, int32_t* counts,
+                 dm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
