@@ -581,9 +581,15 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3_narrow_kernel(WgradNarrowA
   }
 }
 
+// ---- host side of the weight gradient: validate, route, emit ------------------------------------------------------------
+// wgrad_route decides everything about the launches of a call from numbers alone (no pointer, no HIP call but
+// dm_num_cus()); wgrad_emit enqueues exactly what the route says; dm_conv2d_wgrad_plan reports the same value.
+
+enum { WG_GEMM = 0, WG_NARROW = 1, WG_REDUCE = 2 };      // WgradLaunch::kernel, as the header numbers them
+enum { WG_ATOMICS = 0, WG_SLAB = 1, WG_FX = 2 };         // accumulation (asked for: WgradCall::mode, taken: WgradLaunch::accum)
+
 static unsigned dm_magic(unsigned d) { return (unsigned)((0x100000000ULL + d - 1) / d); }
 
-// returns DM_OK after launching, or 1 when the shape is not this kernel's
 static int wgrad_target_wgs() {
   // split-K until the launch is one round of workgroups (two per CU): every further split adds an epilogue
   // (2048 workgroups: 256->256 1x1 at 14x14 0.140 ms, 512: 0.091 ms; the 2304-row DCN GEMMs 0.63 -> 0.60 ms)
@@ -591,116 +597,165 @@ static int wgrad_target_wgs() {
   return wgs_env > 0 ? wgs_env : 2 * dm_num_cus();
 }
 
-static void launch_slab_reduce(const WgradArgs& a, int slabs, int splits, int Jtot, hipStream_t st) {
-  const long long total = (long long)a.Cout * ((Jtot + 3) / 4);                      // quads of outputs
-  const int P = slabs <= 8 ? 1 : (slabs <= 64 ? 4 : (slabs <= 256 ? 16 : 64));      // 680 slabs of a 64 x 64 tile: 64 partitions
-  const long long nblk = (total + 256 / P - 1) / (256 / P) + (a.db ? (a.Cout + 31) / 32 : 0);       // + the bias rows' workgroups
-  const float* sdb = a.db ? a.slab_db : nullptr;
-  if (P == 1)
-    DM_LAUNCH((wgrad_slab_reduce_kernel<1>), dim3((unsigned)nblk), dim3(256), 0, st, a.slab, slabs, a.slab_stride, a.slab_ld, a.Cout, Jtot,
-              a.dw, a.ldw, a.coloff, sdb, splits, a.slab_rows, a.db);
-  else if (P == 4)
-    DM_LAUNCH((wgrad_slab_reduce_kernel<4>), dim3((unsigned)nblk), dim3(256), 0, st, a.slab, slabs, a.slab_stride, a.slab_ld, a.Cout, Jtot,
-              a.dw, a.ldw, a.coloff, sdb, splits, a.slab_rows, a.db);
-  else if (P == 16)
-    DM_LAUNCH((wgrad_slab_reduce_kernel<16>), dim3((unsigned)nblk), dim3(256), 0, st, a.slab, slabs, a.slab_stride, a.slab_ld, a.Cout, Jtot,
-              a.dw, a.ldw, a.coloff, sdb, splits, a.slab_rows, a.db);
-  else
-    DM_LAUNCH((wgrad_slab_reduce_kernel<64>), dim3((unsigned)nblk), dim3(256), 0, st, a.slab, slabs, a.slab_stride, a.slab_ld, a.Cout, Jtot,
-              a.dw, a.ldw, a.coloff, sdb, splits, a.slab_rows, a.db);
-}
+struct WgradCall {          // what a route depends on: the call's numbers, and facts in place of its pointers
+  long long dy_bs, x_bs;
+  int Cout, Cs, NB, H, W, ksize, has_bias, mode;
+  long long scratch_floats;                    // the caller's scratch (mode WG_SLAB)
+  int io_aligned8, scratch_aligned16;          // dy and x 8-byte aligned; the scratch 16-byte (the reduce loads 16 bytes)
+  int target;                                  // wgrad_target_wgs()
+};
 
-static int launch_wgrad3_narrow(const WgradArgs& g, hipStream_t st) {
-  if (g.Cout > 36 || (g.W & 1) || g.W < 8 || g.H < 1) return 1;
-  if (((uintptr_t)g.dy | (uintptr_t)g.x) & 7u) return 1;
-  if ((g.dy_bs | g.x_bs) & 1LL) return 1;
-  const bool tail = g.Cout > 32;
-  const int MR = tail ? 36 : 32, Wp = g.W + 1;
-  const size_t budget = 78 * 1024;
-  auto bytes_for = [&](int R, int* PL, int* LDA) {
-    *PL = ((R + 2) * Wp + 1) | 1;
-    *LDA = (R * g.W) | 1;
-    return sizeof(float) * ((size_t)32 * *PL + (size_t)MR * *LDA);
-  };
-  int PL = 0, LDA = 0, Rmax = 0;
-  for (int R = min(g.H, 64); R >= 1; --R)
-    if (bytes_for(R, &PL, &LDA) <= budget) { Rmax = R; break; }
-  if (Rmax < 1) return 1;
-  const int nb = dm_ceil_div(g.H, Rmax);
-  const int R = dm_ceil_div(g.H, nb);
-  size_t bytes = bytes_for(R, &PL, &LDA);
-  bytes = max(bytes, sizeof(float) * (size_t)9 * MR * 32);                   // the epilogue's reduction buffer
-  if ((long long)32 * (R + 2) * (g.W / 2) >= 65536 || (long long)g.Cout * R * (g.W / 2) >= 65536) return 1;   // magic-division range
-  WgradNarrowArgs a;
-  a.dy = g.dy; a.dy_bs = g.dy_bs; a.x = g.x; a.x_bs = g.x_bs; a.Cout = g.Cout; a.Cs = g.Cs; a.NB = g.NB; a.H = g.H; a.W = g.W;
-  a.HW = g.HW; a.dw = g.dw; a.ldw = g.ldw; a.coloff = g.coloff; a.fx = g.fx; a.db = g.db;
-  a.R = R; a.Wp = Wp; a.PL = PL; a.LDA = LDA; a.bands = nb; a.units = g.NB * nb; a.groups = dm_ceil_div(g.Cs, 32);
-  a.magic_w2 = dm_magic(g.W / 2); a.magic_rr = dm_magic(R + 2); a.magic_band = dm_magic(R * (g.W / 2));
-  const int target = wgrad_target_wgs();
-  const int nsplit = max(1, min(a.units, target / a.groups));
-  a.units_per_split = dm_ceil_div(a.units, nsplit);
-  const int splits = dm_ceil_div(a.units, a.units_per_split);
-  WgradArgs red = g;
-  if (g.scratch && !g.fx && (((uintptr_t)g.scratch) & 15) == 0) {      // (the reduce reads the slabs by 16-byte loads)
-    const int ld = a.groups * 32 * 9;
-    const long long stride = (long long)g.Cout * ld, need = (long long)splits * stride + (long long)splits * MR;
-    if (need <= g.scratch_floats) {
-      a.slab = g.scratch; a.slab_db = g.scratch + (long long)splits * stride;
-      a.slab_stride = stride; a.slab_ld = ld; a.slab_rows = MR;
-      red.slab = a.slab; red.slab_db = a.slab_db; red.slab_stride = stride; red.slab_ld = ld; red.slab_rows = MR;
-    }
-  }
-  static bool attr_t[DM_MAX_DEVICES] = {false}, attr_n[DM_MAX_DEVICES] = {false};
-  if (tail) {
-    if (dm_ensure_lds_limit(reinterpret_cast<const void*>(&conv_wgrad3_narrow_kernel<true>), 80 * 1024, attr_t) != DM_OK) return DM_ERR_LAUNCH;
-    DM_LAUNCH((conv_wgrad3_narrow_kernel<true>), dim3((unsigned)(a.groups * splits)), dim3(256), bytes, st, a);
-  } else {
-    if (dm_ensure_lds_limit(reinterpret_cast<const void*>(&conv_wgrad3_narrow_kernel<false>), 80 * 1024, attr_n) != DM_OK) return DM_ERR_LAUNCH;
-    DM_LAUNCH((conv_wgrad3_narrow_kernel<false>), dim3((unsigned)(a.groups * splits)), dim3(256), bytes, st, a);
-  }
-  if (a.slab) launch_slab_reduce(red, splits, splits, g.Cs * 9, st);
-  return DM_OK;
-}
+// The builds of conv_wgrad_kernel: a TM x TN = 64 WGM x 64 WGN tile, WGK waves along the K chunk.  Widest tile first, a
+// TAIL build in front of its twin (wgrad_build takes the first of equal cost).
+struct WgradBuild { int KS, WGM, WGN, WGK, TAIL; void (*fn)(WgradArgs); };
+#define WG_BUILD(KS, M, N, K, T) {KS, M, N, K, T, conv_wgrad_kernel<KS, M, N, K, T != 0>}
+#define WG_BUILDS(KS) WG_BUILD(KS, 1, 4, 1, 1), WG_BUILD(KS, 1, 4, 1, 0), WG_BUILD(KS, 1, 2, 2, 1), WG_BUILD(KS, 1, 2, 2, 0), \
+                      WG_BUILD(KS, 1, 1, 4, 0), WG_BUILD(KS, 2, 2, 1, 0), WG_BUILD(KS, 2, 1, 2, 0)
+static const WgradBuild WGRAD_BUILDS[] = {WG_BUILDS(1), WG_BUILDS(3)};
 
-template <int KS>
-void launch_wgrad(WgradArgs a, hipStream_t st) {
-  const int J = a.Cs * KS * KS;
-  const int TM = a.Cout <= 64 ? 64 : 128;
-  // candidate column-tile widths; cost = padded columns x (1 + 32/TN) (A re-load share)
-  const int cands[3] = {256, 128, 64};
-  int TN = 64;
-  double best = 1e30;
-  for (int c = 0; c < 3; ++c) {
-    const int tn = cands[c];
-    if (TM == 128 && tn == 256) continue;
+// TM = 64 up to 64 couts, else 128; of the column-tile widths that TM has, the one of least cost = padded columns x
+// (1 + 32/TN) (A re-load share); 33 .. 36 couts (the DCN offset convs) take the TAIL build where the width has one
+static const WgradBuild& wgrad_build(int ksize, int Cout, int J) {
+  const int WGM = Cout <= 64 ? 1 : 2;
+  const bool tail = Cout > 32 && Cout <= 36;
+  const WgradBuild* best = nullptr;
+  double best_cost = 1e30;
+  for (const WgradBuild& b : WGRAD_BUILDS) {
+    if (b.KS != ksize || b.WGM != WGM || (b.TAIL && !tail)) continue;
+    const int tn = 64 * b.WGN;
     const double cost = (double)dm_ceil_div(J, tn) * tn * (1.0 + 32.0 / tn);
-    if (cost < best) { best = cost; TN = tn; }
+    if (cost < best_cost) { best_cost = cost; best = &b; }
   }
-  a.MT = dm_ceil_div(a.Cout, TM);
-  a.JT = dm_ceil_div(J, TN);
-  const int chunks = dm_ceil_div(a.Q, 32);
-  const int target_wgs = wgrad_target_wgs();
-  int nsplit = max(1, min(chunks, target_wgs / max(1, a.MT * a.JT)));
-  a.chunks_per_split = dm_ceil_div(chunks, nsplit);
-  a.nsplit = dm_ceil_div(chunks, a.chunks_per_split);
-  const dim3 grid((unsigned)(a.MT * a.JT * a.nsplit));
-  const int WGK = (TM == 128 && TN == 128) ? 1 : (TM == 128) ? 2 : (TN == 256) ? 1 : (TN == 128) ? 2 : 4;
-  if (a.scratch && !a.fx && (((uintptr_t)a.scratch) & 15) == 0) {      // (the reduce reads the slabs by 16-byte loads)
-    const int rows = a.MT * TM, ld = a.JT * TN;
-    const long long stride = (long long)rows * ld, need = (long long)a.nsplit * WGK * stride + (long long)a.nsplit * rows;
-    if (need <= a.scratch_floats) {
-      a.slab = a.scratch; a.slab_db = a.scratch + (long long)a.nsplit * WGK * stride;
-      a.slab_stride = stride; a.slab_ld = ld; a.slab_rows = rows;
-    }
+  return *best;
+}
+
+// One launch: the ints of dm_conv2d_wgrad_plan's record, in its order
+struct WgradLaunch {
+  int kernel, p[5], grid, threads, lds_bytes, MT, JT, splits, per_split, slabs, slab_ld, slab_rows, slab_stride, accum;
+};
+
+struct WgradRoute {
+  int rc = DM_OK, count = 0;           // launches: the GEMM or the narrow kernel, then the slab reduce where slabs were carved
+  WgradLaunch launch[DM_WGRAD_PLAN_MAX_LAUNCHES];
+  const WgradBuild* build = nullptr;   // launch[0] is WG_GEMM: its build
+  int R = 0, PL = 0, LDA = 0, bands = 0;      // launch[0] is WG_NARROW: rows per band, x plane / dy row strides in LDS, bands per image
+  long long slab_stride = 0;           // floats per slab (the record's int saturates)
+};
+
+// Is the call conv_wgrad3_narrow_kernel's?  Then r has its band geometry, and lds_bytes what a workgroup needs.
+static bool wgrad_narrow(const WgradCall& c, WgradRoute& r, int& lds_bytes) {
+  if (c.ksize != 3 || c.Cout > 36 || (c.W & 1) || c.W < 8) return false;
+  if (!c.io_aligned8 || ((c.dy_bs | c.x_bs) & 1LL)) return false;       // pixel pairs of dy and x by 8-byte loads
+  const int MR = c.Cout > 32 ? 36 : 32, Wp = c.W + 1;
+  auto bytes_for = [&](int R) {
+    r.PL = ((R + 2) * Wp + 1) | 1;
+    r.LDA = (R * c.W) | 1;
+    return sizeof(float) * ((size_t)32 * r.PL + (size_t)MR * r.LDA);
+  };
+  int Rmax = min(c.H, 64);
+  while (Rmax >= 1 && bytes_for(Rmax) > 78 * 1024) --Rmax;
+  if (Rmax < 1) return false;                                           // not even one row fits
+  r.bands = dm_ceil_div(c.H, Rmax);
+  r.R = dm_ceil_div(c.H, r.bands);
+  lds_bytes = (int)max(bytes_for(r.R), sizeof(float) * (size_t)9 * MR * 32);                  // (the epilogue's reduction buffer)
+  // magic-division range (nothing the 78 KB leave room for comes near it: 32 (R + 2) (W + 1) floats fit)
+  return (long long)32 * (r.R + 2) * (c.W / 2) < 65536 && (long long)c.Cout * r.R * (c.W / 2) < 65536;
+}
+
+// The one place that decides "slab or atomics": `slabs` partial tiles of tile_rows x ld floats, then `splits` bias rows of
+// bias_rows floats, carved from the caller's scratch in that order.  Not asked for, not 16-byte aligned or too small: no
+// slabs, and the launch accumulates as the call otherwise would (float atomics, or fixed point in mode WG_FX).
+static void wgrad_carve_slabs(const WgradCall& c, WgradRoute& r, int slabs, int tile_rows, int ld, int bias_rows) {
+  WgradLaunch& l = r.launch[0];
+  const long long stride = (long long)tile_rows * ld;
+  l.accum = c.mode == WG_FX ? WG_FX : WG_ATOMICS;                      // (the slab fields of l: zeros)
+  if (c.mode != WG_SLAB || !c.scratch_aligned16 || slabs * stride + (long long)l.splits * bias_rows > c.scratch_floats) return;
+  l.slabs = slabs; l.slab_ld = ld; l.slab_rows = bias_rows;
+  l.slab_stride = (int)min(stride, (long long)INT_MAX);
+  l.accum = WG_SLAB;
+  r.slab_stride = stride;
+}
+
+static WgradRoute wgrad_route(const WgradCall& c) {
+  WgradRoute r;
+  if (c.Cout <= 0 || c.Cs <= 0 || c.NB <= 0 || c.H <= 0 || c.W <= 0 || (c.ksize != 1 && c.ksize != 3) ||
+      (long long)c.NB * c.H * c.W > 0x7fffffffLL || c.mode < WG_ATOMICS || c.mode > WG_FX ||
+      (c.mode == WG_SLAB && c.scratch_floats <= 0)) {
+    r.rc = DM_ERR_INVALID_ARG;
+    return r;
   }
-  if (TM == 128 && TN == 128) DM_LAUNCH((conv_wgrad_kernel<KS, 2, 2, 1>), grid, dim3(256), 0, st, a);
-  else if (TM == 128) DM_LAUNCH((conv_wgrad_kernel<KS, 2, 1, 2>), grid, dim3(256), 0, st, a);
-  else if (TN == 256 && a.Cout > 32 && a.Cout <= 36) DM_LAUNCH((conv_wgrad_kernel<KS, 1, 4, 1, true>), grid, dim3(256), 0, st, a);
-  else if (TN == 128 && a.Cout > 32 && a.Cout <= 36) DM_LAUNCH((conv_wgrad_kernel<KS, 1, 2, 2, true>), grid, dim3(256), 0, st, a);
-  else if (TN == 256) DM_LAUNCH((conv_wgrad_kernel<KS, 1, 4, 1>), grid, dim3(256), 0, st, a);
-  else if (TN == 128) DM_LAUNCH((conv_wgrad_kernel<KS, 1, 2, 2>), grid, dim3(256), 0, st, a);
-  else DM_LAUNCH((conv_wgrad_kernel<KS, 1, 1, 4>), grid, dim3(256), 0, st, a);
-  if (a.slab) launch_slab_reduce(a, a.nsplit * WGK, a.nsplit, J, st);
+  WgradLaunch& l = r.launch[0];
+  const int J = c.Cs * c.ksize * c.ksize;
+  int lds_bytes = 0;
+  r.count = 1;
+  if (wgrad_narrow(c, r, lds_bytes)) {
+    // a workgroup owns 32 input channels and walks (image, row band) units; the units are split until the launch is one round
+    const int tail = c.Cout > 32, groups = dm_ceil_div(c.Cs, 32), units = c.NB * r.bands;
+    const int per = dm_ceil_div(units, max(1, min(units, c.target / groups)));
+    const int splits = dm_ceil_div(units, per);
+    l = {WG_NARROW, {3, 0, 0, 0, tail}, groups * splits, 256, lds_bytes, 1, groups, splits, per};
+    wgrad_carve_slabs(c, r, splits, c.Cout, groups * 32 * 9, tail ? 36 : 32);
+  } else {
+    // the GEMM: cout tiles x column tiles, the chunks of 32 pixels split until the launch is one round
+    const WgradBuild& b = wgrad_build(c.ksize, c.Cout, J);
+    const int TM = 64 * b.WGM, TN = 64 * b.WGN, MT = dm_ceil_div(c.Cout, TM), JT = dm_ceil_div(J, TN);
+    const int chunks = dm_ceil_div((long long)c.NB * c.H * c.W, 32);
+    const int per = dm_ceil_div(chunks, max(1, min(chunks, c.target / max(1, MT * JT))));
+    const int splits = dm_ceil_div(chunks, per);
+    r.build = &b;
+    l = {WG_GEMM, {b.KS, b.WGM, b.WGN, b.WGK, b.TAIL}, MT * JT * splits, 256, 0, MT, JT, splits, per};
+    wgrad_carve_slabs(c, r, splits * b.WGK, MT * TM, JT * TN, MT * TM);        // (every K-wave of a split has its slab)
+  }
+  if (l.accum == WG_SLAB) {
+    // wgrad_slab_reduce_kernel<P>: 256 / P quads of outputs per workgroup, + the bias rows' workgroups (32 channels each)
+    const int P = l.slabs <= 8 ? 1 : (l.slabs <= 64 ? 4 : (l.slabs <= 256 ? 16 : 64));      // 680 slabs of a 64 x 64 tile: 64 partitions
+    const long long quads = (long long)c.Cout * ((J + 3) / 4);
+    const long long nblk = (quads + 256 / P - 1) / (256 / P) + (c.has_bias ? (c.Cout + 31) / 32 : 0);
+    r.launch[r.count++] = {WG_REDUCE, {P, 0, 0, 0, 0}, (int)nblk, 256, 0, 0, 0, l.splits, 0,
+                           l.slabs, l.slab_ld, l.slab_rows, l.slab_stride, WG_SLAB};
+  }
+  return r;
+}
+
+// The one place a weight-gradient kernel is enqueued: the launches of route r.  g: the call's pointers and numbers.
+static int wgrad_emit(const WgradRoute& r, WgradArgs g, hipStream_t st) {
+  const WgradLaunch& l = r.launch[0];
+  const dim3 grid((unsigned)l.grid), block((unsigned)l.threads);
+  g.fx = l.accum == WG_FX;
+  if (l.accum == WG_SLAB) {
+    g.slab = g.scratch; g.slab_db = g.scratch + l.slabs * r.slab_stride;
+    g.slab_stride = r.slab_stride; g.slab_ld = l.slab_ld; g.slab_rows = l.slab_rows;
+  }
+  if (l.kernel == WG_NARROW) {
+    WgradNarrowArgs a;
+    a.dy = g.dy; a.dy_bs = g.dy_bs; a.x = g.x; a.x_bs = g.x_bs; a.Cout = g.Cout; a.Cs = g.Cs; a.NB = g.NB; a.H = g.H; a.W = g.W;
+    a.HW = g.HW; a.dw = g.dw; a.ldw = g.ldw; a.coloff = g.coloff; a.fx = g.fx; a.db = g.db;
+    a.R = r.R; a.Wp = g.W + 1; a.PL = r.PL; a.LDA = r.LDA; a.bands = r.bands; a.units = g.NB * r.bands;
+    a.groups = l.JT; a.units_per_split = l.per_split;
+    a.magic_w2 = dm_magic(g.W / 2); a.magic_rr = dm_magic(r.R + 2); a.magic_band = dm_magic(r.R * (g.W / 2));
+    a.slab = g.slab; a.slab_db = g.slab_db; a.slab_stride = g.slab_stride; a.slab_ld = g.slab_ld; a.slab_rows = g.slab_rows;
+    const int tail = l.p[4];
+    void (*fn)(WgradNarrowArgs) = tail ? conv_wgrad3_narrow_kernel<true> : conv_wgrad3_narrow_kernel<false>;
+    static bool raised[2][DM_MAX_DEVICES] = {{false}};
+    if (dm_ensure_lds_limit(reinterpret_cast<const void*>(fn), 80 * 1024, raised[tail]) != DM_OK) return DM_ERR_LAUNCH;
+    DM_LAUNCH(fn, grid, block, (size_t)l.lds_bytes, st, a);
+  } else {
+    g.MT = l.MT; g.JT = l.JT; g.chunks_per_split = l.per_split; g.nsplit = l.splits;
+    DM_LAUNCH(r.build->fn, grid, block, 0, st, g);
+  }
+  const int rc = dm_check_launch();
+  if (rc != DM_OK || r.count == 1) return rc;
+  const WgradLaunch& m = r.launch[1];
+#define WG_REDUCE_CASE(P)                                                                                                          \
+  case P: DM_LAUNCH((wgrad_slab_reduce_kernel<P>), dim3((unsigned)m.grid), dim3((unsigned)m.threads), 0, st, g.slab, m.slabs,      \
+                    g.slab_stride, m.slab_ld, g.Cout, g.Cs * l.p[0] * l.p[0], g.dw, g.ldw, g.coloff, g.db ? g.slab_db : nullptr,   \
+                    m.splits, m.slab_rows, g.db); break
+  switch (m.p[0]) {
+    WG_REDUCE_CASE(1); WG_REDUCE_CASE(4); WG_REDUCE_CASE(16); WG_REDUCE_CASE(64);
+    default: return DM_ERR_UNSUPPORTED;                                   // (a route that names no build: a bug in wgrad_route)
+  }
+#undef WG_REDUCE_CASE
+  return dm_check_launch();
 }
 
 // ----------------------------------------------------------------- K11 backward
@@ -2018,42 +2073,37 @@ extern "C" int dm_fx_to_float(long long* fx, long long n, float* out, int accumu
 
 static int conv2d_wgrad_impl(const float* dy, long long dy_batch_stride, int Cout, const float* x,
                              long long x_batch_stride, int Cs, int NB, int H, int W, int ksize, float* dw, int ldw,
-                             int col_offset, float* db, int fx, dm_stream_t stream, float* scratch = nullptr,
+                             int col_offset, float* db, int mode, dm_stream_t stream, float* scratch = nullptr,
                              long long scratch_floats = 0) {
-  if (!dy || !x || !dw || Cout <= 0 || Cs <= 0 || NB <= 0 || H <= 0 || W <= 0 || (ksize != 1 && ksize != 3))
-    return DM_ERR_INVALID_ARG;
-  if ((long long)NB * H * W > 0x7fffffffLL) return DM_ERR_INVALID_ARG;
+  if (!dy || !x || !dw || (mode == WG_SLAB && !scratch)) return DM_ERR_INVALID_ARG;
+  const WgradRoute r = wgrad_route({dy_batch_stride, x_batch_stride, Cout, Cs, NB, H, W, ksize, db != nullptr, mode, scratch_floats,
+                                    (((uintptr_t)dy | (uintptr_t)x) & 7u) == 0, (((uintptr_t)scratch) & 15u) == 0, wgrad_target_wgs()});
+  if (r.rc != DM_OK) return r.rc;
   WgradArgs a;
   a.dy = dy; a.dy_bs = dy_batch_stride; a.x = x; a.x_bs = x_batch_stride; a.Cout = Cout; a.Cs = Cs;
   a.NB = NB; a.H = H; a.W = W; a.HW = H * W; a.Q = NB * H * W; a.dw = dw; a.ldw = ldw; a.coloff = col_offset;
-  a.fx = fx; a.db = db; a.scratch = scratch; a.scratch_floats = scratch_floats;
-  if (ksize == 3) {
-    const int rc = launch_wgrad3_narrow(a, (hipStream_t)stream);
-    if (rc < 0) return rc;
-    if (rc == 1) launch_wgrad<3>(a, (hipStream_t)stream);
-  } else {
-    launch_wgrad<1>(a, (hipStream_t)stream);
-  }
-  return dm_check_launch();
+  a.db = db; a.scratch = scratch; a.scratch_floats = scratch_floats;
+  return wgrad_emit(r, a, (hipStream_t)stream);
 }
 
 extern "C" int dm_conv2d_wgrad(const float* dy, long long dy_batch_stride, int Cout, const float* x,
                                long long x_batch_stride, int Cs, int NB, int H, int W, int ksize, float* dw, int ldw,
                                int col_offset, float* db, dm_stream_t stream) {
-  return conv2d_wgrad_impl(dy, dy_batch_stride, Cout, x, x_batch_stride, Cs, NB, H, W, ksize, dw, ldw, col_offset, db, 0,
+  return conv2d_wgrad_impl(dy, dy_batch_stride, Cout, x, x_batch_stride, Cs, NB, H, W, ksize, dw, ldw, col_offset, db, WG_ATOMICS,
                            stream);
 }
 
 extern "C" long long dm_conv2d_wgrad_scratch_floats(void) {
-  // an upper bound for every shape: slabs x tile <= target workgroups x (K-waves x tile) = target x 16384, + the bias rows
+  // What a call whose launch is split needs at most (MT x JT <= target: slabs x tile <= target workgroups x (K-waves x tile)
+  // = target x 16384, + the bias rows).  A call with MORE output tiles than the target is not split and needs WGK x MT TM x
+  // JT TN floats, which this does not cover: wgrad_carve_slabs then gives it no slabs (dm_conv2d_wgrad_plan shows which).
   return (long long)wgrad_target_wgs() * (16384 + 256);
 }
 
 extern "C" int dm_conv2d_wgrad_slab(const float* dy, long long dy_batch_stride, int Cout, const float* x, long long x_batch_stride,
                                     int Cs, int NB, int H, int W, int ksize, float* dw, int ldw, int col_offset, float* db,
                                     float* scratch, long long scratch_floats, dm_stream_t stream) {
-  if (!scratch || scratch_floats <= 0) return DM_ERR_INVALID_ARG;
-  return conv2d_wgrad_impl(dy, dy_batch_stride, Cout, x, x_batch_stride, Cs, NB, H, W, ksize, dw, ldw, col_offset, db, 0, stream,
+  return conv2d_wgrad_impl(dy, dy_batch_stride, Cout, x, x_batch_stride, Cs, NB, H, W, ksize, dw, ldw, col_offset, db, WG_SLAB, stream,
                            scratch, scratch_floats);
 }
 
@@ -2061,7 +2111,25 @@ extern "C" int dm_conv2d_wgrad_fx(const float* dy, long long dy_batch_stride, in
                                   long long x_batch_stride, int Cs, int NB, int H, int W, int ksize, long long* dw_fx,
                                   int ldw, int col_offset, long long* db_fx, dm_stream_t stream) {
   return conv2d_wgrad_impl(dy, dy_batch_stride, Cout, x, x_batch_stride, Cs, NB, H, W, ksize,
-                           reinterpret_cast<float*>(dw_fx), ldw, col_offset, reinterpret_cast<float*>(db_fx), 1, stream);
+                           reinterpret_cast<float*>(dw_fx), ldw, col_offset, reinterpret_cast<float*>(db_fx), WG_FX, stream);
+}
+
+// (added to ABI 29) What the three entry points above would launch for these host arguments: wgrad_route's own value, the
+// one wgrad_emit enqueues (the header has the record layout).  Nothing below touches HIP but dm_num_cus().
+extern "C" int dm_conv2d_wgrad_plan(long long dy_batch_stride, int Cout, long long x_batch_stride, int Cs, int NB, int H, int W,
+                                    int ksize, int has_bias, int mode, long long scratch_floats, int io_aligned8,
+                                    int scratch_aligned16, int* records, int max_records) {
+  if (!records || max_records < DM_WGRAD_PLAN_MAX_LAUNCHES) return DM_ERR_INVALID_ARG;
+  const WgradRoute r = wgrad_route({dy_batch_stride, x_batch_stride, Cout, Cs, NB, H, W, ksize, has_bias != 0, mode, scratch_floats,
+                                    io_aligned8 != 0, scratch_aligned16 != 0, wgrad_target_wgs()});
+  if (r.rc != DM_OK) return r.rc;
+  for (int l = 0; l < r.count; ++l) {
+    const WgradLaunch& m = r.launch[l];
+    const int rec[DM_WGRAD_PLAN_INTS] = {m.kernel, m.p[0], m.p[1], m.p[2], m.p[3], m.p[4], m.grid, m.threads, m.lds_bytes, m.MT, m.JT,
+                                         m.splits, m.per_split, m.slabs, m.slab_ld, m.slab_rows, m.slab_stride, m.accum};
+    for (int i = 0; i < DM_WGRAD_PLAN_INTS; ++i) records[l * DM_WGRAD_PLAN_INTS + i] = rec[i];
+  }
+  return r.count;
 }
 
 extern "C" int dm_upsample2x_bilinear_bwd(const float* grad_out, const float* fwd_out_for_relu, int NC, int H, int W,

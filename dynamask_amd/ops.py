@@ -1883,36 +1883,78 @@ def conv2d_wgrad(dy, srcs, ksize, dw=None, db=None, want_bias=False):
     if db is not None:
         _chk(db, 'db')
         assert db.shape == (Cout,)
-    if WGRAD_SLAB[0]:
-        # split-K partial tiles into slabs, added in a fixed order: no atomics, the same bits every run (in either mode)
-        if det:
-            if not acc:
-                dw.zero_()
-            if db is not None and not bias_acc:
-                db.zero_()
+    # the accumulation, chosen once: split-K partial tiles into slabs, added in a fixed order (no atomics, the same bits every
+    # run in either mode); else 64-bit fixed point (deterministic) or float atomics
+    mode = 'slab' if WGRAD_SLAB[0] else ('fx' if det else 'atomics')
+    ldw, taps = cin * ksize * ksize, ksize * ksize
+    scratch, nfl = None, 0
+    if mode == 'slab':
         nfl = _wgrad_scratch_floats()
         scratch = torch.empty((nfl,), device=dy.device, dtype=torch.float32)      # from the calling stream's pool
-        base = 0
-        for i, s in enumerate(srcs):
-            check(lib().dm_conv2d_wgrad_slab(_p(dy), dy.stride(0), Cout, _p(s), s.stride(0), s.shape[1], NB, H, W, ksize, _p(dw),
-                                             cin * ksize * ksize, base * ksize * ksize, _p(db if i == 0 else None), _p(scratch),
-                                             nfl, _stream()), 'dm_conv2d_wgrad_slab')
-            base += s.shape[1]
-        return (dw, db) if db is not None else dw
-    fx = _fx_like(dw) if det else None
-    bfx = _fx_like(db) if det and db is not None else None
-    fn = lib().dm_conv2d_wgrad_fx if det else lib().dm_conv2d_wgrad
+        # a source whose slabs the scratch cannot hold would add with float atomics (dm_conv2d_wgrad_slab does not refuse it):
+        # where the same bits are promised, the launcher's own route is asked, and such a call takes the fixed-point form
+        def takes_slabs(i, s):
+            first = conv2d_wgrad_plan(NB, Cout, s.shape[1], H, W, ksize, has_bias=db is not None and i == 0, scratch_floats=nfl,
+                                      dy_bs=dy.stride(0), x_bs=s.stride(0), io_aligned8=(dy.data_ptr() | s.data_ptr()) % 8 == 0,
+                                      scratch_aligned16=scratch.data_ptr() % 16 == 0)[0]
+            return first['accum'] == WGRAD_MODES.index('slab')
+        if det and not all(takes_slabs(i, s) for i, s in enumerate(srcs)):
+            mode, scratch = 'fx', None
+    if mode == 'slab' and det:
+        if not acc:
+            dw.zero_()
+        if db is not None and not bias_acc:
+            db.zero_()
+    fx = _fx_like(dw) if mode == 'fx' else None
+    bfx = _fx_like(db) if mode == 'fx' and db is not None else None
+    name = {'slab': 'dm_conv2d_wgrad_slab', 'fx': 'dm_conv2d_wgrad_fx', 'atomics': 'dm_conv2d_wgrad'}[mode]
     base = 0
     for i, s in enumerate(srcs):
-        bias_ptr = (bfx if det else db) if i == 0 else None
-        check(fn(_p(dy), dy.stride(0), Cout, _p(s), s.stride(0), s.shape[1], NB, H, W, ksize, _p(fx if det else dw),
-                 cin * ksize * ksize, base * ksize * ksize, _p(bias_ptr), _stream()), 'dm_conv2d_wgrad')
+        bias_ptr = (bfx if mode == 'fx' else db) if i == 0 else None
+        tail = (_p(scratch), nfl, _stream()) if mode == 'slab' else (_stream(),)
+        check(getattr(lib(), name)(_p(dy), dy.stride(0), Cout, _p(s), s.stride(0), s.shape[1], NB, H, W, ksize,
+                                   _p(fx if mode == 'fx' else dw), ldw, base * taps, _p(bias_ptr), *tail), name)
         base += s.shape[1]
-    if det:
+    if mode == 'fx':
         _fx_finish(fx, dw, acc)
         if db is not None:
             _fx_finish(bfx, db, bias_acc)
     return (dw, db) if db is not None else dw
+
+
+WGRAD_PLAN_FIELDS = ('kernel', 'P0', 'P1', 'P2', 'P3', 'P4', 'grid', 'threads', 'lds_bytes', 'MT', 'JT', 'splits', 'per_split',
+                     'slabs', 'slab_ld', 'slab_rows', 'slab_stride', 'accum')
+WGRAD_KERNELS = ('gemm', 'narrow', 'reduce')              # field 'kernel' of a plan record
+WGRAD_MODES = ('atomics', 'slab', 'fx')                   # dm_conv2d_wgrad_plan's `mode`, and field 'accum' of a record
+
+
+def conv2d_wgrad_plan_raw(dy_bs, cout, x_bs, cs, NB, H, W, ksize, has_bias=0, mode=0, scratch_floats=0, io_aligned8=1,
+                          scratch_aligned16=1):
+    """dm_conv2d_wgrad_plan: (return code, records).  The code is the number of launches or the (negative) error the call
+    with these arguments would return.  Host only: no tensor, no device."""
+    consts = _abi.load()[1]
+    n, cap = consts['DM_WGRAD_PLAN_INTS'], consts['DM_WGRAD_PLAN_MAX_LAUNCHES']
+    assert len(WGRAD_PLAN_FIELDS) == n
+    rec = (ctypes.c_int * (n * cap))(*([-1] * (n * cap)))
+    rc = lib().dm_conv2d_wgrad_plan(int(dy_bs), int(cout), int(x_bs), int(cs), int(NB), int(H), int(W), int(ksize), int(has_bias),
+                                    int(mode), int(scratch_floats), int(io_aligned8), int(scratch_aligned16), rec, cap)
+    return rc, [dict(zip(WGRAD_PLAN_FIELDS, rec[i * n:(i + 1) * n])) for i in range(max(rc, 0))]
+
+
+def conv2d_wgrad_plan(NB, cout, cs, H, W, ksize, mode='slab', has_bias=False, scratch_floats=None, dy_bs=None, x_bs=None,
+                      io_aligned8=True, scratch_aligned16=True):
+    """The launches the weight gradient of one source of ``cs`` channels would make for this shape, as the launcher's own
+    route says (include/dynamask_hip.h, dm_conv2d_wgrad_plan): a list of one or two dicts with the keys WGRAD_PLAN_FIELDS
+    (two: the slab reduce follows).  ``mode``: one of WGRAD_MODES; 'slab' with ``scratch_floats`` None: the scratch
+    ``conv2d_wgrad`` brings.  A 'slab' call whose first record says ``accum`` 0 adds with float atomics.  Batch strides:
+    those of contiguous tensors unless given.  Raises where the call would fail."""
+    if scratch_floats is None:
+        scratch_floats = _wgrad_scratch_floats() if mode == 'slab' else 0
+    rc, recs = conv2d_wgrad_plan_raw(cout * H * W if dy_bs is None else dy_bs, cout, cs * H * W if x_bs is None else x_bs, cs, NB,
+                                     H, W, ksize, has_bias, WGRAD_MODES.index(mode), scratch_floats, io_aligned8, scratch_aligned16)
+    if rc < 0:
+        check(rc, 'dm_conv2d_wgrad_plan')
+    return recs
 
 
 def upsample2x_backward(grad_out, fwd_out, in_shape, align_corners=False):

@@ -63,7 +63,7 @@ const char* dm_error_string(int code);
  * GroupNorm, neighbour fusion, grouped 4x4 stride-2 deconvolution and box vote (section K27); the convolution launcher's
  * own report of its launches, dm_conv2d_plan (section K5/K6) and dm_conv2d_group_plan (section K25); Double-Head R-CNN's
  * rescaled RoIAlign and global average pool (section K28); the DCN forward launcher's route, dm_deform_conv_plan
- * (section K8). */
+ * (section K8); the weight-gradient launcher's route, dm_conv2d_wgrad_plan. */
 #define DM_ABI_VERSION 29 /* the one definition: dm_abi_version(), dm_build_info() and _lib.ABI_VERSION read it */
 int dm_abi_version(void);
 /* "libdynamask_hip abi=N arch=gfx950 compiler=<clang version> flags=<the product-wide flags of dynamask_amd/build.py>"
@@ -685,13 +685,44 @@ int dm_conv2d_wgrad(const float* dy, long long dy_batch_stride, int Cout, const 
 
 /* The same sums without atomics: every split of the pixel axis writes its partial tile to a slab of `scratch`, a second
  * kernel adds the slabs in index order into dw (and the splits' bias rows into db) -- bit-identical from run to run, as the
- * reference's weight gradient is (a deterministic addmm_, mmdet/ops/dcn/src/deform_conv_cuda.cpp:460-465).  scratch: at
- * least dm_conv2d_wgrad_scratch_floats() floats for ANY shape, 16-byte aligned (a launch that would need more, or a scratch
- * that is not aligned, falls back to the atomics of dm_conv2d_wgrad); contents undefined afterwards; not shared between streams.  dw / db are accumulated into, as above. */
+ * reference's weight gradient is (a deterministic addmm_, mmdet/ops/dcn/src/deform_conv_cuda.cpp:460-465).  scratch:
+ * 16-byte aligned, scratch_floats > 0; contents undefined afterwards; not shared between streams.  dw / db are accumulated
+ * into, as above.  A call whose slabs do not fit the scratch, or whose scratch is not aligned, is NOT refused: it returns
+ * DM_OK and adds with the float atomics of dm_conv2d_wgrad (not the same bits every run).  dm_conv2d_wgrad_plan says which
+ * a call takes (record field 17), and a caller that needs the same bits asks it first.
+ * dm_conv2d_wgrad_scratch_floats(): target x (16384 + 256) floats, target = two workgroups per compute unit (or
+ * DM_WGRAD_WGS).  It suffices for every call whose output tiles (field 9 x field 10 of the plan: cout tiles x column tiles,
+ * or 1 x channel groups of the narrow 3x3 kernel) number at most `target`: such a launch is split into at most target
+ * workgroups of at most 16384 slab floats each.  A call with more tiles is not split and needs a slab as large as its
+ * padded dw (K-waves x cout tiles x 64 WGM x column tiles x 64 WGN floats), which may exceed the bound: 1024 -> 1024
+ * channels 3x3 at 256 compute units is 8 x 72 = 576 tiles, 9.44 M floats against 8.52 M. */
 long long dm_conv2d_wgrad_scratch_floats(void);
 int dm_conv2d_wgrad_slab(const float* dy, long long dy_batch_stride, int Cout, const float* x, long long x_batch_stride,
                          int Cs, int NB, int H, int W, int ksize, float* dw, int ldw, int col_offset, float* db,
                          float* scratch, long long scratch_floats, dm_stream_t stream);
+
+/* (added to ABI 29) The launches dm_conv2d_wgrad / dm_conv2d_wgrad_slab / dm_conv2d_wgrad_fx would make for these HOST
+ * arguments: the route the launcher decides on, the very value it then enqueues (nothing is launched, no device is needed --
+ * without one the compute-unit count is taken as 256).  Arguments as dm_conv2d_wgrad_slab's, with facts in place of the
+ * pointers: has_bias (db given), mode (0 dm_conv2d_wgrad, 1 dm_conv2d_wgrad_slab, 2 dm_conv2d_wgrad_fx), scratch_floats
+ * (mode 1 only), io_aligned8 (dy and x are both 8-byte aligned), scratch_aligned16.  The DM_WGRAD_WGS knob applies as it does
+ * to launches (read once per process).
+ * records: HOST array of max_records (>= DM_WGRAD_PLAN_MAX_LAUNCHES) x DM_WGRAD_PLAN_INTS ints.  Returns the number of
+ * launches (1; 2: the slab reduce follows) or the error code the call would return for these numbers, and then writes
+ * nothing.  Record l, ints [l * DM_WGRAD_PLAN_INTS ..):
+ *   0 kernel: 0 conv_wgrad_kernel (the GEMM), 1 conv_wgrad3_narrow_kernel, 2 wgrad_slab_reduce_kernel;
+ *   1 .. 5 its template parameters: KS, WGM, WGN, WGK, TAIL (kernel 0); 3, 0, 0, 0, TAIL (kernel 1); P, 0, 0, 0, 0 (kernel 2);
+ *   6 grid x, 7 threads per workgroup, 8 dynamic LDS bytes;
+ *   9 MT, 10 JT: cout tiles and column tiles (kernel 1: 1 and groups of 32 input channels; kernel 2: zeros);
+ *   11 splits of the pixel axis, 12 what a split walks: chunks of 32 pixels (kernel 0), (image, row band) units (kernel 1),
+ *      0 (kernel 2);
+ *   13 slabs (0: none), 14 slab row length, 15 rows of a split's bias row block, 16 floats per slab (saturates at INT_MAX);
+ *   17 the accumulation TAKEN: 0 float atomics, 1 slabs + reduce, 2 fixed point.  Mode 1 with 0 here is the fallback. */
+#define DM_WGRAD_PLAN_INTS 18
+#define DM_WGRAD_PLAN_MAX_LAUNCHES 2
+int dm_conv2d_wgrad_plan(long long dy_batch_stride, int Cout, long long x_batch_stride, int Cs, int NB, int H, int W, int ksize,
+                         int has_bias, int mode, long long scratch_floats, int io_aligned8, int scratch_aligned16, int* records,
+                         int max_records);
 
 /* adjoint of dm_upsample2x_bilinear_fwd; fwd_out_for_relu (optional) masks the
  * fused ReLU; grad_in is overwritten (no zero-fill needed; planes up to 64 KB of
