@@ -298,7 +298,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradArgs a) {
             const size_t o = off_lane + (size_t)k * a.ldw;
 #pragma unroll
             for (int j = 0; j < 2; ++j)
-              if (j_ok[j]) atomicAdd(dwx + cj[j] + o, dm_to_fx(acc[i][j][r]));
+              if (j_ok[j]) dm_fx_add(dwx + cj[j] + o, acc[i][j][r]);
           }
         }
     }
@@ -973,7 +973,7 @@ __global__ __launch_bounds__(256) void point_sample_bwd_kernel(const float* __re
                                                                const float* __restrict__ rois, int N, int S, float scale,
                                                                float* __restrict__ gfeat, int lds_elems, int fixed) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long tile[];   // [CT][TH][TW] fixed point
-  __shared__ int bad[CT];            // a NaN / Inf gradient cannot be represented in fixed point: it poisons its plane
+  __shared__ int bad[CT];            // a NaN / Inf / |g| >= 2^27 gradient has no fixed-point value: it poisons its plane
   if (threadIdx.x < CT) bad[threadIdx.x] = 0;
   const int n = blockIdx.y;
   const int c0 = blockIdx.x * CT;
@@ -1033,7 +1033,7 @@ __global__ __launch_bounds__(256) void point_sample_bwd_kernel(const float* __re
     if (use_lds) {
 #pragma unroll
       for (int c = 0; c < CT; ++c)
-        if (!isfinite(gv[c])) { bad[c] = 1; gv[c] = 0.f; }
+        if (!(__builtin_fabsf(gv[c]) < DM_FIX_ADDEND_MAX)) { bad[c] = 1; gv[c] = 0.f; }
       const int tx0 = x0 - fx0, ty0 = y0 - fy0;     // in range by construction of the footprint
 #pragma unroll
       for (int c = 0; c < CT; ++c) {
@@ -1067,7 +1067,7 @@ __global__ __launch_bounds__(256) void point_sample_bwd_kernel(const float* __re
         const int ty = rem / TW, tx = rem - ty * TW;
         const size_t cell = (size_t)c * plane + (size_t)(fy0 + ty) * W + fx0 + tx;
         if (fixed) {      // the LDS sum is already exact in the same fixed-point format: hand it over as it is
-          atomicAdd(reinterpret_cast<unsigned long long*>(gf) + cell, bad[c] ? (unsigned long long)(1LL << 62) : (unsigned long long)q);
+          dm_fx_add_q(reinterpret_cast<unsigned long long*>(gf) + cell, q, bad[c] != 0);
         } else {
           const float v = bad[c] ? __builtin_nanf("") : (float)((double)q * (1.0 / DM_FIX_SCALE));
           atomicAdd(gf + cell, v);
@@ -1690,7 +1690,7 @@ __global__ __launch_bounds__(NT, 4) void dcn_coord_grad_lds_kernel(const float* 
 // accumulates the 9 x HW x 4 scatter-adds in an LDS copy of the planes and writes each
 // plane once: no global atomics (the reference's col2im kernel,
 // deform_conv_cuda_kernel.cu:279-335, uses atomicAdd to HBM).
-// The LDS accumulators are 64-bit FIXED POINT (2^-36 resolution, |sum| < 1.3e8):
+// The LDS accumulators are 64-bit FIXED POINT (2^-36 per addend, |g| and |sum| < 2^27; dynamask_hip.h has the contract):
 // measured on gfx950 (tools/micro/lds_atomics.hip) ds_add_f32 runs at 0.38 lane-atomics
 // per clock per CU, ds_add_u64 at 6.4 (17x) -- and integer sums are order-independent,
 // so this gradient is bitwise reproducible run to run.
@@ -1699,7 +1699,7 @@ __global__ __launch_bounds__(NTH) void dcn_col2im_lds_kernel(const float* __rest
                                                              const float* __restrict__ offset, int NB, int C, int H, int W,
                                                              int dg, float* __restrict__ gx) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long lds[];   // [CT][HW] fixed point
-  __shared__ int bad[CT];            // non-finite column gradients poison their plane (see the header's contract)
+  __shared__ int bad[CT];            // column gradients the cells cannot hold (NaN, Inf, |g| >= 2^27) poison their plane
   if (threadIdx.x < CT) bad[threadIdx.x] = 0;
   const int HW = H * W;
   const int chunks = C / CT;
@@ -1806,7 +1806,7 @@ __global__ __launch_bounds__(NTH) void dcn_col2im_lds_kernel(const float* __rest
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             float gv = cg[u][c][e];
-            if (!isfinite(gv)) { bad[c] = 1; gv = 0.f; }
+            if (!(__builtin_fabsf(gv) < DM_FIX_ADDEND_MAX)) { bad[c] = 1; gv = 0.f; }
             float tl = gv * wa[e][0], bl = gv * wa[e][2];
             if (e > 0 && link[e - 1]) { tl += ct; bl += cb; }
             // (corners outside the map are branched around: adding zero to a clamped cell instead -- no exec-mask
@@ -1831,7 +1831,7 @@ __global__ __launch_bounds__(NTH) void dcn_col2im_lds_kernel(const float* __rest
 #pragma unroll
       for (int c = 0; c < CT; ++c) {
         cgv[c] = cgb[((size_t)tap * C + c) * HW + p];
-        if (!isfinite(cgv[c])) { bad[c] = 1; cgv[c] = 0.f; }
+        if (!(__builtin_fabsf(cgv[c]) < DM_FIX_ADDEND_MAX)) { bad[c] = 1; cgv[c] = 0.f; }
       }
       scatter(tap, p, offb[(size_t)(2 * tap) * HW + p], offb[(size_t)(2 * tap + 1) * HW + p], cgv);
     }

@@ -63,8 +63,9 @@ static inline int dm_ensure_lds_limit(const void* kernel, int bytes, bool* flags
 // ---- order-independent accumulation (deterministic mode; dynamask_hip.h "Deterministic accumulation") ----
 // The *_fx entry points add into 64-bit fixed-point cells (value * 2^36, two's complement through the u64 atomic)
 // instead of float cells: integer addition is associative, so the sum does not depend on the order in which
-// workgroups arrive.  A non-finite addend becomes 2^62 (dm_fx_to_float turns any |cell| >= 2^61 into NaN).
+// workgroups arrive.  The contract (resolution, ranges, poison) is in dynamask_hip.h, "Fixed-point accumulators".
 #define DM_FX_ONE 68719476736.0 /* 2^36 */
+#define DM_FIX_ADDEND_MAX 134217728.f /* 2^27: what dm_fix36_mul / dm_fix36_abs16 convert without saturating */
 // g * w -> the same 2^-36 fixed point in eight fp32 / integer instructions (the fp64 route -- a double multiply and
 // __double2ll_rn, for which there is no hardware convert -- is ~11 and the DCN col2im is bound by exactly these: 5.3e8
 // vector instructions per launch, its VALU pipe 100 % busy).  The caller passes w16 = w * 2^4 and w36 = w * 2^36 (exact
@@ -95,13 +96,28 @@ __device__ __forceinline__ void dm_fix36_accumulate(unsigned long long* cell, fl
   else atomicAdd(cell, mag);
 }
 
-__device__ __forceinline__ unsigned long long dm_to_fx(float v) {
-  const long long q = __builtin_isfinite(v) ? __double2ll_rn((double)v * DM_FX_ONE) : (1LL << 62);
-  return (unsigned long long)q;
+// An addend an fx cell cannot hold (NaN, Inf, |v| >= DM_FX_ADDEND_MAX = 2^25) POISONS the cell: a signed maximum with
+// LLONG_MAX.  The maximum absorbs (adding a marker does not: four markers of 2^62 sum to 0 mod 2^64 and the cell read
+// as clean): whatever the cell held and however many bad addends arrive it is LLONG_MAX afterwards, and in-range addends
+// that follow (|their sum| < 2^61) leave it at |q| >= 2^61, which dm_fx_to_float reads as NaN.
+#define DM_FX_ADDEND_MAX 33554432.f    /* 2^25: |v| * 2^36 < 2^61, below the poison threshold */
+#define DM_FX_POISON 0x7fffffffffffffffLL
+#define DM_FX_POISON_MIN (1LL << 61)   /* |cell| >= this: poisoned */
+__device__ __forceinline__ void dm_fx_poison(unsigned long long* cell) {
+  atomicMax(reinterpret_cast<long long*>(cell), DM_FX_POISON);
+}
+// a sum that is already in the cells' format (the LDS tiles' flush)
+__device__ __forceinline__ void dm_fx_add_q(unsigned long long* cell, long long q, bool bad) {
+  if (bad || q >= DM_FX_POISON_MIN || q <= -DM_FX_POISON_MIN) dm_fx_poison(cell);
+  else atomicAdd(cell, (unsigned long long)q);
+}
+__device__ __forceinline__ void dm_fx_add(unsigned long long* cell, float v) {
+  if (__builtin_fabsf(v) < DM_FX_ADDEND_MAX) atomicAdd(cell, (unsigned long long)__double2ll_rn((double)v * DM_FX_ONE));
+  else dm_fx_poison(cell);
 }
 // accumulate v into cell idx of an accumulator that is float (fx = false) or 64-bit fixed point (fx = true)
 __device__ __forceinline__ void dm_acc_add(float* base, size_t idx, float v, bool fx) {
-  if (fx) atomicAdd(reinterpret_cast<unsigned long long*>(base) + idx, dm_to_fx(v));
+  if (fx) dm_fx_add(reinterpret_cast<unsigned long long*>(base) + idx, v);
   else atomicAdd(base + idx, v);
 }
 

@@ -24,11 +24,10 @@
  *     Calls from several host threads are safe (a race only repeats an
  *     idempotent attribute call);
  *   - LDS scatter-accumulators (dm_deform_col2im_coord, the scatter form of
- *     dm_point_sample_bwd) are 64-bit fixed point with 2^-36 resolution: every
- *     addend is the fp32 product gradient * bilinear weight cut to that grid and
- *     integer sums are associative, so a plane's result does not depend on the
- *     order of arrival, for gradient magnitudes in [1.5e-11, 1.3e8]; a non-finite
- *     contribution poisons its output plane with NaN (it is not silently dropped);
+ *     dm_point_sample_bwd) are 64-bit fixed point: integer sums are associative,
+ *     so a plane's result does not depend on the order of arrival.  Resolution,
+ *     range and poison rules: "Fixed-point accumulators" below (one contract for
+ *     these and for the *_fx entry points);
  *   - return value: 0 = enqueued, negative = error (DM_ERR_*); the host binding
  *     raises on any non-zero code (dm_error_string()).
  *
@@ -885,8 +884,27 @@ int dm_scale(float* x, long long count, float factor, dm_stream_t stream);
  * same arguments whose accumulation target is a buffer of 64-bit FIXED-POINT cells (value * 2^36, two's
  * complement; same indexing as the float target, the caller zero-fills it): integer addition is associative,
  * so the sum is exact in that format and identical on every run.  dm_fx_to_float converts
- * (out[i] (+)= fx[i] * 2^-36, NaN for a cell that received a non-finite addend; `clear` re-zeroes fx).
- * Range: |sum| < 3.3e7 per cell, resolution 1.5e-11 -- far outside what gradients of this path reach.
+ * (out[i] (+)= fx[i] * 2^-36, NaN for a poisoned cell; `clear` re-zeroes fx).
+ *
+ * Fixed-point accumulators: the contract (these cells and the LDS cells of dm_deform_col2im[_coord] and of the
+ * scatter form of dm_point_sample_bwd).
+ *  - Resolution.  ABSOLUTE, 2^-36 (1.5e-11) per ADDEND, whatever the scale of the gradients: an addend is the fp32
+ *    value the float path would add (gradient * bilinear weight, or a workgroup's partial sum) put on the 2^-36 grid
+ *      - cut towards zero in dm_deform_col2im (error < 2^-36 per addend, <= 2 * 2^-36 where H * W % 4 != 0);
+ *      - rounded to nearest everywhere else (error <= 2^-37 per addend; the scatter form of dm_point_sample_bwd rounds
+ *        the exact product, not the fp32 one).
+ *    So a cell that K addends reach is within K grid units of the sum of its fp32 addends, and a gradient of 1e-9 is
+ *    held to about 1 %: there is no relative accuracy below the grid.  (Losses normalised by the element count give
+ *    peaks of 1e-5 .. 1e-3 here: 5 to 7 digits per addend.)
+ *  - Range.  LDS cells: every addend |g * w| < 2^27 (1.3e8), ensured by |g| < 2^27, and |sum| < 2^27 at any
+ *    moment.  *_fx cells: every addend |v| < 2^25 (3.3e7), and |sum| < 2^25 at any moment.  A sum of in-range addends that leaves the range is
+ *    UNSPECIFIED (it may wrap, or read as poison).
+ *  - Poison.  An addend outside the range -- NaN, Inf, or finite and too large -- is not dropped and not saturated: it
+ *    poisons its target, which then reads NaN.  LDS kernels poison the whole output plane (image, channel) of the bad
+ *    gradient; into a float target every cell of the plane's footprint becomes NaN, into an fx target every such cell
+ *    is poisoned.  An fx cell is poisoned by a signed maximum with 2^63 - 1, which absorbs: any number of bad addends,
+ *    mixed in any order with in-range ones, leaves |cell| >= 2^61, and dm_fx_to_float turns exactly those cells into
+ *    NaN.  The bits of every other cell are those of the run without the bad addends.
  * Everything else in the training step is deterministic by construction (fixed-order partial sums, LDS
  * fixed-point scatter, gather-form adjoints) except dm_roi_align_bwd (float atomics into the FPN-map
  * gradients, as in the reference's RoIAlign backward).  The host switch is DM_DETERMINISTIC=1
