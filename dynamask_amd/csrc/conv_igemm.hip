@@ -77,6 +77,11 @@ struct ConvArgs {
   int want_split = 0;        // host side: the launcher's choice of splits for this launch (0: launch_conv_mp decides)
   // POST builds (dm_conv2d_post_add_fwd): same layout as out, added AFTER the activation; may be out itself
   const float* addend = nullptr;
+  // POST == 2 builds (K31, dm_conv2d_up_add_fwd): addend is a dense [NB, Cout, up_Hs, up_Ws] map of its own, read at
+  // (up_iy[y], up_ix[x]) -- device tables of H and W entries; up_plane = up_Hs * up_Ws, its channel stride
+  const int* up_iy = nullptr;
+  const int* up_ix = nullptr;
+  int up_Ws = 0, up_plane = 0;
   ConvPlan* plan = nullptr;  // host side, null in every product call: record the launch instead of making it (dm_conv2d_plan)
 };
 
@@ -773,6 +778,21 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
     const int co_lane = m0 + wave_m * WM * 32 + 4 * hi;
     const size_t off_lane = (size_t)co_lane * HW;
     const bool relu = e_relu & 1;
+    // POST == 2: the addend is a smaller map of its own, gathered through the row and column tables.  One base per pixel
+    // column (image, iy[y], ix[x]: the two lookups happen here, once, in front of the bias loads) and one per-lane channel
+    // offset in the addend's own plane stride; the store loop adds a uniform k * up_plane, as it adds k * HW for out.
+    const float* aj[WN];
+    const int up_plane = POST == 2 ? a.up_plane : 0;
+    const size_t aoff_lane = (size_t)co_lane * up_plane;
+#pragma unroll
+    for (int j = 0; j < WN; ++j) {
+      aj[j] = nullptr;
+      if (POST == 2) {
+        const int y = col_p[j] / W;          // (col_p is that of a pixel inside the map in every lane: q is clamped above)
+        const int x = col_p[j] - y * W;
+        aj[j] = a.addend + (size_t)col_n[j] * a.Cout * up_plane + (a.up_iy[y] * a.up_Ws + a.up_ix[x]);
+      }
+    }
     // all bias values first: a load inside the store loop puts an s_waitcnt vmcnt(0) -- which also
     // waits for the stores issued so far -- in front of every output row
     float bias_r[WM][16];
@@ -793,7 +813,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
         for (int r = 0; r < 16; ++r) asm volatile("" : "+v"(bias_r[i][r]));
     }
     const ptrdiff_t mask_off = e_mask ? e_mask - e_out : 0;
-    const ptrdiff_t add_off = POST ? a.addend - e_out : 0;
+    const ptrdiff_t add_off = POST == 1 ? a.addend - e_out : 0;
     // full: the workgroup's tile lies inside the output (every cout row and every pixel column exists) -- uniform, and then
     // no store is predicated: the row and column tests cost an exec-mask sequence each, 600 scalar instructions per wave in
     // front of the 64 stores of a K = 64 GEMM (SQ counters: 4.8 SALU per MFMA on 64 -> 576 @56^2)
@@ -808,6 +828,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
           if (decltype(full_mode)::value || co_lane + k < a.Cout) {
             const float b = bias_r[i][r];
             const size_t o = off_lane + (size_t)k * HW;
+            const size_t ao = aoff_lane + (size_t)k * up_plane;
 #pragma unroll
             for (int j = 0; j < WN; ++j) {
               if (decltype(full_mode)::value || col_ok[j]) {
@@ -815,7 +836,8 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
                 float v = acc[i][j][r] + b;
                 if (decltype(acc_mode)::value) v += *op;          // accumulate into the destination (gradient sums)
                 if (relu) v = fmaxf(v, 0.f);
-                if (POST) v = op[add_off] + v;                    // (read before this thread's own store: out may be the addend)
+                if (POST == 2) v = aj[j][ao] + v;                 // (a map of its own: it never is out)
+                else if (POST) v = op[add_off] + v;               // (read before this thread's own store: out may be the addend)
                 if (decltype(mask_mode)::value) v = (op[mask_off] > 0.f) ? v : 0.f;   // the producer's ReLU, looking backward
                 if (decltype(nt_mode)::value) __builtin_nontemporal_store(v, op);   // output larger than the Infinity Cache: stream it
                 else *op = v;
@@ -1481,11 +1503,27 @@ extern "C" int dm_conv_pack_weight_batch(const dm_pack_job* jobs_device, int num
   return dm_check_launch();
 }
 
+// (K31) the gather of dm_conv2d_up_add_fwd's addend: [NB, Cout, Hs, Ws] read at (iy[y], ix[x])
+struct UpAdd {
+  int Hs, Ws;
+  const int* iy;
+  const int* ix;
+};
+
+// One launch of `a` with the epilogue the call asks for: plain, the post-activation addend (K26) or the gathered one (K31)
+template <int KS, int WGM, int WGN, int WM, int WN, int CK>
+static int launch_conv_post(ConvArgs& a, hipStream_t st) {
+  if (!a.addend) return launch_conv<KS, WGM, WGN, WM, WN, CK>(a, st);
+  if (a.up_iy) return launch_conv<KS, WGM, WGN, WM, WN, CK, 0, 0, 2>(a, st);
+  return launch_conv<KS, WGM, WGN, WM, WN, CK, 0, 0, 1>(a, st);
+}
+
 static int conv2d_launch(const float* const* srcs, const int* src_channels, const long long* src_batch_strides,
                          int num_srcs, int NB, int H, int W,
                          const float* w_packed, const float* bias, int Cout, int ksize, int relu, float* out,
                          int out_ch_total, int out_ch_offset, const float* mask, dm_stream_t stream, float* ws = nullptr,
-                         long long ws_floats = 0, const float* addend = nullptr, ConvPlan* plan = nullptr) {
+                         long long ws_floats = 0, const float* addend = nullptr, ConvPlan* plan = nullptr,
+                         const UpAdd* up = nullptr) {
   if (mask && (relu & 16)) return DM_ERR_UNSUPPORTED;      // (no bf16x3 build of the data-gradient launches)
   if (!srcs || !src_channels || num_srcs < 1 || num_srcs > DM_MAX_SOURCES || !w_packed || !out) return DM_ERR_INVALID_ARG;
   if (NB < 0 || H <= 0 || W <= 0 || Cout <= 0 || (ksize != 1 && ksize != 3)) return DM_ERR_INVALID_ARG;
@@ -1512,6 +1550,12 @@ static int conv2d_launch(const float* const* srcs, const int* src_channels, cons
     a.addend = addend;
     a.relu = relu & 1;
     a.ws = nullptr;
+    if (up) {
+      a.up_iy = up->iy;
+      a.up_ix = up->ix;
+      a.up_Ws = up->Ws;
+      a.up_plane = up->Hs * up->Ws;
+    }
   }
   if (bf16x3) {
     // one build per kernel size: 64 couts x 128 pixels, four waves of 32 x 64 (see the kernel's header); a workspace
@@ -1586,15 +1630,15 @@ static int conv2d_launch(const float* const* srcs, const int* src_channels, cons
     const int small_wgs = small_env >= 0 ? small_env : (5 * dm_num_cus()) / 4;
     // (the POST builds take the tiles the plain launch of the shape takes: the same products in the same order)
     if (!(relu & 2) && !mask && dm_ceil_div(a.CoutP, 128) * dm_ceil_div(a.Q, 128) <= small_wgs)
-      return addend ? launch_conv<1, 4, 1, 1, 1, 32, 0, 0, 1>(a, st) : launch_conv<1, 4, 1, 1, 1, 32>(a, st);
-    return addend ? launch_conv<1, 2, 2, 2, 2, 16, 0, 0, 1>(a, st) : launch_conv<1, 2, 2, 2, 2, 16>(a, st);
+      return launch_conv_post<1, 4, 1, 1, 1, 32>(a, st);
+    return launch_conv_post<1, 2, 2, 2, 2, 16>(a, st);
   }
   if (Cout > 32) {
     // 64 couts x 128 px as 4 waves of 32 x 64: 0.437 -> 0.379 ms on 576 -> 64 @56^2 x 128 RoIs, 0.098 -> 0.089 ms on
     // 64 -> 64 x 256 (the other tilings tried: docs/HISTORY.md, round 3); one k order per output.
-    return addend ? launch_conv<1, 2, 2, 1, 2, 16, 0, 0, 1>(a, st) : launch_conv<1, 2, 2, 1, 2, 16>(a, st);
+    return launch_conv_post<1, 2, 2, 1, 2, 16>(a, st);
   }
-  return addend ? launch_conv<1, 1, 4, 1, 1, 32, 0, 0, 1>(a, st) : launch_conv<1, 1, 4, 1, 1, 32>(a, st);
+  return launch_conv_post<1, 1, 4, 1, 1, 32>(a, st);
 }
 
 extern "C" int dm_conv2d_fwd(const float* const* srcs, const int* src_channels, const long long* src_batch_strides,
@@ -1648,6 +1692,20 @@ extern "C" int dm_conv2d_post_add_fwd(const float* const* srcs, const int* src_c
   if (!addend) return DM_ERR_INVALID_ARG;
   return conv2d_launch(srcs, src_channels, src_batch_strides, num_srcs, NB, H, W, w_packed, bias, Cout, ksize, relu, out,
                        out_ch_total, out_ch_offset, nullptr, stream, nullptr, 0, addend);
+}
+
+// (K31) out = addend[n, c, iy[y], ix[x]] + act(conv1x1(srcs) + bias): the POST epilogue with the addend gathered from a
+// dense [NB, Cout, Hs, Ws] map of its own through two device index tables (FPN's top-down merge inside the lateral conv).
+// The launch is the plain launch's, as K26's: same tiles, same products in the same order, one more fp32 add.
+extern "C" int dm_conv2d_up_add_fwd(const float* const* srcs, const int* src_channels, const long long* src_batch_strides,
+                                    int num_srcs, int NB, int H, int W, const float* w_packed, const float* bias, int Cout,
+                                    int ksize, int relu, const float* addend, int Hs, int Ws, const int32_t* iy, const int32_t* ix,
+                                    float* out, int out_ch_total, int out_ch_offset, dm_stream_t stream) {
+  if (!addend || !iy || !ix || Hs <= 0 || Ws <= 0) return DM_ERR_INVALID_ARG;
+  if ((long long)Hs * Ws > 0x7fffffffLL) return DM_ERR_INVALID_ARG;
+  const UpAdd up = {Hs, Ws, iy, ix};
+  return conv2d_launch(srcs, src_channels, src_batch_strides, num_srcs, NB, H, W, w_packed, bias, Cout, ksize, relu, out,
+                       out_ch_total, out_ch_offset, nullptr, stream, nullptr, 0, addend, nullptr, &up);
 }
 
 // (added to ABI 28) What dm_conv2d_fwd / _ws / _masked / dm_conv2d_post_add_fwd would launch for these host arguments: the

@@ -1306,3 +1306,30 @@ extern "C" int dm_global_avg_pool_fwd(const float* x, int N, int C, int HW, floa
   DM_LAUNCH(global_avg_pool_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, rows, HW, out);
   return dm_check_launch();
 }
+
+// (K31) FPN's extra levels without extra convs: F.max_pool2d(x, 1, stride=2) = every second row and column.  One output
+// per thread in the flat order of out (consecutive lanes store consecutive addresses), a grid-stride loop over the rest.
+namespace {
+__global__ __launch_bounds__(256) void subsample2_kernel(const float* __restrict__ in, long long total, int H, int W, int OH,
+                                                         int OW, float* __restrict__ out) {
+  const long long step = (long long)gridDim.x * 256;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += step) {
+    const long long row = i / OW;            // nc * OH + y
+    const int x = (int)(i - row * OW);
+    const long long nc = row / OH;
+    const int y = (int)(row - nc * OH);
+    out[i] = in[(nc * H + 2 * y) * W + 2 * x];      // 2 y <= H - 1 and 2 x <= W - 1: OH = ceil(H / 2), OW = ceil(W / 2)
+  }
+}
+}  // namespace
+
+extern "C" int dm_subsample2_fwd(const float* in, long long NC, int H, int W, float* out, dm_stream_t stream) {
+  if (NC < 0 || H <= 0 || W <= 0) return DM_ERR_INVALID_ARG;
+  if (NC == 0) return DM_OK;
+  if (!in || !out) return DM_ERR_INVALID_ARG;
+  const int OH = (H + 1) / 2, OW = (W + 1) / 2;
+  const long long total = NC * OH * OW;
+  const int blocks = (int)min((long long)dm_ceil_div(total, 256), 16384LL);
+  DM_LAUNCH(subsample2_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, in, total, H, W, OH, OW, out);
+  return dm_check_launch();
+}

@@ -2621,6 +2621,61 @@ def conv1x1_post_add(srcs, w_packed, bias, cout, addend, relu=True, out=None):
     return out
 
 
+# ------------------------------------------------------------------ FPN neck (dynamask_hip.h section K31)
+def conv2d_up_add(srcs, w_packed, bias, cout, addend, iy, ix, relu=False, out=None):
+    """``out[n, c, y, x] = addend[n, c, iy[y], ix[x]] + act(conv1x1(cat(srcs)) + bias)`` (dm_conv2d_up_add_fwd): FPN's
+    top-down merge inside the lateral convolution.  ``addend`` [NB, cout, Hs, Ws]; ``iy`` [H] / ``ix`` [W]: device int32
+    tables with values in [0, Hs) / [0, Ws) (``necks.nearest_index``; the values are not checked).  Exact fp32 whatever the
+    inference precision: the bits of ``conv2d(ksize=1)`` followed by an fp32 add of the gathered addend."""
+    if isinstance(srcs, torch.Tensor):
+        srcs = [srcs]
+    srcs = [_chk_src(s) for s in srcs]
+    _chk(w_packed, 'w_packed')
+    _chk(addend, 'addend')
+    _chk(iy, 'iy', torch.int32)
+    _chk(ix, 'ix', torch.int32)
+    if bias is not None:
+        _chk(bias, 'bias')
+    NB, _, H, W = srcs[0].shape
+    for s in srcs:
+        assert s.shape[0] == NB and s.shape[2] == H and s.shape[3] == W
+    if conv_layout(w_packed) != 'fp32':
+        raise ValueError('conv2d_up_add: exact fp32 only (weights packed for bf16x3)')
+    assert w_packed.numel() == packed_floats(cout, 1, [s.shape[1] for s in srcs]), 'weights packed for other sources'
+    if addend.dim() != 4 or tuple(addend.shape[:2]) != (NB, cout) or addend.shape[2] < 1 or addend.shape[3] < 1:
+        raise ValueError(f'addend: [{NB}, {cout}, Hs, Ws] expected, got {list(addend.shape)}')
+    if tuple(iy.shape) != (H,) or tuple(ix.shape) != (W,):
+        raise ValueError(f'iy [{H}] and ix [{W}] expected, got {list(iy.shape)} and {list(ix.shape)}')
+    if out is None:
+        out = torch.empty((NB, cout, H, W), device=srcs[0].device, dtype=torch.float32)
+    else:
+        _chk(out, 'out')
+        assert tuple(out.shape) == (NB, cout, H, W)
+        if out.data_ptr() == addend.data_ptr():
+            raise ValueError('conv2d_up_add: out may not be the addend')
+    strides = (ctypes.c_longlong * len(srcs))(*[int(s.stride(0)) for s in srcs])
+    check(lib().dm_conv2d_up_add_fwd(_ptr_array(srcs), _int_array([s.shape[1] for s in srcs]), strides, len(srcs), NB, H, W,
+                                     _p(w_packed), _p(bias), cout, 1, 1 if relu else 0, _p(addend), addend.shape[2],
+                                     addend.shape[3], _p(iy), _p(ix), _p(out), cout, 0, _stream()), 'dm_conv2d_up_add_fwd')
+    return out
+
+
+def subsample2(x, out=None):
+    """``x[:, :, ::2, ::2]`` as a dense tensor = ``F.max_pool2d(x, 1, stride=2)`` (dm_subsample2_fwd)."""
+    _chk(x, 'x')
+    N, C, H, W = x.shape
+    if H < 1 or W < 1:
+        raise ValueError(f'subsample2: an empty map {list(x.shape)}')
+    shape = (N, C, (H + 1) // 2, (W + 1) // 2)
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=torch.float32)
+    else:
+        _chk(out, 'out')
+        assert tuple(out.shape) == shape
+    check(lib().dm_subsample2_fwd(_p(x), N * C, H, W, _p(out), _stream()), 'dm_subsample2_fwd')
+    return out
+
+
 def roi_align_pool(size, out_size):
     """The pooling that joins ``size`` x ``size`` RoIAlign bins to ``out_size`` x ``out_size`` features in
     ``roi_align_add_``: 1 (identity) or 2 (the exact 2 x 2 mean = ``adaptive_avg_pool2d`` size -> size / 2)."""

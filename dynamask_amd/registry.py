@@ -75,6 +75,7 @@ LOSSES = Registry('loss')
 ROI_LAYERS = Registry('roi_layer')       # stands in for getattr(mmcv.ops, type) (base_roi_extractor.py:49-55)
 UPSAMPLE_LAYERS = Registry('upsample')   # stands in for mmcv's build_upsample_layer
 ANCHOR_GENERATORS = Registry('anchor generator')   # mmdet/core/anchor/builder.py
+NECKS = Registry('neck')
 
 
 def build(cfg, registry, default_args=None):
@@ -93,6 +94,10 @@ def build_head(cfg):
 
 def build_loss(cfg):
     return build(cfg, LOSSES)
+
+
+def build_neck(cfg):
+    return build(cfg, NECKS)
 
 
 def build_anchor_generator(cfg, default_args=None):

@@ -62,7 +62,8 @@ const char* dm_error_string(int code);
  * GroupNorm, neighbour fusion, grouped 4x4 stride-2 deconvolution and box vote (section K27); the convolution launcher's
  * own report of its launches, dm_conv2d_plan (section K5/K6) and dm_conv2d_group_plan (section K25); Double-Head R-CNN's
  * rescaled RoIAlign and global average pool (section K28); the DCN forward launcher's route, dm_deform_conv_plan
- * (section K8); the weight-gradient launcher's route, dm_conv2d_wgrad_plan. */
+ * (section K8); the weight-gradient launcher's route, dm_conv2d_wgrad_plan; RPN inference's selection, decode and merge
+ * (section K30); the FPN neck's gathered addend and stride-2 subsample (section K31). */
 #define DM_ABI_VERSION 29 /* the one definition: dm_abi_version(), dm_build_info() and _lib.ABI_VERSION read it */
 int dm_abi_version(void);
 /* "libdynamask_hip abi=N arch=gfx950 compiler=<clang version> flags=<the product-wide flags of dynamask_amd/build.py>"
@@ -1315,6 +1316,31 @@ int dm_rpn_merge_supported(int num_images, int num_levels, int max_rows, int nms
 int dm_rpn_merge(const long long* seg_tab, int num_images, int num_levels, int max_rows, const int32_t* keep,
                  const int32_t* kept, const float* boxes, const float* score, int nms_post, float* out, int32_t* counts,
                  dm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * K31  FPN neck inference (mmdet/models/necks/fpn.py:164-216).  The lateral 1x1 convolutions are dm_conv2d_fwd launches
+ *      (any Cin), the 3x3 level convolutions dm_conv2d_fwd / dm_conv3x3_dil_fwd (any width), the extra stride-2 ones
+ *      dm_conv3x3_s2_fwd; these two entry points are what the neck adds.  Exact fp32, deterministic, no atomics.
+ *
+ * dm_conv2d_up_add_fwd: out[n, c, y, x] = addend[n, c, iy[y], ix[x]] + act(conv1x1(srcs) + bias) -- the top-down merge
+ * laterals[i - 1] += F.interpolate(laterals[i], mode='nearest') (fpn.py:177-186) inside the lateral convolution of level
+ * i - 1: the merged lateral is written once and the upsampled map never exists.  addend: a dense [NB, Cout, Hs, Ws]
+ * tensor (the merged lateral above); iy [H] and ix [W]: DEVICE int32 tables with values in [0, Hs) and [0, Ws) -- the
+ * source row / column of every output row / column (not checked on the device: a value outside reads outside addend).
+ * addend may not overlap out.  Everything else as dm_conv2d_post_add_fwd: exact fp32 only, ksize == 1 only (3 and the
+ * bf16x3 layout: DM_ERR_UNSUPPORTED), relu bit 0 only (any other bit DM_ERR_INVALID_ARG), no workspace and no K split,
+ * and the tile build the plain launch of the shape takes (dm_conv2d_plan with has_addend reports it: POST 1 there stands
+ * for either addend form).  Every output has the bits of dm_conv2d_fwd followed by one fp32 add of the gathered addend.
+ * Hs, Ws <= 0, Hs * Ws >= 2^31 or a null addend / table: DM_ERR_INVALID_ARG.  NB == 0 enqueues nothing.
+ *
+ * dm_subsample2_fwd: out[nc, y, x] = in[nc, 2 y, 2 x], out [NC, ceil(H / 2), ceil(W / 2)] -- F.max_pool2d(x, 1, stride=2),
+ * FPN's extra levels without extra convolutions (fpn.py:197-199).  Any H, W >= 1; NC == 0 enqueues nothing.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int dm_conv2d_up_add_fwd(const float* const* srcs, const int* src_channels, const long long* src_batch_strides,
+                         int num_srcs, int NB, int H, int W, const float* w_packed, const float* bias, int Cout,
+                         int ksize, int relu, const float* addend, int Hs, int Ws, const int32_t* iy, const int32_t* ix,
+                         float* out, int out_ch_total, int out_ch_offset, dm_stream_t stream);
+int dm_subsample2_fwd(const float* in, long long NC, int H, int W, float* out, dm_stream_t stream);
 
 #ifdef __cplusplus
 }
