@@ -28,7 +28,7 @@ __device__ __forceinline__ float wsum(float v) {
 // ----------------------------------------------------------------- elementwise
 __global__ __launch_bounds__(256) void relu_bwd_kernel(float* __restrict__ g, const float* __restrict__ y, size_t n) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    if (!(y[i] > 0.f)) g[i] = 0.f;
+    if (y[i] <= 0.f) g[i] = 0.f;
 }
 
 // 16 bytes per lane (both pointers 16-byte aligned, n % 4 == 0): the mask pass is pure streaming
@@ -38,7 +38,7 @@ __global__ __launch_bounds__(256) void relu_bwd4_kernel(dm_f32x4* __restrict__ g
     dm_f32x4 v = g[i];
 #pragma unroll
     for (int e = 0; e < 4; ++e)
-      if (!(m[e] > 0.f)) v[e] = 0.f;
+      if (m[e] <= 0.f) v[e] = 0.f;
     g[i] = v;
   }
 }
@@ -769,7 +769,7 @@ __global__ __launch_bounds__(256) void upsample2x_bwd_kernel(const float* __rest
   const float rw = ac ? (OW > 1 ? (float)(W - 1) / (float)(OW - 1) : 0.f) : 0.5f;
   for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
     float g = gout[idx];
-    if (yout && !(yout[idx] > 0.f)) g = 0.f;
+    if (yout && yout[idx] <= 0.f) g = 0.f;
     if (g == 0.f) continue;
     const int ox = (int)(idx % OW);
     const int oy = (int)((idx / OW) % OH);
@@ -830,7 +830,7 @@ __global__ __launch_bounds__(256) void upsample2x_bwd_gather_kernel(const float*
         const int ox = 2 * x - 1 + b;
         if (wx[b] == 0.f) continue;
         float v = g[oy * OW + ox];
-        if (m && !(m[oy * OW + ox] > 0.f)) v = 0.f;
+        if (m && m[oy * OW + ox] <= 0.f) v = 0.f;
         row += wx[b] * v;
       }
       acc += wy[a] * row;
@@ -856,7 +856,7 @@ __global__ __launch_bounds__(256) void upsample2x_bwd_lds_kernel(const float* __
         const dm_f32x4 m = m4[i];
 #pragma unroll
         for (int e = 0; e < 4; ++e)
-          if (!(m[e] > 0.f)) v[e] = 0.f;
+          if (m[e] <= 0.f) v[e] = 0.f;
       }
       reinterpret_cast<dm_f32x4*>(plane)[i] = v;
     }
@@ -912,7 +912,7 @@ __global__ __launch_bounds__(NT) void upsample2x_bwd_ac_lds_kernel(const float* 
         const dm_f32x4 m = m4[i];
 #pragma unroll
         for (int e = 0; e < 4; ++e)
-          if (!(m[e] > 0.f)) v[e] = 0.f;
+          if (m[e] <= 0.f) v[e] = 0.f;
       }
       reinterpret_cast<dm_f32x4*>(plane)[i] = v;
     }

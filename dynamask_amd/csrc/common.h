@@ -125,5 +125,19 @@ __device__ __forceinline__ void dm_acc_add(float* base, size_t idx, float v, boo
 // (dm_merge_aug_masks): one expression, so that a merged probability is bit for bit what the paste computes from the logit.
 __device__ __forceinline__ float dm_sigmoid(float t) { return 1.f / (1.f + expf(-t)); }
 
+// ReLU as torch.relu computes it: NaN stays NaN (fmaxf(v, 0.f) returns its non-NaN operand, so it erased a NaN born in
+// the accumulation), -0 stays -0, every other value is fmaxf's.  A compare and a select: as many instructions as the
+// two v_max_f32 it replaces.  Every fused ReLU of the library is this one expression (the fused launches promise the bits
+// of the unfused sequences).
+__device__ __forceinline__ float dm_relu(float v) { return v < 0.f ? 0.f : v; }
+
+// The ReLU looking backward, autograd's threshold_backward: the gradient g is zeroed where the forward output y <= 0, so it
+// passes at y = NaN (the forward's NaN is already in every product g meets further down).
+__device__ __forceinline__ float dm_relu_mask(float y, float g) { return y <= 0.f ? 0.f : g; }
+
+// Running maximum of a pooling window in torch's max_pool2d order: a later element replaces the maximum when it is larger
+// or NaN, and a NaN stays (the rule of dm_mask_iou_input, csrc/conv_strided.hip).
+__device__ __forceinline__ bool dm_pool_takes(float v, float best) { return v > best || v != v; }
+
 typedef float dm_f32x16 __attribute__((ext_vector_type(16)));
 typedef float dm_f32x4 __attribute__((ext_vector_type(4)));

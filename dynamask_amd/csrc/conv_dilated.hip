@@ -194,7 +194,7 @@ __global__ __launch_bounds__(DM_CONV_NT) void conv3x3_dil_kernel(DilArgs a) {
 #pragma unroll
           for (int j = 0; j < WN; ++j) {
             float t = acc[i][j][r] + bv_;
-            if (a.flags & DIL_RELU) t = fmaxf(t, 0.f);
+            if (a.flags & DIL_RELU) t = dm_relu(t);
             if (b == 0) sum[NBR > 1 ? i : 0][NBR > 1 ? j : 0][r] = t;
             else sum[NBR > 1 ? i : 0][NBR > 1 ? j : 0][r] += t;
           }
@@ -219,7 +219,7 @@ __global__ __launch_bounds__(DM_CONV_NT) void conv3x3_dil_kernel(DilArgs a) {
         float v;
         if (NBR == 1) {
           v = acc[i][j][r] + bv_;
-          if (relu) v = fmaxf(v, 0.f);
+          if (relu) v = dm_relu(v);
         } else {
           v = sum[NBR > 1 ? i : 0][NBR > 1 ? j : 0][r];
         }

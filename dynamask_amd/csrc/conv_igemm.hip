@@ -835,10 +835,10 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
                 float* op = pj[j] + o;
                 float v = acc[i][j][r] + b;
                 if (decltype(acc_mode)::value) v += *op;          // accumulate into the destination (gradient sums)
-                if (relu) v = fmaxf(v, 0.f);
+                if (relu) v = dm_relu(v);
                 if (POST == 2) v = aj[j][ao] + v;                 // (a map of its own: it never is out)
                 else if (POST) v = op[add_off] + v;               // (read before this thread's own store: out may be the addend)
-                if (decltype(mask_mode)::value) v = (op[mask_off] > 0.f) ? v : 0.f;   // the producer's ReLU, looking backward
+                if (decltype(mask_mode)::value) v = dm_relu_mask(op[mask_off], v);   // the producer's ReLU, looking backward
                 if (decltype(nt_mode)::value) __builtin_nontemporal_store(v, op);   // output larger than the Infinity Cache: stream it
                 else *op = v;
               }
@@ -884,7 +884,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
           for (int j = 0; j < WN; ++j) {
             if (col_ok[j]) {
               float v = acc[i][j][r] + b;
-              if (e_relu & 1) v = fmaxf(v, 0.f);
+              if (e_relu & 1) v = dm_relu(v);
               e_out[(((size_t)col_n[j] * a.shuffle + oc) * (2 * H) + 2 * sy[j] + dy) * (2 * W) + 2 * sx[j] + dx] = v;
             }
           }
@@ -904,8 +904,8 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
           if (e_bias) v += e_bias[co];
           float* op = e_out + ((size_t)col_n[j] * e_oct + e_oco + co) * HW + col_p[j];
           if (e_relu & 2) v += *op;
-          if (e_relu & 1) v = fmaxf(v, 0.f);
-          if (e_mask && !(e_mask[op - e_out] > 0.f)) v = 0.f;
+          if (e_relu & 1) v = dm_relu(v);
+          if (e_mask) v = dm_relu_mask(e_mask[op - e_out], v);
           *op = v;
         }
       }
@@ -1097,10 +1097,10 @@ __device__ __forceinline__ void splitk_reduce_body(const float* __restrict__ ws,
         const float4 w = *op;
         v.x += w.x; v.y += w.y; v.z += w.z; v.w += w.w;
       }
-      if (flags & 1) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+      if (flags & 1) { v.x = dm_relu(v.x); v.y = dm_relu(v.y); v.z = dm_relu(v.z); v.w = dm_relu(v.w); }
       if (mask) {
         const float4 m = reinterpret_cast<const float4*>(mask)[o4];
-        v.x = (m.x > 0.f) ? v.x : 0.f; v.y = (m.y > 0.f) ? v.y : 0.f; v.z = (m.z > 0.f) ? v.z : 0.f; v.w = (m.w > 0.f) ? v.w : 0.f;
+        v.x = dm_relu_mask(m.x, v.x); v.y = dm_relu_mask(m.y, v.y); v.z = dm_relu_mask(m.z, v.z); v.w = dm_relu_mask(m.w, v.w);
       }
       *op = v;
     }
@@ -1116,8 +1116,8 @@ __device__ __forceinline__ void splitk_reduce_body(const float* __restrict__ ws,
     if (bias) v += bias[co];
     const size_t o = ((size_t)n * out_ch_total + out_ch_offset + co) * HW + p;
     if (flags & 2) v += out[o];
-    if (flags & 1) v = fmaxf(v, 0.f);
-    if (mask) v = (mask[o] > 0.f) ? v : 0.f;
+    if (flags & 1) v = dm_relu(v);
+    if (mask) v = dm_relu_mask(mask[o], v);
     out[o] = v;
   }
 }

@@ -146,7 +146,7 @@ __global__ __launch_bounds__(DM_CONV_NT) void conv3x3_s2_kernel(S2Args a) {
       const size_t o = ((size_t)n * a.Cout + co) * HoWo + r_pix;
       if (a.splits == 1) {
         float v = acc[i][0][r] + (a.bias ? a.bias[co] : 0.f);
-        if (relu) v = fmaxf(v, 0.f);
+        if (relu) v = dm_relu(v);
         a.out[o] = v;
       } else {
         a.ws[(size_t)split * plane_stride + o] = acc[i][0][r];
@@ -162,7 +162,7 @@ __global__ __launch_bounds__(256) void conv3x3_s2_reduce_kernel(const float* __r
     float v = ws[e];
     for (int s = 1; s < splits; ++s) v += ws[(size_t)s * total + e];
     if (bias) v += bias[(e / HoWo) % Cout];
-    if (relu) v = fmaxf(v, 0.f);
+    if (relu) v = dm_relu(v);
     out[e] = v;
   }
 }

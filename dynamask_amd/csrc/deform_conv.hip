@@ -307,7 +307,7 @@ __global__ __launch_bounds__(WGM* WGN * 64) void deform_conv_kernel(DcnArgs a) {
           for (int j = 0; j < WN; ++j) {
             if (col_ok[j]) {
               float v = acc[i][j][r];
-              if (relu) v = fmaxf(v, 0.f);
+              if (relu) v = dm_relu(v);
               pj[j][o] = v;
             }
           }
@@ -599,7 +599,7 @@ __global__ __launch_bounds__(256, 2) void deform_conv_lds_kernel(DcnArgs a) {
           for (int j = 0; j < 2; ++j)
             if (col_ok[j]) {
               float v = acc[i][j][r];
-              if (relu) v = fmaxf(v, 0.f);
+              if (relu) v = dm_relu(v);
               pj[j][o] = v;
             }
         }
@@ -863,7 +863,7 @@ __global__ __launch_bounds__(256, 2) void deform_conv_c256_kernel(DcnArgs a) {
           for (int j = 0; j < 2; ++j)
             if (col_ok[j]) {
               float v = acc[i][j][r];
-              if (relu) v = fmaxf(v, 0.f);
+              if (relu) v = dm_relu(v);
               pj[j][o] = v;
             }
         }
@@ -1141,7 +1141,7 @@ __global__ __launch_bounds__(256, 2) void deform_conv_band_kernel(DcnArgs a, int
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int kb = i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-        const float b = fmaxf(acc[i][r], 0.f);
+        const float b = dm_relu(acc[i][r]);
 #pragma unroll
         for (int t = 0; t < MT2; ++t)
           if (t * 32 < ld2) acc2[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(w2t[kb * ld2 + t * 32 + l31], b, acc2[t], 0, 0, 0);
@@ -1154,7 +1154,7 @@ __global__ __launch_bounds__(256, 2) void deform_conv_band_kernel(DcnArgs a, int
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int co = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-          if (co < a.M2) po2[(size_t)co * HW] = fmaxf(acc2[t][r] + a.b2[co], 0.f);
+          if (co < a.M2) po2[(size_t)co * HW] = dm_relu(acc2[t][r] + a.b2[co]);
         }
     }
     if (!a.store_out) return;
@@ -1172,7 +1172,7 @@ __global__ __launch_bounds__(256, 2) void deform_conv_band_kernel(DcnArgs a, int
           const int co = (wave_m * WM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
           if (co < a.Cout) {
             float v = acc[i][r];
-            if (relu) v = fmaxf(v, 0.f);
+            if (relu) v = dm_relu(v);
             po[(size_t)co * HW] = v;
           }
         }
@@ -1197,7 +1197,7 @@ __global__ __launch_bounds__(256) void dcn_splitk_reduce_kernel(const float* __r
         const float4 w = ws4[(size_t)s_ * stride4 + e];
         v.x += w.x; v.y += w.y; v.z += w.z; v.w += w.w;
       }
-      if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+      if (relu) { v.x = dm_relu(v.x); v.y = dm_relu(v.y); v.z = dm_relu(v.z); v.w = dm_relu(v.w); }
       out4[e] = v;
     }
     return;
@@ -1205,7 +1205,7 @@ __global__ __launch_bounds__(256) void dcn_splitk_reduce_kernel(const float* __r
   for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
     float v = ws[e];
     for (int s_ = 1; s_ < splits; ++s_) v += ws[(size_t)s_ * stride + e];
-    out[e] = relu ? fmaxf(v, 0.f) : v;
+    out[e] = relu ? dm_relu(v) : v;
   }
 }
 

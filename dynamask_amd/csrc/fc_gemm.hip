@@ -123,7 +123,7 @@ __global__ __launch_bounds__(256) void fc_gemm_kernel(FcArgs a) {
         for (int j = 0; j < 2; ++j) {
           if (m_ok[j]) {
             float v = acc[i][j][r] + bj[j];
-            if (single && relu) v = fmaxf(v, 0.f);
+            if (single && relu) v = dm_relu(v);
             pj[j][o] = v;
           }
         }
@@ -146,14 +146,14 @@ __global__ __launch_bounds__(256) void fc_reduce_kernel(const float* __restrict_
         const int m = (int)(i % M);
         v[0] += bias[m]; v[1] += bias[m + 1]; v[2] += bias[m + 2]; v[3] += bias[m + 3];
       }
-      if (relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
+      if (relu) { v[0] = dm_relu(v[0]); v[1] = dm_relu(v[1]); v[2] = dm_relu(v[2]); v[3] = dm_relu(v[3]); }
       *reinterpret_cast<dm_f32x4*>(out + i) = v;
     } else {
       for (size_t e = i; e < NM && e < i + 4; ++e) {
         float v = part[e];
         for (int s = 1; s < splits; ++s) v += part[(size_t)s * NM + e];
         if (bias) v += bias[e % M];
-        out[e] = relu ? fmaxf(v, 0.f) : v;
+        out[e] = relu ? dm_relu(v) : v;
       }
     }
   }

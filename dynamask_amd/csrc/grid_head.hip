@@ -56,7 +56,7 @@ __global__ __launch_bounds__(GH_NT) void group_norm_kernel(const float* x, int C
   for (int i = threadIdx.x; i < L; i += GH_NT) {
     const int c = g * cpg + i / HW;
     float v = ((xg[i] - x0) - m) * rstd * gamma[c] + beta[c];
-    if (relu) v = fmaxf(v, 0.f);
+    if (relu) v = dm_relu(v);
     yg[i] = v;
   }
 }

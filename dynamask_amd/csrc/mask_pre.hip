@@ -143,8 +143,8 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_kernel(const float* __res
       for (int dx = 0; dx < 3; ++dx) {
         const int xx = 2 * ox - 1 + dx;
         if (xx < 0 || xx >= W) continue;
-        const float v = fmaxf((p[y * W + xx] - m) * invstd * g + b, 0.f);
-        best = fmaxf(best, v);
+        const float v = dm_relu((p[y * W + xx] - m) * invstd * g + b);
+        if (dm_pool_takes(v, best)) best = v;
       }
     }
     out[idx] = best;
@@ -188,9 +188,11 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_rows_kernel(const float* 
     float best = -INFINITY;
 #pragma unroll
     for (int dy = 0; dy < 3; ++dy) {
-      best = fmaxf(best, fmaxf((left[k][dy] - m) * invstd * g + b, 0.f));
-      best = fmaxf(best, fmaxf((ab[k][dy].a - m) * invstd * g + b, 0.f));
-      best = fmaxf(best, fmaxf((ab[k][dy].b - m) * invstd * g + b, 0.f));
+      const float t[3] = {dm_relu((left[k][dy] - m) * invstd * g + b), dm_relu((ab[k][dy].a - m) * invstd * g + b),
+                          dm_relu((ab[k][dy].b - m) * invstd * g + b)};
+#pragma unroll
+      for (int e = 0; e < 3; ++e)
+        if (dm_pool_takes(t[e], best)) best = t[e];      // (a clamped tap repeats one of the window: a NaN among them stays)
     }
     const int o = o0 + k * 256;
     if (o < OHW) out[(size_t)nc * OHW + o] = best;
@@ -243,7 +245,8 @@ extern "C" int dm_bn_relu_maxpool_fwd(const float* x, int NB, int C, int H, int 
   return dm_check_launch();
 }
 
-// Which tap each pooled output took: the plane index (y * W + x) of the window's first maximum of z = relu(bn(x)),
+// Which tap each pooled output took: the plane index (y * W + x) of the window's first maximum of z = relu(bn(x)) -- of its
+// last NaN where it holds one (dm_pool_takes: max_pool2d's rule) --,
 // found with the expression and scan order of the backward kernels below.  Diagnostic: a test compares the
 // choices with the reference's max_pool2d(return_indices=True) and counts the windows (fp32 ties) that differ.
 namespace {
@@ -270,8 +273,8 @@ __global__ __launch_bounds__(256) void maxpool_argmax_kernel(const float* __rest
       for (int dx = 0; dx < 3; ++dx) {
         const int xx = 2 * ox - 1 + dx;
         if (xx < 0 || xx >= W) continue;
-        const float v = fmaxf((p[y * W + xx] - m) * invstd * g + b, 0.f);
-        if (v > best) {
+        const float v = dm_relu((p[y * W + xx] - m) * invstd * g + b);
+        if (dm_pool_takes(v, best)) {
           best = v;
           bi = y * W + xx;
         }
@@ -299,7 +302,7 @@ extern "C" int dm_bn_relu_maxpool_argmax(const float* x, int NB, int C, int H, i
 namespace {
 
 // scatter the pooled gradient to the window's first maximum of z = relu(bn(x))
-// (torch's max_pool2d keeps the first maximum in scan order); g_z is zero-filled
+// (torch's max_pool2d keeps the first maximum in scan order, or the last NaN); g_z is zero-filled
 // by the caller.  ReLU mask folded in: a zero maximum passes no gradient.
 __global__ __launch_bounds__(256) void maxpool_relu_bwd_kernel(const float* __restrict__ x, int NB, int C, int H, int W,
                                                                const float* __restrict__ mean, const float* __restrict__ var,
@@ -325,14 +328,14 @@ __global__ __launch_bounds__(256) void maxpool_relu_bwd_kernel(const float* __re
       for (int dx = 0; dx < 3; ++dx) {
         const int xx = 2 * ox - 1 + dx;
         if (xx < 0 || xx >= W) continue;
-        const float v = fmaxf((p[y * W + xx] - m) * invstd * g + b, 0.f);
-        if (v > best) {
+        const float v = dm_relu((p[y * W + xx] - m) * invstd * g + b);
+        if (dm_pool_takes(v, best)) {
           best = v;
           bi = y * W + xx;
         }
       }
     }
-    if (bi >= 0 && best > 0.f) atomicAdd(gz + (n * C + c) * (size_t)H * W + bi, gout[idx]);
+    if (bi >= 0 && !(best <= 0.f)) atomicAdd(gz + (n * C + c) * (size_t)H * W + bi, gout[idx]);
   }
 }
 
@@ -361,7 +364,7 @@ __global__ __launch_bounds__(256) void maxpool_relu_bwd_lds_kernel(const float* 
       const dm_f32x4 v = x4[i];
       dm_f32x4 z;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) z[e] = fmaxf((v[e] - m) * invstd * g + b, 0.f);      // the expression of the kernel above
+      for (int e = 0; e < 4; ++e) z[e] = dm_relu((v[e] - m) * invstd * g + b);      // the expression of the kernel above
       reinterpret_cast<dm_f32x4*>(zp)[i] = z;
     }
     __syncthreads();
@@ -378,13 +381,13 @@ __global__ __launch_bounds__(256) void maxpool_relu_bwd_lds_kernel(const float* 
           const int xx = 2 * ox - 1 + dx;
           if (xx < 0 || xx >= W) continue;
           const float v = zp[y * W + xx];
-          if (v > best) {
+          if (dm_pool_takes(v, best)) {
             best = v;
             bi = y * W + xx;
           }
         }
       }
-      argp[o] = best > 0.f ? bi : -1;          // a zero maximum passes no gradient (ReLU)
+      argp[o] = best <= 0.f ? -1 : bi;         // a zero maximum passes no gradient (ReLU); a NaN one does
       valp[o] = gout[(size_t)nc * OHW + o];
     }
     __syncthreads();
@@ -549,7 +552,7 @@ __global__ __launch_bounds__(256) void maxpool_relu_bwd_sums_kernel(const float*
   auto stage = [&](const dm_f32x4& v, int i) {
     dm_f32x4 z;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) z[e] = fmaxf((v[e] - m) * invstd * g + b, 0.f);      // the forward's expression (bn_relu_maxpool_kernel)
+    for (int e = 0; e < 4; ++e) z[e] = dm_relu((v[e] - m) * invstd * g + b);      // the forward's expression (bn_relu_maxpool_kernel)
     reinterpret_cast<dm_f32x4*>(zp)[i] = z;
   };
   auto window = [&](int o, float gval) {
@@ -565,13 +568,13 @@ __global__ __launch_bounds__(256) void maxpool_relu_bwd_sums_kernel(const float*
         const int xx = 2 * ox - 1 + dx;
         if (xx < 0 || xx >= W) continue;
         const float v = zp[y * W + xx];
-        if (v > best) {
+        if (dm_pool_takes(v, best)) {
           best = v;
           bi = y * W + xx;
         }
       }
     }
-    argp[o] = best > 0.f ? bi : -1;          // a zero maximum passes no gradient (ReLU)
+    argp[o] = best <= 0.f ? -1 : bi;         // a zero maximum passes no gradient (ReLU); a NaN one does
     valp[o] = gval;
   };
   if (pre && n0 < n1) fetch(n0);

@@ -168,7 +168,7 @@ __device__ __forceinline__ void dm_mlp_relu_store(const dm_f32x16 (&acc)[NI][NJ]
       for (int j = 0; j < NJ; ++j) {
         dm_f32x4 v;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = fmaxf(acc[i][j][4 * g + r] + bq[r], 0.f);
+        for (int r = 0; r < 4; ++r) v[r] = dm_relu(acc[i][j][4 * g + r] + bq[r]);
         lds[(co / 4) * DM_MLP_TP + (pj0 + j) * 32 + l31] = v;
       }
     }

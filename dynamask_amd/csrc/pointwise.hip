@@ -288,7 +288,7 @@ __global__ __launch_bounds__(256) void class_logits_up2x_kernel(const float* __r
         float lx = (e & 1) ? 0.25f : 0.75f;
         if (e == 0 && x0 == 0) lx = 0.f;
         const float hx = 1.f - lx;
-        const float r = fmaxf(dm_up2x_interp(hy, ly, hx, lx, v[ia][ja], v[ia][jb], v[ib][ja], v[ib][jb]), 0.f);
+        const float r = dm_relu(dm_up2x_interp(hy, ly, hx, lx, v[ia][ja], v[ia][jb], v[ib][ja], v[ib][jb]));
         acc[dy * 4 + e] += wci * r;
         acc[8 + dy * 4 + e] += wcd * r;
       }
@@ -363,7 +363,7 @@ __global__ __launch_bounds__(256) void upsample2x_kernel(const float* __restrict
       const int x1 = x0 + ((x0 < W - 1) ? 1 : 0);
       const float lx = sx - (float)x0, hx = 1.f - lx;
       float r = dm_up2x_interp(hy, ly, hx, lx, r0[x0], r0[x1], r1[x0], r1[x1]);
-      if (relu) r = fmaxf(r, 0.f);
+      if (relu) r = dm_relu(r);
       v[e] = r;
     }
     float* o = out + (nc * OH + oy) * (long long)OW + xq * 4;
@@ -483,7 +483,7 @@ __global__ __launch_bounds__(256) void upsample2x_half_kernel(const float* __res
         if (e == 0 && x0 == 0) lx = 0.f;                         // sx clamped to 0
         const float hx = 1.f - lx;
         float r = dm_up2x_interp(hy, ly, hx, lx, v[ia][ja], v[ia][jb], v[ib][ja], v[ib][jb]);
-        if (relu) r = fmaxf(r, 0.f);
+        if (relu) r = dm_relu(r);
         o[dy][e] = r;
       }
     }
@@ -700,7 +700,7 @@ __global__ __launch_bounds__(256) void detail_target_kernel(const float* __restr
         const int yy = y + dy, xx = x + dx;
         if (yy >= 0 && yy < S && xx >= 0 && xx < S) acc += ((dy == 0 && dx == 0) ? 8.f : -1.f) * m[(yy - r_lo) * S + xx];
       }
-    return fmaxf(acc, 0.f);
+    return dm_relu(acc);
   };
   const int S2 = (S - 1) / 2 + 1;  // stride-2 conv output size (pad 1, k 3)
   for (int i = y_begin * S + threadIdx.x; i < y_end * S; i += blockDim.x) {

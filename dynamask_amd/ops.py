@@ -891,7 +891,8 @@ class splitk_scope:
 
 def conv2d(srcs, w_packed, bias, cout, ksize, relu=False, out=None, out_ch_offset=0, accumulate=False, mask=None):
     """Fused concat(srcs) -> conv(ksize, same) -> +bias -> ReLU.  ``mask`` (same shape as ``out``): outputs where it
-    is not > 0 are stored as 0 -- the ReLU adjoint of a data gradient, fused into the epilogue."""
+    is <= 0 are stored as 0 -- the ReLU adjoint of a data gradient (threshold_backward: it passes at NaN), fused into the
+    epilogue."""
     if isinstance(srcs, torch.Tensor):
         srcs = [srcs]
     srcs = [_chk_src(s) for s in srcs]

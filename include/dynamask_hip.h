@@ -264,7 +264,7 @@ int dm_conv1x1_group_fwd(int count, const float* const* x, const int* Cin, const
                          dm_stream_t stream);
 
 /* dm_conv2d_fwd whose epilogue also applies a ReLU adjoint: outputs where `mask` (same layout, channel count and
- * channel offset as `out`) is not > 0 are stored as 0.  Used for data gradients: the mask is the activation the
+ * channel offset as `out`) is <= 0 are stored as 0 (autograd's threshold_backward: a NaN activation passes the gradient).  Used for data gradients: the mask is the activation the
  * gradient flows into, so the separate mask pass (read gradient + activation, write gradient) disappears.  Flag bit 4
  * (the bf16x3 mode) returns DM_ERR_UNSUPPORTED here, as it does on the DCN entry points: those stay exact fp32. */
 int dm_conv2d_fwd_masked(const float* const* srcs, const int* src_channels, const long long* src_batch_strides,
