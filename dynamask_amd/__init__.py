@@ -3,7 +3,8 @@
 Layout:
   csrc/                 HIP kernels + the C ABI (include/dynamask_hip.h)
   _lib.py, ops.py       ctypes binding of libdynamask_hip.so over torch device memory
-  registry.py           mmdet-style HEADS / NECKS / ROI_EXTRACTORS / LOSSES registries + Config
+  registry.py           mmdet-style BACKBONES / HEADS / NECKS / ROI_EXTRACTORS / LOSSES registries + Config
+  backbones.py          ResNet: the image -> the stages the neck reads
   necks.py              FPN: the backbone's stages -> the maps the RPN and the RoI heads read
   roi_extractors.py, mask_heads.py, losses.py, roi_head.py
                         host-side mirror of the reference's plugin classes
@@ -18,11 +19,17 @@ __version__ = '0.1.0'
 from .precision import conv_precision, get_conv_precision, set_conv_precision  # noqa: E402,F401
 
 
-def __getattr__(name):          # NECKS, build_neck, FPN: resolved on first use (necks.py imports the operator bindings)
+def __getattr__(name):          # NECKS, build_neck, FPN, BACKBONES, build_backbone, ResNet: resolved on first use (necks.py imports the operator bindings)
     if name in ('NECKS', 'build_neck'):
         from . import necks, registry  # noqa: F401  (necks registers FPN)
         return getattr(registry, name)
     if name == 'FPN':
         from . import necks
         return necks.FPN
+    if name in ('BACKBONES', 'build_backbone'):
+        from . import backbones, registry  # noqa: F401  (backbones registers ResNet)
+        return getattr(registry, name)
+    if name == 'ResNet':
+        from . import backbones
+        return backbones.ResNet
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

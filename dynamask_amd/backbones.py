@@ -1,0 +1,190 @@
+"""Backbones behind the reference's BACKBONES registry, at inference: ``ResNet`` (mmdet/models/backbones/resnet.py) --
+the image in, the stages the neck (or a C4 head) starts from out.
+
+The stem is two launches: ``ops.conv7x7_s2`` (``dm_conv7x7_s2_fwd``: conv1 with ``bn1`` folded in and the ReLU on) and
+``ops.maxpool3x3_s2``.  Every block is ``bbox_heads.Bottleneck``'s three launches with eval-mode BatchNorm folded into
+weights and bias (``bbox_heads.fold_bn``: float64, rounded once): block 0 of a stage closes with ONE two-source 1x1
+convolution of [conv2 output, identity input] into a new tensor, the blocks behind it run in place on that tensor.  A
+stride of 2 sits, with ``style='caffe'``, in the two 1x1 convolutions of block 0 -- the block runs on
+``ops.subsample2(x)`` -- and, with ``style='pytorch'``, in conv2 (``ops.conv3x3_s2``), the identity input of the closing
+launch being ``ops.subsample2(x)``.  The stride-1 3x3 convolutions are ``ops.conv2d`` launches, ``ops.conv3x3_dil`` at
+dilation 1 on maps wider than ``dense_heads.CONV2D_3X3_MAX_WIDTH``: the width alone decides.  Every launch is exact fp32 in
+every precision mode and none splits its K loop, so an image's bits do not depend on the other images of the call.  The
+host never waits; the image is not written."""
+import torch
+import torch.nn as nn
+
+from . import ops
+from .bbox_heads import Bottleneck, _conv_weight, _FoldedConv
+from .dense_heads import CONV2D_3X3_MAX_WIDTH
+from .registry import BACKBONES
+from .roi_head import _BN
+
+# backbones/resnet.py:356-362 (ResNet.arch_settings): depth -> blocks per stage; 18 / 34 are BasicBlock nets
+_STAGE_BLOCKS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}
+_BASIC_BLOCK_DEPTHS = (18, 34)
+
+
+class _FoldedStem(_FoldedConv):
+    """conv1 + bn1 folded, in ``ops.conv7x7_s2``'s layout."""
+
+    def packed(self):
+        def make():
+            w, b = self.folded()
+            return ops.pack_conv7x7_weight(w), b
+        return self._pk.get_multi('pack7', self._tensors(), make)
+
+
+@BACKBONES.register_module()
+class ResNet(nn.Module):
+    """``ResNet`` -- backbones/resnet.py:303-639, inference.  ``state_dict`` keys as the reference's: ``conv1.weight``,
+    ``bn1.*``, ``layer{1..4}.{i}.conv{1,2,3}.weight``, ``.bn{1,2,3}.*``, ``.downsample.{0,1}.*``.  The Bottleneck depths
+    (50 / 101 / 152) in both styles are built; BasicBlock depths, ``deep_stem``, ``avg_down``, DCN stages, plugins,
+    ``conv_cfg``, norms other than BN, dilations and training are not.  BatchNorm is always evaluated from its running
+    statistics: ``train()``, ``norm_eval`` and ``frozen_stages`` are kept (the latter also clears ``requires_grad`` as the
+    reference does) and change nothing in ``forward``."""
+
+    def __init__(self, depth, in_channels=3, stem_channels=None, base_channels=64, num_stages=4, strides=(1, 2, 2, 2),
+                 dilations=(1, 1, 1, 1), out_indices=(0, 1, 2, 3), style='pytorch', deep_stem=False, avg_down=False,
+                 frozen_stages=-1, conv_cfg=None, norm_cfg=dict(type='BN', requires_grad=True), norm_eval=True, dcn=None,
+                 stage_with_dcn=(False, False, False, False), plugins=None, with_cp=False, zero_init_residual=True):
+        super().__init__()
+        if depth not in _STAGE_BLOCKS and depth not in _BASIC_BLOCK_DEPTHS:
+            raise KeyError(f'invalid depth {depth} for resnet')
+        self.depth = depth
+        if stem_channels is None:
+            stem_channels = base_channels
+        self.stem_channels, self.base_channels, self.num_stages = stem_channels, base_channels, num_stages
+        assert num_stages >= 1 and num_stages <= 4
+        self.strides, self.dilations = strides, dilations
+        assert len(strides) == len(dilations) == num_stages
+        self.out_indices = out_indices
+        assert max(out_indices) < num_stages
+        self.style, self.deep_stem, self.avg_down, self.frozen_stages = style, deep_stem, avg_down, frozen_stages
+        self.conv_cfg, self.norm_cfg, self.with_cp, self.norm_eval = conv_cfg, norm_cfg, with_cp, norm_eval
+        self.dcn, self.stage_with_dcn = dcn, stage_with_dcn
+        if dcn is not None:
+            assert len(stage_with_dcn) == num_stages
+        self.plugins, self.zero_init_residual = plugins, zero_init_residual
+        self.fp16_enabled = False
+
+        if depth in _BASIC_BLOCK_DEPTHS:
+            raise NotImplementedError(f'ResNet: depth={depth} is a BasicBlock net; the Bottleneck depths 50 / 101 / 152 are built')
+        if style not in ('pytorch', 'caffe'):
+            raise ValueError(f"ResNet: style={style!r}; 'pytorch' or 'caffe'")
+        if deep_stem:
+            raise NotImplementedError('ResNet: deep_stem=True (three 3x3 stem convolutions) is not built')
+        if avg_down:
+            raise NotImplementedError('ResNet: avg_down=True (AvgPool2d in the downsample path) is not built')
+        if dcn is not None:
+            raise NotImplementedError(f'ResNet: dcn={dcn} (deformable conv2 in the stages) is not built')
+        if plugins is not None:
+            raise NotImplementedError(f'ResNet: plugins={plugins} are not built')
+        if conv_cfg is not None:
+            raise NotImplementedError(f'ResNet: conv_cfg={conv_cfg} is not built (None: nn.Conv2d)')
+        if not isinstance(norm_cfg, dict) or norm_cfg.get('type') != 'BN' or set(norm_cfg) - {'type', 'requires_grad'}:
+            raise NotImplementedError(f"ResNet: norm_cfg={norm_cfg!r}; dict(type='BN') is built (the eval-mode fold is BatchNorm's)")
+        if any(d != 1 for d in dilations):
+            raise NotImplementedError(f'ResNet: dilations={tuple(dilations)}; 1 in every stage is built')
+        if any(s not in (1, 2) for s in strides):
+            raise NotImplementedError(f'ResNet: strides={tuple(strides)}; 1 and 2 are built')
+        if base_channels % 8 != 0:
+            raise NotImplementedError(f'ResNet: base_channels={base_channels} is not a multiple of 8 (the any-width and the '
+                                      'stride-2 3x3 kernels walk the input channels in chunks of 8)')
+
+        self.stage_blocks = _STAGE_BLOCKS[depth][:num_stages]
+        self.in_channels = in_channels
+        self.conv1 = _conv_weight(stem_channels, in_channels, 7)
+        self.bn1 = _BN(stem_channels)
+        self._stem = _FoldedStem([(self.conv1, self.bn1)], [in_channels])
+
+        self.res_layers = []
+        inplanes = stem_channels
+        for i, num_blocks in enumerate(self.stage_blocks):
+            planes = base_channels * 2 ** i
+            out = planes * Bottleneck.expansion
+            down = strides[i] != 1 or inplanes != out
+            blocks = [Bottleneck(inplanes, planes, downsample=down, stride=strides[i], style=style,
+                                 wide_from=CONV2D_3X3_MAX_WIDTH)]
+            blocks += [Bottleneck(out, planes, wide_from=CONV2D_3X3_MAX_WIDTH) for _ in range(1, num_blocks)]
+            inplanes = out
+            name = f'layer{i + 1}'
+            self.add_module(name, nn.Sequential(*blocks))
+            self.res_layers.append(name)
+        self.feat_dim = Bottleneck.expansion * base_channels * 2 ** (len(self.stage_blocks) - 1)
+
+        if not norm_cfg.get('requires_grad', True):          # build_norm_layer: the norm's parameters
+            for m in self.modules():
+                if isinstance(m, _BN):
+                    for p in m.parameters():
+                        p.requires_grad = False
+        self._freeze_stages()
+
+    @property
+    def norm1(self):
+        return self.bn1
+
+    def _freeze_stages(self):
+        """resnet.py:573-589: the stem and the first ``frozen_stages`` stages stop asking for gradients."""
+        if self.frozen_stages >= 0:
+            for m in (self.conv1, self.bn1):
+                for p in m.parameters():
+                    p.requires_grad = False
+        for i in range(1, self.frozen_stages + 1):
+            for p in getattr(self, f'layer{i}').parameters():
+                p.requires_grad = False
+
+    def init_weights(self, pretrained=None):
+        """resnet.py:591-621 without a checkpoint: kaiming convolutions, unit BatchNorm, and with ``zero_init_residual``
+        a zero ``bn3`` in every block."""
+        if isinstance(pretrained, str):
+            raise NotImplementedError('ResNet.init_weights: load a checkpoint with load_state_dict')
+        if pretrained is not None:
+            raise TypeError('pretrained must be a str or None')
+        for m in self.modules():
+            if isinstance(m, _BN):
+                nn.init.constant_(m.weight, 1)
+                nn.init.constant_(m.bias, 0)
+            elif getattr(m, 'weight', None) is not None and m.weight.dim() == 4:
+                nn.init.kaiming_normal_(m.weight, mode='fan_out', nonlinearity='relu')
+        if self.zero_init_residual:
+            for m in self.modules():
+                if isinstance(m, Bottleneck):
+                    nn.init.constant_(m.bn3.weight, 0)
+                    nn.init.constant_(m.bn3.bias, 0)
+
+    def _check(self, img):
+        if torch.is_grad_enabled() and (img.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError('ResNet: training (BatchNorm in train mode, the backward of the stages) is not built; '
+                                      'run inference under torch.no_grad()')
+        if img.dim() != 4 or img.shape[1] != self.in_channels:
+            raise ValueError(f'ResNet: [B, {self.in_channels}, H, W] images expected, got {tuple(img.shape)}')
+        if not ops.conv7x7_s2_supported(img.shape, self.stem_channels):
+            raise NotImplementedError(f'ResNet: in_channels={self.in_channels}, stem_channels={self.stem_channels} on a '
+                                      f'{tuple(img.shape)} batch: dm_conv7x7_s2_supported refuses the stem (3 input '
+                                      'channels and a non-empty batch are built)')
+
+    def stem(self, img):
+        """relu(bn1(conv1(img))) and the max-pool: two launches."""
+        w, b = self._stem.packed()
+        return ops.maxpool3x3_s2(ops.conv7x7_s2(img, w, b, self.stem_channels, relu=True))
+
+    def run_stage(self, i, x):
+        """Stage ``i`` (``layer{i + 1}``) on its input; ``x`` is not written."""
+        blocks = getattr(self, self.res_layers[i])
+        if blocks[0].downsample is None:          # no new tensor from block 0: the in-place blocks get a copy
+            x = x.clone()
+        for block in blocks:
+            x = block(x)
+        return x
+
+    def forward(self, img):
+        """``img`` [B, 3, H, W] float32 -> the tuple of the ``out_indices`` stages."""
+        self._check(img)
+        x = self.stem(img.contiguous())
+        outs = []
+        for i in range(len(self.res_layers)):
+            x = self.run_stage(i, x)
+            if i in self.out_indices:
+                outs.append(x)
+        return tuple(outs)

@@ -298,14 +298,24 @@ class Bottleneck(nn.Module):
     ``downsample.0`` (1x1, ``inplanes`` -> 4 ``planes``) + ``downsample.1`` (BatchNorm), and the block is three launches
     too -- conv1, conv2, then ONE two-source 1x1 of [conv2 output, x] by [W3' | Wd'] with bias b3' + bd' and ReLU (the
     BasicResBlock pattern) into a NEW tensor: ``x`` is not written.  A stride (style 'caffe': in conv1 and
-    ``downsample.0``, both 1x1) is the caller's subsampling of ``x``."""
+    ``downsample.0``, both 1x1) is the caller's subsampling of ``x``.
+
+    The backbone's arguments (backbones.ResNet; the defaults are the block above).  ``stride=2`` (with ``downsample``):
+    style 'caffe' runs the block on ``ops.subsample2(x)``; style 'pytorch' runs conv1 at full size, conv2 through
+    ``ops.conv3x3_s2`` (one workgroup per tile walks all of K: ``splits=1``) and closes with the two-source 1x1 of
+    [conv2 output, ``ops.subsample2(x)``].  ``wide_from``: a width above which the stride-1 conv2 runs on
+    ``ops.conv3x3_dil`` (dilation 1, any width, the same packed weights) instead of ``ops.conv2d``."""
     expansion = 4
 
-    def __init__(self, inplanes, planes, downsample=False):
+    def __init__(self, inplanes, planes, downsample=False, stride=1, style='pytorch', wide_from=None):
         super().__init__()
         from .roi_head import _BN
         if not downsample and inplanes != planes * self.expansion:
             raise NotImplementedError('Bottleneck: no downsample path (DoubleConvFCBBoxHead: planes = inplanes / 4)')
+        if stride not in (1, 2) or style not in ('pytorch', 'caffe') or (stride == 2 and not downsample):
+            raise NotImplementedError(f'Bottleneck: stride={stride}, style={style!r}, downsample={downsample}; stride 1, or '
+                                      "stride 2 with a downsample path, in style 'pytorch' or 'caffe' are built")
+        self.stride, self.style, self.wide_from = stride, style, wide_from
         self.inplanes, self.planes = inplanes, planes
         out = planes * self.expansion
         self.conv1, self.bn1 = _conv_weight(planes, inplanes, 1), _BN(planes)
@@ -323,8 +333,16 @@ class Bottleneck(nn.Module):
         """Without ``downsample``: ``x`` [N, inplanes, H, W] is overwritten with the block's output and returned.  With
         it: a new [N, 4 planes, H, W] tensor."""
         (w1, b1), (w2, b2), (w3, b3) = (f.packed() for f in self._f)
+        if self.stride == 2 and self.style == 'caffe':
+            x = ops.subsample2(x)
         h = ops.conv2d(x, w1, b1, self.planes, 1, relu=True)
-        h = ops.conv2d(h, w2, b2, self.planes, 3, relu=True)
+        if self.stride == 2 and self.style == 'pytorch':
+            h = ops.conv3x3_s2(h, w2, b2, self.planes, relu=True, splits=1)
+            x = ops.subsample2(x)
+        elif self.wide_from is not None and h.shape[3] > self.wide_from:
+            h = ops.conv3x3_dil(h, w2, b2, self.planes, 1, relu=True)
+        else:
+            h = ops.conv2d(h, w2, b2, self.planes, 3, relu=True)
         if self.downsample is not None:
             return ops.conv2d([h, x], w3, b3, self.planes * self.expansion, 1, relu=True)
         return ops.conv2d(h, w3, b3, self.inplanes, 1, relu=True, out=x, accumulate=True)

@@ -3008,3 +3008,62 @@ def rpn_merge(segs, keep, kept, boxes, score, nms_post):
     check(lib().dm_rpn_merge(_p(segs.tab), B, L, segs.max_rows, _p(keep), _p(kept), _p(boxes), _p(score), int(nms_post),
                              _p(out), _p(counts), _stream()), 'dm_rpn_merge')
     return out, counts
+
+
+# ------------------------------------------------------------------ ResNet stem (dynamask_hip.h section K32)
+# Exact fp32 in every precision mode: the bf16x3 mode does not reach these launches.
+def pack_conv7x7_weight(w):
+    """[cout, C, 7, 7] -> the operand of ``conv7x7_s2``: the matrix [cout, C * 7 * 8] (a zero eighth column behind every
+    kernel row, so a row is a pair of channel quads) in ``pack_conv_weight``'s 1x1 layout."""
+    _chk(w, 'weight')
+    if w.dim() != 4 or tuple(w.shape[2:]) != (7, 7):
+        raise ValueError(f'pack_conv7x7_weight: a [cout, C, 7, 7] weight expected, got {list(w.shape)}')
+    cout, C = w.shape[:2]
+    wide = torch.zeros((cout, C, 7, 8), device=w.device, dtype=torch.float32)
+    wide[..., :7] = w
+    return pack_conv_weight(wide.view(cout, C * 56, 1, 1))
+
+
+def conv7x7_s2_supported(x, cout):
+    """Does ``conv7x7_s2`` take this input (dm_conv7x7_s2_supported: 3 channels, any H, W, any cout)?  ``x``: a tensor
+    or its shape."""
+    NB, C, H, W = x.shape if isinstance(x, torch.Tensor) else x
+    return bool(lib().dm_conv7x7_s2_supported(int(NB), int(C), int(H), int(W), int(cout)))
+
+
+def conv7x7_s2(x, w_packed, bias, cout, relu=False, out=None):
+    """Conv2d(3, cout, 7, stride=2, padding=3)(x) + bias (+ ReLU) -> [NB, cout, ceil(H / 2), ceil(W / 2)]
+    (dm_conv7x7_s2_fwd).  ``w_packed``: ``pack_conv7x7_weight`` of the [cout, 3, 7, 7] weight."""
+    _chk(x, 'x')
+    _chk(w_packed, 'w_packed')
+    if bias is not None:
+        _chk(bias, 'bias')
+    NB, C, H, W = x.shape
+    flags = (1 if relu else 0) | (16 if conv_layout(w_packed) == 'bf16x3' else 0)
+    if not flags & 16:
+        assert w_packed.numel() == packed_floats(cout, 1, [C * 56]), 'weights packed for another shape'
+    shape = (NB, int(cout), (H + 1) // 2, (W + 1) // 2)
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=torch.float32)
+    else:
+        _chk(out, 'out')
+        assert tuple(out.shape) == shape
+    check(lib().dm_conv7x7_s2_fwd(_p(x), NB, C, H, W, _p(w_packed), _p(bias), int(cout), flags, _p(out), _stream()),
+          'dm_conv7x7_s2_fwd')
+    return out
+
+
+def maxpool3x3_s2(x, out=None):
+    """``F.max_pool2d(x, 3, stride=2, padding=1)`` (dm_maxpool3x3_s2_fwd), NaN and -inf as torch treats them."""
+    _chk(x, 'x')
+    N, C, H, W = x.shape
+    if H < 1 or W < 1:
+        raise ValueError(f'maxpool3x3_s2: an empty map {list(x.shape)}')
+    shape = (N, C, (H + 1) // 2, (W + 1) // 2)
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=torch.float32)
+    else:
+        _chk(out, 'out')
+        assert tuple(out.shape) == shape
+    check(lib().dm_maxpool3x3_s2_fwd(_p(x), N * C, H, W, _p(out), _stream()), 'dm_maxpool3x3_s2_fwd')
+    return out

@@ -76,6 +76,7 @@ ROI_LAYERS = Registry('roi_layer')       # stands in for getattr(mmcv.ops, type)
 UPSAMPLE_LAYERS = Registry('upsample')   # stands in for mmcv's build_upsample_layer
 ANCHOR_GENERATORS = Registry('anchor generator')   # mmdet/core/anchor/builder.py
 NECKS = Registry('neck')
+BACKBONES = Registry('backbone')
 
 
 def build(cfg, registry, default_args=None):
@@ -98,6 +99,10 @@ def build_loss(cfg):
 
 def build_neck(cfg):
     return build(cfg, NECKS)
+
+
+def build_backbone(cfg):
+    return build(cfg, BACKBONES)
 
 
 def build_anchor_generator(cfg, default_args=None):

@@ -1342,6 +1342,36 @@ int dm_conv2d_up_add_fwd(const float* const* srcs, const int* src_channels, cons
                          float* out, int out_ch_total, int out_ch_offset, dm_stream_t stream);
 int dm_subsample2_fwd(const float* in, long long NC, int H, int W, float* out, dm_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * K32  ResNet backbone inference (mmdet/models/backbones/resnet.py).  The stages are the launches that exist
+ *      (dm_conv2d_fwd, dm_conv3x3_dil_fwd, dm_conv3x3_s2_fwd, dm_subsample2_fwd); these entry points are the stem.
+ *      Exact fp32, deterministic, no atomics, no workspace.
+ *
+ * dm_conv7x7_s2_fwd: out = act(conv2d(x, w, stride = 2, padding = 3) + bias), x [NB, C, H, W], out
+ * [NB, Cout, ceil(H / 2), ceil(W / 2)]; bias [Cout] or NULL.  w_packed: the [Cout, C, 7, 7] weight as the matrix
+ * [Cout, C * 7 * 8] -- column (c * 7 + ky) * 8 + kx, the columns kx == 7 zero -- in dm_conv_pack_weight's layout for
+ * ksize 1 and one source of C * 56 channels (dm_conv_packed_floats(Cout, 1, 1, {C * 56}) floats).  flags: bit 0 ReLU
+ * (NaN stays NaN); bit 3 is accepted and ignored; bit 4 (the bf16x3 layout): DM_ERR_UNSUPPORTED; any other bit:
+ * DM_ERR_INVALID_ARG.  The sum of an output runs over (c, ky) in order and, in a row, over kx = 0, 4, 1, 5, 2, 6, 3 as
+ * one fp32 fma chain: it does not depend on NB, H, W, the output's position or which taps fall in the padding (those
+ * multiply zeros), so an image's bits do not depend on the other images of the call.
+ * dm_conv7x7_s2_supported: 1 exactly when NB >= 1, C == 3, 1 <= H, W, Cout <= 2^24 (any such Cout: the couts past a
+ * multiple of 32 are dm_conv_packed_cout's padding) and the launch has fewer than 2^31 workgroups
+ * (NB * ceil(Ho / 8) * ceil(Wo / 16) * ceil(CoutP / 64)).  dm_conv7x7_s2_fwd returns DM_ERR_UNSUPPORTED for anything
+ * else, DM_ERR_INVALID_ARG for a null x, w_packed or out.
+ *
+ * dm_maxpool3x3_s2_fwd: F.max_pool2d(in, 3, stride = 2, padding = 1), in [NC, H, W] -> out [NC, ceil(H / 2),
+ * ceil(W / 2)].  Padding taps take no part (a window's result does not depend on the sign of its inputs); the taps of
+ * a window are met row by row and a later one replaces the running maximum when it is larger or NaN (torch's rule), so
+ * a window of -inf gives -inf and a NaN in a window gives NaN.  dm_maxpool3x3_s2_supported: 1 exactly when NC >= 0,
+ * H >= 1, W >= 1 and NC * H * W <= 2^40; anything else: DM_ERR_UNSUPPORTED.  NC == 0 enqueues nothing.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int dm_conv7x7_s2_supported(int NB, int C, int H, int W, int Cout);
+int dm_conv7x7_s2_fwd(const float* x, int NB, int C, int H, int W, const float* w_packed, const float* bias, int Cout,
+                      int flags, float* out, dm_stream_t stream);
+int dm_maxpool3x3_s2_supported(long long NC, int H, int W);
+int dm_maxpool3x3_s2_fwd(const float* in, long long NC, int H, int W, float* out, dm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
