@@ -2132,62 +2132,157 @@ extern "C" int dm_conv2d_wgrad_plan(long long dy_batch_stride, int Cout, long lo
   return r.count;
 }
 
-extern "C" int dm_upsample2x_bilinear_bwd(const float* grad_out, const float* fwd_out_for_relu, int NC, int H, int W,
-                                          int align_corners, float* grad_in, dm_stream_t stream) {
-  if (!grad_out || !grad_in || NC < 0 || H <= 0 || W <= 0) return DM_ERR_INVALID_ARG;
-  if (NC == 0) return DM_OK;
-  if (!align_corners && H >= 2 && W >= 2 && (4 * H * W) % 4 == 0 && (size_t)16 * H * W <= 64 * 1024) {
+// ----------------------------------------------------------------- the other six backward launchers
+// The shape of the weight gradient above: each entry point validates its pointers; its route function decides the launches
+// from numbers alone (no pointer, no HIP call: the compute-unit count is a field of the call); its emit enqueues exactly
+// what the route says; dm_bwd_plan reports the same value.
+
+enum { BK_IM2COL_LDS = 0, BK_IM2COL, BK_COORD_LDS, BK_COORD, BK_COL2IM_LDS, BK_UP_LDS, BK_UP_GATHER, BK_UP_AC_LDS, BK_UP_SCATTER,
+       BK_PS_GATHER, BK_PS_SCATTER, BK_CLB_WAVE, BK_CLB, BK_CLB_REDUCE };      // BwdLaunch::kernel, as the header numbers them
+
+struct BwdCall {            // what a route depends on: the op, its numbers, and facts in place of its pointers
+  int op;                   // DM_BWD_*
+  int N, C, H, W;           // N: images (DCN), planes (upsample), RoIs (point sample, class logits: H = 1, W = HW)
+  int groups;               // deform_groups
+  int align_corners;
+  int B, S;                 // point sample: images of the feature map, samples per side of a RoI
+  int num_classes;
+  int mode;                 // point sample, class logits: WG_ATOMICS / WG_SLAB / WG_FX
+  int aligned16;            // class logits: x, grad_x, grad_inst and grad_det are all 16-byte aligned
+  long long scratch_floats; // class logits, WG_SLAB: the caller's scratch
+  int cus;                  // upsample: dm_num_cus()
+};
+
+static BwdCall bwd_dcn_call(int op, int NB, int C, int H, int W, int deform_groups) {
+  BwdCall c = {};
+  c.op = op; c.N = NB; c.C = C; c.H = H; c.W = W; c.groups = deform_groups;
+  return c;
+}
+static BwdCall bwd_upsample_call(int NC, int H, int W, int align_corners) {
+  BwdCall c = {};
+  c.op = DM_BWD_UPSAMPLE; c.N = NC; c.H = H; c.W = W; c.align_corners = align_corners; c.cus = dm_num_cus();
+  return c;
+}
+static BwdCall bwd_point_sample_call(int B, int C, int H, int W, int N, int S, int fx) {
+  BwdCall c = {};
+  c.op = DM_BWD_POINT_SAMPLE; c.B = B; c.C = C; c.H = H; c.W = W; c.N = N; c.S = S; c.mode = fx ? WG_FX : WG_ATOMICS;
+  return c;
+}
+static BwdCall bwd_class_logits_call(int N, int C, int HW, int num_classes, int mode, int aligned16, long long scratch_floats) {
+  BwdCall c = {};
+  c.op = DM_BWD_CLASS_LOGITS; c.N = N; c.C = C; c.H = 1; c.W = HW; c.num_classes = num_classes; c.mode = mode;
+  c.aligned16 = aligned16; c.scratch_floats = scratch_floats;
+  return c;
+}
+
+// One launch: the ints of dm_bwd_plan's record, in its order
+struct BwdLaunch {
+  int kernel, p[3], grid_x, grid_y, threads, lds_bytes, clear;
+};
+
+struct BwdRoute {
+  int rc = DM_OK, count = 0;           // (an empty call: DM_OK and no launch)
+  BwdLaunch launch[DM_BWD_PLAN_MAX_LAUNCHES];
+  int bands = 0, BRows = 0, XR = 0;    // launch[0] is BK_COORD_LDS: row bands per image, rows per band, rows staged per band
+};
+
+static BwdRoute bwd_refuse(int rc) {
+  BwdRoute r;
+  r.rc = rc;
+  return r;
+}
+static void bwd_add(BwdRoute& r, const BwdLaunch& l) { r.launch[r.count++] = l; }
+static dim3 bwd_grid(const BwdLaunch& l) { return dim3((unsigned)l.grid_x, (unsigned)l.grid_y); }
+
+static BwdRoute upsample_bwd_route(const BwdCall& c) {
+  if (c.N < 0 || c.H <= 0 || c.W <= 0) return bwd_refuse(DM_ERR_INVALID_ARG);
+  BwdRoute r;
+  if (c.N == 0) return r;
+  const size_t HW = (size_t)c.H * c.W;
+  const bool wide = c.H >= 2 && c.W >= 2;
+  const int blocks = min(c.N, 8 * c.cus);
+  if (wide && !c.align_corners && 16 * HW <= 64 * 1024) {
     // LDS-staged gather: overwrites grad_in, every byte of grad_out (and of the ReLU mask) read once
-    const int blocks = min(NC, 8 * dm_num_cus());
-    DM_LAUNCH(upsample2x_bwd_lds_kernel, dim3(blocks), dim3(256), (size_t)16 * H * W, (hipStream_t)stream, grad_out,
-              fwd_out_for_relu, NC, H, W, grad_in);
-    return dm_check_launch();
-  }
-  if (!align_corners && H >= 2 && W >= 2) {
+    bwd_add(r, {BK_UP_LDS, {0, 0, 0}, blocks, 1, 256, (int)(16 * HW), 0});
+  } else if (wide && !c.align_corners) {
     // gather form overwrites grad_in (no zero-fill needed, no atomics)
-    DM_LAUNCH(upsample2x_bwd_gather_kernel, dim3(grid_for((size_t)NC * H * W)), dim3(256), 0, (hipStream_t)stream, grad_out,
-              fwd_out_for_relu, NC, H, W, grad_in);
-    return dm_check_launch();
-  }
-  if (align_corners && H >= 2 && W >= 2 && (size_t)24 * H * W <= 96 * 1024) {
+    bwd_add(r, {BK_UP_GATHER, {0, 0, 0}, grid_for((size_t)c.N * HW), 1, 256, 0, 0});
+  } else if (wide && 24 * HW <= 96 * 1024) {
     // planes [2H][2W] + row sums [2H][W] (56 x 56 inputs: 75 KB).  Few planes (the 256 x 1 x 112 x 112 logit gradients): 1024
     // threads per workgroup, so that a CU with one plane still has 16 waves
-    static bool attr_a[DM_MAX_DEVICES] = {false}, attr_b[DM_MAX_DEVICES] = {false};
-    if (dm_ensure_lds_limit(reinterpret_cast<const void*>(&upsample2x_bwd_ac_lds_kernel<1024>), 96 * 1024, attr_a) != DM_OK ||
-        dm_ensure_lds_limit(reinterpret_cast<const void*>(&upsample2x_bwd_ac_lds_kernel<256>), 96 * 1024, attr_b) != DM_OK)
-      return DM_ERR_LAUNCH;
-    const int blocks = min(NC, 8 * dm_num_cus());
-    if (NC <= 2 * dm_num_cus())
-      DM_LAUNCH((upsample2x_bwd_ac_lds_kernel<1024>), dim3(blocks), dim3(1024), (size_t)24 * H * W, (hipStream_t)stream, grad_out,
-                fwd_out_for_relu, NC, H, W, grad_in);
-    else
-      DM_LAUNCH((upsample2x_bwd_ac_lds_kernel<256>), dim3(blocks), dim3(256), (size_t)24 * H * W, (hipStream_t)stream, grad_out,
-                fwd_out_for_relu, NC, H, W, grad_in);
-    return dm_check_launch();
+    const int NT = c.N <= 2 * c.cus ? 1024 : 256;
+    bwd_add(r, {BK_UP_AC_LDS, {NT, 0, 0}, blocks, 1, NT, (int)(24 * HW), 0});
+  } else {
+    // scatter form (1-pixel inputs, planes beyond 96 KB with align_corners): accumulates, so the output is cleared first
+    bwd_add(r, {BK_UP_SCATTER, {0, 0, 0}, grid_for((size_t)c.N * 4 * HW), 1, 256, 0, 1});
   }
-  // scatter form (1-pixel inputs, planes beyond 64 KB with align_corners): accumulates, so clear the output first
-  if (hipMemsetAsync(grad_in, 0, (size_t)NC * H * W * sizeof(float), (hipStream_t)stream) != hipSuccess) return DM_ERR_LAUNCH;
-  DM_LAUNCH(upsample2x_bwd_kernel, dim3(grid_for((size_t)NC * 4 * H * W)), dim3(256), 0, (hipStream_t)stream, grad_out,
-            fwd_out_for_relu, NC, H, W, align_corners, grad_in);
+  return r;
+}
+
+static int upsample_bwd_emit(const BwdRoute& r, const float* grad_out, const float* fwd_out_for_relu, int NC, int H, int W,
+                             int align_corners, float* grad_in, hipStream_t st) {
+  const BwdLaunch& l = r.launch[0];
+  const dim3 grid = bwd_grid(l), block((unsigned)l.threads);
+  if (l.clear && hipMemsetAsync(grad_in, 0, (size_t)NC * H * W * sizeof(float), st) != hipSuccess) return DM_ERR_LAUNCH;
+  if (l.kernel == BK_UP_AC_LDS) {
+    const int wide = l.p[0] == 1024;
+    const auto fn = wide ? upsample2x_bwd_ac_lds_kernel<1024> : upsample2x_bwd_ac_lds_kernel<256>;
+    static bool raised[2][DM_MAX_DEVICES] = {{false}};
+    if (dm_ensure_lds_limit(reinterpret_cast<const void*>(fn), 96 * 1024, raised[wide]) != DM_OK) return DM_ERR_LAUNCH;
+    DM_LAUNCH(fn, grid, block, (size_t)l.lds_bytes, st, grad_out, fwd_out_for_relu, NC, H, W, grad_in);
+  } else if (l.kernel == BK_UP_SCATTER) {
+    DM_LAUNCH(upsample2x_bwd_kernel, grid, block, 0, st, grad_out, fwd_out_for_relu, NC, H, W, align_corners, grad_in);
+  } else if (l.kernel == BK_UP_LDS) {
+    DM_LAUNCH(upsample2x_bwd_lds_kernel, grid, block, (size_t)l.lds_bytes, st, grad_out, fwd_out_for_relu, NC, H, W, grad_in);
+  } else {
+    DM_LAUNCH(upsample2x_bwd_gather_kernel, grid, block, 0, st, grad_out, fwd_out_for_relu, NC, H, W, grad_in);
+  }
+  return dm_check_launch();
+}
+
+extern "C" int dm_upsample2x_bilinear_bwd(const float* grad_out, const float* fwd_out_for_relu, int NC, int H, int W,
+                                          int align_corners, float* grad_in, dm_stream_t stream) {
+  if (!grad_out || !grad_in) return DM_ERR_INVALID_ARG;
+  const BwdRoute r = upsample_bwd_route(bwd_upsample_call(NC, H, W, align_corners));
+  if (r.rc != DM_OK || r.count == 0) return r.rc;
+  return upsample_bwd_emit(r, grad_out, fwd_out_for_relu, NC, H, W, align_corners, grad_in, (hipStream_t)stream);
+}
+
+constexpr int PS_CT = 4;       // channels per workgroup of both point-sample kernels
+
+static BwdRoute point_sample_bwd_route(const BwdCall& c) {
+  if (c.B <= 0 || c.C <= 0 || c.H <= 0 || c.W <= 0 || c.N < 0 || c.S <= 0) return bwd_refuse(DM_ERR_INVALID_ARG);
+  BwdRoute r;
+  if (c.N == 0) return r;
+  const int S = c.S, groups = dm_ceil_div(c.C, PS_CT);
+  const size_t glds = sizeof(float) * ((size_t)PS_CT * S * S + 4 * (size_t)S + 3 * ((size_t)c.W + 4) + 3 * ((size_t)c.H + 4));
+  if (glds <= 64 * 1024 && S <= 128 && (long long)c.H * c.W * c.W < (1LL << 32))      // (2 S threads build the tables; cell * TW < 2^32)
+    bwd_add(r, {BK_PS_GATHER, {PS_CT, 0, c.mode}, groups, c.N, 256, (int)glds, 0});
+  else                                                                                // 48 KB of 64-bit accumulators
+    bwd_add(r, {BK_PS_SCATTER, {PS_CT, 0, c.mode}, groups, c.N, 256, 6144 * (int)sizeof(unsigned long long), 0});
+  return r;
+}
+
+static int point_sample_bwd_emit(const BwdRoute& r, const float* grad_out, int B, int C, int H, int W, const float* rois, int N, int S,
+                                 float spatial_scale, float* grad_feat, hipStream_t st) {
+  const BwdLaunch& l = r.launch[0];
+  const dim3 grid = bwd_grid(l), block((unsigned)l.threads);
+  const int fx = l.p[2] == WG_FX;
+  if (l.kernel == BK_PS_GATHER)
+    DM_LAUNCH(point_sample_bwd_gather_kernel<PS_CT>, grid, block, (size_t)l.lds_bytes, st, grad_out, B, C, H, W, rois, N, S,
+              spatial_scale, grad_feat, fx);
+  else
+    DM_LAUNCH(point_sample_bwd_kernel<PS_CT>, grid, block, (size_t)l.lds_bytes, st, grad_out, B, C, H, W, rois, N, S, spatial_scale,
+              grad_feat, l.lds_bytes / (int)sizeof(unsigned long long), fx);
   return dm_check_launch();
 }
 
 static int point_sample_bwd_impl(const float* grad_out, int B, int C, int H, int W, const float* rois, int N, int S,
                                  float spatial_scale, float* grad_feat, int fx, dm_stream_t stream) {
-  if (!grad_out || !rois || !grad_feat || B <= 0 || C <= 0 || H <= 0 || W <= 0 || N < 0 || S <= 0) return DM_ERR_INVALID_ARG;
-  if (N == 0) return DM_OK;
-  constexpr int CT = 4;
-  const size_t glds = sizeof(float) * ((size_t)CT * S * S + 4 * (size_t)S + 3 * ((size_t)W + 4) + 3 * ((size_t)H + 4));
-  if (glds <= 64 * 1024 && S <= 128 && (long long)H * W * W < (1LL << 32)) {      // (2 S threads build the tables; cell * TW < 2^32)
-    DM_LAUNCH(point_sample_bwd_gather_kernel<CT>, dim3((unsigned)dm_ceil_div(C, CT), (unsigned)N), dim3(256), glds,
-              (hipStream_t)stream, grad_out, B, C, H, W, rois, N, S, spatial_scale, grad_feat, fx);
-    return dm_check_launch();
-  }
-  const int lds_elems = 6144;                    // 48 KB of 64-bit accumulators
-  DM_LAUNCH(point_sample_bwd_kernel<CT>, dim3((unsigned)dm_ceil_div(C, CT), (unsigned)N), dim3(256),
-            (size_t)lds_elems * sizeof(unsigned long long), (hipStream_t)stream, grad_out, B, C, H, W, rois, N, S,
-            spatial_scale, grad_feat, lds_elems, fx);
-  return dm_check_launch();
+  if (!grad_out || !rois || !grad_feat) return DM_ERR_INVALID_ARG;
+  const BwdRoute r = point_sample_bwd_route(bwd_point_sample_call(B, C, H, W, N, S, fx));
+  if (r.rc != DM_OK || r.count == 0) return r.rc;
+  return point_sample_bwd_emit(r, grad_out, B, C, H, W, rois, N, S, spatial_scale, grad_feat, (hipStream_t)stream);
 }
 
 extern "C" int dm_point_sample_bwd(const float* grad_out, int B, int C, int H, int W, const float* rois, int N, int S,
@@ -2201,34 +2296,66 @@ extern "C" int dm_point_sample_bwd_fx(const float* grad_out, int B, int C, int H
                                stream);
 }
 
+static long long class_logits_bwd_scratch_floats(int N, int C) {
+  return (N < 0 || C <= 0) ? -1 : (long long)N * C * 2 + (long long)N * 2;
+}
+
+static BwdRoute class_logits_bwd_route(const BwdCall& c) {
+  const int HW = c.W;
+  if (c.mode < WG_ATOMICS || c.mode > WG_FX) return bwd_refuse(DM_ERR_INVALID_ARG);
+  if (c.mode == WG_SLAB && (c.scratch_floats < class_logits_bwd_scratch_floats(c.N, c.C) || c.num_classes > 65535))
+    return bwd_refuse(DM_ERR_INVALID_ARG);
+  if (c.N < 0 || c.C <= 0 || HW <= 0 || c.num_classes <= 0) return bwd_refuse(DM_ERR_INVALID_ARG);
+  BwdRoute r;
+  if (c.N == 0) return r;
+  if ((HW & 3) == 0 && HW <= 1024 && c.aligned16) {
+    constexpr int CPW = 4;       // a wave owns CPW channels and reads IT quads of each per lane
+    bwd_add(r, {BK_CLB_WAVE, {CPW, HW <= 256 ? 1 : 4, c.mode}, dm_ceil_div(c.C, 4 * CPW), c.N, 256, 0, 0});
+  } else {
+    bwd_add(r, {BK_CLB, {0, 0, c.mode}, c.C, c.N, 256, 0, 0});
+  }
+  // the slab form: every RoI's sums went to the scratch; added per class in RoI order
+  if (c.mode == WG_SLAB) bwd_add(r, {BK_CLB_REDUCE, {0, 0, WG_SLAB}, dm_ceil_div(c.C, 16), c.num_classes, 256, 0, 0});
+  return r;
+}
+
+// part: the caller's scratch where the route's mode is WG_SLAB, else null
+static int class_logits_bwd_emit(const BwdRoute& r, const float* x, int N, int C, int HW, const float* w_inst, const float* w_det,
+                                 int num_classes, const int64_t* labels, const float* grad_inst, const float* grad_det,
+                                 float* grad_x, int accumulate_x, float* grad_w_inst, float* grad_b_inst, float* grad_w_det,
+                                 float* grad_b_det, float* part, hipStream_t st) {
+  const BwdLaunch& l = r.launch[0];
+  const dim3 grid = bwd_grid(l), block((unsigned)l.threads);
+  const int fx = l.p[2] == WG_FX;
+  if (l.kernel == BK_CLB_WAVE) {
+    const auto fn = l.p[1] == 1 ? class_logits_bwd_wave_kernel<4, 1> : class_logits_bwd_wave_kernel<4, 4>;
+    DM_LAUNCH(fn, grid, block, 0, st, x, N, C, HW, w_inst, w_det, num_classes, labels, grad_inst, grad_det, grad_x, accumulate_x,
+              grad_w_inst, grad_b_inst, grad_w_det, grad_b_det, fx, part);
+  } else {
+    DM_LAUNCH(class_logits_bwd_kernel, grid, block, 0, st, x, N, C, HW, w_inst, w_det, num_classes, labels, grad_inst, grad_det,
+              grad_x, accumulate_x, grad_w_inst, grad_b_inst, grad_w_det, grad_b_det, fx, part);
+  }
+  const int rc = dm_check_launch();
+  if (rc != DM_OK || r.count == 1) return rc;
+  const BwdLaunch& m = r.launch[1];
+  DM_LAUNCH(class_logits_bwd_reduce_kernel, bwd_grid(m), dim3((unsigned)m.threads), 0, st, part, labels, N, C, num_classes,
+            grad_w_inst, grad_b_inst, grad_w_det, grad_b_det);
+  return dm_check_launch();
+}
+
 static int class_logits_bwd_impl(const float* x, int N, int C, int HW, const float* w_inst, const float* w_det,
                                  int num_classes, const int64_t* labels, const float* grad_inst, const float* grad_det,
                                  float* grad_x, int accumulate_x, float* grad_w_inst, float* grad_b_inst,
-                                 float* grad_w_det, float* grad_b_det, int fx, dm_stream_t stream, float* part = nullptr) {
+                                 float* grad_w_det, float* grad_b_det, int mode, dm_stream_t stream, float* scratch = nullptr,
+                                 long long scratch_floats = 0) {
   if (!x || !w_inst || !w_det || !labels || !grad_inst || !grad_det || !grad_x || !grad_w_inst || !grad_b_inst ||
-      !grad_w_det || !grad_b_det)
+      !grad_w_det || !grad_b_det || (mode == WG_SLAB && !scratch))
     return DM_ERR_INVALID_ARG;
-  if (N < 0 || C <= 0 || HW <= 0 || num_classes <= 0) return DM_ERR_INVALID_ARG;
-  if (N == 0) return DM_OK;
-  if ((HW & 3) == 0 && HW <= 1024 && ((((uintptr_t)x | (uintptr_t)grad_x | (uintptr_t)grad_inst | (uintptr_t)grad_det) & 15) == 0)) {
-    constexpr int CPW = 4;
-    if (HW <= 256)
-      DM_LAUNCH((class_logits_bwd_wave_kernel<CPW, 1>), dim3((unsigned)dm_ceil_div(C, 4 * CPW), N), dim3(256), 0, (hipStream_t)stream, x, N, C, HW,
-                w_inst, w_det, num_classes, labels, grad_inst, grad_det, grad_x, accumulate_x, grad_w_inst, grad_b_inst, grad_w_det,
-                grad_b_det, fx, part);
-    else
-      DM_LAUNCH((class_logits_bwd_wave_kernel<CPW, 4>), dim3((unsigned)dm_ceil_div(C, 4 * CPW), N), dim3(256), 0, (hipStream_t)stream, x, N, C, HW,
-                w_inst, w_det, num_classes, labels, grad_inst, grad_det, grad_x, accumulate_x, grad_w_inst, grad_b_inst, grad_w_det,
-                grad_b_det, fx, part);
-  } else {
-    DM_LAUNCH(class_logits_bwd_kernel, dim3(C, N), dim3(256), 0, (hipStream_t)stream, x, N, C, HW, w_inst, w_det, num_classes,
-              labels, grad_inst, grad_det, grad_x, accumulate_x, grad_w_inst, grad_b_inst, grad_w_det, grad_b_det, fx, part);
-  }
-  int rc = dm_check_launch();
-  if (rc != DM_OK || !part) return rc;
-  DM_LAUNCH(class_logits_bwd_reduce_kernel, dim3((unsigned)dm_ceil_div(C, 16), (unsigned)num_classes), dim3(256), 0, (hipStream_t)stream,
-            part, labels, N, C, num_classes, grad_w_inst, grad_b_inst, grad_w_det, grad_b_det);
-  return dm_check_launch();
+  const int aligned16 = (((uintptr_t)x | (uintptr_t)grad_x | (uintptr_t)grad_inst | (uintptr_t)grad_det) & 15) == 0;
+  const BwdRoute r = class_logits_bwd_route(bwd_class_logits_call(N, C, HW, num_classes, mode, aligned16, scratch_floats));
+  if (r.rc != DM_OK || r.count == 0) return r.rc;
+  return class_logits_bwd_emit(r, x, N, C, HW, w_inst, w_det, num_classes, labels, grad_inst, grad_det, grad_x, accumulate_x,
+                               grad_w_inst, grad_b_inst, grad_w_det, grad_b_det, scratch, (hipStream_t)stream);
 }
 
 extern "C" int dm_class_logits_bwd(const float* x, int N, int C, int HW, const float* w_inst, const float* w_det,
@@ -2236,21 +2363,19 @@ extern "C" int dm_class_logits_bwd(const float* x, int N, int C, int HW, const f
                                    float* grad_x, int accumulate_x, float* grad_w_inst, float* grad_b_inst,
                                    float* grad_w_det, float* grad_b_det, dm_stream_t stream) {
   return class_logits_bwd_impl(x, N, C, HW, w_inst, w_det, num_classes, labels, grad_inst, grad_det, grad_x, accumulate_x,
-                               grad_w_inst, grad_b_inst, grad_w_det, grad_b_det, 0, stream);
+                               grad_w_inst, grad_b_inst, grad_w_det, grad_b_det, WG_ATOMICS, stream);
 }
 
-extern "C" long long dm_class_logits_bwd_scratch_floats(int N, int C) {
-  return (N < 0 || C <= 0) ? -1 : (long long)N * C * 2 + (long long)N * 2;
-}
+extern "C" long long dm_class_logits_bwd_scratch_floats(int N, int C) { return class_logits_bwd_scratch_floats(N, C); }
 
 extern "C" int dm_class_logits_bwd_slab(const float* x, int N, int C, int HW, const float* w_inst, const float* w_det,
                                         int num_classes, const int64_t* labels, const float* grad_inst, const float* grad_det,
                                         float* grad_x, int accumulate_x, float* grad_w_inst, float* grad_b_inst,
                                         float* grad_w_det, float* grad_b_det, float* scratch, long long scratch_floats,
                                         dm_stream_t stream) {
-  if (!scratch || scratch_floats < dm_class_logits_bwd_scratch_floats(N, C) || num_classes > 65535) return DM_ERR_INVALID_ARG;
+  // (the route refuses a scratch_floats below dm_class_logits_bwd_scratch_floats(N, C) and num_classes > 65535, the reduce's grid y)
   return class_logits_bwd_impl(x, N, C, HW, w_inst, w_det, num_classes, labels, grad_inst, grad_det, grad_x, accumulate_x,
-                               grad_w_inst, grad_b_inst, grad_w_det, grad_b_det, 0, stream, scratch);
+                               grad_w_inst, grad_b_inst, grad_w_det, grad_b_det, WG_SLAB, stream, scratch, scratch_floats);
 }
 
 extern "C" int dm_class_logits_bwd_fx(const float* x, int N, int C, int HW, const float* w_inst, const float* w_det,
@@ -2260,101 +2385,133 @@ extern "C" int dm_class_logits_bwd_fx(const float* x, int N, int C, int HW, cons
                                       dm_stream_t stream) {
   return class_logits_bwd_impl(x, N, C, HW, w_inst, w_det, num_classes, labels, grad_inst, grad_det, grad_x, accumulate_x,
                                reinterpret_cast<float*>(grad_w_inst_fx), reinterpret_cast<float*>(grad_b_inst_fx),
-                               reinterpret_cast<float*>(grad_w_det_fx), reinterpret_cast<float*>(grad_b_det_fx), 1, stream);
+                               reinterpret_cast<float*>(grad_w_det_fx), reinterpret_cast<float*>(grad_b_det_fx), WG_FX, stream);
+}
+
+static bool dcn_bwd_numbers_ok(const BwdCall& c) {
+  return c.N >= 0 && c.C > 0 && c.H > 0 && c.W > 0 && c.groups > 0 && c.C % c.groups == 0;
+}
+
+static BwdRoute im2col_route(const BwdCall& c) {
+  if (!dcn_bwd_numbers_ok(c)) return bwd_refuse(DM_ERR_INVALID_ARG);
+  if (c.W < 2) return bwd_refuse(DM_ERR_UNSUPPORTED);      // the gather loads row pairs (as dm_deform_conv_fwd)
+  BwdRoute r;
+  if (c.N == 0) return r;
+  const int HW = c.H * c.W, cpg = c.C / c.groups;
+  // LDS-plane build: H*W a multiple of 4, and the most planes CT | C/deform_groups that fit 64 KB
+  if (HW % 4 == 0)
+    for (int CT = 32; CT >= 4; CT /= 2)
+      if (cpg % CT == 0 && (size_t)CT * HW * 4 <= 64 * 1024) {
+        bwd_add(r, {BK_IM2COL_LDS, {CT, 0, 0}, c.N * c.groups * (cpg / CT), 1, 256, CT * HW * 4, 0});
+        return r;
+      }
+  const int CT = 32;                   // (the generic kernel walks its channels in chunks of CT: an argument, not a build)
+  const int pblocks = dm_ceil_div(HW, 256), chunks = dm_ceil_div(cpg, CT);
+  bwd_add(r, {BK_IM2COL, {CT, 0, 0}, c.N * c.groups * 9 * chunks * pblocks, 1, 256, 0, 0});
+  return r;
+}
+
+static int im2col_emit(const BwdRoute& r, const float* x, const float* offset, int NB, int C, int H, int W, int deform_groups,
+                       float* col, hipStream_t st) {
+  const BwdLaunch& l = r.launch[0];
+  const dim3 grid = bwd_grid(l), block((unsigned)l.threads);
+  const int CT = l.p[0];
+  if (l.kernel == BK_IM2COL_LDS) {
+    const auto fn = CT == 32 ? deform_im2col_lds_kernel<32> : CT == 16 ? deform_im2col_lds_kernel<16>
+                  : CT == 8 ? deform_im2col_lds_kernel<8> : deform_im2col_lds_kernel<4>;
+    DM_LAUNCH(fn, grid, block, (size_t)l.lds_bytes, st, x, offset, C, H, W, deform_groups, col);
+  } else {
+    DM_LAUNCH(deform_im2col_kernel, grid, block, 0, st, x, offset, NB, C, H, W, deform_groups, col, CT);
+  }
+  return dm_check_launch();
+}
+
+static BwdRoute coord_grad_route(const BwdCall& c) {
+  if (!dcn_bwd_numbers_ok(c)) return bwd_refuse(DM_ERR_INVALID_ARG);
+  BwdRoute r;
+  if (c.N == 0) return r;
+  // LDS-staged build: 8 | channels per group, W >= 2, H * W < 2^20; a band of BRows rows (<= 224 pixels: 8 items per
+  // thread) with DCN_COORD_HALO rows staged either side
+  const int H = c.H, W = c.W, cpg = c.C / c.groups;
+  const int BRows = max(1, min(H, 224 / W));
+  const int XR = min(H, BRows + 2 * DCN_COORD_HALO);
+  const int bands = dm_ceil_div(H, BRows);
+  const int slots = 2 * (XR + 2) * (W + 2);
+  const size_t lds = (size_t)2 * slots * 16;
+  if (cpg % 8 == 0 && W >= 2 && W <= 224 && H * W < (1 << 20) && 9 * BRows * W <= 2048 && slots <= 2048 &&
+      lds <= 64 * 1024 && (long long)c.N * c.groups * bands <= 0x7fffffffLL) {
+    r.bands = bands; r.BRows = BRows; r.XR = XR;
+    if (slots <= 2 * 512) bwd_add(r, {BK_COORD_LDS, {4, 2, 512}, c.N * c.groups * bands, 1, 512, (int)lds, 0});
+    else bwd_add(r, {BK_COORD_LDS, {2, 2, 1024}, c.N * c.groups * bands, 1, 1024, (int)lds, 0});
+    return r;
+  }
+  bwd_add(r, {BK_COORD, {0, 0, 0}, c.N * c.groups * 9 * dm_ceil_div(H * W, 256), 1, 256, 0, 0});
+  return r;
+}
+
+static int coord_grad_emit(const BwdRoute& r, const float* colgrad, const float* x, const float* offset, int NB, int C, int H, int W,
+                           int deform_groups, float* grad_offset, hipStream_t st) {
+  const BwdLaunch& l = r.launch[0];
+  const dim3 grid = bwd_grid(l), block((unsigned)l.threads);
+  if (l.kernel == BK_COORD_LDS) {
+    const auto fn = l.p[2] == 512 ? dcn_coord_grad_lds_kernel<4, 2, 512> : dcn_coord_grad_lds_kernel<2, 2, 1024>;
+    DM_LAUNCH(fn, grid, block, (size_t)l.lds_bytes, st, colgrad, x, offset, NB, C, H, W, deform_groups, grad_offset, r.bands, r.BRows,
+              r.XR);
+  } else {
+    DM_LAUNCH(dcn_coord_grad_kernel, grid, block, 0, st, colgrad, x, offset, NB, C, H, W, deform_groups, grad_offset);
+  }
+  return dm_check_launch();
+}
+
+static BwdRoute col2im_route(const BwdCall& c) {
+  if (!dcn_bwd_numbers_ok(c)) return bwd_refuse(DM_ERR_INVALID_ARG);
+  BwdRoute r;
+  if (c.N == 0) return r;
+  // channels per workgroup: LDS planes of CT x HW 64-bit accumulators, the largest CT | C/deform_groups that fits 64 KB.
+  // CT = 2 runs 512 threads (56 x 56: two 25 KB planes, three workgroups per CU -- with 8 waves each 1.09 -> 1.02 ms at 256 RoIs
+  // x 64 channels; four planes in 100 KB: 1.85 ms with 4 waves, 1.17 with 8; one plane: 1.29 -- a round-4 probe, docs/HISTORY.md)
+  const int cpg = c.C / c.groups;
+  const size_t plane_b = (size_t)c.H * c.W * sizeof(unsigned long long);
+  for (int CT = 8; CT >= 1; CT /= 2)
+    if (cpg % CT == 0 && CT * plane_b <= 64 * 1024) {
+      bwd_add(r, {BK_COL2IM_LDS, {CT, 0, 0}, c.N * (c.C / CT), 1, CT == 2 ? 512 : 256, (int)(CT * plane_b), 0});
+      return r;
+    }
+  return bwd_refuse(DM_ERR_UNSUPPORTED);
+}
+
+static int col2im_emit(const BwdRoute& r, const float* colgrad, const float* offset, int NB, int C, int H, int W, int deform_groups,
+                       float* grad_x, hipStream_t st) {
+  const BwdLaunch& l = r.launch[0];
+  const int CT = l.p[0];
+  const auto fn = CT == 8 ? dcn_col2im_lds_kernel<8> : CT == 4 ? dcn_col2im_lds_kernel<4>
+                : CT == 2 ? dcn_col2im_lds_kernel<2, 512> : dcn_col2im_lds_kernel<1>;
+  DM_LAUNCH(fn, bwd_grid(l), dim3((unsigned)l.threads), (size_t)l.lds_bytes, st, colgrad, offset, NB, C, H, W, deform_groups, grad_x);
+  return dm_check_launch();
 }
 
 extern "C" int dm_deform_im2col(const float* x, const float* offset, int NB, int C, int H, int W, int deform_groups,
                                 float* col, dm_stream_t stream) {
-  if (!x || !offset || !col || NB < 0 || C <= 0 || H <= 0 || W <= 0 || deform_groups <= 0 || C % deform_groups)
-    return DM_ERR_INVALID_ARG;
-  if (W < 2) return DM_ERR_UNSUPPORTED;      // the gather loads row pairs (as dm_deform_conv_fwd)
-  if (NB == 0) return DM_OK;
-  {
-    // LDS-plane build: H*W a multiple of 4 and CT | C/deform_groups planes that fit 64 KB
-    const int HW = H * W, cpg = C / deform_groups;
-    if (HW % 4 == 0) {
-      const dim3 block(256);
-#define DM_IM2COL(CTV)                                                                                              \
-  if (cpg % CTV == 0 && (size_t)CTV * HW * 4 <= 64 * 1024) {                                                        \
-    DM_LAUNCH(deform_im2col_lds_kernel<CTV>, dim3((unsigned)(NB * deform_groups * (cpg / CTV))), block,              \
-              (size_t)CTV * HW * 4, (hipStream_t)stream, x, offset, C, H, W, deform_groups, col);                   \
-    return dm_check_launch();                                                                                       \
-  }
-      DM_IM2COL(32)
-      DM_IM2COL(16)
-      DM_IM2COL(8)
-      DM_IM2COL(4)
-#undef DM_IM2COL
-    }
-  }
-  const int CT = 32;
-  const int pblocks = dm_ceil_div(H * W, 256), chunks = dm_ceil_div(C / deform_groups, CT);
-  DM_LAUNCH(deform_im2col_kernel, dim3((unsigned)(NB * deform_groups * 9 * chunks * pblocks)), dim3(256), 0,
-            (hipStream_t)stream, x, offset, NB, C, H, W, deform_groups, col, CT);
-  return dm_check_launch();
-}
-
-static int dcn_bwd_args_ok(const float* colgrad, const float* offset, int NB, int C, int H, int W, int deform_groups) {
-  return colgrad && offset && NB >= 0 && C > 0 && H > 0 && W > 0 && deform_groups > 0 && C % deform_groups == 0;
+  if (!x || !offset || !col) return DM_ERR_INVALID_ARG;
+  const BwdRoute r = im2col_route(bwd_dcn_call(DM_BWD_IM2COL, NB, C, H, W, deform_groups));
+  if (r.rc != DM_OK || r.count == 0) return r.rc;
+  return im2col_emit(r, x, offset, NB, C, H, W, deform_groups, col, (hipStream_t)stream);
 }
 
 extern "C" int dm_deform_coord_grad(const float* colgrad, const float* x, const float* offset, int NB, int C, int H, int W,
                                     int deform_groups, float* grad_offset, dm_stream_t stream) {
-  if (!dcn_bwd_args_ok(colgrad, offset, NB, C, H, W, deform_groups) || !x || !grad_offset) return DM_ERR_INVALID_ARG;
-  if (NB == 0) return DM_OK;
-  {
-    // LDS-staged build: 8 | channels per group, W >= 2, H * W < 65536; a band of BRows rows (<= 224 pixels: 8 items per
-    // thread) with DCN_COORD_HALO rows staged either side
-    const int cpg = C / deform_groups;
-    const int BRows = max(1, min(H, 224 / W));
-    const int XR = min(H, BRows + 2 * DCN_COORD_HALO);
-    const int bands = dm_ceil_div(H, BRows);
-    const int slots = 2 * (XR + 2) * (W + 2);
-    const size_t lds = (size_t)2 * slots * 16;
-    if (cpg % 8 == 0 && W >= 2 && W <= 224 && H * W < (1 << 20) && 9 * BRows * W <= 2048 && slots <= 2048 &&
-        lds <= 64 * 1024 && (long long)NB * deform_groups * bands <= 0x7fffffffLL) {
-      const dim3 grid((unsigned)(NB * deform_groups * bands));
-      if (slots <= 2 * 512)
-        DM_LAUNCH((dcn_coord_grad_lds_kernel<4, 2, 512>), grid, dim3(512), lds, (hipStream_t)stream, colgrad, x, offset, NB, C, H, W,
-                  deform_groups, grad_offset, bands, BRows, XR);
-      else
-        DM_LAUNCH((dcn_coord_grad_lds_kernel<2, 2, 1024>), grid, dim3(1024), lds, (hipStream_t)stream, colgrad, x, offset, NB, C, H, W,
-                  deform_groups, grad_offset, bands, BRows, XR);
-      return dm_check_launch();
-    }
-  }
-  const int pblocks = dm_ceil_div(H * W, 256);
-  DM_LAUNCH(dcn_coord_grad_kernel, dim3((unsigned)(NB * deform_groups * 9 * pblocks)), dim3(256), 0, (hipStream_t)stream,
-            colgrad, x, offset, NB, C, H, W, deform_groups, grad_offset);
-  return dm_check_launch();
+  if (!colgrad || !offset || !x || !grad_offset) return DM_ERR_INVALID_ARG;
+  const BwdRoute r = coord_grad_route(bwd_dcn_call(DM_BWD_COORD_GRAD, NB, C, H, W, deform_groups));
+  if (r.rc != DM_OK || r.count == 0) return r.rc;
+  return coord_grad_emit(r, colgrad, x, offset, NB, C, H, W, deform_groups, grad_offset, (hipStream_t)stream);
 }
 
 extern "C" int dm_deform_col2im(const float* colgrad, const float* offset, int NB, int C, int H, int W, int deform_groups,
                                 float* grad_x, dm_stream_t stream) {
-  if (!dcn_bwd_args_ok(colgrad, offset, NB, C, H, W, deform_groups) || !grad_x) return DM_ERR_INVALID_ARG;
-  if (NB == 0) return DM_OK;
-  hipStream_t st = (hipStream_t)stream;
-  // channels per workgroup: LDS planes of CT x HW 64-bit accumulators, CT | C/deform_groups
-  const int cpg = C / deform_groups;
-  const size_t plane_b = (size_t)H * W * sizeof(unsigned long long);
-  if (cpg % 8 == 0 && 8 * plane_b <= 64 * 1024) {
-    DM_LAUNCH(dcn_col2im_lds_kernel<8>, dim3((unsigned)(NB * (C / 8))), dim3(256), 8 * plane_b, st, colgrad, offset, NB, C, H,
-              W, deform_groups, grad_x);
-  } else if (cpg % 4 == 0 && 4 * plane_b <= 64 * 1024) {
-    DM_LAUNCH(dcn_col2im_lds_kernel<4>, dim3((unsigned)(NB * (C / 4))), dim3(256), 4 * plane_b, st, colgrad, offset, NB, C, H,
-              W, deform_groups, grad_x);
-  } else if (cpg % 2 == 0 && 2 * plane_b <= 64 * 1024) {
-    // (56 x 56: two 25 KB planes, three workgroups per CU -- with 8 waves each 1.09 -> 1.02 ms at 256 RoIs x 64 channels; four
-    // planes in 100 KB: 1.85 ms with 4 waves, 1.17 with 8; one plane: 1.29 -- a round-4 probe, docs/HISTORY.md)
-    DM_LAUNCH((dcn_col2im_lds_kernel<2, 512>), dim3((unsigned)(NB * (C / 2))), dim3(512), 2 * plane_b, st, colgrad, offset, NB, C, H,
-              W, deform_groups, grad_x);
-  } else if (plane_b <= 64 * 1024) {
-    DM_LAUNCH(dcn_col2im_lds_kernel<1>, dim3((unsigned)(NB * C)), dim3(256), plane_b, st, colgrad, offset, NB, C, H, W,
-              deform_groups, grad_x);
-  } else {
-    return DM_ERR_UNSUPPORTED;
-  }
-  return dm_check_launch();
+  if (!colgrad || !offset || !grad_x) return DM_ERR_INVALID_ARG;
+  const BwdRoute r = col2im_route(bwd_dcn_call(DM_BWD_COL2IM, NB, C, H, W, deform_groups));
+  if (r.rc != DM_OK || r.count == 0) return r.rc;
+  return col2im_emit(r, colgrad, offset, NB, C, H, W, deform_groups, grad_x, (hipStream_t)stream);
 }
 
 extern "C" int dm_deform_col2im_coord(const float* colgrad, const float* x, const float* offset, int NB, int C, int H,
@@ -2362,6 +2519,33 @@ extern "C" int dm_deform_col2im_coord(const float* colgrad, const float* x, cons
   const int rc = dm_deform_coord_grad(colgrad, x, offset, NB, C, H, W, deform_groups, grad_offset, stream);
   if (rc != DM_OK) return rc;
   return dm_deform_col2im(colgrad, offset, NB, C, H, W, deform_groups, grad_x, stream);
+}
+
+// What the six launchers above would launch for these host numbers: their own route functions' value, the one their emits
+// enqueue (the header has the numbers of each op and the record layout).  Nothing below touches HIP but dm_num_cus().
+extern "C" int dm_bwd_plan(int op, const long long* numbers, int count, int* records, int max_records) {
+  static const int COUNTS[] = {5, 5, 5, 4, 7, 7};      // by DM_BWD_* op
+  if (!numbers || !records || max_records < DM_BWD_PLAN_MAX_LAUNCHES || op < 0 || op > DM_BWD_CLASS_LOGITS || count != COUNTS[op])
+    return DM_ERR_INVALID_ARG;
+  int n[7];
+  for (int i = 0; i < count; ++i) {
+    n[i] = (int)numbers[i];
+    if (n[i] != numbers[i] && !(op == DM_BWD_CLASS_LOGITS && i == 6)) return DM_ERR_INVALID_ARG;      // (an int argument of the call)
+  }
+  const BwdCall c = op <= DM_BWD_COL2IM      ? bwd_dcn_call(op, n[0], n[1], n[2], n[3], n[4])
+                    : op == DM_BWD_UPSAMPLE     ? bwd_upsample_call(n[0], n[1], n[2], n[3])
+                    : op == DM_BWD_POINT_SAMPLE ? bwd_point_sample_call(n[0], n[1], n[2], n[3], n[4], n[5], n[6])
+                                                : bwd_class_logits_call(n[0], n[1], n[2], n[3], n[4], n[5] != 0, numbers[6]);
+  BwdRoute (*const route[])(const BwdCall&) = {im2col_route,       coord_grad_route,       col2im_route,
+                                               upsample_bwd_route, point_sample_bwd_route, class_logits_bwd_route};      // by c.op
+  const BwdRoute r = route[c.op](c);
+  if (r.rc != DM_OK) return r.rc;
+  for (int l = 0; l < r.count; ++l) {
+    const BwdLaunch& m = r.launch[l];
+    const int rec[DM_BWD_PLAN_INTS] = {m.kernel, m.p[0], m.p[1], m.p[2], m.grid_x, m.grid_y, m.threads, m.lds_bytes, m.clear};
+    for (int i = 0; i < DM_BWD_PLAN_INTS; ++i) records[l * DM_BWD_PLAN_INTS + i] = rec[i];
+  }
+  return r.count;
 }
 
 extern "C" int dm_dcn_weight_permute(const float* src, float* dst, int Cout, int C, int to_colmajor, int accumulate,

@@ -1958,6 +1958,59 @@ def conv2d_wgrad_plan(NB, cout, cs, H, W, ksize, mode='slab', has_bias=False, sc
     return recs
 
 
+BWD_OPS = ('im2col', 'coord_grad', 'col2im', 'upsample', 'point_sample', 'class_logits')       # dm_bwd_plan's `op` (DM_BWD_*)
+BWD_KERNELS = ('im2col_lds', 'im2col', 'coord_grad_lds', 'coord_grad', 'col2im_lds', 'upsample_lds', 'upsample_gather',
+               'upsample_ac_lds', 'upsample_scatter', 'point_sample_gather', 'point_sample_scatter', 'class_logits_wave',
+               'class_logits', 'class_logits_reduce')                                         # field 'kernel' of a plan record
+BWD_PLAN_FIELDS = ('kernel', 'P0', 'P1', 'P2', 'grid_x', 'grid_y', 'threads', 'lds_bytes', 'clear')
+BWD_MODES = WGRAD_MODES          # class logits' `mode`; P2 of a point-sample or class-logit record: the accumulation taken
+# every (kernel, P0, P1, P2) the six route functions can name, by op (include/dynamask_hip.h, dm_bwd_plan)
+BWD_BUILDS = {
+    'im2col': {(0, ct, 0, 0) for ct in (32, 16, 8, 4)} | {(1, 32, 0, 0)},
+    'coord_grad': {(2, 4, 2, 512), (2, 2, 2, 1024), (3, 0, 0, 0)},
+    'col2im': {(4, ct, 0, 0) for ct in (8, 4, 2, 1)},
+    'upsample': {(5, 0, 0, 0), (6, 0, 0, 0), (7, 1024, 0, 0), (7, 256, 0, 0), (8, 0, 0, 0)},
+    'point_sample': {(k, 4, 0, acc) for k in (9, 10) for acc in (0, 2)},
+    'class_logits': {(11, 4, it, acc) for it in (1, 4) for acc in (0, 1, 2)} | {(12, 0, 0, acc) for acc in (0, 1, 2)} | {(13, 0, 0, 1)},
+}
+
+
+def backward_plan_raw(op, *numbers):
+    """dm_bwd_plan: (return code, records) for ``op`` (an index into BWD_OPS) and its numbers, in the header's order.  The code
+    is the number of launches or the (negative) error the call with these numbers would return.  Host only."""
+    consts = _abi.load()[1]
+    n, cap = consts['DM_BWD_PLAN_INTS'], consts['DM_BWD_PLAN_MAX_LAUNCHES']
+    assert len(BWD_PLAN_FIELDS) == n
+    rec = (ctypes.c_int * (n * cap))(*([-1] * (n * cap)))
+    nums = (ctypes.c_longlong * len(numbers))(*[int(v) for v in numbers])
+    rc = lib().dm_bwd_plan(int(op), nums, len(numbers), rec, cap)
+    return rc, [dict(zip(BWD_PLAN_FIELDS, rec[i * n:(i + 1) * n])) for i in range(max(rc, 0))]
+
+
+def backward_plan(op, *shape, align_corners=False, aligned16=True, mode=None):
+    """The launches the matching call of this module would make, as its launcher's own route says (include/dynamask_hip.h,
+    dm_bwd_plan): a list of dicts with the keys BWD_PLAN_FIELDS (none: an empty call; two: the class-logit reduce follows).
+    ``op`` (one of BWD_OPS) and ``shape``: 'im2col' / 'coord_grad' / 'col2im': NB, C, H, W, deform_groups; 'upsample': NC, H,
+    W (and ``align_corners``); 'point_sample': B, C, H, W, N, S; 'class_logits': N, C, HW, num_classes.  ``mode`` (one of
+    BWD_MODES; 'point_sample': 'atomics' or 'fx'): None takes what CLB_SLAB and DETERMINISTIC make the call use.  Tensors
+    count as contiguous and 16-byte aligned unless ``aligned16`` says otherwise.  Raises where the call would fail."""
+    i = BWD_OPS.index(op)
+    nums = tuple(shape)
+    if op == 'upsample':
+        nums += (1 if align_corners else 0,)
+    elif op == 'point_sample':
+        nums += (1 if (DETERMINISTIC[0] if mode is None else mode == 'fx') else 0,)
+    elif op == 'class_logits':
+        if mode is None:
+            mode = 'slab' if CLB_SLAB[0] and shape[0] > 0 else ('fx' if DETERMINISTIC[0] else 'atomics')
+        scratch = int(lib().dm_class_logits_bwd_scratch_floats(shape[0], shape[1])) if mode == 'slab' else 0
+        nums += (BWD_MODES.index(mode), 1 if aligned16 else 0, scratch)
+    rc, recs = backward_plan_raw(i, *nums)
+    if rc < 0:
+        check(rc, 'dm_bwd_plan')
+    return recs
+
+
 def upsample2x_backward(grad_out, fwd_out, in_shape, align_corners=False):
     _chk(grad_out, 'grad_out')
     if fwd_out is not None:

@@ -62,7 +62,8 @@ const char* dm_error_string(int code);
  * GroupNorm, neighbour fusion, grouped 4x4 stride-2 deconvolution and box vote (section K27); the convolution launcher's
  * own report of its launches, dm_conv2d_plan (section K5/K6) and dm_conv2d_group_plan (section K25); Double-Head R-CNN's
  * rescaled RoIAlign and global average pool (section K28); the DCN forward launcher's route, dm_deform_conv_plan
- * (section K8); the weight-gradient launcher's route, dm_conv2d_wgrad_plan; RPN inference's selection, decode and merge
+ * (section K8); the weight-gradient launcher's route, dm_conv2d_wgrad_plan, and that of
+ * the other training-side launchers, dm_bwd_plan; RPN inference's selection, decode and merge
  * (section K30); the FPN neck's gathered addend and stride-2 subsample (section K31). */
 #define DM_ABI_VERSION 29 /* the one definition: dm_abi_version(), dm_build_info() and _lib.ABI_VERSION read it */
 int dm_abi_version(void);
@@ -725,17 +726,18 @@ int dm_conv2d_wgrad_plan(long long dy_batch_stride, int Cout, long long x_batch_
                          int max_records);
 
 /* adjoint of dm_upsample2x_bilinear_fwd; fwd_out_for_relu (optional) masks the
- * fused ReLU; grad_in is overwritten (no zero-fill needed; planes up to 64 KB of
- * output gradient are gathered through LDS, larger ones are cleared and scattered). */
+ * fused ReLU; grad_in is overwritten (no zero-fill needed).  Which kernel a shape gets: dm_bwd_plan, DM_BWD_UPSAMPLE. */
 int dm_upsample2x_bilinear_bwd(const float* grad_out, const float* fwd_out_for_relu, int NC, int H, int W,
                                int align_corners, float* grad_in, dm_stream_t stream);
 
-/* adjoint of dm_point_sample_fwd, scatter-add into grad_feat (caller zero-fills). */
+/* adjoint of dm_point_sample_fwd, scatter-add into grad_feat (caller zero-fills).  Launch: dm_bwd_plan,
+ * DM_BWD_POINT_SAMPLE. */
 int dm_point_sample_bwd(const float* grad_out, int B, int C, int H, int W, const float* rois, int N, int S,
                         float spatial_scale, float* grad_feat, dm_stream_t stream);
 
 /* backward of dm_class_logits_fwd: grad_x (+)= W[label] * grad; grad_w/grad_b rows of
- * the RoI's class accumulated atomically (caller zero-fills them). */
+ * the RoI's class accumulated atomically (caller zero-fills them).  Launches of this and of its _slab and _fx forms:
+ * dm_bwd_plan, DM_BWD_CLASS_LOGITS. */
 int dm_class_logits_bwd(const float* x, int N, int C, int HW, const float* w_inst, const float* w_det,
                         int num_classes, const int64_t* labels, const float* grad_inst, const float* grad_det,
                         float* grad_x, int accumulate_x, float* grad_w_inst, float* grad_b_inst, float* grad_w_det,
@@ -755,7 +757,9 @@ int dm_class_logits_bwd_slab(const float* x, int N, int C, int HW, const float* 
  * (row = tap*C + ci).  dm_dcn_weight_permute converts W[co][ci][tap] <->
  * Wt[(tap*C+ci)][co] so that both GEMMs run as 1x1 convs over the column matrix.
  * dm_deform_col2im_coord overwrites grad_x and grad_offset (no zero-fill needed):
- * the scatter-adds of one (image, channel) plane are accumulated in LDS. */
+ * the scatter-adds of one (image, channel) plane are accumulated in LDS.  Which build a shape gets, and the shapes
+ * dm_deform_im2col (W < 2) and dm_deform_col2im (a plane of accumulators beyond 64 KB) refuse as DM_ERR_UNSUPPORTED:
+ * dm_bwd_plan. */
 int dm_deform_im2col(const float* x, const float* offset, int NB, int C, int H, int W, int deform_groups,
                      float* col, dm_stream_t stream);
 int dm_deform_col2im_coord(const float* colgrad, const float* x, const float* offset, int NB, int C, int H, int W,
@@ -768,6 +772,38 @@ int dm_deform_col2im(const float* colgrad, const float* offset, int NB, int C, i
                      float* grad_x, dm_stream_t stream);
 int dm_dcn_weight_permute(const float* src, float* dst, int Cout, int C, int to_colmajor, int accumulate,
                           dm_stream_t stream);
+
+/* The launches of the six training-side launchers above for these HOST numbers: the route each decides on, the very value
+ * it then enqueues (nothing is launched, no device is needed -- without one the compute-unit count is taken as 256).
+ * op and its `numbers` (count of them), the call's int arguments with facts in place of the pointers:
+ *   DM_BWD_IM2COL dm_deform_im2col, DM_BWD_COORD_GRAD dm_deform_coord_grad, DM_BWD_COL2IM dm_deform_col2im (5; the launches
+ *     of dm_deform_col2im_coord are those of the last two, in that order): NB, C, H, W, deform_groups;
+ *   DM_BWD_UPSAMPLE dm_upsample2x_bilinear_bwd (4): NC, H, W, align_corners;
+ *   DM_BWD_POINT_SAMPLE dm_point_sample_bwd / _fx (7): B, C, H, W, N, S, fx (1: dm_point_sample_bwd_fx);
+ *   DM_BWD_CLASS_LOGITS dm_class_logits_bwd / _slab / _fx (7): N, C, HW, num_classes, mode (0 dm_class_logits_bwd, 1 _slab,
+ *     2 _fx), aligned16 (x, grad_x, grad_inst and grad_det are all 16-byte aligned), scratch_floats (mode 1 only).
+ * records: HOST array of max_records (>= DM_BWD_PLAN_MAX_LAUNCHES) x DM_BWD_PLAN_INTS ints.  Returns the number of launches
+ * (0: an empty call; 2: the class-logit reduce follows) or the error code the call would return for these numbers -- also
+ * for an unknown op, a wrong count or a number that is no int -- and then writes nothing.  Record l, ints
+ * [l * DM_BWD_PLAN_INTS ..):
+ *   0 kernel: 0 deform_im2col_lds_kernel, 1 deform_im2col_kernel, 2 dcn_coord_grad_lds_kernel, 3 dcn_coord_grad_kernel,
+ *     4 dcn_col2im_lds_kernel, 5 upsample2x_bwd_lds_kernel, 6 upsample2x_bwd_gather_kernel, 7 upsample2x_bwd_ac_lds_kernel,
+ *     8 upsample2x_bwd_kernel (the scatter), 9 point_sample_bwd_gather_kernel, 10 point_sample_bwd_kernel (the scatter),
+ *     11 class_logits_bwd_wave_kernel, 12 class_logits_bwd_kernel, 13 class_logits_bwd_reduce_kernel;
+ *   1 .. 3 its build: CT, 0, 0 (kernels 0, 4: planes per workgroup; 1: channels per chunk, an argument); IT, XS, NT (2);
+ *     NT, 0, 0 (7); CT, 0, accumulation (9, 10); CPW, IT, accumulation (11); 0, 0, accumulation (12, 13); zeros otherwise.
+ *     Accumulation TAKEN: 0 float atomics, 1 per-RoI slabs + reduce, 2 fixed point;
+ *   4 grid x, 5 grid y, 6 threads per workgroup, 7 dynamic LDS bytes;
+ *   8 clear: 1 where the output is zero-filled (hipMemsetAsync) before the launch. */
+#define DM_BWD_IM2COL 0
+#define DM_BWD_COORD_GRAD 1
+#define DM_BWD_COL2IM 2
+#define DM_BWD_UPSAMPLE 3
+#define DM_BWD_POINT_SAMPLE 4
+#define DM_BWD_CLASS_LOGITS 5
+#define DM_BWD_PLAN_INTS 9
+#define DM_BWD_PLAN_MAX_LAUNCHES 2
+int dm_bwd_plan(int op, const long long* numbers, int count, int* records, int max_records);
 
 /* SGD(momentum, weight decay) step on a flat fp32 buffer; grad_scale folds the
  * 1/world_size of the gradient all-reduce (apis/train.py:75-79 DDP averaging). */

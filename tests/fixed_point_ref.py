@@ -153,8 +153,8 @@ def ps_scatter_route(roi, S, H, W, scale, B, ct=4, lds_elems=6144):
 
 
 # ------------------------------------------------------------------------------------------------ shared test inputs
-# (N, C, dg, H, W) by the build dm_deform_col2im launches: CT = 8 when 8 | C / dg, else 4, else 2 (512 threads), else 1
-# (every plane here fits the 64 KB).  6 x 6 and 8 x 8 take the merged path (H * W % 4 == 0; at 6 x 6 an item of four
+# (N, C, dg, H, W) by the CT of the build dm_deform_col2im launches (the tests that use them ask the launcher's plan,
+# ops.backward_plan('col2im', ...)).  6 x 6 and 8 x 8 take the merged path (H * W % 4 == 0; at 6 x 6 an item of four
 # pixels wraps a row), 5 x 7 the scatter() path.
 COL2IM_SHAPES = {
     8: [(2, 16, 1, 6, 6), (2, 16, 1, 8, 8), (2, 16, 2, 5, 7)],
@@ -164,15 +164,6 @@ COL2IM_SHAPES = {
 }
 COL2IM_VARIANTS = ('planted', 'collapse')
 EXPONENTS = (0, -12, -24, -33, 16)
-
-
-def col2im_build(C, dg, H, W):
-    """The CT that dm_deform_col2im's launch conditions pick (include/dynamask_hip.h; csrc/backward.hip)."""
-    cpg, plane_b = C // dg, H * W * 8
-    for ct in (8, 4, 2, 1):
-        if cpg % ct == 0 and ct * plane_b <= 64 * 1024:
-            return ct
-    return None
 
 
 def col2im_inputs(shape, variant, seed=0):

@@ -46,6 +46,28 @@ def ops():
     return o
 
 
+# The route a case is meant to reach -- (kernel, P0, P1, P2) of every launch, the kernel by its name in ops.BWD_KERNELS -- is
+# written next to the case and asserted through the launcher's own plan (ops.backward_plan) before the case runs;
+# tests/test_bwd_builds_gpu.py asserts that the routes written here and in test_fixed_point_gpu.py are, together, every build
+# the six launchers can name.
+IM2COL_LDS = {ct: ('im2col_lds', ct, 0, 0) for ct in (32, 16, 8, 4)}
+IM2COL = ('im2col', 32, 0, 0)
+COORD_512, COORD_1024, COORD = ('coord_grad_lds', 4, 2, 512), ('coord_grad_lds', 2, 2, 1024), ('coord_grad', 0, 0, 0)
+COL2IM = {ct: ('col2im_lds', ct, 0, 0) for ct in (8, 4, 2, 1)}
+UP_LDS, UP_GATHER, UP_SCATTER = ('upsample_lds', 0, 0, 0), ('upsample_gather', 0, 0, 0), ('upsample_scatter', 0, 0, 0)
+UP_AC = {nt: ('upsample_ac_lds', nt, 0, 0) for nt in (1024, 256)}
+ATOMICS, SLAB, FX = range(3)
+CLB_REDUCE = ('class_logits_reduce', 0, 0, SLAB)
+
+
+def _route(ops, op, *shape, **kw):
+    return [(ops.BWD_KERNELS[r['kernel']], r['P0'], r['P1'], r['P2']) for r in ops.backward_plan(op, *shape, **kw)]
+
+
+def _dcn_routes(ops, N, C, H, W, dg):
+    return tuple(_route(ops, op, N, C, H, W, dg)[0] for op in ('im2col', 'coord_grad', 'col2im'))
+
+
 @pytest.mark.parametrize('N,Cs,Cout,S,ks', [
     (7, [256], 256, 14, 3), (5, [48], 36, 28, 3), (3, [64, 64, 2], 64, 56, 1), (6, [128], 62, 28, 1), (9, [24], 40, 7, 3),
 ])
@@ -73,11 +95,15 @@ def test_conv_wgrad_bias_and_data_grad(ops, N, Cs, Cout, S, ks):
     _close(gx, xcat.grad)
 
 
-@pytest.mark.parametrize('shape', [(5, 6, 14, 14), (3, 1, 56, 56), (2, 3, 9, 13), (2, 2, 2, 2), (1, 2, 72, 72), (2, 1, 1, 5)])
-def test_upsample_backward(ops, shape):
-    """LDS-staged gathers (half-pixel and align_corners), the plain gather, and the scatter fallback for planes
-    beyond 64 KB / one-pixel inputs; the output buffer is handed over uninitialised."""
+# shape: (the half-pixel route, the align_corners route)
+UPSAMPLE_ROUTES = {(5, 6, 14, 14): (UP_LDS, UP_AC[1024]), (3, 1, 56, 56): (UP_LDS, UP_AC[1024]), (2, 3, 9, 13): (UP_LDS, UP_AC[1024]),
+                   (2, 2, 2, 2): (UP_LDS, UP_AC[1024]), (1, 2, 72, 72): (UP_GATHER, UP_SCATTER), (2, 1, 1, 5): (UP_SCATTER, UP_SCATTER)}
+UPSAMPLE_MANY_PLANES_ROUTES = (UP_LDS, UP_AC[256])
+
+
+def _upsample_case(ops, shape, routes):
     for ac, relu in ((False, True), (True, False), (True, True)):
+        assert _route(ops, 'upsample', shape[0] * shape[1], shape[2], shape[3], align_corners=ac) == [routes[ac]]
         x = torch.randn(*shape, generator=_g(30), requires_grad=True)
         y = F.interpolate(x, scale_factor=2, mode='bilinear', align_corners=ac)
         if relu:
@@ -88,12 +114,36 @@ def test_upsample_backward(ops, shape):
         _close(gin, x.grad)
 
 
+@pytest.mark.parametrize('shape', [(5, 6, 14, 14), (3, 1, 56, 56), (2, 3, 9, 13), (2, 2, 2, 2), (1, 2, 72, 72), (2, 1, 1, 5)])
+def test_upsample_backward(ops, shape):
+    """LDS-staged gathers (half-pixel and align_corners), the plain gather, and the scatter fallback for planes
+    beyond 64 KB / one-pixel inputs; the output buffer is handed over uninitialised."""
+    _upsample_case(ops, shape, UPSAMPLE_ROUTES[shape])
+
+
+def test_upsample_backward_with_more_planes_than_two_per_compute_unit(ops):
+    """align_corners with NC > 2 x compute units: the 256-thread build of the LDS kernel (up to there: 1024 threads, so that a
+    CU with one plane still has 16 waves).  The smallest planes it takes, 2 x 3."""
+    planes = 2 * torch.cuda.get_device_properties(0).multi_processor_count + 1
+    _upsample_case(ops, (1, planes, 2, 3), UPSAMPLE_MANY_PLANES_ROUTES)
+
+
+# the point-sample tests of this file: the gather form adding with float atomics (the scatter form, S >= 64, and the
+# fixed-point targets of both are test_fixed_point_gpu.py's)
+POINT_SAMPLE_ROUTE = ('point_sample_gather', 4, 0, ATOMICS)
+
+
+def _point_sample_route(ops):
+    return POINT_SAMPLE_ROUTE[:3] + (FX if ops.DETERMINISTIC[0] else ATOMICS,)        # (DM_DETERMINISTIC=1: fixed point)
+
+
 def test_point_sample_backward(ops):
     hi = gi.head_inputs()
     feat = hi['feats'][2][:, :24].contiguous().requires_grad_(True)
     out = ref_ops.simple_roi_align(feat, hi['rois'], 14, 0.25)
     go = torch.randn(out.shape, generator=_g(40))
     out.backward(go)
+    assert _route(ops, 'point_sample', *feat.shape, hi['rois'].shape[0], 14) == [_point_sample_route(ops)]
     gf = ops.point_sample_backward(_dev(go), tuple(feat.shape), _dev(hi['rois']), 0.25)
     _close(gf, feat.grad)
 
@@ -123,6 +173,7 @@ def test_point_sample_backward_corner_case_rois(ops, S):
     out = ref_ops.simple_roi_align(feat, rois, S, 0.25)
     go = torch.randn(out.shape, generator=_g(42))
     out.backward(go)
+    assert _route(ops, 'point_sample', B, C, H, W, rois.shape[0], S) == [_point_sample_route(ops)]
     gf = ops.point_sample_backward(_dev(go), tuple(feat.shape), _dev(rois), 0.25)
     # a cell of this gradient sums up to ~S * S samples of every RoI over it, in another order than autograd's: the fp64
     # triangle (tests/tolerances.py) instead of round 3's flat atol = 2e-4
@@ -132,14 +183,15 @@ def test_point_sample_backward_corner_case_rois(ops, S):
     assert_close_via_f64(gf, feat.grad, feat64.grad, f'point-sample adjoint S={S}')
 
 
-def test_class_logits_backward(ops):
-    N, C, S, nc = 7, 64, 28, 80
-    x = torch.randn(N, C, S, S, generator=_g(50), requires_grad=True)
+def _class_logits_case(ops, N, C, H, W, labels, routes):
+    """``routes``: {accumulation: the launches}; each is run (the module flags set to ask for it) against autograd."""
+    nc = 80
+    x = torch.randn(N, C, H, W, generator=_g(50), requires_grad=True)
     wi = (torch.randn(nc, C, 1, 1, generator=_g(51)) / 8).requires_grad_(True)
     wd = (torch.randn(nc, C, 1, 1, generator=_g(52)) / 8).requires_grad_(True)
     bi = torch.randn(nc, generator=_g(53)).requires_grad_(True)
     bd = torch.randn(nc, generator=_g(54)).requires_grad_(True)
-    labels = torch.tensor([3, 3, 79, 0, 42, 3, 60])
+    labels = torch.tensor(labels)
     ar = torch.arange(N)
     ip = F.conv2d(x, wi, bi)[ar, labels][:, None]
     dp = F.conv2d(x, wd, bd)[ar, labels][:, None]
@@ -147,16 +199,48 @@ def test_class_logits_backward(ops):
     g2 = torch.randn(dp.shape, generator=_g(56))
     (ip * g1).sum().backward(retain_graph=True)
     (dp * g2).sum().backward()
-    gx = torch.full((N, C, S, S), 1.0).cuda()
-    gwi, gwd = torch.zeros(nc, C).cuda(), torch.zeros(nc, C).cuda()
-    gbi, gbd = torch.zeros(nc).cuda(), torch.zeros(nc).cuda()
-    ops.class_logits_backward(_dev(x), _dev(wi.view(nc, C)), _dev(wd.view(nc, C)), _dev(labels), _dev(g1), _dev(g2), gx,
-                              True, gwi, gbi, gwd, gbd)
-    _close(gx - 1.0, x.grad)
-    _close(gwi, wi.grad.view(nc, C), atol=1e-4, rtol=1e-4)
-    _close(gwd, wd.grad.view(nc, C), atol=1e-4, rtol=1e-4)
-    _close(gbi, bi.grad, atol=1e-4, rtol=1e-4)
-    _close(gbd, bd.grad, atol=1e-4, rtol=1e-4)
+    saved = ops.CLB_SLAB[0], ops.DETERMINISTIC[0]
+    try:
+        for accum, route in routes.items():
+            ops.CLB_SLAB[0], ops.DETERMINISTIC[0] = accum == SLAB, accum == FX
+            assert _route(ops, 'class_logits', N, C, H * W, nc) == route
+            gx = torch.full((N, C, H, W), 1.0).cuda()
+            gwi, gwd = torch.zeros(nc, C).cuda(), torch.zeros(nc, C).cuda()
+            gbi, gbd = torch.zeros(nc).cuda(), torch.zeros(nc).cuda()
+            xd, g1d, g2d = _dev(x), _dev(g1), _dev(g2)
+            assert all(t.data_ptr() % 16 == 0 for t in (xd, g1d, g2d, gx))
+            ops.class_logits_backward(xd, _dev(wi.view(nc, C)), _dev(wd.view(nc, C)), _dev(labels), g1d, g2d, gx, True, gwi, gbi, gwd, gbd)
+            _close(gx - 1.0, x.grad)
+            _close(gwi, wi.grad.view(nc, C), atol=1e-4, rtol=1e-4)
+            _close(gwd, wd.grad.view(nc, C), atol=1e-4, rtol=1e-4)
+            _close(gbi, bi.grad, atol=1e-4, rtol=1e-4)
+            _close(gbd, bd.grad, atol=1e-4, rtol=1e-4)
+    finally:
+        ops.CLB_SLAB[0], ops.DETERMINISTIC[0] = saved
+
+
+def _clb_routes(first, accums=(SLAB, ATOMICS, FX)):
+    return {a: [first + (a,)] + ([CLB_REDUCE] if a == SLAB else []) for a in accums}
+
+
+CLASS_LOGITS_ROUTES = _clb_routes(('class_logits_wave', 4, 4), accums=(SLAB,))
+# N, C, H, W, labels: the routes.  28 x 28: four quads a lane, here in the two accumulations the test above does not ask for;
+# 9 x 9: H W % 4 != 0, 34 x 34: H W > 1024 -- the kernel of one workgroup per (RoI, channel)
+CLASS_LOGITS_BUILD_CASES = [
+    (7, 64, 28, 28, [3, 3, 79, 0, 42, 3, 60], _clb_routes(('class_logits_wave', 4, 4), accums=(ATOMICS, FX))),
+    (3, 8, 9, 9, [3, 3, 79], _clb_routes(('class_logits', 0, 0))),
+    (2, 8, 34, 34, [42, 0], _clb_routes(('class_logits', 0, 0))),
+]
+CLASS_LOGITS_SHARED_ROUTES = _clb_routes(('class_logits_wave', 4, 1), accums=(SLAB, ATOMICS))
+
+
+def test_class_logits_backward(ops):
+    _class_logits_case(ops, 7, 64, 28, 28, [3, 3, 79, 0, 42, 3, 60], CLASS_LOGITS_ROUTES)
+
+
+@pytest.mark.parametrize('N,C,H,W,labels,routes', CLASS_LOGITS_BUILD_CASES, ids=[f'{c[0]}-{c[1]}-{c[2]}x{c[3]}' for c in CLASS_LOGITS_BUILD_CASES])
+def test_class_logits_backward_builds_and_accumulations_not_reached_above(ops, N, C, H, W, labels, routes):
+    _class_logits_case(ops, N, C, H, W, labels, routes)
 
 
 def test_class_logits_backward_slab_matches_atomics_with_shared_classes(ops):
@@ -176,6 +260,8 @@ def test_class_logits_backward_slab_matches_atomics_with_shared_classes(ops):
         old = ops.CLB_SLAB[0]
         ops.CLB_SLAB[0] = slab
         try:
+            accum = SLAB if slab else (FX if ops.DETERMINISTIC[0] else ATOMICS)           # (DM_DETERMINISTIC=1: fixed point for atomics)
+            assert _route(ops, 'class_logits', N, C, S * S, nc) == _clb_routes(('class_logits_wave', 4, 1))[accum]
             gx = torch.empty(N, C, S, S, device='cuda')
             outs = [torch.zeros(nc, C, device='cuda'), torch.zeros(nc, device='cuda'), torch.zeros(nc, C, device='cuda'), torch.zeros(nc, device='cuda')]
             ops.class_logits_backward(x, wi, wd, labels, g1, g2, gx, False, *outs)
@@ -213,10 +299,28 @@ DCN_BWD_CASES = [(5, 64, 14, 2), (3, 32, 28, 2), (2, 16, 9, 2), (5, 64, 14, 1), 
                  (2, 256, 14, 1), (2, 256, 14, 2), (2, 256, 14, 4)]
 
 
-def _dcn_bwd_inputs(N, C, S, dg):
-    x = torch.randn(N, C, S, S, generator=_g(70), requires_grad=True)
+# the case: (im2col, coordinate gradient, col2im) routes
+DCN_BWD_ROUTES = {
+    (5, 64, 14, 2): (IM2COL_LDS[32], COORD_512, COL2IM[8]), (3, 32, 28, 2): (IM2COL_LDS[16], COORD_1024, COL2IM[8]),
+    (2, 16, 9, 2): (IM2COL, COORD_512, COL2IM[8]), (5, 64, 14, 1): (IM2COL_LDS[32], COORD_512, COL2IM[8]),
+    (3, 32, 28, 4): (IM2COL_LDS[8], COORD_1024, COL2IM[8]), (2, 16, 9, 1): (IM2COL, COORD_512, COL2IM[8]),
+    (2, 16, 9, 4): (IM2COL, COORD, COL2IM[4]), (2, 256, 14, 1): (IM2COL_LDS[32], COORD_512, COL2IM[8]),
+    (2, 256, 14, 2): (IM2COL_LDS[32], COORD_512, COL2IM[8]), (2, 256, 14, 4): (IM2COL_LDS[32], COORD_512, COL2IM[8]),
+}
+# (N, C, deform_groups, H, W) of rungs no case above takes: four planes a workgroup (C / deform_groups = 4: also the coordinate
+# gradient's kernel without LDS, as 8 does not divide it); 16 planes because 32 of 24 x 24 pass 64 KB; H W % 4 != 0 with four
+# channels a group; the 1024-thread coordinate gradient on a map of three row bands that is not square
+DCN_BWD_RECT_ROUTES = {
+    (2, 8, 2, 6, 10): (IM2COL_LDS[4], COORD, COL2IM[4]), (1, 32, 1, 24, 24): (IM2COL_LDS[16], COORD_1024, COL2IM[8]),
+    (2, 8, 2, 5, 7): (IM2COL, COORD, COL2IM[4]), (1, 8, 1, 16, 30): (IM2COL_LDS[8], COORD_1024, COL2IM[8]),
+}
+
+
+def _dcn_bwd_inputs(N, C, S, dg, W=None):
+    W = S if W is None else W
+    x = torch.randn(N, C, S, W, generator=_g(70), requires_grad=True)
     w = (torch.randn(C, C, 3, 3, generator=_g(71)) / (9 * C) ** 0.5).requires_grad_(True)
-    off = (torch.randn(N, 18 * dg, S, S, generator=_g(72)) * 1.2)
+    off = (torch.randn(N, 18 * dg, S, W, generator=_g(72)) * 1.2)
     off[0, :, 0, 0] = 30.0
     off = off.requires_grad_(True)
     y = ref_ops.deform_conv2d(x, off, w, 1, 1, 1, dg)
@@ -228,7 +332,18 @@ def _dcn_bwd_inputs(N, C, S, dg):
 @pytest.mark.parametrize('N,C,S,dg', DCN_BWD_CASES,
                          ids=[f'{n}-{c}-{s}' if dg == 2 and c != 256 else f'{n}-{c}-{s}-dg{dg}' for n, c, s, dg in DCN_BWD_CASES])
 def test_deform_conv_backward(ops, N, C, S, dg):
+    assert _dcn_routes(ops, N, C, S, S, dg) == DCN_BWD_ROUTES[(N, C, S, dg)]
     x, w, off, go = _dcn_bwd_inputs(N, C, S, dg)
+    gx, goff, gw = ops.deform_conv_backward(_dev(x), _dev(off), _dev(w), _dev(go), dg)
+    _close(gx, x.grad, atol=1e-4, rtol=1e-4)
+    _close(goff, off.grad, atol=1e-4, rtol=1e-4)
+    _close(gw, w.grad, atol=1e-4, rtol=1e-4)
+
+
+@pytest.mark.parametrize('N,C,dg,H,W', list(DCN_BWD_RECT_ROUTES), ids=[f'{n}-{c}-dg{dg}-{h}x{w}' for n, c, dg, h, w in DCN_BWD_RECT_ROUTES])
+def test_deform_conv_backward_builds_not_reached_above(ops, N, C, dg, H, W):
+    assert _dcn_routes(ops, N, C, H, W, dg) == DCN_BWD_RECT_ROUTES[(N, C, dg, H, W)]
+    x, w, off, go = _dcn_bwd_inputs(N, C, H, dg, W=W)
     gx, goff, gw = ops.deform_conv_backward(_dev(x), _dev(off), _dev(w), _dev(go), dg)
     _close(gx, x.grad, atol=1e-4, rtol=1e-4)
     _close(goff, off.grad, atol=1e-4, rtol=1e-4)
@@ -288,11 +403,18 @@ def test_weight_gradient_by_slab_reduce_is_reproducible_and_equals_the_atomic_su
     assert float((dw3 - 2 * dw1).abs().max()) <= 1e-6 * sw and float((db3 - 2 * db1).abs().max()) <= 1e-6 * sb
 
 
+# (N, C, S) at two deformable groups: (coordinate gradient, col2im) routes -- both LDS-staged builds of the former, 14 bands of
+# 4 rows at 56 x 56, 4 of 8 at 28 x 28, one at 14 x 14
+COORD_FAR_ROUTES = {(2, 16, 56): (COORD_1024, COL2IM[2]), (3, 32, 28): (COORD_1024, COL2IM[8]), (2, 16, 14): (COORD_512, COL2IM[8]),
+                    (1, 16, 56): (COORD_1024, COL2IM[2])}
+
+
 @pytest.mark.parametrize('N,C,S,sigma', [(2, 16, 56, 6.0), (3, 32, 28, 8.0), (2, 16, 14, 5.0), (1, 16, 56, 0.0)])
 def test_deform_coord_grad_with_samples_far_from_their_pixel(ops, N, C, S, sigma):
     """The coordinate gradient stages a band of rows around a workgroup's pixels (DCN_COORD_HALO = 5 rows either side);
     offsets of many rows leave the band and take the global-memory path, samples at the image border read the band's
     zero rows / columns.  Checked against autograd of the oracle (deform_conv_cuda_kernel.cu:145-188, 338-408)."""
+    assert _dcn_routes(ops, N, C, S, S, 2)[1:] == COORD_FAR_ROUTES[(N, C, S)]
     x = torch.randn(N, C, S, S, generator=_g(170), requires_grad=True)
     w = torch.randn(C, C, 3, 3, generator=_g(171)) / (9 * C) ** 0.5
     off = (torch.randn(N, 36, S, S, generator=_g(172)) * sigma).requires_grad_(True)
@@ -326,6 +448,7 @@ def test_fixed_point_scatter_accumulators_propagate_non_finite_gradients(ops):
     feat_shape = (2, 8, 64, 80)
     go = torch.randn(hi['rois'].shape[0], 8, 14, 14, generator=g)
     go[2, 3, 7, 7] = float('nan')
+    assert _route(ops, 'point_sample', *feat_shape, go.shape[0], 14) == [_point_sample_route(ops)]
     gf = ops.point_sample_backward(_dev(go), feat_shape, _dev(hi['rois']), 0.25)
     b = int(hi['rois'][2, 0])
     assert torch.isnan(gf[b, 3]).any()
@@ -397,8 +520,13 @@ def test_bn_relu_maxpool_forward_and_backward_odd_shapes(ops, N, C, H, W):
     _close(gb, br.grad)
 
 
+DCN_NON_SQUARE_ROUTES = {(2, 16, 10, 6): (IM2COL_LDS[8], COORD_512, COL2IM[8]), (1, 32, 20, 12): (IM2COL_LDS[16], COORD_512, COL2IM[8]),
+                         (3, 16, 7, 9): (IM2COL, COORD_512, COL2IM[8])}
+
+
 @pytest.mark.parametrize('N,C,H,W', [(2, 16, 10, 6), (1, 32, 20, 12), (3, 16, 7, 9)])
 def test_deform_conv_backward_non_square(ops, N, C, H, W):
+    assert _dcn_routes(ops, N, C, H, W, 2) == DCN_NON_SQUARE_ROUTES[(N, C, H, W)]
     x = torch.randn(N, C, H, W, generator=_g(120), requires_grad=True)
     w = (torch.randn(C, C, 3, 3, generator=_g(121)) / (9 * C) ** 0.5).requires_grad_(True)
     off = (torch.randn(N, 36, H, W, generator=_g(122)) * 1.5).requires_grad_(True)

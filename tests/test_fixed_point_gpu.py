@@ -121,11 +121,11 @@ def _col2im_case(shape, variant):
 @pytest.mark.parametrize('variant', fr.COL2IM_VARIANTS)
 @pytest.mark.parametrize('ct,shape', [(ct, s) for ct, ss in fr.COL2IM_SHAPES.items() for s in ss], ids=str)
 def test_col2im_every_build_and_both_branches_across_the_range(ops, ct, shape, variant):
-    """dm_deform_col2im launches CT = 8 when 8 | C / dg and 8 planes of H * W 64-bit cells fit 64 KB, else 4, else 2 (512
-    threads), else 1; H * W % 4 == 0 takes the merged path (dm_fix36_abs16 / dm_fix36_accumulate), else scatter()
-    (dm_fix36_mul)."""
+    """Every CT build of dm_deform_col2im, as the launcher's own plan says the shape takes it; H * W % 4 == 0 takes the
+    merged path (dm_fix36_abs16 / dm_fix36_accumulate), else scatter() (dm_fix36_mul)."""
     N, C, dg, H, W = shape
-    assert fr.col2im_build(C, dg, H, W) == ct
+    one, = ops.backward_plan('col2im', N, C, H, W, dg)
+    assert (one['kernel'], one['P0'], one['threads']) == (ops.BWD_KERNELS.index('col2im_lds'), ct, 512 if ct == 2 else 256)
     colgrad, off, s, a, k = _col2im_case(shape, variant)
     assert float(a.max()) * 2.0 ** 16 < 2.0 ** 24             # every input of every exponent is in range by construction
     merged = (H * W) % 4 == 0
@@ -163,6 +163,12 @@ def _ps_case(S):
     return rois, go, routes, s, a, k, k_direct, r_lds
 
 
+# the launch each case is meant to reach, asserted through ops.backward_plan: (kernel, CT, 0, accumulation: 0 float atomics, 2
+# fixed point)
+PS_ROUTES = {(64, 'float'): ('point_sample_scatter', 4, 0, 0), (64, 'fx'): ('point_sample_scatter', 4, 0, 2),
+             (14, 'fx'): ('point_sample_gather', 4, 0, 2)}
+
+
 @pytest.mark.parametrize('S,target', [(64, 'float'), (64, 'fx'), (14, 'fx')])
 def test_point_sample_adjoint_scatter_and_gather_forms_across_the_range(ops, S, target):
     """S = 64 is the scatter form (the gather form's LDS need, 4 planes of S * S floats, passes 64 KB): one 80 x 100 map,
@@ -179,6 +185,8 @@ def test_point_sample_adjoint_scatter_and_gather_forms_across_the_range(ops, S, 
     roisd = _dev(rois)
     worst = 0.0
     with _flags(ops, DETERMINISTIC=target == 'fx'):
+        one, = ops.backward_plan('point_sample', *fr.PS_FEAT_SHAPE, rois.shape[0], S)
+        assert (ops.BWD_KERNELS[one['kernel']], one['P0'], one['P1'], one['P2']) == PS_ROUTES[(S, target)]
         for e in fr.EXPONENTS:
             sc = 2.0 ** e
             god = _dev(go * np.float32(sc))
@@ -257,6 +265,9 @@ def _clb_run(ops, x, wi, wd, labels, g1, g2, nc):
     return [o.check('class_logits_backward parameter gradient').clone() for o in outs]
 
 
+CLB_FX_ROUTE = ('class_logits_wave', 4, 1, 2)       # 14 x 14: one quad a lane; accumulation 2: fixed point
+
+
 def test_class_logits_bwd_fx_against_float64(ops):
     """The shapes of test_class_logits_backward_slab_matches_atomics_with_shared_classes: 1100 RoIs over three classes."""
     N, C, S, nc = 1100, 40, 14, 80
@@ -279,6 +290,8 @@ def test_class_logits_bwd_fx_against_float64(ops):
     # sequence, six wave-shuffle levels; + the final conversion
     depth = 1 + 4 + 6 + 1
     xd, ld = x.cuda(), labels.cuda()
+    one, = ops.backward_plan('class_logits', N, C, S * S, nc, mode='fx')          # (what _clb_run's flags ask for)
+    assert (ops.BWD_KERNELS[one['kernel']], one['P0'], one['P1'], one['P2']) == CLB_FX_ROUTE
     worst = 0.0
     for e in (0, -24):
         sc = 2.0 ** e

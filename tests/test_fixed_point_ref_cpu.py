@@ -83,7 +83,10 @@ def test_the_point_sample_rois_reach_every_sub_route_of_the_scatter_form():
 
 
 def test_col2im_shapes_take_the_builds_they_are_listed_under():
+    from dynamask_amd import ops
     for ct, shapes in fr.COL2IM_SHAPES.items():
         for N, C, dg, H, W in shapes:
-            assert fr.col2im_build(C, dg, H, W) == ct
+            one, = ops.backward_plan('col2im', N, C, H, W, dg)
+            assert (one['kernel'], one['P0']) == (ops.BWD_KERNELS.index('col2im_lds'), ct)
+    assert set(fr.COL2IM_SHAPES) == {b[1] for b in ops.BWD_BUILDS['col2im']}
     assert {(H * W) % 4 == 0 for ss in fr.COL2IM_SHAPES.values() for _, _, _, H, W in ss} == {True, False}
