@@ -4,6 +4,8 @@ Layout:
   csrc/                 HIP kernels + the C ABI (include/dynamask_hip.h)
   _lib.py, ops.py       ctypes binding of libdynamask_hip.so over torch device memory
   registry.py           mmdet-style BACKBONES / HEADS / NECKS / ROI_EXTRACTORS / LOSSES registries + Config
+  layers.py             the parameter holders and weight caches every module below is made of (imports none of them)
+  postprocess.py        host-side result code: NMS, mask paste, per-class result lists (imports none of them)
   backbones.py          ResNet: the image -> the stages the neck reads
   necks.py              FPN: the backbone's stages -> the maps the RPN and the RoI heads read
   roi_extractors.py, mask_heads.py, losses.py, roi_head.py

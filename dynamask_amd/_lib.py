@@ -3,7 +3,7 @@ import ctypes
 import functools
 import os
 
-from . import _abi
+from . import _abi, hazard
 from ._abi import DynaMaskLibraryError  # noqa: F401  (raised here and by the header parse)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -76,7 +76,6 @@ def lib():
             raise DynaMaskLibraryError('libdynamask_hip.so ABI version mismatch: rebuild')
         check_build_info(L.dm_build_info().decode())
         _LIB = L
-    from . import hazard
     if hazard.ENABLED[0]:
         global _PROXY
         if _PROXY is None:

@@ -2,27 +2,21 @@
 the image in, the stages the neck (or a C4 head) starts from out.
 
 The stem is two launches: ``ops.conv7x7_s2`` (``dm_conv7x7_s2_fwd``: conv1 with ``bn1`` folded in and the ReLU on) and
-``ops.maxpool3x3_s2``.  Every block is ``bbox_heads.Bottleneck``'s three launches with eval-mode BatchNorm folded into
-weights and bias (``bbox_heads.fold_bn``: float64, rounded once): block 0 of a stage closes with ONE two-source 1x1
+``ops.maxpool3x3_s2``.  Every block is ``layers.Bottleneck``'s three launches with eval-mode BatchNorm folded into
+weights and bias (``layers.fold_bn``: float64, rounded once): block 0 of a stage closes with ONE two-source 1x1
 convolution of [conv2 output, identity input] into a new tensor, the blocks behind it run in place on that tensor.  A
 stride of 2 sits, with ``style='caffe'``, in the two 1x1 convolutions of block 0 -- the block runs on
 ``ops.subsample2(x)`` -- and, with ``style='pytorch'``, in conv2 (``ops.conv3x3_s2``), the identity input of the closing
 launch being ``ops.subsample2(x)``.  The stride-1 3x3 convolutions are ``ops.conv2d`` launches, ``ops.conv3x3_dil`` at
-dilation 1 on maps wider than ``dense_heads.CONV2D_3X3_MAX_WIDTH``: the width alone decides.  Every launch is exact fp32 in
+dilation 1 on maps wider than ``layers.CONV2D_3X3_MAX_WIDTH``: the width alone decides.  Every launch is exact fp32 in
 every precision mode and none splits its K loop, so an image's bits do not depend on the other images of the call.  The
 host never waits; the image is not written."""
 import torch
 import torch.nn as nn
 
 from . import ops
-from .bbox_heads import Bottleneck, _conv_weight, _FoldedConv
-from .dense_heads import CONV2D_3X3_MAX_WIDTH
+from .layers import _BASIC_BLOCK_DEPTHS, _BN, _STAGE_BLOCKS, CONV2D_3X3_MAX_WIDTH, Bottleneck, _conv_weight, _FoldedConv
 from .registry import BACKBONES
-from .roi_head import _BN
-
-# backbones/resnet.py:356-362 (ResNet.arch_settings): depth -> blocks per stage; 18 / 34 are BasicBlock nets
-_STAGE_BLOCKS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}
-_BASIC_BLOCK_DEPTHS = (18, 34)
 
 
 class _FoldedStem(_FoldedConv):

@@ -11,7 +11,7 @@ Training (second half): ``get_targets`` (bbox2delta = ``dm_bbo
 columns = ``dm_l1_loss_fwd_bwd``) and the backward of the FC stack (``BBoxHeadFn``: data and
 weight gradients as fp32-MFMA GEMMs through the implicit-GEMM kernels on [N, C, 1, 1] tensors).
 ``DoubleConvFCBBoxHead`` (roi_heads/bbox_heads/double_bbox_head.py, inference): the regression from a convolution branch
--- ``BasicResBlock``, ResNet ``Bottleneck``s with eval-mode BatchNorm folded into the exact-fp32 convolutions (``fold_bn``),
+-- ``BasicResBlock``, ``layers.Bottleneck``s with eval-mode BatchNorm folded into the exact-fp32 convolutions (``layers.fold_bn``),
 a global average pool (``dm_global_avg_pool_fwd``) -- the classification from fully connected layers.
 ``BBoxHead`` (roi_heads/bbox_heads/bbox_head.py, inference): the two fully connected layers alone, behind the average pool in
 the C4 configs; its ``Bottleneck`` sibling with a ``downsample`` path is the first block of shared_heads.ResLayer."""
@@ -20,7 +20,11 @@ import torch
 import torch.nn as nn
 
 from . import hazard, ops
-from .registry import HEADS, Registry, build_from_cfg
+from .layers import _FC, BNConvModule, Bottleneck, _FoldedConv
+from .losses import accuracy
+from .postprocess import multiclass_nms
+from .registry import HEADS, Registry, build_from_cfg, build_loss
+from .train_path import _join_caller_after_backward, params_grad
 
 BBOX_CODERS = Registry('bbox_coder')
 
@@ -51,22 +55,6 @@ class DeltaXYWHBBoxCoder:
         return ops.bbox_encode(bboxes.float().contiguous(), gt_bboxes.float().contiguous(), self.means, self.stds)
 
 
-class _FC(nn.Module):
-    """nn.Linear parameters; the product runs on the fp32 MFMA FC kernel (dm_fc_fwd)."""
-
-    def __init__(self, cin, cout):
-        super().__init__()
-        self.in_features, self.out_features = cin, cout
-        self.weight = nn.Parameter(torch.empty(cout, cin))
-        self.bias = nn.Parameter(torch.zeros(cout))
-        nn.init.xavier_uniform_(self.weight)
-        from .mask_heads import _Packed
-        self._pk = _Packed()      # transposed packed weights of the backward's data-gradient GEMM
-
-    def run(self, x, relu=False):
-        return ops.fc(x.contiguous(), self.weight.detach(), self.bias.detach(), relu=relu)
-
-
 @HEADS.register_module()
 class Shared2FCBBoxHead(nn.Module):
     """convfc_bbox_head.py:189-205 (= ConvFCBBoxHead with 2 shared FCs) on top of BBoxHead
@@ -95,7 +83,6 @@ class Shared2FCBBoxHead(nn.Module):
             raise NotImplementedError('reg_decoded_bbox=False in configs/dynamask')
         self.loss_cls_cfg, self.loss_bbox_cfg = loss_cls, loss_bbox
         # bbox_head.py:47-48 (no parameters; built when configured so that inference-only configs stay light)
-        from .registry import build_loss
         self.loss_cls = build_loss(loss_cls) if loss_cls is not None else None
         self.loss_bbox = build_loss(loss_bbox) if loss_bbox is not None else None
         self.shared_fcs = nn.ModuleList([_FC(in_channels * self.roi_feat_area, fc_out_channels),
@@ -164,7 +151,6 @@ class Shared2FCBBoxHead(nn.Module):
 
     def loss(self, cls_score, bbox_pred, rois, labels, label_weights, bbox_targets, bbox_weights, reduction_override=None):
         """bbox_head.py:143-184 -> {'loss_cls', 'acc', 'loss_bbox'}."""
-        from .losses import accuracy
         losses = dict()
         if cls_score is not None:
             known = getattr(label_weights, '_dm_num_weighted', None)      # set by get_targets: all of its rows are weighted
@@ -206,68 +192,7 @@ class Shared2FCBBoxHead(nn.Module):
         return multiclass_nms(bboxes, scores, cfg.score_thr, cfg.nms, cfg.max_per_img)
 
 
-
 # ---------------------------------------------------------------- Double-Head R-CNN (bbox_heads/double_bbox_head.py)
-def fold_bn(pairs):
-    """Eval-mode BatchNorm folded into the convolution in front of it: ``pairs`` = [(conv weight [Cout, Cin_i, k, k], bn),
-    ...] -> (w' [Cout, sum Cin_i, k, k], b' [Cout]) with, per pair, s = gamma / sqrt(running_var + eps),
-    w' = w * s[:, None, None, None], b' = beta - running_mean * s.  Several pairs are the summed outputs of convolutions
-    of different inputs as ONE convolution of their concatenation: the weights side by side along Cin, the biases added.
-    All of it in float64, rounded once to float32."""
-    ws, b = [], None
-    for w, bn in pairs:
-        s = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
-        ws.append(w.detach().double() * s[:, None, None, None])
-        bi = bn.bias.detach().double() - bn.running_mean.detach().double() * s
-        b = bi if b is None else b + bi
-    return torch.cat(ws, 1).float().contiguous(), b.float().contiguous()
-
-
-class _FoldedConv:
-    """Packed folded weights + bias of one launch, cached like ``_Packed`` caches packed weights: made again when any of
-    the convolution weights, BatchNorm parameters or running statistics changes (``load_state_dict`` copies in place and
-    moves their versions; a move to another device changes their addresses)."""
-
-    def __init__(self, pairs, src_channels):
-        from .mask_heads import _Packed
-        self.modules, self.src_channels = pairs, list(src_channels)      # [(convolution holder, BatchNorm holder), ...]
-        self._pk = _Packed()
-
-    def _pairs(self):
-        return [(conv.weight, bn) for conv, bn in self.modules]
-
-    def _tensors(self):
-        return [t for w, bn in self._pairs() for t in (w, bn.weight, bn.bias, bn.running_mean, bn.running_var)]
-
-    def folded(self):
-        """(w', b') in torch's layout, on the parameters' device (CPU included)."""
-        return self._pk.get_multi('fold', self._tensors(), lambda: fold_bn(self._pairs()))
-
-    def packed(self):
-        """(packed w', b') for ops.conv2d: always the exact fp32 layout, whatever the precision mode."""
-        def make():
-            w, b = self.folded()
-            return ops.pack_conv_weight(w, src_channels=self.src_channels), b
-        return self._pk.get_multi('pack', self._tensors(), make)
-
-
-def _conv_weight(cout, cin, k):
-    """nn.Conv2d(bias=False) parameter holder: the key is ``weight`` alone."""
-    from .mask_heads import _Conv
-    return _Conv(cin, cout, k, bias=False)
-
-
-class BNConvModule(nn.Module):
-    """mmcv ConvModule(bias=False, norm_cfg=dict(type='BN')): keys ``conv.weight``, ``bn.*``.  A parameter holder: the
-    block that owns it folds the BatchNorm and launches."""
-
-    def __init__(self, in_channels, out_channels, kernel_size):
-        super().__init__()
-        from .roi_head import _BN
-        self.conv = _conv_weight(out_channels, in_channels, kernel_size)
-        self.bn = _BN(out_channels)
-
-
 class BasicResBlock(nn.Module):
     """double_bbox_head.py:9-68 in eval mode: relu(bn(conv2(relu(bn(conv1 3x3(x))))) + bn(conv_identity(x))) as two
     launches -- conv1 + ReLU, then ONE two-source 1x1 convolution of [conv1 output, x] by [W2' | Wid'] with bias
@@ -288,64 +213,6 @@ class BasicResBlock(nn.Module):
         h = ops.conv2d(x, w1, b1, self.in_channels, 3, relu=True)
         w2, b2 = self._f2.packed()
         return ops.conv2d([h, x], w2, b2, self.out_channels, 1, relu=True)
-
-
-class Bottleneck(nn.Module):
-    """backbones/resnet.py:95-300 (stride 1, no downsample, style 'pytorch') in eval mode; keys ``conv{1,2,3}.weight``,
-    ``bn{1,2,3}.*``.  Three launches: 1x1 + ReLU, 3x3 + ReLU, then the 1x1 back to ``inplanes`` with the ``accumulate |
-    ReLU`` epilogue -- relu(x + conv + bias), the residual sum before the activation -- written IN PLACE into ``x``.
-    ``downsample=True`` (the first block of a ResNet layer, shared_heads.ResLayer): the identity path is
-    ``downsample.0`` (1x1, ``inplanes`` -> 4 ``planes``) + ``downsample.1`` (BatchNorm), and the block is three launches
-    too -- conv1, conv2, then ONE two-source 1x1 of [conv2 output, x] by [W3' | Wd'] with bias b3' + bd' and ReLU (the
-    BasicResBlock pattern) into a NEW tensor: ``x`` is not written.  A stride (style 'caffe': in conv1 and
-    ``downsample.0``, both 1x1) is the caller's subsampling of ``x``.
-
-    The backbone's arguments (backbones.ResNet; the defaults are the block above).  ``stride=2`` (with ``downsample``):
-    style 'caffe' runs the block on ``ops.subsample2(x)``; style 'pytorch' runs conv1 at full size, conv2 through
-    ``ops.conv3x3_s2`` (one workgroup per tile walks all of K: ``splits=1``) and closes with the two-source 1x1 of
-    [conv2 output, ``ops.subsample2(x)``].  ``wide_from``: a width above which the stride-1 conv2 runs on
-    ``ops.conv3x3_dil`` (dilation 1, any width, the same packed weights) instead of ``ops.conv2d``."""
-    expansion = 4
-
-    def __init__(self, inplanes, planes, downsample=False, stride=1, style='pytorch', wide_from=None):
-        super().__init__()
-        from .roi_head import _BN
-        if not downsample and inplanes != planes * self.expansion:
-            raise NotImplementedError('Bottleneck: no downsample path (DoubleConvFCBBoxHead: planes = inplanes / 4)')
-        if stride not in (1, 2) or style not in ('pytorch', 'caffe') or (stride == 2 and not downsample):
-            raise NotImplementedError(f'Bottleneck: stride={stride}, style={style!r}, downsample={downsample}; stride 1, or '
-                                      "stride 2 with a downsample path, in style 'pytorch' or 'caffe' are built")
-        self.stride, self.style, self.wide_from = stride, style, wide_from
-        self.inplanes, self.planes = inplanes, planes
-        out = planes * self.expansion
-        self.conv1, self.bn1 = _conv_weight(planes, inplanes, 1), _BN(planes)
-        self.conv2, self.bn2 = _conv_weight(planes, planes, 3), _BN(planes)
-        self.conv3, self.bn3 = _conv_weight(out, planes, 1), _BN(out)
-        self._f = [_FoldedConv([(c, bn)], [c.in_channels]) for c, bn in ((self.conv1, self.bn1), (self.conv2, self.bn2))]
-        if downsample:
-            self.downsample = nn.Sequential(_conv_weight(out, inplanes, 1), _BN(out))
-            self._f.append(_FoldedConv([(self.conv3, self.bn3), (self.downsample[0], self.downsample[1])], [planes, inplanes]))
-        else:
-            self.downsample = None
-            self._f.append(_FoldedConv([(self.conv3, self.bn3)], [planes]))
-
-    def forward(self, x):
-        """Without ``downsample``: ``x`` [N, inplanes, H, W] is overwritten with the block's output and returned.  With
-        it: a new [N, 4 planes, H, W] tensor."""
-        (w1, b1), (w2, b2), (w3, b3) = (f.packed() for f in self._f)
-        if self.stride == 2 and self.style == 'caffe':
-            x = ops.subsample2(x)
-        h = ops.conv2d(x, w1, b1, self.planes, 1, relu=True)
-        if self.stride == 2 and self.style == 'pytorch':
-            h = ops.conv3x3_s2(h, w2, b2, self.planes, relu=True, splits=1)
-            x = ops.subsample2(x)
-        elif self.wide_from is not None and h.shape[3] > self.wide_from:
-            h = ops.conv3x3_dil(h, w2, b2, self.planes, 1, relu=True)
-        else:
-            h = ops.conv2d(h, w2, b2, self.planes, 3, relu=True)
-        if self.downsample is not None:
-            return ops.conv2d([h, x], w3, b3, self.planes * self.expansion, 1, relu=True)
-        return ops.conv2d(h, w3, b3, self.inplanes, 1, relu=True, out=x, accumulate=True)
 
 
 @HEADS.register_module()
@@ -385,7 +252,6 @@ class DoubleConvFCBBoxHead(nn.Module):
         self.bbox_coder = build_bbox_coder(bbox_coder)
         self.reg_decoded_bbox = reg_decoded_bbox
         self.loss_cls_cfg, self.loss_bbox_cfg = loss_cls, loss_bbox
-        from .registry import build_loss
         self.loss_cls = build_loss(loss_cls) if loss_cls is not None else None
         self.loss_bbox = build_loss(loss_bbox) if loss_bbox is not None else None
         self.res_block = BasicResBlock(in_channels, conv_out_channels)
@@ -458,7 +324,6 @@ class BBoxHead(nn.Module):
         self.reg_decoded_bbox = reg_decoded_bbox
         self.bbox_coder = build_bbox_coder(bbox_coder)
         self.loss_cls_cfg, self.loss_bbox_cfg = loss_cls, loss_bbox
-        from .registry import build_loss
         self.loss_cls = build_loss(loss_cls) if loss_cls is not None else None
         self.loss_bbox = build_loss(loss_bbox) if loss_bbox is not None else None
         fc_in = in_channels if with_avg_pool else in_channels * self.roi_feat_area
@@ -518,13 +383,11 @@ class BBoxHeadFn(torch.autograd.Function):
     @hazard.backward_node
     def backward(ctx, g_cls, g_reg):
         head, acts = ctx.head, ctx.acts
-        from . import hazard
         hazard.engine_handoff(g_cls, g_reg)
         n = acts[0].shape[0]
         pg = {}
 
         def fc_bwd(fc, gy, xin, need_data=True, out=None, accumulate=False):
-            from .train_path import params_grad
             gy4 = gy.contiguous().view(n, fc.out_features, 1, 1)
             x4 = xin.view(n, fc.in_features, 1, 1)
             params_grad(fc.weight, fc.bias, gy4, x4, 1, pg, (fc.out_features, fc.in_features, 1, 1))
@@ -551,108 +414,5 @@ class BBoxHeadFn(torch.autograd.Function):
                 g_h = fc_bwd(head.shared_fcs[i], g_h, acts[i], need_data=need)
             if ctx.need_x:
                 g_x = g_h.reshape(ctx.x_shape)
-        from .train_path import _join_caller_after_backward
         _join_caller_after_backward(acts[0].device)
         return (None, g_x, *[pg.get(p) for p in head.parameters()])
-
-
-def batched_nms(boxes, scores, idxs, nms_cfg, class_agnostic=False):
-    """mmcv.ops.nms.batched_nms (mmcv 1.0.5): boxes of different classes are moved apart by
-    (max coordinate + 1) * class so that one NMS handles all classes."""
-    cfg = dict(nms_cfg)
-    cfg.pop('type', 'nms')
-    class_agnostic = cfg.pop('class_agnostic', class_agnostic)
-    if class_agnostic:
-        boxes_for_nms = boxes
-    else:
-        max_coordinate = boxes.max()
-        offsets = idxs.to(boxes) * (max_coordinate + 1)
-        boxes_for_nms = boxes + offsets[:, None]
-    dets, keep = ops.nms(boxes_for_nms.contiguous(), scores.contiguous(), cfg.get('iou_threshold', cfg.get('iou_thr', 0.5)))
-    return torch.cat([boxes[keep], dets[:, -1:]], 1), keep
-
-
-def multiclass_nms(multi_bboxes, multi_scores, score_thr, nms_cfg, max_num=-1, score_factors=None):
-    """core/post_processing/bbox_nms.py:5-68 -> (dets [k, 5], labels [k]), labels 0-based; the
-    last score column (background) is ignored."""
-    n, ncls = multi_scores.shape[0], multi_scores.shape[1] - 1
-    fg = multi_scores[:, :ncls]
-    cand = (fg > score_thr).nonzero(as_tuple=False)          # row-major: the reference's masked_select order
-    if cand.shape[0] == 0:
-        return multi_bboxes.new_zeros((0, 5)), multi_bboxes.new_zeros((0,), dtype=torch.long)
-    ri, ci = cand[:, 0], cand[:, 1]
-    per_class = multi_bboxes.view(n, -1, 4)
-    boxes = per_class[ri, ci] if per_class.shape[1] > 1 else per_class[ri, 0]
-    scores = fg[ri, ci] if score_factors is None else (fg * score_factors[:, None])[ri, ci]
-    dets, keep = batched_nms(boxes, scores, ci, nms_cfg)
-    if max_num > 0:
-        dets, keep = dets[:max_num], keep[:max_num]
-    return dets, ci[keep]
-
-
-def multiclass_nms_batch(multi_bboxes_list, multi_scores_list, score_thr, nms_cfg, max_num=-1):
-    """``multiclass_nms`` of B images at once -> list of B (dets [k, 5], labels [k]), each what ``multiclass_nms`` gives
-    for that image alone, bit for bit.  The score cut runs on all images' rows together; every image is one segment of
-    ``ops.nms_segmented`` (suppression bits only within the image, greedy pass on the device, ``max_num`` per image).
-    ``batched_nms``'s class offsets use each image's OWN largest coordinate, as the per-image call does.  Host waits: the
-    candidate count, the per-image candidate counts and the per-image kept counts -- three, whatever B is."""
-    B = len(multi_scores_list)
-    assert len(multi_bboxes_list) == B
-    if B == 0:
-        return []
-    ref = multi_bboxes_list[0]
-    empty = lambda: (ref.new_zeros((0, 5)), ref.new_zeros((0,), dtype=torch.long))      # noqa: E731
-    rows = [int(s.shape[0]) for s in multi_scores_list]
-    if sum(rows) == 0:
-        return [empty() for _ in range(B)]
-    scores_all = torch.cat([s for s in multi_scores_list if s.shape[0] > 0], 0)
-    ncls = scores_all.shape[1] - 1
-    bboxes_all = torch.cat([b.reshape(b.shape[0], -1) for b in multi_bboxes_list if b.shape[0] > 0], 0)
-    n = scores_all.shape[0]
-    fg = scores_all[:, :ncls]
-    cand = (fg > score_thr).nonzero(as_tuple=False)          # row-major: image after image, the per-image order in each
-    if cand.shape[0] == 0:
-        return [empty() for _ in range(B)]
-    ri, ci = cand[:, 0], cand[:, 1]
-    per_class = bboxes_all.view(n, -1, 4)
-    boxes = per_class[ri, ci] if per_class.shape[1] > 1 else per_class[ri, 0]
-    scores = fg[ri, ci]
-    row_start = ops._upload([sum(rows[:b + 1]) for b in range(B)], torch.int64, ref.device)
-    img = torch.searchsorted(row_start, ri, right=True)       # image of every candidate
-    counts = torch.bincount(img, minlength=B).cpu().tolist()
-    cfg = dict(nms_cfg)
-    cfg.pop('type', 'nms')
-    class_agnostic = cfg.pop('class_agnostic', False)
-    if class_agnostic:
-        boxes_for_nms = boxes
-    else:
-        # batched_nms: boxes.max() of the image's own candidates, the same fp32 operations in the same order
-        seg_max = torch.full((B,), float('-inf'), device=boxes.device, dtype=boxes.dtype)
-        seg_max = seg_max.scatter_reduce(0, img, boxes.amax(1), 'amax')
-        offsets = ci.to(boxes) * (seg_max + 1)[img]
-        boxes_for_nms = boxes + offsets[:, None]
-    # per-image stable descending sort == stable descending sort of all, then a stable sort by image
-    o1 = torch.sort(scores, descending=True, stable=True)[1]
-    order = o1[torch.sort(img[o1], stable=True)[1]]
-    sb = boxes_for_nms[order].contiguous()
-    keep, kept = ops.nms_segmented(sb, counts, cfg.get('iou_threshold', cfg.get('iou_thr', 0.5)), max_num=max_num)
-    kept = kept.cpu().tolist()
-    out, start = [], 0
-    for b in range(B):
-        k = kept[b]
-        if k == 0:
-            out.append(empty())
-        else:
-            g = order[keep[start:start + k].long() + start]
-            out.append((torch.cat([boxes[g], scores[g][:, None]], 1), ci[g]))
-        start += counts[b]
-    return out
-
-
-def bbox2result(bboxes, labels, num_classes):
-    """core/bbox/transforms.py:76-96."""
-    if bboxes.shape[0] == 0:
-        return [np.zeros((0, 5), dtype=np.float32) for _ in range(num_classes)]
-    bboxes = bboxes.cpu().numpy()
-    labels = labels.cpu().numpy()
-    return [bboxes[labels == i, :] for i in range(num_classes)]

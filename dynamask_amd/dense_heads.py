@@ -21,7 +21,7 @@ import torch.nn as nn
 from . import anchors  # noqa: F401  (registers AnchorGenerator)
 from . import ops
 from .bbox_heads import build_bbox_coder
-from .mask_heads import _Conv
+from .layers import CONV2D_3X3_MAX_WIDTH, _exact_conv
 from .registry import HEADS, build_anchor_generator
 
 # DM_RPN_FUSED=0: the composed path (the launches that existed before the RPN kernels) instead of dm_rpn_*
@@ -30,20 +30,6 @@ def _env_fused():
 
 
 RPN_FUSED = [_env_fused()]
-
-
-# ops.conv2d's 3x3 builds stage whole rows of the map (csrc/conv_igemm.hip: the plane of a 128-pixel tile), which stops
-# fitting their LDS at 169 pixels of width; the 3x3 kernel of csrc/conv_dilated.hip stages 8 x 16 blocks and takes any
-# width, from the same packed weights, exact fp32 too.  rpn_conv runs on it (dilation 1) on maps wider than this -- the
-# stride-4 and stride-8 maps of a 1333 x 800 image -- and on ops.conv2d below; the width alone decides, so a map's kernel
-# does not depend on the batch.
-CONV2D_3X3_MAX_WIDTH = 128
-
-
-def _exact_conv(cin, cout, k):
-    c = _Conv(cin, cout, k)
-    c.exact = True          # a changed score reorders proposals: the bf16x3 mode does not reach the RPN
-    return c
 
 
 @HEADS.register_module()

@@ -18,7 +18,7 @@ import os
 import torch
 import torch.distributed as dist
 
-from . import hazard
+from . import hazard, ops, streams
 
 
 class FlatParamGroup:
@@ -55,7 +55,6 @@ class FlatParamGroup:
         self.steps = 0
         self._work = None
         self._synced = False
-        from . import streams
         # shared pool (hardware queues are few): slot 2 is also the training step's coordinate-gradient stream, which is
         # idle by the time the collective is issued (after the whole backward)
         self._stream = streams.side(dev, 2) if dev.type == 'cuda' else None
@@ -142,7 +141,6 @@ class FlatParamGroup:
     def grad_sumsq(self):
         """Sum of squares of the (reduced) flat gradient as a device scalar: this group's share of
         the model-wide norm of ``clip_grad_norm_``."""
-        from . import ops
         if not self._synced:
             self.sync_grads()
         self.wait()
@@ -156,7 +154,6 @@ class FlatParamGroup:
         detector's remaining parameters, which the caller owns).  After the all-reduce the buffer
         holds the SUM over ranks, so the mean's norm is ||sum|| / world.  No host sync.
         Returns the total squared norm (of the mean gradient), device scalar."""
-        from . import ops
         ss = self.grad_sumsq()
         w = float(self.world_size)
         total = ss / (w * w) if w != 1.0 else ss
@@ -169,7 +166,6 @@ class FlatParamGroup:
         """Multiply the gradients of ``params`` (a subset of this group) by ``factor``, e.g. the reference's optional
         ``OptimizerHook_`` (OptimizerHook.py:27-29): ``roi_head.mask_predictor`` gradients x 0.05 between the
         clipping and the optimizer step.  Adjacent parameters are scaled as one run of the flat buffer."""
-        from . import ops
         if not self._synced:
             self.sync_grads()
         self.wait()
@@ -189,7 +185,6 @@ class FlatParamGroup:
     def sgd_step(self, lr=0.02, momentum=0.9, weight_decay=1e-4, grad_scale=1.0):
         """Fused SGD on the flat buffer; the 1/world averaging (times ``grad_scale``, e.g. the
         clip coefficient of ``clip_grad_norm``) rides in the kernel."""
-        from . import ops
         if not self._synced:                 # no all_reduce_async() this step (single process)
             self.sync_grads()
         self.wait()

@@ -1,0 +1,265 @@
+"""The parameter holders and weight caches every head, neck and backbone is made of.  They own parameters under the
+reference's ``state_dict`` keys and launch through ``ops``; this module imports none of the modules that use them."""
+import torch
+import torch.nn as nn
+
+from . import ops
+
+# ops.conv2d's 3x3 builds stage whole rows of the map (csrc/conv_igemm.hip: the plane of a 128-pixel tile), which stops
+# fitting their LDS at 169 pixels of width; the 3x3 kernel of csrc/conv_dilated.hip stages 8 x 16 blocks and takes any
+# width, from the same packed weights, exact fp32 too.  rpn_conv runs on it (dilation 1) on maps wider than this -- the
+# stride-4 and stride-8 maps of a 1333 x 800 image -- and on ops.conv2d below; the width alone decides, so a map's kernel
+# does not depend on the batch.
+CONV2D_3X3_MAX_WIDTH = 128
+
+# backbones/resnet.py:356-362 (ResNet.arch_settings): depth -> blocks per stage; 18 / 34 are BasicBlock nets
+_STAGE_BLOCKS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}
+_BASIC_BLOCK_DEPTHS = (18, 34)
+
+
+class _Packed:
+    """Cache of kernel-layout weights, refreshed when the parameter changes."""
+
+    def __init__(self):
+        self._c = {}
+
+    def get(self, key, param, fn, job=None, precision='fp32'):
+        """``job`` = (transpose_flip, src_channels | None, lo | None, hi | None): the pack is dm_conv_pack_weight of
+        the parameter itself (or of its input-channel window lo:hi); such packs of contiguous device parameters are
+        registered with ops.PACK_PLAN and refreshed together in one launch.  Anything else goes through ``fn``.
+        ``precision='bf16x3'``: ``fn`` makes the bf16x3 layout (inference only: never a PACK_PLAN job), cached under a key
+        of its own, so that both layouts of a weight coexist."""
+        if precision != 'fp32':
+            key, job = (precision, key), None
+        if job is not None and param.is_cuda and param.dim() == 4 and param.is_contiguous():
+            e = self._c.get(key)
+            if e is None or e[0] != 'plan' or e[1]['param']() is not param:
+                e = ('plan', ops.PACK_PLAN.register(param, *job))
+                self._c[key] = e
+            with torch.no_grad():
+                return ops.PACK_PLAN.get(e[1])
+        ver = (param.data_ptr(), param._version, param.device, ops.WEIGHT_EPOCH[0])
+        e = self._c.get(key)
+        if e is None or e[0] != ver:
+            with torch.no_grad():
+                e = (ver, fn(param.detach().contiguous()))
+            self._c[key] = e
+        return e[1]
+
+    def get_multi(self, key, params, fn):
+        """One pack made from several parameters (a table): ``fn()`` runs again when any of them changes."""
+        ver = tuple((p.data_ptr(), p._version) for p in params) + (params[0].device, ops.WEIGHT_EPOCH[0])
+        e = self._c.get(key)
+        if e is None or e[0] != ver:
+            with torch.no_grad():
+                e = (ver, fn())
+            self._c[key] = e
+        return e[1]
+
+
+class _Conv(nn.Module):
+    """Parameter holder named like nn.Conv2d (weight [Cout,Cin,k,k], bias)."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, bias=True):
+        super().__init__()
+        self.in_channels, self.out_channels, self.kernel_size = in_channels, out_channels, kernel_size
+        self.weight = nn.Parameter(torch.empty(out_channels, in_channels, kernel_size, kernel_size))
+        self.bias = nn.Parameter(torch.zeros(out_channels)) if bias else None
+        nn.init.kaiming_normal_(self.weight, mode='fan_out', nonlinearity='relu')
+        self._pk = _Packed()
+
+    exact = False         # True: always the exact fp32 kernel, whatever the precision mode (MaskPre, the selector)
+
+    def packed(self, src_channels=None, precision='fp32'):
+        key = tuple(src_channels) if src_channels is not None else (self.in_channels,)
+        return self._pk.get(key, self.weight, lambda w: ops.pack_conv_weight(w, src_channels=list(key), precision=precision),
+                            job=(False, list(key), None, None), precision=precision)
+
+    def precision_for(self, H, W):
+        """The kernel this layer's convolution of an H x W map runs now (ops.conv_precision_for)."""
+        return 'fp32' if self.exact else ops.conv_precision_for(self.out_channels, self.kernel_size, H, W)
+
+    def run(self, srcs, relu=False, out=None, out_ch_offset=0):
+        b = self.bias.detach() if self.bias is not None else None
+        if isinstance(srcs, torch.Tensor):
+            srcs = [srcs]
+        wq = self.packed([s.shape[1] for s in srcs], self.precision_for(srcs[0].shape[2], srcs[0].shape[3]))
+        return ops.conv2d(srcs, wq, b, self.out_channels, self.kernel_size, relu=relu, out=out,
+                          out_ch_offset=out_ch_offset)
+
+
+def _exact_conv(cin, cout, k):
+    c = _Conv(cin, cout, k)
+    c.exact = True          # a changed score reorders proposals: the bf16x3 mode does not reach the RPN
+    return c
+
+
+def _conv_weight(cout, cin, k):
+    """nn.Conv2d(bias=False) parameter holder: the key is ``weight`` alone."""
+    return _Conv(cin, cout, k, bias=False)
+
+
+class ConvModule(nn.Module):
+    """mmcv ConvModule without norm: conv(bias) + ReLU; keys ``conv.weight/bias``."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, padding=0, dilation=1, conv_cfg=None, norm_cfg=None,
+                 act_cfg=dict(type='ReLU')):
+        super().__init__()
+        if conv_cfg is not None or norm_cfg is not None:
+            raise NotImplementedError('conv_cfg / norm_cfg are None in configs/dynamask')
+        if dilation != 1 or padding != kernel_size // 2:
+            raise NotImplementedError('only "same" stride-1 convolutions are on the path')
+        self.conv = _Conv(in_channels, out_channels, kernel_size)
+        self.with_activation = act_cfg is not None
+
+    def forward(self, x):
+        return self.conv.run(x, relu=self.with_activation)
+
+
+class _BN(nn.Module):
+    """BatchNorm2d parameter/buffer holder (keys as nn.BatchNorm2d)."""
+
+    def __init__(self, c, eps=1e-5, momentum=0.1):
+        super().__init__()
+        self.eps, self.momentum = eps, momentum
+        self.weight = nn.Parameter(torch.ones(c))
+        self.bias = nn.Parameter(torch.zeros(c))
+        self.register_buffer('running_mean', torch.zeros(c))
+        self.register_buffer('running_var', torch.ones(c))
+        self.register_buffer('num_batches_tracked', torch.tensor(0, dtype=torch.long))
+
+
+class _Linear(nn.Module):
+    """nn.Linear parameter holder at nn.Linear's own initialisation; the product runs on the fp32 MFMA FC kernel
+    (dm_fc_fwd)."""
+
+    def __init__(self, cin, cout):
+        super().__init__()
+        self.in_features, self.out_features = cin, cout
+        self.weight, self.bias = (nn.Parameter(t) for t in self._init(cin, cout))
+        self._pk = _Packed()      # transposed packed weights of the backward's data-gradient GEMM
+
+    @staticmethod
+    def _init(cin, cout):
+        lin = nn.Linear(cin, cout)
+        return lin.weight.detach().clone(), lin.bias.detach().clone()
+
+    def run(self, x, relu=False):
+        return ops.fc(x.contiguous(), self.weight.detach(), self.bias.detach(), relu=relu)
+
+
+class _FC(_Linear):
+    """``_Linear`` as the bbox heads start it: xavier-uniform weight, zero bias."""
+
+    @staticmethod
+    def _init(cin, cout):
+        return nn.init.xavier_uniform_(torch.empty(cout, cin)), torch.zeros(cout)
+
+
+def fold_bn(pairs):
+    """Eval-mode BatchNorm folded into the convolution in front of it: ``pairs`` = [(conv weight [Cout, Cin_i, k, k], bn),
+    ...] -> (w' [Cout, sum Cin_i, k, k], b' [Cout]) with, per pair, s = gamma / sqrt(running_var + eps),
+    w' = w * s[:, None, None, None], b' = beta - running_mean * s.  Several pairs are the summed outputs of convolutions
+    of different inputs as ONE convolution of their concatenation: the weights side by side along Cin, the biases added.
+    All of it in float64, rounded once to float32."""
+    ws, b = [], None
+    for w, bn in pairs:
+        s = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
+        ws.append(w.detach().double() * s[:, None, None, None])
+        bi = bn.bias.detach().double() - bn.running_mean.detach().double() * s
+        b = bi if b is None else b + bi
+    return torch.cat(ws, 1).float().contiguous(), b.float().contiguous()
+
+
+class _FoldedConv:
+    """Packed folded weights + bias of one launch, cached like ``_Packed`` caches packed weights: made again when any of
+    the convolution weights, BatchNorm parameters or running statistics changes (``load_state_dict`` copies in place and
+    moves their versions; a move to another device changes their addresses)."""
+
+    def __init__(self, pairs, src_channels):
+        self.modules, self.src_channels = pairs, list(src_channels)      # [(convolution holder, BatchNorm holder), ...]
+        self._pk = _Packed()
+
+    def _pairs(self):
+        return [(conv.weight, bn) for conv, bn in self.modules]
+
+    def _tensors(self):
+        return [t for w, bn in self._pairs() for t in (w, bn.weight, bn.bias, bn.running_mean, bn.running_var)]
+
+    def folded(self):
+        """(w', b') in torch's layout, on the parameters' device (CPU included)."""
+        return self._pk.get_multi('fold', self._tensors(), lambda: fold_bn(self._pairs()))
+
+    def packed(self):
+        """(packed w', b') for ops.conv2d: always the exact fp32 layout, whatever the precision mode."""
+        def make():
+            w, b = self.folded()
+            return ops.pack_conv_weight(w, src_channels=self.src_channels), b
+        return self._pk.get_multi('pack', self._tensors(), make)
+
+
+class BNConvModule(nn.Module):
+    """mmcv ConvModule(bias=False, norm_cfg=dict(type='BN')): keys ``conv.weight``, ``bn.*``.  A parameter holder: the
+    block that owns it folds the BatchNorm and launches."""
+
+    def __init__(self, in_channels, out_channels, kernel_size):
+        super().__init__()
+        self.conv = _conv_weight(out_channels, in_channels, kernel_size)
+        self.bn = _BN(out_channels)
+
+
+class Bottleneck(nn.Module):
+    """backbones/resnet.py:95-300 (stride 1, no downsample, style 'pytorch') in eval mode; keys ``conv{1,2,3}.weight``,
+    ``bn{1,2,3}.*``.  Three launches: 1x1 + ReLU, 3x3 + ReLU, then the 1x1 back to ``inplanes`` with the ``accumulate |
+    ReLU`` epilogue -- relu(x + conv + bias), the residual sum before the activation -- written IN PLACE into ``x``.
+    ``downsample=True`` (the first block of a ResNet layer, shared_heads.ResLayer): the identity path is
+    ``downsample.0`` (1x1, ``inplanes`` -> 4 ``planes``) + ``downsample.1`` (BatchNorm), and the block is three launches
+    too -- conv1, conv2, then ONE two-source 1x1 of [conv2 output, x] by [W3' | Wd'] with bias b3' + bd' and ReLU (the
+    BasicResBlock pattern) into a NEW tensor: ``x`` is not written.  A stride (style 'caffe': in conv1 and
+    ``downsample.0``, both 1x1) is the caller's subsampling of ``x``.
+
+    The backbone's arguments (backbones.ResNet; the defaults are the block above).  ``stride=2`` (with ``downsample``):
+    style 'caffe' runs the block on ``ops.subsample2(x)``; style 'pytorch' runs conv1 at full size, conv2 through
+    ``ops.conv3x3_s2`` (one workgroup per tile walks all of K: ``splits=1``) and closes with the two-source 1x1 of
+    [conv2 output, ``ops.subsample2(x)``].  ``wide_from``: a width above which the stride-1 conv2 runs on
+    ``ops.conv3x3_dil`` (dilation 1, any width, the same packed weights) instead of ``ops.conv2d``."""
+    expansion = 4
+
+    def __init__(self, inplanes, planes, downsample=False, stride=1, style='pytorch', wide_from=None):
+        super().__init__()
+        if not downsample and inplanes != planes * self.expansion:
+            raise NotImplementedError('Bottleneck: no downsample path (DoubleConvFCBBoxHead: planes = inplanes / 4)')
+        if stride not in (1, 2) or style not in ('pytorch', 'caffe') or (stride == 2 and not downsample):
+            raise NotImplementedError(f'Bottleneck: stride={stride}, style={style!r}, downsample={downsample}; stride 1, or '
+                                      "stride 2 with a downsample path, in style 'pytorch' or 'caffe' are built")
+        self.stride, self.style, self.wide_from = stride, style, wide_from
+        self.inplanes, self.planes = inplanes, planes
+        out = planes * self.expansion
+        self.conv1, self.bn1 = _conv_weight(planes, inplanes, 1), _BN(planes)
+        self.conv2, self.bn2 = _conv_weight(planes, planes, 3), _BN(planes)
+        self.conv3, self.bn3 = _conv_weight(out, planes, 1), _BN(out)
+        self._f = [_FoldedConv([(c, bn)], [c.in_channels]) for c, bn in ((self.conv1, self.bn1), (self.conv2, self.bn2))]
+        if downsample:
+            self.downsample = nn.Sequential(_conv_weight(out, inplanes, 1), _BN(out))
+            self._f.append(_FoldedConv([(self.conv3, self.bn3), (self.downsample[0], self.downsample[1])], [planes, inplanes]))
+        else:
+            self.downsample = None
+            self._f.append(_FoldedConv([(self.conv3, self.bn3)], [planes]))
+
+    def forward(self, x):
+        """Without ``downsample``: ``x`` [N, inplanes, H, W] is overwritten with the block's output and returned.  With
+        it: a new [N, 4 planes, H, W] tensor."""
+        (w1, b1), (w2, b2), (w3, b3) = (f.packed() for f in self._f)
+        if self.stride == 2 and self.style == 'caffe':
+            x = ops.subsample2(x)
+        h = ops.conv2d(x, w1, b1, self.planes, 1, relu=True)
+        if self.stride == 2 and self.style == 'pytorch':
+            h = ops.conv3x3_s2(h, w2, b2, self.planes, relu=True, splits=1)
+            x = ops.subsample2(x)
+        elif self.wide_from is not None and h.shape[3] > self.wide_from:
+            h = ops.conv3x3_dil(h, w2, b2, self.planes, 1, relu=True)
+        else:
+            h = ops.conv2d(h, w2, b2, self.planes, 3, relu=True)
+        if self.downsample is not None:
+            return ops.conv2d([h, x], w3, b3, self.planes * self.expansion, 1, relu=True)
+        return ops.conv2d(h, w3, b3, self.inplanes, 1, relu=True, out=x, accumulate=True)

@@ -18,96 +18,12 @@ import math
 import torch
 import torch.nn as nn
 
+from . import losses  # noqa: F401  (registers CrossEntropyLoss, GridHead's default loss_grid)
 from . import ops
+from .layers import ConvModule, _Conv, _Packed
+from .postprocess import _to_host, group_mask_scores, paste_segms, select_label_channel
 from .registry import HEADS, UPSAMPLE_LAYERS, build_loss
-
-
-class _Packed:
-    """Cache of kernel-layout weights, refreshed when the parameter changes."""
-
-    def __init__(self):
-        self._c = {}
-
-    def get(self, key, param, fn, job=None, precision='fp32'):
-        """``job`` = (transpose_flip, src_channels | None, lo | None, hi | None): the pack is dm_conv_pack_weight of
-        the parameter itself (or of its input-channel window lo:hi); such packs of contiguous device parameters are
-        registered with ops.PACK_PLAN and refreshed together in one launch.  Anything else goes through ``fn``.
-        ``precision='bf16x3'``: ``fn`` makes the bf16x3 layout (inference only: never a PACK_PLAN job), cached under a key
-        of its own, so that both layouts of a weight coexist."""
-        if precision != 'fp32':
-            key, job = (precision, key), None
-        if job is not None and param.is_cuda and param.dim() == 4 and param.is_contiguous():
-            e = self._c.get(key)
-            if e is None or e[0] != 'plan' or e[1]['param']() is not param:
-                e = ('plan', ops.PACK_PLAN.register(param, *job))
-                self._c[key] = e
-            with torch.no_grad():
-                return ops.PACK_PLAN.get(e[1])
-        ver = (param.data_ptr(), param._version, param.device, ops.WEIGHT_EPOCH[0])
-        e = self._c.get(key)
-        if e is None or e[0] != ver:
-            with torch.no_grad():
-                e = (ver, fn(param.detach().contiguous()))
-            self._c[key] = e
-        return e[1]
-
-    def get_multi(self, key, params, fn):
-        """One pack made from several parameters (a table): ``fn()`` runs again when any of them changes."""
-        ver = tuple((p.data_ptr(), p._version) for p in params) + (params[0].device, ops.WEIGHT_EPOCH[0])
-        e = self._c.get(key)
-        if e is None or e[0] != ver:
-            with torch.no_grad():
-                e = (ver, fn())
-            self._c[key] = e
-        return e[1]
-
-
-class _Conv(nn.Module):
-    """Parameter holder named like nn.Conv2d (weight [Cout,Cin,k,k], bias)."""
-
-    def __init__(self, in_channels, out_channels, kernel_size, bias=True):
-        super().__init__()
-        self.in_channels, self.out_channels, self.kernel_size = in_channels, out_channels, kernel_size
-        self.weight = nn.Parameter(torch.empty(out_channels, in_channels, kernel_size, kernel_size))
-        self.bias = nn.Parameter(torch.zeros(out_channels)) if bias else None
-        nn.init.kaiming_normal_(self.weight, mode='fan_out', nonlinearity='relu')
-        self._pk = _Packed()
-
-    exact = False         # True: always the exact fp32 kernel, whatever the precision mode (MaskPre, the selector)
-
-    def packed(self, src_channels=None, precision='fp32'):
-        key = tuple(src_channels) if src_channels is not None else (self.in_channels,)
-        return self._pk.get(key, self.weight, lambda w: ops.pack_conv_weight(w, src_channels=list(key), precision=precision),
-                            job=(False, list(key), None, None), precision=precision)
-
-    def precision_for(self, H, W):
-        """The kernel this layer's convolution of an H x W map runs now (ops.conv_precision_for)."""
-        return 'fp32' if self.exact else ops.conv_precision_for(self.out_channels, self.kernel_size, H, W)
-
-    def run(self, srcs, relu=False, out=None, out_ch_offset=0):
-        b = self.bias.detach() if self.bias is not None else None
-        if isinstance(srcs, torch.Tensor):
-            srcs = [srcs]
-        wq = self.packed([s.shape[1] for s in srcs], self.precision_for(srcs[0].shape[2], srcs[0].shape[3]))
-        return ops.conv2d(srcs, wq, b, self.out_channels, self.kernel_size, relu=relu, out=out,
-                          out_ch_offset=out_ch_offset)
-
-
-class ConvModule(nn.Module):
-    """mmcv ConvModule without norm: conv(bias) + ReLU; keys ``conv.weight/bias``."""
-
-    def __init__(self, in_channels, out_channels, kernel_size, padding=0, dilation=1, conv_cfg=None, norm_cfg=None,
-                 act_cfg=dict(type='ReLU')):
-        super().__init__()
-        if conv_cfg is not None or norm_cfg is not None:
-            raise NotImplementedError('conv_cfg / norm_cfg are None in configs/dynamask')
-        if dilation != 1 or padding != kernel_size // 2:
-            raise NotImplementedError('only "same" stride-1 convolutions are on the path')
-        self.conv = _Conv(in_channels, out_channels, kernel_size)
-        self.with_activation = act_cfg is not None
-
-    def forward(self, x):
-        return self.conv.run(x, relu=self.with_activation)
+from .train_path import FCNMaskHeadFn
 
 
 class DeformConv2dPack(nn.Module):
@@ -233,75 +149,6 @@ def run_steps(gen):
             next(gen)
     except StopIteration as e:
         return e.value
-
-
-def _paste_geometry(det_bboxes, ori_shape, scale_factor, rescale):
-    """The canvas size and the boxes in canvas pixels, as both heads' ``get_seg_masks`` derive them
-    (dynamask_head.py:293-305 = fcn_mask_head.py:176-186)."""
-    import numpy as np
-    bboxes = det_bboxes[:, :4]
-    if rescale:
-        img_h, img_w = ori_shape[:2]
-    else:
-        img_h = int(np.round(ori_shape[0] * scale_factor).astype(np.int32))
-        img_w = int(np.round(ori_shape[1] * scale_factor).astype(np.int32))
-        scale_factor = 1.0
-    if not isinstance(scale_factor, (float, torch.Tensor)):
-        scale_factor = bboxes.new_tensor(scale_factor)
-    return (bboxes / scale_factor).contiguous(), int(img_h), int(img_w)
-
-
-def _to_host(*tensors):
-    """device -> host as the reference does (``t.cpu().numpy()``), but every tensor into a fresh pinned buffer (PCIe rate
-    instead of the pageable-memory rate; the reference copies each mask on its own), all copies non-blocking and ONE
-    synchronisation of the current stream -> the numpy arrays."""
-    hosts = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in tensors]
-    for h, t in zip(hosts, tensors):
-        h.copy_(t, non_blocking=True)
-    torch.cuda.current_stream().synchronize()
-    return [h.numpy() for h in hosts]
-
-
-def _mask_threshold(rcnn_test_cfg):
-    threshold = rcnn_test_cfg.mask_thr_binary
-    if threshold < 0:
-        raise NotImplementedError('visualisation mode (mask_thr_binary < 0) is not on the path')
-    return threshold
-
-
-def select_label_channel(mask_pred, labels):
-    """[n, C, S, S] -> the channel of every detection's label [n, 1, S, S] (fcn_mask_head.py:211-212): one gather when
-    C > 1 (the sigmoid of the paste commutes with it)."""
-    if mask_pred.shape[1] > 1:
-        mask_pred = mask_pred[torch.arange(len(mask_pred), device=mask_pred.device), labels.to(mask_pred.device)][:, None]
-    return mask_pred.contiguous()
-
-
-def paste_segms(mask_pred, det_bboxes, det_labels, rcnn_test_cfg, ori_shape, scale_factor, rescale, encode=False,
-                apply_sigmoid=True, num_classes=None, labels_host=None):
-    """The paste of every ``get_seg_masks`` / ``get_seg_rles`` (dynamask_head.py:279-342, fcn_mask_head.py:151-237) and
-    of the RoI heads' one-image mask tests: ``mask_pred`` [n, 1, S, S] (the label channel; ``apply_sigmoid``: logits)
-    pasted into the image, thresholded, by one kernel for all detections.  Bitmaps: ONE device -> host copy of all masks
-    -> (h, w) bool arrays.  ``encode``: ``get_seg_masks`` followed by ``encode_mask_results`` (core/mask/utils.py:36-63)
-    without the bitmaps -- paste, threshold and run-length encoding on the device, only run boundaries are copied to the
-    host: COCO RLE dicts, what ``mask_util.encode(np.array(m[:, :, None], order='F'))[0]`` yields for the bitmap.
-    Returns one entry per detection, or with ``num_classes`` the per-class lists (``cls_segms``: a class's detections in
-    detection order; ``labels_host``: ``det_labels`` already on the host)."""
-    bboxes, img_h, img_w = _paste_geometry(det_bboxes, ori_shape, scale_factor, rescale)
-    threshold = _mask_threshold(rcnn_test_cfg)
-    if len(mask_pred) == 0:
-        return [] if num_classes is None else [[] for _ in range(num_classes)]
-    if encode:
-        segs = ops.paste_rle(mask_pred, bboxes, img_h, img_w, threshold, apply_sigmoid=apply_sigmoid)
-    else:
-        im, = _to_host(ops.paste_masks(mask_pred, bboxes, img_h, img_w, threshold, apply_sigmoid=apply_sigmoid))
-        segs = list(im)
-    if num_classes is None:
-        return segs
-    cls_segms = [[] for _ in range(num_classes)]
-    for c, segm in zip(det_labels.tolist() if labels_host is None else labels_host, segs):
-        cls_segms[c].append(segm)
-    return cls_segms
 
 
 @HEADS.register_module()
@@ -736,7 +583,6 @@ class FCNMaskHead(nn.Module):
 
     def forward(self, x):
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            from .train_path import FCNMaskHeadFn
             return FCNMaskHeadFn.apply(self, x, *list(self.parameters()))
         for conv in self.convs:
             x = conv(x)
@@ -1391,16 +1237,6 @@ class PointRefineMaskHead(nn.Module):
 
 
 # ---------------------------------------------------------------- Mask Scoring R-CNN: MaskIoUHead (inference)
-def _to_host_pending(*tensors):
-    """Enqueue device -> host copies into fresh pinned buffers WITHOUT a synchronisation: the buffers hold the values once
-    the current stream has been synchronised by the caller's next host wait (the mask paste's copy, or its RLE
-    collection).  -> the pinned host tensors."""
-    hosts = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in tensors]
-    for h, t in zip(hosts, tensors):
-        h.copy_(t, non_blocking=True)
-    return hosts
-
-
 @HEADS.register_module()
 class MaskIoUHead(nn.Module):
     """``MaskIoUHead`` -- mmdet/models/roi_heads/mask_heads/maskiou_head.py, inference: the IoU of a detection's mask
@@ -1493,13 +1329,6 @@ class MaskIoUHead(nn.Module):
     def loss(self, *a, **k):
         raise NotImplementedError('MaskIoUHead.loss: Mask Scoring R-CNN training is unreachable in the reference fork '
                                   '(FCNMaskHead.loss is broken before it, Quirk Q5)')
-
-
-def group_mask_scores(scores, labels, num_classes):
-    """Host arrays [n] -> ``[scores[labels == i] for i in range(num_classes)]`` (maskiou_head.py:178-181)."""
-    import numpy as np
-    scores, labels = np.asarray(scores), np.asarray(labels)
-    return [scores[labels == i] for i in range(num_classes)]
 
 
 @HEADS.register_module()
@@ -1791,7 +1620,6 @@ class GridHead(nn.Module):
         for neighbors in self.neighbor_points:
             self.forder_trans.append(nn.ModuleList([_GridTransition(point_feat_channels) for _ in neighbors]))
             self.sorder_trans.append(nn.ModuleList([_GridTransition(point_feat_channels) for _ in neighbors]))
-        from . import losses  # noqa: F401  (registers CrossEntropyLoss)
         self.loss_grid = build_loss(loss_grid)
         self._pk = _Packed()
 

@@ -5,7 +5,7 @@ the RoI heads start from, made from the backbone's stages.
 is ONE ``ops.conv2d_up_add`` (``dm_conv2d_up_add_fwd``): the 1x1 lateral convolution whose epilogue adds the merged lateral
 above it, read through two nearest-neighbour index tables -- ``laterals[i - 1] += F.interpolate(laterals[i])``
 (fpn.py:177-186) without the upsampled map and without a second pass over the lateral.  The level convolutions are 3x3
-``ops.conv2d`` launches, ``ops.conv3x3_dil`` at dilation 1 on maps wider than ``dense_heads.CONV2D_3X3_MAX_WIDTH`` (the
+``ops.conv2d`` launches, ``ops.conv3x3_dil`` at dilation 1 on maps wider than ``layers.CONV2D_3X3_MAX_WIDTH`` (the
 width alone decides, so a map's kernel does not depend on the batch); extra levels are ``ops.subsample2``
 (``F.max_pool2d(x, 1, stride=2)``) or ``ops.conv3x3_s2``.  Every convolution is exact fp32 in every precision mode: a
 changed feature reorders the proposals made from it.  The host never waits.
@@ -19,7 +19,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .dense_heads import CONV2D_3X3_MAX_WIDTH, _exact_conv
+from .layers import CONV2D_3X3_MAX_WIDTH, _exact_conv
 from .registry import NECKS
 
 

@@ -8,7 +8,7 @@ import ctypes
 
 import torch
 
-from . import _abi, hazard
+from . import _abi, _lib, hazard
 from . import precision as _precision
 from ._lib import check, lib
 
@@ -806,7 +806,6 @@ class PackPlan:
             self._refresh(plan)
 
     def _refresh(self, plan):
-        from ._lib import PackJob
         live = []
         for e in plan.entries:
             p = e['param']()
@@ -824,7 +823,7 @@ class PackPlan:
                 raise RuntimeError('PackPlan: a kernel-layout weight is stale inside a HIP-graph capture and its job table '
                                    'is not on the device yet (the upload cannot be captured: run the path once eagerly first)')
             if ids != plan.table_ids:
-                arr = (PackJob * len(todo))()
+                arr = (_lib.PackJob * len(todo))()      # (derived from the header at first use)
                 for j, (e, p) in zip(arr, todo):
                     j.w, j.w_packed = p.data_ptr(), e['out'].data_ptr()
                     j.Cout, j.Cin, j.ksize, j.transpose_flip = e['cout'], e['cin'], e['ks'], e['flip']

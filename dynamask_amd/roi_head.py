@@ -8,22 +8,22 @@ branch, the one-image / batched / test-time-augmentation entry points and one ma
 ``_mask_forward``, ``get_mask_label`` (MaskPre + straight-through Gumbel selector), ``_mask_forward_train`` (assigner +
 sampler, bbox branch losses, mask targets on the device; dynamask_roi_head.py:21-46) and the merged logits of the test.
 """
+import os
+
+import numpy as np
 import torch
 import torch.nn as nn
 
-import os
-
-from . import ops
-from .mask_heads import _Conv
-from .registry import HEADS, build_head, build_roi_extractor
-
-
-def _bbox2result_host(bboxes, labels, num_classes):
-    """bbox_heads.bbox2result on host arrays already copied (the batched call copies all images' detections at once)."""
-    import numpy as np
-    if bboxes.shape[0] == 0:
-        return [np.zeros((0, 5), dtype=np.float32) for _ in range(num_classes)]
-    return [bboxes[labels == i, :] for i in range(num_classes)]
+# the modules whose classes the configs name: importing them here fills the registries the constructors build from
+from . import bbox_heads, losses, mask_heads, roi_extractors, shared_heads  # noqa: F401
+from . import ops, streams, train_path
+from .assigners import build_assigner, build_sampler
+from .graphs import BATCH_BUCKETS, BUCKETS, GraphedMaskLogits
+from .layers import _BN, _Conv, _Linear
+from .mask_heads import run_steps
+from .postprocess import (_bbox2result_host, _mask_threshold, _paste_geometry, _to_host, _to_host_pending, bbox2result,
+                          group_mask_scores, multiclass_nms, multiclass_nms_batch, paste_segms, select_label_channel)
+from .registry import HEADS, SHARED_HEADS, build, build_head, build_roi_extractor
 
 
 def bbox2roi(bbox_list):
@@ -43,36 +43,6 @@ def bbox2roi(bbox_list):
 FUSED_MERGE_TAIL = [os.environ.get('DM_FUSED_MERGE_TAIL', '1') != '0']
 # training: MaskPre's conv1 on the P2 map + a 128-channel extraction (train_path.MaskPreMapFn); 0 = the reference's order
 _MASKPRE_ON_MAP = os.environ.get('DM_MASKPRE_MAP', '1') != '0'
-
-
-class _BN(nn.Module):
-    """BatchNorm2d parameter/buffer holder (keys as nn.BatchNorm2d)."""
-
-    def __init__(self, c, eps=1e-5, momentum=0.1):
-        super().__init__()
-        self.eps, self.momentum = eps, momentum
-        self.weight = nn.Parameter(torch.ones(c))
-        self.bias = nn.Parameter(torch.zeros(c))
-        self.register_buffer('running_mean', torch.zeros(c))
-        self.register_buffer('running_var', torch.ones(c))
-        self.register_buffer('num_batches_tracked', torch.tensor(0, dtype=torch.long))
-
-
-class _Linear(nn.Module):
-    """nn.Linear parameter holder; runs on the fp32 MFMA FC kernel (dm_fc_fwd)."""
-
-    def __init__(self, cin, cout):
-        super().__init__()
-        self.in_features, self.out_features = cin, cout
-        lin = nn.Linear(cin, cout)
-        self.weight = nn.Parameter(lin.weight.detach().clone())
-        self.bias = nn.Parameter(lin.bias.detach().clone())
-        from .mask_heads import _Packed
-        self._pk = _Packed()      # packed (transposed) weights of the backward's data-gradient GEMM
-
-    def run(self, x, relu=False):
-        return ops.fc(x.reshape(x.shape[0], self.in_features).contiguous(), self.weight.detach(), self.bias.detach(),
-                      relu=relu)
 
 
 class MaskPre(nn.Module):
@@ -167,7 +137,6 @@ class StandardRoIHead(nn.Module):
         self.bbox_roi_extractor_cfg = bbox_roi_extractor
         self.bbox_head_cfg = bbox_head
         if bbox_head is not None:
-            from . import bbox_heads  # noqa: F401  (registers Shared2FCBBoxHead)
             self.bbox_roi_extractor = build_roi_extractor(bbox_roi_extractor)
             self.bbox_head = build_head(bbox_head)
         # standard_roi_head.py:28-44 / base_roi_head.py (shared_head): the C4 configs' per-RoI ResNet stage behind the
@@ -177,8 +146,6 @@ class StandardRoIHead(nn.Module):
             raise NotImplementedError(f'{type(self).__name__}: shared_head / the shared RoI extractor (mask_roi_extractor=None) '
                                       'are built for StandardRoIHead alone (the C4 configs)')
         if shared_head is not None:
-            from . import shared_heads  # noqa: F401  (registers ResLayer)
-            from .registry import SHARED_HEADS, build
             self.shared_head = build(shared_head, SHARED_HEADS)
         if mask_head is not None:
             if mask_roi_extractor is not None:
@@ -203,7 +170,6 @@ class StandardRoIHead(nn.Module):
         self.bbox_assigner = None
         self.bbox_sampler = None
         if self.train_cfg and getattr(self.train_cfg, 'get', None) and self.train_cfg.get('assigner') is not None:
-            from .assigners import build_assigner, build_sampler
             self.bbox_assigner = build_assigner(self.train_cfg.assigner)
             self.bbox_sampler = build_sampler(self.train_cfg.sampler, context=self)
 
@@ -293,7 +259,6 @@ class StandardRoIHead(nn.Module):
         """standard_roi_head.py:147-160."""
         rois = bbox2roi([res.bboxes for res in sampling_results]).contiguous()
         if torch.is_grad_enabled():
-            from . import train_path
             bbox_feats = train_path.roi_extract_train(self.bbox_roi_extractor, x, rois)
         else:
             bbox_feats = self.bbox_roi_extractor(x[:self.bbox_roi_extractor.num_inputs], rois)
@@ -353,7 +318,6 @@ class StandardRoIHead(nn.Module):
     @torch.no_grad()
     def simple_test(self, x, proposal_list, img_metas, proposals=None, rescale=False, encode=False):
         """standard_roi_head.py:217-236: boxes, then masks of the kept detections."""
-        from .bbox_heads import bbox2result
         det_bboxes, det_labels = self.simple_test_bboxes(x, img_metas, proposal_list, self.test_cfg, rescale=rescale)
         bbox_results = bbox2result(det_bboxes, det_labels, self._bbox_num_classes())
         if not self.with_mask:
@@ -429,7 +393,6 @@ class StandardRoIHead(nn.Module):
         (h, w) bool masks: the detections' ``simple_test_mask_logits``, their label channel pasted into the image.
         ``encode=True`` (extension): per-class lists of COCO RLE dicts instead, i.e. the result after the caller's
         ``encode_mask_results`` (apis/test.py:52-57), produced on the device."""
-        from .mask_heads import paste_segms, select_label_channel
         num_classes = self._segm_num_classes()
         if det_bboxes.shape[0] == 0:
             return self._mask_test_result([[] for _ in range(num_classes)], None, 0, 0)
@@ -470,7 +433,6 @@ class StandardRoIHead(nn.Module):
         a pinned buffer: no host wait per image."""
         if isinstance(scale_factor, float):
             return scale_factor
-        import numpy as np
         return torch.from_numpy(np.ascontiguousarray(scale_factor)).pin_memory().to(device, non_blocking=True)
 
     def _mask_boxes(self, det_bboxes, scale_factor, rescale):
@@ -513,8 +475,6 @@ class StandardRoIHead(nn.Module):
         """``simple_test_mask`` of B images: per image the per-class lists of (h, w) bool masks (``encode``: COCO RLE
         dicts) of its detections, on its own canvas (``ori_shape``, ``scale_factor``).  One mask chain, one paste launch
         (dm_paste_masks_multi / dm_paste_rle_multi) and one device -> host copy for all images."""
-        from .mask_heads import _mask_threshold, _paste_geometry, _to_host, select_label_channel
-        import numpy as np
         B = self._check_batch(img_metas, det_bboxes_list=det_bboxes_list, det_labels_list=det_labels_list)
         self._check_metas(img_metas, ('ori_shape', 'scale_factor'))
         num_classes = self._segm_num_classes()
@@ -562,8 +522,7 @@ class StandardRoIHead(nn.Module):
     def batch_simple_test_bboxes(self, x, img_metas, proposals, rcnn_test_cfg, rescale=False):
         """``simple_test_bboxes`` of B images -> list of B (dets [k, 5], labels [k]): one bbox branch over the
         proposals of all images, per-image decode (its own ``img_shape`` clip and ``scale_factor``), one segmented NMS
-        (bbox_heads.multiclass_nms_batch)."""
-        from .bbox_heads import multiclass_nms_batch
+        (postprocess.multiclass_nms_batch)."""
         B = self._check_batch(img_metas, proposals=proposals)
         self._check_metas(img_metas, ('img_shape', 'scale_factor'))
         rows = [int(p.shape[0]) for p in proposals]
@@ -595,7 +554,6 @@ class StandardRoIHead(nn.Module):
         batch dimension B, ``proposal_list`` / ``img_metas`` one entry per image -> list of B ``(bbox_results,
         segm_results)``, each what ``simple_test`` returns for that image alone (just ``bbox_results`` without a mask
         branch).  Host waits do not grow with B: the detections of all images cross to the host in one copy."""
-        from .mask_heads import _to_host
         B = self._check_batch(img_metas, proposal_list=proposal_list)
         self._check_metas(img_metas, self._META_KEYS)
         for i, f in enumerate(x):
@@ -605,7 +563,6 @@ class StandardRoIHead(nn.Module):
         counts = [int(d.shape[0]) for d, _ in dets]
         num_classes = self._bbox_num_classes()
         if sum(counts) == 0:
-            import numpy as np
             bbox_results = [[np.zeros((0, 5), dtype=np.float32) for _ in range(num_classes)] for _ in range(B)]
             labels_h = []
         else:
@@ -656,7 +613,6 @@ class StandardRoIHead(nn.Module):
         """test_mixins.py:73-107: the proposals ``proposal_list[0]`` (original image) mapped into every view, the bbox
         branch and ``get_bboxes(rescale=False)`` per view, the views' boxes mapped back and averaged with their scores
         (merge_aug_bboxes), then ``multiclass_nms`` -> (dets [k, 5], labels [k]) in original-image coordinates."""
-        from .bbox_heads import multiclass_nms
         views = self._check_aug(x, img_metas)
         props = proposal_list[0]
         if props.shape[0] == 0:
@@ -698,7 +654,6 @@ class StandardRoIHead(nn.Module):
         """test_mixins.py:178-208 -> per-class lists of (h, w) bool masks at ``ori_shape`` of the first view
         (``encode``: COCO RLE dicts): the merged probabilities (``aug_test_mask_probs``) pasted without a sigmoid,
         ``scale_factor=1.0, rescale=False``, thresholded at ``mask_thr_binary``."""
-        from .mask_heads import _mask_threshold, paste_segms
         views = self._check_aug(x, img_metas)
         num_classes = self._segm_num_classes()
         if det_bboxes.shape[0] == 0:
@@ -714,8 +669,6 @@ class StandardRoIHead(nn.Module):
         ``(bbox_results, segm_results)`` (just ``bbox_results`` without a mask branch).  ``rescale=False`` scales only
         the boxes of ``bbox_results`` by the first view's ``scale_factor``, as the reference does; the masks stay at
         the original image's size either way."""
-        import numpy as np
-        from .mask_heads import _to_host
         views = self._check_aug(x, img_metas)
         det_bboxes, det_labels = self.aug_test_bboxes(x, img_metas, proposal_list, self.test_cfg)
         num_classes = self._bbox_num_classes()
@@ -764,7 +717,6 @@ class DynaMaskRoIHead(StandardRoIHead):
         """dynamask_roi_head.py:75-81.  (``_between``: see train_path.mask_head_forward_train.)"""
         if torch.is_grad_enabled() and last_stage is None:
             # training: same kernels, forward keeps what the hand-sequenced backward needs
-            from . import train_path
             ins_feats = train_path.roi_extract_train(self.mask_roi_extractor, x, rois)
             ips, dps = train_path.mask_head_forward_train(self.mask_head, ins_feats, x, rois, roi_labels, between=_between)
             return dict(stage_instance_preds=ips, stage_detail_preds=dps)
@@ -784,7 +736,6 @@ class DynaMaskRoIHead(StandardRoIHead):
         instead of the per-stage dict -- the last stage's logits then stay at 56 x 56 and ONE launch per chunk does the
         final align_corners x2 upsample and both boundary merges (ops.boundary_merge_chain; same bits as the four launches
         it replaces), on the chunk's own stream, in front of the join instead of behind it."""
-        from .mask_heads import run_steps
         n = rois.shape[0]
         head, ext = self.mask_head, self.mask_roi_extractor
         dev = rois.device
@@ -842,7 +793,6 @@ class DynaMaskRoIHead(StandardRoIHead):
 
     def _side_streams(self, k, device):
         """k streams for k RoI chunks, from the package's shared pool (streams.py: hardware queues are few)."""
-        from . import streams
         return [streams.side(device, i) for i in range(k)]      # more chunks than pool streams: they share (still ordered)
 
     def sample_uniform(self, shape, device):
@@ -870,7 +820,6 @@ class DynaMaskRoIHead(StandardRoIHead):
         """dynamask_roi_head.py:84-87,97-114: logits -> ST-Gumbel-softmax (hard)."""
         train = torch.is_grad_enabled() and self.mask_predictor.training
         if train:
-            from . import train_path
             logits = train_path.MaskPreFn.apply(self.mask_predictor, ins_semantic_feats.detach(),
                                                 *list(self.mask_predictor.parameters()))
         else:
@@ -889,7 +838,6 @@ class DynaMaskRoIHead(StandardRoIHead):
         (dynamask_roi_head.py:59-60) without the [N, 256, 56, 56] tensor: MaskPre's 1x1 conv1 runs on the map and 128
         channels are extracted (train_path.MaskPreMapFn).  The deterministic mode and DM_MASKPRE_MAP=0 take the
         reference's order of operations."""
-        from . import train_path
         lay = self.semantic_roi_extractor.roi_layers[0]
         if ops.DETERMINISTIC[0] or not _MASKPRE_ON_MAP or self.semantic_roi_extractor.num_inputs != 1:
             return self.get_mask_label(self.semantic_roi_extractor([feat_map], rois), noise, return_index=True)
@@ -919,7 +867,6 @@ class DynaMaskRoIHead(StandardRoIHead):
             return losses
         side = None
         if torch.is_grad_enabled() and x[0].is_cuda:
-            from . import train_path
             side = train_path.side_stream(x[0].device, 'bbox')
         if side is not None:
             main = torch.cuda.current_stream(x[0].device)
@@ -977,7 +924,6 @@ class DynaMaskRoIHead(StandardRoIHead):
         # The resolution selector (56x56 extraction of P2 -> MaskPre -> ST-Gumbel) shares nothing with the mask head
         # until the loss: it is issued on a second stream and runs beside the head (autograd replays each node on
         # the stream of its forward, so the two backward passes overlap the same way and are joined by the engine).
-        from . import train_path
         side = train_path.side_stream(pos_rois.device, 'selector') if torch.is_grad_enabled() else None
         if side is not None:
             # the head is issued FIRST (the host feeds the chain of the step before anything that has slack, see
@@ -1044,7 +990,6 @@ class DynaMaskRoIHead(StandardRoIHead):
         """Replay ``simple_test_mask_logits`` as a HIP graph per bucket of detection counts (16 / 24 / 32 / 48 / 64 / 80 / 100 by
         default; see graphs.py for what a graph is tied to).  Off by default: the eager path is the reference one.
         ``batch_buckets``: the buckets of the total RoI count of ``batch_simple_test_mask_logits`` (graphs.BATCH_BUCKETS)."""
-        from .graphs import BATCH_BUCKETS, BUCKETS, GraphedMaskLogits
         self._mask_graphs = GraphedMaskLogits(self, buckets or BUCKETS,
                                               batch_buckets=batch_buckets or BATCH_BUCKETS) if on else None
         return self._mask_graphs
@@ -1099,7 +1044,6 @@ class DynaMaskRoIHead(StandardRoIHead):
     def dynamic_test_mask(self, x, img_metas, det_bboxes, det_labels, rescale=False, noise=None, merge=True, exits=None):
         """``simple_test_mask`` with per-RoI early exit: same inputs, same per-class lists of
         (h, w) bool masks; each detection is pasted from the logits of its own exit."""
-        from .mask_heads import _paste_geometry, _to_host
         segm_result = [[] for _ in range(self._segm_num_classes())]
         n = det_bboxes.shape[0]
         if n == 0:
@@ -1308,7 +1252,6 @@ class MaskScoringRoIHead(StandardRoIHead):
     def _mask_test_pred(self, x, boxes, labels, det_bboxes):
         """One mask branch for the detections of all images: ``mask_pred`` to paste, and the mask scores of
         ``mask_iou_head`` on the same ``mask_feats`` / ``mask_pred``, copied to pinned host memory without a wait."""
-        from .mask_heads import _to_host_pending
         rois = bbox2roi(list(boxes)).contiguous()
         labels = torch.cat([lab.to(torch.int64) for lab in labels]).contiguous()
         dets = torch.cat(list(det_bboxes)).contiguous()
@@ -1319,7 +1262,6 @@ class MaskScoringRoIHead(StandardRoIHead):
         return res['mask_pred'], _to_host_pending(scores, labels)
 
     def _mask_test_result(self, segms, pending, start, count):
-        from .mask_heads import group_mask_scores
         num_classes = self.mask_iou_head.num_classes
         if pending is None or count == 0:
             return segms, [[] for _ in range(num_classes)]
@@ -1390,7 +1332,6 @@ class GridRoIHead(StandardRoIHead):
         if det_bboxes.shape[0] == 0:
             return det_bboxes
         if not isinstance(scale_factor, (float, torch.Tensor)):
-            import numpy as np
             scale_factor = self._scale_factor_on(np.asarray(scale_factor, dtype=np.float32), det_bboxes.device)
         det_bboxes[:, :4] /= scale_factor
         return det_bboxes
@@ -1407,7 +1348,6 @@ class GridRoIHead(StandardRoIHead):
     @torch.no_grad()
     def simple_test(self, x, proposal_list, img_metas, proposals=None, rescale=False, encode=False):
         """grid_roi_head.py:127-164."""
-        from .bbox_heads import bbox2result
         det_bboxes, det_labels = self.simple_test_grid(x, proposal_list, img_metas, rescale=rescale)
         bbox_results = bbox2result(det_bboxes, det_labels, self._bbox_num_classes())
         if not self.with_mask:
@@ -1437,7 +1377,6 @@ class GridRoIHead(StandardRoIHead):
 
     @torch.no_grad()
     def batch_simple_test(self, x, proposal_list, img_metas, rescale=False, encode=False):
-        from .mask_heads import _to_host
         dets = self.batch_simple_test_grid(x, proposal_list, img_metas, rescale=rescale)
         counts = [int(d.shape[0]) for d, _ in dets]
         num_classes = self._bbox_num_classes()
@@ -1522,7 +1461,6 @@ class CascadeRoIHead(StandardRoIHead):
         self._merge_metas = None        # the metas of the current mask test (the flip of Quirk Q16)
         self.num_stages = num_stages
         self.stage_loss_weights = stage_loss_weights
-        from . import bbox_heads  # noqa: F401  (registers Shared2FCBBoxHead)
         exts, heads = self._per_stage(bbox_roi_extractor, 'bbox_roi_extractor'), self._per_stage(bbox_head, 'bbox_head')
         self.bbox_roi_extractor = nn.ModuleList([build_roi_extractor(c) for c in exts])
         self.bbox_head = nn.ModuleList([build_head(c) for c in heads])

@@ -3,7 +3,7 @@ models/utils/res_layer.py and the caffe branch of backbones/resnet.py's ``Bottle
 configs (configs/_base_/models/{mask,faster}_rcnn_r50_caffe_c4.py), at inference.
 
 Every block is three exact-fp32 ``dm_conv2d_fwd`` launches with eval-mode BatchNorm folded into weights and bias
-(bbox_heads.fold_bn, float64, rounded once); no split-K, so a RoI's bits do not depend on the RoI count.  With
+(layers.fold_bn, float64, rounded once); no split-K, so a RoI's bits do not depend on the RoI count.  With
 ``style='caffe'`` the stride of the layer sits in two 1x1 convolutions of block 0 (``conv1`` and ``downsample.0``) that read
 only the even rows and columns of their input: the layer runs on that subsampled input, which the RoI head extracts
 directly (``SingleRoIExtractor.forward(..., bin_step=2)``, dm_roi_align_strided_fwd) instead of extracting four times as
@@ -11,12 +11,8 @@ much and slicing."""
 import torch
 import torch.nn as nn
 
-from .bbox_heads import Bottleneck
+from .layers import _BASIC_BLOCK_DEPTHS, _STAGE_BLOCKS, Bottleneck
 from .registry import SHARED_HEADS
-
-# backbones/resnet.py:356-362 (ResNet.arch_settings): depth -> blocks per stage; 18 / 34 are BasicBlock nets
-_STAGE_BLOCKS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}
-_BASIC_BLOCK_DEPTHS = (18, 34)
 
 
 @SHARED_HEADS.register_module()

@@ -16,7 +16,7 @@ import os
 
 import torch
 
-from . import hazard, ops
+from . import hazard, ops, streams
 
 # maps of at least this many pixels keep the DCN column matrix from the forward for the weight gradient (56 x 56 and, since the
 # leaf work was dealt over three side streams, 28 x 28: 20.09 -> 20.00 ms per step over three runs each; all three: 20.2)
@@ -32,7 +32,6 @@ def side_stream(dev, which='leaf'):
     the second of two kernels of the chain that only share their inputs, 'bbox' the bbox branch of ``forward_train``."""
     if dev.type != 'cuda' or os.environ.get('DM_TRAIN_SIDE_STREAM', '1') == '0':
         return None
-    from . import streams
     st = streams.side(dev, _SIDE_STREAMS[which])
     if hazard.ENABLED[0]:
         hazard.name_stream(st, f'side{_SIDE_STREAMS[which]}')

@@ -85,7 +85,8 @@ def _band(m, x1, dets, labels, meta, rescale):
     """Per detection: pixels whose per-image probability lies in [THR - BAND, THR + BAND) -- two pastes of the
     per-image logits at the band's edges."""
     from dynamask_amd import ops
-    from dynamask_amd.mask_heads import FCNMaskHead, _paste_geometry
+    from dynamask_amd.mask_heads import FCNMaskHead
+    from dynamask_amd.postprocess import _paste_geometry
     from dynamask_amd.roi_head import bbox2roi
     sf = meta['scale_factor']
     if rescale and not isinstance(sf, float):
@@ -302,7 +303,7 @@ def test_nms_segmented_matches_per_segment_nms(offset):
 
 
 def test_multiclass_nms_batch_matches_per_image():
-    from dynamask_amd.bbox_heads import multiclass_nms, multiclass_nms_batch
+    from dynamask_amd.postprocess import multiclass_nms, multiclass_nms_batch
     g = torch.Generator().manual_seed(11)
     rows = [0, 5, 37, 120, 9]
     bl, sl = [], []

@@ -151,12 +151,12 @@ def test_fold_of_the_merged_launch_and_of_a_plain_bottleneck():
 
 
 def test_fold_is_float64_rounded_once_and_shared_with_the_double_head():
-    from dynamask_amd import bbox_heads, shared_heads
+    from dynamask_amd import bbox_heads, layers, shared_heads
     assert shared_heads.Bottleneck is bbox_heads.Bottleneck          # one block class, one fold
     m = _small_layer()
     b0 = m.res_layer[0]
     pairs = [(b0.conv3.weight, b0.bn3), (b0.downsample[0].weight, b0.downsample[1])]
-    w, b = bbox_heads.fold_bn(pairs)
+    w, b = layers.fold_bn(pairs)
     ws, bs = [], 0
     for cw, bn in pairs:
         s = bn.weight.detach().double() / torch.sqrt(bn.running_var.double() + bn.eps)
@@ -169,7 +169,7 @@ def test_fold_is_float64_rounded_once_and_shared_with_the_double_head():
 
 def test_fold_is_refreshed_after_load_state_dict():
     import c4_inputs as ci
-    from dynamask_amd.bbox_heads import fold_bn
+    from dynamask_amd.layers import fold_bn
     m = _small_layer(seed=5)
     f = m.res_layer[0]._f[2]
     w0, b0 = f.folded()

@@ -121,7 +121,7 @@ def test_bn_fold_equals_conv_then_batchnorm():
 
 
 def test_bn_fold_is_float64_rounded_once():
-    from dynamask_amd.bbox_heads import fold_bn
+    from dynamask_amd.layers import fold_bn
     h = _small_head()
     c, bn = h.res_block.conv1.conv, h.res_block.conv1.bn
     s = bn.weight.detach().double() / torch.sqrt(bn.running_var.double() + bn.eps)
@@ -132,7 +132,7 @@ def test_bn_fold_is_float64_rounded_once():
 
 def test_fold_is_refreshed_when_a_parameter_or_buffer_changes():
     import double_inputs as di
-    from dynamask_amd.bbox_heads import fold_bn
+    from dynamask_amd.layers import fold_bn
     h = _small_head()
     f = h.conv_branch[0]._f[2]
     w0, b0 = f.folded()

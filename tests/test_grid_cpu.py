@@ -119,7 +119,7 @@ def test_zero_detections(golden_dir):
     assert tuple(m.grid_head.get_bboxes(torch.zeros(0, 5), out['fused']).shape) == (0, 5)
     assert tuple(m._grid_refine(None, [torch.zeros(0, 5)]).shape) == (0, 5)
     assert tuple(m._grid_refine(None, [torch.zeros(0, 5), torch.zeros(0, 5)]).shape) == (0, 5)
-    from dynamask_amd.bbox_heads import bbox2result
+    from dynamask_amd.postprocess import bbox2result
     res = bbox2result(torch.zeros(0, 5), torch.zeros(0, dtype=torch.long), 80)
     assert len(res) == 80 and all(r.shape == (0, 5) and r.dtype == np.float32 for r in res)
 

@@ -53,7 +53,7 @@ def _mapping(boxes, meta):
 
 
 def composed_bboxes(m, xs, props, metas):
-    from dynamask_amd.bbox_heads import multiclass_nms
+    from dynamask_amd.postprocess import multiclass_nms
     from dynamask_amd.roi_head import bbox2roi
     bl, sl = [], []
     for x, (meta,) in zip(xs, metas):
@@ -83,7 +83,7 @@ def composed_probs(m, xs, metas, dets, labels):
 
 def composed_call(m, xs, props, metas):
     from dynamask_amd import ops
-    from dynamask_amd.bbox_heads import bbox2result
+    from dynamask_amd.postprocess import bbox2result
     dets, labels = composed_bboxes(m, xs, props, metas)
     bbox_results = bbox2result(dets, labels, m.bbox_head.num_classes)
     probs = composed_probs(m, xs, metas, dets, labels)
