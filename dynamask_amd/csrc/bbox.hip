@@ -234,6 +234,33 @@ __global__ __launch_bounds__(256) void merge_aug_bboxes_kernel(const long long* 
   }
 }
 
+// merge_aug_proposals' first half (merge_augs.py:27-38): every (image, view) segment's [n, 5] proposals mapped back to the
+// original image (bbox_mapping_back: the flip against the view's img_shape, then a true division by the scale factor)
+// and written at the segment's rows of the concatenated [total, 5] buffer, the score copied.  seg_tab[s] = (address of
+// the proposals, n, first output row); view_tab[s] = the segment's view row.  grid = (row blocks, S).
+__global__ __launch_bounds__(256) void proposals_mapping_back_kernel(const long long* __restrict__ seg_tab,
+                                                                     const float* __restrict__ view_tab,
+                                                                     float* __restrict__ out) {
+#pragma clang fp contract(off)
+  const long long* sg = seg_tab + (size_t)blockIdx.y * 3;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int)sg[1]) return;
+  const float* vt = view_tab + (size_t)blockIdx.y * DM_AUG_VIEW_FLOATS;
+  const float* b = reinterpret_cast<const float*>(sg[0]) + (size_t)i * 5;
+  float x1 = b[0], y1 = b[1], x2 = b[2], y2 = b[3];
+  const int flip = (int)vt[6];
+  if (flip == DM_AUG_FLIP_HORIZONTAL) {
+    const float p = vt[5] - x2, q = vt[5] - x1;
+    x1 = p; x2 = q;
+  } else if (flip == DM_AUG_FLIP_VERTICAL) {
+    const float p = vt[4] - y2, q = vt[4] - y1;
+    y1 = p; y2 = q;
+  }
+  float* o = out + ((size_t)sg[2] + i) * 5;
+  o[0] = x1 / vt[0]; o[1] = y1 / vt[1]; o[2] = x2 / vt[2]; o[3] = y2 / vt[3];
+  o[4] = b[4];
+}
+
 // ----- Cascade R-CNN stage step (CascadeRoIHead.simple_test, cascade_roi_head.py:307-315) -----
 // One wave per RoI row i of stage s:
 //   sum[i, :]  = (s == 0 ? 0 : sum[i, :]) + cls[i, :]       (sum(ms_scores): ((0 + s0) + s1) + s2 in fp32)
@@ -407,6 +434,16 @@ extern "C" int dm_merge_aug_bboxes(const long long* ptr_tab, const float* view_t
     return DM_ERR_INVALID_ARG;
   DM_LAUNCH(merge_aug_bboxes_kernel, dim3(dm_ceil_div(box_cols + score_cols, 256), n), dim3(256), 0, (hipStream_t)stream,
             ptr_tab, view_tab, V, n, box_cols, score_cols, out_boxes, out_scores);
+  return dm_check_launch();
+}
+
+extern "C" int dm_proposals_mapping_back(const long long* seg_tab, const float* view_tab, int num_segments, int max_rows,
+                                         float* out, dm_stream_t stream) {
+  if (num_segments < 0 || max_rows < 0) return DM_ERR_INVALID_ARG;
+  if (num_segments == 0 || max_rows == 0) return DM_OK;
+  if (!seg_tab || !view_tab || !out || num_segments > 65535) return DM_ERR_INVALID_ARG;
+  DM_LAUNCH(proposals_mapping_back_kernel, dim3(dm_ceil_div(max_rows, 256), num_segments), dim3(256), 0,
+            (hipStream_t)stream, seg_tab, view_tab, out);
   return dm_check_launch();
 }
 

@@ -9,7 +9,9 @@ dilation 1 on maps wider than CONV2D_3X3_MAX_WIDTH, which the former does not ta
 permuted copy), one segmented NMS (``ops.nms_segmented``) and one merge (``dm_rpn_merge``: the image's best ``nms_post``);
 the host waits once, for the per-image counts.  ``DM_RPN_FUSED=0`` (or clearing ``RPN_FUSED``) runs the same steps composed
 of ``ops.sigmoid``, a stable ``torch.sort``, gathers, ``AnchorGenerator.grid_anchors``, ``ops.bbox_decode``,
-``ops.nms_segmented`` and a stable sort of the concatenated survivors: the same bits.
+``ops.nms_segmented`` and a stable sort of the concatenated survivors: the same bits.  ``aug_test_rpn`` (test-time
+augmentation) runs ``simple_test_rpn`` per view and merges: one ``dm_proposals_mapping_back`` launch for all views and images,
+one segmented NMS over the images, one more host wait whatever the batch.
 
 Deviation from mmcv's ``batched_nms``: it shifts every level's boxes by ``level * (max coordinate + 1)`` in
 fp32 before the IoU; here every level is suppressed on its own unshifted boxes."""
@@ -36,7 +38,7 @@ RPN_FUSED = [_env_fused()]
 class RPNHead(nn.Module):
     """``RPNHead`` -- rpn_head.py:12-168 on AnchorHead (anchor_head.py:13-148, :499-576) and RPNTestMixin.
     ``state_dict`` keys: ``rpn_conv.{weight,bias}``, ``rpn_cls.{weight,bias}``, ``rpn_reg.{weight,bias}``.  The loss
-    configs are stored, not built; training (``loss``, ``forward_train``) and ``aug_test_rpn`` are not built."""
+    configs are stored, not built; training (``loss``, ``forward_train``) is not built."""
 
     def __init__(self, in_channels, feat_channels=256,
                  anchor_generator=dict(type='AnchorGenerator', scales=[8, 16, 32], ratios=[0.5, 1.0, 2.0],
@@ -93,9 +95,6 @@ class RPNHead(nn.Module):
 
     def forward_train(self, *args, **kwargs):
         raise NotImplementedError('RPNHead.forward_train: RPN training is not built')
-
-    def aug_test_rpn(self, *args, **kwargs):
-        raise NotImplementedError('RPNHead.aug_test_rpn: merge_aug_proposals is not built; use simple_test_rpn per view')
 
     # ------------------------------------------------------------------ proposals
     def _checked_cfg(self, cfg):
@@ -193,3 +192,43 @@ class RPNHead(nn.Module):
     def simple_test_rpn(self, x, img_metas):
         """rpn_test_mixin.py:24-37."""
         return self.get_bboxes(*self(x), img_metas)
+
+    def aug_test_rpn(self, feats, img_metas):
+        """rpn_test_mixin.py:40-60 with ``merge_aug_proposals`` (merge_augs.py:8-47): ``feats[v]`` / ``img_metas[v]`` are
+        view v's maps and its B metas.  Per image, a [n, 5] tensor in ORIGINAL-image coordinates: the views' proposals
+        mapped back (one ``dm_proposals_mapping_back`` launch for all views and images), suppressed at ``nms_thr`` (one
+        segmented NMS over the images), the ``max_num`` best in score order.  Host waits: each view's one, and one for the
+        merge whatever B.  The list-of-views form is the one that is built: any other (no maps, one view's maps given
+        bare) raises NotImplementedError."""
+        if not isinstance(feats, (list, tuple)) or not isinstance(img_metas, (list, tuple)):
+            raise NotImplementedError('RPNHead.aug_test_rpn: built for a list of views only -- feats[v] the maps and '
+                                      f'img_metas[v] the metas of view v; got {type(feats).__name__} and '
+                                      f'{type(img_metas).__name__}')
+        cfg = self._checked_cfg(None)
+        if len(feats) != len(img_metas) or len(feats) == 0:
+            raise ValueError(f'RPNHead.aug_test_rpn: {len(feats)} views of maps and {len(img_metas)} of metas')
+        B = len(img_metas[0])
+        if any(len(m) != B for m in img_metas):
+            raise ValueError('RPNHead.aug_test_rpn: every view needs the metas of the same images')
+        views = [self.simple_test_rpn(x, m) for x, m in zip(feats, img_metas)]
+        if B == 0:
+            return []
+        with torch.no_grad():
+            V = len(views)
+            # image after image, its views in order: the reference's torch.cat per image
+            cat = ops.proposals_mapping_back([views[v][b] for b in range(B) for v in range(V)],
+                                             [img_metas[v][b] for b in range(B) for v in range(V)])
+            rows = [sum(int(views[v][b].shape[0]) for v in range(V)) for b in range(B)]
+            # mmcv nms: descending score, the earlier row first among equals -- per image: one stable sort by score, one by image
+            image = torch.repeat_interleave(ops._upload(list(range(B)), torch.int64, cat.device),
+                                            ops._upload(rows, torch.int64, cat.device), output_size=sum(rows))
+            by_score = torch.sort(cat[:, 4], descending=True, stable=True)[1]
+            order = by_score[torch.sort(image[by_score], stable=True)[1]]
+            dets = cat[order]
+            keep, kept = ops.nms_segmented(dets[:, :4].contiguous(), rows, cfg['nms_thr'], max_num=cfg['max_num'])
+            kept = kept.cpu().tolist()                   # the merge's one host wait
+            out, r0 = [], 0
+            for b in range(B):
+                out.append(dets[keep[r0:r0 + kept[b]].long() + r0])
+                r0 += rows[b]
+            return out

@@ -567,6 +567,33 @@ def merge_aug_bboxes(bboxes_list, scores_list, view_tab):
     return out_b, out_s
 
 
+def proposals_mapping_back(proposals, img_metas):
+    """The first half of mmdet ``merge_aug_proposals`` for all segments in one launch (dm_proposals_mapping_back):
+    ``proposals[s]`` [n_s, 5] (view coordinates, score last) with its view's meta ``img_metas[s]`` -> [sum n_s, 5], the
+    segments one after the other, boxes mapped back to the original image (flip, then a true division by the scale
+    factor), scores copied.  No host wait."""
+    S = len(proposals)
+    if len(img_metas) != S:
+        raise ValueError(f'{S} proposal tensors for {len(img_metas)} metas')
+    rows_tab, r0 = [], 0
+    for p in proposals:
+        _chk(p, 'proposals')
+        if p.dim() != 2 or p.shape[1] != 5:
+            raise ValueError(f'proposals: [n, 5] expected, got {list(p.shape)}')
+        rows_tab.append([p.data_ptr(), p.shape[0], r0])
+        r0 += p.shape[0]
+    dev = proposals[0].device if S else torch.device('cuda')
+    out = torch.empty((r0, 5), device=dev, dtype=torch.float32)
+    if r0 > 0:
+        view_tab = aug_view_table(img_metas, dev)
+        tab = _upload(rows_tab, torch.int64, dev)
+        if hazard.ENABLED[0]:
+            hazard.touch('dm_proposals_mapping_back (segment table)', reads=list(proposals))
+        check(lib().dm_proposals_mapping_back(_p(tab), _p(view_tab), S, max(r[1] for r in rows_tab), _p(out), _stream()),
+              'dm_proposals_mapping_back')
+    return out
+
+
 def merge_aug_masks(logits_list, labels, view_tab):
     """mmdet ``merge_aug_masks`` of V views' mask LOGITS [n, K, S, S] in one launch -> probabilities [n, 1, S, S]: the
     ``labels`` [n] channel when K > 1 (the channel the paste would select), sigmoid (the paste's own), un-flipped,
@@ -3119,3 +3146,110 @@ def maxpool3x3_s2(x, out=None):
         assert tuple(out.shape) == shape
     check(lib().dm_maxpool3x3_s2_fwd(_p(x), N * C, H, W, _p(out), _stream()), 'dm_maxpool3x3_s2_fwd')
     return out
+
+
+# ------------------------------------------------------------------ image pre-processing (dynamask_hip.h section K33)
+PREPROCESS_MAX_IMAGES = _abi.load()[1]['DM_PREPROCESS_MAX_IMAGES']
+_RESIZE_TABLES = {}        # (n_src, n_dst) -> resize_axis_table's arrays
+_RESIZE_TAPS = {}          # (device, ((n_src, n_dst), ...)) -> (taps on the device, {(n_src, n_dst): first row})
+
+
+def resize_axis_table(n_src, n_dst):
+    """The per-axis sample table of ``preprocess_u8`` (dynamask_hip.h K33), cached per (n_src, n_dst): numpy arrays
+    (i0 int32, i1 int32, c0 int16, c1 int16) of length n_dst -- the two source indices of every destination index and
+    their 11-bit coefficients (c0 + c1 == 2048)."""
+    import numpy as np
+    n_src, n_dst = int(n_src), int(n_dst)
+    if n_src < 1 or n_dst < 1:
+        raise ValueError(f'resize_axis_table: n_src={n_src}, n_dst={n_dst}; at least 1 each expected')
+    key = (n_src, n_dst)
+    if key not in _RESIZE_TABLES:
+        d = np.arange(n_dst, dtype=np.float64)
+        f = ((d + 0.5) * (1.0 / (n_dst / n_src)) - 0.5).astype(np.float32)
+        i = np.floor(f)
+        t = (f - i).astype(np.float32)
+        i = i.astype(np.int64)
+        low, high = i < 0, i >= n_src - 1
+        i = np.where(low, 0, np.where(high, n_src - 1, i))
+        t = np.where(low | high, np.float32(0), t).astype(np.float32)
+        c0 = np.rint((np.float32(1) - t).astype(np.float32) * np.float32(2048)).astype(np.int16)
+        c1 = np.rint(t * np.float32(2048)).astype(np.int16)
+        _RESIZE_TABLES[key] = (i.astype(np.int32), np.minimum(i + 1, n_src - 1).astype(np.int32), c0, c1)
+    return _RESIZE_TABLES[key]
+
+
+def _resize_taps(keys, device):
+    """The tap table of one launch: the axis tables of ``keys`` (distinct (n_src, n_dst) pairs) one after the other as
+    int32 [rows, 4] on the device, uploaded once per set of keys and kept, with each key's first row."""
+    import numpy as np
+    ck = (str(device), keys)
+    if ck not in _RESIZE_TAPS:
+        if len(_RESIZE_TAPS) >= 64:
+            _RESIZE_TAPS.clear()
+        row0, parts, r = {}, [], 0
+        for k in keys:
+            i0, i1, c0, c1 = resize_axis_table(*k)
+            parts.append(np.stack([i0, i1, c0.astype(np.int32), c1.astype(np.int32)], 1))
+            row0[k] = r
+            r += k[1]
+        taps = torch.from_numpy(np.concatenate(parts)).pin_memory().to(device, non_blocking=True)
+        _RESIZE_TAPS[ck] = (taps, row0)
+    return _RESIZE_TAPS[ck]
+
+
+def preprocess_u8(images, sizes, flips, mean, stdinv, to_rgb, pad_shape, out=None):
+    """B decoded images -> the batch the backbone reads, in one launch (dm_preprocess_u8_fwd): resize to ``sizes[b]`` =
+    (nh, nw) with the 8-bit fixed-point bilinear scheme, flip (``flips[b]``: None / False, 'horizontal' or 'vertical'),
+    ``(v - mean[c]) * stdinv[c]`` (``to_rgb``: output channel c reads source channel 2 - c), zero padding right and bottom
+    to ``pad_shape`` = (Hp, Wp).  ``images[b]``: uint8 [h, w, 3] on the device, dense pixels, any row stride >= 3 w.
+    Returns ``out`` [B, 3, Hp, Wp] float32, every element written."""
+    B = len(images)
+    if len(sizes) != B or len(flips) != B:
+        raise ValueError(f'preprocess_u8: {B} images, {len(sizes)} sizes, {len(flips)} flips')
+    if B == 0:
+        raise ValueError('preprocess_u8: no image')
+    Hp, Wp = int(pad_shape[0]), int(pad_shape[1])
+    dims, keys = [], []
+    for b, (im, (nh, nw), flip) in enumerate(zip(images, sizes, flips)):
+        _chk_u8_image(im, f'images[{b}]')
+        h, w = im.shape[:2]
+        code = 0 if not flip else AUG_FLIP_CODES.get(flip)
+        if code is None:
+            raise ValueError(f"images[{b}]: invalid flipping direction '{flip}'")
+        for k in ((w, int(nw)), (h, int(nh))):
+            if k not in keys and k[1] >= 1:          # (a size below 1 has no table: the library refuses the call below)
+                keys.append(k)
+        dims.append([h, w, im.stride(0) if h > 1 else 3 * w, int(nh), int(nw), code, (w, int(nw)), (h, int(nh))])
+    dev = images[0].device
+    taps, row0 = _resize_taps(tuple(keys), dev) if keys else (torch.zeros((0, 4), device=dev, dtype=torch.int32), {})
+    flat = []
+    for d in dims:
+        flat += d[:6] + [row0.get(d[6], 0), row0.get(d[7], 0)]
+    dims_arr = _int_array(flat)
+    if not lib().dm_preprocess_u8_supported(B, dims_arr, taps.shape[0], Hp, Wp):
+        check(_abi.load()[1]['DM_ERR_UNSUPPORTED'], f'dm_preprocess_u8_fwd ({B} images of at most '
+              f'{PREPROCESS_MAX_IMAGES}, output {Hp} x {Wp})')
+    if out is None:
+        out = torch.empty((B, 3, Hp, Wp), device=dev, dtype=torch.float32)
+    else:
+        _chk(out, 'out')
+        assert tuple(out.shape) == (B, 3, Hp, Wp)
+    if hazard.ENABLED[0]:
+        hazard.touch('dm_preprocess_u8_fwd (image table)', reads=list(images))
+    check(lib().dm_preprocess_u8_fwd(_ptr_array(images), dims_arr, B, _p(taps), taps.shape[0], _float_array(mean),
+                                     _float_array(stdinv), 1 if to_rgb else 0, _p(out), Hp, Wp, _stream()),
+          'dm_preprocess_u8_fwd')
+    return out
+
+
+def _chk_u8_image(t, name):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f'{name}: expected a tensor')
+    if not t.is_cuda:
+        raise RuntimeError(f'{name}: dynamask_amd operators run on the MI355X only (got a {t.device} tensor); '
+                           'there is no CPU fallback')
+    if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise TypeError(f'{name}: a uint8 [h, w, 3] image expected, got {t.dtype} {list(t.shape)}')
+    if t.stride(2) != 1 or t.stride(1) != 3 or (t.shape[0] > 1 and t.stride(0) < 3 * t.shape[1]):
+        raise ValueError(f'{name}: dense pixels (strides [>= 3 w, 3, 1]) expected, got {list(t.stride())}')
+    return t

@@ -77,6 +77,7 @@ UPSAMPLE_LAYERS = Registry('upsample')   # stands in for mmcv's build_upsample_l
 ANCHOR_GENERATORS = Registry('anchor generator')   # mmdet/core/anchor/builder.py
 NECKS = Registry('neck')
 BACKBONES = Registry('backbone')
+DETECTORS = Registry('detector')
 
 
 def build(cfg, registry, default_args=None):
@@ -103,6 +104,11 @@ def build_neck(cfg):
 
 def build_backbone(cfg):
     return build(cfg, BACKBONES)
+
+
+def build_detector(cfg, train_cfg=None, test_cfg=None):
+    """mmdet/models/builder.py:61-63."""
+    return build(cfg, DETECTORS, dict(train_cfg=train_cfg, test_cfg=test_cfg))
 
 
 def build_anchor_generator(cfg, default_args=None):

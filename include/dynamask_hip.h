@@ -656,6 +656,16 @@ int dm_merge_aug_bboxes(const long long* ptr_tab, const float* view_tab, int V, 
 int dm_merge_aug_masks(const long long* logit_tab, const float* view_tab, int V, int n, int K, int S, const long long* labels,
                        float* out, dm_stream_t stream);
 
+/* (added to ABI 29) RPNHead.aug_test_rpn: the first half of merge_aug_proposals (merge_augs.py:27-38) for every image and
+ * view in one launch.  Segment s is one (image, view): seg_tab (int64, device) [S][3] = (address of its proposals [n, 5]
+ * fp32, dense rows; n; its first row of `out`), view_tab (float, device) [S][DM_AUG_VIEW_FLOATS] its view row as above.
+ * out [sum n, 5]: x1 y1 x2 y2 mapped back to the original image (bbox_mapping_back: the flip against the view's
+ * img_shape, then a true fp32 division by the scale factor, never a multiply by a reciprocal) and the score copied.
+ * max_rows >= every n; num_segments <= 65535.  The caller lays the segments out image after image, so `out` is the
+ * reference's torch.cat per image. */
+int dm_proposals_mapping_back(const long long* seg_tab, const float* view_tab, int num_segments, int max_rows, float* out,
+                              dm_stream_t stream);
+
 /* ===========================================================================
  * Backward (training step).  Replaces what autograd derives for the reference
  * modules above plus mmcv's DeformConv2d backward
@@ -1407,6 +1417,42 @@ int dm_conv7x7_s2_fwd(const float* x, int NB, int C, int H, int W, const float* 
                       int flags, float* out, dm_stream_t stream);
 int dm_maxpool3x3_s2_supported(long long NC, int H, int W);
 int dm_maxpool3x3_s2_fwd(const float* in, long long NC, int H, int W, float* out, dm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * K33  (added to ABI 29) Image pre-processing: the reference's test pipeline Resize(keep_ratio) -> RandomFlip ->
+ *      Normalize(to_rgb) -> Pad(size_divisor) -> ImageToTensor -> collate (mmdet/datasets/pipelines/transforms.py,
+ *      done there by cv2 on the host) as one launch over B decoded images.  No resized image exists in memory, the
+ *      sources are only read, `out` is written completely (it may be uninitialised).
+ *
+ * srcs: host array of B device addresses of uint8 HWC images, 3 channels, pixel stride 3.  dims: host
+ * [B][DM_PREPROCESS_DIMS] = (h, w, row stride in bytes >= 3 w, resized nh, resized nw, flip code DM_AUG_FLIP_*, first
+ * row of the image's column taps, first row of its row taps).  taps (int32, device, 16-byte aligned) [tap_rows][4]: one
+ * row (i0, i1, c0, c1) per destination index of an axis -- the two source indices and their 11-bit coefficients,
+ * c0 + c1 == 2048, built on the host:
+ *     f = float32((d + 0.5) * (1.0 / (n_dst / n_src)) - 0.5)   (inner arithmetic in float64)
+ *     i = floor(f), t = float32(f - i);  i < 0: i = 0, t = 0;  i >= n_src - 1: i = n_src - 1, t = 0
+ *     i0 = i, i1 = min(i + 1, n_src - 1), c0 = rint(float32(1 - t) * 2048), c1 = rint(t * 2048)   (half to even, int16)
+ * (an index outside its axis is clamped into it by the kernel).  Per output pixel (y < nh, x < nw) and channel c, with
+ * (x0, x1, a0, a1) the column taps of x -- of nw - 1 - x under a horizontal flip -- and (y0, y1, b0, b1) the row taps
+ * of y -- of nh - 1 - y under a vertical flip -- and sc = to_rgb ? 2 - c : c, all in int32:
+ *     r_top = S[y0][x0][sc] * a0 + S[y0][x1][sc] * a1,  r_bot likewise on row y1
+ *     v = clamp((((b0 * (r_top >> 4)) >> 16) + ((b1 * (r_bot >> 4)) >> 16) + 2) >> 2, 0, 255)
+ *     out[b][c][y][x] = (float(v) - mean[c]) * stdinv[c]        (two fp32 roundings, no contraction)
+ * and out = 0 where y >= nh or x >= nw (the padding to [Hp, Wp], right and bottom).  nh == h and nw == w pass the
+ * source bytes through exactly.  mean, stdinv: host float[3].  This is 8-bit INTER_LINEAR as cv2 is recalled to do it;
+ * parity with cv2 itself is unverified, and cv2's switch to area averaging at exact 2x decimation is not made.
+ * dm_preprocess_u8_supported: 1 exactly when 0 <= B <= DM_PREPROCESS_MAX_IMAGES (the image table travels in the kernel
+ * arguments), 1 <= Hp, Wp <= 2^24, Hp <= 4 * 65535, and for every image 1 <= h, w <= 2^24, 1 <= nh <= Hp,
+ * 1 <= nw <= Wp, row stride >= 3 w, a flip code of the three, and both tap ranges inside [0, tap_rows).
+ * dm_preprocess_u8_fwd returns DM_ERR_UNSUPPORTED for anything else, DM_ERR_INVALID_ARG for a null pointer or
+ * misaligned taps.  B == 0 enqueues nothing.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define DM_PREPROCESS_MAX_IMAGES 32
+#define DM_PREPROCESS_DIMS 8
+int dm_preprocess_u8_supported(int B, const int* dims, long long tap_rows, int Hp, int Wp);
+int dm_preprocess_u8_fwd(const uint8_t* const* srcs, const int* dims, int B, const int32_t* taps, long long tap_rows,
+                         const float* mean, const float* stdinv, int to_rgb, float* out, int Hp, int Wp,
+                         dm_stream_t stream);
 
 #ifdef __cplusplus
 }
