@@ -3,6 +3,8 @@
 // BN -> ReLU -> max_pool2d(3, stride 2, pad 1).  The 1x1 / 3x3 convs and the
 // two FC layers run on the implicit-GEMM kernel (an FC is a 1x1 conv on a 1x1
 // map).
+#include <algorithm>
+
 #include "common.h"
 
 namespace {
@@ -66,6 +68,7 @@ __global__ __launch_bounds__(1024) void bn_stats_kernel(const float* __restrict_
 // of the 256 CUs idle and ran at 1.6 TB/s); partial sums are combined in a fixed order ->
 // still deterministic.  Pass 0: partial sums; pass 1: partial centred second moments.
 constexpr int kBnSplits = 16;
+constexpr int kSumsPrefetchSlots = 4;      // maxpool_relu_bwd_sums_kernel: register slots of 256 threads a plane is prefetched into
 
 __device__ __forceinline__ float bn_partials_ordered(const float* part, int c) {
   float r = 0.f;
@@ -73,7 +76,8 @@ __device__ __forceinline__ float bn_partials_ordered(const float* part, int c) {
   return r;
 }
 
-template <int PASS>
+// VEC: 16-byte loads (HW % 4 == 0 and x 16-byte aligned: the route's decision)
+template <int PASS, bool VEC>
 __global__ __launch_bounds__(256) void bn_stats_split_kernel(const float* __restrict__ x, int NB, int C, int HW,
                                                              float* __restrict__ part_sum, float* __restrict__ part_sq) {
   __shared__ float red[4];
@@ -83,7 +87,7 @@ __global__ __launch_bounds__(256) void bn_stats_split_kernel(const float* __rest
   float acc = 0.f;
   for (int n = n0; n < n1; ++n) {
     const float* p = x + ((size_t)n * C + c) * HW;
-    if ((HW & 3) == 0) {
+    if (VEC) {
       const dm_f32x4* p4 = reinterpret_cast<const dm_f32x4*>(p);
       for (int i = threadIdx.x; i < (HW >> 2); i += 256) {
         const dm_f32x4 v = p4[i];
@@ -203,46 +207,133 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_rows_kernel(const float* 
 
 extern "C" long long dm_bn_scratch_floats(int C) { return C > 0 ? (long long)C * kBnSplits * 2 : -1; }
 
+// ----------------------------------------------------------------- the routes of the three launchers
+// The shape of csrc/backward.hip's launchers: each entry point validates its pointers; its route function decides the
+// launches from numbers alone (no pointer, no HIP call: alignment, "a scratch was given" and the compute-unit count are
+// fields of the call); its emit enqueues exactly what the route says; dm_mask_pre_plan reports the same value.
+
+enum { MK_STATS = 0, MK_STATS_SPLIT, MK_STATS_FINALIZE, MK_FWD, MK_FWD_ROWS, MK_POOL_SCATTER, MK_POOL_LDS, MK_POOL_SUMS, MK_BN_BWD,
+       MK_BN_BWD_SPLIT };      // MaskPreLaunch::kernel, as the header numbers them
+
+constexpr long long kMaskPreLdsLimit = 64 * 1024;      // LDS of a workgroup, static plus dynamic, that a route may ask for
+// static LDS of the kernels (their `red` arrays), counted by the routes and reported with the dynamic bytes
+constexpr int kRedWide = 16 * (int)sizeof(float), kRedNarrow = 4 * (int)sizeof(float);
+
+struct MaskPreCall {       // what a route depends on: the op, its numbers, and facts in place of its pointers
+  int op;                  // DM_MASK_PRE_*
+  int NB, C, H, W;         // statistics: H = 1, W = HW
+  int scratch;             // statistics, backward: the caller gave a scratch (dm_bn_scratch_floats)
+  int align;               // 16, 8 or 4: the bytes x (backward: x and grad_x) is aligned to
+  int cus;                 // backward: dm_num_cus()
+};
+
+// One launch: the ints of dm_mask_pre_plan's record, in its order (the record's LDS bytes are lds_static + lds_dynamic)
+struct MaskPreLaunch {
+  int kernel, p[3], grid_x, grid_y, threads, lds_static, lds_dynamic, clear;
+};
+
+struct MaskPreRoute {
+  int rc = DM_OK, count = 0;           // (an empty call: DM_OK and no launch)
+  MaskPreLaunch launch[DM_MASK_PRE_PLAN_MAX_LAUNCHES];
+};
+
+static MaskPreRoute mp_refuse(int rc) {
+  MaskPreRoute r;
+  r.rc = rc;
+  return r;
+}
+static void mp_add(MaskPreRoute& r, const MaskPreLaunch& l) { r.launch[r.count++] = l; }
+static dim3 mp_grid(const MaskPreLaunch& l) { return dim3((unsigned)l.grid_x, (unsigned)l.grid_y); }
+// the alignment fact of a call: the largest of 16, 8, 4 bytes that every pointer given is a multiple of (b: optional)
+static int mp_align(const void* a, const void* b) {
+  const uintptr_t v = (uintptr_t)a | (uintptr_t)b;
+  return (v & 15) == 0 ? 16 : (v & 7) == 0 ? 8 : 4;
+}
+
+static MaskPreRoute stats_route(const MaskPreCall& c) {
+  const long long HW = (long long)c.H * c.W;
+  if (c.NB <= 0 || c.C <= 0 || c.H <= 0 || c.W <= 0 || HW > 0x7fffffffLL) return mp_refuse(DM_ERR_INVALID_ARG);
+  MaskPreRoute r;
+  if (c.scratch && c.NB >= kBnSplits) {
+    // 16-byte loads where every plane starts on a 16-byte boundary; the scalar loop otherwise
+    const int vec = (HW & 3) == 0 && c.align >= 16;
+    mp_add(r, {MK_STATS_SPLIT, {0, vec, 0}, c.C, kBnSplits, 256, kRedNarrow, 0, 0});
+    mp_add(r, {MK_STATS_SPLIT, {1, vec, 0}, c.C, kBnSplits, 256, kRedNarrow, 0, 0});
+    mp_add(r, {MK_STATS_FINALIZE, {0, 0, 0}, dm_ceil_div(c.C, 128), 1, 128, 0, 0, 0});
+  } else {
+    mp_add(r, {MK_STATS, {0, 0, 0}, c.C, 1, 1024, kRedWide, 0, 0});
+  }
+  return r;
+}
+
+static int stats_emit(const MaskPreRoute& r, const float* x, int NB, int C, int HW, float* mean, float* var, float* running_mean,
+                      float* running_var, float momentum, const float* mean_shift, float* scratch, hipStream_t st) {
+  float* ps = scratch;
+  float* pq = scratch + (size_t)C * kBnSplits;
+  for (int i = 0; i < r.count; ++i) {
+    const MaskPreLaunch& l = r.launch[i];
+    const dim3 grid = mp_grid(l), block((unsigned)l.threads);
+    if (l.kernel == MK_STATS_SPLIT) {
+      const auto fn = l.p[0] == 0 ? (l.p[1] ? bn_stats_split_kernel<0, true> : bn_stats_split_kernel<0, false>)
+                                  : (l.p[1] ? bn_stats_split_kernel<1, true> : bn_stats_split_kernel<1, false>);
+      DM_LAUNCH(fn, grid, block, 0, st, x, NB, C, HW, ps, pq);
+    } else if (l.kernel == MK_STATS_FINALIZE) {
+      DM_LAUNCH(bn_stats_finalize_kernel, grid, block, 0, st, ps, pq, C, (long long)NB * HW, mean, var, running_mean, running_var,
+                momentum, mean_shift);
+    } else {
+      DM_LAUNCH(bn_stats_kernel, grid, block, 0, st, x, NB, C, HW, mean, var, running_mean, running_var, momentum, mean_shift);
+    }
+    const int rc = dm_check_launch();
+    if (rc != DM_OK) return rc;
+  }
+  return DM_OK;
+}
+
 extern "C" int dm_bn_stats(const float* x, int NB, int C, int HW, float* mean, float* var, float* running_mean,
                            float* running_var, float momentum, const float* mean_shift, float* scratch, dm_stream_t stream) {
-  if (!x || !mean || !var || NB <= 0 || C <= 0 || HW <= 0) return DM_ERR_INVALID_ARG;
-  if (scratch && NB >= kBnSplits) {
-    hipStream_t st = (hipStream_t)stream;
-    float* ps = scratch;
-    float* pq = scratch + (size_t)C * kBnSplits;
-    DM_LAUNCH(bn_stats_split_kernel<0>, dim3(C, kBnSplits), dim3(256), 0, st, x, NB, C, HW, ps, pq);
-    int rc = dm_check_launch();
-    if (rc != DM_OK) return rc;
-    DM_LAUNCH(bn_stats_split_kernel<1>, dim3(C, kBnSplits), dim3(256), 0, st, x, NB, C, HW, ps, pq);
-    rc = dm_check_launch();
-    if (rc != DM_OK) return rc;
-    DM_LAUNCH(bn_stats_finalize_kernel, dim3(dm_ceil_div(C, 128)), dim3(128), 0, st, ps, pq, C, (long long)NB * HW, mean, var,
-              running_mean, running_var, momentum, mean_shift);
-    return dm_check_launch();
+  if (!x || !mean || !var) return DM_ERR_INVALID_ARG;
+  const MaskPreRoute r = stats_route({DM_MASK_PRE_STATS, NB, C, 1, HW, scratch != nullptr, mp_align(x, nullptr), 0});
+  if (r.rc != DM_OK || r.count == 0) return r.rc;
+  return stats_emit(r, x, NB, C, HW, mean, var, running_mean, running_var, momentum, mean_shift, scratch, (hipStream_t)stream);
+}
+
+static MaskPreRoute fwd_route(const MaskPreCall& c) {
+  if (c.NB < 0 || c.C <= 0 || c.H <= 0 || c.W <= 0) return mp_refuse(DM_ERR_INVALID_ARG);
+  MaskPreRoute r;
+  if (c.NB == 0) return r;
+  const long long OHW = (long long)((c.H - 1) / 2 + 1) * ((c.W - 1) / 2 + 1);
+  const long long total = (long long)c.NB * c.C * OHW;
+  const long long pblocks = (OHW + 1023) / 1024;
+  // the rows kernel: even W (8-byte loads of column pairs: x 8-byte aligned), 16-bit output indices, a 31-bit grid
+  if (!(c.W & 1) && c.W >= 4 && OHW < 65536 && (long long)c.NB * c.C * pblocks < 0x7fffffffLL && c.align >= 8)
+    mp_add(r, {MK_FWD_ROWS, {0, 0, 0}, (int)((long long)c.NB * c.C * pblocks), 1, 256, 0, 0, 0});
+  else
+    mp_add(r, {MK_FWD, {0, 0, 0}, (int)std::min<long long>((total + 255) / 256, 16384), 1, 256, 0, 0, 0});
+  return r;
+}
+
+static int fwd_emit(const MaskPreRoute& r, const float* x, int NB, int C, int H, int W, const float* mean, const float* var,
+                    const float* gamma, const float* beta, float eps, float* out, hipStream_t st) {
+  const MaskPreLaunch& l = r.launch[0];
+  const dim3 grid = mp_grid(l), block((unsigned)l.threads);
+  const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
+  if (l.kernel == MK_FWD_ROWS) {
+    const unsigned m_ow = 0xFFFFFFFFu / (unsigned)OW + 1u;      // OW >= 2; o * OW < 2^32
+    DM_LAUNCH(bn_relu_maxpool_rows_kernel, grid, block, 0, st, x, dm_ceil_div(OH * OW, 1024), C, H, W, mean, var, gamma, beta, eps,
+              out, OH, OW, m_ow);
+  } else {
+    DM_LAUNCH(bn_relu_maxpool_kernel, grid, block, 0, st, x, NB, C, H, W, mean, var, gamma, beta, eps, out, OH, OW);
   }
-  DM_LAUNCH(bn_stats_kernel, dim3(C), dim3(1024), 0, (hipStream_t)stream, x, NB, C, HW, mean, var,
-                     running_mean, running_var, momentum, mean_shift);
   return dm_check_launch();
 }
 
 extern "C" int dm_bn_relu_maxpool_fwd(const float* x, int NB, int C, int H, int W, const float* mean, const float* var,
                                       const float* gamma, const float* beta, float eps, float* out,
                                       dm_stream_t stream) {
-  if (!x || !mean || !var || !gamma || !beta || !out || NB < 0 || C <= 0 || H <= 0 || W <= 0) return DM_ERR_INVALID_ARG;
-  if (NB == 0) return DM_OK;
-  const int OH = (H + 2 - 3) / 2 + 1, OW = (W + 2 - 3) / 2 + 1;
-  const size_t total = (size_t)NB * C * OH * OW;
-  const int pblocks = dm_ceil_div(OH * OW, 1024);
-  if (!(W & 1) && W >= 4 && OH * OW < 65536 && (long long)NB * C * pblocks < 0x7fffffffLL && (((uintptr_t)x) & 7) == 0) {
-    const unsigned m_ow = 0xFFFFFFFFu / (unsigned)OW + 1u;      // OW >= 2; o * OW < 2^32
-    DM_LAUNCH(bn_relu_maxpool_rows_kernel, dim3((unsigned)(NB * C * pblocks)), dim3(256), 0, (hipStream_t)stream, x, pblocks, C, H, W,
-              mean, var, gamma, beta, eps, out, OH, OW, m_ow);
-    return dm_check_launch();
-  }
-  const int blocks = (int)min((size_t)dm_ceil_div((long long)total, 256), (size_t)16384);
-  DM_LAUNCH(bn_relu_maxpool_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, NB, C, H, W, mean, var,
-                     gamma, beta, eps, out, OH, OW);
-  return dm_check_launch();
+  if (!x || !mean || !var || !gamma || !beta || !out) return DM_ERR_INVALID_ARG;
+  const MaskPreRoute r = fwd_route({DM_MASK_PRE_FWD, NB, C, H, W, 0, mp_align(x, nullptr), 0});
+  if (r.rc != DM_OK || r.count == 0) return r.rc;
+  return fwd_emit(r, x, NB, C, H, W, mean, var, gamma, beta, eps, out, (hipStream_t)stream);
 }
 
 // Which tap each pooled output took: the plane index (y * W + x) of the window's first maximum of z = relu(bn(x)) -- of its
@@ -514,6 +605,9 @@ __global__ __launch_bounds__(256) void bn_bwd_split_kernel(const float* __restri
 // (Measured and dropped: a second pass that rebuilds gz instead of reading it back, so that gz is never written --
 // 1.44 instead of 3.0 GB through HBM, and slower, 0.98 ms: the plane pipeline (stage, arg-max, gather: three barriers)
 // is latency-bound at 2.8 TB/s, the streaming passes it would replace run at 4.6-5.3.)
+// EVEN (the 2 x 2 block form: H and W even, W >= 4; 8-byte accesses) and PRE (the prefetch: a plane's quads and pooled
+// gradients fit PIT = 4 slots of 256 threads) are the route's decisions (bwd_route): the kernel looks at no pointer's value.
+template <bool EVEN, bool PRE>
 __global__ __launch_bounds__(256) void maxpool_relu_bwd_sums_kernel(const float* __restrict__ x, int NB, int C, int H, int W,
                                                                     const float* __restrict__ mean, const float* __restrict__ var,
                                                                     const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -530,13 +624,13 @@ __global__ __launch_bounds__(256) void maxpool_relu_bwd_sums_kernel(const float*
   const float invstd = 1.0f / sqrtf(var[c] + eps);
   const float g = gamma[c], b = beta[c], m = mean[c];
   float s1 = 0.f, s2 = 0.f;
-  const bool even = !(H & 1) && !(W & 1) && W >= 4 && (((uintptr_t)x | (uintptr_t)gz) & 7) == 0;
+  constexpr bool even = EVEN;
   const unsigned m_bw = W >= 4 ? 0xFFFFFFFFu / (unsigned)(W >> 1) + 1u : 0u;      // blk / (W / 2) by multiply-high (W / 2 >= 2)
   // a plane's x quads and grad_out values are fetched into registers one plane ahead (maps up to 4096 / 1024 elements:
   // MaskPre's 56 x 56 and 28 x 28), so that the stage -> arg-max -> gather chain of a plane does not start with a round
   // trip to HBM
-  constexpr int PIT = 4;
-  const bool pre = HW / 4 <= PIT * 256 && OHW <= PIT * 256;
+  constexpr int PIT = kSumsPrefetchSlots;
+  constexpr bool pre = PRE;
   dm_f32x4 nx[PIT];
   float ng[PIT];
   auto fetch = [&](int n) {
@@ -673,50 +767,92 @@ __global__ __launch_bounds__(256) void maxpool_relu_bwd_sums_kernel(const float*
 
 }  // namespace
 
+static MaskPreRoute bwd_route(const MaskPreCall& c) {
+  const long long HW = (long long)c.H * c.W;
+  if (c.NB <= 0 || c.C <= 0 || c.H <= 0 || c.W <= 0 || HW > 0x7fffffffLL) return mp_refuse(DM_ERR_INVALID_ARG);
+  MaskPreRoute r;
+  const long long OHW = (long long)((c.H - 1) / 2 + 1) * ((c.W - 1) / 2 + 1);
+  const long long planes = (long long)c.NB * c.C, total = planes * OHW;
+  const long long plane_lds = (HW + 2 * OHW) * (long long)sizeof(float);      // z plane, arg, val
+  const bool split = c.scratch && c.NB >= kBnSplits;
+  // both plane kernels move x and grad_x as 16-byte vectors: every plane must start on a 16-byte boundary
+  const bool quads = (HW & 3) == 0 && c.align >= 16 && planes <= 0x7fffffffLL;
+  // (a workgroup per (channel, split): needs enough channels to fill the chip -- 256 x 16 x 28 x 28 measured 0.082 vs 0.055 ms)
+  if (split && (long long)c.C * kBnSplits >= 4LL * c.cus && quads && plane_lds + kRedNarrow <= kMaskPreLdsLimit) {
+    const int even = !(c.H & 1) && !(c.W & 1) && c.W >= 4;      // 2 x 2 blocks (8-byte accesses: within the 16 asked for above)
+    const int pre = HW / 4 <= kSumsPrefetchSlots * 256 && OHW <= kSumsPrefetchSlots * 256;
+    mp_add(r, {MK_POOL_SUMS, {even, pre, 0}, c.C, kBnSplits, 256, kRedNarrow, (int)plane_lds, 0});
+    mp_add(r, {MK_BN_BWD_SPLIT, {1, 0, 0}, c.C, kBnSplits, 256, 0, 0, 0});      // (pass 1 reduces nothing: no `red`)
+    return r;
+  }
+  if (quads && plane_lds <= kMaskPreLdsLimit)
+    mp_add(r, {MK_POOL_LDS, {0, 0, 0}, (int)std::min<long long>(planes, 16LL * c.cus), 1, 256, 0, (int)plane_lds, 0});
+  else      // the scatter adds with float atomics: grad_x is cleared first
+    mp_add(r, {MK_POOL_SCATTER, {0, 0, 0}, (int)std::min<long long>((total + 255) / 256, 16384), 1, 256, 0, 0, 1});
+  if (split) {
+    mp_add(r, {MK_BN_BWD_SPLIT, {0, 0, 0}, c.C, kBnSplits, 256, kRedNarrow, 0, 0});
+    mp_add(r, {MK_BN_BWD_SPLIT, {1, 0, 0}, c.C, kBnSplits, 256, 0, 0, 0});      // (pass 1 reduces nothing: no `red`)
+  } else {
+    mp_add(r, {MK_BN_BWD, {0, 0, 0}, c.C, 1, 1024, kRedWide, 0, 0});
+  }
+  return r;
+}
+
+static int bwd_emit(const MaskPreRoute& r, const float* x, int NB, int C, int H, int W, const float* mean, const float* var,
+                    const float* gamma, const float* beta, float eps, const float* grad_out, float* grad_x, float* grad_gamma,
+                    float* grad_beta, float* scratch, hipStream_t st) {
+  const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
+  for (int i = 0; i < r.count; ++i) {
+    const MaskPreLaunch& l = r.launch[i];
+    const dim3 grid = mp_grid(l), block((unsigned)l.threads);
+    const size_t lds = (size_t)l.lds_dynamic;
+    if (l.clear && hipMemsetAsync(grad_x, 0, (size_t)NB * C * H * W * sizeof(float), st) != hipSuccess) return DM_ERR_LAUNCH;
+    if (l.kernel == MK_POOL_SUMS) {
+      const auto fn = l.p[0] ? (l.p[1] ? maxpool_relu_bwd_sums_kernel<true, true> : maxpool_relu_bwd_sums_kernel<true, false>)
+                             : (l.p[1] ? maxpool_relu_bwd_sums_kernel<false, true> : maxpool_relu_bwd_sums_kernel<false, false>);
+      DM_LAUNCH(fn, grid, block, lds, st, x, NB, C, H, W, mean, var, gamma, beta, eps, grad_out, grad_x, OH, OW, scratch);
+    } else if (l.kernel == MK_POOL_LDS) {
+      DM_LAUNCH(maxpool_relu_bwd_lds_kernel, grid, block, lds, st, x, NB, C, H, W, mean, var, gamma, beta, eps, grad_out, grad_x, OH,
+                OW);
+    } else if (l.kernel == MK_POOL_SCATTER) {
+      DM_LAUNCH(maxpool_relu_bwd_kernel, grid, block, 0, st, x, NB, C, H, W, mean, var, gamma, beta, eps, grad_out, grad_x, OH, OW);
+    } else if (l.kernel == MK_BN_BWD_SPLIT) {
+      const auto fn = l.p[0] == 0 ? bn_bwd_split_kernel<0> : bn_bwd_split_kernel<1>;
+      DM_LAUNCH(fn, grid, block, 0, st, x, grad_x, NB, C, H * W, mean, var, gamma, eps, scratch, grad_gamma, grad_beta);
+    } else {
+      DM_LAUNCH(bn_bwd_kernel, grid, block, 0, st, x, grad_x, NB, C, H * W, mean, var, gamma, eps, grad_gamma, grad_beta);
+    }
+    const int rc = dm_check_launch();
+    if (rc != DM_OK) return rc;
+  }
+  return DM_OK;
+}
+
 extern "C" int dm_bn_relu_maxpool_bwd(const float* x, int NB, int C, int H, int W, const float* mean, const float* var,
                                       const float* gamma, const float* beta, float eps, const float* grad_out,
                                       float* grad_x, float* grad_gamma, float* grad_beta, float* scratch,
                                       dm_stream_t stream) {
   if (!x || !mean || !var || !gamma || !beta || !grad_out || !grad_x || !grad_gamma || !grad_beta) return DM_ERR_INVALID_ARG;
-  if (NB <= 0 || C <= 0 || H <= 0 || W <= 0) return DM_ERR_INVALID_ARG;
-  const int OH = (H + 2 - 3) / 2 + 1, OW = (W + 2 - 3) / 2 + 1;
-  const size_t total = (size_t)NB * C * OH * OW;
-  hipStream_t st = (hipStream_t)stream;
-  int rc;
-  const size_t plane_lds = ((size_t)H * W + 2 * (size_t)OH * OW) * 4;
-  // (a workgroup per (channel, split): needs enough channels to fill the chip -- 256 x 16 x 28 x 28 measured 0.082 vs 0.055 ms)
-  if (scratch && NB >= kBnSplits && C * kBnSplits >= 4 * dm_num_cus() && (H * W) % 4 == 0 && plane_lds <= 64 * 1024) {
-    DM_LAUNCH(maxpool_relu_bwd_sums_kernel, dim3(C, kBnSplits), dim3(256), plane_lds, st, x, NB, C, H, W, mean, var, gamma, beta,
-              eps, grad_out, grad_x, OH, OW, scratch);
-    rc = dm_check_launch();
-    if (rc != DM_OK) return rc;
-    DM_LAUNCH(bn_bwd_split_kernel<1>, dim3(C, kBnSplits), dim3(256), 0, st, x, grad_x, NB, C, H * W, mean, var, gamma, eps,
-              scratch, grad_gamma, grad_beta);
-    return dm_check_launch();
+  const MaskPreRoute r = bwd_route({DM_MASK_PRE_BWD, NB, C, H, W, scratch != nullptr, mp_align(x, grad_x), dm_num_cus()});
+  if (r.rc != DM_OK || r.count == 0) return r.rc;
+  return bwd_emit(r, x, NB, C, H, W, mean, var, gamma, beta, eps, grad_out, grad_x, grad_gamma, grad_beta, scratch,
+                  (hipStream_t)stream);
+}
+
+// What the three launchers above would launch for these host numbers: their own route functions' value, the one their emits
+// enqueue (the header has the numbers and the record layout).  Nothing below touches HIP but dm_num_cus().
+extern "C" int dm_mask_pre_plan(int op, int NB, int C, int H, int W, int scratch, int align, int cus, int* records,
+                                int max_records) {
+  if (!records || max_records < DM_MASK_PRE_PLAN_MAX_LAUNCHES || op < DM_MASK_PRE_STATS || op > DM_MASK_PRE_BWD) return DM_ERR_INVALID_ARG;
+  if (align != 4 && align != 8 && align != 16) return DM_ERR_INVALID_ARG;
+  const MaskPreCall c = {op, NB, C, H, W, scratch != 0, align, cus > 0 ? cus : dm_num_cus()};
+  const MaskPreRoute r = op == DM_MASK_PRE_STATS ? stats_route(c) : op == DM_MASK_PRE_FWD ? fwd_route(c) : bwd_route(c);
+  if (r.rc != DM_OK) return r.rc;
+  for (int l = 0; l < r.count; ++l) {
+    const MaskPreLaunch& m = r.launch[l];
+    const int rec[DM_MASK_PRE_PLAN_INTS] = {m.kernel, m.p[0], m.p[1], m.p[2], m.grid_x, m.grid_y, m.threads, m.lds_static + m.lds_dynamic,
+                                            m.clear};
+    for (int i = 0; i < DM_MASK_PRE_PLAN_INTS; ++i) records[l * DM_MASK_PRE_PLAN_INTS + i] = rec[i];
   }
-  if ((H * W) % 4 == 0 && plane_lds <= 64 * 1024) {
-    const int blocks = min(NB * C, 16 * dm_num_cus());
-    DM_LAUNCH(maxpool_relu_bwd_lds_kernel, dim3(blocks), dim3(256), plane_lds, st, x, NB, C, H, W, mean, var, gamma, beta,
-              eps, grad_out, grad_x, OH, OW);
-    rc = dm_check_launch();
-  } else {
-    if (hipMemsetAsync(grad_x, 0, (size_t)NB * C * H * W * sizeof(float), st) != hipSuccess) return DM_ERR_LAUNCH;
-    const int blocks = (int)min((size_t)dm_ceil_div((long long)total, 256), (size_t)16384);
-    DM_LAUNCH(maxpool_relu_bwd_kernel, dim3(blocks), dim3(256), 0, st, x, NB, C, H, W, mean, var, gamma, beta, eps, grad_out,
-              grad_x, OH, OW);
-    rc = dm_check_launch();
-  }
-  if (rc != DM_OK) return rc;
-  if (scratch && NB >= kBnSplits) {
-    DM_LAUNCH(bn_bwd_split_kernel<0>, dim3(C, kBnSplits), dim3(256), 0, st, x, grad_x, NB, C, H * W, mean, var, gamma, eps,
-              scratch, grad_gamma, grad_beta);
-    rc = dm_check_launch();
-    if (rc != DM_OK) return rc;
-    DM_LAUNCH(bn_bwd_split_kernel<1>, dim3(C, kBnSplits), dim3(256), 0, st, x, grad_x, NB, C, H * W, mean, var, gamma, eps,
-              scratch, grad_gamma, grad_beta);
-    return dm_check_launch();
-  }
-  DM_LAUNCH(bn_bwd_kernel, dim3(C), dim3(1024), 0, st, x, grad_x, NB, C, H * W, mean, var, gamma, eps, grad_gamma,
-            grad_beta);
-  return dm_check_launch();
+  return r.count;
 }

@@ -1839,6 +1839,44 @@ def bn_relu_maxpool_argmax(x, mean, var, gamma, beta, eps=1e-5):
     return arg
 
 
+MASK_PRE_OPS = ('stats', 'fwd', 'bwd')           # dm_mask_pre_plan's `op` (DM_MASK_PRE_*): bn_stats, bn_relu_maxpool, its backward
+MASK_PRE_KERNELS = ('stats', 'stats_split', 'stats_finalize', 'fwd', 'fwd_rows', 'pool_scatter', 'pool_lds', 'pool_sums', 'bn_bwd',
+                    'bn_bwd_split')               # field 'kernel' of a plan record
+MASK_PRE_PLAN_FIELDS = ('kernel', 'P0', 'P1', 'P2', 'grid_x', 'grid_y', 'threads', 'lds_bytes', 'clear')
+# every (kernel, P0, P1, P2) the three route functions can name, by op (include/dynamask_hip.h, dm_mask_pre_plan):
+# stats_split (PASS, VEC), pool_sums (EVEN: 2 x 2 blocks or the element form, PRE: prefetch or not), bn_bwd_split (PASS)
+MASK_PRE_BUILDS = {
+    'stats': {(0, 0, 0, 0), (2, 0, 0, 0)} | {(1, p, vec, 0) for p in (0, 1) for vec in (0, 1)},
+    'fwd': {(3, 0, 0, 0), (4, 0, 0, 0)},
+    'bwd': {(5, 0, 0, 0), (6, 0, 0, 0), (8, 0, 0, 0), (9, 0, 0, 0), (9, 1, 0, 0)} | {(7, even, pre, 0) for even in (0, 1) for pre in (0, 1)},
+}
+
+
+def mask_pre_plan_raw(op, NB, C, H, W, scratch, align, cus=0):
+    """dm_mask_pre_plan: (return code, records) for ``op`` (an index into MASK_PRE_OPS).  The code is the number of launches or
+    the (negative) error the call with these numbers would return.  ``cus`` 0: the current device's count.  Host only."""
+    consts = _abi.load()[1]
+    n, cap = consts['DM_MASK_PRE_PLAN_INTS'], consts['DM_MASK_PRE_PLAN_MAX_LAUNCHES']
+    assert len(MASK_PRE_PLAN_FIELDS) == n
+    rec = (ctypes.c_int * (n * cap))(*([-1] * (n * cap)))
+    rc = lib().dm_mask_pre_plan(int(op), int(NB), int(C), int(H), int(W), int(scratch), int(align), int(cus), rec, cap)
+    return rc, [dict(zip(MASK_PRE_PLAN_FIELDS, rec[i * n:(i + 1) * n])) for i in range(max(rc, 0))]
+
+
+def mask_pre_plan(op, NB, C, H, W, scratch=True, aligned=True, cus=0):
+    """The launches ``bn_stats`` ('stats'), ``bn_relu_maxpool`` ('fwd') or ``bn_relu_maxpool_backward`` ('bwd') would make for
+    an [NB, C, H, W] input, as the launcher's own route says (include/dynamask_hip.h, dm_mask_pre_plan): a list of dicts with
+    the keys MASK_PRE_PLAN_FIELDS.  ``scratch``: the call brings one (this module's always do).  ``aligned``: True for
+    16-byte aligned tensors (a fresh torch allocation), False for a float's 4 bytes (a view one float into a buffer), or the
+    bytes themselves (16, 8, 4).  ``cus``: route for that many compute units instead of the device's.  Raises where the call
+    would fail."""
+    align = (16 if aligned else 4) if isinstance(aligned, bool) else aligned
+    rc, recs = mask_pre_plan_raw(MASK_PRE_OPS.index(op), NB, C, H, W, 1 if scratch else 0, align, cus)
+    if rc < 0:
+        check(rc, 'dm_mask_pre_plan')
+    return recs
+
+
 # ------------------------------------------------------------------- backward ops
 def relu_backward_(grad, out):
     _chk(grad, 'grad')

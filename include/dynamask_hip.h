@@ -63,7 +63,7 @@ const char* dm_error_string(int code);
  * own report of its launches, dm_conv2d_plan (section K5/K6) and dm_conv2d_group_plan (section K25); Double-Head R-CNN's
  * rescaled RoIAlign and global average pool (section K28); the DCN forward launcher's route, dm_deform_conv_plan
  * (section K8); the weight-gradient launcher's route, dm_conv2d_wgrad_plan, and that of
- * the other training-side launchers, dm_bwd_plan; RPN inference's selection, decode and merge
+ * the other training-side launchers, dm_bwd_plan and dm_mask_pre_plan; RPN inference's selection, decode and merge
  * (section K30); the FPN neck's gathered addend and stride-2 subsample (section K31). */
 #define DM_ABI_VERSION 29 /* the one definition: dm_abi_version(), dm_build_info() and _lib.ABI_VERSION read it */
 int dm_abi_version(void);
@@ -500,6 +500,32 @@ int dm_bn_relu_maxpool_argmax(const float* x, int NB, int C, int H, int W, const
 int dm_bn_relu_maxpool_bwd(const float* x, int NB, int C, int H, int W, const float* mean, const float* var,
                            const float* gamma, const float* beta, float eps, const float* grad_out, float* grad_x,
                            float* grad_gamma, float* grad_beta, float* scratch, dm_stream_t stream);
+
+/* The launches dm_bn_stats (DM_MASK_PRE_STATS; its HW is H * W here), dm_bn_relu_maxpool_fwd (DM_MASK_PRE_FWD) and
+ * dm_bn_relu_maxpool_bwd (DM_MASK_PRE_BWD) would make for these HOST numbers: the route each launcher decides on, the very
+ * value it then enqueues (nothing is launched, no device is needed).  NB, C, H, W as the call's, and facts in place of its
+ * pointers: scratch (one is given; ignored by the forward), align (16, 8 or 4: the bytes x -- for the backward x AND grad_x --
+ * is aligned to; a float pointer has 4), and cus, the compute-unit count the backward routes by (<= 0: the current
+ * device's, 256 without one).  The routes ask for the alignment of a kernel's widest access: 16 bytes for the vector loop of
+ * the split statistics and for both plane kernels of the backward, 8 for the rows forward; a call that lacks it takes the
+ * scalar kernels (the scalar loop of the split statistics, the generic forward, the atomic scatter).  LDS is counted static
+ * plus dynamic against 64 KB: at exactly 64 KB of plane (1 x 8192) the sums kernel's 16 static bytes take the call to kernel 6.
+ * records: HOST array of max_records (>= DM_MASK_PRE_PLAN_MAX_LAUNCHES) x DM_MASK_PRE_PLAN_INTS ints.  Returns the number of
+ * launches (0: the forward's empty call, NB = 0) or the error code the call would return for these numbers -- also for an
+ * unknown op or align -- and then writes nothing.  Record l, ints [l * DM_MASK_PRE_PLAN_INTS ..):
+ *   0 kernel: 0 bn_stats_kernel, 1 bn_stats_split_kernel, 2 bn_stats_finalize_kernel, 3 bn_relu_maxpool_kernel (generic),
+ *     4 bn_relu_maxpool_rows_kernel, 5 maxpool_relu_bwd_kernel (the atomic scatter), 6 maxpool_relu_bwd_lds_kernel (plane in
+ *     LDS), 7 maxpool_relu_bwd_sums_kernel (plane in LDS, keeps BatchNorm's sums), 8 bn_bwd_kernel, 9 bn_bwd_split_kernel;
+ *   1 .. 3 its build: PASS, VEC (1: 16-byte loads), 0 (kernel 1); EVEN (1: 2 x 2 blocks, 0: the element form), PRE (1: a plane
+ *     is prefetched into registers), 0 (kernel 7); PASS, 0, 0 (kernel 9); zeros otherwise;
+ *   4 grid x, 5 grid y, 6 threads per workgroup, 7 LDS bytes of a workgroup, static plus dynamic;
+ *   8 clear: 1 where grad_x is zero-filled (hipMemsetAsync) before the launch. */
+#define DM_MASK_PRE_STATS 0
+#define DM_MASK_PRE_FWD 1
+#define DM_MASK_PRE_BWD 2
+#define DM_MASK_PRE_PLAN_INTS 9
+#define DM_MASK_PRE_PLAN_MAX_LAUNCHES 3
+int dm_mask_pre_plan(int op, int NB, int C, int H, int W, int scratch, int align, int cus, int* records, int max_records);
 
 /* K10 backward: gradient of the soft branch of the straight-through estimator
  * (y_hard = (one_hot - y).detach() + y, dynamask_roi_head.py:112-113). */

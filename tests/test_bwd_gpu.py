@@ -9,6 +9,7 @@ import torch
 import torch.nn.functional as F
 
 import golden_inputs as gi
+import mask_pre_cases as mc
 from oracle import ref_ops
 
 pytestmark = pytest.mark.gpu
@@ -494,6 +495,16 @@ def test_narrow_wgrad_kernel_odd_shapes(ops, N, Cs, Cout, H, W):
     _close_sum(dw, ref2, mag2, 'narrow wgrad, two sources')
 
 
+# the backward form each shape below is meant to reach (mask_pre_cases.BWD_FORMS: the launches by name), asserted through the
+# launcher's own plan (ops.mask_pre_plan).  The 64 channels of the sums-kernel shapes are what that route needs at 256 compute
+# units: the count is asked of the plan (64 there), so that another device tests the same form.
+BN_POOL_FORMS = {(3, 5, 10, 6): 'plane in LDS', (2, 7, 7, 9): 'atomic scatter', (4, 16, 28, 28): 'plane in LDS', (1, 3, 12, 20): 'plane in LDS',
+                 (2, 2, 56, 56): 'plane in LDS', (16, 4, 12, 20): 'plane in LDS + split BatchNorm backward',
+                 (19, 3, 28, 28): 'plane in LDS + split BatchNorm backward', (16, 3, 7, 9): 'atomic scatter + split BatchNorm backward',
+                 (16, 64, 12, 20): 'sums kernel, 2x2 blocks', (17, 64, 7, 12): 'sums kernel, element form', (16, 64, 2, 6): 'sums kernel, 2x2 blocks',
+                 (18, 64, 6, 2): 'sums kernel, element form', (33, 64, 28, 28): 'sums kernel, 2x2 blocks'}
+
+
 @pytest.mark.parametrize('N,C,H,W', [(3, 5, 10, 6), (2, 7, 7, 9), (4, 16, 28, 28), (1, 3, 12, 20), (2, 2, 56, 56),
                                      (16, 4, 12, 20), (19, 3, 28, 28), (16, 3, 7, 9),
                                      (16, 64, 12, 20), (17, 64, 7, 12), (16, 64, 2, 6), (18, 64, 6, 2), (33, 64, 28, 28)])
@@ -502,6 +513,10 @@ def test_bn_relu_maxpool_forward_and_backward_odd_shapes(ops, N, C, H, W):
     golden: non-square maps, odd sizes (the plane-in-LDS backward needs H * W % 4 == 0; 7 x 9 takes the other
     one), few channels; 16 images or more of 64 channels or more take the backward whose pooling adjoint also
     keeps BatchNorm's sums (2 x 2 blocks on even maps, the element form otherwise).  Against autograd of the same block (forward 1e-5, gradients at the 1e-4 gate)."""
+    form = BN_POOL_FORMS[(N, C, H, W)]
+    if form.startswith('sums kernel'):
+        C = mc.sums_channels(ops)
+    assert mc.route(ops, 'bwd', N, C, H, W) == mc.BWD_FORMS[form], form
     x = torch.randn(N, C, H, W, generator=_g(110)) * 1.5 + 0.3
     gamma = torch.rand(C, generator=_g(111)) + 0.5
     beta = torch.randn(C, generator=_g(112)) * 0.2

@@ -13,6 +13,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import mask_pre_cases as mc
 import nonfinite_cases as nf
 from tolerances import assert_close_via_f64
 
@@ -101,7 +102,9 @@ def test_bn_relu_maxpool_argmax_reports_torchs_index_on_nan_windows(ops, H, W):
     assert torch.equal(taken[pos], val[pos]), 'a reported tap does not hold the window\'s maximum'
 
 
-# (N, C, H, W) -> which backward form (tests/test_bwd_gpu.py::test_bn_relu_maxpool_forward_and_backward_odd_shapes)
+# (N, C, H, W) -> which backward form (tests/test_bwd_gpu.py::test_bn_relu_maxpool_forward_and_backward_odd_shapes), asserted
+# through the launcher's own plan.  The 64 channels of the sums-kernel shapes stand for "as many as that route needs on this
+# device" (64 at 256 compute units): the count is asked of the plan.
 BWD_SHAPES = [(16, 64, 12, 20, 'sums kernel, 2x2 blocks'), (17, 64, 7, 12, 'sums kernel, element form'), (3, 5, 10, 6, 'plane in LDS'),
               (2, 7, 7, 9, 'atomic scatter'), (16, 3, 7, 9, 'atomic scatter + split BatchNorm backward')]
 
@@ -113,6 +116,9 @@ def test_bn_relu_maxpool_backward_with_a_poisoned_channel(ops, N, C, H, W, form)
     routes to each window's last NaN tap and threshold_backward passes there -- a finite number, and the kernel must give
     that number (a kernel that blocks the gradient at a NaN maximum gives 0).  Every other channel holds to autograd at the
     existing gate (tests/test_bwd_gpu.py: 1e-5 forward, 1e-4 gradients)."""
+    if form.startswith('sums kernel'):
+        C = mc.sums_channels(ops)
+    assert mc.route(ops, 'bwd', N, C, H, W) == mc.BWD_FORMS[form], form
     x = torch.randn(N, C, H, W, generator=nf.gen(520)) * 1.5 + 0.3
     x[N - 1, 1, H - 3, 2] = NAN
     gamma, beta = torch.rand(C, generator=nf.gen(521)) + 0.5, torch.randn(C, generator=nf.gen(522)) * 0.2
