@@ -10,7 +10,10 @@ stride of 2 sits, with ``style='caffe'``, in the two 1x1 convolutions of block 0
 launch being ``ops.subsample2(x)``.  The stride-1 3x3 convolutions are ``ops.conv2d`` launches, ``ops.conv3x3_dil`` at
 dilation 1 on maps wider than ``layers.CONV2D_3X3_MAX_WIDTH``: the width alone decides.  Every launch is exact fp32 in
 every precision mode and none splits its K loop, so an image's bits do not depend on the other images of the call.  The
-host never waits; the image is not written."""
+host never waits; the image is not written.
+
+``ResNeXt`` (mmdet/models/backbones/resnext.py) is ``ResNet`` whose blocks run conv2 in ``groups`` groups: one
+``ops.conv3x3_grouped`` launch (``dm_conv3x3_grouped_fwd``, stride 1 or 2) in place of the dense 3x3, at any map width."""
 import torch
 import torch.nn as nn
 
@@ -98,9 +101,9 @@ class ResNet(nn.Module):
             planes = base_channels * 2 ** i
             out = planes * Bottleneck.expansion
             down = strides[i] != 1 or inplanes != out
-            blocks = [Bottleneck(inplanes, planes, downsample=down, stride=strides[i], style=style,
-                                 wide_from=CONV2D_3X3_MAX_WIDTH)]
-            blocks += [Bottleneck(out, planes, wide_from=CONV2D_3X3_MAX_WIDTH) for _ in range(1, num_blocks)]
+            kw = dict(wide_from=CONV2D_3X3_MAX_WIDTH, **self._block_kwargs(planes))
+            blocks = [Bottleneck(inplanes, planes, downsample=down, stride=strides[i], style=style, **kw)]
+            blocks += [Bottleneck(out, planes, **kw) for _ in range(1, num_blocks)]
             inplanes = out
             name = f'layer{i + 1}'
             self.add_module(name, nn.Sequential(*blocks))
@@ -117,6 +120,10 @@ class ResNet(nn.Module):
     @property
     def norm1(self):
         return self.bn1
+
+    def _block_kwargs(self, planes):
+        """What a stage of ``planes`` passes to its blocks beyond ResNet's own arguments (ResNeXt: the groups)."""
+        return {}
 
     def _freeze_stages(self):
         """resnet.py:573-589: the stem and the first ``frozen_stages`` stages stop asking for gradients."""
@@ -182,3 +189,33 @@ class ResNet(nn.Module):
             if i in self.out_indices:
                 outs.append(x)
         return tuple(outs)
+
+
+@BACKBONES.register_module()
+class ResNeXt(ResNet):
+    """``ResNeXt`` -- backbones/resnext.py:87-132, inference: ``ResNet`` whose blocks run conv2 in ``groups`` groups on
+    ``width = floor(planes * base_width / base_channels) * groups`` channels (``layers.Bottleneck``: ONE
+    ``ops.conv3x3_grouped`` launch, stride 1 or 2).  ``state_dict`` keys as ``ResNet``'s, the shapes the reference's:
+    ``conv1`` [width, inplanes, 1, 1], ``conv2`` [width, width / groups, 3, 3], ``conv3`` [4 planes, width, 1, 1].  Every
+    refusal of ``ResNet`` holds; the grouped kernel is built for 4, 8, 16, 32 and 64 channels per group -- what 32x4d,
+    64x4d and 32x8d have in layers 1 to 4 --, anything else is refused here, at construction.  ``groups=1`` is
+    ``ResNet``'s dense path."""
+
+    arch_settings = {d: (Bottleneck, b) for d, b in _STAGE_BLOCKS.items()}
+    CHANNELS_PER_GROUP = (4, 8, 16, 32, 64)
+
+    def __init__(self, groups=1, base_width=4, **kwargs):
+        self.groups, self.base_width = groups, base_width
+        super().__init__(**kwargs)
+
+    def _block_kwargs(self, planes):
+        if self.groups == 1:
+            return {}
+        groups, bw, bc = self.groups, self.base_width, self.base_channels
+        per_group = planes * bw // bc if isinstance(groups, int) and groups > 1 else 0
+        if per_group not in self.CHANNELS_PER_GROUP or per_group * groups % 8 != 0:
+            raise NotImplementedError(
+                f'ResNeXt: groups={groups}, base_width={bw} (base_channels={bc}) give {per_group} channels per group, '
+                f'{per_group * groups if per_group else 0} in all, in the stage of {planes} planes; the grouped 3x3 kernel is built for '
+                f'{self.CHANNELS_PER_GROUP} channels per group and the 1x1 kernels beside it for widths that are multiples of 8')
+        return dict(groups=groups, base_width=bw, base_channels=bc)

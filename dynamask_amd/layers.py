@@ -198,6 +198,21 @@ class _FoldedConv:
         return self._pk.get_multi('pack', self._tensors(), make)
 
 
+class _FoldedGroupedConv(_FoldedConv):
+    """A grouped 3x3 convolution (weight [C, C / groups, 3, 3]) + its BatchNorm folded -- ``fold_bn`` scales per output
+    channel, whatever the weight's second dimension --, in ``ops.conv3x3_grouped``'s layout."""
+
+    def __init__(self, pairs, groups):
+        super().__init__(pairs, [pairs[0][0].out_channels])
+        self.groups = groups
+
+    def packed(self):
+        def make():
+            w, b = self.folded()
+            return ops.pack_grouped_conv_weight(w, self.groups), b
+        return self._pk.get_multi('pack3g', self._tensors(), make)
+
+
 class BNConvModule(nn.Module):
     """mmcv ConvModule(bias=False, norm_cfg=dict(type='BN')): keys ``conv.weight``, ``bn.*``.  A parameter holder: the
     block that owns it folds the BatchNorm and launches."""
@@ -222,10 +237,16 @@ class Bottleneck(nn.Module):
     style 'caffe' runs the block on ``ops.subsample2(x)``; style 'pytorch' runs conv1 at full size, conv2 through
     ``ops.conv3x3_s2`` (one workgroup per tile walks all of K: ``splits=1``) and closes with the two-source 1x1 of
     [conv2 output, ``ops.subsample2(x)``].  ``wide_from``: a width above which the stride-1 conv2 runs on
-    ``ops.conv3x3_dil`` (dilation 1, any width, the same packed weights) instead of ``ops.conv2d``."""
+    ``ops.conv3x3_dil`` (dilation 1, any width, the same packed weights) instead of ``ops.conv2d``.
+
+    ``groups > 1`` (backbones/resnext.py:11-84, backbones.ResNeXt): conv1 and conv3 have ``width = floor(planes *
+    base_width / base_channels) * groups`` channels between them and conv2 is ``width -> width`` in ``groups`` groups
+    (weight [width, width / groups, 3, 3]): ONE ``ops.conv3x3_grouped`` launch at any map width (``wide_from`` does not
+    apply), with ``stride=2`` where style 'pytorch' strides.  The block stays three launches."""
     expansion = 4
 
-    def __init__(self, inplanes, planes, downsample=False, stride=1, style='pytorch', wide_from=None):
+    def __init__(self, inplanes, planes, downsample=False, stride=1, style='pytorch', wide_from=None, groups=1, base_width=4,
+                 base_channels=64):
         super().__init__()
         if not downsample and inplanes != planes * self.expansion:
             raise NotImplementedError('Bottleneck: no downsample path (DoubleConvFCBBoxHead: planes = inplanes / 4)')
@@ -233,18 +254,24 @@ class Bottleneck(nn.Module):
             raise NotImplementedError(f'Bottleneck: stride={stride}, style={style!r}, downsample={downsample}; stride 1, or '
                                       "stride 2 with a downsample path, in style 'pytorch' or 'caffe' are built")
         self.stride, self.style, self.wide_from = stride, style, wide_from
-        self.inplanes, self.planes = inplanes, planes
+        self.inplanes, self.planes, self.groups = inplanes, planes, groups
+        width = self.width = planes if groups == 1 else (planes * base_width // base_channels) * groups
+        if groups < 1 or width < groups:
+            raise ValueError(f'Bottleneck: groups={groups}, base_width={base_width}, base_channels={base_channels} leave '
+                             f'{width} channels for {groups} groups at planes={planes}')
         out = planes * self.expansion
-        self.conv1, self.bn1 = _conv_weight(planes, inplanes, 1), _BN(planes)
-        self.conv2, self.bn2 = _conv_weight(planes, planes, 3), _BN(planes)
-        self.conv3, self.bn3 = _conv_weight(out, planes, 1), _BN(out)
-        self._f = [_FoldedConv([(c, bn)], [c.in_channels]) for c, bn in ((self.conv1, self.bn1), (self.conv2, self.bn2))]
+        self.conv1, self.bn1 = _conv_weight(width, inplanes, 1), _BN(width)
+        self.conv2, self.bn2 = _conv_weight(width, width // groups, 3), _BN(width)
+        self.conv3, self.bn3 = _conv_weight(out, width, 1), _BN(out)
+        self._f = [_FoldedConv([(self.conv1, self.bn1)], [inplanes]),
+                   (_FoldedConv([(self.conv2, self.bn2)], [width]) if groups == 1 else
+                    _FoldedGroupedConv([(self.conv2, self.bn2)], groups))]
         if downsample:
             self.downsample = nn.Sequential(_conv_weight(out, inplanes, 1), _BN(out))
-            self._f.append(_FoldedConv([(self.conv3, self.bn3), (self.downsample[0], self.downsample[1])], [planes, inplanes]))
+            self._f.append(_FoldedConv([(self.conv3, self.bn3), (self.downsample[0], self.downsample[1])], [width, inplanes]))
         else:
             self.downsample = None
-            self._f.append(_FoldedConv([(self.conv3, self.bn3)], [planes]))
+            self._f.append(_FoldedConv([(self.conv3, self.bn3)], [width]))
 
     def forward(self, x):
         """Without ``downsample``: ``x`` [N, inplanes, H, W] is overwritten with the block's output and returned.  With
@@ -252,14 +279,18 @@ class Bottleneck(nn.Module):
         (w1, b1), (w2, b2), (w3, b3) = (f.packed() for f in self._f)
         if self.stride == 2 and self.style == 'caffe':
             x = ops.subsample2(x)
-        h = ops.conv2d(x, w1, b1, self.planes, 1, relu=True)
-        if self.stride == 2 and self.style == 'pytorch':
+        h = ops.conv2d(x, w1, b1, self.width, 1, relu=True)
+        strided = self.stride == 2 and self.style == 'pytorch'
+        if self.groups > 1:
+            h = ops.conv3x3_grouped(h, w2, b2, self.groups, stride=2 if strided else 1, relu=True)
+        elif strided:
             h = ops.conv3x3_s2(h, w2, b2, self.planes, relu=True, splits=1)
-            x = ops.subsample2(x)
         elif self.wide_from is not None and h.shape[3] > self.wide_from:
             h = ops.conv3x3_dil(h, w2, b2, self.planes, 1, relu=True)
         else:
             h = ops.conv2d(h, w2, b2, self.planes, 3, relu=True)
+        if strided:
+            x = ops.subsample2(x)
         if self.downsample is not None:
             return ops.conv2d([h, x], w3, b3, self.planes * self.expansion, 1, relu=True)
         return ops.conv2d(h, w3, b3, self.inplanes, 1, relu=True, out=x, accumulate=True)

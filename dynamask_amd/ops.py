@@ -3186,6 +3186,57 @@ def maxpool3x3_s2(x, out=None):
     return out
 
 
+# ------------------------------------------------------------------ ResNeXt's grouped 3x3 (dynamask_hip.h section K34)
+# Exact fp32 in every precision mode, like the stem.
+def pack_grouped_conv_weight(w, groups):
+    """[C, C / groups, 3, 3] -> the operand of ``conv3x3_grouped``: [C / T][C / groups][9][T] with T =
+    dm_conv3x3_grouped_couts_per_wave(C, groups) neighbouring output channels side by side (dm_conv3x3_grouped_pack's
+    layout, made by a permutation on the weight's own device)."""
+    if not isinstance(w, torch.Tensor) or w.dtype != torch.float32:
+        raise TypeError('pack_grouped_conv_weight: a float32 tensor expected')
+    groups = int(groups)
+    if w.dim() != 4 or groups < 1 or w.shape[0] % groups != 0 or tuple(w.shape[1:]) != (w.shape[0] // groups, 3, 3):
+        raise ValueError(f'pack_grouped_conv_weight: a [C, C / groups, 3, 3] weight expected at groups={groups}, got {list(w.shape)}')
+    C, cg = w.shape[:2]
+    T = lib().dm_conv3x3_grouped_couts_per_wave(int(C), groups)
+    if T == 0:
+        raise NotImplementedError(f'pack_grouped_conv_weight: {cg} channels per group (C={C}, groups={groups}); 4, 8, 16, 32 and 64 are built')
+    return w.reshape(C // T, T, cg, 9).permute(0, 2, 3, 1).contiguous().view(-1)
+
+
+def conv3x3_grouped_supported(x, groups, stride):
+    """Does ``conv3x3_grouped`` take this input (dm_conv3x3_grouped_supported: 4 / 8 / 16 / 32 / 64 channels per group,
+    stride 1 or 2, any H, W)?  ``x``: a tensor or its shape."""
+    NB, C, H, W = x.shape if isinstance(x, torch.Tensor) else x
+    return bool(lib().dm_conv3x3_grouped_supported(int(NB), int(C), int(H), int(W), int(groups), int(stride)))
+
+
+def conv3x3_grouped(x, w_packed, bias, groups, stride=1, relu=False, out=None):
+    """Conv2d(C, C, 3, stride, padding=1, groups=groups)(x) + bias (+ ReLU) -> [NB, C, ceil(H / stride), ceil(W / stride)]
+    (dm_conv3x3_grouped_fwd).  ``w_packed``: ``pack_grouped_conv_weight`` of the [C, C / groups, 3, 3] weight."""
+    _chk(x, 'x')
+    _chk(w_packed, 'w_packed')
+    if bias is not None:
+        _chk(bias, 'bias')
+    NB, C, H, W = x.shape
+    groups, stride = int(groups), int(stride)
+    if stride not in (1, 2):
+        raise NotImplementedError(f'conv3x3_grouped: stride={stride}; 1 and 2 are built')
+    flags = (1 if relu else 0) | (16 if conv_layout(w_packed) == 'bf16x3' else 0)
+    if not flags & 16:
+        assert w_packed.numel() == lib().dm_conv3x3_grouped_packed_floats(C, groups), 'weights packed for another shape'
+        assert bias is None or bias.numel() == C
+    shape = (NB, C, (H + stride - 1) // stride, (W + stride - 1) // stride)
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=torch.float32)
+    else:
+        _chk(out, 'out')
+        assert tuple(out.shape) == shape
+    check(lib().dm_conv3x3_grouped_fwd(_p(x), NB, C, H, W, _p(w_packed), _p(bias), groups, stride, flags, _p(out), _stream()),
+          'dm_conv3x3_grouped_fwd')
+    return out
+
+
 # ------------------------------------------------------------------ image pre-processing (dynamask_hip.h section K33)
 PREPROCESS_MAX_IMAGES = _abi.load()[1]['DM_PREPROCESS_MAX_IMAGES']
 _RESIZE_TABLES = {}        # (n_src, n_dst) -> resize_axis_table's arrays

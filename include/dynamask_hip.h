@@ -1480,6 +1480,39 @@ int dm_preprocess_u8_fwd(const uint8_t* const* srcs, const int* dims, int B, con
                          const float* mean, const float* stdinv, int to_rgb, float* out, int Hp, int Wp,
                          dm_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * K34  (added to ABI 29) ResNeXt backbone inference: the grouped 3x3 convolution that is conv2 of every block
+ *      (mmdet/models/backbones/resnext.py:54-63: build_conv_layer(..., kernel_size=3, stride, padding=1, groups)).
+ *      Everything else of a ResNeXt stage is the launches of K32.  Exact fp32 in every precision mode, deterministic,
+ *      no atomics, no workspace.
+ *
+ * dm_conv3x3_grouped_fwd: out = act(Conv2d(C, C, 3, stride, padding = 1, groups)(x) + bias): x [NB, C, H, W], out
+ * [NB, C, Ho, Wo] with Ho = ceil(H / stride), Wo = ceil(W / stride); bias [C] or NULL; x is only read.  Output channel
+ * co belongs to group co / (C / groups) and reads the C / groups input channels of that group ONLY: no value of another
+ * group's input enters any product, so a NaN or an Inf stays in its group.  flags: bit 0 ReLU (NaN stays NaN); bit 3 is
+ * accepted and ignored; bit 4 (the bf16x3 layout): DM_ERR_UNSUPPORTED; any other bit: DM_ERR_INVALID_ARG.  The sum of
+ * an output is one fp32 fma chain from zero over its group's input channels in order and, in a channel, ky = 0 .. 2,
+ * kx = 0 .. 2 (a tap in the padding multiplies a zero), the bias added last: it does not depend on NB, H, W or the
+ * output's position, so an image's bits do not depend on the other images of the call.
+ * w_packed: the [C, C / groups, 3, 3] weight as [C / T][C / groups][9][T] -- T = dm_conv3x3_grouped_couts_per_wave(C,
+ * groups) neighbouring output channels side by side per (input channel, tap) -- dm_conv3x3_grouped_packed_floats(C,
+ * groups) = 9 C C / groups floats.  dm_conv3x3_grouped_pack writes that layout from HOST memory to HOST memory (the
+ * Python side makes the same permutation on the device, ops.pack_grouped_conv_weight).
+ * dm_conv3x3_grouped_supported: 1 exactly when NB >= 1, groups >= 1, C / groups is one of 4, 8, 16, 32, 64 (C a
+ * multiple of groups), stride is 1 or 2, 1 <= H, W, C <= 2^24 and the launch has fewer than 2^31 workgroups (NB * groups
+ * * ceil(Ho / TH) * ceil(Wo / 32), TH = 32 / 16 / 8 rows at 4 / 8 / >= 16 channels per group).  One build per (C /
+ * groups, stride); nothing else decides.  dm_conv3x3_grouped_fwd returns DM_ERR_UNSUPPORTED for anything else -- from
+ * the host arguments alone --, DM_OK without a launch for NB == 0 (pointers unread), DM_ERR_INVALID_ARG for a null x,
+ * w_packed or out.  dm_conv3x3_grouped_couts_per_wave: 0, dm_conv3x3_grouped_packed_floats: -1 and
+ * dm_conv3x3_grouped_pack: DM_ERR_UNSUPPORTED for channels per group outside the five.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int dm_conv3x3_grouped_couts_per_wave(int C, int groups);
+long long dm_conv3x3_grouped_packed_floats(int C, int groups);
+int dm_conv3x3_grouped_pack(const float* w, int C, int groups, float* w_packed);
+int dm_conv3x3_grouped_supported(int NB, int C, int H, int W, int groups, int stride);
+int dm_conv3x3_grouped_fwd(const float* x, int NB, int C, int H, int W, const float* w_packed, const float* bias,
+                           int groups, int stride, int flags, float* out, dm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
