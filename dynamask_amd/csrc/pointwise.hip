@@ -1333,3 +1333,43 @@ extern "C" int dm_subsample2_fwd(const float* in, long long NC, int H, int W, fl
   DM_LAUNCH(subsample2_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, in, total, H, W, OH, OW, out);
   return dm_check_launch();
 }
+
+// (K35) Res2Net's avg_down identity path: AvgPool2d(2, 2, ceil_mode=True, count_include_pad=False).  One output per thread
+// in the flat order of out; the window's elements inside the map are added row-major from zero and the sum is divided
+// once by their number (4, 2 or 1: an edge window of an odd map covers fewer).
+namespace {
+__global__ __launch_bounds__(256) void avgpool2x2_ceil_kernel(const float* __restrict__ in, long long total, int H, int W, int OH,
+                                                              int OW, float* __restrict__ out) {
+  const long long step = (long long)gridDim.x * 256;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += step) {
+    const long long row = i / OW;            // nc * OH + y
+    const int x = (int)(i - row * OW);
+    const long long nc = row / OH;
+    const int y = (int)(row - nc * OH);
+    const float* p = in + (nc * H + 2 * y) * W + 2 * x;       // 2 y <= H - 1 and 2 x <= W - 1
+    const bool right = 2 * x + 1 < W, below = 2 * y + 1 < H;
+    float sum = p[0];
+    if (right) sum += p[1];
+    if (below) {
+      sum += p[W];
+      if (right) sum += p[W + 1];
+    }
+    out[i] = sum / (float)((right ? 2 : 1) * (below ? 2 : 1));
+  }
+}
+}  // namespace
+
+extern "C" int dm_avgpool2x2_ceil_supported(long long NC, int H, int W) {
+  return (NC >= 0 && H >= 1 && W >= 1 && NC <= (1LL << 40) / ((long long)H * W)) ? 1 : 0;
+}
+
+extern "C" int dm_avgpool2x2_ceil_fwd(const float* in, long long NC, int H, int W, float* out, dm_stream_t stream) {
+  if (!dm_avgpool2x2_ceil_supported(NC, H, W)) return DM_ERR_UNSUPPORTED;
+  if (NC == 0) return DM_OK;
+  if (!in || !out) return DM_ERR_INVALID_ARG;
+  const int OH = (H + 1) / 2, OW = (W + 1) / 2;
+  const long long total = NC * OH * OW;
+  const int blocks = (int)min((long long)dm_ceil_div(total, 256), 16384LL);
+  DM_LAUNCH(avgpool2x2_ceil_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, in, total, H, W, OH, OW, out);
+  return dm_check_launch();
+}

@@ -3,6 +3,8 @@
 //   dm_conv7x7_s2_fwd      conv1: 7x7, stride 2, padding 3, from 3 channels, + bias (the folded bn1) (+ ReLU), out
 //                          [NB, Cout, ceil(H / 2), ceil(W / 2)].  Exact fp32 on v_mfma_f32_32x32x2_f32.
 //   dm_maxpool3x3_s2_fwd   MaxPool2d(3, stride 2, padding 1), torch's NaN rule, padding taps take no part.
+//   dm_conv3x3_s2_c3_fwd   the first convolution of the deep stem (resnet.py:525-545, Res2Net): 3x3, stride 2, padding 1,
+//                          from 3 channels, + bias (+ ReLU).  Exact fp32, a direct vector kernel (below).
 //
 // GEMM view of the convolution: K is the 147 products (c, ky, kx) laid out as 21 ROWS (c, ky) of 8 kx SLOTS, slot 7 a zero
 // weight: K = 168 = 42 quads, the weight operand dm_conv_pack_weight's 1x1 layout [42][CoutP][4] of that [Cout, 168]
@@ -187,7 +189,91 @@ __global__ __launch_bounds__(256) void maxpool3x3_s2_kernel(const float* __restr
   }
 }
 
+// ------------------------------------------------------------------------------------------------ deep stem, first conv
+// 27 products per output: a thread owns ONE output pixel (consecutive lanes are consecutive pixels of the image's flat
+// map, so loads and stores run along rows), reads its own 27 taps into registers -- a tap outside the map is a zero
+// operand, and no other pixel's value enters --, and makes S3_CT output channels from them, four fma chains at a time.
+// The weights [Cout, 27] are torch's own layout, read through wave-uniform addresses.  The chain of an output: c = 0 .. 2,
+// ky = 0 .. 2, kx = 0 .. 2 from zero, the bias added last.
+constexpr int S3_CT = 32;                          // couts per workgroup
+constexpr int S3_MAXDIM = 1 << 24;
+
+__global__ __launch_bounds__(256) void conv3x3_s2_c3_kernel(const float* __restrict__ x, int H, int W, int Ho, int Wo,
+                                                            const float* __restrict__ w, const float* __restrict__ bias, int Cout,
+                                                            int co_tiles, unsigned px_tiles, int relu, float* __restrict__ out) {
+  // block -> (image, pixel tile, cout tile); the cout tiles of a pixel tile are neighbours in launch order
+  unsigned b = blockIdx.x;
+  const int co0 = (int)(b % co_tiles) * S3_CT;
+  b /= co_tiles;
+  const unsigned pt = b % px_tiles;
+  const unsigned n = b / px_tiles;
+  const long long HoWo = (long long)Ho * Wo;
+  const long long e = (long long)pt * 256 + threadIdx.x;
+  if (e >= HoWo) return;
+  const int oy = (int)(e / Wo), ox = (int)(e - (long long)oy * Wo);
+  float v[27];
+  const float* xn = x + (size_t)n * 3 * H * W;
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+      for (int kx = 0; kx < 3; ++kx) {
+        const int iy = 2 * oy - 1 + ky, ix = 2 * ox - 1 + kx;
+        v[(c * 3 + ky) * 3 + kx] = (iy >= 0 && iy < H && ix >= 0 && ix < W) ? xn[((size_t)c * H + iy) * W + ix] : 0.f;
+      }
+  float* on = out + (size_t)n * Cout * HoWo + e;
+#pragma unroll 1
+  for (int j0 = 0; j0 < S3_CT && co0 + j0 < Cout; j0 += 4) {
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    const float* wj[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) wj[j] = w + (size_t)min(co0 + j0 + j, Cout - 1) * 27;     // (a cout past the last: not stored)
+#pragma unroll
+    for (int t = 0; t < 27; ++t)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[j] = __builtin_fmaf(v[t], wj[j][t], acc[j]);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int co = co0 + j0 + j;
+      if (co >= Cout) break;
+      float r = acc[j] + (bias ? bias[co] : 0.f);
+      if (relu) r = dm_relu(r);
+      on[(size_t)co * HoWo] = r;
+    }
+  }
+}
+
+// workgroups of a launch, or -1 when they do not fit a grid
+long long s3_blocks(int NB, int H, int W, int Cout) {
+  const long long px = ((long long)((H + 1) / 2) * ((W + 1) / 2) + 255) / 256;            // < 2^40
+  if (px > 0x7fffffffLL) return -1;
+  const long long per_image = px * dm_ceil_div(Cout, S3_CT);                               // < 2^51
+  if (per_image > 0x7fffffffLL) return -1;
+  const long long blocks = per_image * NB;
+  return blocks > 0x7fffffffLL ? -1 : blocks;
+}
+
 }  // namespace
+
+extern "C" int dm_conv3x3_s2_c3_supported(int NB, int C, int H, int W, int Cout) {
+  if (NB < 1 || C != 3 || H < 1 || W < 1 || Cout < 1 || H > S3_MAXDIM || W > S3_MAXDIM || Cout > S3_MAXDIM) return 0;
+  return s3_blocks(NB, H, W, Cout) > 0 ? 1 : 0;
+}
+
+extern "C" int dm_conv3x3_s2_c3_fwd(const float* x, int NB, int C, int H, int W, const float* w, const float* bias, int Cout,
+                                    int flags, float* out, dm_stream_t stream) {
+  if (!x || !w || !out) return DM_ERR_INVALID_ARG;
+  const int fc = dm_flags_check(flags, S7_RELU);
+  if (fc != DM_OK) return fc;
+  if (!dm_conv3x3_s2_c3_supported(NB, C, H, W, Cout)) return DM_ERR_UNSUPPORTED;
+  const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
+  const int co_tiles = dm_ceil_div(Cout, S3_CT);
+  const unsigned px_tiles = (unsigned)(((long long)Ho * Wo + 255) / 256);
+  DM_LAUNCH(conv3x3_s2_c3_kernel, dim3((unsigned)s3_blocks(NB, H, W, Cout)), dim3(256), 0, (hipStream_t)stream, x, H, W, Ho,
+            Wo, w, bias, Cout, co_tiles, px_tiles, (flags & S7_RELU) ? 1 : 0, out);
+  return dm_check_launch();
+}
 
 extern "C" int dm_conv7x7_s2_supported(int NB, int C, int H, int W, int Cout) {
   if (NB < 1 || C != S7_C || H < 1 || W < 1 || Cout < 1 || H > S7_MAXDIM || W > S7_MAXDIM || Cout > S7_MAXDIM) return 0;

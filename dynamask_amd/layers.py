@@ -294,3 +294,116 @@ class Bottleneck(nn.Module):
         if self.downsample is not None:
             return ops.conv2d([h, x], w3, b3, self.planes * self.expansion, 1, relu=True)
         return ops.conv2d(h, w3, b3, self.inplanes, 1, relu=True, out=x, accumulate=True)
+
+
+class _FoldedSlices(_FoldedConv):
+    """``pairs`` = G (3x3 convolution w -> w, its BatchNorm) of a Bottle2neck, each folded by itself (``fold_bn`` in
+    float64), stacked [G, w, w, 3, 3] with the biases [G * w], in ``ops.conv3x3_slices``'s layout."""
+
+    def __init__(self, pairs):
+        super().__init__(pairs, [pairs[0][0].out_channels])
+
+    def folded(self):
+        def make():
+            each = [fold_bn([p]) for p in self._pairs()]
+            return torch.stack([w for w, _ in each]).contiguous(), torch.cat([b for _, b in each]).contiguous()
+        return self._pk.get_multi('fold', self._tensors(), make)
+
+    def packed(self):
+        def make():
+            w, b = self.folded()
+            return ops.pack_conv_slices_weight(w), b
+        return self._pk.get_multi('pack3s', self._tensors(), make)
+
+
+class Bottle2neck(nn.Module):
+    """backbones/res2net.py:13-158 in eval mode (style 'pytorch').  Keys as the reference's: ``conv1.weight`` [w scales,
+    inplanes, 1, 1], ``bn1.*``, ``conv3.weight`` [4 planes, w scales, 1, 1], ``bn3.*``, with a downsample path
+    ``downsample.1.weight``, ``downsample.2.*`` (index 0 is the parameterless average pool), ``convs.{i}.weight``
+    [w, w, 3, 3] and ``bns.{i}.*`` for i < scales - 1; ``w = floor(planes * base_width / base_channels)``.  There is no
+    ``conv2`` and no ``bn2``: in their place ``scales - 1`` 3x3 convolutions run on the w-channel slices ``spx[i]`` of
+    conv1's output, and the last slice passes through.
+
+    ``stage_type='normal'`` (stride 1): convolution i >= 1 reads ``spx[i]`` + the output of convolution i - 1
+    (res2net.py:125), so they are ``scales - 1`` ``ops.conv3x3_slices`` launches in a row, each with G = 1, launch i >= 1
+    with the previous slice of the concatenation buffer as its addend; the copy of ``spx[scales - 1]`` rides with the
+    first as its tail.  ``stage_type='stage'`` (the first block of a layer, res2net.py:122-123): no hierarchical add, ONE
+    launch with G = scales - 1 at stride 1 or 2 whose tail copies the last slice (stride 1) or takes its
+    ``AvgPool2d(3, 2, 1)`` (stride 2, res2net.py:130-133).  No ``split`` and no ``cat`` is ever made: every launch reads
+    and writes channel slices of the two wide tensors.
+
+    Without ``downsample`` the block closes with conv3's ``accumulate | ReLU`` epilogue IN PLACE into ``x``, as
+    ``Bottleneck`` does: 2 + (scales - 1) launches in a normal block.  With it (``avg_down``: ``AvgPool2d(stride, stride,
+    ceil_mode=True, count_include_pad=False)`` -- ``ops.avgpool2x2_ceil`` at stride 2, the identity and no launch at
+    stride 1 --, then the 1x1 + BatchNorm) it closes with ONE two-source 1x1 of [concatenation buffer, pooled x] by
+    [W3' | Wd'] with ReLU into a NEW tensor: 3 launches at stride 1 and 4 at stride 2 in a stage block."""
+    expansion = 4
+
+    def __init__(self, inplanes, planes, downsample=False, stride=1, scales=4, base_width=26, base_channels=64,
+                 stage_type='normal'):
+        super().__init__()
+        if stage_type not in ('normal', 'stage'):
+            raise ValueError(f"Bottle2neck: stage_type={stage_type!r}; 'normal' or 'stage'")
+        if not isinstance(scales, int) or scales < 2:
+            raise NotImplementedError(f'Bottle2neck: scales={scales}; Res2Net degenerates to ResNet at scales = 1, 2 and more are built')
+        if not downsample and inplanes != planes * self.expansion:
+            raise NotImplementedError(f'Bottle2neck: inplanes={inplanes} != 4 * planes={planes} needs a downsample path')
+        if stride not in (1, 2) or (stride == 2 and (not downsample or stage_type != 'stage')):
+            raise NotImplementedError(f'Bottle2neck: stride={stride}, stage_type={stage_type!r}, downsample={downsample}; stride 1, or '
+                                      "stride 2 in a 'stage' block with a downsample path, are built")
+        width = planes * base_width // base_channels
+        if width < 1 or width * scales % 8 != 0:
+            raise NotImplementedError(
+                f'Bottle2neck: planes={planes}, base_width={base_width}, base_channels={base_channels}, scales={scales} give '
+                f'{width} channels per scale, {width * scales} in all; the 1x1 kernels beside the sliced 3x3 take widths '
+                'that are multiples of 8')
+        # (the map's size is the caller's: 8 x 8 stands for any -- only a launch of 2^31 workgroups depends on it)
+        tail = 2 if stride == 2 else 1
+        groups = scales - 1 if stage_type == 'stage' else 1
+        if not ops.conv3x3_slices_supported((1, width * scales, 8, 8), width, groups, stride, tail=tail):
+            raise NotImplementedError(f'Bottle2neck: dm_conv3x3_slices_supported refuses {groups} slice(s) of {width} channels at '
+                                      f'stride {stride} in a {width * scales}-channel tensor')
+        self.inplanes, self.planes, self.stride, self.scales = inplanes, planes, stride, scales
+        self.base_width, self.base_channels, self.stage_type, self.width = base_width, base_channels, stage_type, width
+        out = planes * self.expansion
+        self.conv1, self.bn1 = _conv_weight(width * scales, inplanes, 1), _BN(width * scales)
+        self.conv3, self.bn3 = _conv_weight(out, width * scales, 1), _BN(out)
+        if downsample:
+            self.downsample = nn.Sequential(nn.AvgPool2d(stride, stride, ceil_mode=True, count_include_pad=False),
+                                            _conv_weight(out, inplanes, 1), _BN(out))
+        else:
+            self.downsample = None
+        self.convs = nn.ModuleList([_conv_weight(width, width, 3) for _ in range(scales - 1)])
+        self.bns = nn.ModuleList([_BN(width) for _ in range(scales - 1)])
+        pairs = list(zip(self.convs, self.bns))
+        self._f1 = _FoldedConv([(self.conv1, self.bn1)], [inplanes])
+        self._f2 = [_FoldedSlices(pairs)] if stage_type == 'stage' else [_FoldedSlices([p]) for p in pairs]
+        if downsample:
+            self._f3 = _FoldedConv([(self.conv3, self.bn3), (self.downsample[1], self.downsample[2])], [width * scales, inplanes])
+        else:
+            self._f3 = _FoldedConv([(self.conv3, self.bn3)], [width * scales])
+
+    def forward(self, x):
+        """Without ``downsample``: ``x`` [N, inplanes, H, W] is overwritten with the block's output and returned.  With
+        it: a new [N, 4 planes, ceil(H / stride), ceil(W / stride)] tensor; ``x`` is not written."""
+        w, s, stride = self.width, self.scales, self.stride
+        w1, b1 = self._f1.packed()
+        h = ops.conv2d(x, w1, b1, w * s, 1, relu=True)
+        N, _, H, W = h.shape
+        cat = torch.empty((N, w * s, (H + stride - 1) // stride, (W + stride - 1) // stride), device=h.device, dtype=torch.float32)
+        last = (s - 1) * w
+        if self.stage_type == 'stage':
+            wq, bq = self._f2[0].packed()
+            ops.conv3x3_slices(h, wq, bq, w, s - 1, cat, stride=stride, relu=True, tail=2 if stride == 2 else 1,
+                               tail_x_ch0=last, tail_o_ch0=last)
+        else:
+            for i, f in enumerate(self._f2):
+                wq, bq = f.packed()
+                ops.conv3x3_slices(h, wq, bq, w, 1, cat, relu=True, x_ch0=i * w, o_ch0=i * w, addend=cat if i else None,
+                                   a_ch0=(i - 1) * w if i else 0, tail=0 if i else 1, tail_x_ch0=last, tail_o_ch0=last)
+        w3, b3 = self._f3.packed()
+        if self.downsample is None:
+            return ops.conv2d(cat, w3, b3, self.inplanes, 1, relu=True, out=x, accumulate=True)
+        if stride == 2:
+            x = ops.avgpool2x2_ceil(x)
+        return ops.conv2d([cat, x], w3, b3, self.planes * self.expansion, 1, relu=True)

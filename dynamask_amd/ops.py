@@ -3237,6 +3237,113 @@ def conv3x3_grouped(x, w_packed, bias, groups, stride=1, relu=False, out=None):
     return out
 
 
+# ------------------------------------------------------------------ Res2Net's kernels (dynamask_hip.h section K35)
+# Exact fp32 in every precision mode, like the stem.
+def pack_conv_slices_weight(w):
+    """Folded weights [G, w, w, 3, 3] of G independent w -> w 3x3 convolutions -> the operand of ``conv3x3_slices``:
+    [G][ceil(w / 8)][w][9][8], 8 neighbouring output channels of a slice side by side, zeros for the output channels
+    from w on (dm_conv3x3_slices_pack's layout, made by a permutation on the weight's own device)."""
+    if not isinstance(w, torch.Tensor) or w.dtype != torch.float32:
+        raise TypeError('pack_conv_slices_weight: a float32 tensor expected')
+    if w.dim() != 5 or w.shape[0] < 1 or w.shape[1] < 1 or tuple(w.shape[2:]) != (w.shape[1], 3, 3):
+        raise ValueError(f'pack_conv_slices_weight: a [G, w, w, 3, 3] weight expected, got {list(w.shape)}')
+    G, c = w.shape[:2]
+    T = (c + 7) // 8
+    wide = torch.zeros((G, T * 8, c, 9), device=w.device, dtype=torch.float32)
+    wide[:, :c] = w.reshape(G, c, c, 9)
+    return wide.view(G, T, 8, c, 9).permute(0, 1, 3, 4, 2).contiguous().view(-1)
+
+
+def conv3x3_slices_supported(x, w, G, stride, out_channels=None, tail=0):
+    """Does ``conv3x3_slices`` take this input (dm_conv3x3_slices_supported: any w >= 1, stride 1 or 2, any H, W)?  ``x``:
+    a tensor or its shape; ``out_channels``: the channels of ``out`` (default: as many as ``x`` has)."""
+    NB, Cx, H, W = x.shape if isinstance(x, torch.Tensor) else x
+    Co = Cx if out_channels is None else out_channels
+    return bool(lib().dm_conv3x3_slices_supported(int(NB), int(w), int(G), int(H), int(W), int(stride), int(Cx), int(Co), int(tail)))
+
+
+def conv3x3_slices(x, w_packed, bias, w, G, out, stride=1, relu=False, x_ch0=0, o_ch0=0, addend=None, a_ch0=0, tail=0,
+                   tail_x_ch0=0, tail_o_ch0=0):
+    """G independent ``Conv2d(w, w, 3, stride, padding=1) + bias (+ ReLU)`` in ONE launch (dm_conv3x3_slices_fwd): slice g
+    reads the channels [x_ch0 + g w, + w) of ``x`` [NB, Cx, H, W] -- plus, with ``addend`` [NB, Ca, H, W], its channels
+    [a_ch0 + g w, + w): one fp32 add before the products -- and writes the channels [o_ch0 + g w, + w) of ``out``
+    [NB, Co, ceil(H / stride), ceil(W / stride)], which is returned; nothing else of ``out`` is written.  ``tail``: 1 copies
+    the ``w`` channels at ``tail_x_ch0`` of ``x`` to ``tail_o_ch0`` of ``out`` (stride 1), 2 writes their
+    ``AvgPool2d(3, stride, padding=1)`` there (the divisor is always 9), in the same launch.  ``w_packed``:
+    ``pack_conv_slices_weight`` of the [G, w, w, 3, 3] weights; ``bias`` [G * w] or None."""
+    _chk(x, 'x')
+    _chk(w_packed, 'w_packed')
+    _chk(out, 'out')
+    if bias is not None:
+        _chk(bias, 'bias')
+    if addend is not None:
+        _chk(addend, 'addend')
+        assert addend.dim() == 4 and addend.shape[0] == x.shape[0] and tuple(addend.shape[2:]) == tuple(x.shape[2:]), \
+            'addend: another batch or map than x'
+    NB, Cx, H, W = x.shape
+    w, G, stride = int(w), int(G), int(stride)
+    if stride not in (1, 2):
+        raise NotImplementedError(f'conv3x3_slices: stride={stride}; 1 and 2 are built')
+    flags = (1 if relu else 0) | (16 if conv_layout(w_packed) == 'bf16x3' else 0)
+    if not flags & 16:
+        assert w_packed.numel() == lib().dm_conv3x3_slices_packed_floats(G, w), 'weights packed for another shape'
+        assert bias is None or bias.numel() == G * w
+    assert out.dim() == 4 and (out.shape[0], out.shape[2], out.shape[3]) == (NB, (H + stride - 1) // stride, (W + stride - 1) // stride), \
+        'out: another batch or map than the convolution gives'
+    check(lib().dm_conv3x3_slices_fwd(_p(x), Cx, int(x_ch0), _p(addend), addend.shape[1] if addend is not None else 0, int(a_ch0),
+                                      NB, w, G, H, W, stride, _p(w_packed), _p(bias), flags, _p(out), out.shape[1], int(o_ch0),
+                                      int(tail), int(tail_x_ch0), int(tail_o_ch0), _stream()), 'dm_conv3x3_slices_fwd')
+    return out
+
+
+def avgpool2x2_ceil(x, out=None):
+    """``F.avg_pool2d(x, 2, 2, ceil_mode=True, count_include_pad=False)`` (dm_avgpool2x2_ceil_fwd): an edge window of an
+    odd map divides by the number of elements it covers."""
+    _chk(x, 'x')
+    N, C, H, W = x.shape
+    if H < 1 or W < 1:
+        raise ValueError(f'avgpool2x2_ceil: an empty map {list(x.shape)}')
+    shape = (N, C, (H + 1) // 2, (W + 1) // 2)
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=torch.float32)
+    else:
+        _chk(out, 'out')
+        assert tuple(out.shape) == shape
+    check(lib().dm_avgpool2x2_ceil_fwd(_p(x), N * C, H, W, _p(out), _stream()), 'dm_avgpool2x2_ceil_fwd')
+    return out
+
+
+def conv3x3_s2_c3_supported(x, cout):
+    """Does ``conv3x3_s2_c3`` take this input (dm_conv3x3_s2_c3_supported: 3 channels, any H, W, any cout)?  ``x``: a
+    tensor or its shape."""
+    NB, C, H, W = x.shape if isinstance(x, torch.Tensor) else x
+    return bool(lib().dm_conv3x3_s2_c3_supported(int(NB), int(C), int(H), int(W), int(cout)))
+
+
+def conv3x3_s2_c3(x, weight, bias, relu=False, out=None):
+    """Conv2d(3, cout, 3, stride=2, padding=1)(x) + bias (+ ReLU) -> [NB, cout, ceil(H / 2), ceil(W / 2)]
+    (dm_conv3x3_s2_c3_fwd).  ``weight``: [cout, 3, 3, 3] as torch has it (no packing)."""
+    _chk(x, 'x')
+    _chk(weight, 'weight')
+    if bias is not None:
+        _chk(bias, 'bias')
+    NB, C, H, W = x.shape
+    if weight.dim() != 4 or tuple(weight.shape[1:]) != (C, 3, 3):
+        raise ValueError(f'conv3x3_s2_c3: a [cout, {C}, 3, 3] weight expected, got {list(weight.shape)}')
+    cout = weight.shape[0]
+    assert bias is None or bias.numel() == cout
+    flags = (1 if relu else 0) | (16 if conv_layout(weight) == 'bf16x3' else 0)
+    shape = (NB, cout, (H + 1) // 2, (W + 1) // 2)
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=torch.float32)
+    else:
+        _chk(out, 'out')
+        assert tuple(out.shape) == shape
+    check(lib().dm_conv3x3_s2_c3_fwd(_p(x), NB, C, H, W, _p(weight), _p(bias), cout, flags, _p(out), _stream()),
+          'dm_conv3x3_s2_c3_fwd')
+    return out
+
+
 # ------------------------------------------------------------------ image pre-processing (dynamask_hip.h section K33)
 PREPROCESS_MAX_IMAGES = _abi.load()[1]['DM_PREPROCESS_MAX_IMAGES']
 _RESIZE_TABLES = {}        # (n_src, n_dst) -> resize_axis_table's arrays

@@ -64,7 +64,9 @@ const char* dm_error_string(int code);
  * rescaled RoIAlign and global average pool (section K28); the DCN forward launcher's route, dm_deform_conv_plan
  * (section K8); the weight-gradient launcher's route, dm_conv2d_wgrad_plan, and that of
  * the other training-side launchers, dm_bwd_plan and dm_mask_pre_plan; RPN inference's selection, decode and merge
- * (section K30); the FPN neck's gathered addend and stride-2 subsample (section K31). */
+ * (section K30); the FPN neck's gathered addend and stride-2 subsample (section K31); ResNeXt's grouped
+ * 3x3 convolution (section K34); Res2Net's sliced 3x3 convolution, 2x2 ceil-mode average pool and deep-stem convolution
+ * (section K35). */
 #define DM_ABI_VERSION 29 /* the one definition: dm_abi_version(), dm_build_info() and _lib.ABI_VERSION read it */
 int dm_abi_version(void);
 /* "libdynamask_hip abi=N arch=gfx950 compiler=<clang version> flags=<the product-wide flags of dynamask_amd/build.py>"
@@ -1512,6 +1514,66 @@ int dm_conv3x3_grouped_pack(const float* w, int C, int groups, float* w_packed);
 int dm_conv3x3_grouped_supported(int NB, int C, int H, int W, int groups, int stride);
 int dm_conv3x3_grouped_fwd(const float* x, int NB, int C, int H, int W, const float* w_packed, const float* bias,
                            int groups, int stride, int flags, float* out, dm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * K35  (added to ABI 29) Res2Net backbone inference (mmdet/models/backbones/res2net.py; the deep stem and avg_down of
+ *      resnet.py:525-571, :623-631): the sliced 3x3 convolution that stands where conv2 stood in every Bottle2neck, the
+ *      2x2 ceil-mode average pool of the downsample path and the first convolution of the deep stem.  Everything else of
+ *      a Res2Net is the launches of K32 and dm_conv3x3_dil_fwd.  Exact fp32 in every precision mode, deterministic, no
+ *      atomics, no workspace.
+ *
+ * dm_conv3x3_slices_fwd: ONE launch of G independent act(Conv2d(w, w, 3, stride, padding = 1)(.) + bias).  x
+ * [NB, Cx, H, W], addend [NB, Ca, H, W] or NULL, out [NB, Co, Ho, Wo] with Ho = ceil(H / stride), Wo = ceil(W / stride);
+ * bias [G * w] or NULL.  Slice g = 0 .. G - 1 reads the channels [x_ch0 + g w, + w) of x -- with an addend the sum
+ * x + addend[a_ch0 + g w ..], ONE fp32 add per element before any product (torch's `sp + spx[i]`); the zero padding
+ * stays zero -- and writes the channels [o_ch0 + g w, + w) of out.  Nothing else of out is written; x and addend are
+ * only read.  A slice forms products with its own w input channels ONLY: K is not padded, neither with foreign channels
+ * nor with anything else, so a NaN or an Inf stays in its slice.  flags: bit 0 ReLU (NaN stays NaN); bit 3 is accepted
+ * and ignored; bit 4 (the bf16x3 layout): DM_ERR_UNSUPPORTED; any other bit: DM_ERR_INVALID_ARG.  The sum of an output is
+ * one fp32 fma chain from zero over its slice's input channels in order and, in a channel, ky = 0 .. 2, kx = 0 .. 2 (a
+ * tap in the padding multiplies a zero), the bias added last: it does not depend on NB, G, H, W or the output's
+ * position, so an image's bits do not depend on the other images of the call.  Maps of any width run (no row staging).
+ * tail: extra workgroups of the same grid.  0: none.  1: the w channels [tail_x_ch0, + w) of x are copied to
+ * [tail_o_ch0, + w) of out (stride 1 only).  2: AvgPool2d(3, stride, padding = 1) of them: THE DIVISOR IS ALWAYS 9 -- the
+ * elements of the window that lie inside the map are added row-major from zero and the sum is divided once by 9,
+ * whatever the window covers (torch's count_include_pad=True).  The addend does not enter the tail.
+ * w_packed: the folded weights [G, w, w, 3, 3] as [G][ceil(w / 8)][w][9][8] -- 8 neighbouring output channels of a slice
+ * side by side per (input channel, tap), zeros for the output channels from w on (their results are not stored) --
+ * dm_conv3x3_slices_packed_floats(G, w) = 72 G w ceil(w / 8) floats.  dm_conv3x3_slices_pack writes that layout from HOST
+ * memory to HOST memory (the Python side makes the same permutation on the device, ops.pack_conv_slices_weight).
+ * dm_conv3x3_slices_supported: 1 exactly when NB >= 1, 1 <= w, G, H, W <= 2^24, Cx, Co <= 2^24, stride is 1 or 2, tail is
+ * 0, 1 (at stride 1) or 2, Cx >= G w, Co >= (G + (tail ? 1 : 0)) w, and the launch has fewer than 2^31 workgroups:
+ * NB * (G * ceil(ceil(w / 8) / WCO) * ceil(Ho / TH) * ceil(Wo / 32) + (tail ? ceil(w Ho Wo / 256) : 0)) with WCO = 1,
+ * TH = 32 for w <= 8 and WCO = 4, TH = 8 above.  Two builds per stride (w <= 8, w > 8); nothing else decides.
+ * dm_conv3x3_slices_fwd returns DM_ERR_INVALID_ARG for a stride outside {1, 2}, DM_ERR_UNSUPPORTED for anything else
+ * dm_conv3x3_slices_supported refuses (NB == 0 apart) -- from the host arguments alone --, DM_ERR_INVALID_ARG for a
+ * slice range (or, with a tail, a tail range) that leaves Cx / Ca / Co or is negative, for a tail whose output channels
+ * meet a slice's, DM_OK without a launch for NB == 0 (pointers unread), DM_ERR_INVALID_ARG for a null x, w_packed or out.
+ *
+ * dm_avgpool2x2_ceil_fwd: AvgPool2d(2, 2, ceil_mode=True, count_include_pad=False), in [NC, H, W] -> out [NC,
+ * ceil(H / 2), ceil(W / 2)]: the elements of the window inside the map are added row-major and divided once by their
+ * number (4, 2 or 1).  dm_avgpool2x2_ceil_supported: 1 exactly when NC >= 0, H >= 1, W >= 1 and NC * H * W <= 2^40;
+ * anything else: DM_ERR_UNSUPPORTED.  NC == 0 enqueues nothing; a null in / out: DM_ERR_INVALID_ARG.
+ *
+ * dm_conv3x3_s2_c3_fwd: out = act(Conv2d(3, Cout, 3, stride = 2, padding = 1)(x) + bias), x [NB, 3, H, W], out
+ * [NB, Cout, ceil(H / 2), ceil(W / 2)]; w: the [Cout, 3, 3, 3] weight in torch's own layout, bias [Cout] or NULL.  An
+ * output reads its own 27 taps and nothing else (a tap in the padding is a zero operand); its sum is one fp32 fma chain
+ * from zero over c = 0 .. 2, ky = 0 .. 2, kx = 0 .. 2, the bias added last.  flags as above.
+ * dm_conv3x3_s2_c3_supported: 1 exactly when NB >= 1, C == 3, 1 <= H, W, Cout <= 2^24 and the launch has fewer than 2^31
+ * workgroups (NB * ceil(Ho Wo / 256) * ceil(Cout / 32)); dm_conv3x3_s2_c3_fwd returns DM_ERR_UNSUPPORTED for anything
+ * else, DM_ERR_INVALID_ARG for a null x, w or out.
+ * ------------------------------------------------------------------------------------------------------------------ */
+long long dm_conv3x3_slices_packed_floats(int G, int w);
+int dm_conv3x3_slices_pack(const float* w_folded, int G, int w, float* w_packed);
+int dm_conv3x3_slices_supported(int NB, int w, int G, int H, int W, int stride, int Cx, int Co, int tail);
+int dm_conv3x3_slices_fwd(const float* x, int Cx, int x_ch0, const float* addend, int Ca, int a_ch0, int NB, int w, int G,
+                          int H, int W, int stride, const float* w_packed, const float* bias, int flags, float* out, int Co,
+                          int o_ch0, int tail, int tail_x_ch0, int tail_o_ch0, dm_stream_t stream);
+int dm_avgpool2x2_ceil_supported(long long NC, int H, int W);
+int dm_avgpool2x2_ceil_fwd(const float* in, long long NC, int H, int W, float* out, dm_stream_t stream);
+int dm_conv3x3_s2_c3_supported(int NB, int C, int H, int W, int Cout);
+int dm_conv3x3_s2_c3_fwd(const float* x, int NB, int C, int H, int W, const float* w, const float* bias, int Cout,
+                         int flags, float* out, dm_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -216,19 +216,20 @@ def step_modules(args, report):
 
 
 # ------------------------------------------------------------------------------------------------ the detector
-def step_detector(args, report):
+def step_detector(args, report, fixture='g30_resnext_configs.json', entry='mask_rcnn_x101_32x4d'):
+    """``fixture`` / ``entry``: the detector config timed beside ResNet-101 (tools/res2net_infer_bench.py passes its own)."""
     import torch
     import bench
     from dynamask_amd import build_detector, detectors
     golden = os.path.join(ROOT, 'tests', 'golden')
     with open(os.path.join(golden, 'g29_detector_configs.json')) as f:
         r50 = json.load(f)['mask_rcnn']
-    with open(os.path.join(golden, 'g30_resnext_configs.json')) as f:
-        x101 = json.load(f)['mask_rcnn_x101_32x4d']
+    with open(os.path.join(golden, fixture)) as f:
+        x101 = json.load(f)[entry]
     r101 = copy.deepcopy(r50)
     r101['model']['backbone']['depth'] = 101
     p = detectors.parse_test_pipeline(r50['test_pipeline'])
-    for name, cfg in (('mask_rcnn_x101_32x4d', x101), ('mask_rcnn_r101', r101)):
+    for name, cfg in ((entry, x101), ('mask_rcnn_r101', r101)):
         cfg = copy.deepcopy(cfg)
         cfg['test_cfg']['rcnn']['score_thr'] = 0.0
         det = build_detector(cfg['model'], test_cfg=cfg['test_cfg'])
@@ -250,17 +251,21 @@ def step_detector(args, report):
         torch.cuda.empty_cache()
 
 
-def run_step(step, args):
+def run_step(step, args, step_fns):
     import torch
 
     def report(**r):
         print(json.dumps(r), flush=True)
 
     with torch.no_grad():
-        {'kernel': step_kernel, 'modules': step_modules, 'detector': step_detector}[step](args, report)
+        step_fns[step](args, report)
 
 
-def main():
+def main(step_fns=None, script=None):
+    """``step_fns`` {step: function} and ``script`` (the file a child runs): another tool's steps on this harness
+    (tools/res2net_infer_bench.py); the defaults are this tool's."""
+    step_fns = step_fns or {'kernel': step_kernel, 'modules': step_modules, 'detector': step_detector}
+    script = os.path.abspath(script or __file__)
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
@@ -271,12 +276,12 @@ def main():
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     if args.step is not None:
-        return run_step(args.step, args)
+        return run_step(args.step, args, step_fns)
     lines = []
     for step in args.steps.split(','):            # the parent never touches the GPU: one fresh child per step, each under its own limit
         if step not in STEPS:
             sys.exit(f'no step {step!r}: {STEPS}')
-        cmd = ['timeout', '-k', '10', str(args.step_timeout), sys.executable, os.path.abspath(__file__), '--step', step,
+        cmd = ['timeout', '-k', '10', str(args.step_timeout), sys.executable, script, '--step', step,
                '--reps', str(args.reps), '--warmup', str(args.warmup), '--rounds', str(args.rounds)]
         p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, cwd=ROOT)
         sys.stdout.write(p.stdout)
