@@ -7,7 +7,7 @@ Layout:
   layers.py             the parameter holders and weight caches every module below is made of (imports none of them)
   postprocess.py        host-side result code: NMS, mask paste, per-class result lists (imports none of them)
   backbones.py          ResNet, ResNeXt, Res2Net: the image -> the stages the neck reads
-  necks.py              FPN: the backbone's stages -> the maps the RPN and the RoI heads read
+  necks.py              FPN, FPN_CARAFE: the backbone's stages -> the maps the RPN and the RoI heads read
   dense_heads.py        RPNHead: the maps -> the proposals (simple_test_rpn, aug_test_rpn)
   roi_extractors.py, mask_heads.py, losses.py, roi_head.py
                         host-side mirror of the reference's plugin classes
@@ -24,13 +24,13 @@ __version__ = '0.1.0'
 from .precision import conv_precision, get_conv_precision, set_conv_precision  # noqa: E402,F401
 
 
-def __getattr__(name):          # NECKS, build_neck, FPN, BACKBONES, build_backbone, ResNet, ResNeXt, Res2Net, DETECTORS, build_detector: resolved on first use (necks.py imports the operator bindings)
+def __getattr__(name):          # NECKS, build_neck, FPN, FPN_CARAFE, BACKBONES, build_backbone, ResNet, ResNeXt, Res2Net, DETECTORS, build_detector: resolved on first use (necks.py imports the operator bindings)
     if name in ('NECKS', 'build_neck'):
-        from . import necks, registry  # noqa: F401  (necks registers FPN)
+        from . import necks, registry  # noqa: F401  (necks registers FPN and FPN_CARAFE)
         return getattr(registry, name)
-    if name == 'FPN':
+    if name in ('FPN', 'FPN_CARAFE'):
         from . import necks
-        return necks.FPN
+        return getattr(necks, name)
     if name in ('BACKBONES', 'build_backbone'):
         from . import backbones, registry  # noqa: F401  (backbones registers ResNet, ResNeXt and Res2Net)
         return getattr(registry, name)

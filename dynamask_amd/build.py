@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libdynamask_hip.so')
-SOURCES = ['api_misc.hip', 'roi_align.hip', 'conv_igemm.hip', 'deform_conv.hip', 'pointwise.hip', 'carafe.hip', 'mask_pre.hip', 'backward.hip', 'rle.hip', 'bbox.hip', 'fc_gemm.hip', 'bbox_train.hip', 'polygon.hip', 'conv_dilated.hip', 'point_refine.hip', 'conv_strided.hip', 'grid_head.hip', 'rpn.hip', 'stem.hip', 'preprocess.hip', 'conv_grouped.hip', 'conv_slices.hip']
+SOURCES = ['api_misc.hip', 'roi_align.hip', 'conv_igemm.hip', 'deform_conv.hip', 'pointwise.hip', 'carafe.hip', 'mask_pre.hip', 'backward.hip', 'rle.hip', 'bbox.hip', 'fc_gemm.hip', 'bbox_train.hip', 'polygon.hip', 'conv_dilated.hip', 'point_refine.hip', 'conv_strided.hip', 'grid_head.hip', 'rpn.hip', 'stem.hip', 'preprocess.hip', 'conv_grouped.hip', 'conv_slices.hip', 'carafe_map.hip']
 
 
 # Product-wide compile flags (beside -O3 -fPIC -std=c++17 --offload-arch=gfx950).

@@ -4,6 +4,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .registry import UPSAMPLE_LAYERS
 
 # ops.conv2d's 3x3 builds stage whole rows of the map (csrc/conv_igemm.hip: the plane of a 128-pixel tile), which stops
 # fitting their LDS at 169 pixels of width; the 3x3 kernel of csrc/conv_dilated.hip stages 8 x 16 blocks and takes any
@@ -114,6 +115,33 @@ class ConvModule(nn.Module):
 
     def forward(self, x):
         return self.conv.run(x, relu=self.with_activation)
+
+
+@UPSAMPLE_LAYERS.register_module(name='carafe')
+class CARAFEPack(nn.Module):
+    """mmcv CARAFEPack: keys channel_compressor.*, content_encoder.*.  It lives here because two sections build it:
+    FCNMaskHead's upsample (mask_heads.py) and FPN_CARAFE's top-down path (necks.py, on the whole-map kernel)."""
+
+    def __init__(self, channels, scale_factor, up_kernel=5, up_group=1, encoder_kernel=3, encoder_dilation=1,
+                 compressed_channels=64):
+        super().__init__()
+        if encoder_kernel != 3 or encoder_dilation != 1:
+            raise NotImplementedError('CARAFE encoder is 3x3, dilation 1 on the path')
+        self.channels, self.scale_factor, self.up_kernel, self.up_group = channels, scale_factor, up_kernel, up_group
+        self.channel_compressor = _Conv(channels, compressed_channels, 1)
+        self.content_encoder = _Conv(compressed_channels, up_kernel * up_kernel * up_group * scale_factor ** 2, 3)
+        self.init_weights()
+
+    def init_weights(self):
+        nn.init.xavier_uniform_(self.channel_compressor.weight)
+        nn.init.zeros_(self.channel_compressor.bias)
+        nn.init.normal_(self.content_encoder.weight, std=0.001)
+        nn.init.zeros_(self.content_encoder.bias)
+
+    def forward(self, x, relu=False):
+        comp = self.channel_compressor.run(x)
+        enc = self.content_encoder.run(comp)
+        return ops.carafe(x, enc, self.up_kernel, self.up_group, self.scale_factor)
 
 
 class _BN(nn.Module):

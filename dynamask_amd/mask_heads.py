@@ -20,7 +20,7 @@ import torch.nn as nn
 
 from . import losses  # noqa: F401  (registers CrossEntropyLoss, GridHead's default loss_grid)
 from . import ops
-from .layers import ConvModule, _Conv, _Packed
+from .layers import CARAFEPack, ConvModule, _Conv, _Packed  # noqa: F401  (layers registers CARAFEPack as the 'carafe' upsample layer)
 from .postprocess import _to_host, group_mask_scores, paste_segms, select_label_channel
 from .registry import HEADS, UPSAMPLE_LAYERS, build_loss
 from .train_path import FCNMaskHeadFn
@@ -460,32 +460,6 @@ class _Deconv(nn.Module):
         p = ops.deconv_precision_for(x.shape[2], x.shape[3])
         wp = self._pk.get('w', self.weight, lambda w: ops.pack_deconv_weight(w, precision=p), precision=p)
         return ops.deconv2x2(x, wp, self.bias.detach(), self.out_channels, relu=relu)
-
-
-@UPSAMPLE_LAYERS.register_module(name='carafe')
-class CARAFEPack(nn.Module):
-    """mmcv CARAFEPack: keys channel_compressor.*, content_encoder.*."""
-
-    def __init__(self, channels, scale_factor, up_kernel=5, up_group=1, encoder_kernel=3, encoder_dilation=1,
-                 compressed_channels=64):
-        super().__init__()
-        if encoder_kernel != 3 or encoder_dilation != 1:
-            raise NotImplementedError('CARAFE encoder is 3x3, dilation 1 on the path')
-        self.channels, self.scale_factor, self.up_kernel, self.up_group = channels, scale_factor, up_kernel, up_group
-        self.channel_compressor = _Conv(channels, compressed_channels, 1)
-        self.content_encoder = _Conv(compressed_channels, up_kernel * up_kernel * up_group * scale_factor ** 2, 3)
-        self.init_weights()
-
-    def init_weights(self):
-        nn.init.xavier_uniform_(self.channel_compressor.weight)
-        nn.init.zeros_(self.channel_compressor.bias)
-        nn.init.normal_(self.content_encoder.weight, std=0.001)
-        nn.init.zeros_(self.content_encoder.bias)
-
-    def forward(self, x, relu=False):
-        comp = self.channel_compressor.run(x)
-        enc = self.content_encoder.run(comp)
-        return ops.carafe(x, enc, self.up_kernel, self.up_group, self.scale_factor)
 
 
 @UPSAMPLE_LAYERS.register_module(name='bilinear')

@@ -1,5 +1,6 @@
-"""Necks behind the reference's NECKS registry, at inference: ``FPN`` (mmdet/models/necks/fpn.py) -- the maps the RPN and
-the RoI heads start from, made from the backbone's stages.
+"""Necks behind the reference's NECKS registry, at inference: ``FPN`` (mmdet/models/necks/fpn.py) and ``FPN_CARAFE``
+(mmdet/models/necks/fpn_carafe.py, at the end of this file) -- the maps the RPN and the RoI heads start from, made from
+the backbone's stages.
 
 ``forward`` walks the laterals from the top level down.  The top lateral is a plain 1x1 ``ops.conv2d``; every level below
 is ONE ``ops.conv2d_up_add`` (``dm_conv2d_up_add_fwd``): the 1x1 lateral convolution whose epilogue adds the merged lateral
@@ -11,7 +12,11 @@ width alone decides, so a map's kernel does not depend on the batch); extra leve
 changed feature reorders the proposals made from it.  The host never waits.
 
 ``DM_FPN_FUSED=0`` (or clearing ``FPN_FUSED``) runs the merge composed: the lateral ``ops.conv2d`` and then
-``lat += F.interpolate(...)`` in torch, the max-pool by slicing.  The same bits."""
+``lat += F.interpolate(...)`` in torch, the max-pool by slicing.  The same bits.
+
+``FPN_CARAFE`` builds every lateral first (the extra levels' are stride-2 3x3 convolutions and take part in the merge) and
+merges top-down with CARAFE: per level the compressor 1x1, the encoder 3x3 and ONE ``ops.carafe_map``
+(``dm_carafe_map_fwd``), the reassembly at scale 2 whose epilogue adds the cropped result to the lateral below in place."""
 import os
 
 import torch
@@ -19,7 +24,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .layers import CONV2D_3X3_MAX_WIDTH, _exact_conv
+from .layers import CONV2D_3X3_MAX_WIDTH, CARAFEPack, _exact_conv
 from .registry import NECKS
 
 
@@ -213,3 +218,170 @@ class FPN(nn.Module):
                         src = torch.relu(outs[-1]) if self.relu_before_extra_convs else outs[-1]
                     outs.append(ops.conv3x3_s2(src, c.packed([c.in_channels]), c.bias.detach(), c.out_channels))
         return tuple(outs)
+
+
+# ---------------------------------------------------------------------------------------------------------- FPN_CARAFE
+def _env_carafe_fused():
+    return os.environ.get('DM_FPN_CARAFE_FUSED', '1') != '0'
+
+
+# DM_FPN_CARAFE_FUSED=0 (or clearing this flag): the top-down merge composed -- ``ops.carafe_map`` without an addend at the
+# full 2H x 2W, then ``lat + up[:, :, :h, :w]`` in torch.  The same bits.
+FPN_CARAFE_FUSED = [_env_carafe_fused()]
+
+_CARAFE_CFG_KEYS = ('type', 'up_kernel', 'up_group', 'encoder_kernel', 'encoder_dilation', 'compressed_channels')
+
+
+class _CarafeUp(CARAFEPack):
+    """``CARAFEPack`` at scale 2 on a whole map: the same keys and initialisation; the two convolutions are exact fp32 in
+    every precision mode and the reassembly is the caller's ``ops.carafe_map`` (``forward`` stays the mask head's path)."""
+
+    def __init__(self, channels, up_kernel, up_group, compressed_channels):
+        super().__init__(channels, 2, up_kernel=up_kernel, up_group=up_group, compressed_channels=compressed_channels)
+        self.channel_compressor.exact = self.content_encoder.exact = True
+
+    def encode(self, x):
+        """The raw content-encoder output [NB, up_group * K * K * 4, H, W] (before pixel_shuffle and softmax)."""
+        comp = self.channel_compressor.run(x)
+        c = self.content_encoder
+        if comp.shape[3] > CONV2D_3X3_MAX_WIDTH:        # (as FPN._conv3x3: the width alone decides)
+            return ops.conv3x3_dil(comp, c.packed([c.in_channels]), c.bias.detach(), c.out_channels, 1)
+        return c.run(comp)
+
+
+@NECKS.register_module()
+class FPN_CARAFE(nn.Module):
+    """``FPN_CARAFE`` -- fpn_carafe.py:8-267, inference, with the CARAFE upsample.  ``state_dict`` keys, in the reference's
+    order: ``lateral_convs.{i}.conv.{weight,bias}`` (the extra levels' laterals are 3x3 stride-2 convolutions, the first
+    on ``in_channels[-1]``), ``fpn_convs.{i}.conv.*``, ``upsample_modules.{i}.channel_compressor.*`` /
+    ``.content_encoder.*`` (module i upsamples lateral i + 1).
+
+    ``forward``: the laterals are 1x1 ``ops.conv2d`` launches, the extra levels ``ops.conv3x3_s2``.  Top-down, per level:
+    the compressor 1x1, the encoder 3x3 and ONE ``ops.carafe_map(lat[i], enc, addend=lat[i - 1], out=lat[i - 1])`` --
+    ``tensor_add(laterals[i - 1], upsample(laterals[i]))`` with ``slice_as`` (fpn_carafe.py:211-259) in the reassembly's
+    epilogue: no upsampled map, no second pass over the lateral.  The outputs are the 3x3 level convolutions, as in
+    ``FPN``.  Every convolution is exact fp32 in every precision mode; the host never waits; the inputs are not written;
+    an image's bits do not depend on the batch.  22 launches for the five levels of configs/carafe.
+
+    Not built (NotImplementedError naming the argument): ``norm_cfg``, ``act_cfg``, ``order=('act', 'conv', 'norm')``,
+    every ``upsample_cfg['type']`` but 'carafe', an encoder that is not 3x3 at dilation 1, ``out_channels`` or
+    ``compressed_channels`` that is no multiple of 8, training."""
+
+    def __init__(self, in_channels, out_channels, num_outs, start_level=0, end_level=-1, norm_cfg=None, act_cfg=None,
+                 order=('conv', 'norm', 'act'),
+                 upsample_cfg=dict(type='carafe', up_kernel=5, up_group=1, encoder_kernel=3, encoder_dilation=1)):
+        super().__init__()
+        assert isinstance(in_channels, list)
+        if norm_cfg is not None:
+            raise NotImplementedError(f'FPN_CARAFE: norm_cfg={norm_cfg} is not built')
+        if act_cfg is not None:
+            raise NotImplementedError(f'FPN_CARAFE: act_cfg={act_cfg} is not built (None in configs/carafe)')
+        order = tuple(order)
+        assert order in [('conv', 'norm', 'act'), ('act', 'conv', 'norm')]
+        if order != ('conv', 'norm', 'act'):
+            raise NotImplementedError(f'FPN_CARAFE: order={order} is not built')
+        upsample_cfg = dict(upsample_cfg)
+        self.upsample = upsample_cfg.get('type')
+        assert self.upsample in ['nearest', 'bilinear', 'deconv', 'pixel_shuffle', 'carafe', None]
+        if self.upsample != 'carafe':
+            raise NotImplementedError(f"FPN_CARAFE: upsample_cfg type={self.upsample!r} is not built; 'carafe' only")
+        if set(upsample_cfg) - set(_CARAFE_CFG_KEYS):
+            raise NotImplementedError(f'FPN_CARAFE: upsample_cfg keys {sorted(set(upsample_cfg) - set(_CARAFE_CFG_KEYS))} '
+                                      'are not built')
+        up_kernel, up_group = upsample_cfg.get('up_kernel', 5), upsample_cfg.get('up_group', 1)
+        compressed = upsample_cfg.get('compressed_channels', 64)
+        if upsample_cfg.get('encoder_kernel', 3) != 3:
+            raise NotImplementedError(f"FPN_CARAFE: encoder_kernel={upsample_cfg['encoder_kernel']} is not built; 3 only")
+        if upsample_cfg.get('encoder_dilation', 1) != 1:
+            raise NotImplementedError(f"FPN_CARAFE: encoder_dilation={upsample_cfg['encoder_dilation']} is not built; 1 only")
+        if up_kernel not in (3, 5):
+            raise NotImplementedError(f'FPN_CARAFE: up_kernel={up_kernel} is not built; 3 and 5 are')
+        if out_channels % 8 != 0:
+            raise NotImplementedError(f'FPN_CARAFE: out_channels={out_channels} is not a multiple of 8 (the any-width and '
+                                      'the stride-2 3x3 kernels walk the input channels in chunks of 8)')
+        if compressed % 8 != 0:
+            raise NotImplementedError(f'FPN_CARAFE: compressed_channels={compressed} is not a multiple of 8 (the encoder\'s '
+                                      '3x3 kernels walk the input channels in chunks of 8)')
+        if up_group < 1 or out_channels % up_group != 0 or (out_channels // up_group) % 4 != 0:
+            raise NotImplementedError(f'FPN_CARAFE: up_group={up_group} does not divide out_channels={out_channels} into '
+                                      'groups of a multiple of 4 channels (the reassembly walks channel quads)')
+        self.in_channels = in_channels
+        self.out_channels = out_channels
+        self.num_ins = len(in_channels)
+        self.num_outs = num_outs
+        self.norm_cfg, self.act_cfg, self.order = norm_cfg, act_cfg, order
+        self.with_bias = True
+        self.upsample_cfg = upsample_cfg
+        self.up_kernel, self.up_group = up_kernel, up_group
+        if end_level == -1:
+            self.backbone_end_level = self.num_ins
+            assert num_outs >= self.num_ins - start_level
+        else:
+            # if end_level < inputs, no extra level is allowed (fpn_carafe.py:77-80)
+            self.backbone_end_level = end_level
+            assert end_level <= len(in_channels)
+            assert num_outs == end_level - start_level
+        assert 0 <= start_level < self.backbone_end_level
+        self.start_level = start_level
+        self.end_level = end_level
+
+        self.lateral_convs = nn.ModuleList()
+        self.fpn_convs = nn.ModuleList()
+        self.upsample_modules = nn.ModuleList()
+        for i in range(self.start_level, self.backbone_end_level):
+            if i != self.backbone_end_level - 1:
+                self.upsample_modules.append(_CarafeUp(out_channels, up_kernel, up_group, compressed))
+            self.lateral_convs.append(_NeckConv(in_channels[i], out_channels, 1))
+            self.fpn_convs.append(_NeckConv(out_channels, out_channels, 3))
+        # extra levels (fpn_carafe.py:139-199): a 3x3 stride-2 lateral, the first on the last backbone stage
+        for i in range(num_outs - self.backbone_end_level + self.start_level):
+            cin = in_channels[self.backbone_end_level - 1] if i == 0 else out_channels
+            self.upsample_modules.append(_CarafeUp(out_channels, up_kernel, up_group, compressed))
+            self.fpn_convs.append(_NeckConv(out_channels, out_channels, 3))
+            self.lateral_convs.append(_NeckConv(cin, out_channels, 3, stride=2))
+
+    def init_weights(self):
+        """fpn_carafe.py:202-209: xavier uniform weights and zero biases, then CARAFEPack's own rule for its two."""
+        for m in list(self.lateral_convs) + list(self.fpn_convs):
+            nn.init.xavier_uniform_(m.conv.weight, gain=1)
+            nn.init.constant_(m.conv.bias, 0)
+        for m in self.upsample_modules:
+            m.init_weights()
+
+    _conv3x3 = FPN._conv3x3
+
+    def forward(self, inputs):
+        """``inputs``: the backbone's stages, [B, in_channels[i], H_i, W_i]; returns the tuple of ``num_outs`` maps."""
+        assert len(inputs) == len(self.in_channels)
+        if torch.is_grad_enabled() and (any(x.requires_grad for x in inputs) or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError('FPN_CARAFE: training is not built; run inference under torch.no_grad()')
+        for i, x in enumerate(inputs):
+            if x.dim() != 4 or x.shape[1] != self.in_channels[i]:
+                raise ValueError(f'FPN_CARAFE: input {i}: [B, {self.in_channels[i]}, H, W] expected, got {tuple(x.shape)}')
+        fused = FPN_CARAFE_FUSED[0]
+        used = self.backbone_end_level - self.start_level
+        laterals = []
+        for i, m in enumerate(self.lateral_convs):
+            # fpn_carafe.py:245-250: the first extra lateral reads the last input, the later ones the lateral before them
+            src = inputs[min(i + self.start_level, len(inputs) - 1)].contiguous() if i <= used else laterals[-1]
+            c = m.conv
+            if m.stride == 1:
+                laterals.append(c.run(src))
+                continue
+            if src.shape[1] % 8 != 0 or not ops.conv3x3_s2_supported(src, c.out_channels):
+                raise NotImplementedError(f'FPN_CARAFE: the stride-2 3x3 kernel does not take the extra level\'s input '
+                                          f'{list(src.shape)} (lateral_convs.{i})')
+            laterals.append(ops.conv3x3_s2(src, c.packed([c.in_channels]), c.bias.detach(), c.out_channels))
+        for i in range(len(laterals) - 1, 0, -1):
+            up, src, dst = self.upsample_modules[i - 1], laterals[i], laterals[i - 1]
+            size = tuple(dst.shape[2:])
+            if not ops.carafe_map_supported(src, self.up_kernel, self.up_group, size):
+                raise NotImplementedError(f'FPN_CARAFE: level {i} {list(src.shape)} does not upsample into the lateral below '
+                                          f'{list(dst.shape)} (2H - 1 <= OH <= 2H, 2W - 1 <= OW <= 2W)')
+            enc = up.encode(src)
+            if fused:
+                ops.carafe_map(src, enc, self.up_kernel, self.up_group, addend=dst, out=dst)
+            else:
+                full = ops.carafe_map(src, enc, self.up_kernel, self.up_group)
+                laterals[i - 1] = dst + full[:, :, :size[0], :size[1]]
+        return tuple(self._conv3x3(m, lat) for m, lat in zip(self.fpn_convs, laterals))

@@ -1560,6 +1560,56 @@ def carafe(x, enc, up_kernel=5, group=1, scale=2):
     return out
 
 
+def _carafe_map_size(H, W, out_size):
+    if out_size is None:
+        return 2 * H, 2 * W
+    OH, OW = out_size
+    return int(OH), int(OW)
+
+
+def carafe_map_supported(x_or_shape, up_kernel, group, out_size=None):
+    """dm_carafe_map_supported: does ``carafe_map`` take this map (a tensor or its shape) at this ``out_size`` (default
+    2H x 2W)?  Host only."""
+    NB, C, H, W = x_or_shape.shape if isinstance(x_or_shape, torch.Tensor) else x_or_shape
+    OH, OW = _carafe_map_size(int(H), int(W), out_size)
+    return bool(lib().dm_carafe_map_supported(int(NB), int(C), int(H), int(W), int(up_kernel), int(group), OH, OW))
+
+
+def carafe_map(x, enc, up_kernel=5, group=1, addend=None, out=None, out_size=None, chan_split=0):
+    """``addend + carafe(x, softmax_taps(pixel_shuffle(enc)))[:, :, :OH, :OW]`` at scale 2, one launch (dm_carafe_map_fwd):
+    CARAFE on a whole map with FPN_CARAFE's cropped add.  ``x`` [NB, C, H, W]; ``enc`` [NB, group * K * K * 4, H, W], the
+    raw content-encoder output; ``out_size`` (OH, OW) with 2H - 1 <= OH <= 2H and 2W - 1 <= OW <= 2W (default: that of
+    ``out``, else of ``addend``, else 2H x 2W); ``addend`` [NB, C, OH, OW] or None; ``out`` may be ``addend`` itself.
+    ``chan_split``: workgroups per pixel tile over the group's channels (0: the library's choice; the bits do not depend
+    on it)."""
+    _chk(x, 'x')
+    _chk(enc, 'enc')
+    if x.dim() != 4 or enc.dim() != 4:
+        raise ValueError(f'carafe_map: x and enc are 4-D, got {list(x.shape)} and {list(enc.shape)}')
+    NB, C, H, W = x.shape
+    up_kernel, group = int(up_kernel), int(group)
+    if tuple(enc.shape) != (NB, up_kernel * up_kernel * group * 4, H, W):
+        raise ValueError(f'enc: [{NB}, {up_kernel * up_kernel * group * 4}, {H}, {W}] expected, got {list(enc.shape)}')
+    if out_size is None:
+        ref = out if out is not None else addend
+        out_size = tuple(ref.shape[2:]) if isinstance(ref, torch.Tensor) and ref.dim() == 4 else None
+    OH, OW = _carafe_map_size(H, W, out_size)
+    shape = (NB, C, OH, OW)
+    if addend is not None:
+        _chk(addend, 'addend')
+        if tuple(addend.shape) != shape:
+            raise ValueError(f'addend: {list(shape)} expected, got {list(addend.shape)}')
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=torch.float32)
+    else:
+        _chk(out, 'out')
+        if tuple(out.shape) != shape:
+            raise ValueError(f'out: {list(shape)} expected, got {list(out.shape)}')
+    check(lib().dm_carafe_map_fwd(_p(x), _p(enc), NB, C, H, W, up_kernel, group, _p(addend), OH, OW, int(chan_split), _p(out),
+                                  _stream()), 'dm_carafe_map_fwd')
+    return out
+
+
 # ------------------------------------------------------------ bandwidth kernels
 def point_sample(feat, rois, output_size, spatial_scale):
     _chk(feat, 'feat')

@@ -1575,6 +1575,34 @@ int dm_conv3x3_s2_c3_supported(int NB, int C, int H, int W, int Cout);
 int dm_conv3x3_s2_c3_fwd(const float* x, int NB, int C, int H, int W, const float* w, const float* bias, int Cout,
                          int flags, float* out, dm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * K36  CARAFE on whole feature maps, merged into the lateral below (csrc/carafe_map.hip; added entry points, the ABI
+ *      number stays).  replaces: FPN_CARAFE's top-down step (mmdet/models/necks/fpn_carafe.py:211-259):
+ *      tensor_add(laterals[i - 1], CARAFEPack.kernel_normalizer + feature_reassemble (laterals[i])) with slice_as.
+ *
+ * dm_carafe_map_fwd: out = addend + carafe(x, softmax_taps(pixel_shuffle(enc)))[:, :, :OH, :OW] at scale 2.  x
+ * [NB, C, H, W]; enc [NB, group * K * K * 4, H, W], the RAW content-encoder output in dm_carafe_fwd's layout (channel
+ * ((g K K + tap) * 4 + dy * 2 + dx)); out and addend [NB, C, OH, OW] with 2H - 1 <= OH <= 2H and 2W - 1 <= OW <= 2W.
+ * addend may be NULL (nothing is added) and out may be the addend's own memory (every element is read by the thread
+ * that writes it); x and enc are only read and may not overlap out.  The upsampled map is never stored, the cropped row
+ * and column are neither loaded nor stored.  An output's value: the maximum of its K K raw taps in tap order (fmaxf),
+ * expf(v - max) per tap and their sum in tap order, each weight times 1 / sum, ONE fmaf chain over the taps in order
+ * i * K + j from zero, then ONE fp32 add of the addend.  A tap outside the image is a zero operand of a zero-padded tile
+ * (never another pixel's value times 0): a NaN or an Inf of x reaches exactly the outputs whose window holds its pixel,
+ * in its channel; a NaN of enc reaches its one output pixel in every channel of its group.  The bits do not depend on
+ * NB, on the position in the grid or on chan_split.  Deterministic, no atomics, no workspace.
+ * chan_split: the workgroups a group's channel quads (C / group / 4) are dealt over per pixel tile; 0: the launcher
+ * chooses (whole chunks of 2 quads per workgroup, the split that fills the compute units in the fewest rounds).
+ * dm_carafe_map_supported: a pure host function; 1 exactly when NB >= 0, C, H, W, group >= 1, up_kernel is 3 or 5,
+ * C % group == 0, (C / group) % 4 == 0, OH and OW are in the ranges above and x, enc and out have fewer than 2^31
+ * elements each.  dm_carafe_map_fwd returns DM_ERR_INVALID_ARG for a negative NB or chan_split, a non-positive C, H, W or
+ * group and a chan_split above C / group / 4; DM_ERR_UNSUPPORTED for anything else dm_carafe_map_supported refuses; then
+ * DM_OK without a launch for NB == 0 (pointers unread); DM_ERR_INVALID_ARG for a null x, enc or out.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int dm_carafe_map_supported(int NB, int C, int H, int W, int up_kernel, int group, int OH, int OW);
+int dm_carafe_map_fwd(const float* x, const float* enc, int NB, int C, int H, int W, int up_kernel, int group,
+                      const float* addend, int OH, int OW, int chan_split, float* out, dm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
