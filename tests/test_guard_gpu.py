@@ -4,136 +4,13 @@ patterns.  After each pass the bands must be bit-for-bit intact (a kernel stored
 start, of a buffer otherwise) and every result finite (float bands are NaN: an out-of-range READ that reaches a result
 poisons it).  Shapes are the odd ones of tools/stress.py: RoI counts 1 / 7 / 129 / 513 on 333x500 ... 2048x1024
 pyramids -- magic-number divisions, LDS band staging and the "last round" second launches all see ragged edges."""
-import contextlib
-
 import pytest
 import torch
 
 import golden_inputs as gi
+from guard_arena import Arena, guarded, _put, _finite  # noqa: F401  (the arena lives in guard_arena.py, shared with the surface passes)
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 256          # elements on each side (1 KB of fp32): keeps the interior 256-byte aligned
-_PATTERN = {1: 0x5A, 2: 0x5A5A, 4: 0x7FC0DEAD, 8: 0x7FF8DEAD7FC0DEAD}      # 4 / 8 bytes: NaN bit patterns
-
-
-class Arena:
-    """Guarded allocation: replaces torch's tensor factories for CUDA tensors while active."""
-
-    def __init__(self):
-        self.blocks = []          # (parent int-view, n interior elements, shape, dtype)
-        self.count = 0
-
-    def _int_dtype(self, dtype):
-        return {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[torch.empty((), dtype=dtype).element_size()]
-
-    def alloc(self, shape, dtype, device, fill=None):
-        shape = tuple(int(s) for s in shape)
-        n = 1
-        for s in shape:
-            n *= s
-        idt = self._int_dtype(dtype)
-        esz = torch.empty((), dtype=dtype).element_size()
-        pat = _PATTERN[esz]
-        if esz == 1:
-            raw = self._empty((n + 2 * GUARD,), dtype=idt, device=device)
-            raw.fill_(pat)
-        else:
-            raw = self._full((n + 2 * GUARD,), pat if pat < 2 ** 63 else pat - 2 ** 64, dtype=torch.int64 if esz == 8 else idt,
-                             device=device)
-        inner = raw[GUARD:GUARD + n].view(dtype).view(shape)
-        if fill is not None:
-            inner.fill_(fill)
-        self.blocks.append((raw, n, pat))
-        self.count += 1
-        return inner
-
-    def check(self):
-        torch.cuda.synchronize()
-        bad = []
-        for k, (raw, n, pat) in enumerate(self.blocks):
-            p = pat if pat < 2 ** 63 else pat - 2 ** 64
-            lo, hi = raw[:GUARD], raw[GUARD + n:]
-            if not bool((lo == p).all()) or not bool((hi == p).all()):
-                bad.append((k, n, int((lo != p).sum()), int((hi != p).sum())))
-        assert not bad, f'guard bands overwritten (block, elements, cells before, cells after): {bad[:8]}'
-        return len(self.blocks)
-
-
-@contextlib.contextmanager
-def guarded(monkeypatch):
-    arena = Arena()
-    o_empty, o_zeros, o_full, o_ones = torch.empty, torch.zeros, torch.full, torch.ones
-    o_empty_like, o_zeros_like = torch.empty_like, torch.zeros_like
-    arena._empty, arena._full = o_empty, o_full
-
-    def _is_cuda(device):
-        return device is not None and torch.device(device).type == 'cuda'
-
-    def _shape(args):
-        return tuple(args[0]) if len(args) == 1 and isinstance(args[0], (tuple, list, torch.Size)) else tuple(args)
-
-    def mk(orig, fill):
-        def f(*args, dtype=None, device=None, **kw):
-            if not _is_cuda(device) or kw.get('out') is not None or kw.get('memory_format') is not None:
-                return orig(*args, dtype=dtype, device=device, **kw)
-            t = arena.alloc(_shape(args), dtype or torch.float32, device, fill)
-            return t.requires_grad_(True) if kw.get('requires_grad') else t
-        return f
-
-    def full(size, fill_value, *, dtype=None, device=None, **kw):
-        if not _is_cuda(device):
-            return o_full(size, fill_value, dtype=dtype, device=device, **kw)
-        if dtype is None:
-            dtype = torch.float32 if isinstance(fill_value, float) else (torch.bool if isinstance(fill_value, bool) else torch.int64)
-        return arena.alloc(size, dtype, device, fill_value)
-
-    def like(fill):
-        def f(t, *, dtype=None, device=None, **kw):
-            device = device or t.device
-            if not _is_cuda(device) or not t.is_contiguous():
-                return (o_empty_like if fill is None else o_zeros_like)(t, dtype=dtype, device=device, **kw)
-            return arena.alloc(t.shape, dtype or t.dtype, device, fill)
-        return f
-
-    def new(fill):
-        def f(self, *args, dtype=None, device=None, **kw):
-            device = device or self.device
-            if not _is_cuda(device):
-                return (o_empty if fill is None else o_zeros)(*args, dtype=dtype or self.dtype, device=device)
-            return arena.alloc(_shape(args), dtype or self.dtype, device, fill)
-        return f
-
-    def new_full(self, size, fill_value, *, dtype=None, device=None, **kw):
-        device = device or self.device
-        if not _is_cuda(device):
-            return o_full(size, fill_value, dtype=dtype or self.dtype, device=device)
-        return arena.alloc(size, dtype or self.dtype, device, fill_value)
-
-    monkeypatch.setattr(torch, 'empty', mk(o_empty, None))
-    monkeypatch.setattr(torch, 'zeros', mk(o_zeros, 0))
-    monkeypatch.setattr(torch, 'ones', mk(o_ones, 1))
-    monkeypatch.setattr(torch, 'full', full)
-    monkeypatch.setattr(torch, 'empty_like', like(None))
-    monkeypatch.setattr(torch, 'zeros_like', like(0))
-    monkeypatch.setattr(torch.Tensor, 'new_empty', new(None))
-    monkeypatch.setattr(torch.Tensor, 'new_zeros', new(0))
-    monkeypatch.setattr(torch.Tensor, 'new_full', new_full)
-    try:
-        yield arena
-    finally:
-        monkeypatch.undo()
-
-
-def _put(arena, t):
-    """Copy a host tensor into guarded device storage."""
-    g = arena.alloc(t.shape, t.dtype, torch.device('cuda'))
-    g.copy_(t)
-    return g
-
-
-def _finite(ts):
-    return all(bool(torch.isfinite(t).all()) for t in ts if t.is_floating_point())
 
 
 def _full_head():
@@ -159,6 +36,42 @@ def test_arena_catches_a_store_past_the_end(monkeypatch):
         t.view(-1).as_strided((16,), (1,))[15] = 1.0          # element 15 of a 15-element buffer
         with pytest.raises(AssertionError, match='guard bands overwritten'):
             arena.check()
+
+
+def test_launch_log_reports_a_store_outside_the_arena(monkeypatch):
+    """The net itself: an ``out=`` from the un-patched factory is a store pointer outside every arena block."""
+    from guard_arena import LaunchLog
+    from dynamask_amd import hazard, ops
+    name = 'dm_maxpool3x3_s2_fwd'
+    arg = hazard.parse_header()[name].index('out')
+    with guarded(monkeypatch) as arena, LaunchLog(arena) as log:
+        x = _put(arena, torch.randn(1, 2, 5, 7, generator=torch.Generator().manual_seed(1)))
+        inside = ops.maxpool3x3_s2(x)
+        assert log.launches == {name: 1} and log.reached_guarded() == {name} and log.unguarded_stores() == set()
+        assert log.stores == {(name, arg): [1, 0]} and log.reads == {(name, 0): [1, 0]}
+        out = arena._empty((1, 2, 3, 4), dtype=torch.float32, device='cuda')           # torch.empty as it was
+        assert ops.maxpool3x3_s2(x, out=out) is out
+        assert log.launches == {name: 2} and log.guarded_launches == {name: 1}
+        assert log.unguarded_stores() == {(name, arg)} and log.stores == {(name, arg): [1, 1]}
+        assert torch.equal(out, inside)
+        arena.check()
+    from dynamask_amd import _lib
+    assert _lib.lib() is not None and not hasattr(_lib.lib(), '_log'), 'the library proxy was not taken off again'
+
+
+def test_arena_poisons_a_read_that_reaches_into_a_band(monkeypatch):
+    """The net itself: a read one element behind the end, or in front of the start, of a buffer makes the result
+    non-finite (float bands are NaN).  A torch-level ``as_strided`` inside the arena's own raw allocation."""
+    with guarded(monkeypatch) as arena:
+        t = torch.ones((5, 3), device='cuda')
+        assert _finite([t.sum(), t])
+        behind = t.as_strided((16,), (1,), t.storage_offset())               # elements 0 .. 15 of a 15-element buffer
+        before = t.as_strided((15,), (1,), t.storage_offset() - 1)           # element -1 .. 13
+        assert not _finite([behind.sum()]) and not _finite([before.sum()])
+        assert _finite([t.as_strided((15,), (1,), t.storage_offset()).sum()])
+        ints = torch.zeros((4,), dtype=torch.int32, device='cuda')            # integer bands: the NaN pattern read as float
+        assert not _finite([ints.as_strided((5,), (1,), ints.storage_offset()).view(torch.float32)])
+        arena.check()                                                        # reading breaks no band
 
 
 @pytest.mark.parametrize('H,W', [(333, 500), (608, 1024), (800, 1333), (1024, 2048)])
