@@ -8,10 +8,10 @@ Layout:
   postprocess.py        host-side result code: NMS, mask paste, per-class result lists (imports none of them)
   backbones.py          ResNet, ResNeXt, Res2Net: the image -> the stages the neck reads
   necks.py              FPN, FPN_CARAFE: the backbone's stages -> the maps the RPN and the RoI heads read
-  dense_heads.py        RPNHead: the maps -> the proposals (simple_test_rpn, aug_test_rpn)
+  dense_heads.py        RPNHead: the maps -> the proposals (simple_test_rpn, aug_test_rpn); FCOSHead: the maps -> detections
   roi_extractors.py, mask_heads.py, losses.py, roi_head.py
                         host-side mirror of the reference's plugin classes
-  detectors.py          MaskRCNN and its siblings: decoded images -> results (above all of the modules before it);
+  detectors.py          MaskRCNN and its siblings, FCOS: decoded images -> results (above all of the modules before it);
                         the image pre-processing in front of the backbone, load_checkpoint
   synth.py              synthetic workload
   dist.py               RCCL gradient all-reduce of the mask-head parameters
@@ -37,6 +37,12 @@ def __getattr__(name):          # NECKS, build_neck, FPN, FPN_CARAFE, BACKBONES,
     if name in ('ResNet', 'ResNeXt', 'Res2Net'):
         from . import backbones
         return getattr(backbones, name)
+    if name in ('FCOS', 'SingleStageDetector'):
+        from . import detectors
+        return getattr(detectors, name)
+    if name == 'FCOSHead':
+        from . import dense_heads
+        return dense_heads.FCOSHead
     if name in ('DETECTORS', 'build_detector'):
         from . import detectors, registry  # noqa: F401  (detectors registers MaskRCNN and its siblings)
         return getattr(registry, name)

@@ -26,6 +26,9 @@ static inline int dm_check_launch() {
   return e == hipSuccess ? DM_OK : DM_ERR_LAUNCH;
 }
 
+// dm_reload_env_knobs (roi_align.hip) also re-reads DM_GN_WIDE, which lives with the GroupNorm launcher (grid_head.hip).
+void dm_gn_reload_knobs();
+
 // Per-device facts.  One process may drive several devices (a rehearsal of ranks on one box, a
 // single-process multi-GPU caller): compute-unit counts and "this kernel's LDS limit has been
 // raised" flags are properties of a device, not of the process, so they are kept per device.

@@ -61,6 +61,115 @@ __global__ __launch_bounds__(GH_NT) void group_norm_kernel(const float* x, int C
   }
 }
 
+// The wide build, for the groups of a dense head's towers (FCOSHead on a 1333 x 800 image: 8 x 100 x 168 floats = 525 KB at
+// stride 8): the same three passes and the same expressions, by 1024 threads instead of 256 and with 16-byte loads and
+// stores.  A group starts wherever (n G + g) L floats lead -- 4-byte aligned only when L is odd -- so it is walked as a
+// scalar head (up to the first 16-byte boundary of x), an aligned middle of float4s and a scalar tail; the stores are
+// float4s where y's group has x's offset from a 16-byte boundary (in place: always), four scalars each otherwise.
+// Thread t owns the middle's vectors t, t + 1024, ... and head / tail element t; it adds its vectors' components into four
+// accumulators in that order, then ((a0 + a1) + (a2 + a3)) + its head / tail element; the 64 lanes by shuffle, the 16 waves
+// in index order: one fixed order for a given L and offset of the group from a 16-byte boundary, both fixed by the shape and
+// the group's place in the tensor -- the same bits on every run, and a sample's bits do not depend on the samples beside
+// it.  The channel of an element is carried along (quotient and remainder by H W advance by constants): one division per
+// thread.  In place is safe for the same reason as above.
+constexpr int GW_NT = 1024;
+constexpr int GW_WAVES = GW_NT / 64;
+
+__device__ __forceinline__ float gw_block_sum(float v, float* red) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();                       // (the previous call's reads of red are over)
+  if (lane == 0) red[wave] = v;
+  __syncthreads();
+  float s = red[0];
+#pragma unroll
+  for (int w = 1; w < GW_WAVES; ++w) s += red[w];
+  return s;
+}
+
+__global__ __launch_bounds__(GW_NT) void group_norm_wide_kernel(const float* x, int C, int G, int HW, const float* __restrict__ gamma,
+                                                               const float* __restrict__ beta, float eps, int relu, float* y) {
+  __shared__ float red[GW_WAVES];
+  const int cpg = C / G;
+  const int L = cpg * HW;
+  const size_t base = (size_t)blockIdx.x * L;
+  const int g = (int)(blockIdx.x % (unsigned)G);
+  const float* xg = x + base;
+  float* yg = y + base;
+  const int tid = threadIdx.x;
+  // head: the elements in front of x's first 16-byte boundary (0 .. 3; L > 3 here), nv aligned vectors, then the tail
+  const int head = (int)(((16u - (unsigned)((uintptr_t)xg & 15u)) & 15u) >> 2);
+  const int nv = (L - head) >> 2;
+  const int tail0 = head + 4 * nv;                     // first tail element; L - tail0 in 0 .. 3
+  const dm_f32x4* xv = reinterpret_cast<const dm_f32x4*>(xg + head);
+  const int ei = tid < 4 ? tid : tail0 + (tid - 4);    // threads 0 .. 3: head elements; 4 .. 7: tail elements
+  const bool edge = tid < 4 ? tid < head : (tid < 8 && ei < L);
+  const float x0 = xg[0];
+
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+#pragma unroll 4
+  for (int v = tid; v < nv; v += GW_NT) {
+    const dm_f32x4 t = xv[v];
+    a0 += t.x - x0; a1 += t.y - x0; a2 += t.z - x0; a3 += t.w - x0;
+  }
+  float s = (a0 + a1) + (a2 + a3);
+  if (edge) s += xg[ei] - x0;
+  const float m = gw_block_sum(s, red) / (float)L;
+
+  a0 = a1 = a2 = a3 = 0.f;
+#pragma unroll 4
+  for (int v = tid; v < nv; v += GW_NT) {
+    const dm_f32x4 t = xv[v];
+    const float d0 = (t.x - x0) - m, d1 = (t.y - x0) - m, d2 = (t.z - x0) - m, d3 = (t.w - x0) - m;
+    a0 += d0 * d0; a1 += d1 * d1; a2 += d2 * d2; a3 += d3 * d3;
+  }
+  float q = (a0 + a1) + (a2 + a3);
+  if (edge) {
+    const float d = (xg[ei] - x0) - m;
+    q += d * d;
+  }
+  const float var = gw_block_sum(q, red) / (float)L;
+  const float rstd = 1.f / sqrtf(var + eps);
+
+  if (edge) {
+    const int c = g * cpg + ei / HW;
+    float v = ((xg[ei] - x0) - m) * rstd * gamma[c] + beta[c];
+    if (relu) v = dm_relu(v);
+    yg[ei] = v;
+  }
+  const bool vec_store = (((uintptr_t)yg ^ (uintptr_t)xg) & 15u) == 0;       // (uniform over the workgroup)
+  dm_f32x4* yv = reinterpret_cast<dm_f32x4*>(yg + head);
+  // element i = head + 4 v + j lies in channel g cpg + i / HW: (qc, rc) = divmod(i, HW) of the vector's first element
+  const int step = 4 * GW_NT, dq = step / HW, dr = step - dq * HW;
+  int i0 = head + 4 * tid;
+  int qc = i0 / HW, rc = i0 - qc * HW;
+  for (int v = tid; v < nv; v += GW_NT) {
+    const dm_f32x4 t = xv[v];
+    const float in[4] = {t.x, t.y, t.z, t.w};
+    float o[4];
+    int qj = qc, rj = rc;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int c = g * cpg + qj;
+      float r = ((in[j] - x0) - m) * rstd * gamma[c] + beta[c];
+      if (relu) r = dm_relu(r);
+      o[j] = r;
+      if (++rj == HW) { rj = 0; ++qj; }
+    }
+    if (vec_store) {
+      dm_f32x4 w;
+      w.x = o[0]; w.y = o[1]; w.z = o[2]; w.w = o[3];
+      yv[v] = w;
+    } else {
+      float* yo = yg + head + 4 * (size_t)v;
+      yo[0] = o[0]; yo[1] = o[1]; yo[2] = o[2]; yo[3] = o[3];
+    }
+    qc += dq; rc += dr;
+    if (rc >= HW) { rc -= HW; ++qc; }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ neighbour fusion
 // One workgroup per (RoI, point i).  Per neighbour slot j (the reference's order: left, up, down, right): the source
 // point's c x S x S slice goes to LDS, the depthwise 5x5 (+ its bias) of it to LDS, then the 1x1: lane = pixel
@@ -317,7 +426,24 @@ bool deconv_ok(int G, int ci, int co, int S) {
          ci <= DECONV_MAX_CI && S <= DECONV_MAX_S;
 }
 
+// The wide build takes the groups of at least GN_WIDE_MIN_L floats.  Above 16384 on purpose: every group the Grid head
+// launches (768 .. 12544 floats) keeps group_norm_kernel and its bits.  The value is the smallest measured length from which
+// the wide build is faster at one and at four samples (tools/fcos_infer_bench.py; the table is in DESIGN.md).
+// DM_GN_WIDE=0: group_norm_kernel for every L (the A/B baseline of that tool); read once, re-read by dm_reload_env_knobs.
+constexpr int GN_WIDE_MIN_L = 16385;
+int g_gn_wide = -1;
+
+int gn_wide() {
+  if (g_gn_wide < 0) dm_gn_reload_knobs();      // (a race between two host threads repeats an idempotent load)
+  return g_gn_wide;
+}
+
 }  // namespace
+
+void dm_gn_reload_knobs() {
+  const char* e = getenv("DM_GN_WIDE");
+  g_gn_wide = (e && *e && atoi(e) == 0) ? 0 : 1;
+}
 
 extern "C" int dm_group_norm_supported(long long N, int C, int G, int H, int W) {
   if (N < 0 || C < 1 || G < 1 || H < 1 || W < 1 || C % G != 0) return 0;
@@ -332,8 +458,12 @@ extern "C" int dm_group_norm_fwd(const float* x, long long N, int C, int G, int 
   if (relu & ~1) return DM_ERR_INVALID_ARG;
   if (N == 0) return DM_OK;
   if (!x || !y || !gamma || !beta || !(eps > 0.f)) return DM_ERR_INVALID_ARG;
-  DM_LAUNCH(group_norm_kernel, dim3((unsigned)(N * G)), dim3(GH_NT), 0, (hipStream_t)stream, x, C, G, H * W, gamma, beta, eps,
-            relu, y);
+  if ((long long)(C / G) * H * W >= GN_WIDE_MIN_L && gn_wide())
+    DM_LAUNCH(group_norm_wide_kernel, dim3((unsigned)(N * G)), dim3(GW_NT), 0, (hipStream_t)stream, x, C, G, H * W, gamma, beta,
+              eps, relu, y);
+  else
+    DM_LAUNCH(group_norm_kernel, dim3((unsigned)(N * G)), dim3(GH_NT), 0, (hipStream_t)stream, x, C, G, H * W, gamma, beta, eps,
+              relu, y);
   return dm_check_launch();
 }
 

@@ -1629,6 +1629,7 @@ int roi_align_fwd_impl(const float* const* feats, const int* H, const int* W, co
 
 extern "C" int dm_reload_env_knobs(void) {
   roi_load_knobs();
+  dm_gn_reload_knobs();
   return DM_OK;
 }
 

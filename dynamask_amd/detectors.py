@@ -1,7 +1,8 @@
 """The detectors behind the reference's DETECTORS registry, at inference: ``TwoStageDetector`` (mmdet/models/detectors/
 two_stage.py over base.py) and its thin registered subclasses -- ``MaskRCNN``, ``FasterRCNN``, ``CascadeRCNN``,
 ``HybridTaskCascade``, ``MaskScoringRCNN``, ``PointRend``, ``GridRCNN``, ``FastRCNN`` -- the object that runs
-``ResNet -> FPN -> RPNHead -> roi_head`` from the image to the results.
+``ResNet -> FPN -> RPNHead -> roi_head`` from the image to the results; and ``SingleStageDetector`` (single_stage.py) with
+``FCOS``: ``backbone -> neck -> bbox_head``, no RPN and no RoI head.
 
 This module sits above backbones, necks, dense_heads and roi_head; none of them imports it.  It adds no arithmetic to
 the model: ``simple_test`` / ``aug_test`` call the parts in the reference's order and add no host wait.  What it does add
@@ -16,6 +17,7 @@ import torch.nn as nn
 
 from . import backbones, dense_heads, necks, roi_head  # noqa: F401  (each registers its section's classes)
 from . import ops
+from .postprocess import _bbox2result_host, _to_host
 from .registry import DETECTORS, _to_cfgdict, build_backbone, build_head, build_neck
 
 
@@ -164,64 +166,13 @@ def _sub_cfg(cfg, key):
     return None if cfg is None else _to_cfgdict(cfg[key])
 
 
-@DETECTORS.register_module()
-class TwoStageDetector(nn.Module):
-    """``TwoStageDetector`` -- two_stage.py:9-211 on ``BaseDetector`` (base.py).  ``state_dict`` keys: ``backbone.*``,
-    ``neck.*``, ``rpn_head.*``, ``roi_head.*``, the reference's.  ``rpn_head`` gets ``test_cfg.rpn`` and ``roi_head``
-    ``test_cfg.rcnn`` (two_stage.py:26-46), in copies: the caller's config is not changed.  ``pretrained`` is stored and
-    otherwise ignored (no model zoo).  Inference only."""
+class _DetectorBase(nn.Module):
+    """What ``BaseDetector`` (base.py) gives every detector at inference: the features, ``forward_test`` / ``forward``'s
+    dispatch over the views, the path from decoded images, and the refusals."""
 
-    def __init__(self, backbone, neck=None, rpn_head=None, roi_head=None, train_cfg=None, test_cfg=None, pretrained=None):
-        super().__init__()
-        self.fp16_enabled = False
-        self.backbone = build_backbone(dict(backbone))
-        if neck is not None:
-            self.neck = build_neck(dict(neck))
-        if rpn_head is not None:
-            rpn_head_ = dict(rpn_head)
-            rpn_head_.update(train_cfg=_sub_cfg(train_cfg, 'rpn'), test_cfg=_sub_cfg(test_cfg, 'rpn'))
-            self.rpn_head = build_head(rpn_head_)
-        if roi_head is not None:
-            roi_head_ = dict(roi_head)
-            roi_head_.update(train_cfg=_sub_cfg(train_cfg, 'rcnn'), test_cfg=_sub_cfg(test_cfg, 'rcnn'))
-            self.roi_head = build_head(roi_head_)
-        self.train_cfg = train_cfg
-        self.test_cfg = test_cfg
-        self.pretrained = pretrained
-
-    # ------------------------------------------------------------------ what the detector has (base.py:22-47, two_stage.py:50-58)
     @property
     def with_neck(self):
         return hasattr(self, 'neck') and self.neck is not None
-
-    @property
-    def with_rpn(self):
-        return hasattr(self, 'rpn_head') and self.rpn_head is not None
-
-    @property
-    def with_roi_head(self):
-        return hasattr(self, 'roi_head') and self.roi_head is not None
-
-    @property
-    def with_shared_head(self):
-        return hasattr(self.roi_head, 'shared_head') and self.roi_head.shared_head is not None
-
-    @property
-    def with_bbox(self):
-        return hasattr(self.roi_head, 'bbox_head') and self.roi_head.bbox_head is not None
-
-    @property
-    def with_mask(self):
-        return hasattr(self.roi_head, 'mask_head') and self.roi_head.mask_head is not None
-
-    # ------------------------------------------------------------------ refusals
-    def forward_train(self, *args, **kwargs):
-        raise NotImplementedError(f'{type(self).__name__}.forward_train: backbone, neck and RPN training (their backward, the '
-                                  'anchor targets and the RPN losses) are not built; the detector runs at inference only')
-
-    def forward_dummy(self, *args, **kwargs):
-        raise NotImplementedError(f'{type(self).__name__}.forward_dummy: the RoI heads\' forward_dummy (the flops counter\'s '
-                                  'path) is not built')
 
     async def async_simple_test(self, *args, **kwargs):
         raise NotImplementedError(f'{type(self).__name__}.async_simple_test: the async test paths of the RPN and RoI heads '
@@ -234,7 +185,6 @@ class TwoStageDetector(nn.Module):
     def show_result(self, *args, **kwargs):
         raise NotImplementedError(f'{type(self).__name__}.show_result: drawing (mmcv.imshow_det_bboxes, cv2) is not built')
 
-    # ------------------------------------------------------------------ inference
     def extract_feat(self, img):
         """two_stage.py:80-85: backbone, then the neck when there is one."""
         x = self.backbone(img)
@@ -246,28 +196,6 @@ class TwoStageDetector(nn.Module):
         """base.py:54-65: one ``extract_feat`` per view."""
         assert isinstance(imgs, list)
         return [self.extract_feat(img) for img in imgs]
-
-    def simple_test(self, img, img_metas, proposals=None, rescale=False, encode=False):
-        """two_stage.py:187-199.  One image: what ``roi_head.simple_test`` returns.  B > 1 images (the reference asserts
-        one): ``roi_head.batch_simple_test``'s list of B such results.  ``proposals``: used instead of the RPN's."""
-        assert self.with_bbox, 'Bbox head must be implemented.'
-        if proposals is None and not self.with_rpn:
-            raise ValueError(f'{type(self).__name__}.simple_test: no rpn_head: pass proposals')
-        x = self.extract_feat(img)
-        if proposals is None:
-            proposal_list = self.rpn_head.simple_test_rpn(x, img_metas)
-        else:
-            proposal_list = proposals
-        if len(img_metas) == 1:
-            return self.roi_head.simple_test(x, proposal_list, img_metas, rescale=rescale, encode=encode)
-        return self.roi_head.batch_simple_test(x, proposal_list, img_metas, rescale=rescale, encode=encode)
-
-    def aug_test(self, imgs, img_metas, rescale=False, encode=False):
-        """two_stage.py:201-211: the views' features, the RPN's proposals merged over the views, the RoI head's
-        ``aug_test``."""
-        x = self.extract_feats(imgs)
-        proposal_list = self.rpn_head.aug_test_rpn(x, img_metas)
-        return self.roi_head.aug_test(x, proposal_list, img_metas, rescale=rescale, encode=encode)
 
     def forward_test(self, imgs, img_metas, **kwargs):
         """base.py:123-158: ``imgs`` / ``img_metas`` hold one entry per view; one view goes to ``simple_test``, several
@@ -305,12 +233,13 @@ class TwoStageDetector(nn.Module):
             out.append(im)
         return out
 
-    def detect(self, images, cfg_or_pipeline, rescale=True, encode=False):
+    def detect(self, images, cfg_or_pipeline, rescale=True, **kw_test):
         """From decoded uint8 HWC images (device tensors, or host numpy arrays, which are copied up) to results, the views
         read from the config's ``test_pipeline`` (``parse_test_pipeline``).  One scale and no flip: one ``preprocess``
         launch and ``simple_test`` (one image: its result; several: the list).  Several scales or ``flip=True``:
         ``aug_test`` over the views in ``MultiScaleFlipAug``'s order, one ``preprocess`` launch per view; test-time
-        augmentation runs one image at a time, so several images give the list of their results."""
+        augmentation runs one image at a time, so several images give the list of their results.  Further keywords
+        (``encode=`` of the two-stage detectors) go to ``simple_test`` / ``aug_test``."""
         p = parse_test_pipeline(cfg_or_pipeline)
         images = self._on_device(images)
         views = [(s, f, d) for s in p['img_scales']
@@ -318,7 +247,7 @@ class TwoStageDetector(nn.Module):
         kw = dict(keep_ratio=p['keep_ratio'], size_divisor=p['size_divisor'])
         if len(views) == 1:
             img, metas = preprocess(images, p['img_norm_cfg'], img_scale=views[0][0], **kw)
-            return self.simple_test(img, metas, rescale=rescale, encode=encode)
+            return self.simple_test(img, metas, rescale=rescale, **kw_test)
         results = []
         for im in images:
             imgs, metas = [], []
@@ -326,8 +255,87 @@ class TwoStageDetector(nn.Module):
                 img, m = preprocess([im], p['img_norm_cfg'], img_scale=s, flip=f, flip_direction=d or 'horizontal', **kw)
                 imgs.append(img)
                 metas.append(m)
-            results.append(self.aug_test(imgs, metas, rescale=rescale, encode=encode))
+            results.append(self.aug_test(imgs, metas, rescale=rescale, **kw_test))
         return results[0] if len(images) == 1 else results
+
+
+@DETECTORS.register_module()
+class TwoStageDetector(_DetectorBase):
+    """``TwoStageDetector`` -- two_stage.py:9-211 on ``BaseDetector`` (base.py).  ``state_dict`` keys: ``backbone.*``,
+    ``neck.*``, ``rpn_head.*``, ``roi_head.*``, the reference's.  ``rpn_head`` gets ``test_cfg.rpn`` and ``roi_head``
+    ``test_cfg.rcnn`` (two_stage.py:26-46), in copies: the caller's config is not changed.  ``pretrained`` is stored and
+    otherwise ignored (no model zoo).  Inference only."""
+
+    def __init__(self, backbone, neck=None, rpn_head=None, roi_head=None, train_cfg=None, test_cfg=None, pretrained=None):
+        super().__init__()
+        self.fp16_enabled = False
+        self.backbone = build_backbone(dict(backbone))
+        if neck is not None:
+            self.neck = build_neck(dict(neck))
+        if rpn_head is not None:
+            rpn_head_ = dict(rpn_head)
+            rpn_head_.update(train_cfg=_sub_cfg(train_cfg, 'rpn'), test_cfg=_sub_cfg(test_cfg, 'rpn'))
+            self.rpn_head = build_head(rpn_head_)
+        if roi_head is not None:
+            roi_head_ = dict(roi_head)
+            roi_head_.update(train_cfg=_sub_cfg(train_cfg, 'rcnn'), test_cfg=_sub_cfg(test_cfg, 'rcnn'))
+            self.roi_head = build_head(roi_head_)
+        self.train_cfg = train_cfg
+        self.test_cfg = test_cfg
+        self.pretrained = pretrained
+
+    # ------------------------------------------------------------------ what the detector has (base.py:22-47, two_stage.py:50-58)
+    @property
+    def with_rpn(self):
+        return hasattr(self, 'rpn_head') and self.rpn_head is not None
+
+    @property
+    def with_roi_head(self):
+        return hasattr(self, 'roi_head') and self.roi_head is not None
+
+    @property
+    def with_shared_head(self):
+        return hasattr(self.roi_head, 'shared_head') and self.roi_head.shared_head is not None
+
+    @property
+    def with_bbox(self):
+        return hasattr(self.roi_head, 'bbox_head') and self.roi_head.bbox_head is not None
+
+    @property
+    def with_mask(self):
+        return hasattr(self.roi_head, 'mask_head') and self.roi_head.mask_head is not None
+
+    # ------------------------------------------------------------------ refusals
+    def forward_train(self, *args, **kwargs):
+        raise NotImplementedError(f'{type(self).__name__}.forward_train: backbone, neck and RPN training (their backward, the '
+                                  'anchor targets and the RPN losses) are not built; the detector runs at inference only')
+
+    def forward_dummy(self, *args, **kwargs):
+        raise NotImplementedError(f'{type(self).__name__}.forward_dummy: the RoI heads\' forward_dummy (the flops counter\'s '
+                                  'path) is not built')
+
+    # ------------------------------------------------------------------ inference
+    def simple_test(self, img, img_metas, proposals=None, rescale=False, encode=False):
+        """two_stage.py:187-199.  One image: what ``roi_head.simple_test`` returns.  B > 1 images (the reference asserts
+        one): ``roi_head.batch_simple_test``'s list of B such results.  ``proposals``: used instead of the RPN's."""
+        assert self.with_bbox, 'Bbox head must be implemented.'
+        if proposals is None and not self.with_rpn:
+            raise ValueError(f'{type(self).__name__}.simple_test: no rpn_head: pass proposals')
+        x = self.extract_feat(img)
+        if proposals is None:
+            proposal_list = self.rpn_head.simple_test_rpn(x, img_metas)
+        else:
+            proposal_list = proposals
+        if len(img_metas) == 1:
+            return self.roi_head.simple_test(x, proposal_list, img_metas, rescale=rescale, encode=encode)
+        return self.roi_head.batch_simple_test(x, proposal_list, img_metas, rescale=rescale, encode=encode)
+
+    def aug_test(self, imgs, img_metas, rescale=False, encode=False):
+        """two_stage.py:201-211: the views' features, the RPN's proposals merged over the views, the RoI head's
+        ``aug_test``."""
+        x = self.extract_feats(imgs)
+        proposal_list = self.rpn_head.aug_test_rpn(x, img_metas)
+        return self.roi_head.aug_test(x, proposal_list, img_metas, rescale=rescale, encode=encode)
 
 
 @DETECTORS.register_module()
@@ -389,3 +397,60 @@ class FastRCNN(TwoStageDetector):
             raise NotImplementedError('FastRCNN.forward_test: test-time augmentation with given proposals is not built '
                                       '(nor is it in the reference)')
         return self.simple_test(imgs[0], img_metas[0], proposals[0], **kwargs)
+
+
+# ---------------------------------------------------------------------------------------------- single-stage detectors
+@DETECTORS.register_module()
+class SingleStageDetector(_DetectorBase):
+    """``SingleStageDetector`` -- single_stage.py:9-154 on ``BaseDetector``: ``backbone -> neck -> bbox_head``, no RPN and
+    no RoI head.  ``state_dict`` keys: ``backbone.*``, ``neck.*``, ``bbox_head.*``, the reference's.  ``test_cfg`` goes
+    whole to the head (single_stage.py:28-30), in a copy: the caller's config is not changed.  ``pretrained`` is stored
+    and otherwise ignored.  Inference only; the detector adds no arithmetic of its own."""
+
+    def __init__(self, backbone, neck=None, bbox_head=None, train_cfg=None, test_cfg=None, pretrained=None):
+        super().__init__()
+        self.fp16_enabled = False
+        self.backbone = build_backbone(dict(backbone))
+        if neck is not None:
+            self.neck = build_neck(dict(neck))
+        bbox_head_ = dict(bbox_head)
+        bbox_head_.update(train_cfg=None if train_cfg is None else _to_cfgdict(train_cfg),
+                          test_cfg=None if test_cfg is None else _to_cfgdict(test_cfg))
+        self.bbox_head = build_head(bbox_head_)
+        self.train_cfg = train_cfg
+        self.test_cfg = test_cfg
+        self.pretrained = pretrained
+
+    @property
+    def with_bbox(self):
+        return hasattr(self, 'bbox_head') and self.bbox_head is not None
+
+    # ------------------------------------------------------------------ refusals
+    def forward_train(self, *args, **kwargs):
+        raise NotImplementedError(f'{type(self).__name__}.forward_train: backbone, neck and dense-head training (their '
+                                  'backward, the point targets and the losses) are not built; the detector runs at inference only')
+
+    def forward_dummy(self, *args, **kwargs):
+        raise NotImplementedError(f'{type(self).__name__}.forward_dummy: the flops counter\'s path is not built')
+
+    def aug_test(self, imgs, img_metas, rescale=False):
+        """single_stage.py:152-154: the reference raises too."""
+        raise NotImplementedError(f'{type(self).__name__}.aug_test: test-time augmentation of a single-stage detector is not '
+                                  'built (nor is it in the reference)')
+
+    # ------------------------------------------------------------------ inference
+    def simple_test(self, img, img_metas, rescale=False):
+        """single_stage.py:116-150.  One image: its ``bbox2result`` list (one [k, 5] array per class).  B > 1 images (the
+        reference returns the first only): the list of B such results.  The detections of all images reach the host in
+        one copy."""
+        x = self.extract_feat(img)
+        outs = self.bbox_head(x)
+        bbox_list = self.bbox_head.get_bboxes(*outs, img_metas, rescale=rescale)
+        host = _to_host(*[t for pair in bbox_list for t in pair])
+        results = [_bbox2result_host(host[2 * b], host[2 * b + 1], self.bbox_head.num_classes) for b in range(len(bbox_list))]
+        return results[0] if len(img_metas) == 1 else results
+
+
+@DETECTORS.register_module()
+class FCOS(SingleStageDetector):
+    """fcos.py: the constructor only."""

@@ -2875,6 +2875,12 @@ def roi_align_add_(feats, fmap, rois, size, spatial_scale, sampling_ratio=0):
 
 # ------------------------------------------------ Grid R-CNN: the GridHead launches (csrc/grid_head.hip)
 # Exact fp32 in every precision mode: the bf16x3 mode does not reach these launches.
+# Groups of at least this many floats run the wide build of dm_group_norm_fwd (1024 threads, 16-byte loads) unless
+# DM_GN_WIDE=0; the library's constant of the same name (csrc/grid_head.hip) decides, this copy is for tools and tests
+# (tests/test_fcos_cpu.py holds the two equal).
+GN_WIDE_MIN_L = 16385
+
+
 def group_norm_supported(x, num_groups):
     N, C, H, W = x.shape
     return bool(lib().dm_group_norm_supported(N, C, int(num_groups), H, W))

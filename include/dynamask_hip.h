@@ -11,13 +11,15 @@
  *     What the library does keep, per device and only as a cache: the device's
  *     compute-unit count and "this kernel's dynamic-LDS limit has been raised"
  *     flags (hipFuncSetAttribute once per device).  A few knobs are read from
- *     the environment on first use, seven in all, none of which changes what is
- *     computed: DM_CONV_TAIL / DM_DCN_TAIL (0: no separate launch for the last,
+ *     the environment on first use, eight in all, none of which changes what is
+ *     computed but DM_GN_WIDE, which changes a rounding: DM_CONV_TAIL / DM_DCN_TAIL (0: no separate launch for the last,
  *     underfull round of workgroups), DM_CONV1_SMALL_WGS (up to how many 128 x 128
  *     tiles a 1x1 launch takes 128 x 32 tiles instead; default 1.25 per CU, 0: never),
  *     DM_WGRAD_WGS (split-K workgroups of the
  *     weight gradients), DM_ROI_SORT / DM_ROI_SORT_MIN (the RoI ordering launch of
- *     dm_roi_align_fwd_ws; re-read by dm_reload_env_knobs()), DM_CONV_SPLITK is the
+ *     dm_roi_align_fwd_ws; re-read by dm_reload_env_knobs()), DM_GN_WIDE (0: the
+ *     narrow build of dm_group_norm_fwd for every group length; re-read by
+ *     dm_reload_env_knobs() too), DM_CONV_SPLITK is the
  *     host binding's.  (Rounds 2-4 had twenty more -- first-generation kernels and
  *     rejected variants kept for A/B timing; their measurements are in
  *     docs/HISTORY.md and profiles/, the kernels are gone.)
@@ -74,8 +76,9 @@ int dm_abi_version(void);
  * build.py); the host binding checks this string at load time and refuses a library that does not say so.  A build
  * recipe other than build.py passes its flag set as -DDM_BUILD_FLAGS="..."; without it the string says flags=unknown. */
 const char* dm_build_info(void);
-/* Re-read the DM_ROI_* experiment knobs from the environment (they are otherwise read once, at the first launch, and
- * clamped to validated ranges).  For measurement tools that sweep settings inside one process; no knob changes a result. */
+/* Re-read the DM_ROI_* experiment knobs and DM_GN_WIDE from the environment (they are otherwise read once, at the first
+ * launch, and clamped to validated ranges).  For measurement tools that sweep settings inside one process; no DM_ROI_* knob
+ * changes a result, DM_GN_WIDE chooses between two builds that differ in rounding (section K27). */
 int dm_reload_env_knobs(void);
 
 /* ---------------------------------------------------------------------------
@@ -1240,7 +1243,11 @@ int dm_roi_align_add_fwd(const float* feat, int B, int C, int H, int W, float sp
  * biased variance; y may be x (in place).  The statistics are two passes over the group on values shifted by its first
  * element (never E[x^2] - E[x]^2): a constant group gives exactly beta.  dm_group_norm_supported: 1 exactly when N >= 0,
  * C, G, H, W >= 1, C % G == 0, (C / G) * H * W <= 2^24 and N * G < 2^31.  N == 0 enqueues nothing; relu other than 0 / 1
- * or eps <= 0: DM_ERR_INVALID_ARG.
+ * or eps <= 0: DM_ERR_INVALID_ARG.  Two builds, one contract: groups of up to 16384 floats (every group of the Grid head)
+ * run 256 threads a group with scalar loads; from a host constant above that (csrc/grid_head.hip GN_WIDE_MIN_L, chosen by
+ * measurement) a group runs 1024 threads with 16-byte loads on its aligned middle -- the groups of a dense head's towers
+ * (FCOSHead: 8 x 100 x 168 floats).  They associate the same sums differently (a rounding apart); each gives the same bits
+ * on every run, and a sample's bits do not depend on the batch.  DM_GN_WIDE=0 runs the first for every length.
  *
  * dm_grid_fusion_fwd: one order of the neighbour fusion (grid_head.py:157-170) in one launch.  x, src, out
  * [N, P * c, S, S] (point i = channels [i c, (i + 1) c)); for every sample and point i
