@@ -41,7 +41,8 @@ __device__ __forceinline__ unsigned sel_key(const float* __restrict__ row, int i
     return reinterpret_cast<const unsigned*>(row)[i] & MAG;
   } else {
     const float v = MODE == SEL_DESC_SIGMOID ? dm_sigmoid(row[i]) : row[i];
-    const unsigned b = __float_as_uint(v);
+    unsigned b = __float_as_uint(v);
+    if (b == 0x80000000u) b = 0u;                  // -0 and +0 are one key, as they compare: the lower index wins the tie
     const unsigned up = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
     return ~up;
   }

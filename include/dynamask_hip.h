@@ -1119,7 +1119,8 @@ int dm_mask_iou_scores(const float* mask_iou_pred, int n, int NC, const long lon
  * dm_point_topk_select: map [n, HW] (the label row of the detail logits) -> idx [n, P] int32: per row the P cells of
  * LARGEST key (get_roi_rel_points_train's topk), key = 1 / (1 + expf(-v)) (mode 1, mask_use_sigmoid; the paste kernels'
  * sigmoid, so saturated cells tie at 1.0f) or v (mode 0); indices in ascending order; among cells of equal key at the
- * cut, the lower flat index is taken.  dm_point_topk_select_supported: 1 exactly when mode is 0 or 1 and
+ * cut, the lower flat index is taken (keys are equal when they compare equal as floats: +0 and -0 are one key).
+ * dm_point_topk_select_supported: 1 exactly when mode is 0 or 1 and
  * dm_point_select_supported(n, HW, P).  n == 0 enqueues nothing.
  * ------------------------------------------------------------------------------------------------------------------ */
 int dm_point_topk_select_supported(int n, int HW, int P, int mode);
